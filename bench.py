@@ -12,7 +12,10 @@ loop of fused forward/loss/backward + Adam).  Workload at N=1: BASELINE configs[
 shared PPO, num_envs=1024, obs 18, A=5, T=25, MLP 64-64).  N>1: env shards per rank (weak scaling:
 1024 envs per GPU, BASELINE configs[3]) with one RCCL all-reduce of the flat gradient per gradient step.
 value = env-steps/s = (n_env * n_agent * T * n_gpus) / max-over-ranks step time.
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the headline figure
+(`value`, `ms_per_step`); `--full` adds, after the timed steps, the collect / update split, the replica check, the
+rooflines and `cpu_baseline`.  `--dump-outputs DIR` writes what the last timed step computed (buffer rows, parameters,
+episode returns, losses) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -153,6 +156,12 @@ def parse():
     ap.add_argument("--workload", default="c2", choices=["c2", "c3", "c3ppo", "tag"],
                     help="c2 (default, the headline line): simple_spread N=3 shared PPO; c3: N=8 CTDEPolicy, 4096 envs; "
                          "c3ppo: N=8 PPO with a centralized critic, 4096 envs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline figure does not need: the collect / "
+                         "update split, the replica check of N > 1, the batch-64 update, the kernel rooflines and their 4096 x 8 "
+                         "grid, the CPU baseline (each --no-* switch above still drops its part)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     return ap.parse_args()
 
 
@@ -193,6 +202,56 @@ def _resolve(stats):
     r = getattr(stats, "resolve", None)
     if callable(r):
         r()
+
+
+DUMP_LIMIT = 64 << 20        # --dump-outputs: bytes in all
+DUMP_BUFFER_BYTES = 32 << 20  # of them for the buffer rows: a larger buffer is cut to a fixed, seeded sample of its rows
+
+
+def buffer_outputs(buf) -> dict:
+    """The rows the last collect wrote: every store of the buffer, [slot, env, agent] rows flattened.  All of them while they
+    fit DUMP_BUFFER_BYTES, else the same fixed, seeded sample of rows from every store (the same rows from run to run)."""
+    stores = {"obs": buf.obs_store, "obs_next": buf.obs_next_store, "act": buf.act_store, "rew": buf.rew_store,
+              "terminated": buf.term_store, "truncated": buf.trunc_store, "logp": buf.logp_store, "v_s": buf.vs_store,
+              "v_next": buf.vnext_store}
+    rows = buf.act_store.numel()
+    stores = {k: v.reshape(rows, -1) for k, v in stores.items() if v is not None}
+    keep = min(rows, DUMP_BUFFER_BYTES // (4 * sum(v.shape[1] for v in stores.values())))
+    if keep < rows:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(1626).choice(rows, keep, replace=False))).to(buf.act_store.device)
+        stores = {k: v[idx] for k, v in stores.items()}
+    return stores
+
+
+def episode_outputs(cs) -> dict:
+    """Returns and lengths of the episodes a collect finished (CollectStats)."""
+    return {"episode_returns": np.asarray(cs.returns, np.float64), "episode_lens": np.asarray(cs.lens, np.float64)}
+
+
+def scalar_outputs(prefix: str, stats) -> dict:
+    """Every scalar of a statistics object (TrainingStats: its loss statistics) or of a (nested) dict of them, one array each."""
+    if hasattr(stats, "get_loss_stats_dict"):
+        stats = stats.get_loss_stats_dict()
+    if hasattr(stats, "items"):
+        out = {}
+        for k, v in sorted(stats.items()):
+            out.update(scalar_outputs("%s_%s" % (prefix, str(k).replace("/", "_")), v))
+        return out
+    return {prefix: np.array([float(stats)], np.float64)}
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every array as path/<name>.npy, float64 kept as it is and everything else as float32."""
+    out = {}
+    for name, x in arrays.items():
+        x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        out[name] = x.astype(np.float64 if x.dtype == np.float64 else np.float32)
+    total = sum(x.nbytes for x in out.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("bench.py --dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    for name, x in out.items():
+        np.save(os.path.join(path, name + ".npy"), x)
 
 
 def one_step(a, algo, buf, col):
@@ -703,7 +762,7 @@ def run_c3(a, device):
             losses = trainer.train_step(agent_batches_from_buffer(buf, env.agents, copies=False))
         _resolve(cs)  # read every step's statistics (see one_step)
         col.reset_buffer(keep_statistics=True)
-        return losses
+        return cs, losses
 
     prev = None
     for _ in range(a.warmup):
@@ -711,32 +770,17 @@ def run_c3(a, device):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        losses = step()
+        cs, losses = step()
         if prev is not None:  # every learner's losses are read, one step late (as a logger would)
             for v in prev.values():
                 float(v["critic_loss"])
         prev = losses
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
-    ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
-    e0, e1, e2 = ev(), ev(), ev()
-    with policy_within_training_step(mgr):
-        e0.record()
-        col.collect(n_step=n_env * T)
-        e1.record()
-        trainer.train_step(agent_batches_from_buffer(buf, env.agents, copies=False))
-        e2.record()
-    torch.cuda.synchronize()
-    col.reset_buffer(keep_statistics=True)
-    # roofline of one learn() call AS EXECUTED (one hipGraph replay: V(last slot), TD step of the critic with its split-K dW1
-    # pass, actor step, finalize, two Adam launches), priced against the f32-MFMA peak: flops per row of the agent batch =
-    # critic forward + backward down to dH1 (2 (K1 H + H H + H n) + 4 H H + 4 n H) + dW1 (2 K1 H) + the actor's gradient step
-    # (useful flops, mlp_flops: no layer-1 dX)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {**buffer_outputs(buf), "actor_params": pol.actor.flat.data,
+                                      "critic_params": pol.critic.flat.data, **episode_outputs(cs), **scalar_outputs("train", losses)})
     R = n_env * T
-    K1, A_ = N * D, 5
-    flop_row = sum(mlp_flops((K1, H, H, N))) + sum(mlp_flops((D, H, H, A_)))
-    learn_flop = R * flop_row + n_env * 2 * (K1 * H + H * H + H * N)
-    learn_s = e1.elapsed_time(e2) * 1e-3 / N
     out = {
         "metric": "env-steps/sec (n_env x n_agent) incl. CTDE update, simple_spread N=8", "value": n_env * N * T / dt,
         "unit": "env-steps/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt * 1e3,
@@ -744,14 +788,34 @@ def run_c3(a, device):
         "config": {"workload": "simple_spread_v3 N=8 CTDEPolicy (shared actor 48-128-128-5, centralized critic 384-128-128-8), "
                                "num_envs=4096, T=25", "learn_calls_per_step": N, "rows_per_learn": R,
                                "learn": "fused: rows read in place, critic forward / TD step / dW1 / actor step / two Adam steps"},
-        "collect_ms": e0.elapsed_time(e1), "ctde_update_ms": e1.elapsed_time(e2),
         "losses_agent_0": {k: float(v) for k, v in losses["agent_0"].items()},
-        "roofline": {"bound": "mfma", "kernel": "CTDEPolicy.learn as executed (critic_rows_forward + critic_rows_train_kernel<24, true, 1> + "
-                               "critic_dw1_kernel + actor_rows64_kernel<3> + ctde_finalize + 2 x adam_segs; one hipGraph replay)",
-                     "achieved": learn_flop / learn_s / 1e12, "peak": MFMA_F32_PEAK / 1e12, "unit": "TFLOP/s",
-                     "frac": learn_flop / learn_s / MFMA_F32_PEAK, "traffic": None, "us_per_learn": learn_s * 1e6,
-                     "flop_per_learn": learn_flop, "rows_per_learn": R},
     }
+    if a.full:
+        ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
+        e0, e1, e2 = ev(), ev(), ev()
+        with policy_within_training_step(mgr):
+            e0.record()
+            col.collect(n_step=n_env * T)
+            e1.record()
+            trainer.train_step(agent_batches_from_buffer(buf, env.agents, copies=False))
+            e2.record()
+        torch.cuda.synchronize()
+        col.reset_buffer(keep_statistics=True)
+        # roofline of one learn() call AS EXECUTED (one hipGraph replay: V(last slot), TD step of the critic with its split-K dW1
+        # pass, actor step, finalize, two Adam launches), priced against the f32-MFMA peak: flops per row of the agent batch =
+        # critic forward + backward down to dH1 (2 (K1 H + H H + H n) + 4 H H + 4 n H) + dW1 (2 K1 H) + the actor's gradient step
+        # (useful flops, mlp_flops: no layer-1 dX)
+        K1, A_ = N * D, 5
+        flop_row = sum(mlp_flops((K1, H, H, N))) + sum(mlp_flops((D, H, H, A_)))
+        learn_flop = R * flop_row + n_env * 2 * (K1 * H + H * H + H * N)
+        learn_s = e1.elapsed_time(e2) * 1e-3 / N
+        out.update({
+            "collect_ms": e0.elapsed_time(e1), "ctde_update_ms": e1.elapsed_time(e2),
+            "roofline": {"bound": "mfma", "kernel": "CTDEPolicy.learn as executed (critic_rows_forward + critic_rows_train_kernel<24, true, 1> + "
+                                   "critic_dw1_kernel + actor_rows64_kernel<3> + ctde_finalize + 2 x adam_segs; one hipGraph replay)",
+                         "achieved": learn_flop / learn_s / 1e12, "peak": MFMA_F32_PEAK / 1e12, "unit": "TFLOP/s",
+                         "frac": learn_flop / learn_s / MFMA_F32_PEAK, "traffic": None, "us_per_learn": learn_s * 1e6,
+                         "flop_per_learn": learn_flop, "rows_per_learn": R}})
     _ = ops
     _emit(out)
 
@@ -788,28 +852,21 @@ def run_c3ppo(a, device):
         _resolve(prev[0])
         prev[0] = ts
         col.reset_buffer(keep_statistics=True)
-        return ts
+        return cs, ts
 
     for _ in range(max(a.warmup, 2)):  # the 2nd update captures the graph
         step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        ts = step()
+        cs, ts = step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
-    ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
-    e0, e1, e2 = ev(), ev(), ev()
-    with policy_within_training_step(algo):
-        e0.record()
-        col.collect(n_step=n_env * T)
-        e1.record()
-        algo.update(buf, mb, 1)
-        e2.record()
-    torch.cuda.synchronize()
-    col.reset_buffer(keep_statistics=True)
     d = ts.get_loss_stats_dict()
-    _emit({
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {**buffer_outputs(buf), "params": net.flat.data, **episode_outputs(cs),
+                                      **scalar_outputs("train", d)})
+    out = {
         "metric": "env-steps/sec (n_env x n_agent) incl. PPO update, simple_spread N=8, centralized critic",
         "value": n_env * N * T / dt, "unit": "env-steps/s", "n_gpus": 1, "steps": a.steps, "warmup": max(a.warmup, 2),
         "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
@@ -817,20 +874,33 @@ def run_c3ppo(a, device):
         "config": {"workload": "simple_spread_v3 N=8 PPO, shared actor 48-128-128-5 + centralized critic 384-128-128-1, "
                                "num_envs=4096, T=25", "minibatch": mb, "repeat": 1, "dispatch": a.c3_dispatch,
                    **({"buffer": "ignore_obs_next=True"} if a.ignore_obs_next else {})},
-        "collect_ms": e0.elapsed_time(e1), "gae_ppo_update_ms": e1.elapsed_time(e2),
-        # the whole GAE + PPO update as executed (one hipGraph replay), priced against the f32-MFMA peak: V(obs) of every joint
-        # row + V(obs_next) of the last slot, then one gradient step (useful flops: mlp_flops) of every sample through the actor
-        # and of every joint row through the critic (the default bench line's roofline_grid has the same count, medians and
-        # the kernels' own entries)
-        "roofline": (lambda fl, s_: {"bound": "mfma", "kernel": "C3 whole GAE + PPO update (GenericPPO.update, one hipGraph replay)",
-                                     "achieved": fl / s_ / 1e12, "peak": MFMA_F32_PEAK / 1e12, "unit": "TFLOP/s",
-                                     "frac": fl / s_ / MFMA_F32_PEAK, "traffic": None, "flop_per_update": fl,
-                                     "peak_note": PEAK_NOTE})(
-            (n_env * T + n_env) * mlp_flops((N * D, 128, 128, 1))[0]
-            + n_env * T * N * sum(mlp_flops((D, 128, 128, 5))) + n_env * T * sum(mlp_flops((N * D, 128, 128, 1))),
-            e1.elapsed_time(e2) * 1e-3),
         "gradient_steps_per_update": sum(int(v) for k, v in d.items() if k.endswith("gradient_steps")),
-        "loss": d.get("agent_0/loss", d.get("loss"))})
+        "loss": d.get("agent_0/loss", d.get("loss"))}
+    if a.full:
+        ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
+        e0, e1, e2 = ev(), ev(), ev()
+        with policy_within_training_step(algo):
+            e0.record()
+            col.collect(n_step=n_env * T)
+            e1.record()
+            algo.update(buf, mb, 1)
+            e2.record()
+        torch.cuda.synchronize()
+        col.reset_buffer(keep_statistics=True)
+        out.update({
+            "collect_ms": e0.elapsed_time(e1), "gae_ppo_update_ms": e1.elapsed_time(e2),
+            # the whole GAE + PPO update as executed (one hipGraph replay), priced against the f32-MFMA peak: V(obs) of every joint
+            # row + V(obs_next) of the last slot, then one gradient step (useful flops: mlp_flops) of every sample through the actor
+            # and of every joint row through the critic (the default bench line's roofline_grid has the same count, medians and
+            # the kernels' own entries)
+            "roofline": (lambda fl, s_: {"bound": "mfma", "kernel": "C3 whole GAE + PPO update (GenericPPO.update, one hipGraph replay)",
+                                         "achieved": fl / s_ / 1e12, "peak": MFMA_F32_PEAK / 1e12, "unit": "TFLOP/s",
+                                         "frac": fl / s_ / MFMA_F32_PEAK, "traffic": None, "flop_per_update": fl,
+                                         "peak_note": PEAK_NOTE})(
+                (n_env * T + n_env) * mlp_flops((N * D, 128, 128, 1))[0]
+                + n_env * T * N * sum(mlp_flops((D, 128, 128, 5))) + n_env * T * sum(mlp_flops((N * D, 128, 128, 1))),
+                e1.elapsed_time(e2) * 1e-3)})
+    _emit(out)
 
 
 def run_tag(a, device, rank, world, dist, census=None):
@@ -909,8 +979,11 @@ def run_tag(a, device, rank, world, dist, census=None):
         tt = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {**buffer_outputs(buf), **{"params_" + k: p.net.flat.data for k, p in sorted(teams.items())},
+                                      **episode_outputs(prev[0]), **scalar_outputs("train", losses)})
     replicas_identical = None
-    if dist is not None:
+    if dist is not None and a.full:
         diff = torch.zeros(1, device=device)
         for p in teams.values():
             ref = p.net.flat.data.clone()
@@ -1141,10 +1214,13 @@ def _main():
     value = agent_steps / (dt / a.steps)
     grad_steps = getattr(ts, "gradient_steps", None) or sum(
         s.gradient_steps for s in getattr(ts, "_agent_id_to_stats", {}).values())
-    # every rank runs the phase split: update() contains the gradient all-reduce when N > 1
-    t_col_ms, t_upd_ms = phase_times(a, algo, buf, col)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {**buffer_outputs(buf), "params": net.flat.data, **episode_outputs(cs),
+                                      **scalar_outputs("train", ts)})
+    if a.full:  # every rank runs the phase split: update() contains the gradient all-reduce when N > 1
+        t_col_ms, t_upd_ms = phase_times(a, algo, buf, col)
     replicas_identical = None
-    if dist is not None:  # data-parallel invariant: after any number of synced steps every rank holds the same bits
+    if dist is not None and a.full:  # data-parallel invariant: after any number of synced steps every rank holds the same bits
         mine = net.flat.data.clone()
         ref = mine.clone()
         dist.broadcast(ref, src=0)
@@ -1163,20 +1239,21 @@ def _main():
                        **({} if dist is None else {"collectives": "captured in the update hipGraph" if getattr(algo, "graph_collectives", False)
                                                    else "eager, between segmented hipGraphs"}),
                        **_allreduce_path(getattr(algo, "_grad_sync", None))},
-            "collect_ms": t_col_ms, "ppo_update_ms": t_upd_ms,
-            "collect_env_steps_per_s": a.n_env * a.n_agent * a.horizon / (t_col_ms * 1e-3),
             "gradient_steps_per_update": grad_steps,
         }
-        if replicas_identical is not None:
-            out["replicas_identical"] = replicas_identical
-        if world == 1 and not a.no_batch64:
-            out["update_reference_default_batch64"] = batch64_update(a, algo, buf, col)
-        out.update(kernel_rooflines(a, algo, buf))
-        if world == 1 and not a.no_c3_grid:
-            del algo, buf, col, env  # (free the headline job's graphs before the 4096-env job is built)
-            out["roofline_grid"] += c3_rooflines(device)
-        if not a.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(a)
+        if a.full:
+            out.update({"collect_ms": t_col_ms, "ppo_update_ms": t_upd_ms,
+                        "collect_env_steps_per_s": a.n_env * a.n_agent * a.horizon / (t_col_ms * 1e-3)})
+            if replicas_identical is not None:
+                out["replicas_identical"] = replicas_identical
+            if world == 1 and not a.no_batch64:
+                out["update_reference_default_batch64"] = batch64_update(a, algo, buf, col)
+            out.update(kernel_rooflines(a, algo, buf))
+            if world == 1 and not a.no_c3_grid:
+                del algo, buf, col, env  # (free the headline job's graphs before the 4096-env job is built)
+                out["roofline_grid"] += c3_rooflines(device)
+            if not a.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(a)
         _emit(out)
     if dist is not None:
         dist.barrier()

@@ -10,6 +10,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -98,9 +99,9 @@ def test_bench_reads_its_kernel_configuration_from_the_library():
 def test_bench_gpus_2_runs_two_ranks_and_counts_them(workload, p2p):
     """The driver's command shape with N = 2 and nothing around it: two ranks on cuda:0 over gloo; p2p = 1: the gradient
     sums on the one-shot peer-memory all-reduce (csrc/p2p.hip) instead of the process group's; auto (the default, variable
-    unset): the first-use handshake decides -- it passes here."""
+    unset): the first-use handshake decides -- it passes here.  (The replica check is part of a --full run.)"""
     extra = ["--no-cpu-baseline", "--no-c3-grid"] if workload == "c2" else ["--workload", "tag", "--tag-envs", "64"]
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "2", *extra],
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "2", "--full", *extra],
              {"TSM_SHARE_GPU": "1", "TSM_DIST_BACKEND": "gloo", **({} if p2p == "auto" else {"TSM_P2P_ALLREDUCE": p2p})})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -110,3 +111,29 @@ def test_bench_gpus_2_runs_two_ranks_and_counts_them(workload, p2p):
     assert out["replicas_identical"] is True
     assert out["steps"] == 3 and out["value"] > 0
     assert out["config"]["gradient_all_reduce"].startswith("process group (gloo)" if p2p == "0" else "peer memory (one-shot")
+
+
+def test_bench_has_full_and_dump_outputs_options():
+    r = _run(["--help"])  # (bench.py sends fd 1 to stderr while it runs: stdout carries the JSON line only)
+    assert r.returncode == 0 and "--full" in r.stderr and "--dump-outputs" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_what_the_last_one_computed(tmp_path):
+    """A plain run prints the headline figure only (nothing that --full adds) over exactly `--steps` timed steps; --dump-outputs
+    writes the last timed step's buffer rows, parameters, episodes and losses as float32 / float64 arrays, 64 MB at most."""
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert {"metric", "unit", "higher_is_better", "dtype"} <= set(out)
+    assert not {"roofline", "roofline_grid", "cpu_baseline", "collect_ms", "update_reference_default_batch64"} & set(out)
+    files = {f.name: np.load(f) for f in tmp_path.glob("*.npy")}
+    assert {"params.npy", "obs.npy", "act.npy", "rew.npy", "logp.npy", "episode_returns.npy", "episode_lens.npy"} <= set(files)
+    assert any(n.startswith("train_") and n.endswith("loss.npy") for n in files)
+    assert all(x.dtype in (np.float32, np.float64) for x in files.values())
+    assert sum(x.nbytes for x in files.values()) <= 64 << 20
+    assert files["obs.npy"].shape == (25 * 1024 * 3, 18)
+    assert all(np.isfinite(x).all() for x in files.values())

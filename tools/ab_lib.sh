@@ -7,9 +7,9 @@ timeout -k 10 400 python -m pytest tests/test_gpu_rollout.py tests/test_gpu_marl
 tail -2 $O/tests.log
 for i in 1 2; do
   cp $L/new.so $L/libtsmarl_hip.so
-  timeout -k 10 200 python bench.py --no-cpu-baseline --no-batch64 > $O/new_$i.json 2> $O/new_$i.err
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-batch64 > $O/new_$i.json 2> $O/new_$i.err
   cp $L/base.so $L/libtsmarl_hip.so
-  timeout -k 10 200 python bench.py --no-cpu-baseline --no-batch64 > $O/base_$i.json 2> $O/base_$i.err
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-batch64 > $O/base_$i.json 2> $O/base_$i.err
 done
 cp $L/new.so $L/libtsmarl_hip.so
 python - <<'P'

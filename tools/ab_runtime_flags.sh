@@ -1,7 +1,7 @@
 # (GPU box, from the repo root) the default bench line under HIP runtime switches that change how kernels of a hipGraph are dispatched:
 # kernel arguments in device memory or not, AQL packet capture for graph launches or not.  Same box, alternating, two passes.
 O=gpurun_out/abflags; mkdir -p $O
-run() { name=$1; shift; env "$@" timeout -k 10 200 python bench.py --no-cpu-baseline --no-batch64 --no-c3-grid > $O/$name.json 2> $O/$name.err; }
+run() { name=$1; shift; env "$@" timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-batch64 --no-c3-grid > $O/$name.json 2> $O/$name.err; }
 for i in 1 2; do
   run default_$i TSM_NOOP=1
   run devkernarg1_$i HIP_FORCE_DEV_KERNARG=1

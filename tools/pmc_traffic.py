@@ -1,16 +1,16 @@
 #!/usr/bin/env python3
 """HBM traffic per launch from rocprofv3 PMC passes (FETCH_SIZE and WRITE_SIZE collected in SEPARATE runs).
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_fetch -o f -- python3 bench.py ...
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_write -o w -- python3 bench.py ...
-    python tools/pmc_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write profiles/r01_pmc_traffic
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d out/pmc_fetch -o f -- python3 bench.py --full ...
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d out/pmc_write -o w -- python3 bench.py --full ...
+    python tools/pmc_traffic.py out/pmc_fetch out/pmc_write profiles/r01_pmc_traffic
 
 Units and corrections (MI355X_MICROARCH.md, "HBM" / "rocprofv3 PMC slots"): both counters are in KiB of memory-side
 (fabric) requests of the L2s, Infinity-Cache hits included.  On gfx950 FETCH_SIZE tallies 128-B read requests at 64 B:
 a wide coalesced streaming read reports exactly half its bytes, so reads are doubled ("fetch_x2").  The guide calibrates
 that factor for 16-B-per-lane loads only; the kernels here load 4 B per lane, so the factor is re-calibrated on kernels
 of this very access pattern whose byte count is known and which have no reuse (the GAE scan and the stand-alone loss
-kernel at 819 200 samples, both run by bench.py's roofline grid): see "calibration" in the output.
+kernel at 819 200 samples, both run by the roofline grid of bench.py --full): see "calibration" in the output.
 Writes are taken as reported (exact for streaming stores per the guide).
 """
 import csv
