@@ -110,7 +110,7 @@ int tsm_gae_set_scan_error_word(int32_t *host_pinned);
 
 /* RunningMeanStd.update (utils/statistics.py:97-114) with the UNNORMALISED returns of a2c.py:144-146:
  * x[i] = returns[ids ? ids[i] : i] * sqrt(rms[1] + rms_eps), i < n; batch mean / population variance in f64
- * (two-level fixed-order sums), then the parallel-variance merge into rms = {mean, var, count} in place.
+ * (two-level fixed-order sums of x - x[0]), then the parallel-variance merge into rms = {mean, var, count} in place.
  * work: f64[tsm_rms_update_work_elems(n)]. */
 int64_t tsm_rms_update_work_elems(int64_t n);
 int tsm_rms_update(const float *returns, const int64_t *ids, int64_t n, double *rms, double rms_eps,
@@ -277,7 +277,8 @@ int tsm_ppo_adv_stats(const float *adv, const int64_t *perm, const int64_t *mb_s
                       int32_t n_mb, float *stats_out, void *stream);
 /* The same statistics for long minibatches: every 8192-row chunk of a minibatch is reduced by its own workgroup
  * (shifted f64 sums), a second launch folds the chunks in chunk order (deterministic; independent of the grid).
- * max_rows >= the longest minibatch (host knowledge: mb_start lives in HBM); work: f64[tsm_ppo_adv_stats_work_elems]. */
+ * max_rows >= the longest minibatch (host knowledge: mb_start lives in HBM); a longer minibatch gets {NaN, NaN};
+ * work: f64[tsm_ppo_adv_stats_work_elems]. */
 int64_t tsm_ppo_adv_stats_work_elems(int32_t n_mb, int64_t max_rows);
 int tsm_ppo_adv_stats_wide(const float *adv, const int64_t *perm, const int64_t *mb_start, int32_t n_mb,
                            int64_t max_rows, double *work, float *stats_out, void *stream);
@@ -285,7 +286,8 @@ int tsm_ppo_adv_stats_wide(const float *adv, const int64_t *perm, const int64_t 
 /* Env-sharded replicas: the advantage normalisation of ppo.py:184-186 over the GLOBAL minibatch (the union
  * of the ranks' parts).  pack: stats [n_mb][2] = this rank's {mean, unbiased std} and its row counts mb_start[k+1] -
  * mb_start[k] -> pack_out f64 [n_mb][3] = {n, sum x, sum x^2}; the caller sums pack over the ranks (one all-reduce
- * for every minibatch of the update); unpack: summed pack -> stats_out [n_mb][2] = {mean, unbiased std} of the union. */
+ * for every minibatch of the update); unpack: summed pack -> stats_out [n_mb][2] = {mean, unbiased std} of the union.
+ * A part of one row packs {1, m, m^2} (its std is NaN), an empty part {0, 0, 0}; a union of one row has std NaN. */
 int tsm_ppo_adv_stats_pack(const float *stats, const int64_t *mb_start, int32_t n_mb, double *pack_out, void *stream);
 int tsm_ppo_adv_stats_unpack(const double *pack, int32_t n_mb, float *stats_out, void *stream);
 

@@ -124,3 +124,67 @@ def test_ops_refuse_cpu_tensors():
     x = torch.zeros(4, 8)
     with pytest.raises(RuntimeError, match="no CPU path"):
         ops.gae_lanes(x, x, x, x.to(torch.uint8), x.to(torch.uint8))
+
+
+# Entry points that no test names, itself or through the ops function that calls it, with the test that reaches each one
+# through a class.  Queries, one-time set-up and exports for outside callers only: no numerical kernel belongs here.
+_REACHED_THROUGH_CLASSES = {
+    # env and rollout kernels behind DeviceSimpleSpreadVectorEnv / DeviceSimpleTagVectorEnv / Collector
+    "tsm_mpe_spread_reset": "test_gpu_pipeline.py", "tsm_mpe_spread_step": "test_gpu_pipeline.py",
+    "tsm_mpe_tag_obs_dim": "test_gpu_tag.py", "tsm_mpe_tag_reset": "test_gpu_tag.py", "tsm_mpe_tag_step": "test_gpu_tag.py",
+    "tsm_rollout_spread": "test_gpu_rollout.py", "tsm_rollout_spread_actor": "test_gpu_rollout.py",
+    "tsm_rollout_tag": "test_gpu_tag.py",
+    # the peer-memory gradient sum behind parallel.GradSync
+    **{f"tsm_p2p_{s}": "test_gpu_parallel.py" for s in ("ipc_handle_bytes", "create", "export", "import", "all_reduce",
+                                                        "adam_step", "set_timeout", "handshake", "failed", "error_async",
+                                                        "destroy")},
+    # support / grid / workspace queries and one-time set-up of the rows kernels
+    "tsm_ppo_actor_rows_supported": "test_gpu_generic_ppo.py", "tsm_ppo_rows_init": "test_gpu_generic_ppo.py",
+    "tsm_ppo_critic_rows_grid": "test_gpu_generic_ppo.py", "tsm_critic_rows_forward_supported": "test_gpu_generic_ppo.py",
+    "tsm_critic_rows_init": "test_gpu_generic_ppo.py", "tsm_critic_rows_grad_grid": "test_gpu_generic_ppo.py",
+    "tsm_critic_rows_dw1_chunks": "test_gpu_generic_ppo.py",
+    # exports for ctypes callers and the runtime's own error path
+    **{f"tsm_mem_{s}": "test_abi_symbols.py" for s in ("alloc", "free", "h2d", "d2h", "set")},
+    "tsm_stream_sync": "test_abi_symbols.py", "tsm_stream_abort_capture": "test_abi_symbols.py",
+    "tsm_last_error": "test_abi_symbols.py",
+}
+
+
+def _ops_callers():
+    """{C-ABI name: names of the ops functions / classes whose body calls it}."""
+    import ast
+    import re
+
+    from tianshou_marl_amd import ops
+
+    src = open(ops.__file__).read()
+    callers = {}
+    for node in ast.parse(src).body:
+        if isinstance(node, (ast.FunctionDef, ast.ClassDef)):
+            for name in re.findall(r'"(tsm_\w+)"', ast.get_source_segment(src, node)):
+                callers.setdefault(name, set()).add(node.name)
+    return callers
+
+
+def test_every_entry_point_is_named_by_a_test():
+    """Every name in _abi.SIGNATURES appears in some tests/test_*.py, itself or as the ops function that calls it;
+    the only other way through is the explicit list above.  A new entry point without a test fails here."""
+    import glob
+    import re
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    files = sorted(glob.glob(os.path.join(here, "test_*.py")))
+    text = "\n".join(open(f).read() for f in files)
+    text = re.sub(r"(?s)\n_REACHED_THROUGH_CLASSES = \{.*?\n\}\n", "\n", text)  # the list itself does not count
+    callers = _ops_callers()
+
+    def named(word):
+        return re.search(r"\b" + re.escape(word) + r"\b", text) is not None
+
+    untested = [s for s in _abi.SIGNATURES if not named(s) and not any(named(c) for c in callers.get(s, ()))]
+    missing = sorted(set(untested) - set(_REACHED_THROUGH_CLASSES))
+    assert not missing, f"C-ABI entry points that no test names (add a test, or list the test that reaches them): {missing}"
+    stale = sorted(set(_REACHED_THROUGH_CLASSES) - set(untested))
+    assert not stale, f"listed as reached through classes, but named by a test or no longer bound (drop them): {stale}"
+    for name, test_file in _REACHED_THROUGH_CLASSES.items():
+        assert os.path.exists(os.path.join(here, test_file)), (name, test_file)

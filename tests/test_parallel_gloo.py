@@ -146,23 +146,31 @@ def _worker(rank: int, world: int, port: int, out_dir: str) -> None:
         # part of each minibatch; pack -> ONE all-reduce -> unpack turns them into the statistics of the union, identical
         # on every rank.  The pack / unpack arithmetic is a pair of HIP kernels in the product (checked bit for bit in
         # tests/test_gpu_parallel.py); here the same formulas in torch stand in for them and the PROTOCOL is under test.
+        # A part of one row has std NaN (torch.std) and packs (1, m, m^2); an empty part packs zeros; a union of one row
+        # has std NaN.
         def pack_fn(stats, mb_start):
             n = (mb_start[1:] - mb_start[:-1]).double()
             m, sd = stats[:, 0].double(), stats[:, 1].double()
-            return torch.stack([n, n * m, (n - 1.0) * (sd * sd) + n * m * m], dim=1).contiguous()
+            zero = torch.zeros_like(n)
+            ss = torch.where(n > 1.0, (n - 1.0) * (sd * sd), zero)
+            return torch.stack([n, torch.where(n > 0.0, n * m, zero), torch.where(n > 0.0, ss + n * m * m, zero)],
+                               dim=1).contiguous()
 
         def unpack_fn(pack, stats):
             m = pack[:, 1] / pack[:, 0]
             var = (pack[:, 2] - pack[:, 0] * m * m) / (pack[:, 0] - 1.0)
-            stats.copy_(torch.stack([m, var.clamp_min(0.0).sqrt()], dim=1).float())
+            sd = torch.where(pack[:, 0] > 1.0, var.clamp_min(0.0).sqrt(), torch.full_like(var, float("nan")))
+            stats.copy_(torch.stack([m, sd], dim=1).float())
 
         sync._stat_codec = (pack_fn, unpack_fn)
         gen = torch.Generator().manual_seed(7)
-        parts = [[torch.randn(n, generator=gen) * (1 + k) + k for n in (40 + 8 * k, 64)] for k in range(world)]  # [rank][minibatch]
+        # [rank][minibatch]; the last minibatch has one row on every rank (its std is NaN on each)
+        parts = [[torch.randn(n, generator=gen) * (1 + k) + k for n in (40 + 8 * k, 64, 1)] for k in range(world)]
         mine = torch.tensor([[float(x.mean()), float(x.std())] for x in parts[rank]], dtype=torch.float32)
-        mb_start = torch.tensor([0, parts[rank][0].numel(), parts[rank][0].numel() + parts[rank][1].numel()])
+        assert torch.isnan(mine[2, 1])
+        mb_start = torch.tensor([0] + [int(x) for x in torch.cumsum(torch.tensor([x.numel() for x in parts[rank]]), 0)])
         sync.merge_adv_stats_(mine, mb_start)
-        for j in range(2):
+        for j in range(3):
             union = torch.cat([parts[k][j] for k in range(world)]).double()
             assert mine[j, 0].item() == pytest.approx(float(union.mean()), rel=1e-6, abs=1e-6)
             assert mine[j, 1].item() == pytest.approx(float(union.std()), rel=1e-6)

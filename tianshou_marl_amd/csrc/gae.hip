@@ -189,23 +189,32 @@ __global__ void mc_return_kernel(const float *__restrict__ rew, int64_t T, int64
 }
 
 // ---- RunningMeanStd.update on the unnormalised returns (a2c.py:144-146, utils/statistics.py:97-114) ----
-// level 1: one workgroup per 8192 elements -> {sum x, sum x^2} f64 (x = returns * scale, scale from the OLD var);
+// level 1: one workgroup per 8192 elements -> {sum (x - c), sum (x - c)^2} f64 (x = returns * scale, scale from the OLD
+// var; c = the batch's first x: shifted sums, no cancellation between the two when |mean| >> std);
 // level 2: one workgroup folds the partials in index order and merges the batch moments into rms in place.
 constexpr int kRmsThreads = 1024, kRmsPer = 8;
 constexpr int64_t kRmsChunk = (int64_t)kRmsThreads * kRmsPer;
+
+// scale and shift of a batch, from rms before the update: the same expression in both levels (the same bits)
+__device__ inline void rms_scale_shift(const float *x, const int64_t *ids, const double *rms, double eps, double &scale,
+                                       double &shift) {
+    scale = sqrt(rms[1] + eps);
+    shift = (double)x[ids ? ids[0] : 0] * scale;
+}
 
 __global__ __launch_bounds__(kRmsThreads) void rms_partial_kernel(const float *__restrict__ x, const int64_t *__restrict__ ids,
                                                                   int64_t n, const double *__restrict__ rms, double eps,
                                                                   double *__restrict__ work) {
     __shared__ double sm[kRmsThreads / 64];
-    const double scale = sqrt(rms[1] + eps);
+    double scale, shift;
+    rms_scale_shift(x, ids, rms, eps, scale, shift);
     const int64_t base = (int64_t)blockIdx.x * kRmsChunk;
     double a1 = 0.0, a2 = 0.0;
 #pragma unroll
     for (int k = 0; k < kRmsPer; ++k) {
         const int64_t i = base + threadIdx.x + (int64_t)kRmsThreads * k;
         if (i < n) {
-            const double v = (double)x[ids ? ids[i] : i] * scale;
+            const double v = (double)x[ids ? ids[i] : i] * scale - shift;
             a1 += v;
             a2 += v * v;
         }
@@ -215,13 +224,17 @@ __global__ __launch_bounds__(kRmsThreads) void rms_partial_kernel(const float *_
     if (threadIdx.x == 0) { work[2 * blockIdx.x] = a1; work[2 * blockIdx.x + 1] = a2; }
 }
 
-__global__ __launch_bounds__(64) void rms_merge_kernel(const double *__restrict__ work, int64_t n_part, int64_t n,
-                                                       double *__restrict__ rms) {
+__global__ __launch_bounds__(64) void rms_merge_kernel(const float *__restrict__ x, const int64_t *__restrict__ ids,
+                                                       const double *__restrict__ work, int64_t n_part, int64_t n,
+                                                       double eps, double *__restrict__ rms) {
     if (threadIdx.x != 0) return;
+    double scale, shift;
+    rms_scale_shift(x, ids, rms, eps, scale, shift);
     double a1 = 0.0, a2 = 0.0;
     for (int64_t b = 0; b < n_part; ++b) { a1 += work[2 * b]; a2 += work[2 * b + 1]; }
-    const double bm = a1 / (double)n;
-    double bv = a2 / (double)n - bm * bm;  // np.var (population)
+    const double ms = a1 / (double)n;  // mean of x - shift
+    const double bm = shift + ms;
+    double bv = a2 / (double)n - ms * ms;  // np.var (population)
     if (bv < 0.0) bv = 0.0;
     const double mean = rms[0], var = rms[1], count = rms[2];
     const double delta = bm - mean, total = count + (double)n;
@@ -639,7 +652,7 @@ TSM_EXPORT int tsm_rms_update(const float *returns, const int64_t *ids, int64_t 
     hipLaunchKernelGGL(rms_partial_kernel, dim3((unsigned)n_part), dim3(kRmsThreads), 0, tsm_stream(stream), returns, ids,
                        n, rms, rms_eps, work);
     TSM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rms_merge_kernel, dim3(1), dim3(64), 0, tsm_stream(stream), work, n_part, n, rms);
+    hipLaunchKernelGGL(rms_merge_kernel, dim3(1), dim3(64), 0, tsm_stream(stream), returns, ids, work, n_part, n, rms_eps, rms);
     TSM_LAUNCH_CHECK();
     return TSM_OK;
 }

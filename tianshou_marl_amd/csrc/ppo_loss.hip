@@ -106,6 +106,11 @@ __global__ __launch_bounds__(64) void adv_stats_fold_kernel(const float *__restr
                                                             const double *__restrict__ work, float *__restrict__ stats_out) {
     const int64_t s0 = mb_start[blockIdx.x], M = mb_start[blockIdx.x + 1] - s0;
     if (threadIdx.x != 0) return;
+    if (M > (int64_t)n_chunk * kStatChunk) {  // max_rows was too small: the chunks cover a prefix only -- no statistics
+        stats_out[2 * blockIdx.x + 0] = NAN;
+        stats_out[2 * blockIdx.x + 1] = NAN;
+        return;
+    }
     double a1 = 0.0, a2 = 0.0;
     for (int c = 0; c < n_chunk; ++c) {
         a1 += work[((int64_t)blockIdx.x * n_chunk + c) * 2 + 0];
@@ -113,7 +118,7 @@ __global__ __launch_bounds__(64) void adv_stats_fold_kernel(const float *__restr
     }
     const double shift = M > 0 ? (double)adv[perm ? perm[s0] : s0] : 0.0;
     const double mean_s = M > 0 ? a1 / (double)M : 0.0;
-    stats_out[2 * blockIdx.x + 0] = (float)(shift + mean_s);
+    stats_out[2 * blockIdx.x + 0] = M > 0 ? (float)(shift + mean_s) : NAN;  // torch.mean of nothing, as adv_stats_kernel
     const double ss = a2 - a1 * mean_s;  // sum (x - mean)^2
     stats_out[2 * blockIdx.x + 1] = M > 1 ? (float)sqrt((ss > 0.0 ? ss : 0.0) / (double)(M - 1)) : NAN;
 }
@@ -303,16 +308,23 @@ Cfg to_cfg(const tsm_ppo_cfg *c) {
 // Data-parallel replicas: (mean, unbiased std) of a rank's part of each minibatch <-> the additive form (n, sum x,
 // sum x^2) in f64 that ONE all-reduce sums over the ranks.  Every operation is rounded on its own (no fma contraction),
 // so the pair is bit-reproducible from plain f64 arithmetic in any language (tests/test_gpu_parallel.py).
+// Degenerate parts: a part of one row has std NaN (torch.std) and contributes (1, m, m^2); an empty part (mean NaN)
+// contributes zeros.  A union of at most one row has std NaN, as torch.std of it.
 __global__ void adv_stats_pack_kernel(const float *__restrict__ stats, const int64_t *__restrict__ mb_start, int32_t n_mb,
                                       double *__restrict__ pack) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_mb) return;
     const double n = (double)(mb_start[k + 1] - mb_start[k]);
-    const double m = (double)stats[2 * k], sd = (double)stats[2 * k + 1];
-    const double nm1 = n > 1.0 ? __dsub_rn(n, 1.0) : 0.0;
     pack[3 * k] = n;
+    if (!(n > 0.0)) {
+        pack[3 * k + 1] = 0.0;
+        pack[3 * k + 2] = 0.0;
+        return;
+    }
+    const double m = (double)stats[2 * k], sd = (double)stats[2 * k + 1];
+    const double ss = n > 1.0 ? __dmul_rn(__dsub_rn(n, 1.0), __dmul_rn(sd, sd)) : 0.0;  // sum (x - m)^2
     pack[3 * k + 1] = __dmul_rn(n, m);
-    pack[3 * k + 2] = __dadd_rn(__dmul_rn(nm1, __dmul_rn(sd, sd)), __dmul_rn(__dmul_rn(n, m), m));
+    pack[3 * k + 2] = __dadd_rn(ss, __dmul_rn(__dmul_rn(n, m), m));
 }
 
 __global__ void adv_stats_unpack_kernel(const double *__restrict__ pack, int32_t n_mb, float *__restrict__ stats) {
@@ -320,11 +332,14 @@ __global__ void adv_stats_unpack_kernel(const double *__restrict__ pack, int32_t
     if (k >= n_mb) return;
     const double N = pack[3 * k], S1 = pack[3 * k + 1], S2 = pack[3 * k + 2];
     const double m = __ddiv_rn(S1, N);
-    const double den = N > 1.0 ? __dsub_rn(N, 1.0) : 1.0;
-    double var = __ddiv_rn(__dsub_rn(S2, __dmul_rn(__dmul_rn(N, m), m)), den);
-    if (!(var > 0.0)) var = 0.0;
+    float sd = NAN;
+    if (N > 1.0) {
+        double var = __ddiv_rn(__dsub_rn(S2, __dmul_rn(__dmul_rn(N, m), m)), __dsub_rn(N, 1.0));
+        if (!(var > 0.0)) var = 0.0;
+        sd = (float)__dsqrt_rn(var);
+    }
     stats[2 * k] = (float)m;
-    stats[2 * k + 1] = (float)__dsqrt_rn(var);
+    stats[2 * k + 1] = sd;
 }
 
 }  // namespace
