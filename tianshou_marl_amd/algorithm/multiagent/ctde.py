@@ -26,6 +26,7 @@ from torch import nn
 
 from ... import ops
 from ...data.batch import Batch
+from ...data.stats import LazyDict, ResultRing, pinned_slot, recycle
 from ...utils.net import FlatAdam, FlatMLP
 
 
@@ -76,60 +77,12 @@ class GlobalStateConstructor(nn.Module):
         return ops.global_state([obs[:, a].contiguous() for a in range(obs.shape[1])], "mean")
 
 
-class LazyScalars(dict):
+class LazyScalars(LazyDict):
     """Named f32 scalars a kernel is writing into pinned host memory: a dict filled in when first read (the reference
     returns `.item()` floats, ctde.py:196-199; here the host need not wait for them to queue the next learner)."""
 
     def __init__(self, slot: dict, names: tuple) -> None:
-        super().__init__()
-        self._slot, self._names = slot, names
-
-    def _force(self) -> None:
-        slot = self._slot
-        if slot is None:
-            return
-        self._slot = None
-        slot["event"].synchronize()
-        vals = slot["h"].numpy()
-        dict.update(self, {k: float(vals[i]) for i, k in enumerate(self._names)})
-        if slot.get("pending") is self:
-            slot["pending"] = None
-
-    def __getitem__(self, k):
-        self._force()
-        return dict.__getitem__(self, k)
-
-    def get(self, k, default=None):
-        self._force()
-        return dict.get(self, k, default)
-
-    def __contains__(self, k):
-        self._force()
-        return dict.__contains__(self, k)
-
-    def __iter__(self):
-        self._force()
-        return dict.__iter__(self)
-
-    def __len__(self):
-        self._force()
-        return dict.__len__(self)
-
-    def keys(self):
-        self._force()
-        return dict.keys(self)
-
-    def values(self):
-        self._force()
-        return dict.values(self)
-
-    def items(self):
-        self._force()
-        return dict.items(self)
-
-    def __repr__(self):
-        self._force()
-        return dict.__repr__(self)
+        super().__init__(slot, lambda slot: {k: float(v) for k, v in zip(names, slot["h"].numpy())})
 
 
 class CTDEPolicy(nn.Module):
@@ -236,7 +189,7 @@ class CTDEPolicy(nn.Module):
                 v_full=torch.empty(B, dtype=torch.float32, device=dev),
                 em_rows=(torch.arange(B, dtype=torch.int64, device=dev) % T * E
                          + torch.div(torch.arange(B, dtype=torch.int64, device=dev), T, rounding_mode="floor")).contiguous(),
-                mean_adv=torch.zeros(1, dtype=torch.float32, device=dev), ring=[], pos=0, calls=0, graphs={}, gslots={},
+                mean_adv=torch.zeros(1, dtype=torch.float32, device=dev), calls=0, graphs={}, gslots={},
                 step_dev=torch.zeros(1, dtype=torch.int64, device=dev))
         nW1 = H * K1
 
@@ -254,7 +207,6 @@ class CTDEPolicy(nn.Module):
             self.optim_critic.step_segs([(w1s, 0, nW1), (rest, nW1, critic.flat.numel() - nW1)], step_dev=step_dev)
             self.optim_actor.step_segs([(w["slabs_a"], 0, actor.flat.numel(), w["mean_adv"])], step_dev=step_dev)
 
-        mk_slot = lambda: dict(h=torch.zeros(2, dtype=torch.float32).pin_memory(), event=torch.cuda.Event(), pending=None)  # noqa: E731
         w["calls"] += 1
         same_steps = self.optim_actor.step_count == self.optim_critic.step_count
         hyper = tuple((o.lr, tuple(o.betas), o.eps, o.weight_decay) for o in (self.optim_actor, self.optim_critic)) + \
@@ -267,9 +219,10 @@ class CTDEPolicy(nn.Module):
             # per agent take turns, each with a pinned slot of its own for the statistics, so that a replay never overwrites
             # numbers the caller has not read yet; the optimizer step count lives in HBM (advanced by the actor kernel)
             k = w["calls"] & 1
-            slot = w["gslots"].setdefault(k, mk_slot())
-            if slot["pending"] is not None:
-                slot["pending"]._force()
+            if k not in w["gslots"]:
+                w["gslots"][k] = pinned_slot(2)
+            slot = w["gslots"][k]
+            recycle(slot)
             if w.get("step_host") != self.optim_actor.step_count:
                 w["step_dev"].fill_(self.optim_actor.step_count)
             if k not in w["graphs"]:
@@ -282,12 +235,8 @@ class CTDEPolicy(nn.Module):
             self.optim_critic.step_count += 1
             w["step_host"] = self.optim_actor.step_count
         else:
-            if len(w["ring"]) < 4:  # pinned slots the finalize kernel writes straight into (no copy on the stream)
-                w["ring"].append(mk_slot())
-            slot = w["ring"][w["pos"] % len(w["ring"])] if len(w["ring"]) == 4 else w["ring"][-1]
-            w["pos"] += 1
-            if slot["pending"] is not None:
-                slot["pending"]._force()
+            # pinned slots the finalize kernel writes straight into (no copy on the stream; a read slot is not waited for)
+            slot = ResultRing.of(w, lambda: pinned_slot(2)).take("resolve", wait=False)
             body(slot, None)
         slot["event"].record()
         out = LazyScalars(slot, ("actor_loss", "critic_loss"))

@@ -24,7 +24,8 @@ from torch import nn
 from .. import ops
 from ..data.batch import Batch, split_bounds
 from ..data.buffer import DeviceVectorReplayBuffer
-from ..data.stats import A2CTrainingStats, LazyStats, MapTrainingStats, SequenceSummaryStats
+from ..data.stats import (A2CTrainingStats, LazyDict, MapTrainingStats, ResultRing, lazy_training_stats, pinned_slot,
+                          training_stats_from_steps)
 from ..utils.net import DeviceRunningMeanStd, DiscreteActorCritic
 
 
@@ -420,10 +421,7 @@ class PPO(nn.Module):
         s_h = scal.cpu().numpy()  # the only host sync of the update (the reference does 4 .item() per minibatch)
         if self._grad_sync is not None:
             self._grad_sync.raise_if_failed()
-        return A2CTrainingStats(
-            loss=SequenceSummaryStats.from_sequence(s_h[:, 0]), actor_loss=SequenceSummaryStats.from_sequence(s_h[:, 1]),
-            vf_loss=SequenceSummaryStats.from_sequence(s_h[:, 2]), ent_loss=SequenceSummaryStats.from_sequence(s_h[:, 3]),
-            gradient_steps=n_steps)
+        return training_stats_from_steps(s_h)
 
     # ---- hipGraph path: the whole update (critic passes, GAE, every gradient step) is ONE graph launch ----
     def _warm_kernels(self, buffer: DeviceVectorReplayBuffer) -> None:
@@ -642,45 +640,15 @@ class PPO(nn.Module):
         # loss statistics (reference: 4 .item() per minibatch): one launch folds the loss partials of EVERY gradient step
         # and writes the result straight into a pinned (mapped) host slot -- no D2H copy on the stream; the host only
         # blocks when the stats are read
-        ring = g.setdefault("ring", [])
-        if len(ring) < 4:
-            ring.append(dict(h=torch.empty(g["scal"].shape, dtype=torch.float32, pin_memory=True),
-                             event=torch.cuda.Event(), pending=None))
-            slot = ring[-1]
-        else:
-            slot = ring[g.get("ring_pos", 0) % 4]
-            g["ring_pos"] = g.get("ring_pos", 0) + 1
-            if slot["pending"] is not None:
-                if self.async_stats:
-                    slot["pending"].expire("training stats were not read within 4 update() calls (async_stats=True)")
-                else:
-                    slot["pending"].resolve()
-            # never queue more than 4 updates ahead of the device: an unbounded run-ahead fills the HIP command queue,
-            # and the runtime then drains it with a ~2 ms stall every ~10 steps (tools/step_jitter.py)
-            slot["event"].synchronize()
+        slot = ResultRing.of(g, lambda: pinned_slot(*g["scal"].shape)).take(
+            "expire" if self.async_stats else "resolve", "training stats were not read within 4 update() calls (async_stats=True)")
         ops.ppo_finalize_many(g["partial"], g["nb_max"] * 4, g["nb_dev"], g["M_dev"], self._cfg, slot["h"])
         sync = self._grad_sync
         if sync is not None:
             sync.post_check()  # a lost peer (peer-memory all-reduce) is reported where the statistics are read: every rank raises
         slot["event"].record()
 
-        def build():
-            slot["event"].synchronize()
-            if sync is not None:
-                sync.raise_if_failed()
-            s_h = slot["h"].numpy().copy()
-            slot["pending"] = None
-            mk = lambda x: A2CTrainingStats(  # noqa: E731
-                loss=SequenceSummaryStats.from_sequence(x[:, 0]), actor_loss=SequenceSummaryStats.from_sequence(x[:, 1]),
-                vf_loss=SequenceSummaryStats.from_sequence(x[:, 2]), ent_loss=SequenceSummaryStats.from_sequence(x[:, 3]),
-                gradient_steps=len(x))
-            if per_agent:
-                per = len(s_h) // N
-                return MapTrainingStats({f"agent_{a}": mk(s_h[a * per:(a + 1) * per]) for a in range(N)})
-            return mk(s_h)
-
-        out = LazyStats(build)
-        slot["pending"] = out
+        out = lazy_training_stats(slot, sync, N if per_agent else None)
         if not self.async_stats:
             out.resolve()
         return out
@@ -948,16 +916,7 @@ class PPO(nn.Module):
         self.opt_step += n_steps
         w["step_host"] = self.opt_step
         self.param_version += 1
-        ring = w.setdefault("ring", [])
-        if len(ring) < 4:
-            ring.append(dict(h=torch.empty(n_steps, 4, dtype=torch.float32, pin_memory=True), event=torch.cuda.Event(),
-                             pending=None))
-            slot = ring[-1]
-        else:
-            slot = ring[w.get("ring_pos", 0) % 4]
-            w["ring_pos"] = w.get("ring_pos", 0) + 1
-            if slot["pending"] is not None:
-                slot["pending"]._force()
+        slot = ResultRing.of(w, lambda: pinned_slot(n_steps, 4)).take("resolve", wait=False)  # (a read slot is not waited for)
         if "scal" in w:  # (GenericPPO._learn_static folds its statistics inside the graph)
             slot["h"].copy_(w["scal"], non_blocking=True)
         else:
@@ -1079,83 +1038,24 @@ class PPO(nn.Module):
         return self.create_trainer(params).run()
 
 
-class LazyLosses(dict):
+def _fill_losses(slot: dict) -> dict:
+    if slot.get("sync") is not None:
+        slot["sync"].raise_if_failed()
+    if ops.gae_scan_failed():
+        raise RuntimeError("GAE: a workgroup of the parallel long-series scan gave up waiting for another one's map "
+                           "(returns / advantages of that learn() call are NaN)")
+    s_h = slot["h"].numpy()
+    return dict(loss=float(s_h[:, 0].mean()), actor_loss=float(s_h[:, 1].mean()), vf_loss=float(s_h[:, 2].mean()),
+                ent_loss=float(s_h[:, 3].mean()))
+
+
+class LazyLosses(LazyDict):
     """What `learn()` returns with `async_stats=True` ({"loss", "actor_loss", "vf_loss", "ent_loss"}: means over the call's
     gradient steps): a dict filled in when it is first read -- the statistics are on their way to pinned host memory behind
-    the captured update.  Every Python-level read resolves it; C code that walks the dict storage directly (json.dumps
-    without `indent`) does not, so pass `dict(x)` to such consumers."""
+    the captured update."""
 
     def __init__(self, slot: dict) -> None:
-        super().__init__()
-        self._slot = slot
-
-    def _force(self) -> None:
-        slot = self._slot
-        if slot is None:
-            return
-        self._slot = None
-        slot["event"].synchronize()
-        if slot.get("sync") is not None:
-            slot["sync"].raise_if_failed()
-        if ops.gae_scan_failed():
-            raise RuntimeError("GAE: a workgroup of the parallel long-series scan gave up waiting for another one's map "
-                               "(returns / advantages of that learn() call are NaN)")
-        s_h = slot["h"].numpy()
-        dict.update(self, loss=float(s_h[:, 0].mean()), actor_loss=float(s_h[:, 1].mean()), vf_loss=float(s_h[:, 2].mean()),
-                    ent_loss=float(s_h[:, 3].mean()))
-        if slot.get("pending") is self:
-            slot["pending"] = None
-
-    def __getitem__(self, k):
-        self._force()
-        return dict.__getitem__(self, k)
-
-    def get(self, k, default=None):
-        self._force()
-        return dict.get(self, k, default)
-
-    def __contains__(self, k):
-        self._force()
-        return dict.__contains__(self, k)
-
-    def __iter__(self):
-        self._force()
-        return dict.__iter__(self)
-
-    def __len__(self):
-        self._force()
-        return dict.__len__(self)
-
-    def keys(self):
-        self._force()
-        return dict.keys(self)
-
-    def values(self):
-        self._force()
-        return dict.values(self)
-
-    def items(self):
-        self._force()
-        return dict.items(self)
-
-    def __eq__(self, other):
-        self._force()
-        if isinstance(other, LazyLosses):
-            other._force()
-        return dict.__eq__(self, other)
-
-    def __ne__(self, other):
-        return not self.__eq__(other)
-
-    __hash__ = None
-
-    def __repr__(self):
-        self._force()
-        return dict.__repr__(self)
-
-    def copy(self):
-        self._force()
-        return dict(self)
+        super().__init__(slot, _fill_losses)
 
 
 def drive_steps(gen, grad_sync):

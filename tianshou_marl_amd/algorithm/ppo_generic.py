@@ -27,7 +27,7 @@ import torch
 from .. import ops
 from ..data.batch import Batch, split_bounds
 from ..data.buffer import DeviceVectorReplayBuffer
-from ..data.stats import A2CTrainingStats, SequenceSummaryStats
+from ..data.stats import A2CTrainingStats, ResultRing, lazy_training_stats, pinned_slot, training_stats_from_steps
 from ..utils.net import FlatMLP, MLPActorCritic
 from .ppo import PPO, drive_steps, ref_order_rows
 
@@ -370,8 +370,6 @@ class GenericPPO(PPO):
 
     # ---- hipGraph path: one replay per update() (uniform, unrotated buffers; local advantage statistics) ------------
     def _update_graph_generic(self, buffer: DeviceVectorReplayBuffer, batch_size: int | None, repeat: int):
-        from ..data.stats import MapTrainingStats
-
         T = buffer.host_uniform_len()
         if not T:
             return None
@@ -464,17 +462,6 @@ class GenericPPO(PPO):
         self.opt_step += n_steps
         w["step_host"] = self.opt_step
         self.param_version += 1
-        mk = lambda x: A2CTrainingStats(  # noqa: E731
-            loss=SequenceSummaryStats.from_sequence(x[:, 0]), actor_loss=SequenceSummaryStats.from_sequence(x[:, 1]),
-            vf_loss=SequenceSummaryStats.from_sequence(x[:, 2]), ent_loss=SequenceSummaryStats.from_sequence(x[:, 3]),
-            gradient_steps=len(x))
-
-        def finish(s_h):
-            if per_agent:
-                per = len(s_h) // N
-                return MapTrainingStats({f"agent_{a}": mk(s_h[a * per:(a + 1) * per]) for a in range(N)})
-            return mk(s_h)
-
         sync = self._grad_sync
         if sync is not None:
             sync.post_check()  # (peer-memory all-reduce: a lost peer is reported where the statistics are read)
@@ -482,36 +469,15 @@ class GenericPPO(PPO):
             s_h = w["scal"].cpu().numpy()
             if sync is not None:
                 sync.raise_if_failed()
-            return finish(s_h)
+            return training_stats_from_steps(s_h, N if per_agent else None)
         # async_stats=True (as PPO.update): the statistics travel to a pinned host slot behind the replay and are parsed when
         # the returned object is first read -- the host goes on to queue the next collect while the update runs; a ring of
         # four slots bounds the run-ahead
-        ring = w.setdefault("ring", [])
-        if len(ring) < 4:
-            ring.append(dict(h=torch.empty(w["scal"].shape, dtype=torch.float32, pin_memory=True), event=torch.cuda.Event(),
-                             pending=None))
-            slot = ring[-1]
-        else:
-            slot = ring[w.get("ring_pos", 0) % 4]
-            w["ring_pos"] = w.get("ring_pos", 0) + 1
-            if slot["pending"] is not None:
-                slot["pending"].expire("training stats were not read within 4 update() calls (async_stats=True)")
-            slot["event"].synchronize()
+        slot = ResultRing.of(w, lambda: pinned_slot(*w["scal"].shape)).take(
+            "expire", "training stats were not read within 4 update() calls (async_stats=True)")
         slot["h"].copy_(w["scal"], non_blocking=True)
         slot["event"].record()
-
-        def build():
-            slot["event"].synchronize()
-            if sync is not None:
-                sync.raise_if_failed()
-            slot["pending"] = None
-            return finish(slot["h"].numpy().copy())
-
-        from ..data.stats import LazyStats
-
-        out = LazyStats(build)
-        slot["pending"] = out
-        return out
+        return lazy_training_stats(slot, sync, N if per_agent else None)
 
     def _update(self, buffer: DeviceVectorReplayBuffer, batch_size: int | None, repeat: int, t0: float):
         # (data parallel: only with capturable collectives -- RCCL; otherwise eager launches with inline collectives)
@@ -578,10 +544,7 @@ class GenericPPO(PPO):
         s_h = torch.stack(scal).cpu().numpy()
         if self._grad_sync is not None:
             self._grad_sync.raise_if_failed()
-        return A2CTrainingStats(
-            loss=SequenceSummaryStats.from_sequence(s_h[:, 0]), actor_loss=SequenceSummaryStats.from_sequence(s_h[:, 1]),
-            vf_loss=SequenceSummaryStats.from_sequence(s_h[:, 2]), ent_loss=SequenceSummaryStats.from_sequence(s_h[:, 3]),
-            gradient_steps=len(scal))
+        return training_stats_from_steps(s_h)
 
     def learn(self, batch: Batch, batch_size: int | None = None, repeat: int = 1, **kwargs) -> dict[str, float]:
         """One PPO pass on an explicit agent batch (training_coordinator.py:336); a centralized critic takes
