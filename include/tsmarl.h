@@ -812,6 +812,49 @@ int tsm_mlp_backward(const tsm_mlp_desc *desc, const float *params, const float 
  * several networks write their gradients side by side into the slabs of ONE joint parameter vector (actor + critic
  * under one optimizer with a global gradient-norm clip, algorithm_base.py:485-498). */
 
+/* ---------------------------------------------------------------------------------------------
+ * QMIX  (tianshou/algorithm/multiagent/ctde.py:417-725)
+ * tsm_qmix_mix_td replaces  QMIXMixer.forward on both sides + the TD target + mse_loss + the mixer's part of
+ *           loss.backward() in QMIXPolicy.learn (ctde.py:468-499, 628-697), between the network forwards (tsm_mlp_forward)
+ *           and the networks' backward (tsm_mlp_backward).  One launch over the B joint rows.
+ *   agents:  per agent i < n_agents: q [B][n_act] (online Q-net on obs), q_next [B][n_act] (target Q-net on obs_next),
+ *            act i64 [B], rew f32 [B]; out: dq [B][n_act] = d loss / d q, non-zero only at act.
+ *   w1raw [B][n_agents * E], b1 [B][E], w2raw [B][E], b2 [B]: the online hypernetwork outputs on global_obs (hyper_w1,
+ *            hyper_b1, hyper_w2, hyper_b2); tw1raw .. tb2 the target hypernetworks' on global_obs_next.  term u8 [B]: agent
+ *            0's `terminated` (ctde.py:688).  monotonic != 0: w = |w_raw| (d|x|/dx = sign(x), sign(0) = 0).
+ *   out: dw1 / db1 / dw2 / db2 = gradients w.r.t. the four online hypernetwork outputs (same layouts);
+ *        partial f64 [tsm_qmix_partial_elems(B, E)] = per workgroup {sum (q_tot - y)^2, sum q_tot}.
+ *        qtot_out (nullable) f32 [B]: q_tot of every row (QMIXMixer.forward alone: act = 0 with n_act = 1).
+ *   Bounds: n_agents <= 8, E in {32, 64}, n_act <= 64; the [B][.] f32 arrays of the hypernetworks 16-byte aligned
+ *   (TSM_ERR_INVALID otherwise).  No atomics: every output element has one writer.
+ * tsm_qmix_finalize: out[2] = {loss = mse, q_values = mean(q_tot)} from the partials in a fixed order (one wave); out may
+ *   be pinned host memory.
+ * tsm_qmix_egreedy replaces  the epsilon-greedy choice of QMIXPolicy.forward (ctde.py:606-612) on the device:
+ *   act_out[b * act_row_stride + i] = a uniform action in [0, n_act) when agent i's coin lands (u < *eps_dev), else the
+ *   first argmax of q_i[b].  ONE coin per (call, agent), shared by the batch (quirk Q10).  Philox4x32-10 keyed by seed;
+ *   counter c = offset + *offset_dev (offset_dev nullable): the coin of agent i is word 1 at c + i, the uniform action of
+ *   (b, i) word 0 at c + b * n_agents + i -- a caller advancing c by B * n_agents per call keeps draws apart.
+ *   act_row_stride >= n_agents (n_agents for the Collector's [E][N] action array).
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_QMIX_MAX_AGENTS 8
+typedef struct tsm_qmix_agents {
+    const float *q[TSM_QMIX_MAX_AGENTS];
+    const float *q_next[TSM_QMIX_MAX_AGENTS];
+    const int64_t *act[TSM_QMIX_MAX_AGENTS];
+    const float *rew[TSM_QMIX_MAX_AGENTS];
+    float *dq[TSM_QMIX_MAX_AGENTS];
+} tsm_qmix_agents;
+int64_t tsm_qmix_partial_elems(int64_t B, int32_t E);
+int tsm_qmix_mix_td(const tsm_qmix_agents *agents, int32_t n_agents, int32_t n_act, int64_t B, int32_t E,
+                    const float *w1raw, const float *b1, const float *w2raw, const float *b2, const float *tw1raw,
+                    const float *tb1, const float *tw2raw, const float *tb2, const uint8_t *term, float gamma,
+                    int monotonic, float *dw1, float *db1, float *dw2, float *db2, double *partial, float *qtot_out,
+                    void *stream);
+int tsm_qmix_finalize(const double *partial, int32_t n_blocks, int64_t B, float *out, void *stream);
+int tsm_qmix_egreedy(const float *const *q_by_agent_host, int32_t n_agents, int64_t B, int32_t n_act,
+                     const float *eps_dev, uint64_t seed, uint64_t offset, const uint64_t *offset_dev, int32_t *act_out,
+                     int64_t act_row_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,8 +6,9 @@ Mirror of /root/reference/tianshou/algorithm/multiagent/ctde.py for the componen
                                        learned modules outside the hot path (out of scope)
   `DecentralizedActor`       :346-379  obs -> H -> H -> action logits, ReLU
   `CentralizedCritic`        :382-414  global_obs -> H -> H -> n_agents values, ReLU
-QMIX / MADDPG (:417-954) are off-policy value-decomposition / continuous-control algorithms outside the
-north-star path and are not built.
+  `QMIXMixer`, `QMIXPolicy` :417-725  value decomposition with a monotonic mixer: built in qmix.py (csrc/qmix.hip) and
+                                       re-exported here, so `from ...multiagent.ctde import QMIXPolicy` works as upstream
+MADDPG (:728-954) is continuous control, outside the north-star path, and is not built.
 
 Networks are `FlatMLP`s (one flat HBM parameter vector each, csrc/dense.hip f32-MFMA GEMMs for forward, dgrad
 and wgrad); the TD-target / MSE / policy-gradient head between them is `tsm_ctde_td_head` (csrc/ctde.hip) and the
@@ -312,3 +313,6 @@ class CTDEPolicy(nn.Module):
     def load_state_dict(self, sd, *args, **kwargs):
         for name, net in (("actor", self.actor), ("critic", self.critic)):
             net.load_reference_state_dict({k[len(name) + 1:]: v for k, v in sd.items() if k.startswith(name + ".")})
+
+
+from .qmix import QMIXMixer, QMIXPolicy  # noqa: E402  (qmix.py imports LazyScalars from this module)

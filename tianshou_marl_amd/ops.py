@@ -929,6 +929,102 @@ def ctde_td_head(q, q_next, rew, terminated, gamma: float, logits, act):
 
 
 # --------------------------------------------------------------------------------------------
+# QMIX (ctde.py:417-725; csrc/qmix.hip)
+# --------------------------------------------------------------------------------------------
+QMIX_EMBED_DIMS = (32, 64)
+
+
+def qmix_check(n_agents: int, embed_dim: int, n_act: int | None = None) -> None:
+    """The bounds of the QMIX kernels (include/tsmarl.h): ValueError naming the limit."""
+    if not 1 <= n_agents <= _abi.QMIX_MAX_AGENTS:
+        raise ValueError(f"QMIX: n_agents = {n_agents}; the HIP kernels serve 1 to {_abi.QMIX_MAX_AGENTS} agents")
+    if embed_dim not in QMIX_EMBED_DIMS:
+        raise ValueError(f"QMIX: mixing_embed_dim = {embed_dim}; the HIP kernels serve {QMIX_EMBED_DIMS}")
+    if n_act is not None and not 1 <= n_act <= 64:
+        raise ValueError(f"QMIX: n_act = {n_act}; the HIP kernels serve 1 to 64 actions")
+
+
+def qmix_partial_elems(B: int, embed_dim: int) -> int:
+    return call("tsm_qmix_partial_elems", B, embed_dim)
+
+
+def qmix_mix_td(q, q_next, act, rew, hyper, hyper_next, term, gamma: float, monotonic: bool = True, out=None,
+                qtot_out=None):
+    """Mixer forward on both sides + TD target + MSE + the mixer's backward (QMIXPolicy.learn, ctde.py:628-697).
+    q, q_next: per agent [B, A] (online Q on obs, target Q on obs_next); act: per agent i64 [B]; rew: per agent f32 [B];
+    hyper / hyper_next: (w1raw [B, N*E], b1 [B, E], w2raw [B, E], b2 [B, 1]) of the online / target hypernetworks;
+    term: agent 0's terminated [B] (u8 / bool).  out: optional (dq list, (dw1, db1, dw2, db2), partial) to write into.
+    qtot_out: optional f32 [B] that receives q_tot of every row.
+    -> (dq [per agent [B, A]], (dw1, db1, dw2, db2), partial f64)."""
+    N = len(q)
+    B, A = q[0].shape
+    E = hyper[1].shape[1]
+    qmix_check(N, E, A)
+    if not (len(q_next) == len(act) == len(rew) == N):
+        raise ValueError("qmix_mix_td: q, q_next, act and rew need one entry per agent")
+    for k, (x, x1) in enumerate(zip(q, q_next)):
+        if tuple(x.shape) != (B, A) or tuple(x1.shape) != (B, A) or act[k].numel() != B or rew[k].numel() != B:
+            raise ValueError(f"qmix_mix_td: agent {k}: expected Q [{B}, {A}], act [{B}], rew [{B}]")
+    for h in (hyper, hyper_next):
+        if (tuple(h[0].shape) != (B, N * E) or tuple(h[1].shape) != (B, E) or tuple(h[2].shape) != (B, E)
+                or h[3].numel() != B):
+            raise ValueError(f"qmix_mix_td: hypernetwork outputs must be [{B}, {N * E}], [{B}, {E}], [{B}, {E}], [{B}, 1]")
+    term = term.contiguous().view(torch.uint8) if term.dtype == torch.bool else _chk(term, torch.uint8, "term")
+    if term.numel() != B:
+        raise ValueError(f"qmix_mix_td: term must have {B} entries")
+    dev = q[0].device
+    if out is None:
+        dq = [torch.empty(B, A, dtype=torch.float32, device=dev) for _ in range(N)]
+        grads = tuple(torch.empty(B, w, dtype=torch.float32, device=dev) for w in (N * E, E, E, 1))
+        partial = torch.empty(qmix_partial_elems(B, E), dtype=torch.float64, device=dev)
+    else:
+        dq, grads, partial = out
+    ag = _abi.tsm_qmix_agents()
+    for k in range(N):
+        ag.q[k] = ptr(_chk(q[k], torch.float32, "q"))
+        ag.q_next[k] = ptr(_chk(q_next[k], torch.float32, "q_next"))
+        ag.act[k] = ptr(_chk(act[k], torch.int64, "act"))
+        ag.rew[k] = ptr(_chk(rew[k], torch.float32, "rew"))
+        ag.dq[k] = ptr(_chk(dq[k], torch.float32, "dq"))
+    hp = [ptr(_chk(x, torch.float32, "hyper")) for x in (*hyper, *hyper_next)]
+    call("tsm_qmix_mix_td", C.byref(ag), N, A, B, E, *hp, ptr(term), float(gamma), int(bool(monotonic)),
+         *(ptr(_chk(x, torch.float32, "grad")) for x in grads), ptr(_chk(partial, torch.float64, "partial")),
+         ptr(None if qtot_out is None else _chk(qtot_out, torch.float32, "qtot_out")), stream_ptr())
+    return dq, grads, partial
+
+
+def qmix_finalize(partial, B: int, out):
+    """{loss, q_values} of QMIXPolicy.learn from tsm_qmix_mix_td's partials (one launch).  out: device f32[2] or pinned
+    host f32[2]."""
+    if out.is_cuda:
+        out_p = ptr(out)
+    elif out.is_pinned() and out.is_contiguous() and out.dtype == torch.float32:
+        out_p = out.data_ptr()
+    else:
+        raise RuntimeError("qmix_finalize: out must be a device tensor or pinned host memory (f32)")
+    partial = _chk(partial, torch.float64, "partial")
+    call("tsm_qmix_finalize", ptr(partial), partial.numel() // 2, B, out_p, stream_ptr())
+    return out
+
+
+def qmix_egreedy(q, eps_dev, seed: int, offset: int = 0, offset_dev=None, out=None, row_stride: int | None = None):
+    """Epsilon-greedy actions of QMIXPolicy.forward (ctde.py:606-612) on the device: q per agent [B, A] -> act i32 with
+    act[b * row_stride + i] (default [B, N]).  One coin per (call, agent); eps read from the device scalar eps_dev."""
+    N = len(q)
+    B, A = q[0].shape
+    qmix_check(N, 32, A)
+    stride = N if row_stride is None else int(row_stride)
+    if out is None:
+        out = torch.empty(B, stride, dtype=torch.int32, device=q[0].device)
+    if out.numel() < (B - 1) * stride + N if B else False:
+        raise ValueError("qmix_egreedy: out is too small")
+    arr = (C.c_void_p * N)(*[ptr(_chk(x, torch.float32, "q")) for x in q])
+    call("tsm_qmix_egreedy", arr, N, B, A, ptr(_chk(eps_dev, torch.float32, "eps_dev")), seed & (2**64 - 1),
+         offset & (2**64 - 1), ptr(offset_dev), ptr(_chk(out, torch.int32, "out")), stride, stream_ptr())
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # fully-connected networks of arbitrary width (csrc/dense.hip)
 # --------------------------------------------------------------------------------------------
 _ACT = {"none": 0, None: 0, "relu": 1, "tanh": 2}
