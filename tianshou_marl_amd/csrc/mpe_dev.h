@@ -55,6 +55,31 @@ __device__ __forceinline__ float mpe_obs_elem(const MpeCfg &c, const float *ap, 
     return 0.f;  // communication channel of silent agents
 }
 
+// The same element as LDS offsets: mpe_obs_elem(.., i, k) == lds[oa] - lds[ob], where AP / AV / LP are the offsets of the env's
+// agent positions, velocities and landmarks and `zero` is the offset of a cell that holds 0.f (it stands in where there is no
+// subtrahend, x - 0.f == x bit for bit, and for the silent communication channel).  Returned packed, oa << 16 | ob: the
+// persistent rollouts work the pair out once per (thread, element) and an element then costs two LDS reads and a subtraction.
+__device__ __forceinline__ uint32_t mpe_obs_offsets(int N, int AP, int AV, int LP, int zero, int i, int k) {
+    int oa = zero, ob = zero;
+    if (k < 2) oa = AV + 2 * i + k;
+    else if (k < 4) oa = AP + 2 * i + (k - 2);
+    else {
+        int kk = k - 4;
+        if (kk < 2 * N) { oa = LP + kk; ob = AP + 2 * i + (kk & 1); }
+        else {
+            kk -= 2 * N;
+            if (kk < 2 * (N - 1)) {
+                int jj = kk >> 1;
+                const int x = kk & 1;
+                if (jj >= i) ++jj;  // others in increasing index, skipping self
+                oa = AP + 2 * jj + x; ob = AP + 2 * i + x;
+            }
+        }
+    }
+    return ((uint32_t)oa << 16) | (uint32_t)ob;
+}
+__device__ __forceinline__ uint32_t mpe_obs_offsets_zero(int zero) { return ((uint32_t)zero << 16) | (uint32_t)zero; }   // 0.f - 0.f
+
 // All N agent positions of one env into registers, branch-free (index clamped to N - 1): the LDS reads issue back
 // to back and cost one round trip instead of one per loop iteration; the loops over them then branch on the
 // wave-uniform N, so only N iterations execute.
@@ -124,6 +149,48 @@ __device__ __forceinline__ void mpe_agent_move(const MpeCfg &c, const float *ap,
         if (j != i && mpe_pair_force(c, px, py, p.x[j], p.y[j], i, j, sx, sy)) { fx += sx; fy += sy; }
     }
     mpe_integrate(c, px, py, vx, vy, fx, fy, npx, npy, nvx, nvy);
+}
+
+// The pair forces of a step as (agent row, other agent) tasks, one or two per thread, where a block of consecutive rows (<= 16 / N
+// whole envs per 16 rows) has its positions in LDS: task p <-> row p >> 3, other agent p & 7; a thread owns p0 and p0 + stride.
+// mpe_pair_table: the tasks' (env << 3 | agent) once per rollout, -1 = no such row; mpe_pair_tasks: one step's forces into
+// cx / cy / cv[p] (cv: 1 = the pair is in contact range); mpe_pair_fold: the agent lane of row r adds its row's terms in partner
+// order (six 16-byte reads) -- the same additions in the same order as mpe_agent_move.
+__device__ __forceinline__ void mpe_pair_table(int N, int rows_here, int p0, int stride, int (&pair_ei)[2]) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int rp = (p0 + stride * q) >> 3, ep = rp / N;
+        pair_ei[q] = rp < rows_here ? (ep << 3) | (rp - ep * N) : -1;
+    }
+}
+__device__ __forceinline__ void mpe_pair_tasks(const MpeCfg &c, const int (&pair_ei)[2], int p0, int stride, const float *s_ap,
+                                               float *s_cx, float *s_cy, int *s_cv) {
+    const int st = 2 * c.N;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int p = p0 + stride * q, jp = p & 7;
+        float sx = 0.f, sy = 0.f;
+        int ok = 0;
+        if (pair_ei[q] >= 0 && jp < c.N) {
+            const int ip = pair_ei[q] & 7;
+            const float *ap = s_ap + (pair_ei[q] >> 3) * st;
+            if (jp != ip) ok = mpe_pair_force(c, ap[2 * ip], ap[2 * ip + 1], ap[2 * jp], ap[2 * jp + 1], ip, jp, sx, sy) ? 1 : 0;
+        }
+        s_cx[p] = sx; s_cy[p] = sy; s_cv[p] = ok;
+    }
+}
+__device__ __forceinline__ void mpe_pair_fold(const MpeCfg &c, const float *s_cx, const float *s_cy, const int *s_cv, int r, float &fx,
+                                              float &fy) {
+    typedef int i4 __attribute__((ext_vector_type(4)));
+    typedef float v4 __attribute__((ext_vector_type(4)));
+    const i4 v0 = *reinterpret_cast<const i4 *>(s_cv + 8 * r), v1 = *reinterpret_cast<const i4 *>(s_cv + 8 * r + 4);
+    const v4 x0 = *reinterpret_cast<const v4 *>(s_cx + 8 * r), x1 = *reinterpret_cast<const v4 *>(s_cx + 8 * r + 4);
+    const v4 y0 = *reinterpret_cast<const v4 *>(s_cy + 8 * r), y1 = *reinterpret_cast<const v4 *>(s_cy + 8 * r + 4);
+#pragma unroll
+    for (int j = 0; j < kMpeMaxN; ++j) {
+        const int ok = j < 4 ? v0[j & 3] : v1[j & 3];
+        if (j < c.N && ok) { fx += j < 4 ? x0[j & 3] : x1[j & 3]; fy += j < 4 ? y0[j & 3] : y1[j & 3]; }
+    }
 }
 
 // min over agents of the distance to landmark l (on the NEW positions).  Correctly rounded sqrt is monotone, so

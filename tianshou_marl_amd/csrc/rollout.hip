@@ -20,7 +20,7 @@
 #include "mlp_tile.h"
 #include "mpe_dev.h"
 #include "philox.h"
-#include "vrb_dev.h"
+#include "rollout_dev.h"
 #include "wave_mlp.h"
 
 int tsm_mpe_check_cfg(const tsm_mpe_cfg *h, MpeCfg *c);  // mpe.hip
@@ -43,30 +43,50 @@ struct RolloutArgs {
     int32_t *steps;
     int auto_reset;
     float *obs_cur_out;  // [n_env][N][D] next policy input after the rollout
-    // buffer
-    void *vrb_state;
-    int64_t S;
-    uint8_t *done_store;
-    float *obs_store, *obs_next_store, *rew_store, *logp_store, *vs_store, *vnext_store;
-    int32_t *act_store;
-    uint8_t *term_store, *trunc_store;
-    // per-step outputs [n_steps][n_env]...
-    int64_t *ptr_out, *ep_len_out, *ep_idx_out;
-    double *ep_rew_out;
-    int n_steps;
-    // compact record of the episodes finished during this rollout (nullable): i64 words
-    //   [n_env] count | [n_env][max_ep] (step << 32 | length) | [n_env][max_ep][N] f64 return
-    int64_t *ep_rec;
-    int max_ep;
-    uint64_t offset_inc;
-    uint64_t *offset_dev_rw;
-    uint32_t *done_ctr;
+    RolloutBufArgs b;   // buffer, per-step outputs, episode record, counter advance
     long long *stamps;  // diagnostic build only (tsm_debug_set_stamps): phase time stamps of workgroup 0
 };
 
 
 #define XSTAMP(k) do { if (a.stamps && blockIdx.x == 0 && threadIdx.x == 0 && t < 4) a.stamps[900 + t * 8 + (k)] = (long long)wall_clock64(); } while (0)
 #define STAMP(k) do { if (a.stamps && blockIdx.x == 0 && threadIdx.x == 0 && t < 4) a.stamps[t * 8 + (k)] = (long long)wall_clock64(); } while (0)
+
+// rollout_kernel's LDS behind the forward layout Lay<H> (offsets in floats): the kernel takes its pointers from it, the launcher the
+// size it requests
+struct RtLay {
+    int XN0, AP, AV, LP, REW, LOGP, VAL, MIN, ACT, STEPS, DONE, ROW, EP, CX, CY, CV, U, ANY, total;
+    __host__ __device__ RtLay(int fwd_total, int ld1) {
+        int o = fwd_total;
+        XN0 = o; o += R * ld1;      // [R][ld1] second observation tile (obs_next rows)
+        AP = o; o += R * 2;         // [EPB][N][2]
+        AV = o; o += R * 2;
+        LP = o; o += R * 2;
+        REW = o; o += R;            // [R]
+        LOGP = o; o += R;           // [R]
+        VAL = o; o += R;            // [R]
+        MIN = o; o += R;            // [R] landmark minima
+        ACT = o; o += R;            // int [R]
+        STEPS = o; o += R;          // int [EPB]
+        DONE = o; o += 2 * R;       // int [2][EPB] done flag of the step just taken (generation t & 1)
+        // (8-byte alignment by INDEX arithmetic off the 16-byte aligned LDS base: rounding the address through uintptr_t made s_row /
+        //  s_ep generic pointers, every access to them a FLAT instruction, and every flat load waits for vmcnt(0) -- i.e. for all of the
+        //  step's outstanding global stores: round 5, 24 flat operations in this file)
+        o = (o + 1) & ~1;
+        ROW = o; o += 2 * 2 * R;    // int64 [2][EPB] slot*B + env of the step just added (generation t & 1)
+        EP = o; o += 2 * R;         // uint64 [EPB] episode counter of finished envs
+        o = (o + 3) & ~3;
+        CX = o; o += R * 8;         // [R][8] pair forces of (row, other agent), phase D; 16-byte rows
+        CY = o; o += R * 8;
+        CV = o; o += R * 8;         // int [R][8] "the pair is in range"
+        U = o; o += 2 * R;          // [2][R] the sampling uniforms of step t (generation t & 1)
+        ANY = o; o += 2;            // int [2] "an episode of this tile ends at step t"
+        // (unused tail, the slack of the hand-kept sum this struct replaced: the launcher's eight- / four-wave rule compares the
+        //  size with half a CU's LDS, and for 3 to 5 agents it is the tail that puts 81 880 bytes above 80 KB -- kept, so that the
+        //  rule chooses what it chose; profiles/rollout_shared_bookkeeping.md has the byte counts per agent count)
+        o += 3 * R + 12;
+        total = o;
+    }
+};
 
 // With NT2 = 512 the workgroup has EIGHT waves: in the forward pass waves 0-3 carry the actor and waves 4-7 the critic (one MFMA chain
 // per wave and layer); the element-wise loops (observation build, payload scatter) spread over all 512 threads;
@@ -92,29 +112,14 @@ __global__ __launch_bounds__(NT2) void rollout_kernel(RolloutArgs a) {
     const int n_here = min(EPB, c.n_env - e0);
     const int rows_here = n_here * N;         // live tile rows (<= 16): row r = (env el, agent i), r = el*N + i
     const int64_t B = c.n_env;
-    // extra LDS behind the forward layout
-    float *XN0 = lds + ly.total;              // [R][ld1] second observation tile (obs_next rows)
-    float *s_ap = XN0 + R * d.ld1;             // [EPB][N][2]
-    float *s_av = s_ap + R * 2;
-    float *s_lp = s_av + R * 2;
-    float *s_rew = s_lp + R * 2;              // [R]
-    float *s_logp = s_rew + R;                // [R]
-    float *s_val = s_logp + R;                // [R]
-    float *s_m = s_val + R;                   // [R] landmark minima
-    int *s_act = reinterpret_cast<int *>(s_m + R);          // [R]
-    int *s_steps = s_act + R;                               // [EPB]
-    int *s_done = s_steps + R;                              // [2][EPB] done flag of the step just taken (generation t & 1)
-    // (8-byte alignment by INDEX arithmetic off the 16-byte aligned LDS base: rounding the address through uintptr_t made s_row /
-    //  s_ep generic pointers, every access to them a FLAT instruction, and every flat load waits for vmcnt(0) -- i.e. for all of the
-    //  step's outstanding global stores: round 5, 24 flat operations in this file)
-    int64_t *s_row = reinterpret_cast<int64_t *>(                    // [2][EPB] slot*B + env of the step just added (generation t & 1)
-        lds + (((int)(reinterpret_cast<float *>(s_done + 2 * R) - lds) + 1) & ~1));
-    uint64_t *s_ep = reinterpret_cast<uint64_t *>(s_row + 2 * R);    // [EPB] episode counter of finished envs
-    float *s_cx = lds + (((int)(reinterpret_cast<float *>(s_ep + R) - lds) + 3) & ~3);   // [R][8] pair forces of (row, other agent), phase D; 16-byte rows
-    float *s_cy = s_cx + R * 8;
-    int *s_cv = reinterpret_cast<int *>(s_cy + R * 8);               // [R][8] "the pair is in range"
-    float *s_u = reinterpret_cast<float *>(s_cv + R * 8);            // [2][R] the sampling uniforms of step t (generation t & 1)
-    int *s_any = reinterpret_cast<int *>(s_u + 2 * R);               // [2] "an episode of this tile ends at step t"
+    const RtLay tl(ly.total, d.ld1);          // extra LDS behind the forward layout
+    float *XN0 = lds + tl.XN0, *s_ap = lds + tl.AP, *s_av = lds + tl.AV, *s_lp = lds + tl.LP, *s_rew = lds + tl.REW,
+          *s_logp = lds + tl.LOGP, *s_val = lds + tl.VAL, *s_m = lds + tl.MIN, *s_cx = lds + tl.CX, *s_cy = lds + tl.CY, *s_u = lds + tl.U;
+    int *s_act = reinterpret_cast<int *>(lds + tl.ACT), *s_steps = reinterpret_cast<int *>(lds + tl.STEPS),
+        *s_done = reinterpret_cast<int *>(lds + tl.DONE), *s_cv = reinterpret_cast<int *>(lds + tl.CV),
+        *s_any = reinterpret_cast<int *>(lds + tl.ANY);
+    int64_t *s_row = reinterpret_cast<int64_t *>(lds + tl.ROW);
+    uint64_t *s_ep = reinterpret_cast<uint64_t *>(lds + tl.EP);
     // s_done / s_row in two generations: step t's index algebra (wave 4, beside the head of phase C) writes generation t & 1 while
     // the head reads generation (t - 1) & 1 as "the previous step" (pending V(obs_next) stores)
 
@@ -127,7 +132,7 @@ __global__ __launch_bounds__(NT2) void rollout_kernel(RolloutArgs a) {
         else stage_weights<H>(lds, ly, d, a.P);
     }
     for (int i = threadIdx.x; i < R * d.ld1; i += NT2) { lds[ly.X + i] = 0.f; XN0[i] = 0.f; }
-    const VrbState vs = vrb_view(a.vrb_state, B, N);
+    const VrbState vs = vrb_view(a.b.vrb_state, B, N);
     // agent lane r < rows_here (wave 0) <-> (env el, agent i); env lane 256 + q (wave 4) owns env q's bookkeeping: the buffer
     // index algebra of a step runs beside its head (phase C: waves 0-3), off the step's dependent chain
     const int r = threadIdx.x, el = r / N, ai = r - el * N;
@@ -155,37 +160,18 @@ __global__ __launch_bounds__(NT2) void rollout_kernel(RolloutArgs a) {
     bool pending = false;                                 // (uniform) the previous step's reward terms are still to do
     // sub-buffer bookkeeping of "my" env lives in registers for the whole rollout: the per-step index algebra
     // then has no dependent global loads, only fire-and-forget stores
-    int64_t v_ins = 0, v_size = 0, v_eplen = 0, v_epstart = 0, v_last = 0;
-    int n_fin = 0;    // episodes this env finished during the rollout (env lanes)
+    VrbLane vl;       // (vl.n_fin: episodes this env finished during the rollout, on the env lanes)
     int n_fin_r = 0;  // the same count on the return lanes
-    double v_epret[kMpeMaxN];
-#pragma unroll
-    for (int k = 0; k < kMpeMaxN; ++k) v_epret[k] = 0.0;
-    if (ret_lane) {
-#pragma unroll
-        for (int k = 0; k < kMpeMaxN; ++k) if (k < N) v_epret[k] = vs.ep_return[(int64_t)(e0 + rq) * N + k];
-    }
+    EpReturns<kMpeMaxN> epr;
+    if (ret_lane) epr.load(vs, N, e0 + rq);
     // episode returns of step tt on the return lanes from the rewards in s_rew: trq = the env's episode ends at that step
     auto step_returns = [&](int tt, bool trq) {
         const int64_t bq = e0 + rq;
-        const bool recq = trq && a.ep_rec && n_fin_r < a.max_ep;
-        const int64_t oq = (int64_t)tt * B + bq;
-        double *rec_rew = recq ? reinterpret_cast<double *>(a.ep_rec + B + (int64_t)B * a.max_ep) +
-                                     ((int64_t)bq * a.max_ep + n_fin_r) * N : nullptr;
-#pragma unroll
-        for (int k = 0; k < kMpeMaxN; ++k) {
-            if (k < N) {
-                const double acc = v_epret[k] + (double)s_rew[rq * N + k];
-                a.ep_rew_out[oq * N + k] = trq ? acc : 0.0;
-                if (recq) rec_rew[k] = acc;
-                v_epret[k] = trq ? 0.0 : acc;
-            }
-        }
-        n_fin_r += trq ? 1 : 0;
+        const bool recq = trq && a.b.ep_rec && n_fin_r < a.b.max_ep;
+        epr.fold(a.b.ep_rew_out, a.b.ep_rec, a.b.max_ep, N, B, bq, (int64_t)tt * B + bq, trq, recq, n_fin_r, s_rew + rq * N);
     };
     if (env_lane) {
-        v_ins = vs.ins[be]; v_size = vs.size[be]; v_eplen = vs.ep_len[be]; v_epstart = vs.ep_start[be];
-        v_last = vs.last_index[be];
+        vl.load(vs, be);
         s_steps[bel] = a.steps[be];
         s_done[bel] = 1; s_done[R + bel] = 1;  // "no pending v_next" before the first step
         s_row[bel] = 0; s_row[R + bel] = 0;
@@ -205,7 +191,7 @@ __global__ __launch_bounds__(NT2) void rollout_kernel(RolloutArgs a) {
     // two observation tiles, swapped every step: obs_next of step t IS obs of step t + 1 (rows of re-initialised
     // envs are rebuilt in F), so the observation function runs once per step, not twice
     Lay<H> lyf = ly;
-    int xcur = ly.X, xnxt = ly.total;
+    int xcur = ly.X, xnxt = tl.XN0;
     // A. observation rows from the LDS-resident state: one (row, element) per thread
     for (int i = threadIdx.x; i < rows_here * D; i += NT2) {
         const int rr = i / D, k = i - rr * D, ee = rr / N;
@@ -213,9 +199,9 @@ __global__ __launch_bounds__(NT2) void rollout_kernel(RolloutArgs a) {
     }
     __syncthreads();
 
-    for (int t = 0; t <= a.n_steps; ++t) {
+    for (int t = 0; t <= a.b.n_steps; ++t) {
         const int g = (t & 1) * R;   // this step's generation of s_row / s_done; g ^ R: the previous step's
-        const bool last = t == a.n_steps;  // extra pass: bootstrap value of the final observation only
+        const bool last = t == a.b.n_steps;  // extra pass: bootstrap value of the final observation only
         float *XN = lds + xnxt;
         STAMP(0);
         if (a.stamps && blockIdx.x == 0 && threadIdx.x == 0 && t < 64) a.stamps[640 + t] = (long long)wall_clock64();
@@ -225,30 +211,14 @@ __global__ __launch_bounds__(NT2) void rollout_kernel(RolloutArgs a) {
         if constexpr (NT2 == 2 * NT) tile_forward_split<H>(lds, lyf, d);
         else tile_forward<H>(lds, lyf, d);
         STAMP(2);
-        bool tr = false, rec = false;
-        int64_t o = 0;
+        bool tr = false;
         if (env_lane && !last) {   // the buffer index algebra of this step (beside the head; D .. F read generation t & 1)
             const int stp = s_steps[bel] + 1;
             tr = stp >= c.max_cycles;
             s_steps[bel] = stp;
-            o = (int64_t)t * B + be;
-            const int64_t cur = v_ins;
-            int64_t sz = v_size + 1; if (sz > a.S) sz = a.S;
-            int64_t nxt = cur + 1; if (nxt >= a.S) nxt -= a.S;
-            const int64_t elen = v_eplen + 1;
-            if (v_epstart > sz) atomicExch((unsigned long long *)vs.error_flag, 1ull);
-            rec = tr && a.ep_rec && n_fin < a.max_ep;
-            // (the record carries CollectStats.lens = len(episode_batch): the episode's rows IN THE BUFFER, collector.py:203,990-993 --
-            //  after a reset_buffer(keep_statistics=True) an episode counts its rows since the reset; ep_len_out stays add()'s ep_len)
-            if (rec) a.ep_rec[B + (int64_t)be * a.max_ep + n_fin] = ((int64_t)t << 32) | ((cur >= v_epstart ? cur - v_epstart : cur - v_epstart + a.S) + 1);
-            n_fin += tr ? 1 : 0;
-            a.ep_len_out[o] = tr ? elen : 0;
-            a.ptr_out[o] = cur + (int64_t)be * a.S;
-            a.ep_idx_out[o] = v_epstart + (int64_t)be * a.S;
-            v_ins = nxt; v_size = sz; v_eplen = tr ? 0 : elen; v_epstart = tr ? nxt : v_epstart;
-            v_last = cur + (int64_t)be * a.S;
-            a.done_store[cur * B + be] = tr ? 1 : 0;
-            s_row[g + bel] = cur * B + be;
+            const VrbStep sp = vl.add(vs, a.b.S, t, be, B, tr, a.b.done_store, a.b.ptr_out, a.b.ep_len_out, a.b.ep_idx_out, a.b.ep_rec, a.b.max_ep);
+            vl.n_fin += tr ? 1 : 0;   // (the return lanes keep their own count: n_fin_r)
+            s_row[g + bel] = sp.row;
             s_done[g + bel] = tr ? 1 : 0;
             const unsigned long long ends = __ballot(tr);   // (the env lanes share wave 4)
             if (bel == 0) s_any[t & 1] = ends != 0ull;
@@ -269,7 +239,7 @@ __global__ __launch_bounds__(NT2) void rollout_kernel(RolloutArgs a) {
 #pragma unroll
                 for (int l = 0; l < kMpeMaxN; ++l) mv[l] = l < N ? __shfl(md, wel * N + l, 64) : 0.f;
                 const float rw = mpe_reward_regs(c, mv, local);
-                if (wl < rows_here) { s_rew[wl] = rw; a.rew_store[rowq * N + wai] = rw; }
+                if (wl < rows_here) { s_rew[wl] = rw; a.b.rew_store[rowq * N + wai] = rw; }
             }
             pending = false;
         }
@@ -308,8 +278,8 @@ __global__ __launch_bounds__(NT2) void rollout_kernel(RolloutArgs a) {
             if (j == 0 && hr < rows_here) {
                 const float val = lg[16];
                 const int hel = hr / N;
-                if (!s_done[(g ^ R) + hel] && a.vnext_store)  // V(obs_next) of the previous step == V(obs) of this one
-                    a.vnext_store[s_row[(g ^ R) + hel] * N + (hr - hel * N)] = val;
+                if (!s_done[(g ^ R) + hel] && a.b.vnext_store)  // V(obs_next) of the previous step == V(obs) of this one
+                    a.b.vnext_store[s_row[(g ^ R) + hel] * N + (hr - hel * N)] = val;
                 if (!last) s_val[hr] = val;
             }
             if (!last) {
@@ -365,15 +335,7 @@ __global__ __launch_bounds__(NT2) void rollout_kernel(RolloutArgs a) {
             const float vx = s_av[el * st + 2 * ai], vy = s_av[el * st + 2 * ai + 1];
             float fx = mpe_action_force(c, s_act[r], 0);
             float fy = mpe_action_force(c, s_act[r], 1);
-            typedef int i4 __attribute__((ext_vector_type(4)));
-            const i4 v0 = *reinterpret_cast<const i4 *>(s_cv + 8 * r), v1 = *reinterpret_cast<const i4 *>(s_cv + 8 * r + 4);
-            const f4 x0 = *reinterpret_cast<const f4 *>(s_cx + 8 * r), x1 = *reinterpret_cast<const f4 *>(s_cx + 8 * r + 4);
-            const f4 y0 = *reinterpret_cast<const f4 *>(s_cy + 8 * r), y1 = *reinterpret_cast<const f4 *>(s_cy + 8 * r + 4);
-#pragma unroll
-            for (int j = 0; j < kMpeMaxN; ++j) {
-                const int ok = j < 4 ? v0[j & 3] : v1[j & 3];
-                if (j < N && ok) { fx += j < 4 ? x0[j & 3] : x1[j & 3]; fy += j < 4 ? y0[j & 3] : y1[j & 3]; }
-            }
+            mpe_pair_fold(c, s_cx, s_cy, s_cv, r, fx, fy);
             float npx, npy, nvx, nvy;
             mpe_integrate(c, px, py, vx, vy, fx, fy, npx, npy, nvx, nvy);
             s_ap[el * st + 2 * ai] = npx; s_ap[el * st + 2 * ai + 1] = npy;
@@ -421,29 +383,29 @@ __global__ __launch_bounds__(NT2) void rollout_kernel(RolloutArgs a) {
                 v = XN[rr * d.ld1 + k];
             }
             const int64_t dst = (s_row[g + ee] * N + (rr - ee * N)) * D + k;
-            a.obs_store[dst] = lds[xcur + rr * d.ld1 + k];
-            if (a.obs_next_store) a.obs_next_store[dst] = v;
+            a.b.obs_store[dst] = lds[xcur + rr * d.ld1 + k];
+            if (a.b.obs_next_store) a.b.obs_next_store[dst] = v;
         }
         if (ur >= 0 && ur < rows_here) {   // (the rows' payload on wave 5: wave 0 has its observation elements to store)
             const int pel = ur / N, pai = ur - pel * N;
             const int64_t dst = s_row[g + pel] * N + pai;
-            a.act_store[dst] = s_act[ur];
-            if (now) a.rew_store[dst] = s_rew[ur];
-            a.term_store[dst] = 0;
-            a.trunc_store[dst] = (uint8_t)s_done[g + pel];
-            if (a.logp_store) a.logp_store[dst] = s_logp[ur];
-            if (a.vs_store) a.vs_store[dst] = s_val[ur];
+            a.b.act_store[dst] = s_act[ur];
+            if (now) a.b.rew_store[dst] = s_rew[ur];
+            a.b.term_store[dst] = 0;
+            a.b.trunc_store[dst] = (uint8_t)s_done[g + pel];
+            if (a.b.logp_store) a.b.logp_store[dst] = s_logp[ur];
+            if (a.b.vs_store) a.b.vs_store[dst] = s_val[ur];
         }
         if constexpr (DEFER) __syncthreads();   // the next forward (or F's) reads the obs_next rows at once
         pending = !now;
         STAMP(5);
         // F. finished episodes: critic value of the terminal observation, then re-initialise the env
         if (any_done) {
-            if (a.vnext_store) {
+            if (a.b.vnext_store) {
                 lyf.X = xnxt;
                 if constexpr (NT2 == 2 * NT) tile_forward_split<H>(lds, lyf, d);
                 else tile_forward<H>(lds, lyf, d);
-                if (lane_live && s_done[g + el]) a.vnext_store[s_row[g + el] * N + ai] = lds[ly.OUT + r * ly.ldo + 16];
+                if (lane_live && s_done[g + el]) a.b.vnext_store[s_row[g + el] * N + ai] = lds[ly.OUT + r * ly.ldo + 16];
             }
             if (a.auto_reset) {
                 if (env_lane && s_done[g + bel]) {
@@ -481,21 +443,10 @@ __global__ __launch_bounds__(NT2) void rollout_kernel(RolloutArgs a) {
     }
     if (env_lane) {
         a.steps[be] = s_steps[bel];
-        vs.ins[be] = v_ins; vs.size[be] = v_size; vs.ep_len[be] = v_eplen; vs.ep_start[be] = v_epstart;
-        vs.last_index[be] = v_last; vs.lengths[be] = v_size;
-        if (a.ep_rec) a.ep_rec[be] = n_fin;  // may exceed max_ep: the host treats that as an overflow
+        vl.store(vs, a.b.ep_rec, be);
     }
-    if (ret_lane) {
-#pragma unroll
-        for (int k = 0; k < kMpeMaxN; ++k) if (k < N) vs.ep_return[(int64_t)(e0 + rq) * N + k] = v_epret[k];
-    }
-    // the last workgroup to get here advances the sampling counter: every workgroup read it (off0) before finishing
-    if (a.done_ctr && threadIdx.x == 0) {
-        if (atomicAdd(a.done_ctr, 1u) == gridDim.x - 1) {
-            *a.offset_dev_rw += a.offset_inc;
-            *a.done_ctr = 0u;
-        }
-    }
+    if (ret_lane) epr.store(vs, N, e0 + rq);
+    rollout_advance_counter(a.b.done_ctr, a.b.offset_dev_rw, a.b.offset_inc, threadIdx.x == 0);   // (every workgroup read it, off0, before finishing)
 }
 
 // ---- wave-autonomous form ------------------------------------------------------------------------------------------------
@@ -573,7 +524,7 @@ __global__ __launch_bounds__(NT) void rollout_wave64_kernel(RolloutArgs a) {
     int64_t *s_row = reinterpret_cast<int64_t *>(wv + wl.ROW);
     uint64_t *s_ep = reinterpret_cast<uint64_t *>(wv + wl.EP);
 
-    const VrbState vs = vrb_view(a.vrb_state, B, N);
+    const VrbState vs = vrb_view(a.b.vrb_state, B, N);
     // agent lane r = lane < rows_here <-> (env el, agent ai) of the wave; env lane 16 + bel owns env bel's bookkeeping
     const int r = lane, el = r / N, ai = r - el * N;
     const bool lane_live = r < rows_here;
@@ -581,16 +532,11 @@ __global__ __launch_bounds__(NT) void rollout_wave64_kernel(RolloutArgs a) {
     const int bel = lane - 16;
     const bool env_lane = bel >= 0 && bel < n_here;
     const int be = e0 + bel;
-    int64_t v_ins = 0, v_size = 0, v_eplen = 0, v_epstart = 0, v_last = 0;
-    int n_fin = 0;
-    double v_epret[kMpeMaxN];
-#pragma unroll
-    for (int k = 0; k < kMpeMaxN; ++k) v_epret[k] = 0.0;
+    VrbLane vl;
+    EpReturns<kMpeMaxN> epr;
     if (env_lane) {
-        v_ins = vs.ins[be]; v_size = vs.size[be]; v_eplen = vs.ep_len[be]; v_epstart = vs.ep_start[be];
-        v_last = vs.last_index[be];
-#pragma unroll
-        for (int k = 0; k < kMpeMaxN; ++k) if (k < N) v_epret[k] = vs.ep_return[(int64_t)be * N + k];
+        vl.load(vs, be);
+        epr.load(vs, N, be);
     }
     float st_ap = 0.f, st_av = 0.f, st_lp = 0.f;   // (the wave's env state: loaded here, stored to LDS behind the barrier)
     if (lane < n_here * st) {
@@ -615,45 +561,14 @@ __global__ __launch_bounds__(NT) void rollout_wave64_kernel(RolloutArgs a) {
 #pragma unroll
     for (int kb = 0; kb < KB1; ++kb) {
         const int k = 4 * kb + kq;
-        int oa = zoff, ob = zoff;
-        if (sn_live && k < D) {
-            const int base = sn_el * st, i_ = sn_ai;
-            if (k < 2) oa = wvo + wl.AV + base + 2 * i_ + k;
-            else if (k < 4) oa = wvo + wl.AP + base + 2 * i_ + (k - 2);
-            else {
-                int kk = k - 4;
-                if (kk < 2 * N) { oa = wvo + wl.LP + base + kk; ob = wvo + wl.AP + base + 2 * i_ + (kk & 1); }
-                else {
-                    kk -= 2 * N;
-                    if (kk < 2 * (N - 1)) {
-                        int jj = kk >> 1;
-                        const int x = kk & 1;
-                        if (jj >= i_) ++jj;  // others in increasing index, skipping self
-                        oa = wvo + wl.AP + base + 2 * jj + x; ob = wvo + wl.AP + base + 2 * i_ + x;
-                    }
-                }
-            }
-        }
-        el_ab[kb] = ((uint32_t)oa << 16) | (uint32_t)ob;
+        const int base = wvo + sn_el * st;
+        el_ab[kb] = sn_live && k < D ? mpe_obs_offsets(N, base + wl.AP, base + wl.AV, base + wl.LP, zoff, sn_ai, k) : mpe_obs_offsets_zero(zoff);
     }
     const int ND = N * D;
     const int obs_col = sn_ai * D + kq;
-    auto obs_frags = [&](float (&x)[KB1]) {
-        float xa[KB1], xs[KB1];
-#pragma unroll
-        for (int kb = 0; kb < KB1; ++kb) { xa[kb] = lds[el_ab[kb] >> 16]; xs[kb] = lds[el_ab[kb] & 0xFFFFu]; }
-#pragma unroll
-        for (int kb = 0; kb < KB1; ++kb) x[kb] = xa[kb] - xs[kb];
-    };
-    const int kb_full = D >> 2, k_rem = D & 3;
-    auto obs_rows_out = [&](float *dst, const float (&x)[KB1]) {
-#pragma unroll
-        for (int kb = 0; kb < KB1; ++kb) {
-            if (kb < kb_full) dst[4 * kb] = x[kb];
-            else if (kb == kb_full && kq < k_rem) dst[4 * kb] = x[kb];
-        }
-    };
     int pair_ei[2];
+    // (mpe_pair_table(N, rows_here, lane, 64, pair_ei), written out: through the helper the three-block instantiation of this kernel,
+    //  which sits at 256 VGPRs + 82 AGPRs, spilled ten vector registers -- tools/resource_usage.py)
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const int rp = (lane + 64 * q) >> 3, ep = rp / N;
@@ -689,8 +604,8 @@ __global__ __launch_bounds__(NT) void rollout_wave64_kernel(RolloutArgs a) {
         return s;
     };
 
-    for (int t = 0; t <= a.n_steps; ++t) {
-        const bool last = t == a.n_steps;  // extra pass: bootstrap value of the final observation only
+    for (int t = 0; t <= a.b.n_steps; ++t) {
+        const bool last = t == a.b.n_steps;  // extra pass: bootstrap value of the final observation only
         // the previous step's row slot / done flag of this lane's env (V(obs_next) of step t - 1 == V(obs) of step t)
         int64_t p_row = 0;
         int p_done = 1;
@@ -702,35 +617,21 @@ __global__ __launch_bounds__(NT) void rollout_wave64_kernel(RolloutArgs a) {
             const int stp = s_steps[bel] + 1;
             tr = stp >= c.max_cycles;
             s_steps[bel] = stp;
-            o = (int64_t)t * B + be;
-            const int64_t cur = v_ins;
-            int64_t sz = v_size + 1; if (sz > a.S) sz = a.S;
-            int64_t nxt = cur + 1; if (nxt >= a.S) nxt -= a.S;
-            const int64_t elen = v_eplen + 1;
-            if (v_epstart > sz) atomicExch((unsigned long long *)vs.error_flag, 1ull);
-            rec = tr && a.ep_rec && n_fin < a.max_ep;
-            // (the record carries CollectStats.lens = len(episode_batch): the episode's rows IN THE BUFFER, collector.py:203,990-993 --
-            //  after a reset_buffer(keep_statistics=True) an episode counts its rows since the reset; ep_len_out stays add()'s ep_len)
-            if (rec) a.ep_rec[B + (int64_t)be * a.max_ep + n_fin] = ((int64_t)t << 32) | ((cur >= v_epstart ? cur - v_epstart : cur - v_epstart + a.S) + 1);
-            a.ep_len_out[o] = tr ? elen : 0;
-            a.ptr_out[o] = cur + (int64_t)be * a.S;
-            a.ep_idx_out[o] = v_epstart + (int64_t)be * a.S;
-            v_ins = nxt; v_size = sz; v_eplen = tr ? 0 : elen; v_epstart = tr ? nxt : v_epstart;
-            v_last = cur + (int64_t)be * a.S;
-            a.done_store[cur * B + be] = tr ? 1 : 0;
-            s_row[bel] = cur * B + be;
+            const VrbStep sp = vl.add(vs, a.b.S, t, be, B, tr, a.b.done_store, a.b.ptr_out, a.b.ep_len_out, a.b.ep_idx_out, a.b.ep_rec, a.b.max_ep);
+            o = sp.o; rec = sp.rec;
+            s_row[bel] = sp.row;
             s_done[bel] = tr ? 1 : 0;
         }
         // ---- B. observation fragments (also the buffer's obs rows), critic value, actor logits ----
         float xb[KB1];
-        obs_frags(xb);
+        wave_obs_frags(lds, el_ab, xb);
         if (last) {
-            if (a.obs_cur_out && sn_live) obs_rows_out(a.obs_cur_out + ((int64_t)e0 * N + c16) * D + kq, xb);
+            if (a.obs_cur_out && sn_live) wave_obs_rows_out(a.obs_cur_out + ((int64_t)e0 * N + c16) * D + kq, xb, D, kq);
         } else if (sn_live) {
-            obs_rows_out(a.obs_store + s_row[sn_el] * ND + obs_col, xb);
+            wave_obs_rows_out(a.b.obs_store + s_row[sn_el] * ND + obs_col, xb, D, kq);
         }
         const float val = critic_value(xb);
-        if (lane_live && !p_done && a.vnext_store) a.vnext_store[p_row * N + ai] = val;
+        if (lane_live && !p_done && a.b.vnext_store) a.b.vnext_store[p_row * N + ai] = val;
         if (last) break;
         {
             wf4 acc[MB];
@@ -786,34 +687,13 @@ __global__ __launch_bounds__(NT) void rollout_wave64_kernel(RolloutArgs a) {
             s_val[lane] = val;
         }
         // ---- D. env step (mpe_dev.h): 16 x 8 pair tasks over the 64 lanes, folded by the agent lanes in partner order ----
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int p = lane + 64 * q, jp = p & 7;
-            float sx = 0.f, sy = 0.f;
-            int ok = 0;
-            if (pair_ei[q] >= 0 && jp < N) {
-                const int ip = pair_ei[q] & 7;
-                const float *ap = s_ap + (pair_ei[q] >> 3) * st;
-                if (jp != ip) ok = mpe_pair_force(c, ap[2 * ip], ap[2 * ip + 1], ap[2 * jp], ap[2 * jp + 1], ip, jp, sx, sy) ? 1 : 0;
-            }
-            s_cx[p] = sx; s_cy[p] = sy; s_cv[p] = ok;
-        }
+        mpe_pair_tasks(c, pair_ei, lane, 64, s_ap, s_cx, s_cy, s_cv);
         if (lane_live) {
             const float px = s_ap[el * st + 2 * ai], py = s_ap[el * st + 2 * ai + 1];
             const float vx = s_av[el * st + 2 * ai], vy = s_av[el * st + 2 * ai + 1];
             float fx = mpe_action_force(c, s_act[r], 0);
             float fy = mpe_action_force(c, s_act[r], 1);
-            {
-                typedef int i4 __attribute__((ext_vector_type(4)));
-                const i4 v0 = *reinterpret_cast<const i4 *>(s_cv + 8 * r), v1 = *reinterpret_cast<const i4 *>(s_cv + 8 * r + 4);
-                const wf4 x0 = *reinterpret_cast<const wf4 *>(s_cx + 8 * r), x1 = *reinterpret_cast<const wf4 *>(s_cx + 8 * r + 4);
-                const wf4 y0 = *reinterpret_cast<const wf4 *>(s_cy + 8 * r), y1 = *reinterpret_cast<const wf4 *>(s_cy + 8 * r + 4);
-#pragma unroll
-                for (int j = 0; j < kMpeMaxN; ++j) {
-                    const int ok = j < 4 ? v0[j & 3] : v1[j & 3];
-                    if (j < N && ok) { fx += j < 4 ? x0[j & 3] : x1[j & 3]; fy += j < 4 ? y0[j & 3] : y1[j & 3]; }
-                }
-            }
+            mpe_pair_fold(c, s_cx, s_cy, s_cv, r, fx, fy);
             float npx, npy, nvx, nvy;
             mpe_integrate(c, px, py, vx, vy, fx, fy, npx, npy, nvx, nvy);
             s_ap[el * st + 2 * ai] = npx; s_ap[el * st + 2 * ai + 1] = npy;
@@ -828,8 +708,8 @@ __global__ __launch_bounds__(NT) void rollout_wave64_kernel(RolloutArgs a) {
         // obs_next fragments (the terminal observation for finished episodes): into the buffer, and kept for F
         float xn[KB1];
         const unsigned long long done_mask = __ballot(lane_live && s_done[el]);
-        if (a.obs_next_store || (done_mask && a.vnext_store)) obs_frags(xn);
-        if (a.obs_next_store && sn_live) obs_rows_out(a.obs_next_store + s_row[sn_el] * ND + obs_col, xn);
+        if (a.b.obs_next_store || (done_mask && a.b.vnext_store)) wave_obs_frags(lds, el_ab, xn);
+        if (a.b.obs_next_store && sn_live) wave_obs_rows_out(a.b.obs_next_store + s_row[sn_el] * ND + obs_col, xn, D, kq);
         if (lane_live) {
             float mv[kMpeMaxN];
 #pragma unroll
@@ -839,35 +719,22 @@ __global__ __launch_bounds__(NT) void rollout_wave64_kernel(RolloutArgs a) {
             for (int l = 0; l < kMpeMaxN; ++l) if (l < N) global -= mv[l];
             s_rew[r] = global * (1.f - c.local_ratio) + local * c.local_ratio;
         }
-        if (env_lane) {  // episode returns
-            double *rec_rew = rec ? reinterpret_cast<double *>(a.ep_rec + B + (int64_t)B * a.max_ep) +
-                                        ((int64_t)be * a.max_ep + n_fin) * N : nullptr;
-#pragma unroll
-            for (int k = 0; k < kMpeMaxN; ++k) {
-                if (k < N) {
-                    const double ac = v_epret[k] + (double)s_rew[bel * N + k];
-                    a.ep_rew_out[o * N + k] = tr ? ac : 0.0;
-                    if (rec) rec_rew[k] = ac;
-                    v_epret[k] = tr ? 0.0 : ac;
-                }
-            }
-            n_fin += tr ? 1 : 0;
-        }
+        if (env_lane) epr.fold(a.b.ep_rew_out, a.b.ep_rec, a.b.max_ep, N, B, be, o, tr, rec, vl.n_fin, s_rew + bel * N);   // episode returns
         // ---- E. payload ----
         if (lane_live) {
             const int64_t dst = s_row[el] * N + ai;
-            a.act_store[dst] = s_act[r];
-            a.rew_store[dst] = s_rew[r];
-            a.term_store[dst] = 0;
-            a.trunc_store[dst] = (uint8_t)s_done[el];
-            if (a.logp_store) a.logp_store[dst] = s_logp[r];
-            if (a.vs_store) a.vs_store[dst] = s_val[r];
+            a.b.act_store[dst] = s_act[r];
+            a.b.rew_store[dst] = s_rew[r];
+            a.b.term_store[dst] = 0;
+            a.b.trunc_store[dst] = (uint8_t)s_done[el];
+            if (a.b.logp_store) a.b.logp_store[dst] = s_logp[r];
+            if (a.b.vs_store) a.b.vs_store[dst] = s_val[r];
         }
         // ---- F. finished episodes: critic value of the terminal observation, then re-initialise the env ----
         if (done_mask) {   // (wave-uniform)
-            if (a.vnext_store) {
+            if (a.b.vnext_store) {
                 const float vt = critic_value(xn);
-                if (lane_live && s_done[el]) a.vnext_store[s_row[el] * N + ai] = vt;
+                if (lane_live && s_done[el]) a.b.vnext_store[s_row[el] * N + ai] = vt;
             }
             if (a.auto_reset) {
                 if (env_lane && s_done[bel]) {
@@ -889,18 +756,10 @@ __global__ __launch_bounds__(NT) void rollout_wave64_kernel(RolloutArgs a) {
     }
     if (env_lane) {
         a.steps[be] = s_steps[bel];
-        vs.ins[be] = v_ins; vs.size[be] = v_size; vs.ep_len[be] = v_eplen; vs.ep_start[be] = v_epstart;
-        vs.last_index[be] = v_last; vs.lengths[be] = v_size;
-        if (a.ep_rec) a.ep_rec[be] = n_fin;  // may exceed max_ep: the host treats that as an overflow
-#pragma unroll
-        for (int k = 0; k < kMpeMaxN; ++k) if (k < N) vs.ep_return[(int64_t)be * N + k] = v_epret[k];
+        vl.store(vs, a.b.ep_rec, be);
+        epr.store(vs, N, be);
     }
-    if (a.done_ctr && tid == 0) {  // the last workgroup advances the sampling counter (every wave has read it: the barrier above)
-        if (atomicAdd(a.done_ctr, 1u) == gridDim.x - 1) {
-            *a.offset_dev_rw += a.offset_inc;
-            *a.done_ctr = 0u;
-        }
-    }
+    rollout_advance_counter(a.b.done_ctr, a.b.offset_dev_rw, a.b.offset_inc, tid == 0);   // (every wave has read it: the barrier above)
 }
 
 __global__ void u64_add_kernel(uint64_t *p, uint64_t inc) { *p += inc; }
@@ -925,26 +784,14 @@ TSM_EXPORT int tsm_rollout_spread(const tsm_rollout_desc *desc_host, void *strea
     TSM_REQUIRE(a.c.N <= R, "tsm_rollout_spread: n_agent exceeds the row tile");
     TSM_REQUIRE(h.n_steps >= 1 && h.sub_size >= 1, "tsm_rollout_spread: bad n_steps / sub_size");
     TSM_REQUIRE(h.mode == 1 || h.mode == 2, "tsm_rollout_spread: mode must be 1 (sample) or 2 (argmax)");
-    TSM_REQUIRE((h.params || h.param_image) && h.episode_ctr && h.agent_pos && h.agent_vel && h.landmark_pos &&
-                    h.steps && h.vrb_state && h.done_store && h.obs_store && h.act_store && h.rew_store &&
-                    h.term_store && h.trunc_store && h.ptr_out && h.ep_rew_out && h.ep_len_out && h.ep_idx_out,
+    TSM_REQUIRE((h.params || h.param_image) && h.episode_ctr && h.agent_pos && h.agent_vel && h.landmark_pos && h.steps,
                 "tsm_rollout_spread: null pointer");
+    if (int rc = rollout_buf_args(h, "tsm_rollout_spread", &a.b)) return rc;
     a.P = h.params; a.img = h.param_image;
     a.pol_seed = h.policy_seed; a.offset = h.offset; a.offset_dev = h.offset_dev; a.mode = h.mode;
     a.env_seed = h.env_seed; a.episode_ctr = h.episode_ctr;
     a.apos = h.agent_pos; a.avel = h.agent_vel; a.lpos = h.landmark_pos; a.steps = h.steps;
     a.auto_reset = h.auto_reset; a.obs_cur_out = h.obs_cur_out;
-    a.vrb_state = h.vrb_state; a.S = h.sub_size; a.done_store = h.done_store;
-    a.obs_store = h.obs_store; a.obs_next_store = h.obs_next_store; a.rew_store = h.rew_store;
-    a.logp_store = h.logp_store; a.vs_store = h.vs_store; a.vnext_store = h.vnext_store;
-    a.act_store = h.act_store; a.term_store = h.term_store; a.trunc_store = h.trunc_store;
-    a.ptr_out = h.ptr_out; a.ep_len_out = h.ep_len_out; a.ep_idx_out = h.ep_idx_out; a.ep_rew_out = h.ep_rew_out;
-    a.n_steps = h.n_steps;
-    TSM_REQUIRE(!h.ep_rec || h.max_ep >= 1, "tsm_rollout_spread: ep_rec needs max_ep >= 1");
-    a.ep_rec = h.ep_rec; a.max_ep = h.max_ep;
-    TSM_REQUIRE(!h.done_ctr || h.offset_dev, "tsm_rollout_spread: done_ctr needs offset_dev");
-    a.offset_inc = h.offset_inc; a.done_ctr = h.done_ctr;
-    a.offset_dev_rw = const_cast<uint64_t *>(reinterpret_cast<const uint64_t *>(h.offset_dev));
     a.stamps = g_tsm_stamps;
     const Lay<64> ly(a.d, false);
     {   // Which form (option "rollout_form": 0 by rule, 1 tile, 2 wave).  Rule: the tile form while its workgroups (one 16-row tile
@@ -991,8 +838,7 @@ TSM_EXPORT int tsm_rollout_spread(const tsm_rollout_desc *desc_host, void *strea
             return TSM_OK;
         }
     }
-    const size_t extra = (size_t)R * a.d.ld1 + 3 * R * 2 + 4 * R + 4 * R + 3 * 2 * R + 8 + 3 * R * 8 + 4 + 3 * R + 2 * R + 4;
-    const size_t shmem = ((size_t)ly.total + extra) * sizeof(float);
+    const size_t shmem = (size_t)RtLay(ly.total, a.d.ld1).total * sizeof(float);
     static bool attr_set = false;
     if (!attr_set) {
         TSM_HIP(tsm_allow_max_lds(reinterpret_cast<const void *>(rollout_kernel<64, NT>)));

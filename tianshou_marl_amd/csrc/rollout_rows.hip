@@ -18,7 +18,7 @@
 #include "common.h"
 #include "mpe_dev.h"
 #include "philox.h"
-#include "vrb_dev.h"
+#include "rollout_dev.h"
 #include "wave_mlp.h"
 
 int tsm_mpe_check_cfg(const tsm_mpe_cfg *h, MpeCfg *c);  // mpe.hip
@@ -76,20 +76,7 @@ struct RrArgs {
     int32_t *steps;
     int auto_reset;
     float *obs_cur_out;
-    void *vrb_state;
-    int64_t S;
-    uint8_t *done_store;
-    float *obs_store, *obs_next_store, *rew_store, *logp_store;
-    int32_t *act_store;
-    uint8_t *term_store, *trunc_store;
-    int64_t *ptr_out, *ep_len_out, *ep_idx_out;
-    double *ep_rew_out;
-    int n_steps;
-    int64_t *ep_rec;
-    int max_ep;
-    uint64_t offset_inc;
-    uint64_t *offset_dev_rw;
-    uint32_t *done_ctr;
+    RolloutBufArgs b;   // buffer, per-step outputs, episode record, counter advance (vs_store / vnext_store: not written here)
     long long *stamps;  // diagnostics only (tsm_debug_set_stamps): phase time stamps of workgroup 0, steps 0..3
 };
 
@@ -126,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void rollout_rows_kernel(RrArgs a) {
     if (tid < 16) lds[ly.B3 + tid] = tid < A ? a.P[oB3 + tid] : 0.f;
     for (int i = tid; i < kTile * ld1; i += kThreads) lds[ly.X + i] = 0.f;
 
-    const VrbState vs = vrb_view(a.vrb_state, B, N);
+    const VrbState vs = vrb_view(a.b.vrb_state, B, N);
     // agent lane r (threads 0..127) <-> (env el, agent ai); env lane (threads 128..128+EPB) owns env bel's bookkeeping
     const int r = tid, el = r / N, ai = r - el * N;
     const bool lane_live = r < rows_here;
@@ -134,16 +121,11 @@ __global__ __launch_bounds__(kThreads) void rollout_rows_kernel(RrArgs a) {
     const int bel = tid - kRowsWg;
     const bool env_lane = bel >= 0 && bel < n_here;
     const int be = e0 + bel;
-    int64_t v_ins = 0, v_size = 0, v_eplen = 0, v_epstart = 0, v_last = 0;
-    int n_fin = 0;
-    double v_epret[kMpeMaxN];
-#pragma unroll
-    for (int k = 0; k < kMpeMaxN; ++k) v_epret[k] = 0.0;
+    VrbLane vl;
+    EpReturns<kMpeMaxN> epr;
     if (env_lane) {
-        v_ins = vs.ins[be]; v_size = vs.size[be]; v_eplen = vs.ep_len[be]; v_epstart = vs.ep_start[be];
-        v_last = vs.last_index[be];
-#pragma unroll
-        for (int k = 0; k < kMpeMaxN; ++k) if (k < N) v_epret[k] = vs.ep_return[(int64_t)be * N + k];
+        vl.load(vs, be);
+        epr.load(vs, N, be);
         s_steps[bel] = a.steps[be];
         s_done[bel] = 0;
         s_row[bel] = 0;
@@ -167,28 +149,13 @@ __global__ __launch_bounds__(kThreads) void rollout_rows_kernel(RrArgs a) {
 #pragma unroll
     for (int q = 0; q < kEl; ++q) {
         const int e_ = tid + kThreads * q;
-        int oa = zoff, ob = zoff;
-        uint32_t rk = 0xFFFFFFFFu;
+        uint32_t ab = mpe_obs_offsets_zero(zoff), rk = 0xFFFFFFFFu;
         if (e_ < rows_here * D) {
             const int rr = e_ / D, k = e_ - rr * D, ee = rr / N, i_ = rr - ee * N, base = ee * st;
-            if (k < 2) oa = ly.AV + base + 2 * i_ + k;
-            else if (k < 4) oa = ly.AP + base + 2 * i_ + (k - 2);
-            else {
-                int kk = k - 4;
-                if (kk < 2 * N) { oa = ly.LP + base + kk; ob = ly.AP + base + 2 * i_ + (kk & 1); }
-                else {
-                    kk -= 2 * N;
-                    if (kk < 2 * (N - 1)) {
-                        int jj = kk >> 1;
-                        const int x = kk & 1;
-                        if (jj >= i_) ++jj;  // others in increasing index, skipping self
-                        oa = ly.AP + base + 2 * jj + x; ob = ly.AP + base + 2 * i_ + x;
-                    }
-                }
-            }
+            ab = mpe_obs_offsets(N, ly.AP + base, ly.AV + base, ly.LP + base, zoff, i_, k);
             rk = ((uint32_t)ee << 24) | ((uint32_t)rr << 16) | ((uint32_t)i_ << 8) | (uint32_t)k;
         }
-        el_ab[q] = ((uint32_t)oa << 16) | (uint32_t)ob;
+        el_ab[q] = ab;
         el_rk[q] = rk;
     }
     auto obs_val = [&](int q) { return lds[el_ab[q] >> 16] - lds[el_ab[q] & 0xFFFFu]; };
@@ -203,17 +170,13 @@ __global__ __launch_bounds__(kThreads) void rollout_rows_kernel(RrArgs a) {
     };
     // the pair (agent lane, other agent) tasks of the env step: task p = tid + 512 q -> agent lane p >> 3, other p & 7
     int pair_ei[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int rp = (tid + kThreads * q) >> 3, ep = rp / N;
-        pair_ei[q] = rp < rows_here ? (ep << 3) | (rp - ep * N) : -1;
-    }
+    mpe_pair_table(N, rows_here, tid, kThreads, pair_ei);
     float *s_cx = lds + ly.H1, *s_cy = s_cx + 8 * kRowsWg;           // [128][8] pair forces (H1 is idle during the env step)
     int *s_cv = reinterpret_cast<int *>(s_cy + 8 * kRowsWg);         // [128][8] 1 = the pair is in contact range
     const int ND = N * D;
     __syncthreads();
 
-    for (int t = 0; t < a.n_steps; ++t) {
+    for (int t = 0; t < a.b.n_steps; ++t) {
         // ---- A. buffer index algebra of this step on the env lanes (buffer_base.py:373-410 + manager.py:170-177; same
         //         arithmetic as vrb_add_row): the slot of the row is known before the payload exists ----
         RSTAMP(0);
@@ -223,23 +186,9 @@ __global__ __launch_bounds__(kThreads) void rollout_rows_kernel(RrArgs a) {
             const int stp = s_steps[bel] + 1;
             tr = stp >= c.max_cycles;
             s_steps[bel] = stp;
-            o = (int64_t)t * B + be;
-            const int64_t cur = v_ins;
-            int64_t sz = v_size + 1; if (sz > a.S) sz = a.S;
-            int64_t nxt = cur + 1; if (nxt >= a.S) nxt -= a.S;
-            const int64_t elen = v_eplen + 1;
-            if (v_epstart > sz) atomicExch((unsigned long long *)vs.error_flag, 1ull);
-            rec = tr && a.ep_rec && n_fin < a.max_ep;
-            // (the record carries CollectStats.lens = len(episode_batch): the episode's rows IN THE BUFFER, collector.py:203,990-993 --
-            //  after a reset_buffer(keep_statistics=True) an episode counts its rows since the reset; ep_len_out stays add()'s ep_len)
-            if (rec) a.ep_rec[B + (int64_t)be * a.max_ep + n_fin] = ((int64_t)t << 32) | ((cur >= v_epstart ? cur - v_epstart : cur - v_epstart + a.S) + 1);
-            a.ep_len_out[o] = tr ? elen : 0;
-            a.ptr_out[o] = cur + (int64_t)be * a.S;
-            a.ep_idx_out[o] = v_epstart + (int64_t)be * a.S;
-            v_ins = nxt; v_size = sz; v_eplen = tr ? 0 : elen; v_epstart = tr ? nxt : v_epstart;
-            v_last = cur + (int64_t)be * a.S;
-            a.done_store[cur * B + be] = tr ? 1 : 0;
-            s_row[bel] = cur * B + be;
+            const VrbStep sp = vl.add(vs, a.b.S, t, be, B, tr, a.b.done_store, a.b.ptr_out, a.b.ep_len_out, a.b.ep_idx_out, a.b.ep_rec, a.b.max_ep);
+            o = sp.o; rec = sp.rec;
+            s_row[bel] = sp.row;
             s_done[bel] = tr ? 1 : 0;
         }
         __syncthreads();
@@ -253,7 +202,7 @@ __global__ __launch_bounds__(kThreads) void rollout_rows_kernel(RrArgs a) {
             const uint32_t rk = el_rk[q];
             if (rk != 0xFFFFFFFFu) {
                 const float v = obs_val(q);
-                a.obs_store[s_row[rk >> 24] * ND + (int)((rk >> 8) & 0xFF) * D + (int)(rk & 0xFF)] = v;
+                a.b.obs_store[s_row[rk >> 24] * ND + (int)((rk >> 8) & 0xFF) * D + (int)(rk & 0xFF)] = v;
                 const int rr = (rk >> 16) & 0xFF;
                 if (rr < kTile) lds[ly.X + rr * ld1 + (int)(rk & 0xFF)] = v;
             }
@@ -348,18 +297,7 @@ __global__ __launch_bounds__(kThreads) void rollout_rows_kernel(RrArgs a) {
         // ---- C. env step (mpe_dev.h).  The soft contact forces -- sqrt / exp / log1p per pair in range, ~6 us when every
         //         agent lane walks its N - 1 partners -- are evaluated as 128 x 8 pair tasks over all 512 threads and
         //         folded by the agent lanes in partner order: the same additions in the same order as mpe_agent_move ----
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int p = tid + kThreads * q, jp = p & 7;
-            float sx = 0.f, sy = 0.f;
-            int ok = 0;
-            if (pair_ei[q] >= 0 && jp < N) {
-                const int ip = pair_ei[q] & 7;
-                const float *ap = s_ap + (pair_ei[q] >> 3) * st;
-                if (jp != ip) ok = mpe_pair_force(c, ap[2 * ip], ap[2 * ip + 1], ap[2 * jp], ap[2 * jp + 1], ip, jp, sx, sy) ? 1 : 0;
-            }
-            s_cx[p] = sx; s_cy[p] = sy; s_cv[p] = ok;
-        }
+        mpe_pair_tasks(c, pair_ei, tid, kThreads, s_ap, s_cx, s_cy, s_cv);
         __syncthreads();
         RSTAMP(15);
         RSTAMP(16);
@@ -388,12 +326,12 @@ __global__ __launch_bounds__(kThreads) void rollout_rows_kernel(RrArgs a) {
             local = mpe_local_penalty(c, pos, s_ap + el * st, ai);
         }
         // obs_next rows (the terminal observation for finished episodes) straight into the buffer
-        if (a.obs_next_store) {
+        if (a.b.obs_next_store) {
 #pragma unroll
             for (int q = 0; q < kEl; ++q) {
                 const uint32_t rk = el_rk[q];
                 if (rk != 0xFFFFFFFFu)
-                    a.obs_next_store[s_row[rk >> 24] * ND + (int)((rk >> 8) & 0xFF) * D + (int)(rk & 0xFF)] = obs_val(q);
+                    a.b.obs_next_store[s_row[rk >> 24] * ND + (int)((rk >> 8) & 0xFF) * D + (int)(rk & 0xFF)] = obs_val(q);
             }
         }
         __syncthreads();
@@ -401,27 +339,14 @@ __global__ __launch_bounds__(kThreads) void rollout_rows_kernel(RrArgs a) {
         if (lane_live) s_rew[r] = mpe_reward(c, s_m + el * N, local);
         __syncthreads();
         RSTAMP(19);
-        if (env_lane) {  // episode returns
-            double *rec_rew = rec ? reinterpret_cast<double *>(a.ep_rec + B + (int64_t)B * a.max_ep) +
-                                        ((int64_t)be * a.max_ep + n_fin) * N : nullptr;
-#pragma unroll
-            for (int k = 0; k < kMpeMaxN; ++k) {
-                if (k < N) {
-                    const double acc = v_epret[k] + (double)s_rew[bel * N + k];
-                    a.ep_rew_out[o * N + k] = tr ? acc : 0.0;
-                    if (rec) rec_rew[k] = acc;
-                    v_epret[k] = tr ? 0.0 : acc;
-                }
-            }
-            n_fin += tr ? 1 : 0;
-        }
+        if (env_lane) epr.fold(a.b.ep_rew_out, a.b.ep_rec, a.b.max_ep, N, B, be, o, tr, rec, vl.n_fin, s_rew + bel * N);   // episode returns
         if (lane_live) {
             const int64_t dst = s_row[el] * N + ai;
-            a.act_store[dst] = s_act[r];
-            a.rew_store[dst] = s_rew[r];
-            a.term_store[dst] = 0;
-            a.trunc_store[dst] = (uint8_t)s_done[el];
-            if (a.logp_store) a.logp_store[dst] = s_logp[r];
+            a.b.act_store[dst] = s_act[r];
+            a.b.rew_store[dst] = s_rew[r];
+            a.b.term_store[dst] = 0;
+            a.b.trunc_store[dst] = (uint8_t)s_done[el];
+            if (a.b.logp_store) a.b.logp_store[dst] = s_logp[r];
         }
         RSTAMP(20);
         // ---- D. finished episodes: re-initialise the env (the next step's observation rows see the new state) ----
@@ -455,18 +380,10 @@ __global__ __launch_bounds__(kThreads) void rollout_rows_kernel(RrArgs a) {
     }
     if (env_lane) {
         a.steps[be] = s_steps[bel];
-        vs.ins[be] = v_ins; vs.size[be] = v_size; vs.ep_len[be] = v_eplen; vs.ep_start[be] = v_epstart;
-        vs.last_index[be] = v_last; vs.lengths[be] = v_size;
-        if (a.ep_rec) a.ep_rec[be] = n_fin;
-#pragma unroll
-        for (int k = 0; k < kMpeMaxN; ++k) if (k < N) vs.ep_return[(int64_t)be * N + k] = v_epret[k];
+        vl.store(vs, a.b.ep_rec, be);
+        epr.store(vs, N, be);
     }
-    if (a.done_ctr && tid == 0) {  // the last workgroup advances the sampling counter (every one has read it)
-        if (atomicAdd(a.done_ctr, 1u) == gridDim.x - 1) {
-            *a.offset_dev_rw += a.offset_inc;
-            *a.done_ctr = 0u;
-        }
-    }
+    rollout_advance_counter(a.b.done_ctr, a.b.offset_dev_rw, a.b.offset_inc, tid == 0);   // (every workgroup has read it)
 }
 
 
@@ -558,7 +475,7 @@ __global__ __launch_bounds__(kThreads) void rollout_wave_kernel(RrArgs a) {
     if (tid < kH) { lds[ly.B1 + tid] = a.P[oB1 + tid]; lds[ly.B2 + tid] = a.P[oB2 + tid]; }
     if (tid < 16) lds[ly.B3 + tid] = tid < A ? a.P[oB3 + tid] : 0.f;
 
-    const VrbState vs = vrb_view(a.vrb_state, B, N);
+    const VrbState vs = vrb_view(a.b.vrb_state, B, N);
     // agent lane r = lane < rows_here <-> (env el, agent ai) of the wave; env lane 16 + bel owns env bel's bookkeeping
     const int r = lane, el = r / N, ai = r - el * N;
     const bool lane_live = r < rows_here;
@@ -566,16 +483,11 @@ __global__ __launch_bounds__(kThreads) void rollout_wave_kernel(RrArgs a) {
     const int bel = lane - 16;
     const bool env_lane = bel >= 0 && bel < n_here;
     const int be = e0 + bel;
-    int64_t v_ins = 0, v_size = 0, v_eplen = 0, v_epstart = 0, v_last = 0;
-    int n_fin = 0;
-    double v_epret[kMpeMaxN];
-#pragma unroll
-    for (int k = 0; k < kMpeMaxN; ++k) v_epret[k] = 0.0;
+    VrbLane vl;
+    EpReturns<kMpeMaxN> epr;
     if (env_lane) {
-        v_ins = vs.ins[be]; v_size = vs.size[be]; v_eplen = vs.ep_len[be]; v_epstart = vs.ep_start[be];
-        v_last = vs.last_index[be];
-#pragma unroll
-        for (int k = 0; k < kMpeMaxN; ++k) if (k < N) v_epret[k] = vs.ep_return[(int64_t)be * N + k];
+        vl.load(vs, be);
+        epr.load(vs, N, be);
         s_steps[bel] = a.steps[be];
         s_done[bel] = 0;
         s_row[bel] = 0;
@@ -599,58 +511,18 @@ __global__ __launch_bounds__(kThreads) void rollout_wave_kernel(RrArgs a) {
 #pragma unroll
     for (int kb = 0; kb < KB1; ++kb) {
         const int k = 4 * kb + kq;
-        int oa = zoff, ob = zoff;
-        if (sn_live && k < D) {
-            const int base = sn_el * st, i_ = sn_ai;
-            if (k < 2) oa = wvo + ly.AV + base + 2 * i_ + k;
-            else if (k < 4) oa = wvo + ly.AP + base + 2 * i_ + (k - 2);
-            else {
-                int kk = k - 4;
-                if (kk < 2 * N) { oa = wvo + ly.LP + base + kk; ob = wvo + ly.AP + base + 2 * i_ + (kk & 1); }
-                else {
-                    kk -= 2 * N;
-                    if (kk < 2 * (N - 1)) {
-                        int jj = kk >> 1;
-                        const int x = kk & 1;
-                        if (jj >= i_) ++jj;  // others in increasing index, skipping self
-                        oa = wvo + ly.AP + base + 2 * jj + x; ob = wvo + ly.AP + base + 2 * i_ + x;
-                    }
-                }
-            }
-        }
-        el_ab[kb] = ((uint32_t)oa << 16) | (uint32_t)ob;
+        const int base = wvo + sn_el * st;
+        el_ab[kb] = sn_live && k < D ? mpe_obs_offsets(N, base + ly.AP, base + ly.AV, base + ly.LP, zoff, sn_ai, k) : mpe_obs_offsets_zero(zoff);
     }
     const int ND = N * D;
     const int obs_col = sn_ai * D + kq;   // + 4 kb: the element's place inside its env's row block
-    // all 2 x KB1 LDS reads in flight, then the subtractions (written as one loop the reads are waited for pair by pair)
-    auto obs_frags = [&](float (&x)[KB1]) {
-        float xa[KB1], xs[KB1];
-#pragma unroll
-        for (int kb = 0; kb < KB1; ++kb) { xa[kb] = lds[el_ab[kb] >> 16]; xs[kb] = lds[el_ab[kb] & 0xFFFFu]; }
-#pragma unroll
-        for (int kb = 0; kb < KB1; ++kb) x[kb] = xa[kb] - xs[kb];
-    };
-    // elements k = 4 kb + kq < D of the lane's sample to row memory: whole k-steps under a wave-uniform test, the one
-    // partial k-step of an odd agent count (D = 6 N, D & 3 == 2) under a lane test
-    const int kb_full = D >> 2, k_rem = D & 3;
-    auto obs_rows_out = [&](float *dst, const float (&x)[KB1]) {
-#pragma unroll
-        for (int kb = 0; kb < KB1; ++kb) {
-            if (kb < kb_full) dst[4 * kb] = x[kb];
-            else if (kb == kb_full && kq < k_rem) dst[4 * kb] = x[kb];
-        }
-    };
     // the pair (agent row, other agent) tasks of the env step: task p = lane + 64 q -> agent row p >> 3, other p & 7
     int pair_ei[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int rp = (lane + 64 * q) >> 3, ep = rp / N;
-        pair_ei[q] = rp < rows_here ? (ep << 3) | (rp - ep * N) : -1;
-    }
+    mpe_pair_table(N, rows_here, lane, 64, pair_ei);
     const float *w1f = lds + ly.W1 + c16 * ld1 + kq, *w2f = lds + ly.W2 + c16 * kLdh + kq, *w3f = lds + ly.W3 + c16 * kLdh + kq;
     __syncthreads();   // weights staged; every wave has read the sampling counter.  The only workgroup barrier.
     if (n_here == 0) return;  // a wave without environments (never wave 0, whose thread 0 updates the counter below)
-    for (int t = 0; t < a.n_steps; ++t) {
+    for (int t = 0; t < a.b.n_steps; ++t) {
         // ---- A. buffer index algebra of this step on the env lanes (as in the tile form) ----
         WSTAMP(0);
         bool tr = false, rec = false;
@@ -659,29 +531,15 @@ __global__ __launch_bounds__(kThreads) void rollout_wave_kernel(RrArgs a) {
             const int stp = s_steps[bel] + 1;
             tr = stp >= c.max_cycles;
             s_steps[bel] = stp;
-            o = (int64_t)t * B + be;
-            const int64_t cur = v_ins;
-            int64_t sz = v_size + 1; if (sz > a.S) sz = a.S;
-            int64_t nxt = cur + 1; if (nxt >= a.S) nxt -= a.S;
-            const int64_t elen = v_eplen + 1;
-            if (v_epstart > sz) atomicExch((unsigned long long *)vs.error_flag, 1ull);
-            rec = tr && a.ep_rec && n_fin < a.max_ep;
-            // (the record carries CollectStats.lens = len(episode_batch): the episode's rows IN THE BUFFER, collector.py:203,990-993 --
-            //  after a reset_buffer(keep_statistics=True) an episode counts its rows since the reset; ep_len_out stays add()'s ep_len)
-            if (rec) a.ep_rec[B + (int64_t)be * a.max_ep + n_fin] = ((int64_t)t << 32) | ((cur >= v_epstart ? cur - v_epstart : cur - v_epstart + a.S) + 1);
-            a.ep_len_out[o] = tr ? elen : 0;
-            a.ptr_out[o] = cur + (int64_t)be * a.S;
-            a.ep_idx_out[o] = v_epstart + (int64_t)be * a.S;
-            v_ins = nxt; v_size = sz; v_eplen = tr ? 0 : elen; v_epstart = tr ? nxt : v_epstart;
-            v_last = cur + (int64_t)be * a.S;
-            a.done_store[cur * B + be] = tr ? 1 : 0;
-            s_row[bel] = cur * B + be;
+            const VrbStep sp = vl.add(vs, a.b.S, t, be, B, tr, a.b.done_store, a.b.ptr_out, a.b.ep_len_out, a.b.ep_idx_out, a.b.ep_rec, a.b.max_ep);
+            o = sp.o; rec = sp.rec;
+            s_row[bel] = sp.row;
             s_done[bel] = tr ? 1 : 0;
         }
         // ---- B. observation fragments (also the buffer's obs rows), the actor forward, the Categorical heads ----
         float xb[KB1];
-        obs_frags(xb);
-        if (sn_live) obs_rows_out(a.obs_store + s_row[sn_el] * ND + obs_col, xb);
+        wave_obs_frags(lds, el_ab, xb);
+        if (sn_live) wave_obs_rows_out(a.b.obs_store + s_row[sn_el] * ND + obs_col, xb, D, kq);
         WSTAMP(1);
         f4 acc[8];
         float hb[32];
@@ -740,35 +598,14 @@ __global__ __launch_bounds__(kThreads) void rollout_wave_kernel(RrArgs a) {
         }
         WSTAMP(5);
         // ---- C. env step (mpe_dev.h): 16 x 8 pair tasks over the 64 lanes, folded by the agent lanes in partner order ----
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int p = lane + 64 * q, jp = p & 7;
-            float sx = 0.f, sy = 0.f;
-            int ok = 0;
-            if (pair_ei[q] >= 0 && jp < N) {
-                const int ip = pair_ei[q] & 7;
-                const float *ap = s_ap + (pair_ei[q] >> 3) * st;
-                if (jp != ip) ok = mpe_pair_force(c, ap[2 * ip], ap[2 * ip + 1], ap[2 * jp], ap[2 * jp + 1], ip, jp, sx, sy) ? 1 : 0;
-            }
-            s_cx[p] = sx; s_cy[p] = sy; s_cv[p] = ok;
-        }
+        mpe_pair_tasks(c, pair_ei, lane, 64, s_ap, s_cx, s_cy, s_cv);
         WSTAMP(6);
         if (lane_live) {
             const float px = s_ap[el * st + 2 * ai], py = s_ap[el * st + 2 * ai + 1];
             const float vx = s_av[el * st + 2 * ai], vy = s_av[el * st + 2 * ai + 1];
             float fx = mpe_action_force(c, s_act[r], 0);
             float fy = mpe_action_force(c, s_act[r], 1);
-            {   // the row's 8 pair terms in six 16-byte reads, folded in partner order
-                typedef int i4 __attribute__((ext_vector_type(4)));
-                const i4 v0 = *reinterpret_cast<const i4 *>(s_cv + 8 * r), v1 = *reinterpret_cast<const i4 *>(s_cv + 8 * r + 4);
-                const f4 x0 = *reinterpret_cast<const f4 *>(s_cx + 8 * r), x1 = *reinterpret_cast<const f4 *>(s_cx + 8 * r + 4);
-                const f4 y0 = *reinterpret_cast<const f4 *>(s_cy + 8 * r), y1 = *reinterpret_cast<const f4 *>(s_cy + 8 * r + 4);
-#pragma unroll
-                for (int j = 0; j < kMpeMaxN; ++j) {
-                    const int ok = j < 4 ? v0[j & 3] : v1[j & 3];
-                    if (j < N && ok) { fx += j < 4 ? x0[j & 3] : x1[j & 3]; fy += j < 4 ? y0[j & 3] : y1[j & 3]; }
-                }
-            }
+            mpe_pair_fold(c, s_cx, s_cy, s_cv, r, fx, fy);
             float npx, npy, nvx, nvy;
             mpe_integrate(c, px, py, vx, vy, fx, fy, npx, npy, nvx, nvy);
             s_ap[el * st + 2 * ai] = npx; s_ap[el * st + 2 * ai + 1] = npy;
@@ -782,10 +619,10 @@ __global__ __launch_bounds__(kThreads) void rollout_wave_kernel(RrArgs a) {
             local = mpe_local_penalty(c, pos, s_ap + el * st, ai);
         }
         // obs_next rows (the terminal observation for finished episodes) straight into the buffer
-        if (a.obs_next_store) {
+        if (a.b.obs_next_store) {
             float xn[KB1];
-            obs_frags(xn);
-            if (sn_live) obs_rows_out(a.obs_next_store + s_row[sn_el] * ND + obs_col, xn);
+            wave_obs_frags(lds, el_ab, xn);
+            if (sn_live) wave_obs_rows_out(a.b.obs_next_store + s_row[sn_el] * ND + obs_col, xn, D, kq);
         }
         if (lane_live) {   // mpe_reward's fold in landmark order, the N minima read back to back
             float mv[kMpeMaxN];
@@ -797,27 +634,14 @@ __global__ __launch_bounds__(kThreads) void rollout_wave_kernel(RrArgs a) {
             s_rew[r] = global * (1.f - c.local_ratio) + local * c.local_ratio;
         }
         WSTAMP(8);
-        if (env_lane) {  // episode returns
-            double *rec_rew = rec ? reinterpret_cast<double *>(a.ep_rec + B + (int64_t)B * a.max_ep) +
-                                        ((int64_t)be * a.max_ep + n_fin) * N : nullptr;
-#pragma unroll
-            for (int k = 0; k < kMpeMaxN; ++k) {
-                if (k < N) {
-                    const double ac = v_epret[k] + (double)s_rew[bel * N + k];
-                    a.ep_rew_out[o * N + k] = tr ? ac : 0.0;
-                    if (rec) rec_rew[k] = ac;
-                    v_epret[k] = tr ? 0.0 : ac;
-                }
-            }
-            n_fin += tr ? 1 : 0;
-        }
+        if (env_lane) epr.fold(a.b.ep_rew_out, a.b.ep_rec, a.b.max_ep, N, B, be, o, tr, rec, vl.n_fin, s_rew + bel * N);   // episode returns
         if (lane_live) {
             const int64_t dst = s_row[el] * N + ai;
-            a.act_store[dst] = s_act[r];
-            a.rew_store[dst] = s_rew[r];
-            a.term_store[dst] = 0;
-            a.trunc_store[dst] = (uint8_t)s_done[el];
-            if (a.logp_store) a.logp_store[dst] = s_logp[r];
+            a.b.act_store[dst] = s_act[r];
+            a.b.rew_store[dst] = s_rew[r];
+            a.b.term_store[dst] = 0;
+            a.b.trunc_store[dst] = (uint8_t)s_done[el];
+            if (a.b.logp_store) a.b.logp_store[dst] = s_logp[r];
         }
         // ---- D. finished episodes: re-initialise the env (the next step's observation fragments see the new state) ----
         if (a.auto_reset) {
@@ -835,8 +659,8 @@ __global__ __launch_bounds__(kThreads) void rollout_wave_kernel(RrArgs a) {
     // the observation of the next collect() call, env state and sub-buffer bookkeeping back to HBM
     if (a.obs_cur_out) {
         float xn[KB1];
-        obs_frags(xn);
-        if (sn_live) obs_rows_out(a.obs_cur_out + ((int64_t)e0 * N + c16) * D + kq, xn);
+        wave_obs_frags(lds, el_ab, xn);
+        if (sn_live) wave_obs_rows_out(a.obs_cur_out + ((int64_t)e0 * N + c16) * D + kq, xn, D, kq);
     }
     if (lane < n_here * st) {
         a.apos[(int64_t)e0 * st + lane] = s_ap[lane];
@@ -845,18 +669,10 @@ __global__ __launch_bounds__(kThreads) void rollout_wave_kernel(RrArgs a) {
     }
     if (env_lane) {
         a.steps[be] = s_steps[bel];
-        vs.ins[be] = v_ins; vs.size[be] = v_size; vs.ep_len[be] = v_eplen; vs.ep_start[be] = v_epstart;
-        vs.last_index[be] = v_last; vs.lengths[be] = v_size;
-        if (a.ep_rec) a.ep_rec[be] = n_fin;
-#pragma unroll
-        for (int k = 0; k < kMpeMaxN; ++k) if (k < N) vs.ep_return[(int64_t)be * N + k] = v_epret[k];
+        vl.store(vs, a.b.ep_rec, be);
+        epr.store(vs, N, be);
     }
-    if (a.done_ctr && tid == 0) {  // the last workgroup advances the sampling counter (every wave has read it: the barrier above)
-        if (atomicAdd(a.done_ctr, 1u) == gridDim.x - 1) {
-            *a.offset_dev_rw += a.offset_inc;
-            *a.done_ctr = 0u;
-        }
-    }
+    rollout_advance_counter(a.b.done_ctr, a.b.offset_dev_rw, a.b.offset_inc, tid == 0);   // (every wave has read it: the barrier above)
 }
 
 }  // namespace
@@ -876,24 +692,15 @@ TSM_EXPORT int tsm_rollout_spread_actor(const tsm_rollout_desc *desc_host, void 
     TSM_REQUIRE(a.c.N >= 1 && a.c.N <= kMpeMaxN, "tsm_rollout_spread_actor: n_agent out of range");
     TSM_REQUIRE(h.n_steps >= 1 && h.sub_size >= 1, "tsm_rollout_spread_actor: bad n_steps / sub_size");
     TSM_REQUIRE(h.mode == 1 || h.mode == 2, "tsm_rollout_spread_actor: mode must be 1 (sample) or 2 (argmax)");
-    TSM_REQUIRE(h.params && h.episode_ctr && h.agent_pos && h.agent_vel && h.landmark_pos && h.steps && h.vrb_state &&
-                    h.done_store && h.obs_store && h.act_store && h.rew_store && h.term_store && h.trunc_store && h.ptr_out &&
-                    h.ep_rew_out && h.ep_len_out && h.ep_idx_out,
+    TSM_REQUIRE(h.params && h.episode_ctr && h.agent_pos && h.agent_vel && h.landmark_pos && h.steps,
                 "tsm_rollout_spread_actor: null pointer");
-    TSM_REQUIRE(!h.ep_rec || h.max_ep >= 1, "tsm_rollout_spread_actor: ep_rec needs max_ep >= 1");
-    TSM_REQUIRE(!h.done_ctr || h.offset_dev, "tsm_rollout_spread_actor: done_ctr needs offset_dev");
+    if (int rc = rollout_buf_args(h, "tsm_rollout_spread_actor", &a.b)) return rc;
+    a.b.vs_store = nullptr; a.b.vnext_store = nullptr;   // (the critic does not run inside this rollout)
     a.P = h.params; a.D = h.obs_dim; a.A = h.n_act; a.mode = h.mode;
     a.pol_seed = h.policy_seed; a.offset = h.offset; a.offset_dev = h.offset_dev;
     a.env_seed = h.env_seed; a.episode_ctr = h.episode_ctr;
     a.apos = h.agent_pos; a.avel = h.agent_vel; a.lpos = h.landmark_pos; a.steps = h.steps;
     a.auto_reset = h.auto_reset; a.obs_cur_out = h.obs_cur_out;
-    a.vrb_state = h.vrb_state; a.S = h.sub_size; a.done_store = h.done_store;
-    a.obs_store = h.obs_store; a.obs_next_store = h.obs_next_store; a.rew_store = h.rew_store; a.logp_store = h.logp_store;
-    a.act_store = h.act_store; a.term_store = h.term_store; a.trunc_store = h.trunc_store;
-    a.ptr_out = h.ptr_out; a.ep_len_out = h.ep_len_out; a.ep_idx_out = h.ep_idx_out; a.ep_rew_out = h.ep_rew_out;
-    a.n_steps = h.n_steps; a.ep_rec = h.ep_rec; a.max_ep = h.max_ep;
-    a.offset_inc = h.offset_inc; a.done_ctr = h.done_ctr;
-    a.offset_dev_rw = const_cast<uint64_t *>(reinterpret_cast<const uint64_t *>(h.offset_dev));
     a.stamps = g_tsm_stamps;
     hipStream_t st = tsm_stream(stream);
     // the wave-autonomous form (default); "rollout_form" = 1 selects the tile form where it has a spill-free instantiation (widths

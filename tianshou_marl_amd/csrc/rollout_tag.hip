@@ -21,7 +21,7 @@
 #include "mlp_tile.h"
 #include "mpe_tag_dev.h"
 #include "philox.h"
-#include "vrb_dev.h"
+#include "rollout_dev.h"
 
 int tsm_mpe_tag_check_cfg(const tsm_mpe_tag_cfg *h, TagCfg *c);  // mpe_tag.hip
 
@@ -45,23 +45,7 @@ struct TagRolloutArgs {
     int32_t *steps;
     int auto_reset;
     float *obs_cur_out;  // [n_env][NA][D] next policy input after the rollout
-    // buffer
-    void *vrb_state;
-    int64_t S;
-    uint8_t *done_store;
-    float *obs_store, *obs_next_store, *rew_store, *logp_store, *vs_store, *vnext_store;
-    int32_t *act_store;
-    uint8_t *term_store, *trunc_store;
-    // per-step outputs [n_steps][n_env]...
-    int64_t *ptr_out, *ep_len_out, *ep_idx_out;
-    double *ep_rew_out;
-    int n_steps;
-    // compact record of the episodes finished during this rollout (nullable), layout as in rollout.hip
-    int64_t *ep_rec;
-    int max_ep;
-    uint64_t offset_inc;
-    uint64_t *offset_dev_rw;
-    uint32_t *done_ctr;
+    RolloutBufArgs b;   // buffer, per-step outputs, episode record, counter advance
     long long *stamps;  // diagnostics only (tsm_debug_set_stamps, tools/stamp_rollout_tag.py): phase time stamps of workgroup 0
 };
 
@@ -69,6 +53,42 @@ struct TagRolloutArgs {
 #define TSTAMP(k) do { if (a.stamps && blockIdx.x == 0 && threadIdx.x == 0 && t < 4) a.stamps[t * 8 + (k)] = (long long)wall_clock64(); } while (0)
 
 constexpr int NT2 = 2 * NT;  // eight waves: actor chains on waves 0-3, critic chains on waves 4-7 (tile_forward_split)
+constexpr int kPS = 16;      // pair slots per row (entities: <= 8 agents + 4 obstacles)
+
+// LDS layout in floats behind team 0's Lay<H> (weights + the shared activation buffers); the kernel takes its pointers from it, the
+// launcher the size it requests
+template <int H>
+struct TagLay {
+    int WB, OUTB, XN0, AP, AV, LP, REW, LOGP, VAL, ACT, STEPS, DONE, ROW, EP, CX, CY, CV, U, ANY, total;
+    __host__ __device__ TagLay(const Lay<H> &ly, int ld1) {
+        int o = ly.total;
+        WB = o; o += (ly.X + 3) & ~3;         // team 1: weights only, the image layout of [0, ly.X) behind team 0
+        OUTB = o; o += R * Lay<H>::ldo;       // [R][ldo] team 1's logits | value
+        XN0 = o; o += R * ld1;                // [R][ld1] second observation tile
+        AP = o; o += R * 2;                   // [EPB][NA][2]
+        AV = o; o += R * 2;
+        LP = o; o += 2 * 8 * kTagMaxObst;     // [EPB][n_obst][2]  (EPB * n_obst <= 8 * 4)
+        o += R;                               // (unused: the team's hit terms travel by shuffle)
+        REW = o; o += R;                      // [R]
+        LOGP = o; o += R;                     // [R]
+        VAL = o; o += R;                      // [R]
+        ACT = o; o += R;                      // int [R]
+        STEPS = o; o += R;                    // int [EPB]
+        DONE = o; o += 2 * R;                 // int [2][EPB] done flag of the step just taken (generation t & 1)
+        // (aligned by index arithmetic off the 16-byte aligned base: an address rounded through uintptr_t is a generic pointer, its
+        //  accesses FLAT instructions that wait for every outstanding global store -- see csrc/rollout.hip)
+        o = (o + 1) & ~1;
+        ROW = o; o += 2 * 2 * R;              // int64 [2][EPB] slot*B + env of the step just added (two generations, see csrc/rollout.hip)
+        EP = o; o += 2 * R;                   // uint64 [EPB] episode counter of finished envs
+        o = (o + 3) & ~3;
+        CX = o; o += R * kPS;                 // [R][kPS] pair forces, phase D; 16-byte rows
+        CY = o; o += R * kPS;
+        CV = o; o += R * kPS;                 // int [R][kPS] "the pair is in range"
+        U = o; o += 2 * R;                    // [2][R] the sampling uniforms of step t (generation t & 1)
+        ANY = o; o += 2;                      // int [2] "an episode of this tile ends at step t"
+        total = o;
+    }
+};
 
 template <int H>
 __global__ __launch_bounds__(NT2) void rollout_tag_kernel(TagRolloutArgs a) {
@@ -76,46 +96,32 @@ __global__ __launch_bounds__(NT2) void rollout_tag_kernel(TagRolloutArgs a) {
     const Dims d = a.d;
     const TagCfg c = a.c;
     const Lay<H> ly(d, false);                    // team 0: weights + the shared activation buffers
-    const int wB = ly.total;                      // team 1: weights only, the image layout of [0, ly.X) behind team 0
-    const int w_size = (ly.X + 3) & ~3;
-    Lay<H> lyB = ly;
+    const TagLay<H> tl(ly, d.ld1);
+    const int wB = tl.WB, xn0 = tl.XN0;
+    Lay<H> lyB = ly;                              // team 1: weights only
     lyB.W1 += wB; lyB.W2a += wB; lyB.W2c += wB; lyB.W3a += wB; lyB.W3c += wB;
     lyB.B1 += wB; lyB.B2 += wB; lyB.B3a += wB; lyB.B3c += wB;
-    lyB.OUT = wB + w_size;                        // [R][ldo] team 1's logits | value
-    const int xn0 = lyB.OUT + R * ly.ldo;         // [R][ld1] second observation tile
+    lyB.OUT = tl.OUTB;
     const int NA = c.n_adv + c.n_good, D = d.D, st = 2 * NA, lst = 2 * c.n_obst;
     const int EPB = R / NA;                       // worlds per workgroup
     const int e0 = blockIdx.x * EPB;
     const int n_here = min(EPB, c.n_env - e0);
     const int rows_here = n_here * NA;            // live tile rows (<= 16): row r = (env el, agent i), r = el*NA + i
     const int64_t B = c.n_env;
-    float *s_ap = lds + xn0 + R * d.ld1;          // [EPB][NA][2]
-    float *s_av = s_ap + R * 2;
-    float *s_lp = s_av + R * 2;                   // [EPB][n_obst][2]  (EPB * n_obst <= 8 * 4)
-    float *s_rew = s_lp + 2 * 8 * kTagMaxObst + R;  // [R]  (R floats in front of it are unused: the team's hit terms travel by shuffle)
-    float *s_logp = s_rew + R;                    // [R]
-    float *s_val = s_logp + R;                    // [R]
-    int *s_act = reinterpret_cast<int *>(s_val + R);        // [R]
-    int *s_steps = s_act + R;                               // [EPB]
-    int *s_done = s_steps + R;                              // [2][EPB] done flag of the step just taken (generation t & 1)
-    // (aligned by index arithmetic off the 16-byte aligned base: an address rounded through uintptr_t is a generic pointer, its
-    //  accesses FLAT instructions that wait for every outstanding global store -- see csrc/rollout.hip)
-    int64_t *s_row = reinterpret_cast<int64_t *>(                    // [EPB] slot*B + env of the step just added
-        lds + (((int)(reinterpret_cast<float *>(s_done + 2 * R) - lds) + 1) & ~1));   // (two generations, see csrc/rollout.hip)
-    uint64_t *s_ep = reinterpret_cast<uint64_t *>(s_row + 2 * R);    // [EPB] episode counter of finished envs
-    constexpr int kPS = 16;                                          // pair slots per row (entities: <= 8 agents + 4 obstacles)
-    float *s_cx = lds + (((int)(reinterpret_cast<float *>(s_ep + R) - lds) + 3) & ~3);   // [R][kPS] pair forces, phase D; 16-byte rows
-    float *s_cy = s_cx + R * kPS;
-    int *s_cv = reinterpret_cast<int *>(s_cy + R * kPS);             // [R][kPS] "the pair is in range"
-    float *s_u = reinterpret_cast<float *>(s_cv + R * kPS);          // [2][R] the sampling uniforms of step t (generation t & 1)
-    int *s_any = reinterpret_cast<int *>(s_u + 2 * R);               // [2] "an episode of this tile ends at step t"
+    float *s_ap = lds + tl.AP, *s_av = lds + tl.AV, *s_lp = lds + tl.LP, *s_rew = lds + tl.REW, *s_logp = lds + tl.LOGP,
+          *s_val = lds + tl.VAL, *s_cx = lds + tl.CX, *s_cy = lds + tl.CY, *s_u = lds + tl.U;
+    int *s_act = reinterpret_cast<int *>(lds + tl.ACT), *s_steps = reinterpret_cast<int *>(lds + tl.STEPS),
+        *s_done = reinterpret_cast<int *>(lds + tl.DONE), *s_cv = reinterpret_cast<int *>(lds + tl.CV),
+        *s_any = reinterpret_cast<int *>(lds + tl.ANY);
+    int64_t *s_row = reinterpret_cast<int64_t *>(lds + tl.ROW);
+    uint64_t *s_ep = reinterpret_cast<uint64_t *>(lds + tl.EP);
 
     if (a.stamps && blockIdx.x == 0 && threadIdx.x == 0) a.stamps[40] = (long long)wall_clock64();
     // waves 0-3 stage team 0's weights, waves 4-7 team 1's (batches of 4 loads per thread: ~1 us per workgroup)
     if (threadIdx.x < NT) stage_weights<H>(lds, ly, d, a.P[0]);
     else stage_weights<H>(lds + wB, ly, d, a.P[1], (int)threadIdx.x - NT);
     for (int i = threadIdx.x; i < R * d.ld1; i += NT2) { lds[ly.X + i] = 0.f; lds[xn0 + i] = 0.f; }
-    const VrbState vs = vrb_view(a.vrb_state, B, NA);
+    const VrbState vs = vrb_view(a.b.vrb_state, B, NA);
     // agent lane r < rows_here (wave 0) <-> (env el, agent ai); env lane 256 + q (wave 4) owns env q's bookkeeping; beside the head on
     // waves 0-3 run the index algebra (wave 4), the next step's uniforms (wave 5) and this step's pair forces (waves 6, 7)
     const int r = threadIdx.x, el = r / NA, ai = r - el * NA;
@@ -124,16 +130,11 @@ __global__ __launch_bounds__(NT2) void rollout_tag_kernel(TagRolloutArgs a) {
     const int bel = (int)threadIdx.x - 256;  // env lane: local env index
     const bool env_lane = bel >= 0 && bel < n_here;
     const int be = e0 + bel;
-    int64_t v_ins = 0, v_size = 0, v_eplen = 0, v_epstart = 0, v_last = 0;
-    int n_fin = 0;  // episodes this env finished during the rollout
-    double v_epret[kTagMaxAgents];
-#pragma unroll
-    for (int k = 0; k < kTagMaxAgents; ++k) v_epret[k] = 0.0;
+    VrbLane vl;                       // sub-buffer bookkeeping of "my" env: in registers for the whole rollout
+    EpReturns<kTagMaxAgents> epr;
     if (env_lane) {
-        v_ins = vs.ins[be]; v_size = vs.size[be]; v_eplen = vs.ep_len[be]; v_epstart = vs.ep_start[be];
-        v_last = vs.last_index[be];
-#pragma unroll
-        for (int k = 0; k < kTagMaxAgents; ++k) if (k < NA) v_epret[k] = vs.ep_return[(int64_t)be * NA + k];
+        vl.load(vs, be);
+        epr.load(vs, NA, be);
         s_steps[bel] = a.steps[be];
         s_done[bel] = 0; s_done[R + bel] = 0;
         s_row[bel] = 0; s_row[R + bel] = 0;
@@ -173,7 +174,7 @@ __global__ __launch_bounds__(NT2) void rollout_tag_kernel(TagRolloutArgs a) {
     __syncthreads();
 
     if (a.stamps && blockIdx.x == 0 && threadIdx.x == 0) a.stamps[41] = (long long)wall_clock64();
-    for (int t = 0; t < a.n_steps; ++t) {
+    for (int t = 0; t < a.b.n_steps; ++t) {
         const int g = (t & 1) * R;   // this step's generation of s_row / s_done; g ^ R: the previous step's
         float *XN = lds + xnxt;
         TSTAMP(0);
@@ -190,28 +191,14 @@ __global__ __launch_bounds__(NT2) void rollout_tag_kernel(TagRolloutArgs a) {
             const int stp = s_steps[bel] + 1;
             tr = stp >= c.max_cycles;
             s_steps[bel] = stp;
-            o = (int64_t)t * B + be;
-            const int64_t cur = v_ins;
-            int64_t sz = v_size + 1; if (sz > a.S) sz = a.S;
-            int64_t nxt = cur + 1; if (nxt >= a.S) nxt -= a.S;
-            const int64_t elen = v_eplen + 1;
-            if (v_epstart > sz) atomicExch((unsigned long long *)vs.error_flag, 1ull);
-            rec = tr && a.ep_rec && n_fin < a.max_ep;
-            // (the record carries CollectStats.lens = len(episode_batch): the episode's rows IN THE BUFFER, collector.py:203,990-993 --
-            //  after a reset_buffer(keep_statistics=True) an episode counts its rows since the reset; ep_len_out stays add()'s ep_len)
-            if (rec) a.ep_rec[B + (int64_t)be * a.max_ep + n_fin] = ((int64_t)t << 32) | ((cur >= v_epstart ? cur - v_epstart : cur - v_epstart + a.S) + 1);
-            a.ep_len_out[o] = tr ? elen : 0;
-            a.ptr_out[o] = cur + (int64_t)be * a.S;
-            a.ep_idx_out[o] = v_epstart + (int64_t)be * a.S;
-            v_ins = nxt; v_size = sz; v_eplen = tr ? 0 : elen; v_epstart = tr ? nxt : v_epstart;
-            v_last = cur + (int64_t)be * a.S;
-            a.done_store[cur * B + be] = tr ? 1 : 0;
-            s_row[g + bel] = cur * B + be;
+            const VrbStep sp = vl.add(vs, a.b.S, t, be, B, tr, a.b.done_store, a.b.ptr_out, a.b.ep_len_out, a.b.ep_idx_out, a.b.ep_rec, a.b.max_ep);
+            o = sp.o; rec = sp.rec;
+            s_row[g + bel] = sp.row;
             s_done[g + bel] = tr ? 1 : 0;
             const unsigned long long ends = __ballot(tr);   // (the env lanes share wave 4)
             if (bel == 0) s_any[t & 1] = ends != 0ull;
         }
-        if (u_lane && t + 1 < a.n_steps)
+        if (u_lane && t + 1 < a.b.n_steps)
             s_u[((t + 1) & 1) * R + ur] = tsm_philox_uniform(a.pol_seed[u_team], a.offset[u_team] + off0 + (uint64_t)(t + 1) * B * NA + u_gi);
         // The pair forces of THIS step depend on the positions alone, not on the actions the head is sampling: waves 6 and 7 evaluate
         // them beside the head, one (agent row, other entity) task per lane, and phase D starts at the fold (csrc/rollout.hip has the
@@ -260,7 +247,7 @@ __global__ __launch_bounds__(NT2) void rollout_tag_kernel(TagRolloutArgs a) {
                 s_logp[hr] = la - (m + logf(ssum));
                 // V(obs_next) of the previous step's row == V(obs) of this one where the episode goes on (s_row / s_done still hold
                 // the previous step: D rewrites them behind the barrier below)
-                if (a.vnext_store && t > 0 && !s_done[(g ^ R) + hel]) a.vnext_store[s_row[(g ^ R) + hel] * NA + hai] = lg[16];
+                if (a.b.vnext_store && t > 0 && !s_done[(g ^ R) + hel]) a.b.vnext_store[s_row[(g ^ R) + hel] * NA + hai] = lg[16];
             }
         }
         __syncthreads();
@@ -308,48 +295,36 @@ __global__ __launch_bounds__(NT2) void rollout_tag_kernel(TagRolloutArgs a) {
             }
         }
         __syncthreads();
-        if (env_lane) {  // episode returns (needs the rewards); runs beside the payload scatter below
-            double *rec_rew = rec ? reinterpret_cast<double *>(a.ep_rec + B + (int64_t)B * a.max_ep) +
-                                        ((int64_t)be * a.max_ep + n_fin) * NA : nullptr;
-#pragma unroll
-            for (int k = 0; k < kTagMaxAgents; ++k) {
-                if (k < NA) {
-                    const double acc = v_epret[k] + (double)s_rew[bel * NA + k];
-                    a.ep_rew_out[o * NA + k] = tr ? acc : 0.0;
-                    if (rec) rec_rew[k] = acc;
-                    v_epret[k] = tr ? 0.0 : acc;
-                }
-            }
-            n_fin += tr ? 1 : 0;
-        }
+        // episode returns (needs the rewards); runs beside the payload scatter below
+        if (env_lane) epr.fold(a.b.ep_rew_out, a.b.ep_rec, a.b.max_ep, NA, B, be, o, tr, rec, vl.n_fin, s_rew + bel * NA);
         TSTAMP(3);
         // E. payload scatter into the time-major SoA store (rows of consecutive envs are adjacent)
         for (int i = threadIdx.x; i < rows_here * D; i += NT2) {
             const int rr = i / D, k = i - rr * D, ee = rr / NA;
             const int64_t dst = (s_row[g + ee] * NA + (rr - ee * NA)) * D + k;
-            a.obs_store[dst] = lds[xcur + rr * d.ld1 + k];
-            if (a.obs_next_store) a.obs_next_store[dst] = XN[rr * d.ld1 + k];
+            a.b.obs_store[dst] = lds[xcur + rr * d.ld1 + k];
+            if (a.b.obs_next_store) a.b.obs_next_store[dst] = XN[rr * d.ld1 + k];
         }
         if (lane_live) {
             const int64_t dst = s_row[g + el] * NA + ai;
-            a.act_store[dst] = s_act[r];
-            a.rew_store[dst] = s_rew[r];
-            a.term_store[dst] = 0;
-            a.trunc_store[dst] = (uint8_t)s_done[g + el];
-            if (a.logp_store) a.logp_store[dst] = s_logp[r];
-            if (a.vs_store) a.vs_store[dst] = s_val[r];
+            a.b.act_store[dst] = s_act[r];
+            a.b.rew_store[dst] = s_rew[r];
+            a.b.term_store[dst] = 0;
+            a.b.trunc_store[dst] = (uint8_t)s_done[g + el];
+            if (a.b.logp_store) a.b.logp_store[dst] = s_logp[r];
+            if (a.b.vs_store) a.b.vs_store[dst] = s_val[r];
         }
         TSTAMP(4);
         // F. finished episodes: the critic value of the terminal observation (both teams' nets on the obs_next tile, every row takes
         //    its own team's), then re-initialise the env, first observation of the new episode
-        if (a.auto_reset || a.vnext_store) {
+        if (a.auto_reset || a.b.vnext_store) {
             const int any_done = s_any[t & 1];   // (left by the env lanes beside the index algebra: no workgroup-wide OR)
-            if (any_done && a.vnext_store) {
+            if (any_done && a.b.vnext_store) {
                 lyf.X = xnxt; lyg.X = xnxt;
                 tile_forward_split<H>(lds, lyf, d);
                 tile_forward_split<H>(lds, lyg, d);
                 if (lane_live && s_done[g + el])
-                    a.vnext_store[s_row[g + el] * NA + ai] = lds[(ai >= c.n_adv ? lyB.OUT : ly.OUT) + r * ly.ldo + 16];
+                    a.b.vnext_store[s_row[g + el] * NA + ai] = lds[(ai >= c.n_adv ? lyB.OUT : ly.OUT) + r * ly.ldo + 16];
             }
             if (any_done && a.auto_reset) {
                 if (env_lane && s_done[g + bel]) {
@@ -376,8 +351,8 @@ __global__ __launch_bounds__(NT2) void rollout_tag_kernel(TagRolloutArgs a) {
     }
     if (a.stamps && blockIdx.x == 0 && threadIdx.x == 0) a.stamps[42] = (long long)wall_clock64();
     // V(obs_next) of the final step's rows whose episode goes on: one more pass over the observation the next collect starts from
-    if (a.vnext_store) {
-        const int gl = ((a.n_steps - 1) & 1) * R;   // the final step's generation
+    if (a.b.vnext_store) {
+        const int gl = ((a.b.n_steps - 1) & 1) * R;   // the final step's generation
         int open_rows = lane_live ? !s_done[gl + el] : 0;
         open_rows = __syncthreads_or(open_rows);
         if (open_rows) {
@@ -385,7 +360,7 @@ __global__ __launch_bounds__(NT2) void rollout_tag_kernel(TagRolloutArgs a) {
             tile_forward_split<H>(lds, lyf, d);
             tile_forward_split<H>(lds, lyg, d);
             if (lane_live && !s_done[gl + el])
-                a.vnext_store[s_row[gl + el] * NA + ai] = lds[(ai >= c.n_adv ? lyB.OUT : ly.OUT) + r * ly.ldo + 16];
+                a.b.vnext_store[s_row[gl + el] * NA + ai] = lds[(ai >= c.n_adv ? lyB.OUT : ly.OUT) + r * ly.ldo + 16];
         }
     }
     // the observation of the next collect() call
@@ -402,26 +377,10 @@ __global__ __launch_bounds__(NT2) void rollout_tag_kernel(TagRolloutArgs a) {
     for (int i = threadIdx.x; i < n_here * lst; i += NT2) a.lpos[(int64_t)e0 * lst + i] = s_lp[i];
     if (env_lane) {
         a.steps[be] = s_steps[bel];
-        vs.ins[be] = v_ins; vs.size[be] = v_size; vs.ep_len[be] = v_eplen; vs.ep_start[be] = v_epstart;
-        vs.last_index[be] = v_last; vs.lengths[be] = v_size;
-        if (a.ep_rec) a.ep_rec[be] = n_fin;  // may exceed max_ep: the host treats that as an overflow
-#pragma unroll
-        for (int k = 0; k < kTagMaxAgents; ++k) if (k < NA) vs.ep_return[(int64_t)be * NA + k] = v_epret[k];
+        vl.store(vs, a.b.ep_rec, be);
+        epr.store(vs, NA, be);
     }
-    // the last workgroup to get here advances the sampling counter: every workgroup read it (off0) before finishing
-    if (a.done_ctr && threadIdx.x == 0) {
-        if (atomicAdd(a.done_ctr, 1u) == gridDim.x - 1) {
-            *a.offset_dev_rw += a.offset_inc;
-            *a.done_ctr = 0u;
-        }
-    }
-}
-
-size_t tag_rollout_lds_floats(const Dims &d) {
-    const Lay<64> ly(d, false);
-    const size_t w_size = (size_t)((ly.X + 3) & ~3);
-    return (size_t)ly.total + w_size + (size_t)R * ly.ldo + (size_t)R * d.ld1 + 2 * R * 2 + 2 * 8 * kTagMaxObst + 4 * R +
-           3 * R + 2 * 2 * R + 8 + 3 * R * 16 + 4 + 3 * R + 2 * R + 4;
+    rollout_advance_counter(a.b.done_ctr, a.b.offset_dev_rw, a.b.offset_inc, threadIdx.x == 0);   // (every workgroup read the counter, off0, before finishing)
 }
 
 }  // namespace
@@ -442,28 +401,15 @@ TSM_EXPORT int tsm_rollout_tag(const tsm_rollout_tag_desc *desc_host, void *stre
         TSM_REQUIRE(h.params[k], "tsm_rollout_tag: null parameters");
         a.P[k] = h.params[k]; a.pol_seed[k] = h.policy_seed[k]; a.offset[k] = h.offset[k]; a.mode[k] = h.mode[k];
     }
-    TSM_REQUIRE(h.episode_ctr && h.agent_pos && h.agent_vel && h.landmark_pos && h.steps && h.vrb_state && h.done_store &&
-                    h.obs_store && h.act_store && h.rew_store && h.term_store && h.trunc_store && h.ptr_out &&
-                    h.ep_rew_out && h.ep_len_out && h.ep_idx_out,
-                "tsm_rollout_tag: null pointer");
+    TSM_REQUIRE(h.episode_ctr && h.agent_pos && h.agent_vel && h.landmark_pos && h.steps, "tsm_rollout_tag: null pointer");
+    if (int rc = rollout_buf_args(h, "tsm_rollout_tag", &a.b)) return rc;
     a.offset_dev = h.offset_dev;
     a.env_major = h.env_major_counter ? 1 : 0;
     a.env_seed = h.env_seed; a.episode_ctr = h.episode_ctr;
     a.apos = h.agent_pos; a.avel = h.agent_vel; a.lpos = h.landmark_pos; a.steps = h.steps;
     a.auto_reset = h.auto_reset; a.obs_cur_out = h.obs_cur_out;
-    a.vrb_state = h.vrb_state; a.S = h.sub_size; a.done_store = h.done_store;
-    a.obs_store = h.obs_store; a.obs_next_store = h.obs_next_store; a.rew_store = h.rew_store;
-    a.logp_store = h.logp_store; a.vs_store = h.vs_store; a.vnext_store = h.vnext_store;
-    a.act_store = h.act_store; a.term_store = h.term_store; a.trunc_store = h.trunc_store;
-    a.ptr_out = h.ptr_out; a.ep_len_out = h.ep_len_out; a.ep_idx_out = h.ep_idx_out; a.ep_rew_out = h.ep_rew_out;
-    a.n_steps = h.n_steps;
-    TSM_REQUIRE(!h.ep_rec || h.max_ep >= 1, "tsm_rollout_tag: ep_rec needs max_ep >= 1");
-    a.ep_rec = h.ep_rec; a.max_ep = h.max_ep;
-    TSM_REQUIRE(!h.done_ctr || h.offset_dev, "tsm_rollout_tag: done_ctr needs offset_dev");
-    a.offset_inc = h.offset_inc; a.done_ctr = h.done_ctr;
-    a.offset_dev_rw = const_cast<uint64_t *>(reinterpret_cast<const uint64_t *>(h.offset_dev));
     a.stamps = g_tsm_stamps;
-    const size_t shmem = tag_rollout_lds_floats(a.d) * sizeof(float);
+    const size_t shmem = (size_t)TagLay<64>(Lay<64>(a.d, false), a.d.ld1).total * sizeof(float);
     TSM_REQUIRE(shmem <= kTsmMaxLds, "tsm_rollout_tag: %zu bytes of LDS needed", shmem);
     static bool attr_set = false;
     if (!attr_set) {

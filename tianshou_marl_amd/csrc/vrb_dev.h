@@ -56,3 +56,56 @@ __device__ inline int64_t vrb_add_row(const VrbState &s, int64_t B, int64_t S, i
     done_store[cur * B + e] = d ? 1 : 0;
     return cur;
 }
+
+// The same bookkeeping for the persistent rollout kernels: the sub-buffer state of "my" env lives in the registers of one lane
+// (the env lane) for the whole rollout, so a step's index algebra has no dependent global loads, only fire-and-forget stores.
+// (vrb_add_row above stays the unfused path these kernels are tested against: it does not go through this type.)
+struct VrbStep {
+    int64_t row;  // slot * B + env: where the step's payload rows go
+    int64_t o;    // t * B + env: the step's place in the per-step outputs
+    bool rec;     // the episode that ends here gets an ep_rec entry (index n_fin)
+};
+
+struct VrbLane {
+    int64_t ins = 0, size = 0, ep_len = 0, ep_start = 0, last = 0;   // zero: a lane that owns no env
+    int n_fin = 0;   // episodes this env finished during the rollout; counted by the caller (a kernel may keep a second count on
+                     // the lanes that fold the episode returns)
+
+    __device__ __forceinline__ void load(const VrbState &vs, int be) {
+        ins = vs.ins[be]; size = vs.size[be]; ep_len = vs.ep_len[be]; ep_start = vs.ep_start[be];
+        last = vs.last_index[be];
+    }
+
+    // Row t of env `be` (tr: its episode ends here): buffer_base.py:373-410 + manager.py:170-177, same arithmetic as vrb_add_row.
+    // The outputs are [n_steps][B] arrays; ep_rec (nullable, max_ep entries per env) is the rollout's compact episode record.
+    // (Pointers and sizes come by value: handing the kernel's argument struct over by reference made every field of it a load
+    //  the compiler may hoist to the kernel's entry -- rollout_tag_kernel 184 -> 199 VGPRs, 234 -> 288 spilled scalar registers.)
+    __device__ __forceinline__ VrbStep add(const VrbState &vs, int64_t S, int t, int be, int64_t B, bool tr, uint8_t *done_store,
+                                           int64_t *ptr_out, int64_t *ep_len_out, int64_t *ep_idx_out, int64_t *ep_rec, int max_ep) {
+        VrbStep s;
+        s.o = (int64_t)t * B + be;
+        const int64_t cur = ins;
+        int64_t sz = size + 1; if (sz > S) sz = S;
+        int64_t nxt = cur + 1; if (nxt >= S) nxt -= S;
+        const int64_t elen = ep_len + 1;
+        if (ep_start > sz) atomicExch((unsigned long long *)vs.error_flag, 1ull);
+        s.rec = tr && ep_rec && n_fin < max_ep;
+        // (the record carries CollectStats.lens = len(episode_batch): the episode's rows IN THE BUFFER, collector.py:203,990-993 --
+        //  after a reset_buffer(keep_statistics=True) an episode counts its rows since the reset; ep_len_out stays add()'s ep_len)
+        if (s.rec) ep_rec[B + (int64_t)be * max_ep + n_fin] = ((int64_t)t << 32) | ((cur >= ep_start ? cur - ep_start : cur - ep_start + S) + 1);
+        ep_len_out[s.o] = tr ? elen : 0;
+        ptr_out[s.o] = cur + (int64_t)be * S;
+        ep_idx_out[s.o] = ep_start + (int64_t)be * S;
+        ins = nxt; size = sz; ep_len = tr ? 0 : elen; ep_start = tr ? nxt : ep_start;
+        last = cur + (int64_t)be * S;
+        done_store[cur * B + be] = tr ? 1 : 0;
+        s.row = cur * B + be;
+        return s;
+    }
+
+    __device__ __forceinline__ void store(const VrbState &vs, int64_t *ep_rec, int be) const {
+        vs.ins[be] = ins; vs.size[be] = size; vs.ep_len[be] = ep_len; vs.ep_start[be] = ep_start;
+        vs.last_index[be] = last; vs.lengths[be] = size;
+        if (ep_rec) ep_rec[be] = n_fin;  // may exceed max_ep: the host treats that as an overflow
+    }
+};

@@ -26,6 +26,29 @@ __device__ __forceinline__ void lane_group_transpose(wf4 &r) {
     r = wf4{r0, r1, r2, r3};
 }
 
+// The layer-1 B fragments of the wave's samples straight from LDS-resident env state: fragment kb is element k = 4 kb + (lane >> 4)
+// of sample lane & 15, given as two LDS offsets el_ab[kb] = oa << 16 | ob (value = lds[oa] - lds[ob]: mpe_obs_offsets, mpe_dev.h).
+// All 2 x KB LDS reads in flight, then the subtractions (written as one loop the reads are waited for pair by pair).
+template <int KB>
+__device__ __forceinline__ void wave_obs_frags(const float *lds, const uint32_t (&el_ab)[KB], float (&x)[KB]) {
+    float xa[KB], xs[KB];
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) { xa[kb] = lds[el_ab[kb] >> 16]; xs[kb] = lds[el_ab[kb] & 0xFFFFu]; }
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) x[kb] = xa[kb] - xs[kb];
+}
+// ... and the same fragments to row memory (dst = the sample's row + (lane >> 4)): elements k = 4 kb + kq < D, whole k-steps under a
+// wave-uniform test, the one partial k-step of an odd agent count (D = 6 N, D & 3 == 2) under a lane test
+template <int KB>
+__device__ __forceinline__ void wave_obs_rows_out(float *dst, const float (&x)[KB], int D, int kq) {
+    const int kb_full = D >> 2, k_rem = D & 3;
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+        if (kb < kb_full) dst[4 * kb] = x[kb];
+        else if (kb == kb_full && kq < k_rem) dst[4 * kb] = x[kb];
+    }
+}
+
 // out[unit][sample] = sum_k W[unit][k] x[k][sample] for MB blocks of 16 units; xb[kb] = the B fragment of k-step kb; only the
 // first kb_n (wave-uniform, <= KB) k-steps are issued
 template <int MB, int KB>
