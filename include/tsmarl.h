@@ -855,6 +855,74 @@ int tsm_qmix_egreedy(const float *const *q_by_agent_host, int32_t n_agents, int6
                      const float *eps_dev, uint64_t seed, uint64_t offset, const uint64_t *offset_dev, int32_t *act_out,
                      int64_t act_row_stride, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Gradient of a fully-connected net w.r.t. a window of its input
+ * Replaces  the part of `actor_loss.backward()` that runs through critic_i back to agent i's action columns
+ *           (MADDPGPolicy.learn, ctde.py:918-924).
+ * tsm_mlp_input_grad: after tsm_mlp_forward(desc, params, x, B, acts): the dgrad chain of tsm_mlp_backward with NO
+ *   weight-gradient launches, ended by dx[b][0 .. n_col) = dZ_0[b] . W_0[:, col0 .. col0 + n_col) (row pitch ldx floats).
+ *   d_out [B][dims[L]]; d_acts: workspace of tsm_mlp_act_elems floats (n_layers > 1).  0 <= col0, col0 + n_col <= dims[0].
+ * ------------------------------------------------------------------------------------------- */
+int tsm_mlp_input_grad(const tsm_mlp_desc *desc, const float *params, const float *x, int64_t B, const float *acts,
+                       const float *d_out, float *d_acts, int32_t col0, int32_t n_col, float *dx, int64_t ldx,
+                       void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * MADDPG  (tianshou/algorithm/multiagent/ctde.py:728-955)
+ * Within one learn call the agents are independent (ctde.py:829-925 reads, for agent i, the batch, the target actors,
+ * target critic i, critic i and actor i), so each entry serves all n_agents <= 8 agents in one launch.
+ * tsm_maddpg_joint_rows replaces  the torch.cat chains that build the critics' inputs (ctde.py:875-880, 888, 893, 913-919).
+ *   obs[i] [B][D], act[i] [B][Ad] (host arrays of device pointers).  W = n_agents * (D + Ad).
+ *   replace == NULL: out [B][W], row b = [obs_0[b] .. obs_{N-1}[b] | act_0[b] .. act_{N-1}[b]].
+ *   replace != NULL: out [n_agents][B][W]; matrix m is the same with replace[m][b] ([B][Ad]) in agent m's action slot.
+ *   16-byte accesses for the regions whose rows allow them (D resp. Ad, their offsets and W multiples of 4, aligned
+ *   pointers), scalar ones otherwise.
+ * tsm_maddpg_td replaces  td_target, F.mse_loss and its gradient w.r.t. q (ctde.py:895-898) for every agent:
+ *   y_i = rew_i + gamma q_next_i (1 - term_i) with agent i's OWN terminated flags, dq_i = 2 (q_i - y_i) / B, formed in f64
+ *   from the f32 inputs and rounded once;
+ *   partial f64 [tsm_maddpg_partial_elems(B, n_agents)] = per workgroup (256 rows) and agent the sum of (q_i - y_i)^2.
+ *   No atomics: every output element has one writer.
+ * tsm_maddpg_finalize replaces  the .item() reads of ctde.py:927-928: out[2 i] = actor_loss_i = -mean(q_pi[i]) with
+ *   q_pi[i] [B] = critic_i on the rows carrying actor_i's action, out[2 i + 1] = critic_loss_i = the MSE from the
+ *   partials; sums in f64 in a fixed order.  out f32 [2 n_agents] may be pinned host memory.
+ * tsm_maddpg_act: the acting epilogue on the device (ctde.py:803-813 returns the actor output; exploration noise and the
+ *   clamp to the Box are the caller's there): act_out [(e * n_agents + i)][k] = mu[i][e][k] + *sigma_dev * z, clamped to
+ *   [low[k], high[k]] when the bounds are given (both or neither).  z: standard normal (Box-Muller on words 0 and 1 of
+ *   Philox4x32-10 keyed by seed at counter offset + *offset_dev + element index).  *sigma_dev == 0 draws nothing and,
+ *   without bounds, stores the actor's bits.
+ * tsm_polyak replaces  update_target_networks (ctde.py:936-955): target[i] = tau * param[i] + (1 - tau) * target[i] with
+ *   both products rounded to f32 before the sum (no FMA) and 1 - tau formed in double, then rounded to f32.
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_MADDPG_MAX_AGENTS 8
+typedef struct tsm_maddpg_agents {
+    const float *q[TSM_MADDPG_MAX_AGENTS];
+    const float *q_next[TSM_MADDPG_MAX_AGENTS];
+    const float *rew[TSM_MADDPG_MAX_AGENTS];
+    const uint8_t *term[TSM_MADDPG_MAX_AGENTS];
+    float *dq[TSM_MADDPG_MAX_AGENTS];
+} tsm_maddpg_agents;
+int tsm_maddpg_joint_rows(const float *const *obs_by_agent_host, const float *const *act_by_agent_host,
+                          const float *const *replace_by_agent_host, int32_t n_agents, int64_t B, int32_t D, int32_t Ad,
+                          float *out, void *stream);
+int64_t tsm_maddpg_partial_elems(int64_t B, int32_t n_agents);
+int tsm_maddpg_td(const tsm_maddpg_agents *agents, int32_t n_agents, int64_t B, double gamma, double *partial,
+                  void *stream);
+int tsm_maddpg_finalize(const double *partial, int32_t n_blocks, const float *const *q_pi_by_agent_host,
+                        int32_t n_agents, int64_t B, float *out, void *stream);
+int tsm_maddpg_act(const float *const *mu_by_agent_host, int32_t n_agents, int64_t E, int32_t Ad, const float *sigma_dev,
+                   uint64_t seed, uint64_t offset, const uint64_t *offset_dev, const float *low, const float *high,
+                   float *act_out, void *stream);
+int tsm_polyak(float *target, const float *param, int64_t n, double tau, void *stream);
+/* tsm_adam_step (same arguments) with the coefficients 1 - beta1 and 1 - beta2 formed in f64 and rounded to f32 once, as
+ * torch.optim.Adam forms them (`lerp_(grad, 1 - beta1)`, `addcmul_(grad, grad, value=1 - beta2)`).  tsm_adam_step and its kin
+ * keep the f32 differences 1.f - (float)beta, bit for bit as before: 1.f - 0.999f lies 1.3e-5 below 0.001, which lengthens
+ * every step by 6.4e-6 of itself along the gradient's sign.  MADDPG's actor loss is a MEAN over the outputs of the critic that
+ * was just stepped, where that one-sided error does not average out, so its two optimizers use this entry. */
+int tsm_adam_step_coef64(float *param, const float *grad_slabs, int32_t n_slab, int64_t n, float *exp_avg,
+                         float *exp_avg_sq, int64_t step, const int64_t *step_dev, double lr, const double *lr_dev,
+                         double beta1, double beta2, double eps, double weight_decay, double max_grad_norm, float *work,
+                         float *param_image, const int32_t *image_map, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,15 @@ class tsm_qmix_agents(C.Structure):
 QMIX_MAX_AGENTS = 8
 
 
+class tsm_maddpg_agents(C.Structure):
+    """include/tsmarl.h: per-agent arrays of tsm_maddpg_td (up to TSM_MADDPG_MAX_AGENTS)."""
+    _fields_ = [("q", C.c_void_p * 8), ("q_next", C.c_void_p * 8), ("rew", C.c_void_p * 8), ("term", C.c_void_p * 8),
+                ("dq", C.c_void_p * 8)]
+
+
+MADDPG_MAX_AGENTS = 8
+
+
 class tsm_mlp_desc(C.Structure):
     _fields_ = [("n_layers", C.c_int32), ("act", C.c_int32), ("dims", C.c_int32 * 9)]
 
@@ -237,6 +246,14 @@ SIGNATURES = {
                                C.c_float, _int, _p, _p, _p, _p, _p, _p, _p]),
     "tsm_qmix_finalize": (_int, [_p, _i32, _i64, _p, _p]),
     "tsm_qmix_egreedy": (_int, [_p, _i32, _i64, _i32, _p, _u64, _u64, _p, _p, _i64, _p]),
+    "tsm_mlp_input_grad": (_int, [C.POINTER(tsm_mlp_desc), _p, _p, _i64, _p, _p, _p, _i32, _i32, _p, _i64, _p]),
+    "tsm_maddpg_joint_rows": (_int, [_p, _p, _p, _i32, _i64, _i32, _i32, _p, _p]),
+    "tsm_maddpg_partial_elems": (_i64, [_i64, _i32]),
+    "tsm_maddpg_td": (_int, [C.POINTER(tsm_maddpg_agents), _i32, _i64, _f64, _p, _p]),
+    "tsm_maddpg_finalize": (_int, [_p, _i32, _p, _i32, _i64, _p, _p]),
+    "tsm_maddpg_act": (_int, [_p, _i32, _i64, _i32, _p, _u64, _u64, _p, _p, _p, _p, _p]),
+    "tsm_polyak": (_int, [_p, _p, _i64, _f64, _p]),
+    "tsm_adam_step_coef64": (_int, [_p, _p, _i32, _i64, _p, _p, _i64, _p, _f64, _p, _f64, _f64, _f64, _f64, _f64, _p, _p, _p, _p]),
     "tsm_ppo_update_grid": (_int, [_i64, _i32]),
     "tsm_ppo_finalize_many": (_int, [_p, _i64, _p, _p, _i32, C.POINTER(tsm_ppo_cfg), _p, _p]),
     "tsm_ppo_update_fused": (_int, [_p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p,
@@ -248,7 +265,7 @@ _NO_STATUS = {"tsm_critic_rows_w1_image_kj", "tsm_critic_rows_w1_image_elems", "
               "tsm_rms_update_work_elems", "tsm_ppo_adv_stats_work_elems", "tsm_abi_version", "tsm_last_error", "tsm_stream_abort_capture", "tsm_vrb_state_bytes", "tsm_ppo_loss_partial_elems",
               "tsm_policy_param_count", "tsm_ppo_update_grid", "tsm_adam_work_elems", "tsm_policy_image_elems",
               "tsm_mlp_param_count", "tsm_mlp_act_elems", "tsm_ctde_head_partial_elems", "tsm_mpe_tag_obs_dim",
-              "tsm_gae_scan_workspace_bytes", "tsm_qmix_partial_elems"}
+              "tsm_gae_scan_workspace_bytes", "tsm_qmix_partial_elems", "tsm_maddpg_partial_elems"}
 
 _lib = None
 

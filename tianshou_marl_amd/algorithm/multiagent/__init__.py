@@ -3,6 +3,7 @@
 from ...data.stats import MapTrainingStats
 from .ctde import CentralizedCritic, CTDEPolicy, DecentralizedActor, GlobalStateConstructor
 from .flexible_policy import FlexibleMultiAgentPolicyManager
+from .maddpg import MADDPGPolicy
 from .qmix import QMIXMixer, QMIXPolicy
 from .marl import MARLDispatcher, MultiAgentOnPolicyAlgorithm, MultiAgentPolicy
 from .training_coordinator import (
@@ -18,5 +19,5 @@ __all__ = [
     "MultiAgentPolicy", "MultiAgentOnPolicyAlgorithm", "MARLDispatcher", "MapTrainingStats",
     "FlexibleMultiAgentPolicyManager", "MATrainer", "SimultaneousTrainer", "SequentialTrainer",
     "SelfPlayTrainer", "LeaguePlayTrainer", "agent_batches_from_buffer", "CTDEPolicy", "GlobalStateConstructor",
-    "DecentralizedActor", "CentralizedCritic", "QMIXMixer", "QMIXPolicy",
+    "DecentralizedActor", "CentralizedCritic", "QMIXMixer", "QMIXPolicy", "MADDPGPolicy",
 ]

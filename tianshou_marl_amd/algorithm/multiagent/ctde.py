@@ -8,7 +8,8 @@ Mirror of /root/reference/tianshou/algorithm/multiagent/ctde.py for the componen
   `CentralizedCritic`        :382-414  global_obs -> H -> H -> n_agents values, ReLU
   `QMIXMixer`, `QMIXPolicy` :417-725  value decomposition with a monotonic mixer: built in qmix.py (csrc/qmix.hip) and
                                        re-exported here, so `from ...multiagent.ctde import QMIXPolicy` works as upstream
-MADDPG (:728-954) is continuous control, outside the north-star path, and is not built.
+  `MADDPGPolicy`            :728-955  per-agent actors and centralized critics on continuous actions: built in maddpg.py
+                                       (csrc/maddpg.hip) and re-exported here in the same way
 
 Networks are `FlatMLP`s (one flat HBM parameter vector each, csrc/dense.hip f32-MFMA GEMMs for forward, dgrad
 and wgrad); the TD-target / MSE / policy-gradient head between them is `tsm_ctde_td_head` (csrc/ctde.hip) and the
@@ -316,3 +317,4 @@ class CTDEPolicy(nn.Module):
 
 
 from .qmix import QMIXMixer, QMIXPolicy  # noqa: E402  (qmix.py imports LazyScalars from this module)
+from .maddpg import MADDPGPolicy  # noqa: E402  (so does maddpg.py)

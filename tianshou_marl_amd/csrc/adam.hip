@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const 
                                                    int64_t step_host, const int64_t *__restrict__ step_dev,
                                                    float eps, float weight_decay, float max_norm,
                                                    const float *__restrict__ work, float *__restrict__ img,
-                                                   const int32_t *__restrict__ img_map) {
+                                                   const int32_t *__restrict__ img_map, int coef_f64) {
     __shared__ float sm[256];
     __shared__ float s_coef;
     const int lane = threadIdx.x & 63, sl = threadIdx.x >> 6;
@@ -72,7 +72,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const 
         g = slab_sum_block(slabs, n_slab, n, i, sm, n);
     }
     if (sl != 0 || i >= n) return;
-    const float pn = adam_apply(p, m, v, i, g, lr_host, lr_dev, beta1d, beta2d, step_host, step_dev, eps, weight_decay);
+    const float pn = adam_apply(p, m, v, i, g, lr_host, lr_dev, beta1d, beta2d, step_host, step_dev, eps, weight_decay,
+                                coef_f64 != 0);
     if (img) img[img_map[i]] = pn;
 }
 
@@ -248,16 +249,16 @@ TSM_EXPORT int tsm_adam_step_segs(float *param, const tsm_slab_seg *segs, int32_
 // (room for the per-block squares of the segmented form too: every segment rounds its block count up)
 TSM_EXPORT int64_t tsm_adam_work_elems(int64_t n) { return n < 0 ? -1 : n + ceil_div(n > 0 ? n : 1, kCols) + TSM_MAX_SLAB_SEGS; }
 
-TSM_EXPORT int tsm_adam_step(float *param, const float *grad_slabs, int32_t n_slab, int64_t n, float *exp_avg,
+static int adam_step_impl(float *param, const float *grad_slabs, int32_t n_slab, int64_t n, float *exp_avg,
                              float *exp_avg_sq, int64_t step, const int64_t *step_dev, double lr, const double *lr_dev,
                              double beta1, double beta2, double eps, double weight_decay, double max_grad_norm, float *work,
-                             float *param_image, const int32_t *image_map, void *stream) {
-    TSM_REQUIRE(n >= 0 && n_slab >= 1 && (step >= 1 || step_dev), "tsm_adam_step: bad sizes n=%lld n_slab=%d step=%lld",
+                             float *param_image, const int32_t *image_map, void *stream, int coef_f64, const char *who) {
+    TSM_REQUIRE(n >= 0 && n_slab >= 1 && (step >= 1 || step_dev), "%s: bad sizes n=%lld n_slab=%d step=%lld", who,
                 (long long)n, n_slab, (long long)step);
     if (n == 0) return TSM_OK;
-    TSM_REQUIRE(param && grad_slabs && exp_avg && exp_avg_sq, "tsm_adam_step: null pointer");
-    TSM_REQUIRE(max_grad_norm <= 0.0 || work, "tsm_adam_step: clipping needs work[tsm_adam_work_elems(n)]");
-    TSM_REQUIRE(!param_image || image_map, "tsm_adam_step: param_image needs image_map");
+    TSM_REQUIRE(param && grad_slabs && exp_avg && exp_avg_sq, "%s: null pointer", who);
+    TSM_REQUIRE(max_grad_norm <= 0.0 || work, "%s: clipping needs work[tsm_adam_work_elems(n)]", who);
+    TSM_REQUIRE(!param_image || image_map, "%s: param_image needs image_map", who);
     hipStream_t st = tsm_stream(stream);
     const dim3 grid((unsigned)ceil_div(n, kCols));
     if (max_grad_norm > 0.0) {
@@ -266,9 +267,26 @@ TSM_EXPORT int tsm_adam_step(float *param, const float *grad_slabs, int32_t n_sl
     }
     hipLaunchKernelGGL(adam_kernel, grid, dim3(256), 0, st, param, grad_slabs, n_slab, n, exp_avg, exp_avg_sq, lr,
                        lr_dev, beta1, beta2, step, step_dev, (float)eps, (float)weight_decay, (float)max_grad_norm, work,
-                       param_image, image_map);
+                       param_image, image_map, coef_f64);
     TSM_LAUNCH_CHECK();
     return TSM_OK;
+}
+
+TSM_EXPORT int tsm_adam_step(float *param, const float *grad_slabs, int32_t n_slab, int64_t n, float *exp_avg,
+                             float *exp_avg_sq, int64_t step, const int64_t *step_dev, double lr, const double *lr_dev,
+                             double beta1, double beta2, double eps, double weight_decay, double max_grad_norm, float *work,
+                             float *param_image, const int32_t *image_map, void *stream) {
+    return adam_step_impl(param, grad_slabs, n_slab, n, exp_avg, exp_avg_sq, step, step_dev, lr, lr_dev, beta1, beta2, eps,
+                          weight_decay, max_grad_norm, work, param_image, image_map, stream, 0, "tsm_adam_step");
+}
+
+// tsm_adam_step with 1 - beta1 and 1 - beta2 formed in f64 and rounded once (torch's own f32 coefficients)
+TSM_EXPORT int tsm_adam_step_coef64(float *param, const float *grad_slabs, int32_t n_slab, int64_t n, float *exp_avg,
+                                    float *exp_avg_sq, int64_t step, const int64_t *step_dev, double lr, const double *lr_dev,
+                                    double beta1, double beta2, double eps, double weight_decay, double max_grad_norm,
+                                    float *work, float *param_image, const int32_t *image_map, void *stream) {
+    return adam_step_impl(param, grad_slabs, n_slab, n, exp_avg, exp_avg_sq, step, step_dev, lr, lr_dev, beta1, beta2, eps,
+                          weight_decay, max_grad_norm, work, param_image, image_map, stream, 1, "tsm_adam_step_coef64");
 }
 
 // img[map[i]] = param[i] (initial fill / after load_state_dict); pads of `img` must be zero already.

@@ -74,16 +74,22 @@ __device__ __forceinline__ float slab_sum_block(const float *__restrict__ slabs,
 // algorithm_base.py:626-627).  Returns the new parameter value (already stored).
 __device__ __forceinline__ float adam_apply(float *__restrict__ p, float *__restrict__ m, float *__restrict__ v, int64_t i, float g,
                                             double lr_host, const double *__restrict__ lr_dev, double beta1d, double beta2d,
-                                            int64_t step_host, const int64_t *__restrict__ step_dev, float eps, float weight_decay) {
+                                            int64_t step_host, const int64_t *__restrict__ step_dev, float eps, float weight_decay,
+                                            bool coef_f64 = false) {
     const int64_t step = step_dev ? *step_dev : step_host;
     const double lr = lr_dev ? *lr_dev : lr_host;
     const float step_size = (float)(lr / (1.0 - ipow(beta1d, step)));
     const float bc2_sqrt = (float)sqrt(1.0 - ipow(beta2d, step));
     const float beta1 = (float)beta1d, beta2 = (float)beta2d;
+    // coef_f64: 1 - beta formed in f64 and rounded once, as torch's python scalars are (`lerp_(grad, 1 - beta1)`,
+    // `addcmul_(grad, grad, value=1 - beta2)`).  The default keeps the f32 difference of every caller before MADDPG, bit for
+    // bit: 1.f - 0.999f is 0.00099998713, 1.3e-5 below 0.001, which makes a step 6.4e-6 too long -- along the gradient's sign
+    // on every parameter, so a mean over a stepped net's outputs (MADDPG's actor loss) does not average it out.
+    const float omb1 = coef_f64 ? (float)(1.0 - beta1d) : 1.f - beta1, omb2 = coef_f64 ? (float)(1.0 - beta2d) : 1.f - beta2;
     const float pi = p[i];
     if (weight_decay != 0.f) g += weight_decay * pi;
-    const float mi = beta1 * m[i] + (1.f - beta1) * g;
-    const float vi = beta2 * v[i] + (1.f - beta2) * g * g;
+    const float mi = beta1 * m[i] + omb1 * g;
+    const float vi = beta2 * v[i] + omb2 * g * g;
     m[i] = mi;
     v[i] = vi;
     const float denom = sqrtf(vi) / bc2_sqrt + eps;

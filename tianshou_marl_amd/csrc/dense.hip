@@ -359,3 +359,51 @@ TSM_EXPORT int tsm_mlp_backward(const tsm_mlp_desc *d, const float *params, cons
     }
     return TSM_OK;
 }
+
+// Gradient w.r.t. a window of the net's INPUT: the dgrad chain of tsm_mlp_backward without its weight-gradient launches,
+// ended by dX[:, col0 : col0 + n_col] = dZ_0 . W_0[:, col0 : col0 + n_col] (no activation derivative: the input is not an
+// activation).  Serves the deterministic policy gradient of MADDPG (ctde.py:918-924: -critic_i(.., actor_i(obs_i), ..).mean()
+// backpropagated into the actor through the critic's action columns).
+TSM_EXPORT int tsm_mlp_input_grad(const tsm_mlp_desc *d, const float *params, const float *x, int64_t B, const float *acts,
+                                  const float *d_out, float *d_acts, int32_t col0, int32_t n_col, float *dx, int64_t ldx,
+                                  void *stream) {
+    if (int rc = check_desc(d, "tsm_mlp_input_grad")) return rc;
+    TSM_REQUIRE(B >= 1, "tsm_mlp_input_grad: batch must be >= 1");
+    TSM_REQUIRE(col0 >= 0 && n_col >= 1 && (int64_t)col0 + n_col <= d->dims[0],
+                "tsm_mlp_input_grad: columns [%d, %d + %d) leave the input width %d", col0, col0, n_col, d->dims[0]);
+    TSM_REQUIRE(ldx >= n_col, "tsm_mlp_input_grad: ldx = %lld smaller than n_col = %d", (long long)ldx, n_col);
+    TSM_REQUIRE(params && x && acts && d_out && dx, "tsm_mlp_input_grad: null pointer");
+    TSM_REQUIRE(d->n_layers == 1 || d_acts, "tsm_mlp_input_grad: d_acts workspace required for n_layers > 1");
+    TSM_REQUIRE(ceil_div(B, BM) <= 65535, "tsm_mlp_input_grad: batch too large for one launch");
+    const int L = d->n_layers;
+    int64_t p_off[TSM_MLP_MAX_LAYERS], a_off[TSM_MLP_MAX_LAYERS + 1];
+    {
+        int64_t po = 0, ao = 0;
+        for (int l = 0; l < L; ++l) {
+            p_off[l] = po;
+            a_off[l] = ao;  // block holding the OUTPUT of layer l
+            po += (int64_t)d->dims[l + 1] * d->dims[l] + d->dims[l + 1];
+            ao += B * d->dims[l + 1];
+        }
+    }
+    const float *dz = d_out;
+    for (int l = L - 1; l >= 0; --l) {
+        const int64_t K = d->dims[l], O = d->dims[l + 1];
+        const float *W = params + p_off[l];
+        GemmArgs g{};
+        g.A = dz; g.lda = O; g.M = B; g.K = O; g.k_per_split = O;
+        if (l > 0) {  // as tsm_mlp_backward: times the derivative of the previous layer's activation
+            float *da = d_acts + a_off[l - 1];
+            g.B = W; g.ldb = K; g.N = K;
+            g.C = da; g.ldc = K; g.X = acts + a_off[l - 1]; g.ldx = K; g.act = d->act;
+            dz = da;
+        } else {      // the window of W_0's columns; rows of W_0 keep their pitch
+            g.B = W + col0; g.ldb = K; g.N = n_col;
+            g.C = dx; g.ldc = ldx; g.act = 0;
+        }
+        dim3 grid((unsigned)ceil_div(g.N, BN), (unsigned)ceil_div(B, BM), 1);
+        hipLaunchKernelGGL((gemm_kernel<false, true, EPI_DGRAD, 1>), grid, dim3(NT), 0, tsm_stream(stream), g);
+        TSM_LAUNCH_CHECK();
+    }
+    return TSM_OK;
+}

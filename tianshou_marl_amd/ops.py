@@ -361,13 +361,16 @@ def ppo_loss_fwd_bwd(logits, value, act, logp_old, adv, returns, cfg: tsm_ppo_cf
 # optimizer (algorithm_base.py:485-498; optim.py:91-111)
 # --------------------------------------------------------------------------------------------
 def adam_step(param, grad_slabs, exp_avg, exp_avg_sq, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-              weight_decay=0.0, max_grad_norm=None, work=None, step_dev=None, image=None, image_map=None, lr_dev=None):
-    """In-place Adam on a flat f32 vector; grad_slabs [n_slab, n] are summed in slab order."""
+              weight_decay=0.0, max_grad_norm=None, work=None, step_dev=None, image=None, image_map=None, lr_dev=None,
+              coef64=False):
+    """In-place Adam on a flat f32 vector; grad_slabs [n_slab, n] are summed in slab order.  coef64: 1 - beta formed in f64
+    and rounded once, as torch forms them (include/tsmarl.h: tsm_adam_step_coef64)."""
     n = param.numel()
     grad_slabs = _chk(grad_slabs, torch.float32, "grad_slabs").reshape(-1, n)
     if max_grad_norm and work is None:
         work = torch.empty(call("tsm_adam_work_elems", n), dtype=torch.float32, device=param.device)
-    call("tsm_adam_step", ptr(param), ptr(grad_slabs), grad_slabs.shape[0], n, ptr(exp_avg), ptr(exp_avg_sq),
+    call("tsm_adam_step_coef64" if coef64 else "tsm_adam_step", ptr(param), ptr(grad_slabs), grad_slabs.shape[0], n, ptr(exp_avg),
+         ptr(exp_avg_sq),
          int(step), ptr(step_dev), float(lr), ptr(lr_dev), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
          float(max_grad_norm or 0.0), ptr(work), ptr(image), ptr(image_map), stream_ptr())
     return param
@@ -1025,6 +1028,129 @@ def qmix_egreedy(q, eps_dev, seed: int, offset: int = 0, offset_dev=None, out=No
 
 
 # --------------------------------------------------------------------------------------------
+# MADDPG (ctde.py:728-955; csrc/maddpg.hip)
+# --------------------------------------------------------------------------------------------
+def maddpg_check(n_agents: int, act_dim: int | None = None) -> None:
+    """The bounds of the MADDPG kernels (include/tsmarl.h): ValueError naming the limit."""
+    if not 1 <= n_agents <= _abi.MADDPG_MAX_AGENTS:
+        raise ValueError(f"MADDPG: n_agents = {n_agents}; the HIP kernels serve 1 to {_abi.MADDPG_MAX_AGENTS} agents")
+    if act_dim is not None and act_dim < 1:
+        raise ValueError(f"MADDPG: act_dim = {act_dim}; at least one action component is needed")
+
+
+def _ptr_array(ts, name: str):
+    return (C.c_void_p * len(ts))(*[ptr(_chk(t, torch.float32, name)) for t in ts])
+
+
+def maddpg_joint_rows(obs, act, replace=None, out=None):
+    """The centralized critics' inputs (ctde.py:875-880, 888, 893, 913-919) in one launch.  obs: per agent [B, D]; act: per
+    agent [B, Ad].  replace=None -> [B, W] rows [obs_0 .. obs_{N-1} | act_0 .. act_{N-1}], W = N (D + Ad); replace = per
+    agent [B, Ad] -> [N, B, W], matrix m carrying replace[m] in agent m's action slot."""
+    N = len(obs)
+    B, D = obs[0].shape
+    Ad = act[0].shape[1]
+    maddpg_check(N, Ad)
+    if len(act) != N or (replace is not None and len(replace) != N):
+        raise ValueError("maddpg_joint_rows: obs, act and replace need one entry per agent")
+    for k in range(N):
+        if tuple(obs[k].shape) != (B, D) or tuple(act[k].shape) != (B, Ad) or (
+                replace is not None and tuple(replace[k].shape) != (B, Ad)):
+            raise ValueError(f"maddpg_joint_rows: agent {k}: expected obs [{B}, {D}], act [{B}, {Ad}]")
+    W = N * (D + Ad)
+    shape = (B, W) if replace is None else (N, B, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=obs[0].device)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f"maddpg_joint_rows: out must be {shape}")
+    call("tsm_maddpg_joint_rows", _ptr_array(obs, "obs"), _ptr_array(act, "act"),
+         None if replace is None else _ptr_array(replace, "replace"), N, B, D, Ad, ptr(_chk(out, torch.float32, "out")),
+         stream_ptr())
+    return out
+
+
+def maddpg_partial_elems(B: int, n_agents: int) -> int:
+    return call("tsm_maddpg_partial_elems", B, n_agents)
+
+
+def maddpg_td(q, q_next, rew, term, gamma: float, out=None):
+    """TD target, MSE and its gradient for every agent in one launch (ctde.py:895-898).  Per agent: q, q_next, rew f32 [B]
+    (or [B, 1]), term u8 / bool [B] -- agent i's OWN flags.  -> (dq per agent [B], partial f64)."""
+    N = len(q)
+    B = q[0].numel()
+    maddpg_check(N)
+    if not (len(q_next) == len(rew) == len(term) == N):
+        raise ValueError("maddpg_td: q, q_next, rew and term need one entry per agent")
+    term = [t.contiguous().view(torch.uint8) if t.dtype == torch.bool else _chk(t, torch.uint8, "term") for t in term]
+    for k in range(N):
+        if not (q[k].numel() == q_next[k].numel() == rew[k].numel() == term[k].numel() == B):
+            raise ValueError(f"maddpg_td: agent {k}: every array needs {B} entries")
+    dev = q[0].device
+    if out is None:
+        dq = [torch.empty(B, dtype=torch.float32, device=dev) for _ in range(N)]
+        partial = torch.empty(maddpg_partial_elems(B, N), dtype=torch.float64, device=dev)
+    else:
+        dq, partial = out
+    ag = _abi.tsm_maddpg_agents()
+    for k in range(N):
+        ag.q[k] = ptr(_chk(q[k], torch.float32, "q"))
+        ag.q_next[k] = ptr(_chk(q_next[k], torch.float32, "q_next"))
+        ag.rew[k] = ptr(_chk(rew[k], torch.float32, "rew"))
+        ag.term[k] = ptr(term[k])
+        ag.dq[k] = ptr(_chk(dq[k], torch.float32, "dq"))
+    call("tsm_maddpg_td", C.byref(ag), N, B, float(gamma), ptr(_chk(partial, torch.float64, "partial")), stream_ptr())
+    return dq, partial
+
+
+def maddpg_finalize(partial, q_pi, B: int, out):
+    """out[2 i] = actor_loss_i = -mean(q_pi[i]), out[2 i + 1] = critic_loss_i from tsm_maddpg_td's partials (one launch,
+    fixed summation order).  out: device f32 [2 N] or pinned host f32 [2 N]."""
+    N = len(q_pi)
+    maddpg_check(N)
+    if out.is_cuda:
+        out_p = ptr(out)
+    elif out.is_pinned() and out.is_contiguous() and out.dtype == torch.float32:
+        out_p = out.data_ptr()
+    else:
+        raise RuntimeError("maddpg_finalize: out must be a device tensor or pinned host memory (f32)")
+    if out.numel() < 2 * N or any(x.numel() != B for x in q_pi):
+        raise ValueError(f"maddpg_finalize: out needs {2 * N} entries and every q_pi {B}")
+    partial = _chk(partial, torch.float64, "partial")
+    call("tsm_maddpg_finalize", ptr(partial), partial.numel() // N, _ptr_array(q_pi, "q_pi"), N, B, out_p, stream_ptr())
+    return out
+
+
+def maddpg_act(mu, sigma_dev, seed: int, offset: int = 0, offset_dev=None, low=None, high=None, out=None):
+    """The acting epilogue: mu per agent [E, Ad] -> act f32 [E * N, Ad] (row e * N + i), plus *sigma_dev times a standard
+    normal draw, clamped to [low, high] (device f32 [Ad], both or neither)."""
+    N = len(mu)
+    E, Ad = mu[0].shape
+    maddpg_check(N, Ad)
+    if any(tuple(m.shape) != (E, Ad) for m in mu):
+        raise ValueError(f"maddpg_act: every actor output must be [{E}, {Ad}]")
+    if (low is None) != (high is None) or (low is not None and (low.numel() != Ad or high.numel() != Ad)):
+        raise ValueError(f"maddpg_act: low and high come together, {Ad} entries each")
+    if out is None:
+        out = torch.empty(E * N, Ad, dtype=torch.float32, device=mu[0].device)
+    elif out.numel() != E * N * Ad:
+        raise ValueError(f"maddpg_act: out needs {E * N * Ad} entries")
+    call("tsm_maddpg_act", _ptr_array(mu, "mu"), N, E, Ad, ptr(_chk(sigma_dev, torch.float32, "sigma_dev")),
+         seed & (2**64 - 1), offset & (2**64 - 1), ptr(offset_dev),
+         ptr(None if low is None else _chk(low, torch.float32, "low")),
+         ptr(None if high is None else _chk(high, torch.float32, "high")), ptr(_chk(out, torch.float32, "out")), stream_ptr())
+    return out
+
+
+def polyak(target, param, tau: float):
+    """target <- tau * param + (1 - tau) * target in place (update_target_networks, ctde.py:936-955), bit for bit the torch
+    expression on f32 device tensors."""
+    target, param = _chk(target, torch.float32, "target"), _chk(param, torch.float32, "param")
+    if target.numel() != param.numel():
+        raise ValueError("polyak: target and param differ in size")
+    call("tsm_polyak", ptr(target), ptr(param), target.numel(), float(tau), stream_ptr())
+    return target
+
+
+# --------------------------------------------------------------------------------------------
 # fully-connected networks of arbitrary width (csrc/dense.hip)
 # --------------------------------------------------------------------------------------------
 _ACT = {"none": 0, None: 0, "relu": 1, "tanh": 2}
@@ -1180,6 +1306,26 @@ def mlp_backward(desc, params, x, acts, d_out, n_split: int = 0, slabs=None, sla
     call("tsm_mlp_backward", C.byref(desc), ptr(params), ptr(x), B, ptr(acts), ptr(d_out), ptr(d_acts), n_split,
          slabs.data_ptr(), slab_stride, stream_ptr())
     return slabs
+
+
+def mlp_input_grad(desc, params, x, acts, d_out, col0: int, n_col: int, out=None, d_acts=None):
+    """Gradient of sum(out * d_out) w.r.t. the input columns [col0, col0 + n_col) -> [B, n_col]; no weight gradients are
+    computed (include/tsmarl.h: tsm_mlp_input_grad).  `acts`: the activations of mlp_forward on x."""
+    x, d_out = _chk(x, torch.float32, "x"), _chk(d_out, torch.float32, "d_out")
+    B = x.shape[0]
+    if not (0 <= col0 and n_col >= 1 and col0 + n_col <= desc.dims[0]):
+        raise ValueError(f"mlp_input_grad: columns [{col0}, {col0 + n_col}) leave the input width {desc.dims[0]}")
+    if d_out.numel() != B * desc.dims[desc.n_layers]:
+        raise ValueError("mlp_input_grad: d_out must be [B, dims[-1]]")
+    if out is None:
+        out = torch.empty(B, n_col, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (B, n_col):
+        raise ValueError(f"mlp_input_grad: out must be [{B}, {n_col}]")
+    if d_acts is None:
+        d_acts = torch.empty_like(acts)
+    call("tsm_mlp_input_grad", C.byref(desc), ptr(_chk(params, torch.float32, "params")), ptr(x), B, ptr(acts), ptr(d_out),
+         ptr(d_acts), col0, n_col, ptr(_chk(out, torch.float32, "out")), n_col, stream_ptr())
+    return out
 
 
 def device_info() -> dict:

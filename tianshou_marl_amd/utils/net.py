@@ -213,6 +213,15 @@ class FlatMLP(nn.Module):
         return ops.mlp_backward(self.desc, self.flat.data, x2, acts, d_out.reshape(x2.shape[0], self.dims[-1]).contiguous(),
                                 n_split, slabs=slabs, slab_stride=slab_stride)
 
+    def input_grad(self, d_out: torch.Tensor, col0: int, n_col: int, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Gradient [B, n_col] w.r.t. the input columns [col0, col0 + n_col) of the last `forward(save=True)`; no weight
+        gradient is computed (the critic's side of a deterministic policy gradient)."""
+        if self._saved is None:
+            raise RuntimeError("FlatMLP.input_grad called before forward")
+        x2, acts = self._saved
+        return ops.mlp_input_grad(self.desc, self.flat.data, x2, acts, d_out.reshape(x2.shape[0], self.dims[-1]), col0, n_col,
+                                  out=out)
+
     # reference module key names: fc1/fc2/fc3 (ctde.py:362-364, 398-400)
     def to_reference_state_dict(self) -> OrderedDict:
         sd = OrderedDict()
@@ -290,7 +299,8 @@ class FlatAdam:
     `optim.Adam(module.parameters(), lr=...)` stands in the reference's CTDE constructors (ctde.py:36-37)."""
 
     def __init__(self, module, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 max_grad_norm: float | None = None) -> None:
+                 max_grad_norm: float | None = None, coef64: bool = False) -> None:
+        self.coef64 = bool(coef64)  # `step` runs tsm_adam_step_coef64: torch's own f32 coefficients 1 - beta
         self.param = module.flat.data if hasattr(module, "flat") else module
         self._module = module
         self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm = lr, betas, eps, weight_decay, max_grad_norm
@@ -307,7 +317,7 @@ class FlatAdam:
         self.step_count += 1
         ops.adam_step(self.param, grad_slabs, self.exp_avg, self.exp_avg_sq, self.step_count, lr=self.lr,
                       betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, max_grad_norm=self.max_grad_norm,
-                      work=self._work)
+                      work=self._work, coef64=self.coef64)
 
     def step_segs(self, segs: list, step_dev: torch.Tensor | None = None) -> None:
         """`step` for gradients that arrive as several slab arrays (ops.adam_step_segs: segments tiling the vector, each
