@@ -30,6 +30,7 @@ from ... import ops
 from ...data.batch import Batch
 from ...data.stats import LazyDict, ResultRing, pinned_slot, recycle
 from ...utils.net import FlatAdam, FlatMLP
+from ...utils.tensor import to_tensor
 
 
 class DecentralizedActor(FlatMLP):
@@ -119,8 +120,7 @@ class CTDEPolicy(nn.Module):
         return self.actor.flat.device
 
     def _t(self, x, dtype) -> torch.Tensor:
-        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-        return t.to(self.device, dtype).contiguous()
+        return to_tensor(x, self.device, dtype)
 
     def forward(self, batch: Batch, state: Any = None, **kwargs: Any) -> Batch:
         """Decentralized execution (ctde.py:85-119): `act` holds the actor's raw output (logits), as upstream."""

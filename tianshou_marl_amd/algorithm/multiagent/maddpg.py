@@ -32,6 +32,7 @@ from ... import ops
 from ...data.batch import Batch
 from ...data.stats import ResultRing, pinned_slot
 from ...utils.net import FlatAdam, FlatMLP
+from ...utils.tensor import to_tensor
 from .ctde import LazyScalars
 
 
@@ -159,8 +160,7 @@ class MADDPGPolicy(nn.Module):
         self._sigma_dev.fill_(self._noise_std)
 
     def _t(self, x, dtype) -> torch.Tensor:
-        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-        return t.to(self.device, dtype).contiguous()
+        return to_tensor(x, self.device, dtype)
 
     # ---- host acting path (ctde.py:790-815) ----------------------------------------------------------------
     def forward(self, batch: Batch, state: Any = None, **kwargs: Any) -> Batch:

@@ -27,6 +27,7 @@ from ... import ops
 from ...data.batch import Batch
 from ...data.stats import ResultRing, pinned_slot
 from ...utils.net import FlatAdam, FlatMLP
+from ...utils.tensor import to_tensor
 from .ctde import LazyScalars
 
 _HYPER = ("hyper_w1", "hyper_w2", "hyper_b1", "hyper_b2")
@@ -197,8 +198,7 @@ class QMIXPolicy(nn.Module):
         self._eps_dev.fill_(self._epsilon)
 
     def _t(self, x, dtype) -> torch.Tensor:
-        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-        return t.to(self.device, dtype).contiguous()
+        return to_tensor(x, self.device, dtype)
 
     # ---- host acting path (ctde.py:557-616) ----------------------------------------------------------------
     def _act_host(self, actor: FlatMLP, obs) -> torch.Tensor:

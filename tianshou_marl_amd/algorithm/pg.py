@@ -24,6 +24,7 @@ from .. import ops
 from ..data.buffer import DeviceVectorReplayBuffer
 from ..data.stats import SequenceSummaryStats, TrainingStats
 from ..utils.net import DiscreteActorCritic
+from ..utils.tensor import to_tensor
 from .ppo import PPO
 
 
@@ -122,7 +123,7 @@ class Reinforce(PPO):
     def learn(self, batch, batch_size: int | None = None, repeat: int = 1, **kwargs) -> dict[str, float]:
         """One Reinforce pass on an explicit agent batch (one time-ordered lane; the last row ends the lane)."""
         dev = self.device
-        t = lambda x, dt: (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))).to(dev, dt).contiguous()  # noqa: E731
+        t = lambda x, dt: to_tensor(x, dev, dt)  # noqa: E731
         obs = t(batch.obs, torch.float32)
         n = obs.shape[0]
         term = t(batch.terminated, torch.uint8).reshape(n, 1)

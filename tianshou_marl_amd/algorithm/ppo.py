@@ -27,6 +27,7 @@ from ..data.buffer import DeviceVectorReplayBuffer
 from ..data.stats import (A2CTrainingStats, LazyDict, MapTrainingStats, ResultRing, lazy_training_stats, pinned_slot,
                           training_stats_from_steps)
 from ..utils.net import DeviceRunningMeanStd, DiscreteActorCritic
+from ..utils.tensor import to_tensor
 
 
 class PPO(nn.Module):
@@ -353,6 +354,73 @@ class PPO(nn.Module):
         ops.call("tsm_u64_add", ops.ptr(self._perm_ctr), 1, ops.stream_ptr())
         return perm
 
+    def _minibatch_plan(self, n: int, batch_size: int | None, reps: int, defer: bool, agree: bool = True) -> dict:
+        """What the gradient steps of `reps` passes over n rows need besides the rows: the minibatch `bounds` (Batch.split's
+        merge-last rule) and their starts on the device, and where the steps write -- the gradient slabs, the flat gradient
+        of a data-parallel replica, and the loss partials.  defer: the partials of EVERY step stay (one row per step) until
+        ONE `ppo_finalize_many` launch behind the captured sequence folds them, which reads `nb_dev` / `M_dev`; otherwise
+        each step folds its own.  agree: data-parallel replicas make sure here that they take the same number of steps
+        (a collective -- on every eager update, at capture time for a graph: `GradSync.require_equal`)."""
+        dev, P = self.device, self.net.flat.data
+        bounds = split_bounds(n, batch_size or -1, merge_last=True)
+        n_steps = reps * len(bounds)
+        if agree and self._grad_sync is not None:
+            self._grad_sync.require_equal(n_steps, "the number of gradient steps per update")
+        grids = [ops.ppo_update_grid(e - s) for s, e in bounds]
+        # the grid is not monotone in the minibatch size (ops.ppo_update_grid): size the slabs / partials for the largest grid
+        nb_max = max(grids)
+        plan = dict(bounds=bounds, n_steps=n_steps, nb_max=nb_max, max_rows=max(e - s for s, e in bounds),
+                    mb_start=torch.as_tensor([b[0] for b in bounds] + [n], dtype=torch.int64, device=dev))
+        if defer:  # static allocations of one captured sequence
+            plan.update(slabs=torch.zeros(nb_max, P.numel(), dtype=torch.float32, device=dev),
+                        partial=torch.zeros(n_steps, nb_max * 4, dtype=torch.float64, device=dev),
+                        nb_dev=torch.as_tensor(grids * reps, dtype=torch.int32, device=dev),
+                        M_dev=torch.as_tensor([e - s for s, e in bounds] * reps, dtype=torch.int64, device=dev),
+                        flat_g=torch.zeros_like(P) if self._grad_sync is not None else None)
+            return plan
+        slabs = self._ws.get(("slabs", nb_max))
+        if slabs is None:
+            slabs = self._ws[("slabs", nb_max)] = torch.empty(nb_max, P.numel(), dtype=torch.float32, device=dev)
+        plan.update(slabs=slabs, partial=torch.empty(nb_max * 4, dtype=torch.float64, device=dev),
+                    flat_g=self._ws.setdefault("flat_grad", torch.empty_like(P)) if self._grad_sync is not None else None)
+        return plan
+
+    def _grad_step_steps(self, pb: dict, idx: torch.Tensor, adv_stats, step_dev: torch.Tensor | None = None, *, plan: dict,
+                         partial: torch.Tensor, image: torch.Tensor | None, scalars: torch.Tensor | None = None):
+        """One gradient step of the fused 64-wide net: forward, loss and backward into the slabs in ONE launch, then the
+        optimizer.  A generator: a data-parallel replica YIELDS the flat gradient (scaled by 1 / world) where it has to be
+        summed over the ranks and continues with Adam once the caller has reduced it in place (`drive_steps`: one
+        all-reduce; `parallel.learn_lockstep`: several policy groups packed into one; captured: `ops.capture_steps`).
+        pb: obs, act, logp_old, adv, ret (and v_s when value-clipping) of ALL rows; idx: the minibatch's slice of the
+        permutation; adv_stats: its (mean, std); plan: `_minibatch_plan` (slabs, flat gradient); partial: the step's loss
+        partials.  step_dev: the device-resident optimizer step count (captured sequences), None = the host counter.
+        image: the padded parameter image the kernel reads, None = read `flat` itself (the first step of a captured
+        sequence: the image may be stale).  scalars: where the step's 4 loss statistics go; None = deferred (see
+        `_minibatch_plan`)."""
+        P, gs = self.net.flat.data, self._grad_sync
+        M = idx.numel()
+        nb = ops.ppo_update_grid(M)
+        ops.ppo_update_fused(P, pb["obs"], pb["act"], pb["logp_old"], pb["adv"], pb["ret"], self._cfg, self.net.n_act,
+                             self.net.hidden, adv_stats=adv_stats, v_s_old=pb["v_s"] if self.value_clip else None, perm=idx,
+                             image=image, M=M, n_blocks=nb, slabs=plan["slabs"][:nb], partial=partial, scalars=scalars,
+                             want_scalars=scalars is not None, opt_step_dev=step_dev)
+        if step_dev is None:
+            self.opt_step += 1
+        grads = plan["slabs"][:nb]
+        hyper = dict(lr=self.lr, lr_dev=self._lr_dev, betas=self.betas, eps=self.adam_eps, weight_decay=self.weight_decay,
+                     step_dev=step_dev, image=self.net.image, image_map=self.net.image_map)
+        step = self.opt_step if step_dev is None else 1
+        if gs is not None and gs.fused_step_ok(self.max_grad_norm, P.numel()):
+            # peer-memory path: slab sum, sum over the replicas and Adam in ONE launch (csrc/p2p.hip)
+            gs.p2p.adam_step(P, grads, self.exp_avg, self.exp_avg_sq, step, **hyper)
+            return
+        if gs is not None:  # env-sharded data parallel: ONE flat all-reduce (parallel.py)
+            ops.reduce_slabs(grads, out=plan["flat_g"], scale=1.0 / gs.world)  # mean = sum of g_i / world
+            yield plan["flat_g"]  # summed over the ranks by the driver, in place
+            grads = plan["flat_g"].view(1, -1)
+        ops.adam_step(P, grads, self.exp_avg, self.exp_avg_sq, step, max_grad_norm=self.max_grad_norm, work=self._adam_work,
+                      **hyper)
+
     def _update_steps(self, pb: dict, batch_size: int | None, repeat: int, agent: int | None = None,
                       buffer: DeviceVectorReplayBuffer | None = None, perm_base: int | None = None):
         """The minibatch loop as a generator: with data-parallel replicas it YIELDS the flat gradient of each gradient
@@ -363,20 +431,9 @@ class PPO(nn.Module):
         ids = self._sample_ids(pb, agent)
         n = ids.numel() if ids is not None else pb["obs"].shape[0]
         dev = self.device
-        bounds = split_bounds(n, batch_size or -1, merge_last=True)
-        mb_start = torch.as_tensor([b[0] for b in bounds] + [n], dtype=torch.int64, device=dev)
-        P, A, H = self.net.flat.data, self.net.n_act, self.net.hidden
-        n_steps = repeat * len(bounds)
-        if self._grad_sync is not None:
-            self._grad_sync.require_equal(n_steps, "the number of gradient steps per update")
-        scal = torch.zeros(n_steps, 4, dtype=torch.float32, device=dev)
-        # the grid is not monotone in the minibatch size (ops.ppo_update_grid): size the slabs for the largest grid
-        n_blk_max = max(ops.ppo_update_grid(e - s) for s, e in bounds)
-        slabs = self._ws.get(("slabs", n_blk_max))
-        if slabs is None:
-            slabs = torch.empty(n_blk_max, P.numel(), dtype=torch.float32, device=dev)
-            self._ws[("slabs", n_blk_max)] = slabs
-        partial = torch.empty(n_blk_max * 4, dtype=torch.float64, device=dev)
+        plan = self._minibatch_plan(n, batch_size, repeat, defer=False)
+        bounds, mb_start = plan["bounds"], plan["mb_start"]
+        scal = torch.zeros(plan["n_steps"], 4, dtype=torch.float32, device=dev)
         k = 0
         for step in range(repeat):
             if self.recompute_adv and step > 0:  # ppo.py:174-178: returns / advantages only, logp_old stays
@@ -386,34 +443,12 @@ class PPO(nn.Module):
             else:
                 perm_local = self._device_perm(n, perm_base, agent, repeat, step)
             perm = perm_local if ids is None else ids[perm_local]
-            stats = (ops.ppo_adv_stats(pb["adv"], mb_start, perm=perm, max_rows=max(e - s for s, e in bounds))
+            stats = (ops.ppo_adv_stats(pb["adv"], mb_start, perm=perm, max_rows=plan["max_rows"])
                      if self.advantage_normalization else None)
             self._global_adv_stats(stats, mb_start)
             for j, (s, e) in enumerate(bounds):
-                M = e - s
-                nb = ops.ppo_update_grid(M)
-                ops.ppo_update_fused(P, pb["obs"], pb["act"], pb["logp_old"], pb["adv"], pb["ret"], self._cfg, A, H,
-                                     adv_stats=None if stats is None else stats[j],
-                                     v_s_old=pb["v_s"] if self.value_clip else None, perm=perm[s:e], image=self.net.image, M=M,
-                                     n_blocks=nb, slabs=slabs[:nb], partial=partial, scalars=scal[k])
-                self.opt_step += 1
-                grads = slabs[:nb]
-                if self._grad_sync is not None and self._grad_sync.fused_step_ok(self.max_grad_norm, P.numel()):
-                    # peer-memory path: slab sum, sum over the replicas and Adam in ONE launch (csrc/p2p.hip)
-                    self._grad_sync.p2p.adam_step(P, grads, self.exp_avg, self.exp_avg_sq, self.opt_step, lr=self.lr,
-                                                  lr_dev=self._lr_dev, betas=self.betas, eps=self.adam_eps,
-                                                  weight_decay=self.weight_decay, image=self.net.image, image_map=self.net.image_map)
-                    k += 1
-                    continue
-                if self._grad_sync is not None:  # env-sharded data parallel: ONE flat all-reduce (parallel.py)
-                    flat_g = self._ws.setdefault("flat_grad", torch.empty_like(P))
-                    ops.reduce_slabs(grads, out=flat_g, scale=1.0 / self._grad_sync.world)  # mean = sum of g_i / world
-                    yield flat_g  # summed over the ranks by the driver, in place
-                    grads = flat_g.view(1, -1)
-                ops.adam_step(P, grads, self.exp_avg, self.exp_avg_sq, self.opt_step, lr=self.lr, lr_dev=self._lr_dev,
-                              betas=self.betas, eps=self.adam_eps, weight_decay=self.weight_decay,
-                              max_grad_norm=self.max_grad_norm, work=self._adam_work, image=self.net.image,
-                              image_map=self.net.image_map)
+                yield from self._grad_step_steps(pb, perm[s:e], None if stats is None else stats[j], plan=plan,
+                                                 partial=plan["partial"], image=self.net.image, scalars=scal[k])
                 k += 1
         self.param_version += 1
         if self._grad_sync is not None:
@@ -444,6 +479,40 @@ class PPO(nn.Module):
         torch.cuda.synchronize()
         self._ws["warm"] = True
 
+    def _sum_over_ranks(self, t: torch.Tensor) -> None:
+        """What a launch sequence's yielded tensors meet (`ops.capture_steps` / `replay_steps`): the replicas' all-reduce."""
+        if self._grad_sync is None:
+            raise RuntimeError("a single-GPU update has no collectives")
+        self._grad_sync.all_reduce_sum_(t)
+
+    def _ref_ids(self, T: int, B: int, N: int, groups: list, row_mode: bool = False) -> list:
+        """shuffle="numpy": per agent group, position of the reference batch (sample(0) order) -> lane id of the time-major
+        stores (joint-row id with row minibatches)."""
+        base = ref_order_rows(T, B, self.device)
+        return [base if row_mode else base * N + a if a is not None else
+                (base[:, None] * N + torch.arange(N, device=self.device)[None, :]).reshape(-1) for a in groups]
+
+    def _refill_host_perms(self, w: dict) -> None:
+        """shuffle="numpy": this update's permutations, one per agent group and repeat as Batch.split draws them
+        (batch.py:1219), into the captured sequence's `w["perm"]`."""
+        if self.shuffle != "numpy":
+            return
+        n_g = w["perm"].shape[2]
+        for gi in range(w["perm"].shape[0]):
+            for r in range(w["perm"].shape[1]):
+                pl = torch.as_tensor(np.random.permutation(n_g)).to(self.device)
+                w["perm"][gi, r].copy_(w["ref_ids"][gi][pl])
+
+    def _refill_step_dev(self, w: dict) -> None:
+        if w.get("step_host") != self.opt_step:  # the device-side step count is stale (eager updates, a loaded checkpoint)
+            w["step_dev"].fill_(self.opt_step)
+
+    def _account_steps(self, w: dict) -> None:
+        """Behind a replay: the host's counters follow what the captured steps did to the device's."""
+        self.opt_step += w["n_steps"]
+        w["step_host"] = self.opt_step
+        self.param_version += 1
+
     def _update_graph(self, buffer: DeviceVectorReplayBuffer, batch_size: int | None, repeat: int):
         T = buffer.host_uniform_len()  # host mirror of the fill level (no device round trip)
         if T is None and self._grad_sync is not None:
@@ -464,7 +533,6 @@ class PPO(nn.Module):
         per_agent = self.dispatch == "per_agent"
         groups = list(range(N)) if per_agent else [None]
         n_g = T * B if per_agent else T * L
-        bounds = split_bounds(n_g, batch_size or -1, merge_last=True)
         # (the rollout's stored V(obs_next) is that of the TRUE next observation: not what an ignore_obs_next buffer hands out)
         stored = buffer.vnext_store is not None and buffer.policy_outputs_version == self.param_version and not no_next
         key = ("graph", buffer.storage_key(), T, batch_size, repeat, self.dispatch, self.max_grad_norm, stored,
@@ -473,23 +541,13 @@ class PPO(nn.Module):
         P, A, H = self.net.flat.data, self.net.n_act, self.net.hidden
         if g is None:
             self._warm_kernels(buffer)
-            n_steps = len(groups) * repeat * len(bounds)
-            if self._grad_sync is not None:
-                self._grad_sync.require_equal(n_steps, "the number of gradient steps per update")
-            # the grid is not monotone in the minibatch size: size the slabs / partials for the largest grid
-            nb_max = max(ops.ppo_update_grid(e - s) for s, e in bounds)
+            w = self._minibatch_plan(n_g, batch_size, len(groups) * repeat, defer=True)
+            bounds, n_steps = w["bounds"], w["n_steps"]
             f = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)  # noqa: E731
-            w = dict(perm=torch.zeros(len(groups), repeat, n_g, dtype=torch.int64, device=dev),
-                     mb_start=torch.as_tensor([b[0] for b in bounds] + [n_g], dtype=torch.int64, device=dev),
-                     stats=f(len(groups), repeat, len(bounds), 2), scal=f(n_steps, 4), slabs=f(nb_max, P.numel()),
-                     partial=torch.zeros(n_steps, nb_max * 4, dtype=torch.float64, device=dev), nb_max=nb_max,
-                     nb_dev=torch.as_tensor([ops.ppo_update_grid(e - s) for s, e in bounds] * (len(groups) * repeat),
-                                            dtype=torch.int32, device=dev),
-                     M_dev=torch.as_tensor([e - s for s, e in bounds] * (len(groups) * repeat), dtype=torch.int64,
-                                           device=dev),
-                     perm_ctr=self._perm_ctr,
+            w.update(perm=torch.zeros(len(groups), repeat, n_g, dtype=torch.int64, device=dev),
+                     stats=f(len(groups), repeat, len(bounds), 2), scal=f(n_steps, 4), perm_ctr=self._perm_ctr,
                      step_dev=torch.zeros(1, dtype=torch.int64, device=dev), v_s=f(T, L), v_next=f(T, L),
-                     logp=f(T * L), ret=f(T, L), adv=f(T, L), n_steps=n_steps, flat_g=f(P.numel()))
+                     logp=f(T * L), ret=f(T, L), adv=f(T, L))
             obs = buffer.obs_store[:T].reshape(T * L, D)
             obs_next = None if no_next else buffer.obs_next_store[:T].reshape(T * L, D)
             act = buffer.act_store[:T].reshape(T * L)
@@ -545,8 +603,10 @@ class PPO(nn.Module):
                 preprocess()
                 if "mb_start_all" in w:
                     ops.ppo_adv_stats(w["adv"], w["mb_start_all"], perm=w["perm"].view(-1), out=w["stats"].view(-1, 2),
-                                      max_rows=max(e - s for s, e in bounds))
+                                      max_rows=w["max_rows"])
                     yield from self._global_adv_stats_steps(w["stats"].view(-1, 2), w["mb_start_all"])
+                pb = dict(obs=obs, act=act, logp_old=w["logp"], adv=w["adv"].view(-1), ret=w["ret"].view(-1),
+                          v_s=w["v_s"].view(-1))
                 k = 0
                 for gi in range(len(groups)):
                     for r in range(repeat):
@@ -555,88 +615,30 @@ class PPO(nn.Module):
                         perm = w["perm"][gi, r]
                         if self.advantage_normalization and "mb_start_all" not in w:
                             ops.ppo_adv_stats(w["adv"], w["mb_start"], perm=perm, out=w["stats"][gi, r],
-                                              max_rows=max(e - s for s, e in bounds))
+                                              max_rows=w["max_rows"])
                             yield from self._global_adv_stats_steps(w["stats"][gi, r], w["mb_start"])
                         for j, (s, e) in enumerate(bounds):
-                            nb = ops.ppo_update_grid(e - s)
-                            ops.ppo_update_fused(P, obs, act, w["logp"], w["adv"].view(-1), w["ret"].view(-1), self._cfg,
-                                                 A, H, adv_stats=w["stats"][gi, r, j] if self.advantage_normalization else None,
-                                                 v_s_old=w["v_s"].view(-1) if self.value_clip else None, perm=perm[s:e],
-                                                 image=self.net.image if k > 0 else None,  # k == 0: image may be stale
-                                                 M=e - s, n_blocks=nb, slabs=w["slabs"][:nb], partial=w["partial"][k],
-                                                 want_scalars=False, opt_step_dev=w["step_dev"])
-                            grads = w["slabs"][:nb]
-                            if self._grad_sync is not None and self._grad_sync.fused_step_ok(self.max_grad_norm, P.numel()):
-                                # peer-memory path: slab sum + sum over the replicas + Adam, ONE launch per gradient step
-                                self._grad_sync.p2p.adam_step(P, grads, self.exp_avg, self.exp_avg_sq, 1, lr=self.lr,
-                                                              lr_dev=self._lr_dev, betas=self.betas, eps=self.adam_eps,
-                                                              weight_decay=self.weight_decay, step_dev=w["step_dev"],
-                                                              image=self.net.image, image_map=self.net.image_map)
-                                k += 1
-                                continue
-                            if self._grad_sync is not None:  # env-sharded replicas: one captured RCCL all-reduce
-                                ops.reduce_slabs(grads, out=w["flat_g"], scale=1.0 / self._grad_sync.world)
-                                yield w["flat_g"]  # summed over the ranks, in place
-                                grads = w["flat_g"].view(1, -1)
-                            ops.adam_step(P, grads, self.exp_avg, self.exp_avg_sq, 1, lr=self.lr, lr_dev=self._lr_dev,
-                                          betas=self.betas, eps=self.adam_eps, weight_decay=self.weight_decay,
-                                          max_grad_norm=self.max_grad_norm, work=self._adam_work,
-                                          step_dev=w["step_dev"], image=self.net.image, image_map=self.net.image_map)
+                            yield from self._grad_step_steps(
+                                pb, perm[s:e], w["stats"][gi, r, j] if self.advantage_normalization else None, w["step_dev"],
+                                plan=w, partial=w["partial"][k], image=self.net.image if k > 0 else None)  # k == 0: image may be stale
                             k += 1
                 # (the 4 loss statistics of every gradient step are folded from w["partial"] by ONE launch after the
                 # replay, straight into the pinned slot the host will read)
 
-            def run_inline():  # collectives inside the capture (RCCL) / no collectives at all
-                for t_ in body():
-                    self._grad_sync.all_reduce_sum_(t_)
-
-            graph = torch.cuda.CUDAGraph()
-            if self._grad_sync is not None and not self.graph_collectives:
-                # SEGMENTED form: the backend's collectives cannot be captured (gloo), or the capture probe failed.  Every
-                # stretch between two collectives is its own hipGraph (one shared memory pool, replayed in capture order);
-                # the collectives run eagerly in between: ~20 graph launches + ~19 collectives per update instead of ~80
-                # eager kernel launches (one rank over RCCL: 2.5 -> ~1 ms per step).
-                pool = torch.cuda.graph_pool_handle()
-                segs, gen, more = [], body(), True
-                while more:
-                    g_ = torch.cuda.CUDAGraph()
-                    t_ = None
-                    with ops.graph_capture(g_, pool=pool):
-                        try:
-                            t_ = next(gen)
-                        except StopIteration:
-                            more = False
-                    segs.append((g_, t_))
-                w["segments"] = segs
-                graph = None
-            else:
-                self._capture_graph(graph, run_inline)
-            w["graph"] = graph
+            # collectives inside the capture (RCCL) / no collectives at all: ONE graph.  SEGMENTED form: the backend's
+            # collectives cannot be captured (gloo), or the capture probe failed: ~20 graph launches + ~19 collectives per
+            # update instead of ~80 eager kernel launches (one rank over RCCL: 2.5 -> ~1 ms per step).
+            ops.capture_steps(w, body, self._sum_over_ranks, capture=self._capture_graph,
+                              segmented=self._grad_sync is not None and not self.graph_collectives)
             if self.shuffle == "numpy":
-                base = ref_order_rows(T, B, dev)
-                w["ref_ids"] = [base * N + a if a is not None else
-                                (base[:, None] * N + torch.arange(N, device=dev)[None, :]).reshape(-1) for a in groups]
+                w["ref_ids"] = self._ref_ids(T, B, N, groups)
             self._ws[key] = g = w
         # fresh permutations for this update (Batch.split draws one per repeat, batch.py:1219)
-        if self.shuffle == "numpy":
-            for gi, a in enumerate(groups):
-                for r in range(repeat):
-                    pl = torch.as_tensor(np.random.permutation(n_g)).to(dev)
-                    # positions of the reference batch (sample(0) order) -> lane ids of the time-major stores
-                    g["perm"][gi, r].copy_(g["ref_ids"][gi][pl])
         # shuffle == "device": the permutations are drawn inside the graph (tsm_random_permutations)
-        if g.get("step_host") != self.opt_step:  # the device-side step count is stale (eager updates, a loaded checkpoint)
-            g["step_dev"].fill_(self.opt_step)
-        if g.get("segments") is not None:
-            for g_, t_ in g["segments"]:
-                g_.replay()
-                if t_ is not None:
-                    self._grad_sync.all_reduce_sum_(t_)
-        else:
-            g["graph"].replay()
-        self.opt_step += g["n_steps"]
-        g["step_host"] = self.opt_step
-        self.param_version += 1
+        self._refill_host_perms(g)
+        self._refill_step_dev(g)
+        ops.replay_steps(g, self._sum_over_ranks)
+        self._account_steps(g)
         # loss statistics (reference: 4 .item() per minibatch): one launch folds the loss partials of EVERY gradient step
         # and writes the result straight into a pinned (mapped) host slot -- no D2H copy on the stream; the host only
         # blocks when the stats are read
@@ -693,32 +695,37 @@ class PPO(nn.Module):
         return self._update_with_batch(pb, batch_size, repeat, agent=None, buffer=buffer, perm_base=perm_base)
 
     # ---- `.learn(batch)` for the MARL trainers (training_coordinator.py:336) ----------------------
+    def _lane_pb(self, obs, act, rew, term, trunc, image, obs_next=None, stored=None) -> dict:
+        """One time-ordered lane of n rows (an agent batch of `learn`) -> `pb`: V(obs), V(obs_next) and logp_old -- `stored`
+        = (logp_old, v_s, v_next) as the rollout kernel stored them, computed by this policy at this parameter version: the
+        same bits as the two passes over obs / obs_next (tests/test_gpu_tag.py), without them -- then GAE; the last row
+        ends the lane.  image: what the passes read, None = `flat` itself (the image may be stale)."""
+        n = obs.shape[0]
+        P, A, H = self.net.flat.data, self.net.n_act, self.net.hidden
+        if stored is not None:
+            cur, nxt = dict(logp=stored[0], value=stored[1]), dict(value=stored[2])
+        else:
+            cur = ops.policy_forward(P, obs, A, H, image=image, mode="given", act=act, want_logits=False)
+            nxt = ops.policy_forward(P, obs_next, A, H, image=image, mode="none", want_logits=False)
+        ret, adv = ops.gae_lanes(cur["value"].view(n, 1), nxt["value"].view(n, 1), rew, term, trunc, self.gamma, self.gae_lambda)
+        return dict(T=n, rows=None, obs=obs, act=act, v_s=cur["value"], ret=ret.reshape(-1), adv=adv.reshape(-1),
+                    logp_old=cur["logp"], n_env=1, n_agent=1)
+
     def learn_steps(self, batch: Batch, batch_size: int | None = None, repeat: int = 1, **kwargs):
         """`learn` as a generator of gradient synchronisation points (see `_update_steps`)."""
-        dev = self.device
-        t = lambda x, dt: (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))).to(dev, dt).contiguous()  # noqa: E731
+        t = lambda x, dt: to_tensor(x, self.device, dt)  # noqa: E731
         self.net.sync_image()
         if self._batch_store(batch) is not None:  # rows read in place by the graph path: the eager path takes the copies
             batch = self._batch_store(batch).agent_batch(int(batch.agent_index))
         obs = t(batch.obs, torch.float32)
         n = obs.shape[0]
-        act = t(batch.act, torch.int32).reshape(n)
-        P = self.net.flat.data
-        if self._stored_outputs_ok(batch):
-            # the rollout kernel stored these rows' logp / V(obs) / V(obs_next), computed by this policy at this parameter version:
-            # the same bits as the three passes below (tests/test_gpu_tag.py), without them
-            cur = dict(logp=t(batch.logp_old, torch.float32).reshape(n), value=t(batch.v_s, torch.float32).reshape(n))
-            nxt = dict(value=t(batch.v_next, torch.float32).reshape(n))
-        else:
-            cur = ops.policy_forward(P, obs, self.net.n_act, self.net.hidden, image=self.net.image, mode="given", act=act, want_logits=False)
-            nxt = ops.policy_forward(P, t(batch.obs_next, torch.float32), self.net.n_act, self.net.hidden, image=self.net.image, mode="none",
-                                     want_logits=False)
+        stored = self._stored_outputs_ok(batch)
         term = t(batch.terminated, torch.uint8).reshape(n, 1)
-        trunc = t(batch.truncated, torch.uint8).reshape(n, 1) if "truncated" in batch else torch.zeros_like(term)
-        ret, adv = ops.gae_lanes(cur["value"].view(n, 1), nxt["value"].view(n, 1), t(batch.rew, torch.float32).view(n, 1),
-                                 term, trunc, self.gamma, self.gae_lambda)
-        pb = dict(T=n, rows=None, obs=obs, act=act, v_s=cur["value"], ret=ret.reshape(-1), adv=adv.reshape(-1),
-                  logp_old=cur["logp"], n_env=1, n_agent=1)
+        pb = self._lane_pb(
+            obs, t(batch.act, torch.int32).reshape(n), t(batch.rew, torch.float32).view(n, 1), term,
+            t(batch.truncated, torch.uint8).reshape(n, 1) if "truncated" in batch else torch.zeros_like(term), self.net.image,
+            obs_next=None if stored else t(batch.obs_next, torch.float32),
+            stored=tuple(t(batch[k_], torch.float32).reshape(n) for k_ in ("logp_old", "v_s", "v_next")) if stored else None)
         st = yield from self._update_steps(pb, batch_size, repeat)
         return {"loss": st.loss.mean, "actor_loss": st.actor_loss.mean, "vf_loss": st.vf_loss.mean,
                 "ent_loss": st.ent_loss.mean}
@@ -775,44 +782,29 @@ class PPO(nn.Module):
         the flat gradient of each step) exactly where `learn_steps` does.  The optimizer step count and the permutation
         counter live in HBM, so replays advance them; the learning rate is read from HBM."""
         dev = self.device
-        D, A, H = self.net.obs_dim, self.net.n_act, self.net.hidden
+        D = self.net.obs_dim
         dp = self._grad_sync is not None
         key = ("learn_graph", n, batch_size, repeat, has_trunc, self.shuffle, dp, ops.kernel_options(), stored)
         w = self._ws.get(key)
         if w is not None:
             return w
-        bounds = split_bounds(n, batch_size or -1, merge_last=True)
-        n_steps = repeat * len(bounds)
         self._warm_kernels(None)
-        P = self.net.flat.data
         z = lambda *sh, dt=torch.float32: torch.zeros(*sh, dtype=dt, device=dev)  # noqa: E731
-        nb_max = max(ops.ppo_update_grid(e - s) for s, e in bounds)
-        w = dict(n=n, n_steps=n_steps, repeat=repeat, has_trunc=has_trunc, stored=stored,
+        # (the loss partials of EVERY gradient step stay until ONE launch behind the replay folds them, straight into the
+        # pinned slot the host reads (as update() does): no per-step finalize launch, no device -> host copy)
+        w = self._minibatch_plan(n, batch_size, repeat, defer=True, agree=False)  # (the lock-step agrees on the shapes itself)
+        bounds = w["bounds"]
+        w.update(n=n, repeat=repeat, has_trunc=has_trunc, stored=stored,
                  obs=z(n, D), obs_next=None if stored else z(n, D), act=z(n, dt=torch.int32), rew=z(n, 1), term=z(n, 1, dt=torch.uint8),
                  trunc=z(n, 1, dt=torch.uint8), step_dev=z(1, dt=torch.int64),
-                 slabs=torch.empty(nb_max, P.numel(), dtype=torch.float32, device=dev),
-                 # the loss partials of EVERY gradient step stay until ONE launch behind the replay folds them, straight into the
-                 # pinned slot the host reads (as update() does): no per-step finalize launch, no device -> host copy
-                 partial=torch.zeros(n_steps, nb_max * 4, dtype=torch.float64, device=dev), nb_max=nb_max,
-                 nb_dev=torch.as_tensor([ops.ppo_update_grid(e - s) for s, e in bounds] * repeat, dtype=torch.int32, device=dev),
-                 M_dev=torch.as_tensor([e - s for s, e in bounds] * repeat, dtype=torch.int64, device=dev),
-                 perm=z(repeat, n, dt=torch.int64), perm_done=z(1, dt=torch.int32),
-                 mb_start=torch.as_tensor([b[0] for b in bounds] + [n], dtype=torch.int64, device=dev))
+                 perm=z(repeat, n, dt=torch.int64), perm_done=z(1, dt=torch.int32))
         if stored:  # logp_old / V(obs) / V(obs_next) as the rollout stored them (see _stored_outputs_ok)
             w.update(logp=z(n), v_s=z(n), v_next=z(n))
-        if dp:
-            w["flat_g"] = z(P.numel())
 
         def body():
-            if stored:
-                cur, nxt = dict(logp=w["logp"], value=w["v_s"]), dict(value=w["v_next"])
-            else:
-                # `flat` is the source of truth before the first Adam step of this call (the image may be stale)
-                cur = ops.policy_forward(P, w["obs"], A, H, image=None, mode="given", act=w["act"], want_logits=False)
-                nxt = ops.policy_forward(P, w["obs_next"], A, H, image=None, mode="none", want_logits=False)
-            ret, adv = ops.gae_lanes(cur["value"].view(n, 1), nxt["value"].view(n, 1), w["rew"], w["term"], w["trunc"],
-                                     self.gamma, self.gae_lambda)
-            ret, adv = ret.reshape(-1), adv.reshape(-1)
+            # `flat` is the source of truth before the first Adam step of this call (the image may be stale)
+            pb = self._lane_pb(w["obs"], w["act"], w["rew"], w["term"], w["trunc"], None, obs_next=w["obs_next"],
+                               stored=(w["logp"], w["v_s"], w["v_next"]) if stored else None)
             k = 0
             for r in range(repeat):
                 if self.shuffle != "numpy":
@@ -820,33 +812,13 @@ class PPO(nn.Module):
                     ops.random_permutations(n, 1, self.seed ^ 0x5DEECE66D, counter_dev=self._perm_ctr, out=w["perm"][r:r + 1],
                                             advance=1, done_ctr=w["perm_done"])
                 perm = w["perm"][r]
-                stats = (ops.ppo_adv_stats(adv, w["mb_start"], perm=perm, max_rows=max(e - s for s, e in bounds))
+                stats = (ops.ppo_adv_stats(pb["adv"], w["mb_start"], perm=perm, max_rows=w["max_rows"])
                          if self.advantage_normalization else None)
                 if dp:  # the union minibatch's statistics: ONE f64 pack summed over the ranks
                     yield from self._global_adv_stats_steps(stats, w["mb_start"])
                 for j, (s_, e_) in enumerate(bounds):
-                    nb = ops.ppo_update_grid(e_ - s_)
-                    ops.ppo_update_fused(P, w["obs"], w["act"], cur["logp"], adv, ret, self._cfg, A, H,
-                                         adv_stats=None if stats is None else stats[j],
-                                         v_s_old=cur["value"] if self.value_clip else None, perm=perm[s_:e_],
-                                         image=self.net.image if k > 0 else None, M=e_ - s_, n_blocks=nb,
-                                         slabs=w["slabs"][:nb], partial=w["partial"][k], want_scalars=False,
-                                         opt_step_dev=w["step_dev"])
-                    grads = w["slabs"][:nb]
-                    if dp and self._grad_sync.fused_step_ok(self.max_grad_norm, P.numel()):
-                        self._grad_sync.p2p.adam_step(P, grads, self.exp_avg, self.exp_avg_sq, 1, lr=self.lr, lr_dev=self._lr_dev,
-                                                      betas=self.betas, eps=self.adam_eps, weight_decay=self.weight_decay,
-                                                      step_dev=w["step_dev"], image=self.net.image, image_map=self.net.image_map)
-                        k += 1
-                        continue
-                    if dp:
-                        ops.reduce_slabs(grads, out=w["flat_g"], scale=1.0 / self._grad_sync.world)
-                        yield w["flat_g"]  # summed over the ranks, in place
-                        grads = w["flat_g"].view(1, -1)
-                    ops.adam_step(P, grads, self.exp_avg, self.exp_avg_sq, 1, lr=self.lr, lr_dev=self._lr_dev,
-                                  betas=self.betas, eps=self.adam_eps, weight_decay=self.weight_decay,
-                                  max_grad_norm=self.max_grad_norm, work=self._adam_work, step_dev=w["step_dev"],
-                                  image=self.net.image, image_map=self.net.image_map)
+                    yield from self._grad_step_steps(pb, perm[s_:e_], None if stats is None else stats[j], w["step_dev"], plan=w,
+                                                     partial=w["partial"][k], image=self.net.image if k > 0 else None)
                     k += 1
 
         w["body"] = body
@@ -857,7 +829,7 @@ class PPO(nn.Module):
         """The batch into the static buffers (copy_ converts int64 actions / bool flags; host arrays are uploaded), this
         call's host-drawn permutations, and the device-side step count if it went stale."""
         n, D, repeat = w["n"], self.net.obs_dim, w["repeat"]
-        t = lambda x: x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))  # noqa: E731
+        t = to_tensor
         stored = w.get("stored", False)
         st = self._batch_store(batch)
         if st is not None:
@@ -905,17 +877,14 @@ class PPO(nn.Module):
         if self.shuffle == "numpy":  # Batch.split draws np.random.permutation per repeat (batch.py:1219)
             for r in range(repeat):
                 w["perm"][r].copy_(torch.as_tensor(np.random.permutation(n)), non_blocking=True)
-        if w.get("step_host") != self.opt_step:  # the device-side step count is stale (eager updates, a loaded checkpoint)
-            w["step_dev"].fill_(self.opt_step)
+        self._refill_step_dev(w)
 
     def _learn_finish(self, w: dict):
         """Behind the replay: host-side counters, and the statistics on their way to a pinned host slot.
         async_stats=True: the returned mapping waits for them only when it is read (the reference's learn() returns floats:
         4 .item() per minibatch) -- the host never blocks here, except to keep at most 4 calls in flight."""
         n_steps = w["n_steps"]
-        self.opt_step += n_steps
-        w["step_host"] = self.opt_step
-        self.param_version += 1
+        self._account_steps(w)
         slot = ResultRing.of(w, lambda: pinned_slot(n_steps, 4)).take("resolve", wait=False)  # (a read slot is not waited for)
         if "scal" in w:  # (GenericPPO._learn_static folds its statistics inside the graph)
             slot["h"].copy_(w["scal"], non_blocking=True)
@@ -931,20 +900,26 @@ class PPO(nn.Module):
         slot["pending"] = out
         return out
 
+    def _learn_ws(self, batch: Batch, batch_size: int | None, repeat: int) -> dict:
+        """`_learn_static` for the shape of `batch`."""
+        return self._learn_static(self._learn_rows(batch), batch_size, repeat, "truncated" in batch or self._batch_store(batch) is not None,
+                                  stored=self._stored_outputs_ok(batch))
+
     def _learn_graph(self, batch: Batch, batch_size: int | None, repeat: int) -> dict[str, float]:
         """`learn` as ONE hipGraph replay per call (the MARL trainers call it once per policy and step,
         training_coordinator.py:118,154,336): the batch is copied into static HBM buffers, then `_learn_static`'s body
-        replays as captured."""
-        w = self._learn_static(self._learn_rows(batch), batch_size, repeat, "truncated" in batch or self._batch_store(batch) is not None,
-                               stored=self._stored_outputs_ok(batch))
+        replays as captured.  A workspace that says `warm=False` (GenericPPO) runs the body eagerly on the static buffers
+        at the first call of a shape.  (No replica: nothing is yielded.)"""
+        w = self._learn_ws(batch, batch_size, repeat)
         self._learn_load(w, batch)
+        if not w.get("warm", True):
+            for t_ in w["body"]():
+                self._sum_over_ranks(t_)
+            w["warm"] = True
+            return self._learn_finish(w)
         if "graph" not in w:
-            graph = torch.cuda.CUDAGraph()
-            with ops.graph_capture(graph):
-                for _ in w["body"]():  # (no replica: nothing is yielded)
-                    raise RuntimeError("a single-GPU learn() has no collectives")
-            w["graph"] = graph
-        w["graph"].replay()
+            ops.capture_steps(w, w["body"], self._sum_over_ranks)
+        ops.replay_steps(w, self._sum_over_ranks)
         return self._learn_finish(w)
 
     def __deepcopy__(self, memo):

@@ -27,9 +27,10 @@ import torch
 from .. import ops
 from ..data.batch import Batch, split_bounds
 from ..data.buffer import DeviceVectorReplayBuffer
-from ..data.stats import A2CTrainingStats, ResultRing, lazy_training_stats, pinned_slot, training_stats_from_steps
+from ..data.stats import ResultRing, lazy_training_stats, pinned_slot, training_stats_from_steps
 from ..utils.net import FlatMLP, MLPActorCritic
-from .ppo import PPO, drive_steps, ref_order_rows
+from ..utils.tensor import to_tensor
+from .ppo import PPO, ref_order_rows
 
 
 class GenericPPO(PPO):
@@ -205,11 +206,6 @@ class GenericPPO(PPO):
         return dict(T=T, rows=rows, obs=obs, act=act, v_s=v_s.reshape(-1).contiguous(), ret=ret.reshape(-1),
                     adv=adv.reshape(-1), logp_old=logp_old, n_env=B, n_agent=N, joint=joint)
 
-    def _grad_step(self, pb: dict, idx: torch.Tensor, adv_stats, step_dev: torch.Tensor | None = None,
-                   rows: torch.Tensor | None = None, partial_out: torch.Tensor | None = None) -> torch.Tensor | None:
-        """`_grad_step_steps` run to its end, the gradient summed over the data-parallel ranks where it falls due."""
-        return drive_steps(self._grad_step_steps(pb, idx, adv_stats, step_dev, rows, partial_out), self._grad_sync)
-
     def _grad_step_steps(self, pb: dict, idx: torch.Tensor, adv_stats, step_dev: torch.Tensor | None = None,
                          rows: torch.Tensor | None = None, partial_out: torch.Tensor | None = None):
         """One minibatch: forward both nets, loss, backward into joint slabs, clip + Adam.  A generator: with data-parallel
@@ -264,6 +260,16 @@ class GenericPPO(PPO):
     def _rows_grids(self, M: int, Mr: int, crit_rows: bool) -> tuple[int, int]:
         """(actor workgroups, loss-partial groups of the value term) of a row-kernel gradient step of M samples / Mr units."""
         return ops.ppo_actor_rows_grid(M), (ops.ppo_critic_rows_grid(Mr) if crit_rows else ops.ppo_loss_partial_elems(M) // 4)
+
+    def _deferred_partials(self, bounds: list, unit: int, reps: int) -> dict:
+        """Row-kernel steps leave their loss partials behind; ONE launch folds them all at the end of the captured sequence:
+        one row of partials per gradient step of `reps` passes over `bounds` (units of `unit` lanes), sized for the largest
+        grid, and what `ppo_finalize_many` reads besides."""
+        crit = self.fused_critic and (unit > 1 or self.critic_input != "global")
+        grids = [sum(self._rows_grids((e - s) * unit, e - s, crit)) for s, e in bounds]
+        return dict(partial=torch.zeros(reps * len(bounds), max(grids) * 4, dtype=torch.float64, device=self.device),
+                    nb_dev=torch.as_tensor(grids * reps, dtype=torch.int32, device=self.device),
+                    M_dev=torch.as_tensor([(e - s) * unit for s, e in bounds] * reps, dtype=torch.int64, device=self.device))
 
     def _grad_step_fused_actor(self, pb: dict, idx: torch.Tensor, adv_stats, step_dev, rows,
                                partial_out: torch.Tensor | None = None) -> torch.Tensor | None:
@@ -393,7 +399,7 @@ class GenericPPO(PPO):
         if "graph" not in w:
             if self._grad_sync is not None:
                 self._grad_sync.require_equal(n_steps, "the number of gradient steps per update")
-            w.update(perm=torch.zeros(len(groups), repeat, n_g, dtype=torch.int64, device=dev),
+            w.update(n_steps=n_steps, perm=torch.zeros(len(groups), repeat, n_g, dtype=torch.int64, device=dev),
                      step_dev=torch.zeros(1, dtype=torch.int64, device=dev),
                      scal=torch.zeros(n_steps, 4, dtype=torch.float32, device=dev),
                      mb_start=torch.as_tensor([b[0] * unit for b in bounds] + [n_g * unit], dtype=torch.int64, device=dev))
@@ -402,19 +408,9 @@ class GenericPPO(PPO):
             w["mb_all"] = mb_all = torch.cat([(seg + w["mb_start"][:-1].view(1, -1)).reshape(-1),
                                               torch.tensor([len(groups) * repeat * n_g * unit], dtype=torch.int64, device=dev)])
             w["lane_of_row"] = torch.arange(N, dtype=torch.int64, device=dev).view(1, 1, 1, N)
-            # row-kernel steps leave their loss partials behind; ONE launch folds them all at the end of the update
             defer = self.fused_actor
             if defer:
-                glob_rows = self.critic_input == "global"
-                grids = []
-                for s_, e_ in bounds:
-                    M_, Mr_ = (e_ - s_) * unit, e_ - s_
-                    crit = self.fused_critic and (row_mode or not glob_rows)
-                    grids.append(sum(self._rows_grids(M_, Mr_ if row_mode else M_, crit)))
-                reps = len(groups) * repeat
-                w["partial"] = torch.zeros(n_steps, max(grids) * 4, dtype=torch.float64, device=dev)
-                w["nb_dev"] = torch.as_tensor(grids * reps, dtype=torch.int32, device=dev)
-                w["M_dev"] = torch.as_tensor([(e_ - s_) * unit for s_, e_ in bounds] * reps, dtype=torch.int64, device=dev)
+                w.update(self._deferred_partials(bounds, unit, len(groups) * repeat))
 
             def body():
                 self._w1_img_ok = False  # (the parameters may have changed since the last step this object took)
@@ -430,38 +426,30 @@ class GenericPPO(PPO):
                 if self.advantage_normalization:
                     stats = ops.ppo_adv_stats(pb["adv"], mb_all, perm=lanes.reshape(-1),
                                               max_rows=max(e - s for s, e in bounds) * unit)
-                    stats = self._global_adv_stats(stats, mb_all).view(len(groups), repeat, len(bounds), 2)
+                    yield from self._global_adv_stats_steps(stats, mb_all)
+                    stats = stats.view(len(groups), repeat, len(bounds), 2)
                 k = 0
                 for gi in range(len(groups)):
                     for r in range(repeat):
                         for j, (s, e) in enumerate(bounds):
-                            sc = self._grad_step(pb, lanes[gi, r, s * unit:e * unit], None if stats is None else stats[gi, r, j],
-                                                 step_dev=w["step_dev"], rows=w["perm"][gi, r, s:e] if row_mode else None,
-                                                 partial_out=w["partial"][k] if defer else None)
+                            sc = yield from self._grad_step_steps(
+                                pb, lanes[gi, r, s * unit:e * unit], None if stats is None else stats[gi, r, j],
+                                step_dev=w["step_dev"], rows=w["perm"][gi, r, s:e] if row_mode else None,
+                                partial_out=w["partial"][k] if defer else None)
                             if not defer:
                                 w["scal"][k].copy_(sc)
                             k += 1
                 if defer:  # the loss statistics of every gradient step: one launch
                     ops.ppo_finalize_many(w["partial"], w["partial"].shape[1], w["nb_dev"], w["M_dev"], self._cfg, w["scal"])
 
-            graph = torch.cuda.CUDAGraph()
-            self._capture_graph(graph, body)  # (data parallel over RCCL: the all-reduces of every step are captured too)
-            w["graph"] = graph
+            # (data parallel over RCCL: the all-reduces of every step are captured too)
+            ops.capture_steps(w, body, self._sum_over_ranks, capture=self._capture_graph)
             if self.shuffle == "numpy":
-                base = ref_order_rows(T, B, dev)
-                w["ref_ids"] = [base if row_mode else base * N + a if a is not None else
-                                (base[:, None] * N + torch.arange(N, device=dev)[None, :]).reshape(-1) for a in groups]
-        if self.shuffle == "numpy":
-            for gi, a in enumerate(groups):
-                for r in range(repeat):
-                    pl = torch.as_tensor(np.random.permutation(n_g)).to(dev)
-                    w["perm"][gi, r].copy_(w["ref_ids"][gi][pl])  # reference batch position -> lane id (ppo.ref_order_rows)
-        if w.get("step_host") != self.opt_step:
-            w["step_dev"].fill_(self.opt_step)
-        w["graph"].replay()
-        self.opt_step += n_steps
-        w["step_host"] = self.opt_step
-        self.param_version += 1
+                w["ref_ids"] = self._ref_ids(T, B, N, groups, row_mode)
+        self._refill_host_perms(w)
+        self._refill_step_dev(w)
+        ops.replay_steps(w, self._sum_over_ranks)
+        self._account_steps(w)
         sync = self._grad_sync
         if sync is not None:
             sync.post_check()  # (peer-memory all-reduce: a lost peer is reported where the statistics are read)
@@ -486,11 +474,6 @@ class GenericPPO(PPO):
             if out is not None:
                 return out
         return super()._update(buffer, batch_size, repeat, t0)
-
-    def _update_with_batch(self, pb: dict, batch_size: int | None, repeat: int, agent: int | None = None,
-                           buffer: DeviceVectorReplayBuffer | None = None, perm_base: int | None = None) -> A2CTrainingStats:
-        return drive_steps(self._update_steps(pb, batch_size, repeat, agent=agent, buffer=buffer, perm_base=perm_base),
-                           self._grad_sync)
 
     def _update_steps(self, pb: dict, batch_size: int | None, repeat: int, agent: int | None = None,
                       buffer: DeviceVectorReplayBuffer | None = None, perm_base: int | None = None):
@@ -546,20 +529,6 @@ class GenericPPO(PPO):
             self._grad_sync.raise_if_failed()
         return training_stats_from_steps(s_h)
 
-    def learn(self, batch: Batch, batch_size: int | None = None, repeat: int = 1, **kwargs) -> dict[str, float]:
-        """One PPO pass on an explicit agent batch (training_coordinator.py:336); a centralized critic takes
-        `batch.global_obs` / `batch.global_obs_next`.  With `graph=True`: the call's launch sequence on static buffers --
-        ONE hipGraph replay per call from the second call of a shape on; for a data-parallel replica with its collectives
-        captured (RCCL) or between segmented graphs (`parallel.learn_lockstep_graph`), as `PPO.learn`."""
-        if self.learn_graph_ok(repeat):
-            if self._grad_sync is None:
-                return self._learn_graph(batch, batch_size, repeat)
-            from ..parallel import learn_lockstep_graph, lockstep_graphs_enabled
-
-            if lockstep_graphs_enabled():
-                return learn_lockstep_graph([(self, batch, batch_size, repeat)], self._grad_sync)[0]
-        return drive_steps(self.learn_steps(batch, batch_size, repeat, **kwargs), self._grad_sync)
-
     def learn_graph_ok(self, repeat: int = 1) -> bool:
         """Can `learn` run from static buffers inside captured graphs?  (`graph` is this class's capture switch; recompute_advantage
         re-runs the critic between repeats from the host.)"""
@@ -598,26 +567,13 @@ class GenericPPO(PPO):
                  mb_start=torch.as_tensor([b[0] for b in bounds] + [n], dtype=torch.int64, device=dev))
         if glob:
             w.update(joint=z(n, Kc), joint_next=z(n, Kc))
-        defer = self.fused_actor  # row-kernel steps leave their loss partials behind: ONE launch folds them all (as update())
+        defer = self.fused_actor  # (as update())
         if defer:
-            grids = [sum(self._rows_grids(e - s, e - s, self.fused_critic and not glob)) for s, e in bounds]
-            w.update(partial=z(n_steps, max(grids) * 4, dt=torch.float64),
-                     nb_dev=torch.as_tensor(grids * repeat, dtype=torch.int32, device=dev),
-                     M_dev=torch.as_tensor([e - s for s, e in bounds] * repeat, dtype=torch.int64, device=dev))
+            w.update(self._deferred_partials(bounds, 1, repeat))
 
         def body():
             self._w1_img_ok = False  # (the parameters may have changed since the last step this object took)
-            obs, act = w["obs"], w["act"]
-            if glob:
-                joint = w["joint"]
-                v_s, v_next = self._critic_values(joint), self._critic_values(w["joint_next"])
-            else:
-                joint = None
-                v_s, v_next = self._critic_values(obs), self._critic_values(w["obs_next"])
-            logp_old, _ = ops.categorical_logp_entropy(FlatMLP.forward(net.actor, obs, save=False), act)
-            ret, adv = ops.gae_lanes(v_s.view(n, 1), v_next.view(n, 1), w["rew"], w["term"], w["trunc"], self.gamma, self.gae_lambda)
-            pb = dict(T=n, rows=None, obs=obs, act=act, v_s=v_s.contiguous(), ret=ret.reshape(-1), adv=adv.reshape(-1),
-                      logp_old=logp_old, n_env=1, n_agent=1, joint=joint)
+            pb = self._lane_pb(w["obs"], w["act"], w["rew"], w["term"], w["trunc"], w["obs_next"], w.get("joint"), w.get("joint_next"))
             k = 0
             for r in range(repeat):
                 if self.shuffle != "numpy":
@@ -645,52 +601,42 @@ class GenericPPO(PPO):
         if "joint" in w:
             if "global_obs" not in batch:
                 raise ValueError("GenericPPO(critic_input='global').learn needs batch.global_obs / global_obs_next")
-            t = lambda x: x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))  # noqa: E731
+            t = to_tensor
             w["joint"].copy_(t(batch.global_obs).reshape(w["joint"].shape), non_blocking=True)
             w["joint_next"].copy_(t(batch.global_obs_next).reshape(w["joint"].shape), non_blocking=True)
 
-    def _learn_graph(self, batch: Batch, batch_size: int | None, repeat: int) -> dict[str, float]:
-        """`learn` of a single replica-less policy: eager launches on the static buffers at the first call of a shape, ONE
-        hipGraph replay from the second on."""
-        w = self._learn_static(len(batch.rew), batch_size, repeat, "truncated" in batch)
-        self._learn_load(w, batch)
-        if not w["warm"]:
-            for _ in w["body"]():
-                raise RuntimeError("a single-GPU learn() has no collectives")
-            w["warm"] = True
-            return self._learn_finish(w)
-        if "graph" not in w:
-            graph = torch.cuda.CUDAGraph()
-            with ops.graph_capture(graph):
-                for _ in w["body"]():
-                    raise RuntimeError("a single-GPU learn() has no collectives")
-            w["graph"] = graph
-        w["graph"].replay()
-        return self._learn_finish(w)
+    def _learn_ws(self, batch: Batch, batch_size: int | None, repeat: int) -> dict:
+        return self._learn_static(len(batch.rew), batch_size, repeat, "truncated" in batch)
 
-    def learn_steps(self, batch: Batch, batch_size: int | None = None, repeat: int = 1, **kwargs):
-        """`learn` as a generator of gradient synchronisation points: wide nets take part in the lock-step of grouped /
-        league policies under data parallelism (`parallel.learn_lockstep`, SURVEY.md section 8e)."""
-        dev = self.device
-        t = lambda x, dt: (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))).to(dev, dt).contiguous()  # noqa: E731
-        obs, obs_next = t(batch.obs, torch.float32), t(batch.obs_next, torch.float32)
+    def _lane_pb(self, obs, act, rew, term, trunc, obs_next, joint=None, joint_next=None) -> dict:
+        """One time-ordered lane of n rows (an agent batch of `learn`) -> `pb`: critic values of obs / obs_next (of the joint
+        observations with a centralized critic), logp_old, GAE; the last row ends the lane."""
         n = obs.shape[0]
-        act = t(batch.act, torch.int32).reshape(n)
         if self.critic_input == "global":
-            if "global_obs" not in batch:
-                raise ValueError("GenericPPO(critic_input='global').learn needs batch.global_obs / global_obs_next")
-            joint, joint_next = t(batch.global_obs, torch.float32), t(batch.global_obs_next, torch.float32)
             v_s, v_next = self._critic_values(joint), self._critic_values(joint_next)
         else:
             joint = None
             v_s, v_next = self._critic_values(obs), self._critic_values(obs_next)
         logp_old, _ = ops.categorical_logp_entropy(FlatMLP.forward(self.net.actor, obs, save=False), act)
+        ret, adv = ops.gae_lanes(v_s.view(n, 1), v_next.view(n, 1), rew, term, trunc, self.gamma, self.gae_lambda)
+        return dict(T=n, rows=None, obs=obs, act=act, v_s=v_s.contiguous(), ret=ret.reshape(-1), adv=adv.reshape(-1),
+                    logp_old=logp_old, n_env=1, n_agent=1, joint=joint)
+
+    def learn_steps(self, batch: Batch, batch_size: int | None = None, repeat: int = 1, **kwargs):
+        """`learn` as a generator of gradient synchronisation points: wide nets take part in the lock-step of grouped /
+        league policies under data parallelism (`parallel.learn_lockstep`, SURVEY.md section 8e)."""
+        t = lambda x, dt: to_tensor(x, self.device, dt)  # noqa: E731
+        obs, obs_next = t(batch.obs, torch.float32), t(batch.obs_next, torch.float32)
+        n = obs.shape[0]
+        joint = joint_next = None
+        if self.critic_input == "global":
+            if "global_obs" not in batch:
+                raise ValueError("GenericPPO(critic_input='global').learn needs batch.global_obs / global_obs_next")
+            joint, joint_next = t(batch.global_obs, torch.float32), t(batch.global_obs_next, torch.float32)
         term = t(batch.terminated, torch.uint8).reshape(n, 1)
         trunc = t(batch.truncated, torch.uint8).reshape(n, 1) if "truncated" in batch else torch.zeros_like(term)
-        ret, adv = ops.gae_lanes(v_s.view(n, 1), v_next.view(n, 1), t(batch.rew, torch.float32).view(n, 1), term, trunc,
-                                 self.gamma, self.gae_lambda)
-        pb = dict(T=n, rows=None, obs=obs, act=act, v_s=v_s.contiguous(), ret=ret.reshape(-1), adv=adv.reshape(-1),
-                  logp_old=logp_old, n_env=1, n_agent=1, joint=joint)
+        pb = self._lane_pb(obs, t(batch.act, torch.int32).reshape(n), t(batch.rew, torch.float32).view(n, 1), term, trunc, obs_next,
+                           joint, joint_next)
         st = yield from self._update_steps(pb, batch_size, repeat)
         return {"loss": st.loss.mean, "actor_loss": st.actor_loss.mean, "vf_loss": st.vf_loss.mean,
                 "ent_loss": st.ent_loss.mean}

@@ -1419,6 +1419,54 @@ class gc_hold:
         return False
 
 
+def capture_steps(w: dict, make_steps, reduce_, segmented: bool = False, capture=None) -> None:
+    """Capture a launch sequence written as a generator of synchronisation points: `make_steps()` launches everything in
+    order and YIELDS each tensor that has to be summed over the ranks at that point; `reduce_(tensor)` sums it in place.
+      * not segmented: ONE graph with the collectives inside (or none at all) -> w["graph"].  `capture(graph, fn)` captures
+        where a plain `graph_capture` will not do (PPO._capture_graph: RCCL collectives on a side stream);
+      * segmented (the backend's collectives cannot be captured -- gloo --, or the capture probe failed): every stretch
+        between two collectives is its own hipGraph on ONE shared memory pool, replayed in capture order with the
+        collectives run eagerly in between -> w["segments"] = [(graph, tensor to reduce behind it | None)].
+    One definition of the sequence serves both forms, and the eager launches too (drive the generator with `reduce_`)."""
+    if not segmented:
+        graph = torch.cuda.CUDAGraph()
+
+        def run():
+            for t in make_steps():
+                reduce_(t)
+
+        if capture is None:
+            with graph_capture(graph):
+                run()
+        else:
+            capture(graph, run)
+        w["graph"] = graph
+        return
+    pool = torch.cuda.graph_pool_handle()
+    segs, gen, more = [], make_steps(), True
+    while more:
+        g_ = torch.cuda.CUDAGraph()
+        t_ = None
+        with graph_capture(g_, pool=pool):
+            try:
+                t_ = next(gen)
+            except StopIteration:
+                more = False
+        segs.append((g_, t_))
+    w["segments"] = segs
+
+
+def replay_steps(w: dict, reduce_) -> None:
+    """Replay what `capture_steps` left in `w`: the one graph, or the segments with their collectives in between."""
+    if w.get("graph") is not None:
+        w["graph"].replay()
+        return
+    for g_, t_ in w["segments"]:
+        g_.replay()
+        if t_ is not None:
+            reduce_(t_)
+
+
 class kernel_override:
     """`with ops.kernel_override(actor_tile=64): ...` -- options set inside, restored on exit."""
 

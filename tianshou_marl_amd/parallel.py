@@ -410,38 +410,10 @@ def learn_lockstep_graph(jobs, sync: "GradSync", names: list | None = None) -> l
         def steps():
             return lockstep_steps([w["body"]() for w in ws], g["results"], g["packed"])
 
-        if inline:
-            graph = torch.cuda.CUDAGraph()
-
-            def run():
-                for t in steps():
-                    sync.all_reduce_sum_(t)
-
-            jobs[0][0]._capture_graph(graph, run)  # side stream, thread-local capture mode; a failure is fatal (see there)
-            g["graph"] = graph
-        else:
-            pool = torch.cuda.graph_pool_handle()
-            segs, gen, more = [], steps(), True
-            while more:
-                g_ = torch.cuda.CUDAGraph()
-                t_ = None
-                from . import ops as _ops
-
-                with _ops.graph_capture(g_, pool=pool):
-                    try:
-                        t_ = next(gen)
-                    except StopIteration:
-                        more = False
-                segs.append((g_, t_))
-            g["segments"] = segs
+        # (inline: side stream, thread-local capture mode; a failure is fatal -- see PPO._capture_graph)
+        _ops.capture_steps(g, steps, sync.all_reduce_sum_, segmented=not inline, capture=jobs[0][0]._capture_graph)
         cache[key] = g
-    if "graph" in g:
-        g["graph"].replay()
-    else:
-        for g_, t_ in g["segments"]:
-            g_.replay()
-            if t_ is not None:
-                sync.all_reduce_sum_(t_)
+    _ops.replay_steps(g, sync.all_reduce_sum_)
     return [p._learn_finish(w) for (p, _, _, _), w in zip(jobs, ws)]
 
 
