@@ -923,6 +923,56 @@ int tsm_adam_step_coef64(float *param, const float *grad_slabs, int32_t n_slab, 
                          double beta1, double beta2, double eps, double weight_decay, double max_grad_norm, float *work,
                          float *param_image, const int32_t *image_map, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * n-step targets  (tianshou/algorithm/algorithm_base.py:720-815, 1155-1216)
+ * tsm_nstep_return replaces  the `buffer.next` stack (:773-777), `value_mask` (:796), the end flags (:797-798) and the
+ *           loop of `_nstep_return` (:1195-1211) of Algorithm.compute_nstep_return, for all I sampled flat indices in one
+ *           launch (one thread per index, at most n_step dependent loads each).
+ *   state / done_store: as for tsm_vrb_next.  term_store u8 [S][B][term_row_stride], column term_col.
+ *   rew_store f32 [S][B][rew_row_stride], column rew_col: the agent's lane of a joint-step buffer, or the column that
+ *   MARLDispatcher swaps in for `buffer.rew` on AEC rows (marl.py:231,240) -- the walk still visits ALL rows.
+ *   out: idx_n i64 [I] = next^(n_step - 1)(indices); mc f32 [I] = the Monte-Carlo part; gpow f32 [I] = gamma^m with
+ *        m = (first n with an end flag) + 1, else n_step; vmask u8 [I] = !terminated[idx_n].
+ *        End flags are done | isin(index, unfinished_index()).  mc and gamma^m are float64 in registers, rounded once.
+ *   returns = target_q(idx_n) * vmask * gpow + mc  is formed by the consumer (tsm_dqn_td_head).
+ *   n_step < 1, gamma outside [0, 1], a column outside its row: TSM_ERR_INVALID.
+ *
+ * DQN  (tianshou/algorithm/modelfree/dqn.py)
+ * tsm_dqn_check: the bounds of the DQN kernels (n_act in [1, 64], n_step >= 1; QLearningOffPolicyAlgorithm.__init__,
+ *   dqn.py:235-237): TSM_ERR_INVALID naming the limit.
+ * tsm_dqn_td_head replaces  DQN._target_q after its network forwards (dqn.py:365-379), `_nstep_return`'s last line
+ *           (algorithm_base.py:1213-1215) and DQN._update_with_batch between `self.policy(batch).logits` and
+ *           `optim.step(loss)` (dqn.py:387-402).  One launch over the B rows.
+ *   q [B][n_act]: the online net on obs; q_next_online [B][n_act]: the online net on obs_next[idx_n]; q_next_target: the
+ *   lagged net on the same rows, NULL when target_update_freq == 0 (the online values stand in).  mask_next u8 [B][n_act]
+ *   (nullable): the action mask that travels with obs_next.  act i64 [B]; mc / gpow / vmask from tsm_nstep_return; weight
+ *   f32 [B] (nullable: 1).  is_double != 0: target = q_target[first argmax of compute_q_value(q_next_online, mask)], else
+ *   the row maximum of q_target.  compute_q_value's offset is min - max - 1 over the WHOLE q_next_online tensor
+ *   (dqn.py:147-150): each workgroup reduces it itself.  huber_delta <= 0: loss = mean(td^2 weight); else
+ *   huber_loss(q, returns, delta, "mean") (weight is not used, dqn.py:392-397).
+ *   out: returns f32 [B]; td_error f32 [B] = returns - q[b][act[b]]; dq f32 [B][n_act] = d loss / d q, non-zero only at
+ *        act; partial f64 [tsm_dqn_partial_elems(B)] = per workgroup {sum of loss terms, sum of q[b][act[b]]} -- the
+ *        layout of tsm_qmix_mix_td's partials, so tsm_qmix_finalize(partial, n_blocks, B, out) gives
+ *        out[2] = {loss, mean q[b][act[b]]} (out may be pinned host memory).
+ * tsm_dqn_egreedy replaces  DiscreteQLearningPolicy.forward's argmax with add_exploration_noise (dqn.py:140-141, 153-171)
+ *           on the device: q [R][n_act], mask u8 [R][n_act] (nullable).  Per row r: the first argmax of the masked q, or --
+ *           when the ROW's coin lands (u < *eps_dev) -- the first argmax of uniform[n_act] + mask.  All draws of row r are
+ *           words of Philox4x32-10 keyed by seed at counter offset + *offset_dev + r (offset_dev nullable), so a batch
+ *           drawn in pieces with the offset advanced equals the batch drawn at once.  act_out i32 [R].
+ * ------------------------------------------------------------------------------------------- */
+int tsm_nstep_return(const void *state, int64_t buffer_num, int64_t sub_size, const uint8_t *done_store,
+                     const uint8_t *term_store, int64_t term_row_stride, int32_t term_col, const float *rew_store,
+                     int64_t rew_row_stride, int32_t rew_col, const int64_t *indices, int64_t I, int32_t n_step,
+                     double gamma, int64_t *idx_n, float *mc, float *gpow, uint8_t *vmask, void *stream);
+int tsm_dqn_check(int32_t n_act, int32_t n_step);
+int64_t tsm_dqn_partial_elems(int64_t B);
+int tsm_dqn_td_head(const float *q, const float *q_next_online, const float *q_next_target, const uint8_t *mask_next,
+                    const int64_t *act, const float *mc, const float *gpow, const uint8_t *vmask, const float *weight,
+                    int64_t B, int32_t n_act, int is_double, float huber_delta, float *returns_out, float *td_error,
+                    float *dq, double *partial, void *stream);
+int tsm_dqn_egreedy(const float *q, const uint8_t *mask, int64_t R, int32_t n_act, const float *eps_dev, uint64_t seed,
+                    uint64_t offset, const uint64_t *offset_dev, int32_t *act_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,347 @@
+"""DQN (double / vanilla, optional lagged target network, n-step targets, action masks) on the HIP path.
+
+Mirror of /root/reference/tianshou/algorithm/modelfree/dqn.py:
+  `DiscreteQLearningPolicy`      :39-174   Q-network -> masked greedy action, per-row epsilon-greedy noise
+  `QLearningOffPolicyAlgorithm`  :180-285  n-step return, periodic full copy into the lagged network
+  `DQN`                          :288-404  `_target_q`, MSE / Huber TD loss
+and of `Algorithm.compute_nstep_return` / `OffPolicyAlgorithm.update` (algorithm_base.py:720-815, 866-905).
+The Q-network is a `FlatMLP` (csrc/dense.hip); the n-step walk over the device buffer is one launch
+(`tsm_nstep_return`, csrc/nstep.hip); the bootstrap value, the target, the loss and its gradient are one launch
+(`tsm_dqn_td_head`, csrc/dqn.hip); the device acting path is `tsm_dqn_egreedy`.  There is no autograd fallback.
+
+Kept quirks: Q15 -- `compute_q_value`'s mask offset is taken over the whole batch tensor; Q16 -- the
+lagged network is copied BEFORE the gradient step of calls 0, f, 2f, ... (`_iter` starts at 0), so the first copy changes
+nothing; Q17 -- `weight` does not enter the Huber loss, and the vanilla (non-double) target ignores the mask; Q18 -- on AEC
+rows the agent's reward column stands in for `buffer.rew` while the n-step walk visits the rows of every agent; Q19 -- the
+mask read with obs_next[idx_n] is the one the buffer keeps for row idx_n.
+"""
+from __future__ import annotations
+
+from collections import OrderedDict
+from dataclasses import dataclass
+from typing import Any
+
+import numpy as np
+import torch
+from torch import nn
+
+from .. import ops
+from ..data.batch import Batch
+from ..data.stats import ResultRing, TrainingStats, pinned_slot
+from ..utils.net import FlatAdam, FlatMLP
+from ..utils.tensor import to_tensor
+from .optim import AdamOptimizerFactory
+
+
+@dataclass(kw_only=True)
+class SimpleLossTrainingStats(TrainingStats):
+    """reinforce.py `SimpleLossTrainingStats`."""
+    loss: float
+
+
+def _obs_rows(obs):
+    """(observation array, mask or None) of `batch.obs` / `batch.obs_next` (dqn.py:135-138)."""
+    if isinstance(obs, Batch):
+        return (obs.obs if "obs" in obs else obs), (obs.mask if "mask" in obs else None)
+    return obs, None
+
+
+class DiscreteQLearningPolicy(nn.Module):
+    """dqn.py:39-174 with a `FlatMLP` Q-network (obs -> ... -> n actions)."""
+
+    def __init__(self, *, model: FlatMLP, action_space: Any, observation_space: Any = None, eps_training: float = 0.0,
+                 eps_inference: float = 0.0, seed: int = 0) -> None:
+        super().__init__()
+        if not isinstance(model, FlatMLP):
+            raise TypeError("DiscreteQLearningPolicy needs a FlatMLP Q-network: the update runs in HIP, there is no "
+                            f"autograd fallback (got {type(model).__name__})")
+        n = getattr(action_space, "n", None)
+        if n is None or int(n) != model.dims[-1]:
+            raise ValueError(f"DiscreteQLearningPolicy: the model has {model.dims[-1]} outputs, the action space "
+                             f"{'no size' if n is None else f'{int(n)} actions'}")
+        ops.dqn_check(model.dims[-1])
+        self.model = model
+        self.action_space, self.observation_space = action_space, observation_space
+        self.n_act = model.dims[-1]
+        self.seed = int(seed)
+        self._sample_ctr = 0
+        dev = model.flat.device
+        # the epsilon the acting kernel reads: a device scalar, so that a captured collect graph sees every change
+        self._eps_dev = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._zero_dev = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._within = False
+        self.eps_training, self.eps_inference = float(eps_training), float(eps_inference)
+        self._push_eps()
+
+    @property
+    def device(self) -> torch.device:
+        return self.model.flat.device
+
+    def _eps(self) -> float:
+        return self.eps_training if self._within else self.eps_inference
+
+    def _push_eps(self) -> None:
+        self._eps_dev.fill_(self._eps())
+
+    @property
+    def is_within_training_step(self) -> bool:
+        return self._within
+
+    @is_within_training_step.setter
+    def is_within_training_step(self, v: bool) -> None:
+        self._within = bool(v)
+        self._push_eps()
+
+    def set_eps_training(self, eps: float) -> None:
+        self.eps_training = float(eps)
+        self._push_eps()
+
+    def set_eps_inference(self, eps: float) -> None:
+        self.eps_inference = float(eps)
+        self._push_eps()
+
+    def compute_q_value(self, logits: torch.Tensor, mask) -> torch.Tensor:
+        """dqn.py:145-151: masked entries sink below the smallest logit of the WHOLE tensor (quirk Q15)."""
+        if mask is not None:
+            min_value = logits.min() - logits.max() - 1.0
+            logits = logits + (1 - to_tensor(mask, logits.device, logits.dtype)) * min_value
+        return logits
+
+    def forward(self, batch: Batch, state: Any = None, model: FlatMLP | None = None) -> Batch:
+        """-> Batch(logits [B, A] in HBM, act = the first argmax of the masked Q (numpy i64), state)."""
+        model = self.model if model is None else model
+        obs, mask = _obs_rows(batch.obs)
+        x = to_tensor(obs, self.device, torch.float32)
+        logits = FlatMLP.forward(model, x.reshape(-1, model.dims[0]), save=False)
+        m = None if mask is None else to_tensor(np.asarray(mask, bool) if not isinstance(mask, torch.Tensor) else mask,
+                                                 self.device, torch.uint8).reshape(logits.shape)
+        act = ops.dqn_egreedy(logits, self._zero_dev, 0, mask=m)
+        return Batch(logits=logits, act=act.to(torch.int64).cpu().numpy(), state=state)
+
+    def add_exploration_noise(self, act, batch):
+        """dqn.py:153-171 on the host RNG: `np.random.rand` for the row coins, then for the candidate actions."""
+        eps = self._eps()
+        if np.isclose(eps, 0.0):
+            return act
+        if isinstance(act, np.ndarray):
+            batch_size = len(act)
+            rand_mask = np.random.rand(batch_size) < eps
+            q = np.random.rand(batch_size, int(self.action_space.n))
+            if isinstance(batch.obs, Batch) and "mask" in batch.obs:
+                q += np.asarray(batch.obs.mask)
+            rand_act = q.argmax(axis=1)
+            act[rand_mask] = rand_act[rand_mask]
+            return act
+        raise NotImplementedError(f"Currently only numpy array is supported for action, but got {type(act)}")
+
+    def act_device(self, obs: torch.Tensor, out: dict | None = None, offset_dev: torch.Tensor | None = None,
+                   row_offset: int = 0, mask: torch.Tensor | None = None) -> dict:
+        """obs [..., D] in HBM -> act i32 [rows] (the Q-net, then tsm_dqn_egreedy with the epsilon of the current phase);
+        logp, value = 0.  The Philox counter is offset_dev (the env's device tick: captured graphs advance it) or the
+        policy's own."""
+        rows = obs.reshape(-1, self.model.dims[0])
+        R = rows.shape[0]
+        q = FlatMLP.forward(self.model, rows, save=False)
+        m = None if mask is None else mask.reshape(R, self.n_act)
+        act = ops.dqn_egreedy(q, self._eps_dev, self.seed, offset=self._sample_ctr + row_offset, offset_dev=offset_dev,
+                              mask=m, out=None if out is None else out["act"].view(-1))
+        if offset_dev is None:
+            self._sample_ctr += R
+        if out is not None:
+            out["logp"].zero_()
+            out["value"].zero_()
+            return out
+        z = torch.zeros(R, dtype=torch.float32, device=self.device)
+        return dict(act=act, logp=z, value=z.clone(), q=q)
+
+
+class DQN(nn.Module):
+    """dqn.py:180-404 on the device buffer.  `optim`: an `AdamOptimizerFactory` (its hyper-parameters drive the HIP Adam
+    over the model's flat vector) or a `FlatAdam` over that vector."""
+
+    def __init__(self, *, policy: DiscreteQLearningPolicy, optim: Any, gamma: float = 0.99, n_step_return_horizon: int = 1,
+                 target_update_freq: int = 0, is_double: bool = True, huber_loss_delta: float | None = None) -> None:
+        super().__init__()
+        if not isinstance(policy, DiscreteQLearningPolicy):
+            raise TypeError(f"DQN needs a DiscreteQLearningPolicy, got {type(policy).__name__}")
+        assert 0.0 <= gamma <= 1.0, f"discount factor should be in [0, 1] but got: {gamma}"
+        assert n_step_return_horizon > 0, f"n_step_return_horizon should be greater than 0 but got: {n_step_return_horizon}"
+        ops.dqn_check(policy.n_act, int(n_step_return_horizon))
+        self.policy = policy
+        model = policy.model
+        self.lr_scheduler = None
+        if isinstance(optim, AdamOptimizerFactory):
+            kw = optim.adam_kwargs()
+            self.optim = FlatAdam(model, lr=kw["lr"], betas=kw["betas"], eps=kw["adam_eps"], weight_decay=kw["weight_decay"],
+                                  coef64=True)
+            if optim.lr_scheduler_factory is not None:
+                self.lr_scheduler = optim.lr_scheduler_factory.create_scheduler(self.optim)
+        elif isinstance(optim, FlatAdam):
+            if optim.param.data_ptr() != model.flat.data.data_ptr() or optim.param.numel() != model.flat.numel():
+                raise ValueError("DQN: the FlatAdam must step the policy model's own flat parameter vector")
+            self.optim = optim
+        else:
+            raise TypeError(f"DQN: optim must be an AdamOptimizerFactory or a FlatAdam, got {type(optim).__name__}")
+        self.gamma = gamma
+        self.n_step = int(n_step_return_horizon)
+        self.target_update_freq = int(target_update_freq)
+        self.is_double = bool(is_double)
+        self.huber_loss_delta = huber_loss_delta
+        self._iter = 0
+        self.model_old: FlatMLP | None = None
+        if self.use_target_network:
+            # one flat copy viewed by a net of the same shape; its constructor draws from a private generator (seed given)
+            # and the copy overwrites that: the global torch RNG is not drawn from, as the reference's deepcopy draws nothing
+            self.target_flat = model.flat.data.clone()
+            self.model_old = FlatMLP(model.dims, model.act, device=model.flat.device, seed=0, storage=self.target_flat)
+            self.target_flat.copy_(model.flat.data)
+        self._ws: dict = {}
+
+    @property
+    def device(self) -> torch.device:
+        return self.policy.device
+
+    @property
+    def use_target_network(self) -> bool:
+        return self.target_update_freq > 0
+
+    @property
+    def is_within_training_step(self) -> bool:
+        return self.policy.is_within_training_step
+
+    @is_within_training_step.setter
+    def is_within_training_step(self, v: bool) -> None:
+        self.policy.is_within_training_step = v
+
+    def _periodically_update_lagged_network_weights(self) -> None:
+        """dqn.py:277-285: a full copy on calls 0, f, 2f, ... -- `_iter` starts at 0 (quirk Q16)."""
+        if self.use_target_network and self._iter % self.target_update_freq == 0:
+            self.target_flat.copy_(self.policy.model.flat.data)
+        self._iter += 1
+
+    # ---- compute_nstep_return (algorithm_base.py:720-815) with DQN._target_q's forwards (dqn.py:365-375) ----------
+    def _preprocess_batch(self, batch: Batch, buffer, indices, agent: int | None = None) -> Batch:
+        """The n-step walk for `indices` (one launch), then the networks on obs_next[idx_n] (and mask[idx_n] if the buffer
+        keeps masks), gathered with tsm_vrb_gather.  `agent`: the agent's column -- its lane of a joint-step buffer, its
+        reward column of an AEC buffer (the walk still visits all rows, quirk Q18).  The batch leaves with what the TD
+        head needs; `returns` is set by `_update_with_batch`, where the head runs."""
+        dev = self.device
+        idx = to_tensor(indices, dev, torch.int64).reshape(-1)
+        if len(batch.get_keys()) != 0 and len(batch) != idx.numel():
+            raise ValueError(f"Batch size {len(batch)} and indices size {idx.numel()} mismatch.")
+        aec = bool(getattr(buffer, "aec", False))
+        n_col = buffer.rew_store.shape[2]
+        if agent is None:
+            if n_col != 1:
+                raise ValueError(f"DQN: the buffer holds {n_col} reward columns; say which agent's (agent=k)")
+            agent = 0
+        if not 0 <= int(agent) < n_col:
+            raise ValueError(f"DQN: agent column {agent} outside the buffer's {n_col}")
+        k = int(agent)
+        col = 0 if aec else k  # AEC rows: one observation / flag per row; joint rows: the agent's lane
+        idx_n, mc, gpow, vmask = ops.nstep_return(buffer.index, buffer.term_store, buffer.rew_store, idx, self.n_step,
+                                                  self.gamma, rew_col=k, term_col=col)
+        if buffer._save_obs_next:
+            nxt = buffer._gather(buffer.obs_next_store, idx_n)
+        else:  # ignore_obs_next: obs at next(index) (buffer_base.py:612-616)
+            nxt = buffer._gather(buffer.obs_store, buffer.index.next(idx_n))
+        nxt = nxt[:, col].contiguous()
+        mask_store = getattr(buffer, "mask_store", None)
+        mask_next = None if mask_store is None else buffer._gather(mask_store, idx_n)
+        model = self.policy.model
+        batch.q_next_online = FlatMLP.forward(model, nxt, save=False)
+        if self.use_target_network:
+            batch.q_next_target = FlatMLP.forward(self.model_old, nxt, save=False)
+        if mask_next is not None:
+            batch.mask_next = mask_next
+        batch.idx_n, batch.mc, batch.gpow, batch.vmask = idx_n, mc, gpow, vmask
+        if "obs" not in batch:  # rows straight from the device stores (DQN.update)
+            batch.obs = buffer._gather(buffer.obs_store, idx)[:, col].contiguous()
+            batch.act = buffer._gather(buffer.act_store, idx)[:, col].contiguous().to(torch.int64)
+        return batch
+
+    # ---- DQN._update_with_batch (dqn.py:381-404) --------------------------------------------------------------
+    def _update_with_batch(self, batch: Batch) -> SimpleLossTrainingStats:
+        """The online forward (saved), the TD head, the backward into slabs, one Adam step, the loss into a pinned slot."""
+        self._periodically_update_lagged_network_weights()
+        dev = self.device
+        weight = batch.pop("weight", None) if "weight" in batch else None
+        if weight is not None and not isinstance(weight, (torch.Tensor, np.ndarray)):
+            weight = None if float(weight) == 1.0 else np.full(len(batch.mc), float(weight), np.float32)
+        obs, _ = _obs_rows(batch.obs)
+        model = self.policy.model
+        x = to_tensor(obs, dev, torch.float32).reshape(-1, model.dims[0])
+        B = x.shape[0]
+        act = to_tensor(batch.act, dev, torch.int64).reshape(-1)
+        w = self._ws.get(B)
+        if w is None:
+            n_split = ops.mlp_n_split(B)
+            w = self._ws[B] = dict(n_split=n_split,
+                                   slabs=torch.empty(n_split, model.flat.numel(), dtype=torch.float32, device=dev))
+        q = FlatMLP.forward(model, x, save=True)
+        head = ops.dqn_td_head(q, batch.q_next_online, batch.get("q_next_target"), act, batch.mc, batch.gpow, batch.vmask,
+                               mask_next=batch.get("mask_next"),
+                               weight=None if weight is None else to_tensor(weight, dev, torch.float32).reshape(-1),
+                               is_double=self.is_double, huber_delta=self.huber_loss_delta)
+        model.backward(head["dq"], w["n_split"], slabs=w["slabs"])
+        self.optim.step(w["slabs"])
+        slot = ResultRing.of(w, lambda: pinned_slot(2)).take("resolve", wait=False)
+        ops.qmix_finalize(head["partial"], B, slot["h"])
+        slot["event"].record()
+        batch.returns = head["returns"]
+        batch.weight = head["td_error"]  # prio-buffer
+        slot["event"].synchronize()
+        return SimpleLossTrainingStats(loss=float(slot["h"][0]))
+
+    def update(self, buffer, sample_size: int | None, agent: int | None = None) -> SimpleLossTrainingStats:
+        """OffPolicyAlgorithm.update (algorithm_base.py:889-905): sample, preprocess, update.  The sampled rows are read
+        from the device stores in place (`buffer.sample` would carry them through the host)."""
+        if not self.is_within_training_step:
+            raise RuntimeError("update() was called outside of a training step as signalled by "
+                               "`is_within_training_step=False`")
+        indices = buffer.sample_indices(sample_size)
+        batch = self._preprocess_batch(Batch(), buffer, indices, agent=agent)
+        stats = self._update_with_batch(batch)
+        if self.lr_scheduler is not None:
+            self.lr_scheduler.step()
+        return stats
+
+    # ---- checkpoints ---------------------------------------------------------------------------------------------
+    def state_dict(self, *args, **kwargs):  # type: ignore[override]
+        sd = OrderedDict(model=self.policy.model.flat.data.detach().clone().cpu(),
+                         model_old=self.target_flat.detach().clone().cpu() if self.use_target_network else None,
+                         optim=self.optim.state_dict(), iter=self._iter)
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, sd, *args, **kwargs):  # type: ignore[override]
+        self.policy.model.flat.data.copy_(sd["model"])
+        if self.use_target_network:
+            self.target_flat.copy_(sd["model_old"] if sd.get("model_old") is not None else sd["model"])
+        self.optim.load_state_dict(sd["optim"])
+        self._iter = int(sd["iter"])
+
+    def _ref_keys(self, prefix: str) -> list[str]:
+        """The reference's parameter names of a `Net(hidden_sizes=[...])` Q-network below `prefix`: hidden layer i is
+        `model.model.{2 i}` (Linear, activation, Linear, ...), as is the output layer."""
+        L = self.policy.model.n_layers
+        return [f"{prefix}model.model.{2 * i}.{p}" for i in range(L) for p in ("weight", "bias")]
+
+    def to_reference_state_dict(self) -> OrderedDict:
+        """The module state_dict of the reference's DQN around a `Net`: `policy.model.*`, then `model_old.module.*` when
+        a target network is used (lagged_network.py wraps it in an EvalModeModuleWrapper)."""
+        sd = OrderedDict()
+        nets = [("policy.model.", self.policy.model)] + ([("model_old.module.", self.model_old)] if self.use_target_network else [])
+        for prefix, net in nets:
+            keys = self._ref_keys(prefix)
+            for i in range(net.n_layers):
+                sd[keys[2 * i]] = net.weight(i).detach().clone().cpu()
+                sd[keys[2 * i + 1]] = net.bias(i).detach().clone().cpu()
+        return sd
+
+    @torch.no_grad()
+    def load_reference_state_dict(self, sd) -> None:
+        nets = [("policy.model.", self.policy.model)] + ([("model_old.module.", self.model_old)] if self.use_target_network else [])
+        for prefix, net in nets:
+            keys = self._ref_keys(prefix)
+            net.load_layers([(sd[keys[2 * i]], sd[keys[2 * i + 1]]) for i in range(net.n_layers)])

@@ -5,7 +5,7 @@ from .ctde import CentralizedCritic, CTDEPolicy, DecentralizedActor, GlobalState
 from .flexible_policy import FlexibleMultiAgentPolicyManager
 from .maddpg import MADDPGPolicy
 from .qmix import QMIXMixer, QMIXPolicy
-from .marl import MARLDispatcher, MultiAgentOnPolicyAlgorithm, MultiAgentPolicy
+from .marl import MARLDispatcher, MultiAgentOffPolicyAlgorithm, MultiAgentOnPolicyAlgorithm, MultiAgentPolicy
 from .training_coordinator import (
     LeaguePlayTrainer,
     MATrainer,
@@ -16,7 +16,7 @@ from .training_coordinator import (
 )
 
 __all__ = [
-    "MultiAgentPolicy", "MultiAgentOnPolicyAlgorithm", "MARLDispatcher", "MapTrainingStats",
+    "MultiAgentPolicy", "MultiAgentOnPolicyAlgorithm", "MultiAgentOffPolicyAlgorithm", "MARLDispatcher", "MapTrainingStats",
     "FlexibleMultiAgentPolicyManager", "MATrainer", "SimultaneousTrainer", "SequentialTrainer",
     "SelfPlayTrainer", "LeaguePlayTrainer", "agent_batches_from_buffer", "CTDEPolicy", "GlobalStateConstructor",
     "DecentralizedActor", "CentralizedCritic", "QMIXMixer", "QMIXPolicy", "MADDPGPolicy",

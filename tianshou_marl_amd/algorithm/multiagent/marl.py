@@ -3,6 +3,7 @@
 Mirror of /root/reference/tianshou/algorithm/multiagent/marl.py:
   `MultiAgentPolicy(policies)`            :77-185   forward() routes rows to the owning agent's policy
   `MARLDispatcher(algorithms, env)`       :191-268  per-agent `_preprocess_batch` / `_update_with_batch`
+  `MultiAgentOffPolicyAlgorithm(...)`     :271-311
   `MultiAgentOnPolicyAlgorithm(...)`      :314-353
   `MapTrainingStats`                      :29-59    (data/stats.py)
 
@@ -295,6 +296,39 @@ class MARLDispatcher:
                                   logp_old=cur["logp"], n_env=1, n_agent=1, aec=True)
         return results
 
+    # ---- off-policy algorithms: sampled flat indices, per-agent n-step targets (marl.py:208-249) ----------------------
+    @staticmethod
+    def aec_partition_of(buffer, indices: torch.Tensor):
+        """`aec_partition` for sampled flat indices i64 [n]: (positions into `indices` grouped by agent, host offsets)."""
+        codes = buffer._gather(buffer.agent_store.unsqueeze(-1), indices).view(-1)
+        pos, offs = ops.agent_index(codes, len(buffer.agents))
+        return pos, offs.cpu().numpy()
+
+    def dispatch_process_offpolicy(self, buffer, indices=None) -> dict:
+        """agent_id -> that agent's preprocessed batch (None: no rows).  Joint-step lanes: every agent takes all sampled rows
+        with its own column.  AEC rows: each agent takes the rows whose `obs.agent_id` is its own plus their flat indices, and
+        its reward column stands in for `buffer.rew` (:231,240) -- the n-step walk still visits the rows of every agent."""
+        dev = buffer.device
+        results = {}
+        if not getattr(buffer, "aec", False):
+            idx = torch.as_tensor(np.asarray(buffer.sample_indices(0) if indices is None else indices)).to(dev, torch.int64)
+            for agent, algorithm in self.algorithms.items():
+                results[agent] = algorithm._preprocess_batch(Batch(), buffer, idx, agent=self.agent_idx[agent]) if idx.numel() else None
+            return results
+        if indices is None:
+            idx, pos, offs = self.aec_partition(buffer)
+        else:
+            idx = torch.as_tensor(np.asarray(indices)).to(dev, torch.int64).reshape(-1)
+            pos, offs = self.aec_partition_of(buffer, idx)
+        for agent, algorithm in self.algorithms.items():
+            k = self.agent_idx[agent]
+            lo, hi = int(offs[k]), int(offs[k + 1])
+            if hi == lo:
+                results[agent] = None
+                continue
+            results[agent] = algorithm._preprocess_batch(Batch(), buffer, idx[pos[lo:hi]].contiguous(), agent=k)
+        return results
+
     def dispatch_update_with_batch(self, batch: dict, algorithm_update_with_batch_fn: Callable) -> MapTrainingStats:
         agent_id_to_stats = {}
         for agent_id, algorithm in self.algorithms.items():
@@ -302,6 +336,54 @@ class MARLDispatcher:
             if data is not None and len(data) != 0:
                 agent_id_to_stats[agent_id] = algorithm_update_with_batch_fn(algorithm, data, self.agent_idx[agent_id])
         return MapTrainingStats(agent_id_to_stats)
+
+
+class MultiAgentOffPolicyAlgorithm(nn.Module):
+    """marl.py:271-311: each agent's rows update that agent's off-policy algorithm (independent learners, e.g. one `DQN`
+    per agent)."""
+
+    def __init__(self, *, algorithms: list, env) -> None:
+        super().__init__()
+        self._dispatcher = MARLDispatcher(algorithms, env)
+        self.policy = self._dispatcher.create_policy()
+        self._submodules = nn.ModuleList([a for a in _unique(algorithms) if isinstance(a, nn.Module)])
+
+    @property
+    def is_within_training_step(self) -> bool:
+        return self.policy.is_within_training_step
+
+    @is_within_training_step.setter
+    def is_within_training_step(self, v: bool) -> None:
+        self.policy.is_within_training_step = v
+
+    def get_algorithm(self, agent_id):
+        return self._dispatcher.algorithms[agent_id]
+
+    def _preprocess_batch(self, batch, buffer, indices) -> dict:
+        """`batch` is not read: every agent's rows come from the device stores at `indices` (None: all of sample_indices(0))."""
+        return self._dispatcher.dispatch_process_offpolicy(buffer, indices)
+
+    def _update_with_batch(self, batch: dict) -> MapTrainingStats:
+        return self._dispatcher.dispatch_update_with_batch(batch, lambda algorithm, data, agent_col: algorithm._update_with_batch(data))
+
+    def update(self, buffer, sample_size: int | None):
+        """OffPolicyAlgorithm.update (algorithm_base.py:889-905) through the dispatcher."""
+        if not self.is_within_training_step:
+            raise RuntimeError("update() was called outside of a training step as signalled by "
+                               "`is_within_training_step=False`")
+        indices = None if sample_size == 0 else buffer.sample_indices(sample_size)
+        stats = self._update_with_batch(self._preprocess_batch(None, buffer, indices))
+        for a in _unique(self._dispatcher.algorithms.values()):
+            if getattr(a, "lr_scheduler", None) is not None:
+                a.lr_scheduler.step()
+        return stats
+
+    def state_dict(self, *args, **kwargs):
+        return {str(a): alg.state_dict() for a, alg in self._dispatcher.algorithms.items()}
+
+    def load_state_dict(self, sd, *args, **kwargs):
+        for a, alg in self._dispatcher.algorithms.items():
+            alg.load_state_dict(sd[str(a)])
 
 
 class MultiAgentOnPolicyAlgorithm(nn.Module):

@@ -1,0 +1,226 @@
+// dqn.hip -- DQN: the bootstrap value, the n-step target, the TD loss with its backward, and masked epsilon-greedy acting.
+//
+// Replaces DQN._target_q and the arithmetic of DQN._update_with_batch between the network forwards and `optim.step(loss)`
+// (/root/reference/tianshou/algorithm/modelfree/dqn.py:365-404), the last line of `_nstep_return`
+// (algorithm_base.py:1213-1215) and, on the device, DiscreteQLearningPolicy.forward's action choice with
+// add_exploration_noise (dqn.py:140-141, 153-171).  The Q-networks run in csrc/dense.hip, the n-step walk in csrc/nstep.hip.
+//
+// Per row b (one thread):
+//   qt      = q_next_target, or q_next_online when there is no target network
+//   double: a* = first argmax_a (q_next_online[b][a] + (1 - mask[b][a]) * mv),  target = qt[b][a*]
+//           mv = min(q_next_online) - max(q_next_online) - 1 over the WHOLE [B][A] tensor (compute_q_value, dqn.py:147-150):
+//           every workgroup reduces the tensor itself (min and max do not depend on the order, so all agree bit for bit);
+//           without a mask no offset is applied and the reduction is skipped
+//   else:   target = max_a qt[b][a]                      (the mask does not enter: dqn.py:379 takes the raw maximum)
+//   returns = target * vmask * gpow + mc  in float64, rounded once (numpy's f32 * f64 + f64, then to_torch_as)
+//   td      = returns - q[b][act[b]]
+//   MSE:    l = td^2 w[b]                                d q[b][act] = -2 td w[b] / B
+//   Huber:  e = -td; l = |e| < delta ? e^2 / 2 : delta (|e| - delta / 2);   d q[b][act] = clamp(e, -delta, delta) / B
+//           (`weight` does not enter the Huber loss: dqn.py:392-397 drops it)
+// Loss and mean(q[b][act]) leave as per-workgroup f64 partials in tsm_qmix_mix_td's layout {sum l, sum q}, so
+// tsm_qmix_finalize turns them into {loss, mean q} in a pinned slot.
+#include "common.h"
+#include "philox.h"
+
+namespace {
+constexpr int kDThreads = 256;
+constexpr int kDMaxA = 64;
+
+__global__ __launch_bounds__(kDThreads) void dqn_td_head_kernel(
+    const float *__restrict__ q, const float *__restrict__ qn_on, const float *__restrict__ qn_tg,
+    const uint8_t *__restrict__ mask_next, const int64_t *__restrict__ act, const float *__restrict__ mc,
+    const float *__restrict__ gpow, const uint8_t *__restrict__ vmask, const float *__restrict__ weight, int64_t B,
+    int32_t A, int is_double, float huber_delta, float *__restrict__ returns_out, float *__restrict__ td_out,
+    float *__restrict__ dq, double *__restrict__ partial) {
+    __shared__ float s_min[kDThreads / kWave], s_max[kDThreads / kWave];
+    __shared__ double s_red[2][kDThreads / kWave];
+    const int t = threadIdx.x, lane = t & (kWave - 1), w = t / kWave;
+    const bool masked = is_double && mask_next != nullptr;
+
+    float mv = 0.f;
+    if (masked) {  // logits.min() - logits.max() - 1 over the whole tensor
+        // fminf / fmaxf skip a NaN where torch's min() / max() return it: a flag carries a NaN logit through the reduction and
+        // makes the offset NaN, as in the reference
+        float lo = INFINITY, hi = -INFINITY;
+        int bad = 0;
+        const int64_t n = B * A;
+        for (int64_t j = t; j < n; j += kDThreads) {
+            const float v = qn_on[j];
+            bad |= (v != v);
+            lo = fminf(lo, v);
+            hi = fmaxf(hi, v);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            lo = fminf(lo, __shfl_xor(lo, off, kWave));
+            hi = fmaxf(hi, __shfl_xor(hi, off, kWave));
+            bad |= __shfl_xor(bad, off, kWave);
+        }
+        if (lane == 0) { s_min[w] = bad ? __builtin_nanf("") : lo; s_max[w] = hi; }
+        __syncthreads();
+        lo = s_min[0];
+        hi = s_max[0];
+        bad = lo != lo;
+#pragma unroll
+        for (int k = 1; k < kDThreads / kWave; ++k) {
+            bad |= s_min[k] != s_min[k];
+            lo = fminf(lo, s_min[k]);
+            hi = fmaxf(hi, s_max[k]);
+        }
+        mv = bad ? __builtin_nanf("") : (lo - hi) - 1.0f;
+    }
+
+    const int64_t b = (int64_t)blockIdx.x * kDThreads + t;
+    double p_l = 0.0, p_q = 0.0;
+    if (b < B) {
+        const float *qt = (qn_tg ? qn_tg : qn_on) + b * A;
+        float target;
+        if (is_double) {
+            const float *row = qn_on + b * A;
+            const uint8_t *mrow = masked ? mask_next + b * A : nullptr;
+            int a_star = 0;
+            float best = 0.f;
+            for (int a = 0; a < A; ++a) {
+                float v = row[a];
+                if (mrow) v = v + (mrow[a] ? 0.f : 1.f) * mv;   // logits + (1 - mask) * min_value, in f32 as torch
+                // first maximum, as torch.argmax -- which takes the first NaN for the maximum when there is one
+                if (a == 0 || v > best || (v != v && best == best)) { best = v; a_star = a; }
+            }
+            target = qt[a_star];
+        } else {
+            target = qt[0];
+            for (int a = 1; a < A; ++a) target = fmaxf(target, qt[a]);
+        }
+        const float tm = vmask[b] ? target : target * 0.f;  // target_q *= value_mask (a NaN stays a NaN)
+        const float ret = (float)((double)tm * (double)gpow[b] + (double)mc[b]);
+        const int64_t ac = act[b];
+        const bool ok = ac >= 0 && ac < A;  // an action outside [0, A) reads nothing and poisons the loss
+        const float qs = ok ? q[b * A + ac] : __builtin_nanf("");
+        const float td = ret - qs;
+        float l, g;
+        if (huber_delta > 0.f) {
+            const float e = -td, ae = fabsf(e);
+            l = ae < huber_delta ? 0.5f * e * e : huber_delta * (ae - 0.5f * huber_delta);
+            g = (e <= -huber_delta ? -huber_delta : (e >= huber_delta ? huber_delta : e)) / (float)B;
+        } else {
+            const float wt = weight ? weight[b] : 1.f;
+            l = td * td * wt;
+            g = -2.f * td * wt / (float)B;
+        }
+        returns_out[b] = ret;
+        td_out[b] = td;
+        float *drow = dq + b * A;
+        for (int a = 0; a < A; ++a) drow[a] = (ok && a == (int)ac) ? g : 0.f;
+        p_l = (double)l;
+        p_q = (double)qs;
+    }
+    p_l = wave_sum(p_l);
+    p_q = wave_sum(p_q);
+    if (lane == 0) { s_red[0][w] = p_l; s_red[1][w] = p_q; }
+    __syncthreads();
+    if (t < 2) {
+        double acc = 0.0;
+        for (int k = 0; k < kDThreads / kWave; ++k) acc += s_red[t][k];
+        partial[(int64_t)blockIdx.x * 2 + t] = acc;
+    }
+}
+
+// Draws of row r are words of Philox4x32-10 at (seed, counter c + r): the coin is word 0; uniform[a] is word a % 4 of the
+// block whose third counter word is 1 + a / 4 (tsm_philox4 keeps that word zero, so these blocks belong to no other site).
+__device__ __forceinline__ void philox4_sub(uint64_t seed, uint64_t counter, uint32_t sub, uint32_t out[4]) {
+    uint32_t c0 = (uint32_t)counter, c1 = (uint32_t)(counter >> 32), c2 = sub, c3 = 0;
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        tsm_philox_round(c0, c1, c2, c3, k0, k1);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+__global__ __launch_bounds__(kDThreads) void dqn_egreedy_kernel(const float *__restrict__ q,
+                                                                const uint8_t *__restrict__ mask, int64_t R, int32_t A,
+                                                                const float *__restrict__ eps_dev, uint64_t seed,
+                                                                uint64_t offset, const uint64_t *__restrict__ offset_dev,
+                                                                int32_t *__restrict__ act) {
+    const int64_t r = (int64_t)blockIdx.x * kDThreads + threadIdx.x;
+    if (r >= R) return;
+    const uint64_t c = offset + (offset_dev ? *offset_dev : 0ull) + (uint64_t)r;
+    const float eps = *eps_dev;
+    const uint8_t *mrow = mask ? mask + r * A : nullptr;
+    uint32_t bits[4];
+    tsm_philox4(seed, c, bits);
+    int a_sel = 0;
+    if (tsm_u01(bits[0]) < eps) {  // rand_act = (uniform[A] + mask).argmax()   (dqn.py:166-169)
+        float best = 0.f;
+        for (int a = 0; a < A; ++a) {
+            if ((a & 3) == 0) philox4_sub(seed, c, 1u + (uint32_t)(a >> 2), bits);
+            const float v = tsm_u01(bits[a & 3]) + ((mrow && mrow[a]) ? 1.f : 0.f);
+            if (a == 0 || v > best) { best = v; a_sel = a; }
+        }
+    } else {
+        // first argmax of the masked q.  compute_q_value lowers every illegal entry below the smallest logit, so a row with
+        // a legal action picks its first best LEGAL entry; a row without one picks the first maximum of the raw row.
+        const float *row = q + r * A;
+        bool any = false;
+        float best = 0.f;
+        for (int a = 0; a < A; ++a)
+            if (!mrow || mrow[a]) {
+                if (!any || row[a] > best) { best = row[a]; a_sel = a; any = true; }
+            }
+        if (!any)
+            for (int a = 0; a < A; ++a)
+                if (a == 0 || row[a] > best) { best = row[a]; a_sel = a; }
+    }
+    act[r] = a_sel;
+}
+
+int dqn_check_act(const char *who, int32_t A) {
+    TSM_REQUIRE(A >= 1 && A <= kDMaxA, "%s: n_act = %d outside [1, %d]", who, A, kDMaxA);
+    return TSM_OK;
+}
+}  // namespace
+
+TSM_EXPORT int tsm_dqn_check(int32_t n_act, int32_t n_step) {
+    if (int rc = dqn_check_act("tsm_dqn_check", n_act)) return rc;
+    TSM_REQUIRE(n_step >= 1, "tsm_dqn_check: n_step_return_horizon should be greater than 0 but got: %d", n_step);
+    return TSM_OK;
+}
+
+TSM_EXPORT int64_t tsm_dqn_partial_elems(int64_t B) {
+    if (B < 1) return -1;
+    return 2 * ceil_div(B, kDThreads);
+}
+
+TSM_EXPORT int tsm_dqn_td_head(const float *q, const float *q_next_online, const float *q_next_target,
+                               const uint8_t *mask_next, const int64_t *act, const float *mc, const float *gpow,
+                               const uint8_t *vmask, const float *weight, int64_t B, int32_t n_act, int is_double,
+                               float huber_delta, float *returns_out, float *td_error, float *dq, double *partial,
+                               void *stream) {
+    if (int rc = dqn_check_act("tsm_dqn_td_head", n_act)) return rc;
+    // (With a mask and is_double every workgroup of 256 rows reads all B * n_act logits for the batch-wide offset: B^2 n_act /
+    //  256 loads in all -- 16 MB of L2 reads at B = 4096, n_act = 9, but quadratic in B.  The bound below is the index range,
+    //  not a promise of speed: a replay batch far beyond 10^5 masked rows wants a reduction launch of its own.)
+    TSM_REQUIRE(B >= 1 && B <= ((int64_t)1 << 31) / kDMaxA, "tsm_dqn_td_head: B = %lld out of range", (long long)B);
+    TSM_REQUIRE(q && q_next_online && act && mc && gpow && vmask && returns_out && td_error && dq && partial,
+                "tsm_dqn_td_head: null pointer");
+    hipLaunchKernelGGL(dqn_td_head_kernel, dim3((unsigned)ceil_div(B, kDThreads)), dim3(kDThreads), 0, tsm_stream(stream),
+                       q, q_next_online, q_next_target, mask_next, act, mc, gpow, vmask, weight, B, n_act, is_double,
+                       huber_delta, returns_out, td_error, dq, partial);
+    TSM_LAUNCH_CHECK();
+    return TSM_OK;
+}
+
+TSM_EXPORT int tsm_dqn_egreedy(const float *q, const uint8_t *mask, int64_t R, int32_t n_act, const float *eps_dev,
+                               uint64_t seed, uint64_t offset, const uint64_t *offset_dev, int32_t *act_out,
+                               void *stream) {
+    if (int rc = dqn_check_act("tsm_dqn_egreedy", n_act)) return rc;
+    TSM_REQUIRE(R >= 0, "tsm_dqn_egreedy: R = %lld is negative", (long long)R);
+    if (R == 0) return TSM_OK;
+    TSM_REQUIRE(q && eps_dev && act_out, "tsm_dqn_egreedy: null pointer");
+    hipLaunchKernelGGL(dqn_egreedy_kernel, dim3((unsigned)ceil_div(R, kDThreads)), dim3(kDThreads), 0, tsm_stream(stream),
+                       q, mask, R, n_act, eps_dev, seed, offset, offset_dev, act_out);
+    TSM_LAUNCH_CHECK();
+    return TSM_OK;
+}

@@ -1028,6 +1028,100 @@ def qmix_egreedy(q, eps_dev, seed: int, offset: int = 0, offset_dev=None, out=No
 
 
 # --------------------------------------------------------------------------------------------
+# n-step targets and DQN (algorithm_base.py:720-815; dqn.py; csrc/nstep.hip, csrc/dqn.hip)
+# --------------------------------------------------------------------------------------------
+def _dev_only(name: str, *tensors) -> None:
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{name} needs device (HIP) tensors; there is no CPU path")
+
+
+def dqn_check(n_act: int, n_step: int = 1) -> None:
+    """The bounds of the DQN kernels (include/tsmarl.h): ValueError naming the limit."""
+    call("tsm_dqn_check", int(n_act), int(n_step))
+
+
+def nstep_return(index: "VrbState", term_store, rew_store, indices, n_step: int, gamma: float, rew_col: int = 0,
+                 term_col: int = 0):
+    """The n-step walk of Algorithm.compute_nstep_return (algorithm_base.py:773-806, 1195-1211) for flat `indices` i64 [I]
+    over a device buffer: `index` its VrbState, term_store u8 [S, B, ...], rew_store f32 [S, B, ...]; rew_col / term_col
+    pick the agent's column.  -> (idx_n i64 [I], mc f32 [I], gpow f32 [I], vmask u8 [I])."""
+    _dev_only("nstep_return", term_store, rew_store, indices)
+    S, B = index.sub_size, index.buffer_num
+    term_store = _chk(term_store, torch.uint8, "term_store")
+    rew_store = _chk(rew_store, torch.float32, "rew_store")
+    if tuple(term_store.shape[:2]) != (S, B) or tuple(rew_store.shape[:2]) != (S, B):
+        raise ValueError(f"nstep_return: the stores must be [{S}, {B}, ...]")
+    indices = _chk(indices, torch.int64, "indices").reshape(-1)
+    I, dev = indices.numel(), indices.device
+    idx_n = torch.empty(I, dtype=torch.int64, device=dev)
+    mc = torch.empty(I, dtype=torch.float32, device=dev)
+    gpow = torch.empty(I, dtype=torch.float32, device=dev)
+    vmask = torch.empty(I, dtype=torch.uint8, device=dev)
+    call("tsm_nstep_return", ptr(index.state), B, S, ptr(index.done_store), ptr(term_store), term_store[0, 0].numel(),
+         int(term_col), ptr(rew_store), rew_store[0, 0].numel(), int(rew_col), ptr(indices), I, int(n_step), float(gamma),
+         ptr(idx_n), ptr(mc), ptr(gpow), ptr(vmask), stream_ptr())
+    return idx_n, mc, gpow, vmask
+
+
+def dqn_td_head(q, q_next_online, q_next_target, act, mc, gpow, vmask, mask_next=None, weight=None, is_double: bool = True,
+                huber_delta: float | None = None):
+    """DQN._target_q after its forwards + the n-step target + the TD loss and its gradient (dqn.py:365-402) in one launch.
+    q, q_next_online [B, A]; q_next_target [B, A] or None (no target network); act i64 [B]; mc, gpow, vmask from
+    nstep_return; mask_next u8 / bool [B, A] or None; weight f32 [B] or None.
+    -> dict(returns [B], td_error [B], dq [B, A], partial f64): `qmix_finalize(partial, B, out)` gives {loss, mean q}."""
+    _dev_only("dqn_td_head", q, q_next_online, q_next_target, act, mc, gpow, vmask, mask_next, weight)
+    q = _chk(q, torch.float32, "q")
+    if q.dim() != 2:
+        raise ValueError("dqn_td_head: q must be [B, A]")
+    B, A = q.shape
+    dqn_check(A)
+    if B < 1:
+        raise ValueError("dqn_td_head: empty batch")
+    for name, x in (("q_next_online", q_next_online), ("q_next_target", q_next_target), ("mask_next", mask_next)):
+        if x is not None and tuple(x.shape) != (B, A):
+            raise ValueError(f"dqn_td_head: {name} must be [{B}, {A}]")
+    for name, x in (("act", act), ("mc", mc), ("gpow", gpow), ("vmask", vmask), ("weight", weight)):
+        if x is not None and x.numel() != B:
+            raise ValueError(f"dqn_td_head: {name} must have {B} entries")
+    u8 = lambda x, n: x.contiguous().view(torch.uint8) if x.dtype == torch.bool else _chk(x, torch.uint8, n)  # noqa: E731
+    dev = q.device
+    out = dict(returns=torch.empty(B, dtype=torch.float32, device=dev), td_error=torch.empty(B, dtype=torch.float32, device=dev),
+               dq=torch.empty(B, A, dtype=torch.float32, device=dev),
+               partial=torch.empty(call("tsm_dqn_partial_elems", B), dtype=torch.float64, device=dev))
+    call("tsm_dqn_td_head", ptr(q), ptr(_chk(q_next_online, torch.float32, "q_next_online")),
+         ptr(None if q_next_target is None else _chk(q_next_target, torch.float32, "q_next_target")),
+         ptr(None if mask_next is None else u8(mask_next, "mask_next")), ptr(_chk(act, torch.int64, "act").reshape(-1)),
+         ptr(_chk(mc, torch.float32, "mc").reshape(-1)), ptr(_chk(gpow, torch.float32, "gpow").reshape(-1)),
+         ptr(u8(vmask, "vmask").reshape(-1)), ptr(None if weight is None else _chk(weight, torch.float32, "weight").reshape(-1)),
+         B, A, int(bool(is_double)), float(huber_delta) if huber_delta is not None else 0.0, ptr(out["returns"]),
+         ptr(out["td_error"]), ptr(out["dq"]), ptr(out["partial"]), stream_ptr())
+    return out
+
+
+def dqn_egreedy(q, eps_dev, seed: int, offset: int = 0, offset_dev=None, mask=None, out=None):
+    """Masked epsilon-greedy actions (dqn.py:140-141, 153-171) on the device: q [R, A], mask u8 / bool [R, A] or None ->
+    act i32 [R].  One coin per ROW; eps read from the device scalar eps_dev; row r draws at Philox counter offset + r."""
+    _dev_only("dqn_egreedy", q, eps_dev, mask, out, offset_dev)
+    q = _chk(q, torch.float32, "q")
+    if q.dim() != 2:
+        raise ValueError("dqn_egreedy: q must be [R, A]")
+    R, A = q.shape
+    dqn_check(A)
+    if mask is not None:
+        if tuple(mask.shape) != (R, A):
+            raise ValueError(f"dqn_egreedy: mask must be [{R}, {A}]")
+        mask = mask.contiguous().view(torch.uint8) if mask.dtype == torch.bool else _chk(mask, torch.uint8, "mask")
+    if out is None:
+        out = torch.empty(R, dtype=torch.int32, device=q.device)
+    elif out.numel() < R or not out.is_contiguous():
+        raise ValueError(f"dqn_egreedy: out must be a contiguous i32 tensor of at least {R} entries")
+    call("tsm_dqn_egreedy", ptr(q), ptr(mask), R, A, ptr(_chk(eps_dev, torch.float32, "eps_dev")), seed & (2**64 - 1),
+         offset & (2**64 - 1), ptr(offset_dev), ptr(_chk(out, torch.int32, "out")), stream_ptr())
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # MADDPG (ctde.py:728-955; csrc/maddpg.hip)
 # --------------------------------------------------------------------------------------------
 def maddpg_check(n_agents: int, act_dim: int | None = None) -> None:
