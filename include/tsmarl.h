@@ -973,6 +973,51 @@ int tsm_dqn_td_head(const float *q, const float *q_next_online, const float *q_n
 int tsm_dqn_egreedy(const float *q, const uint8_t *mask, int64_t R, int32_t n_act, const float *eps_dev, uint64_t seed,
                     uint64_t offset, const uint64_t *offset_dev, int32_t *act_out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Prioritized experience replay  (tianshou/data/utils/segtree.py, tianshou/data/buffer/prio.py)
+ * The tree is the reference's: double tree[2 * bound], bound = tsm_segtree_bound(size) = the smallest power of two >= size
+ * (-1 for a size outside [1, 2^30]); leaf i at tree[bound + i], node k = tree[2k] + tree[2k + 1], tree[1] the total,
+ * padding leaves 0.  mark: i32 [bound] scratch of the set, all -1 before the first call and after every call.
+ * err: one i64 word in HBM; a set / IS-weight launch that meets an index outside [0, size) skips that entry and stores 1
+ * there -- tsm_segtree_check reads the word (one synchronisation), clears it and returns TSM_ERR_INVALID if it was set.
+ * prio: f64 [2] = {max_prio, min_prio} in HBM, both 1.0 at the start (prio.py:39); read and folded on the device only.
+ *
+ * tsm_segtree_set replaces  `_setitem` (segtree.py:95-101) behind SegmentTree.__setitem__ (:35-51): leaves index[n] <-
+ *           value[value_n], value_n == n or 1 (one value for all), then every ancestor.  One launch of one workgroup with a
+ *           barrier per level.  Of several entries with one index the LAST wins, as in numpy's `tree[index] = value`.
+ * tsm_segtree_prefix_sum_idx replaces  `_get_prefix_sum_idx` (segtree.py:119-134): per value[n] (f64) the descent from the
+ *           root with `tree[left] < value` (strict) -> leaf indices i64 [n].  size == 1: 0.
+ * tsm_segtree_reduce replaces  `_reduce` (segtree.py:104-116) behind SegmentTree.reduce(start, end) (:53-61): the sum of
+ *           leaves [start, end) by the reference's additions in its order -> out f64 [1] in HBM.
+ * tsm_per_sample replaces  `np.random.rand(batch_size) * self.weight.reduce()` + get_prefix_sum_idx of
+ *           PrioritizedReplayBuffer.sample_indices (prio.py:63-66) in one launch: draw i = words 0, 1 of Philox4x32-10 at
+ *           (seed, offset + *offset_dev + i) (offset_dev nullable), u = 52 bits * 2^-52, value = u * tree[1] < tree[1] for
+ *           every draw (so no zero-weight padding leaf is reached) -> index_out i64 [n].
+ * tsm_per_update_weight replaces  PrioritizedReplayBuffer.update_weight (prio.py:81-90): w = |td| + eps(f32) in float32,
+ *           leaf = (double) w ** alpha with the power in float32 (alpha == 1: w itself), the set above, and
+ *           prio <- {max(max_prio, max w), min(min_prio, min w)}.
+ * tsm_per_init_weight replaces  init_weight (prio.py:46-47): leaves index[n] <- max_prio ** alpha, max_prio read from prio.
+ * tsm_per_get_weight replaces  get_weight (prio.py:69-79) and the normalisation of __getitem__ (:103-106):
+ *           (tree[bound + index] / min_prio) ** (-beta) in float64, divided by the batch maximum when weight_norm != 0
+ *           -> out64 f64 [n] (the Batch the host API returns) and out32 f32 [n] = the same values rounded (the TD head's
+ *           `weight`).  One workgroup.
+ * ------------------------------------------------------------------------------------------- */
+int64_t tsm_segtree_bound(int64_t size);
+int tsm_segtree_set(double *tree, int32_t *mark, int64_t size, const int64_t *index, int64_t n, const double *value,
+                    int64_t value_n, int64_t *err, void *stream);
+int tsm_segtree_prefix_sum_idx(const double *tree, int64_t size, const double *value, int64_t n, int64_t *index_out,
+                               void *stream);
+int tsm_segtree_reduce(const double *tree, int64_t size, int64_t start, int64_t end, double *out, void *stream);
+int tsm_segtree_check(int64_t *err, void *stream);
+int tsm_per_sample(const double *tree, int64_t size, int64_t n, uint64_t seed, uint64_t offset, const uint64_t *offset_dev,
+                   int64_t *index_out, void *stream);
+int tsm_per_update_weight(double *tree, int32_t *mark, int64_t size, const int64_t *index, const float *td, int64_t n,
+                          double alpha, double *prio, int64_t *err, void *stream);
+int tsm_per_init_weight(double *tree, int32_t *mark, int64_t size, const int64_t *index, int64_t n, double alpha,
+                        double *prio, int64_t *err, void *stream);
+int tsm_per_get_weight(const double *tree, int64_t size, const int64_t *index, int64_t n, double beta, int weight_norm,
+                       const double *prio, float *out32, double *out64, int64_t *err, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

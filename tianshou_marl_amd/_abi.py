@@ -263,6 +263,15 @@ SIGNATURES = {
     "tsm_dqn_partial_elems": (_i64, [_i64]),
     "tsm_dqn_td_head": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _int, C.c_float, _p, _p, _p, _p, _p]),
     "tsm_dqn_egreedy": (_int, [_p, _p, _i64, _i32, _p, _u64, _u64, _p, _p, _p]),
+    "tsm_segtree_bound": (_i64, [_i64]),
+    "tsm_segtree_set": (_int, [_p, _p, _i64, _p, _i64, _p, _i64, _p, _p]),
+    "tsm_segtree_prefix_sum_idx": (_int, [_p, _i64, _p, _i64, _p, _p]),
+    "tsm_segtree_reduce": (_int, [_p, _i64, _i64, _i64, _p, _p]),
+    "tsm_segtree_check": (_int, [_p, _p]),
+    "tsm_per_sample": (_int, [_p, _i64, _i64, _u64, _u64, _p, _p, _p]),
+    "tsm_per_update_weight": (_int, [_p, _p, _i64, _p, _p, _i64, _f64, _p, _p, _p]),
+    "tsm_per_init_weight": (_int, [_p, _p, _i64, _p, _i64, _f64, _p, _p, _p]),
+    "tsm_per_get_weight": (_int, [_p, _i64, _p, _i64, _f64, _int, _p, _p, _p, _p, _p]),
 }
 
 _NO_STATUS = {"tsm_critic_rows_w1_image_kj", "tsm_critic_rows_w1_image_elems", "tsm_p2p_ipc_handle_bytes", "tsm_p2p_failed", "tsm_critic_rows_forward_supported", "tsm_critic_rows_param_count", "tsm_critic_rows_grad_grid", "tsm_critic_rows_dw1_chunks", "tsm_ppo_critic_rows_supported", "tsm_ppo_critic_rows_param_count", "tsm_ppo_critic_rows_grid",
@@ -270,7 +279,8 @@ _NO_STATUS = {"tsm_critic_rows_w1_image_kj", "tsm_critic_rows_w1_image_elems", "
               "tsm_rms_update_work_elems", "tsm_ppo_adv_stats_work_elems", "tsm_abi_version", "tsm_last_error", "tsm_stream_abort_capture", "tsm_vrb_state_bytes", "tsm_ppo_loss_partial_elems",
               "tsm_policy_param_count", "tsm_ppo_update_grid", "tsm_adam_work_elems", "tsm_policy_image_elems",
               "tsm_mlp_param_count", "tsm_mlp_act_elems", "tsm_ctde_head_partial_elems", "tsm_mpe_tag_obs_dim",
-              "tsm_gae_scan_workspace_bytes", "tsm_qmix_partial_elems", "tsm_maddpg_partial_elems", "tsm_dqn_partial_elems"}
+              "tsm_gae_scan_workspace_bytes", "tsm_qmix_partial_elems", "tsm_maddpg_partial_elems", "tsm_dqn_partial_elems",
+              "tsm_segtree_bound"}
 
 _lib = None
 

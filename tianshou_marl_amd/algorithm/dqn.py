@@ -17,6 +17,7 @@ mask read with obs_next[idx_n] is the one the buffer keeps for row idx_n.
 """
 from __future__ import annotations
 
+import logging
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Any
@@ -31,6 +32,8 @@ from ..data.stats import ResultRing, TrainingStats, pinned_slot
 from ..utils.net import FlatAdam, FlatMLP
 from ..utils.tensor import to_tensor
 from .optim import AdamOptimizerFactory
+
+log = logging.getLogger(__name__)
 
 
 @dataclass(kw_only=True)
@@ -293,15 +296,38 @@ class DQN(nn.Module):
         slot["event"].synchronize()
         return SimpleLossTrainingStats(loss=float(slot["h"][0]))
 
+    @staticmethod
+    def _sampled_batch(buffer, indices) -> Batch:
+        """What `update` keeps of `buffer[indices]`: the rows stay in the device stores (`_preprocess_batch` gathers them); a
+        prioritized buffer adds `weight`, its importance-sampling weights (prio.py:103-106) as float32 in HBM -- the TD head's
+        `weight` (quirk Q17: the Huber loss ignores it)."""
+        batch = Batch()
+        if hasattr(buffer, "update_weight"):
+            batch.weight = buffer.batch_weight_device(indices)[0]
+        return batch
+
+    def _postprocess_batch(self, batch: Batch, buffer, indices) -> None:
+        """Algorithm._postprocess_batch (algorithm_base.py:560-582): a prioritized buffer takes `batch.weight` -- after
+        `_update_with_batch` the TD errors, still in HBM -- as the new priorities of `indices`."""
+        if hasattr(buffer, "update_weight"):
+            if "weight" in batch:
+                buffer.update_weight(indices, batch.weight)
+            else:
+                log.warning("batch has no attribute 'weight', but buffer has an update_weight method. This is probably a "
+                            "mistake. Prioritized replay is disabled for this batch.")
+
     def update(self, buffer, sample_size: int | None, agent: int | None = None) -> SimpleLossTrainingStats:
-        """OffPolicyAlgorithm.update (algorithm_base.py:889-905): sample, preprocess, update.  The sampled rows are read
-        from the device stores in place (`buffer.sample` would carry them through the host)."""
+        """OffPolicyAlgorithm.update (algorithm_base.py:889-905): sample, preprocess, update, postprocess.  The sampled rows
+        are read from the device stores in place (`buffer.sample` would carry them through the host); with a prioritized
+        buffer the indices, the IS weights and the new priorities stay in HBM too, so the loss slot is the only host read."""
         if not self.is_within_training_step:
             raise RuntimeError("update() was called outside of a training step as signalled by "
                                "`is_within_training_step=False`")
-        indices = buffer.sample_indices(sample_size)
-        batch = self._preprocess_batch(Batch(), buffer, indices, agent=agent)
+        prioritized = hasattr(buffer, "update_weight")
+        indices = buffer.sample_indices_device(sample_size) if prioritized else buffer.sample_indices(sample_size)
+        batch = self._preprocess_batch(self._sampled_batch(buffer, indices), buffer, indices, agent=agent)
         stats = self._update_with_batch(batch)
+        self._postprocess_batch(batch, buffer, indices)
         if self.lr_scheduler is not None:
             self.lr_scheduler.step()
         return stats

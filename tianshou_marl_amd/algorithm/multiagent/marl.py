@@ -17,6 +17,7 @@ Two row formats reach `forward`:
 """
 from __future__ import annotations
 
+import logging
 from collections.abc import Callable
 from typing import Any
 
@@ -27,6 +28,8 @@ from torch import nn
 from ... import ops
 from ...data.batch import Batch
 from ...data.stats import MapTrainingStats
+
+log = logging.getLogger(__name__)
 
 
 def _unique(objs) -> list:
@@ -313,7 +316,8 @@ class MARLDispatcher:
         if not getattr(buffer, "aec", False):
             idx = torch.as_tensor(np.asarray(buffer.sample_indices(0) if indices is None else indices)).to(dev, torch.int64)
             for agent, algorithm in self.algorithms.items():
-                results[agent] = algorithm._preprocess_batch(Batch(), buffer, idx, agent=self.agent_idx[agent]) if idx.numel() else None
+                results[agent] = (algorithm._preprocess_batch(self._rows_of(buffer, idx), buffer, idx, agent=self.agent_idx[agent])
+                                  if idx.numel() else None)
             return results
         if indices is None:
             idx, pos, offs = self.aec_partition(buffer)
@@ -326,8 +330,18 @@ class MARLDispatcher:
             if hi == lo:
                 results[agent] = None
                 continue
-            results[agent] = algorithm._preprocess_batch(Batch(), buffer, idx[pos[lo:hi]].contiguous(), agent=k)
+            results[agent] = algorithm._preprocess_batch(self._rows_of(buffer, idx, pos[lo:hi]), buffer, idx[pos[lo:hi]].contiguous(),
+                                                         agent=k)
         return results
+
+    @staticmethod
+    def _rows_of(buffer, idx: torch.Tensor, rows: torch.Tensor | None = None) -> Batch:
+        """`batch[agent_index]` (marl.py:237) as far as an off-policy update reads it: of a prioritized buffer the IS weights of
+        the WHOLE sampled batch (normalised over it, prio.py:103-106), sliced to the agent's rows."""
+        if not hasattr(buffer, "update_weight") or idx.numel() == 0:
+            return Batch()
+        w = buffer.batch_weight_device(idx)[0]
+        return Batch(weight=w if rows is None else w[rows].contiguous())
 
     def dispatch_update_with_batch(self, batch: dict, algorithm_update_with_batch_fn: Callable) -> MapTrainingStats:
         agent_id_to_stats = {}
@@ -347,6 +361,7 @@ class MultiAgentOffPolicyAlgorithm(nn.Module):
         self._dispatcher = MARLDispatcher(algorithms, env)
         self.policy = self._dispatcher.create_policy()
         self._submodules = nn.ModuleList([a for a in _unique(algorithms) if isinstance(a, nn.Module)])
+        self._warned_no_weight = False
 
     @property
     def is_within_training_step(self) -> bool:
@@ -366,13 +381,24 @@ class MultiAgentOffPolicyAlgorithm(nn.Module):
     def _update_with_batch(self, batch: dict) -> MapTrainingStats:
         return self._dispatcher.dispatch_update_with_batch(batch, lambda algorithm, data, agent_col: algorithm._update_with_batch(data))
 
+    def _postprocess_batch(self, batch: dict, buffer, indices) -> None:
+        """Algorithm._postprocess_batch (algorithm_base.py:560-582) as the reference runs it here: the batch is a per-agent dict
+        without `weight`, so a prioritized buffer is sampled by priority but its priorities are not written back -- the
+        reference warns on every update, this says it once."""
+        if hasattr(buffer, "update_weight") and not self._warned_no_weight:
+            self._warned_no_weight = True
+            log.warning("batch has no attribute 'weight', but buffer has an update_weight method. This is probably a mistake. "
+                        "Prioritized replay is disabled for this batch.")
+
     def update(self, buffer, sample_size: int | None):
         """OffPolicyAlgorithm.update (algorithm_base.py:889-905) through the dispatcher."""
         if not self.is_within_training_step:
             raise RuntimeError("update() was called outside of a training step as signalled by "
                                "`is_within_training_step=False`")
         indices = None if sample_size == 0 else buffer.sample_indices(sample_size)
-        stats = self._update_with_batch(self._preprocess_batch(None, buffer, indices))
+        batch = self._preprocess_batch(None, buffer, indices)
+        stats = self._update_with_batch(batch)
+        self._postprocess_batch(batch, buffer, indices)
         for a in _unique(self._dispatcher.algorithms.values()):
             if getattr(a, "lr_scheduler", None) is not None:
                 a.lr_scheduler.step()

@@ -27,6 +27,10 @@ _RESERVED = ("obs", "act", "rew", "terminated", "truncated", "done", "obs_next",
 
 
 class DeviceVectorReplayBuffer:
+    # True: every row must arrive through add_device (a subclass hooks it), so a Collector does not take a persistent rollout,
+    # whose kernel writes the rows itself
+    unfused_adds_only = False
+
     def __init__(self, total_size: int, buffer_num: int, n_agent: int, obs_dim: int, device: str | torch.device = "cuda",
                  ignore_obs_next: bool = False, store_policy_outputs: bool = True) -> None:
         self.buffer_num = int(buffer_num)
@@ -490,6 +494,98 @@ class VectorReplayBuffer(DeviceVectorReplayBuffer):
         if key in ("index", "obs_store") or key.endswith("_store"):
             raise AttributeError(f"{key}: the buffer is not allocated yet (bind it to an env through a Collector, or add a row)")
         return super().__getattr__(key)
+
+
+class PrioritizedVectorReplayBuffer(VectorReplayBuffer):
+    """`PrioritizedVectorReplayBuffer(total_size, buffer_num, alpha=, beta=)` (vecbuf.py:40-66, manager.py:234-262,
+    prio.py:12-113): one sum tree over all `maxsize` rows, in HBM (`weight`: ops.DeviceSegmentTree, csrc/segtree.hip), next to
+    `prio` = {max_prio, min_prio} f64 [2], which only kernels read and fold.  Sampling, the IS weights and the priority
+    write-back are launches without a host round trip (`sample_indices_device`, `batch_weight_device`, `update_weight` with
+    device tensors); the reference-shaped methods copy their results to numpy.
+
+    Where it differs from the reference: `weight_norm=False` is honoured (the reference's manager re-initialises itself from
+    `options`, which drops it: manager.py:250-255); `update_weight` takes the power in float32 whatever the dtype of
+    `new_weight` (the reference does for the float32 TD errors an update hands it); draws come from Philox (seed, counter),
+    not from numpy's global RNG."""
+
+    unfused_adds_only = True  # rows enter through add_device, which gives them max_prio ** alpha
+
+    def __init__(self, total_size: int, buffer_num: int, alpha: float, beta: float, weight_norm: bool = True,
+                 n_agent: int | None = None, obs_dim: int | None = None, device: str | torch.device = "cuda", seed: int = 0,
+                 **kwargs) -> None:
+        assert alpha > 0.0, f"alpha should be positive but got: {alpha}"
+        assert beta >= 0.0, f"beta should be non-negative but got: {beta}"
+        super().__init__(total_size, buffer_num, n_agent, obs_dim, device=device, **kwargs)
+        self._alpha, self._beta, self._weight_norm = float(alpha), float(beta), bool(weight_norm)
+        self.weight = ops.DeviceSegmentTree(self.maxsize, device=device)
+        self.prio = torch.ones(2, dtype=torch.float64, device=self.weight.device)
+        self.options = dict(stack_num=1, ignore_obs_next=bool(kwargs.get("ignore_obs_next", False)), save_only_last_obs=False,
+                            sample_avail=False, alpha=alpha, beta=beta)
+        self.seed = int(seed)
+        self._sample_ctr = 0
+        self._has_rows = False  # host mirror of `len(self) > 0` (prio.py:64) that costs no device read
+
+    def storage_key(self) -> tuple:
+        return super().storage_key() + (self.weight.tree.data_ptr(), self.weight.mark.data_ptr(), self.prio.data_ptr())
+
+    def set_beta(self, beta: float) -> None:
+        self._beta = float(beta)
+
+    def _tree_index(self, index) -> torch.Tensor:
+        """i64 device indices; host indices are checked here (segtree.py:49-50), device ones by the kernel's error word."""
+        if isinstance(index, torch.Tensor) and index.is_cuda:
+            return index.to(torch.int64).reshape(-1)
+        idx = np.atleast_1d(np.asarray(index.cpu() if isinstance(index, torch.Tensor) else index)).astype(np.int64).reshape(-1)
+        assert np.all(idx >= 0) and np.all(idx < self.maxsize), "index outside the segment tree"
+        return torch.as_tensor(idx).to(self.weight.device)
+
+    def init_weight(self, index) -> None:
+        ops.per_init_weight(self.weight, self._tree_index(index), self._alpha, self.prio)
+
+    def update_weight(self, index, new_weight) -> None:
+        w = new_weight if isinstance(new_weight, torch.Tensor) else torch.as_tensor(np.asarray(new_weight))
+        ops.per_update_weight(self.weight, self._tree_index(index), w.detach().to(self.weight.device, torch.float32).reshape(-1),
+                              self._alpha, self.prio)
+
+    def get_weight(self, index):
+        """prio.py:69-79 -> float64 numpy (a float for a scalar index)."""
+        w = ops.per_get_weight(self.weight, self._tree_index(index), self._beta, False, self.prio)[1].cpu().numpy()
+        return float(w[0]) if np.isscalar(index) else w
+
+    def batch_weight_device(self, index):
+        """`self[index].weight` (prio.py:103-106) in HBM -> (f32 [n] for the TD head, f64 [n])."""
+        return ops.per_get_weight(self.weight, self._tree_index(index), self._beta, self._weight_norm, self.prio)
+
+    def add_device(self, *args, **kwargs):
+        out = super().add_device(*args, **kwargs)
+        self.init_weight(out[0])  # prio.py:59-60 on the device `ptr`
+        self._has_rows = self._has_rows or out[0].numel() > 0
+        return out
+
+    def reset(self, keep_statistics: bool = False) -> None:
+        """The tree and the priority pair stay as they are: ReplayBuffer.reset never touches `weight`."""
+        super().reset(keep_statistics)
+        self._has_rows = False
+
+    def sample_indices_device(self, batch_size: int | None) -> torch.Tensor:
+        """`sample_indices` without the copy to the host: i64 [batch_size] in HBM."""
+        if batch_size is not None and batch_size > 0 and self._has_rows:  # prio.py:64
+            idx = ops.per_sample(self.weight, batch_size, self.seed, offset=self._sample_ctr)
+            self._sample_ctr += int(batch_size)
+            return idx
+        return torch.as_tensor(super().sample_indices(batch_size), dtype=torch.int64).to(self.weight.device)
+
+    def sample_indices(self, batch_size: int | None = 0) -> np.ndarray:
+        if batch_size is not None and batch_size > 0 and self._has_rows:
+            return self.sample_indices_device(batch_size).cpu().numpy()
+        return super().sample_indices(batch_size)
+
+    def __getitem__(self, index) -> Batch:
+        if isinstance(index, slice):
+            index = self.sample_indices(0) if index == slice(None) else np.arange(len(self))[index]
+        batch = super().__getitem__(index)
+        batch.weight = self.batch_weight_device(index)[1].cpu().numpy()
+        return batch
 
 
 def _obs_array(obs) -> np.ndarray:

@@ -1122,6 +1122,134 @@ def dqn_egreedy(q, eps_dev, seed: int, offset: int = 0, offset_dev=None, mask=No
 
 
 # --------------------------------------------------------------------------------------------
+# Prioritized replay (data/utils/segtree.py, data/buffer/prio.py; csrc/segtree.hip)
+# --------------------------------------------------------------------------------------------
+def segtree_bound(size: int) -> int:
+    """The smallest power of two >= size (segtree.py:20-22); ValueError outside [1, 2^30]."""
+    bound = call("tsm_segtree_bound", int(size))
+    if bound < 0:
+        raise ValueError(f"segment tree: size = {size} outside [1, 2^30]")
+    return bound
+
+
+def _tree_index(t: "DeviceSegmentTree", name: str, index) -> torch.Tensor:
+    _dev_only(name, index)
+    return _chk(index, torch.int64, "index").reshape(-1)
+
+
+def segtree_set(t: "DeviceSegmentTree", index, value) -> None:
+    """`_setitem` (segtree.py:95-101): leaves index i64 [n] <- value f64 [n] or [1] (one for all), then their ancestors, in one
+    launch.  Of several entries with one index the last wins."""
+    index = _tree_index(t, "segtree_set", index)
+    _dev_only("segtree_set", value)
+    value = _chk(value, torch.float64, "value").reshape(-1)
+    call("tsm_segtree_set", ptr(t.tree), ptr(t.mark), t.size, ptr(index), index.numel(), ptr(value), value.numel(),
+         ptr(t.err), stream_ptr())
+
+
+def segtree_prefix_sum_idx(t: "DeviceSegmentTree", value) -> torch.Tensor:
+    """`_get_prefix_sum_idx` (segtree.py:119-134): value f64 [n] -> leaf indices i64 [n]."""
+    _dev_only("segtree_prefix_sum_idx", value)
+    value = _chk(value, torch.float64, "value").reshape(-1)
+    out = torch.empty(value.numel(), dtype=torch.int64, device=value.device)
+    call("tsm_segtree_prefix_sum_idx", ptr(t.tree), t.size, ptr(value), value.numel(), ptr(out), stream_ptr())
+    return out
+
+
+def segtree_reduce(t: "DeviceSegmentTree", start: int, end: int) -> torch.Tensor:
+    """`_reduce` (segtree.py:104-116): the sum of leaves [start, end) -> f64 [1] in HBM."""
+    out = torch.empty(1, dtype=torch.float64, device=t.tree.device)
+    call("tsm_segtree_reduce", ptr(t.tree), t.size, int(start), int(end), ptr(out), stream_ptr())
+    return out
+
+
+def segtree_check(t: "DeviceSegmentTree") -> None:
+    """ValueError if a launch since the last check met an index outside [0, size) (one synchronisation)."""
+    call("tsm_segtree_check", ptr(t.err), stream_ptr())
+
+
+def per_sample(t: "DeviceSegmentTree", n: int, seed: int, offset: int = 0, offset_dev=None) -> torch.Tensor:
+    """prio.py:63-66 in one launch: n leaf indices i64 drawn in proportion to the leaves; draw i at Philox counter offset +
+    *offset_dev + i."""
+    _dev_only("per_sample", offset_dev)
+    out = torch.empty(int(n), dtype=torch.int64, device=t.tree.device)
+    call("tsm_per_sample", ptr(t.tree), t.size, int(n), seed & (2**64 - 1), offset & (2**64 - 1), ptr(offset_dev), ptr(out),
+         stream_ptr())
+    return out
+
+
+def per_update_weight(t: "DeviceSegmentTree", index, td, alpha: float, prio) -> None:
+    """prio.py:81-90: leaves index <- (|td| + eps) ** alpha in float32, and prio f64 [2] = {max_prio, min_prio} folded."""
+    index = _tree_index(t, "per_update_weight", index)
+    _dev_only("per_update_weight", td, prio)
+    td = _chk(td, torch.float32, "td").reshape(-1)
+    if td.numel() != index.numel():
+        raise ValueError(f"per_update_weight: {td.numel()} weights for {index.numel()} indices")
+    call("tsm_per_update_weight", ptr(t.tree), ptr(t.mark), t.size, ptr(index), ptr(td), index.numel(), float(alpha),
+         ptr(_chk(prio, torch.float64, "prio")), ptr(t.err), stream_ptr())
+
+
+def per_init_weight(t: "DeviceSegmentTree", index, alpha: float, prio) -> None:
+    """prio.py:46-47: leaves index <- max_prio ** alpha, max_prio read on the device."""
+    index = _tree_index(t, "per_init_weight", index)
+    _dev_only("per_init_weight", prio)
+    call("tsm_per_init_weight", ptr(t.tree), ptr(t.mark), t.size, ptr(index), index.numel(), float(alpha),
+         ptr(_chk(prio, torch.float64, "prio")), ptr(t.err), stream_ptr())
+
+
+def per_get_weight(t: "DeviceSegmentTree", index, beta: float, weight_norm: bool, prio):
+    """prio.py:69-79, 103-106: (leaf / min_prio) ** (-beta), over the batch maximum when weight_norm -> (f32 [n], f64 [n])."""
+    index = _tree_index(t, "per_get_weight", index)
+    _dev_only("per_get_weight", prio)
+    n, dev = index.numel(), index.device
+    out32 = torch.empty(n, dtype=torch.float32, device=dev)
+    out64 = torch.empty(n, dtype=torch.float64, device=dev)
+    call("tsm_per_get_weight", ptr(t.tree), t.size, ptr(index), n, float(beta), int(bool(weight_norm)),
+         ptr(_chk(prio, torch.float64, "prio")), ptr(out32), ptr(out64), ptr(t.err), stream_ptr())
+    return out32, out64
+
+
+class DeviceSegmentTree:
+    """`SegmentTree(size)` (segtree.py:5-93) in HBM: `tree` f64 [2 * bound] in the reference's layout."""
+
+    def __init__(self, size: int, device="cuda") -> None:
+        self.size = int(size)
+        self.bound = segtree_bound(self.size)
+        self.device = torch.device(device)
+        self.tree = torch.zeros(2 * self.bound, dtype=torch.float64, device=self.device)
+        self.mark = torch.full((self.bound,), -1, dtype=torch.int32, device=self.device)
+        self.err = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def __len__(self) -> int:
+        return self.size
+
+    def _dev(self, x, dtype) -> torch.Tensor:
+        # (dtype given to as_tensor: a Python float would otherwise pass through torch's default float32 and lose bits)
+        return torch.as_tensor(x, dtype=dtype).to(self.device).reshape(-1)
+
+    def __getitem__(self, index) -> torch.Tensor:
+        return self.tree[self._dev(index, torch.int64) + self.bound]
+
+    def __setitem__(self, index, value) -> None:
+        segtree_set(self, self._dev(index, torch.int64), self._dev(value, torch.float64))
+
+    def reduce(self, start: int = 0, end: int | None = None) -> torch.Tensor:
+        if start == 0 and end is None:
+            return self.tree[1:2]
+        if end is None:
+            end = self.size
+        if end < 0:
+            end += self.size
+        return segtree_reduce(self, start, end)
+
+    def get_prefix_sum_idx(self, value) -> torch.Tensor:
+        return segtree_prefix_sum_idx(self, self._dev(value, torch.float64))
+
+    def check(self) -> None:
+        segtree_check(self)
+
+
+# --------------------------------------------------------------------------------------------
 # MADDPG (ctde.py:728-955; csrc/maddpg.hip)
 # --------------------------------------------------------------------------------------------
 def maddpg_check(n_agents: int, act_dim: int | None = None) -> None:
