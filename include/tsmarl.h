@@ -1018,6 +1018,52 @@ int tsm_per_init_weight(double *tree, int32_t *mark, int64_t size, const int64_t
 int tsm_per_get_weight(const double *tree, int64_t size, const int64_t *index, int64_t n, double beta, int weight_norm,
                        const double *prio, float *out32, double *out64, int64_t *err, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Distributional Q-learning: C51 and QR-DQN  (tianshou/algorithm/modelfree/c51.py, qrdqn.py; csrc/distq.hip)
+ * The Q-network emits raw f32 [rows][n_act * n_atoms]; a row is read as [n_act][n_atoms].  The softmax over atoms that the
+ * reference's Net(num_atoms=N, softmax=True) applies inside the module is part of these kernels.
+ * tsm_distq_check: the bounds of the kernels (n_act in [1, 64] as for tsm_dqn_egreedy, n_atoms in [2, 256]; C51Policy.__init__,
+ *   c51.py:56, QRDQN.__init__, qrdqn.py:78): TSM_ERR_INVALID naming the limit.
+ * tsm_distq_values replaces  the reduction of C51Policy.compute_q_value (c51.py:67: `(logits * self.support).sum(2)`, with the
+ *           module's softmax) when categorical != 0, of QRDQNPolicy.compute_q_value (qrdqn.py:20: `logits.mean(2)`) otherwise.
+ *   raw [R][n_act][n_atoms]; support f32 [n_atoms] (categorical only: torch.linspace(v_min, v_max, n_atoms), filled by the
+ *   host so that it holds the reference's values).  out: q f32 [R][n_act]; probs f32 [R][n_act][n_atoms] (nullable,
+ *   categorical only): the softmax, `Batch.logits` of C51Policy.forward.  q feeds tsm_dqn_egreedy and the heads below.
+ * tsm_c51_head replaces  C51._target_dist after its forwards (c51.py:123-141) and C51._update_with_batch between
+ *           `self.policy(batch).logits` and `optim.step(loss)` (c51.py:150-158), with compute_nstep_return's last line for
+ *           `_target_q` = the support (c51.py:120-121, algorithm_base.py:796, 1213-1215).  One launch.
+ *   raw [B][n_act][n_atoms]: the online net on obs.  q_next [B][n_act]: tsm_distq_values of the ONLINE net on the successor
+ *   rows; a* = its first argmax under mask_next (nullable) with compute_q_value's whole-tensor offset, as tsm_dqn_td_head.
+ *   raw_next [B][n_act][n_atoms]: the lagged net on the same rows when there is one, else the online net's output.
+ *   act i64 [B]; mc / gpow / vmask from tsm_nstep_return; weight f32 [B] (nullable: 1).
+ *   returns[b][k] = (float)((double)(support[k] * vmask) * gpow + mc);  Tz = clamp(returns, v_min, v_max);
+ *   m[j] = sum_k clamp(1 - |Tz[k] - support[j]| / dz, 0, 1) softmax(raw_next[b][a*])[k], dz = (v_max - v_min) / (n_atoms - 1);
+ *   ce = -sum_j m[j] log(softmax(raw[b][act])[j] + 1e-8);  loss = mean(ce * weight).
+ *   out: returns f32 [B][n_atoms]; prio f32 [B] = ce (`batch.weight` for a prioritized buffer); d_out f32 [B][n_act * n_atoms]
+ *        = d loss / d raw through the 1e-8 and the softmax, zero off the taken action; partial f64
+ *        [2 * ceil(B / TSM_DISTQ_ROWS_PER_BLOCK)] = per workgroup {sum ce * weight, sum E[z | act]} for tsm_qmix_finalize.
+ * tsm_qrdqn_head replaces  QRDQN._target_q after its forwards (qrdqn.py:94-106), the same last line of the n-step return, and
+ *           QRDQN._update_with_batch between `self.policy(batch).logits` and `optim.step(loss)` (qrdqn.py:113-129).  One launch.
+ *   Arguments as above with raw values in place of logits; tau_hat f32 [n_quantiles]: the midpoints of
+ *   torch.linspace(0, 1, n_quantiles + 1) (qrdqn.py:87-90), filled by the host.
+ *   returns[b][j] = (float)((double)(raw_next[b][a*][j] * vmask) * gpow + mc);  u_ij = returns[j] - raw[b][act][i];
+ *   loss_b = mean_i sum_j smooth_l1(u_ij) |tau_hat[i] - 1[u_ij <= 0]|;  loss = mean(loss_b * weight);
+ *   prio[b] = mean_i sum_j |smooth_l1(u_ij)|;  the second partial is the mean quantile of the taken action.
+ * Both heads: an action outside [0, n_act) reads nothing; the row's prio and loss term are NaN and its gradient zero.
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_DISTQ_ROWS_PER_BLOCK 16
+int tsm_distq_check(int32_t n_act, int32_t n_atoms);
+int tsm_distq_values(const float *raw, const float *support, int64_t R, int32_t n_act, int32_t n_atoms, int categorical,
+                     float *q, float *probs, void *stream);
+int tsm_c51_head(const float *raw, const float *q_next, const float *raw_next, const uint8_t *mask_next, const int64_t *act,
+                 const float *mc, const float *gpow, const uint8_t *vmask, const float *weight, const float *support,
+                 int64_t B, int32_t n_act, int32_t n_atoms, double v_min, double v_max, float *returns_out, float *prio,
+                 float *d_out, double *partial, void *stream);
+int tsm_qrdqn_head(const float *raw, const float *q_next, const float *raw_next, const uint8_t *mask_next, const int64_t *act,
+                   const float *mc, const float *gpow, const uint8_t *vmask, const float *weight, const float *tau_hat,
+                   int64_t B, int32_t n_act, int32_t n_quantiles, float *returns_out, float *prio, float *d_out,
+                   double *partial, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

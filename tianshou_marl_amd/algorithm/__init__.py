@@ -1,7 +1,9 @@
 """Algorithms on the device-resident rollout (mirror of tianshou.algorithm for the north-star path)."""
+from .distq import C51, QRDQN, C51Policy, QRDQNPolicy
 from .dqn import DQN, DiscreteQLearningPolicy
 from .pg import A2C, Reinforce
 from .ppo import PPO, policy_within_training_step
 from .ppo_generic import GenericPPO
 
-__all__ = ["PPO", "A2C", "Reinforce", "GenericPPO", "DQN", "DiscreteQLearningPolicy", "policy_within_training_step"]
+__all__ = ["PPO", "A2C", "Reinforce", "GenericPPO", "DQN", "DiscreteQLearningPolicy", "C51", "C51Policy", "QRDQN",
+           "QRDQNPolicy", "policy_within_training_step"]

@@ -53,19 +53,20 @@ class DiscreteQLearningPolicy(nn.Module):
     """dqn.py:39-174 with a `FlatMLP` Q-network (obs -> ... -> n actions)."""
 
     def __init__(self, *, model: FlatMLP, action_space: Any, observation_space: Any = None, eps_training: float = 0.0,
-                 eps_inference: float = 0.0, seed: int = 0) -> None:
+                 eps_inference: float = 0.0, seed: int = 0, atoms: int = 1) -> None:
+        """`atoms`: outputs per action -- 1 here; the distributional policies (algorithm/distq.py) pass their N."""
         super().__init__()
         if not isinstance(model, FlatMLP):
             raise TypeError("DiscreteQLearningPolicy needs a FlatMLP Q-network: the update runs in HIP, there is no "
                             f"autograd fallback (got {type(model).__name__})")
         n = getattr(action_space, "n", None)
-        if n is None or int(n) != model.dims[-1]:
+        if n is None or int(n) * int(atoms) != model.dims[-1]:
             raise ValueError(f"DiscreteQLearningPolicy: the model has {model.dims[-1]} outputs, the action space "
-                             f"{'no size' if n is None else f'{int(n)} actions'}")
-        ops.dqn_check(model.dims[-1])
+                             f"{'no size' if n is None else f'{int(n)} actions'}" + (f" of {atoms} atoms each" if atoms != 1 else ""))
+        ops.dqn_check(int(n))
         self.model = model
         self.action_space, self.observation_space = action_space, observation_space
-        self.n_act = model.dims[-1]
+        self.n_act = int(n)
         self.seed = int(seed)
         self._sample_ctr = 0
         dev = model.flat.device
@@ -223,50 +224,62 @@ class DQN(nn.Module):
         self._iter += 1
 
     # ---- compute_nstep_return (algorithm_base.py:720-815) with DQN._target_q's forwards (dqn.py:365-375) ----------
-    def _preprocess_batch(self, batch: Batch, buffer, indices, agent: int | None = None) -> Batch:
-        """The n-step walk for `indices` (one launch), then the networks on obs_next[idx_n] (and mask[idx_n] if the buffer
-        keeps masks), gathered with tsm_vrb_gather.  `agent`: the agent's column -- its lane of a joint-step buffer, its
-        reward column of an AEC buffer (the walk still visits all rows, quirk Q18).  The batch leaves with what the TD
-        head needs; `returns` is set by `_update_with_batch`, where the head runs."""
+    def _nstep_rows(self, batch: Batch, buffer, indices, agent: int | None):
+        """The n-step walk for `indices` (one launch): the batch leaves with idx_n, mc, gpow, vmask and -- when it came empty,
+        as from `update` -- with obs and act gathered from the device stores.  `agent`: the agent's column -- its lane of a
+        joint-step buffer, its reward column of an AEC buffer (the walk still visits all rows, quirk Q18).
+        -> (idx, idx_n, col): the flat indices, their n-step successors, the lane the rows are read from."""
         dev = self.device
         idx = to_tensor(indices, dev, torch.int64).reshape(-1)
         if len(batch.get_keys()) != 0 and len(batch) != idx.numel():
             raise ValueError(f"Batch size {len(batch)} and indices size {idx.numel()} mismatch.")
         aec = bool(getattr(buffer, "aec", False))
         n_col = buffer.rew_store.shape[2]
+        name = type(self).__name__
         if agent is None:
             if n_col != 1:
-                raise ValueError(f"DQN: the buffer holds {n_col} reward columns; say which agent's (agent=k)")
+                raise ValueError(f"{name}: the buffer holds {n_col} reward columns; say which agent's (agent=k)")
             agent = 0
         if not 0 <= int(agent) < n_col:
-            raise ValueError(f"DQN: agent column {agent} outside the buffer's {n_col}")
+            raise ValueError(f"{name}: agent column {agent} outside the buffer's {n_col}")
         k = int(agent)
         col = 0 if aec else k  # AEC rows: one observation / flag per row; joint rows: the agent's lane
         idx_n, mc, gpow, vmask = ops.nstep_return(buffer.index, buffer.term_store, buffer.rew_store, idx, self.n_step,
                                                   self.gamma, rew_col=k, term_col=col)
-        if buffer._save_obs_next:
-            nxt = buffer._gather(buffer.obs_next_store, idx_n)
-        else:  # ignore_obs_next: obs at next(index) (buffer_base.py:612-616)
-            nxt = buffer._gather(buffer.obs_store, buffer.index.next(idx_n))
-        nxt = nxt[:, col].contiguous()
-        mask_store = getattr(buffer, "mask_store", None)
-        mask_next = None if mask_store is None else buffer._gather(mask_store, idx_n)
-        model = self.policy.model
-        batch.q_next_online = FlatMLP.forward(model, nxt, save=False)
-        if self.use_target_network:
-            batch.q_next_target = FlatMLP.forward(self.model_old, nxt, save=False)
-        if mask_next is not None:
-            batch.mask_next = mask_next
         batch.idx_n, batch.mc, batch.gpow, batch.vmask = idx_n, mc, gpow, vmask
         if "obs" not in batch:  # rows straight from the device stores (DQN.update)
             batch.obs = buffer._gather(buffer.obs_store, idx)[:, col].contiguous()
             batch.act = buffer._gather(buffer.act_store, idx)[:, col].contiguous().to(torch.int64)
+        return idx, idx_n, col
+
+    @staticmethod
+    def _successor_rows(buffer, rows, col: int):
+        """obs_next[rows] (with ignore_obs_next: obs at next(rows), buffer_base.py:612-616) and the mask the buffer keeps for
+        those rows (quirk Q19), gathered with tsm_vrb_gather.  -> (obs_next [I, D], mask or None)."""
+        if buffer._save_obs_next:
+            nxt = buffer._gather(buffer.obs_next_store, rows)
+        else:
+            nxt = buffer._gather(buffer.obs_store, buffer.index.next(rows))
+        mask_store = getattr(buffer, "mask_store", None)
+        return nxt[:, col].contiguous(), (None if mask_store is None else buffer._gather(mask_store, rows))
+
+    def _preprocess_batch(self, batch: Batch, buffer, indices, agent: int | None = None) -> Batch:
+        """The n-step walk, then the networks on obs_next[idx_n] (and mask[idx_n] if the buffer keeps masks).  The batch
+        leaves with what the TD head needs; `returns` is set by `_update_with_batch`, where the head runs."""
+        _, idx_n, col = self._nstep_rows(batch, buffer, indices, agent)
+        nxt, mask_next = self._successor_rows(buffer, idx_n, col)
+        batch.q_next_online = FlatMLP.forward(self.policy.model, nxt, save=False)
+        if self.use_target_network:
+            batch.q_next_target = FlatMLP.forward(self.model_old, nxt, save=False)
+        if mask_next is not None:
+            batch.mask_next = mask_next
         return batch
 
     # ---- DQN._update_with_batch (dqn.py:381-404) --------------------------------------------------------------
     def _update_with_batch(self, batch: Batch) -> SimpleLossTrainingStats:
         """The online forward (saved), the TD head, the backward into slabs, one Adam step, the loss into a pinned slot."""
         self._periodically_update_lagged_network_weights()
+        self._after_lagged_copy(batch)
         dev = self.device
         weight = batch.pop("weight", None) if "weight" in batch else None
         if weight is not None and not isinstance(weight, (torch.Tensor, np.ndarray)):
@@ -282,19 +295,31 @@ class DQN(nn.Module):
             w = self._ws[B] = dict(n_split=n_split,
                                    slabs=torch.empty(n_split, model.flat.numel(), dtype=torch.float32, device=dev))
         q = FlatMLP.forward(model, x, save=True)
-        head = ops.dqn_td_head(q, batch.q_next_online, batch.get("q_next_target"), act, batch.mc, batch.gpow, batch.vmask,
-                               mask_next=batch.get("mask_next"),
-                               weight=None if weight is None else to_tensor(weight, dev, torch.float32).reshape(-1),
-                               is_double=self.is_double, huber_delta=self.huber_loss_delta)
-        model.backward(head["dq"], w["n_split"], slabs=w["slabs"])
+        d_out, partial, returns, prio = self._head(batch, q, act, None if weight is None else
+                                                   to_tensor(weight, dev, torch.float32).reshape(-1))
+        model.backward(d_out, w["n_split"], slabs=w["slabs"])
         self.optim.step(w["slabs"])
         slot = ResultRing.of(w, lambda: pinned_slot(2)).take("resolve", wait=False)
-        ops.qmix_finalize(head["partial"], B, slot["h"])
+        ops.qmix_finalize(partial, B, slot["h"])
         slot["event"].record()
-        batch.returns = head["returns"]
-        batch.weight = head["td_error"]  # prio-buffer
+        batch.returns = returns
+        batch.weight = prio  # prio-buffer
         slot["event"].synchronize()
-        return SimpleLossTrainingStats(loss=float(slot["h"][0]))
+        return self._stats(float(slot["h"][0]))
+
+    def _after_lagged_copy(self, batch: Batch) -> None:
+        """What a learner computes between the lagged copy and its loss (C51's successor forwards); nothing here."""
+
+    def _head(self, batch: Batch, q, act, weight):
+        """-> (d loss / d network output, f64 partials for tsm_qmix_finalize, returns, the new priorities)."""
+        head = ops.dqn_td_head(q, batch.q_next_online, batch.get("q_next_target"), act, batch.mc, batch.gpow, batch.vmask,
+                               mask_next=batch.get("mask_next"), weight=weight, is_double=self.is_double,
+                               huber_delta=self.huber_loss_delta)
+        return head["dq"], head["partial"], head["returns"], head["td_error"]
+
+    @staticmethod
+    def _stats(loss: float) -> TrainingStats:
+        return SimpleLossTrainingStats(loss=loss)
 
     @staticmethod
     def _sampled_batch(buffer, indices) -> Batch:

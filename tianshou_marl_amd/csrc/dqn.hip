@@ -21,6 +21,7 @@
 // tsm_qmix_finalize turns them into {loss, mean q} in a pinned slot.
 #include "common.h"
 #include "philox.h"
+#include "qargmax.h"
 
 namespace {
 constexpr int kDThreads = 256;
@@ -37,38 +38,8 @@ __global__ __launch_bounds__(kDThreads) void dqn_td_head_kernel(
     const int t = threadIdx.x, lane = t & (kWave - 1), w = t / kWave;
     const bool masked = is_double && mask_next != nullptr;
 
-    float mv = 0.f;
-    if (masked) {  // logits.min() - logits.max() - 1 over the whole tensor
-        // fminf / fmaxf skip a NaN where torch's min() / max() return it: a flag carries a NaN logit through the reduction and
-        // makes the offset NaN, as in the reference
-        float lo = INFINITY, hi = -INFINITY;
-        int bad = 0;
-        const int64_t n = B * A;
-        for (int64_t j = t; j < n; j += kDThreads) {
-            const float v = qn_on[j];
-            bad |= (v != v);
-            lo = fminf(lo, v);
-            hi = fmaxf(hi, v);
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            lo = fminf(lo, __shfl_xor(lo, off, kWave));
-            hi = fmaxf(hi, __shfl_xor(hi, off, kWave));
-            bad |= __shfl_xor(bad, off, kWave);
-        }
-        if (lane == 0) { s_min[w] = bad ? __builtin_nanf("") : lo; s_max[w] = hi; }
-        __syncthreads();
-        lo = s_min[0];
-        hi = s_max[0];
-        bad = lo != lo;
-#pragma unroll
-        for (int k = 1; k < kDThreads / kWave; ++k) {
-            bad |= s_min[k] != s_min[k];
-            lo = fminf(lo, s_min[k]);
-            hi = fmaxf(hi, s_max[k]);
-        }
-        mv = bad ? __builtin_nanf("") : (lo - hi) - 1.0f;
-    }
+    // logits.min() - logits.max() - 1 over the whole tensor (qargmax.h)
+    const float mv = masked ? tsm_q_mask_offset<kDThreads>(qn_on, B * A, s_min, s_max) : 0.f;
 
     const int64_t b = (int64_t)blockIdx.x * kDThreads + t;
     double p_l = 0.0, p_q = 0.0;
@@ -78,14 +49,7 @@ __global__ __launch_bounds__(kDThreads) void dqn_td_head_kernel(
         if (is_double) {
             const float *row = qn_on + b * A;
             const uint8_t *mrow = masked ? mask_next + b * A : nullptr;
-            int a_star = 0;
-            float best = 0.f;
-            for (int a = 0; a < A; ++a) {
-                float v = row[a];
-                if (mrow) v = v + (mrow[a] ? 0.f : 1.f) * mv;   // logits + (1 - mask) * min_value, in f32 as torch
-                // first maximum, as torch.argmax -- which takes the first NaN for the maximum when there is one
-                if (a == 0 || v > best || (v != v && best == best)) { best = v; a_star = a; }
-            }
+            const int a_star = tsm_q_first_argmax(row, mrow, A, mv);
             target = qt[a_star];
         } else {
             target = qt[0];

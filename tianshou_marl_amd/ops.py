@@ -1122,6 +1122,89 @@ def dqn_egreedy(q, eps_dev, seed: int, offset: int = 0, offset_dev=None, mask=No
 
 
 # --------------------------------------------------------------------------------------------
+# Distributional Q-learning: C51 and QR-DQN (c51.py; qrdqn.py; csrc/distq.hip)
+# --------------------------------------------------------------------------------------------
+def distq_check(n_act: int, n_atoms: int) -> None:
+    """The bounds of the distributional kernels (include/tsmarl.h): ValueError naming the limit."""
+    call("tsm_distq_check", int(n_act), int(n_atoms))
+
+
+def distq_values(raw, n_act: int, n_atoms: int, support=None, want_probs: bool = False):
+    """C51Policy.compute_q_value's expectation (support f32 [N] given: softmax over atoms, then the sum with the support;
+    c51.py:67) or QRDQNPolicy.compute_q_value's mean over quantiles (support None; qrdqn.py:20), before the action mask.
+    raw [R, A * N] -> q [R, A], or (q, probs [R, A, N]) with want_probs (categorical only)."""
+    _dev_only("distq_values", raw, support)
+    raw = _chk(raw, torch.float32, "raw")
+    A, N = int(n_act), int(n_atoms)
+    distq_check(A, N)
+    if raw.dim() != 2 or raw.shape[1] != A * N:
+        raise ValueError(f"distq_values: raw must be [R, {A} * {N}]")
+    if support is not None and support.numel() != N:
+        raise ValueError(f"distq_values: support must have {N} entries")
+    if want_probs and support is None:
+        raise ValueError("distq_values: probabilities belong to the categorical mode (give the support)")
+    R, dev = raw.shape[0], raw.device
+    q = torch.empty(R, A, dtype=torch.float32, device=dev)
+    probs = torch.empty(R, A, N, dtype=torch.float32, device=dev) if want_probs else None
+    call("tsm_distq_values", ptr(raw), ptr(None if support is None else _chk(support, torch.float32, "support")), R, A, N,
+         int(support is not None), ptr(q), ptr(probs), stream_ptr())
+    return (q, probs) if want_probs else q
+
+
+def _distq_head(name: str, entry: str, raw, q_next, raw_next, act, mc, gpow, vmask, aux, aux_name: str, mask_next, weight,
+                extra: tuple):
+    _dev_only(name, raw, q_next, raw_next, act, mc, gpow, vmask, aux, mask_next, weight)
+    raw = _chk(raw, torch.float32, "raw")
+    if q_next.dim() != 2 or raw.dim() != 2:
+        raise ValueError(f"{name}: raw must be [B, A * N] and q_next [B, A]")
+    B, A = q_next.shape
+    N = aux.numel()
+    distq_check(A, N)
+    if B < 1:
+        raise ValueError(f"{name}: empty batch")
+    for nm, x, shape in (("raw", raw, (B, A * N)), ("raw_next", raw_next, (B, A * N)), ("mask_next", mask_next, (B, A))):
+        if x is not None and tuple(x.shape) != shape:
+            raise ValueError(f"{name}: {nm} must be [{shape[0]}, {shape[1]}] ({aux_name} has {N} entries)")
+    for nm, x in (("act", act), ("mc", mc), ("gpow", gpow), ("vmask", vmask), ("weight", weight)):
+        if x is not None and x.numel() != B:
+            raise ValueError(f"{name}: {nm} must have {B} entries")
+    u8 = lambda x, n: x.contiguous().view(torch.uint8) if x.dtype == torch.bool else _chk(x, torch.uint8, n)  # noqa: E731
+    dev = raw.device
+    n_blocks = -(-B // _abi.DISTQ_ROWS_PER_BLOCK)
+    out = dict(returns=torch.empty(B, N, dtype=torch.float32, device=dev), prio=torch.empty(B, dtype=torch.float32, device=dev),
+               d_out=torch.empty(B, A * N, dtype=torch.float32, device=dev),
+               partial=torch.empty(2 * n_blocks, dtype=torch.float64, device=dev))
+    call(entry, ptr(raw), ptr(_chk(q_next, torch.float32, "q_next")), ptr(_chk(raw_next, torch.float32, "raw_next")),
+         ptr(None if mask_next is None else u8(mask_next, "mask_next")), ptr(_chk(act, torch.int64, "act").reshape(-1)),
+         ptr(_chk(mc, torch.float32, "mc").reshape(-1)), ptr(_chk(gpow, torch.float32, "gpow").reshape(-1)),
+         ptr(u8(vmask, "vmask").reshape(-1)), ptr(None if weight is None else _chk(weight, torch.float32, "weight").reshape(-1)),
+         ptr(_chk(aux, torch.float32, aux_name).reshape(-1)), B, A, N, *extra, ptr(out["returns"]), ptr(out["prio"]),
+         ptr(out["d_out"]), ptr(out["partial"]), stream_ptr())
+    return out
+
+
+def c51_head(raw, q_next, raw_next, act, mc, gpow, vmask, support, v_min: float, v_max: float, mask_next=None, weight=None):
+    """C51._target_dist after its forwards + the cross entropy of C51._update_with_batch and its gradient with respect to
+    the raw outputs (c51.py:123-158) in one launch.  raw [B, A * N]: the online net on obs; q_next [B, A]: `distq_values` of
+    the online net on the successor rows; raw_next [B, A * N]: the lagged net there (the online net's output when there is
+    none); act i64 [B]; mc, gpow, vmask from nstep_return; support f32 [N]; mask_next u8 / bool [B, A] or None; weight
+    f32 [B] or None.  -> dict(returns [B, N], prio [B], d_out [B, A * N], partial f64): `qmix_finalize(partial, B, out)`
+    gives {loss, mean expected value of the taken action}."""
+    if not float(v_min) < float(v_max):
+        raise ValueError(f"c51_head: v_max should be larger than v_min, but got v_min={v_min} and v_max={v_max}")
+    return _distq_head("c51_head", "tsm_c51_head", raw, q_next, raw_next, act, mc, gpow, vmask, support, "support", mask_next,
+                       weight, (float(v_min), float(v_max)))
+
+
+def qrdqn_head(raw, q_next, raw_next, act, mc, gpow, vmask, tau_hat, mask_next=None, weight=None):
+    """QRDQN._target_q after its forwards + the quantile Huber loss of QRDQN._update_with_batch and its gradient
+    (qrdqn.py:94-129) in one launch.  Arguments as `c51_head`, with q_next the mean over quantiles and tau_hat f32 [N] the
+    quantile midpoints.  -> dict(returns [B, N], prio [B], d_out [B, A * N], partial f64)."""
+    return _distq_head("qrdqn_head", "tsm_qrdqn_head", raw, q_next, raw_next, act, mc, gpow, vmask, tau_hat, "tau_hat",
+                       mask_next, weight, ())
+
+
+# --------------------------------------------------------------------------------------------
 # Prioritized replay (data/utils/segtree.py, data/buffer/prio.py; csrc/segtree.hip)
 # --------------------------------------------------------------------------------------------
 def segtree_bound(size: int) -> int:
