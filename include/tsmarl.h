@@ -1064,6 +1064,60 @@ int tsm_qrdqn_head(const float *raw, const float *q_next, const float *raw_next,
                    int64_t B, int32_t n_act, int32_t n_quantiles, float *returns_out, float *prio, float *d_out,
                    double *partial, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Discrete SAC  (tianshou/algorithm/modelfree/discrete_sac.py, sac.py `Alpha` / `AutoAlpha`; csrc/dsac.hip)
+ * The actor emits logits f32 [B][n_act], each critic Q values f32 [B][n_act]; Categorical(logits) is part of these kernels:
+ * ln = logits - logsumexp, p = softmax, H = -sum p ln (Categorical.entropy; its clamp of ln at finfo.min acts only at p = 0,
+ * which finite logits never give), formed in float64 from the float32 logits and rounded where they leave.  alpha_dev f32 [1]
+ * in HBM: the entropy coefficient, read on the device.
+ * tsm_dsac_check: the bounds of the kernels (n_act in [1, 64] as for tsm_dqn_check, n_step >= 1): TSM_ERR_INVALID naming
+ *   the limit.
+ * tsm_dsac_target replaces  DiscreteSAC._target_q_compute_value (discrete_sac.py:147-155) after its forwards and
+ *           `_nstep_return`'s last line (algorithm_base.py:796, 1213-1215).  One launch, one wave per row.
+ *   logits_next: the ONLINE actor on obs_next[idx_n]; q1_next_old / q2_next_old: the two lagged critics on the same rows;
+ *   mc / gpow / vmask from tsm_nstep_return.
+ *   target_q = sum_a p[a] min(q1, q2)[a] + alpha H(p);  returns[b] = (float)((double)(target_q * vmask) * gpow + mc), the
+ *   rounding rule of tsm_dqn_td_head.  out: returns f32 [B].
+ * tsm_dsac_critic_head replaces  both critic losses of DiscreteSAC._update_with_batch (discrete_sac.py:162-174) between the
+ *           critics' forwards and `critic_optim.step` / `critic2_optim.step`.  One launch.
+ *   q1 / q2 [B][n_act]: the critics on obs; act i64 [B]; returns f32 [B]; weight f32 [B] (nullable: 1).
+ *   td_i = q_i[b][act[b]] - returns[b]  (the reference's sign: the opposite of tsm_dqn_td_head's td_error).
+ *   out: dq1 / dq2 f32 [B][n_act] = d mean(td_i^2 weight) / d q_i = 2 td_i weight / B at act, exactly zero elsewhere;
+ *        prio f32 [B] = (td_1 + td_2) / 2 (`batch.weight` for a prioritized buffer, which takes the absolute value);
+ *        partial f64 [2 * ceil(B / TSM_DSAC_ROWS_PER_BLOCK)] = per workgroup {sum td_1^2 weight, sum td_2^2 weight} in the
+ *        layout of tsm_qmix_mix_td's partials: tsm_qmix_finalize gives out[2] = {critic1_loss, critic2_loss}.
+ *   An action outside [0, n_act) reads nothing; the row's prio and loss terms are NaN and its gradient zero.
+ * tsm_dsac_actor_head replaces  the actor loss of DiscreteSAC._update_with_batch and its backward down to the logits
+ *           (discrete_sac.py:177-184), and the entropy that AutoAlpha.update reads (sac.py:203-205).  One launch.
+ *   logits [B][n_act]: the actor on obs; q1 / q2 [B][n_act]: the critics on obs AFTER their own steps (constants here).
+ *   loss_b = -(alpha H_b + sum_a p[a] min(q1, q2)[a]).
+ *   out: entropy f32 [B]; d_logits f32 [B][n_act] = d mean_b(loss_b) / d logits
+ *        = p[j] (alpha (ln[j] + H) - (q[j] - sum_a p[a] q[a])) / B;
+ *        partial f64 (same size) = per workgroup {sum loss_b, sum H_b}: tsm_qmix_finalize gives {actor_loss, mean entropy}.
+ * tsm_dsac_alpha_step replaces  AutoAlpha.update (sac.py:203-209) and the refresh of `alpha.value`: one launch of one wave
+ *           on device scalars, no host read.
+ *   entropy_partial f64 [2 * n_blocks]: tsm_dsac_actor_head's partials, of which the second of every pair is read; the mean
+ *   entropy = their sum / B is formed in float64 in a fixed order and is not rounded to float32 before it is
+ *   taken from target_entropy (near the target that difference is small against the entropy: one float32 ulp of the mean
+ *   is several 1e-6 of it).  log_alpha, exp_avg, exp_avg_sq f32 [1], step i64 [1] (the count of steps taken so far;
+ *   incremented here), all in HBM.
+ *   alpha_loss = -(log_alpha * (target_entropy - mean entropy));  grad = -(target_entropy - mean entropy);  one torch Adam
+ *   step (amsgrad off, 1 - beta formed in float64 as tsm_adam_step_coef64);  alpha_dev[0] = exp(log_alpha).
+ *   out f32 [2] (HBM or mapped pinned memory) = {alpha_loss, the new alpha}.
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_DSAC_ROWS_PER_BLOCK 16
+int tsm_dsac_check(int32_t n_act, int32_t n_step);
+int tsm_dsac_target(const float *logits_next, const float *q1_next_old, const float *q2_next_old, const float *alpha_dev,
+                    const float *mc, const float *gpow, const uint8_t *vmask, int64_t B, int32_t n_act, float *returns_out,
+                    void *stream);
+int tsm_dsac_critic_head(const float *q1, const float *q2, const int64_t *act, const float *returns, const float *weight,
+                         int64_t B, int32_t n_act, float *dq1, float *dq2, float *prio, double *partial, void *stream);
+int tsm_dsac_actor_head(const float *logits, const float *q1, const float *q2, const float *alpha_dev, int64_t B,
+                        int32_t n_act, float *entropy, float *d_logits, double *partial, void *stream);
+int tsm_dsac_alpha_step(const double *entropy_partial, int32_t n_blocks, int64_t B, float *log_alpha, float *exp_avg,
+                        float *exp_avg_sq, int64_t *step, double target_entropy, double lr, double beta1, double beta2,
+                        double eps, double weight_decay, float *alpha_dev, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,7 +159,89 @@ class DiscreteQLearningPolicy(nn.Module):
         return dict(act=act, logp=z, value=z.clone(), q=q)
 
 
-class DQN(nn.Module):
+class DeviceOffPolicyRows:
+    """What every off-policy learner on the device buffers shares (algorithm_base.py:720-815, 866-905): the n-step walk, the
+    successor rows, the sampled batch of a prioritized buffer, the priority write-back and `update`.  A learner supplies
+    `device`, `gamma`, `n_step`, `lr_scheduler`, `is_within_training_step`, `_preprocess_batch` and `_update_with_batch`."""
+
+    # ---- compute_nstep_return (algorithm_base.py:720-815) ---------------------------------------------------------
+    def _nstep_rows(self, batch: Batch, buffer, indices, agent: int | None):
+        """The n-step walk for `indices` (one launch): the batch leaves with idx_n, mc, gpow, vmask and -- when it came empty,
+        as from `update` -- with obs and act gathered from the device stores.  `agent`: the agent's column -- its lane of a
+        joint-step buffer, its reward column of an AEC buffer (the walk still visits all rows, quirk Q18).
+        -> (idx, idx_n, col): the flat indices, their n-step successors, the lane the rows are read from."""
+        dev = self.device
+        idx = to_tensor(indices, dev, torch.int64).reshape(-1)
+        if len(batch.get_keys()) != 0 and len(batch) != idx.numel():
+            raise ValueError(f"Batch size {len(batch)} and indices size {idx.numel()} mismatch.")
+        aec = bool(getattr(buffer, "aec", False))
+        n_col = buffer.rew_store.shape[2]
+        name = type(self).__name__
+        if agent is None:
+            if n_col != 1:
+                raise ValueError(f"{name}: the buffer holds {n_col} reward columns; say which agent's (agent=k)")
+            agent = 0
+        if not 0 <= int(agent) < n_col:
+            raise ValueError(f"{name}: agent column {agent} outside the buffer's {n_col}")
+        k = int(agent)
+        col = 0 if aec else k  # AEC rows: one observation / flag per row; joint rows: the agent's lane
+        idx_n, mc, gpow, vmask = ops.nstep_return(buffer.index, buffer.term_store, buffer.rew_store, idx, self.n_step,
+                                                  self.gamma, rew_col=k, term_col=col)
+        batch.idx_n, batch.mc, batch.gpow, batch.vmask = idx_n, mc, gpow, vmask
+        if "obs" not in batch:  # rows straight from the device stores (DQN.update)
+            batch.obs = buffer._gather(buffer.obs_store, idx)[:, col].contiguous()
+            batch.act = buffer._gather(buffer.act_store, idx)[:, col].contiguous().to(torch.int64)
+        return idx, idx_n, col
+
+    @staticmethod
+    def _successor_rows(buffer, rows, col: int):
+        """obs_next[rows] (with ignore_obs_next: obs at next(rows), buffer_base.py:612-616) and the mask the buffer keeps for
+        those rows (quirk Q19), gathered with tsm_vrb_gather.  -> (obs_next [I, D], mask or None)."""
+        if buffer._save_obs_next:
+            nxt = buffer._gather(buffer.obs_next_store, rows)
+        else:
+            nxt = buffer._gather(buffer.obs_store, buffer.index.next(rows))
+        mask_store = getattr(buffer, "mask_store", None)
+        return nxt[:, col].contiguous(), (None if mask_store is None else buffer._gather(mask_store, rows))
+
+    @staticmethod
+    def _sampled_batch(buffer, indices) -> Batch:
+        """What `update` keeps of `buffer[indices]`: the rows stay in the device stores (`_preprocess_batch` gathers them); a
+        prioritized buffer adds `weight`, its importance-sampling weights (prio.py:103-106) as float32 in HBM -- the TD head's
+        `weight` (quirk Q17: the Huber loss ignores it)."""
+        batch = Batch()
+        if hasattr(buffer, "update_weight"):
+            batch.weight = buffer.batch_weight_device(indices)[0]
+        return batch
+
+    def _postprocess_batch(self, batch: Batch, buffer, indices) -> None:
+        """Algorithm._postprocess_batch (algorithm_base.py:560-582): a prioritized buffer takes `batch.weight` -- after
+        `_update_with_batch` the TD errors, still in HBM -- as the new priorities of `indices`."""
+        if hasattr(buffer, "update_weight"):
+            if "weight" in batch:
+                buffer.update_weight(indices, batch.weight)
+            else:
+                log.warning("batch has no attribute 'weight', but buffer has an update_weight method. This is probably a "
+                            "mistake. Prioritized replay is disabled for this batch.")
+
+    def update(self, buffer, sample_size: int | None, agent: int | None = None) -> SimpleLossTrainingStats:
+        """OffPolicyAlgorithm.update (algorithm_base.py:889-905): sample, preprocess, update, postprocess.  The sampled rows
+        are read from the device stores in place (`buffer.sample` would carry them through the host); with a prioritized
+        buffer the indices, the IS weights and the new priorities stay in HBM too, so the loss slot is the only host read."""
+        if not self.is_within_training_step:
+            raise RuntimeError("update() was called outside of a training step as signalled by "
+                               "`is_within_training_step=False`")
+        prioritized = hasattr(buffer, "update_weight")
+        indices = buffer.sample_indices_device(sample_size) if prioritized else buffer.sample_indices(sample_size)
+        batch = self._preprocess_batch(self._sampled_batch(buffer, indices), buffer, indices, agent=agent)
+        stats = self._update_with_batch(batch)
+        self._postprocess_batch(batch, buffer, indices)
+        if self.lr_scheduler is not None:
+            self.lr_scheduler.step()
+        return stats
+
+
+class DQN(DeviceOffPolicyRows, nn.Module):
     """dqn.py:180-404 on the device buffer.  `optim`: an `AdamOptimizerFactory` (its hyper-parameters drive the HIP Adam
     over the model's flat vector) or a `FlatAdam` over that vector."""
 
@@ -223,46 +305,6 @@ class DQN(nn.Module):
             self.target_flat.copy_(self.policy.model.flat.data)
         self._iter += 1
 
-    # ---- compute_nstep_return (algorithm_base.py:720-815) with DQN._target_q's forwards (dqn.py:365-375) ----------
-    def _nstep_rows(self, batch: Batch, buffer, indices, agent: int | None):
-        """The n-step walk for `indices` (one launch): the batch leaves with idx_n, mc, gpow, vmask and -- when it came empty,
-        as from `update` -- with obs and act gathered from the device stores.  `agent`: the agent's column -- its lane of a
-        joint-step buffer, its reward column of an AEC buffer (the walk still visits all rows, quirk Q18).
-        -> (idx, idx_n, col): the flat indices, their n-step successors, the lane the rows are read from."""
-        dev = self.device
-        idx = to_tensor(indices, dev, torch.int64).reshape(-1)
-        if len(batch.get_keys()) != 0 and len(batch) != idx.numel():
-            raise ValueError(f"Batch size {len(batch)} and indices size {idx.numel()} mismatch.")
-        aec = bool(getattr(buffer, "aec", False))
-        n_col = buffer.rew_store.shape[2]
-        name = type(self).__name__
-        if agent is None:
-            if n_col != 1:
-                raise ValueError(f"{name}: the buffer holds {n_col} reward columns; say which agent's (agent=k)")
-            agent = 0
-        if not 0 <= int(agent) < n_col:
-            raise ValueError(f"{name}: agent column {agent} outside the buffer's {n_col}")
-        k = int(agent)
-        col = 0 if aec else k  # AEC rows: one observation / flag per row; joint rows: the agent's lane
-        idx_n, mc, gpow, vmask = ops.nstep_return(buffer.index, buffer.term_store, buffer.rew_store, idx, self.n_step,
-                                                  self.gamma, rew_col=k, term_col=col)
-        batch.idx_n, batch.mc, batch.gpow, batch.vmask = idx_n, mc, gpow, vmask
-        if "obs" not in batch:  # rows straight from the device stores (DQN.update)
-            batch.obs = buffer._gather(buffer.obs_store, idx)[:, col].contiguous()
-            batch.act = buffer._gather(buffer.act_store, idx)[:, col].contiguous().to(torch.int64)
-        return idx, idx_n, col
-
-    @staticmethod
-    def _successor_rows(buffer, rows, col: int):
-        """obs_next[rows] (with ignore_obs_next: obs at next(rows), buffer_base.py:612-616) and the mask the buffer keeps for
-        those rows (quirk Q19), gathered with tsm_vrb_gather.  -> (obs_next [I, D], mask or None)."""
-        if buffer._save_obs_next:
-            nxt = buffer._gather(buffer.obs_next_store, rows)
-        else:
-            nxt = buffer._gather(buffer.obs_store, buffer.index.next(rows))
-        mask_store = getattr(buffer, "mask_store", None)
-        return nxt[:, col].contiguous(), (None if mask_store is None else buffer._gather(mask_store, rows))
-
     def _preprocess_batch(self, batch: Batch, buffer, indices, agent: int | None = None) -> Batch:
         """The n-step walk, then the networks on obs_next[idx_n] (and mask[idx_n] if the buffer keeps masks).  The batch
         leaves with what the TD head needs; `returns` is set by `_update_with_batch`, where the head runs."""
@@ -320,42 +362,6 @@ class DQN(nn.Module):
     @staticmethod
     def _stats(loss: float) -> TrainingStats:
         return SimpleLossTrainingStats(loss=loss)
-
-    @staticmethod
-    def _sampled_batch(buffer, indices) -> Batch:
-        """What `update` keeps of `buffer[indices]`: the rows stay in the device stores (`_preprocess_batch` gathers them); a
-        prioritized buffer adds `weight`, its importance-sampling weights (prio.py:103-106) as float32 in HBM -- the TD head's
-        `weight` (quirk Q17: the Huber loss ignores it)."""
-        batch = Batch()
-        if hasattr(buffer, "update_weight"):
-            batch.weight = buffer.batch_weight_device(indices)[0]
-        return batch
-
-    def _postprocess_batch(self, batch: Batch, buffer, indices) -> None:
-        """Algorithm._postprocess_batch (algorithm_base.py:560-582): a prioritized buffer takes `batch.weight` -- after
-        `_update_with_batch` the TD errors, still in HBM -- as the new priorities of `indices`."""
-        if hasattr(buffer, "update_weight"):
-            if "weight" in batch:
-                buffer.update_weight(indices, batch.weight)
-            else:
-                log.warning("batch has no attribute 'weight', but buffer has an update_weight method. This is probably a "
-                            "mistake. Prioritized replay is disabled for this batch.")
-
-    def update(self, buffer, sample_size: int | None, agent: int | None = None) -> SimpleLossTrainingStats:
-        """OffPolicyAlgorithm.update (algorithm_base.py:889-905): sample, preprocess, update, postprocess.  The sampled rows
-        are read from the device stores in place (`buffer.sample` would carry them through the host); with a prioritized
-        buffer the indices, the IS weights and the new priorities stay in HBM too, so the loss slot is the only host read."""
-        if not self.is_within_training_step:
-            raise RuntimeError("update() was called outside of a training step as signalled by "
-                               "`is_within_training_step=False`")
-        prioritized = hasattr(buffer, "update_weight")
-        indices = buffer.sample_indices_device(sample_size) if prioritized else buffer.sample_indices(sample_size)
-        batch = self._preprocess_batch(self._sampled_batch(buffer, indices), buffer, indices, agent=agent)
-        stats = self._update_with_batch(batch)
-        self._postprocess_batch(batch, buffer, indices)
-        if self.lr_scheduler is not None:
-            self.lr_scheduler.step()
-        return stats
 
     # ---- checkpoints ---------------------------------------------------------------------------------------------
     def state_dict(self, *args, **kwargs):  # type: ignore[override]

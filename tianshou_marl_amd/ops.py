@@ -1205,6 +1205,109 @@ def qrdqn_head(raw, q_next, raw_next, act, mc, gpow, vmask, tau_hat, mask_next=N
 
 
 # --------------------------------------------------------------------------------------------
+# Discrete SAC (discrete_sac.py; sac.py Alpha / AutoAlpha; csrc/dsac.hip)
+# --------------------------------------------------------------------------------------------
+def dsac_check(n_act: int, n_step: int = 1) -> None:
+    """The bounds of the Discrete SAC kernels (include/tsmarl.h): ValueError naming the limit."""
+    call("tsm_dsac_check", int(n_act), int(n_step))
+
+
+def _dsac_rows(name: str, first, others: tuple, per_row: tuple):
+    """[B, A] of `first`; every tensor of `others` must have that shape, every one of `per_row` B entries."""
+    first = _chk(first, torch.float32, "logits / q")
+    if first.dim() != 2:
+        raise ValueError(f"{name}: logits and Q values must be [B, A]")
+    B, A = first.shape
+    dsac_check(A)
+    if B < 1:
+        raise ValueError(f"{name}: empty batch")
+    for nm, x in others:
+        if x is not None and tuple(x.shape) != (B, A):
+            raise ValueError(f"{name}: {nm} must be [{B}, {A}]")
+    for nm, x in per_row:
+        if x is not None and x.numel() != B:
+            raise ValueError(f"{name}: {nm} must have {B} entries")
+    return first, B, A
+
+
+def _dsac_partial(B: int, dev) -> torch.Tensor:
+    return torch.empty(2 * -(-B // _abi.DSAC_ROWS_PER_BLOCK), dtype=torch.float64, device=dev)
+
+
+def dsac_target(logits_next, q1_next_old, q2_next_old, alpha_dev, mc, gpow, vmask):
+    """DiscreteSAC._target_q_compute_value after its forwards + the n-step target (discrete_sac.py:147-155,
+    algorithm_base.py:1213-1215) in one launch.  logits_next [B, A]: the online actor on obs_next[idx_n]; q1_next_old,
+    q2_next_old [B, A]: the lagged critics there; alpha_dev f32 [1]; mc, gpow, vmask from nstep_return.  -> returns f32 [B]."""
+    _dev_only("dsac_target", logits_next, q1_next_old, q2_next_old, alpha_dev, mc, gpow, vmask)
+    logits_next, B, A = _dsac_rows("dsac_target", logits_next, (("q1_next_old", q1_next_old), ("q2_next_old", q2_next_old)),
+                                   (("mc", mc), ("gpow", gpow), ("vmask", vmask)))
+    vm = vmask.contiguous().view(torch.uint8) if vmask.dtype == torch.bool else _chk(vmask, torch.uint8, "vmask")
+    returns = torch.empty(B, dtype=torch.float32, device=logits_next.device)
+    call("tsm_dsac_target", ptr(logits_next), ptr(_chk(q1_next_old, torch.float32, "q1_next_old")),
+         ptr(_chk(q2_next_old, torch.float32, "q2_next_old")), ptr(_chk(alpha_dev, torch.float32, "alpha_dev")),
+         ptr(_chk(mc, torch.float32, "mc").reshape(-1)), ptr(_chk(gpow, torch.float32, "gpow").reshape(-1)), ptr(vm.reshape(-1)),
+         B, A, ptr(returns), stream_ptr())
+    return returns
+
+
+def dsac_critic_head(q1, q2, act, returns, weight=None):
+    """Both critic losses of DiscreteSAC._update_with_batch and their gradients (discrete_sac.py:162-174) in one launch.
+    q1, q2 [B, A]: the critics on obs; act i64 [B]; returns f32 [B]; weight f32 [B] or None.
+    -> dict(dq1, dq2 [B, A], prio [B] = (td1 + td2) / 2 with td = q[act] - returns, partial f64):
+    `qmix_finalize(partial, B, out)` gives {critic1_loss, critic2_loss}."""
+    _dev_only("dsac_critic_head", q1, q2, act, returns, weight)
+    q1, B, A = _dsac_rows("dsac_critic_head", q1, (("q2", q2),), (("act", act), ("returns", returns), ("weight", weight)))
+    dev = q1.device
+    out = dict(dq1=torch.empty(B, A, dtype=torch.float32, device=dev), dq2=torch.empty(B, A, dtype=torch.float32, device=dev),
+               prio=torch.empty(B, dtype=torch.float32, device=dev), partial=_dsac_partial(B, dev))
+    call("tsm_dsac_critic_head", ptr(q1), ptr(_chk(q2, torch.float32, "q2")), ptr(_chk(act, torch.int64, "act").reshape(-1)),
+         ptr(_chk(returns, torch.float32, "returns").reshape(-1)),
+         ptr(None if weight is None else _chk(weight, torch.float32, "weight").reshape(-1)), B, A, ptr(out["dq1"]),
+         ptr(out["dq2"]), ptr(out["prio"]), ptr(out["partial"]), stream_ptr())
+    return out
+
+
+def dsac_actor_head(logits, q1, q2, alpha_dev):
+    """The actor loss of DiscreteSAC._update_with_batch with its backward down to the logits, and the entropy AutoAlpha
+    reads (discrete_sac.py:177-184) in one launch.  logits [B, A]: the actor on obs; q1, q2 [B, A]: the critics on obs after
+    their steps; alpha_dev f32 [1].  -> dict(entropy [B], d_logits [B, A], partial f64): `qmix_finalize(partial, B, out)`
+    gives {actor_loss, mean entropy}."""
+    _dev_only("dsac_actor_head", logits, q1, q2, alpha_dev)
+    logits, B, A = _dsac_rows("dsac_actor_head", logits, (("q1", q1), ("q2", q2)), ())
+    dev = logits.device
+    out = dict(entropy=torch.empty(B, dtype=torch.float32, device=dev), d_logits=torch.empty(B, A, dtype=torch.float32, device=dev),
+               partial=_dsac_partial(B, dev))
+    call("tsm_dsac_actor_head", ptr(logits), ptr(_chk(q1, torch.float32, "q1")), ptr(_chk(q2, torch.float32, "q2")),
+         ptr(_chk(alpha_dev, torch.float32, "alpha_dev")), B, A, ptr(out["entropy"]), ptr(out["d_logits"]), ptr(out["partial"]),
+         stream_ptr())
+    return out
+
+
+def dsac_alpha_step(entropy_partial, B: int, log_alpha, exp_avg, exp_avg_sq, step, target_entropy: float, alpha_dev, out,
+                    lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
+    """AutoAlpha.update (sac.py:203-209) on device scalars, one launch: entropy_partial f64: `dsac_actor_head`'s partials over
+    B rows (the mean entropy is formed from them in float64); log_alpha, exp_avg, exp_avg_sq f32 [1] and step i64 [1] in
+    HBM, updated in place; alpha_dev f32 [1] <- exp(log_alpha); out f32 [2] (device or pinned host memory) <- {alpha_loss,
+    the new alpha}."""
+    _dev_only("dsac_alpha_step", entropy_partial, log_alpha, exp_avg, exp_avg_sq, step, alpha_dev)
+    if out.is_cuda:
+        out_p = ptr(_chk(out, torch.float32, "out"))
+    elif out.is_pinned() and out.is_contiguous() and out.dtype == torch.float32:
+        out_p = out.data_ptr()
+    else:
+        raise RuntimeError("dsac_alpha_step needs device (HIP) tensors; there is no CPU path (out is neither in HBM nor pinned f32)")
+    entropy_partial = _chk(entropy_partial, torch.float64, "entropy_partial")
+    if out.numel() < 2 or entropy_partial.numel() < 2 or entropy_partial.numel() % 2:
+        raise ValueError("dsac_alpha_step: out must have 2 entries and entropy_partial pairs of {loss, entropy} sums")
+    call("tsm_dsac_alpha_step", ptr(entropy_partial), entropy_partial.numel() // 2, int(B),
+         ptr(_chk(log_alpha, torch.float32, "log_alpha")), ptr(_chk(exp_avg, torch.float32, "exp_avg")),
+         ptr(_chk(exp_avg_sq, torch.float32, "exp_avg_sq")), ptr(_chk(step, torch.int64, "step")), float(target_entropy), float(lr),
+         float(betas[0]), float(betas[1]), float(eps), float(weight_decay), ptr(_chk(alpha_dev, torch.float32, "alpha_dev")), out_p,
+         stream_ptr())
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # Prioritized replay (data/utils/segtree.py, data/buffer/prio.py; csrc/segtree.hip)
 # --------------------------------------------------------------------------------------------
 def segtree_bound(size: int) -> int:
