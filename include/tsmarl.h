@@ -1118,6 +1118,59 @@ int tsm_dsac_alpha_step(const double *entropy_partial, int32_t n_blocks, int64_t
                         float *exp_avg_sq, int64_t *step, double target_entropy, double lr, double beta1, double beta2,
                         double eps, double weight_decay, float *alpha_dev, float *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Implicit Quantile Network  (tianshou/algorithm/modelfree/iqn.py; utils/net/discrete.py:127-217; csrc/iqn.hip)
+ * A network row is (b, s) = b * sample_size + s: out f32 [R][sample_size][n_act] (the reference's [B, A, S] logits are its
+ * transposed view), e / phi f32 [R * sample_size][embedding_dim], taus f32 [R][sample_size].  The MLPs before and after the
+ * embedding run through tsm_mlp_forward / tsm_mlp_backward / tsm_mlp_input_grad.
+ * tsm_iqn_check: the bounds of the kernels (num_cosines a multiple of 4 in [4, 64], embedding_dim a multiple of 16 in
+ *   [16, 512], sample_size in [2, 64], n_act in [1, 64]): TSM_ERR_INVALID naming the limit.  Needs no device.
+ * tsm_iqn_taus replaces  `torch.rand(batch_size, sample_size)` of ImplicitQuantileNetwork.forward (discrete.py:211).
+ *   Row r draws at Philox4x32-10 counter offset + *offset_dev (nullable) + r, as tsm_dqn_egreedy counts its rows, under a
+ *   key that differs from that of the epsilon draws, so a policy may hand both the same counter.  Values in [0, 1).
+ * tsm_iqn_embed_forward replaces  CosineEmbeddingNetwork.forward and the product `logits.unsqueeze(1) * embed(taus)`
+ *           (discrete.py:145-161, 212-215).  One launch; the cosines never reach HBM.
+ *   f [R][embedding_dim]: the preprocess net's last LINEAR output; relu_f != 0 applies the ReLU with which the reference's
+ *   Net ends (common.py: every hidden layer is followed by its activation) here, g = relu, else g = identity.
+ *   We [embedding_dim][num_cosines], be [embedding_dim].
+ *   c[i] = cosf(tau * (f32(pi) * f32(i))), i = 1 .. num_cosines, each product rounded to f32;  phi = relu(We c + be) on f32
+ *   MFMA;  e[b,s] = g(f[b]) * phi[b,s].  out: e, and phi for the backward.
+ * tsm_iqn_embed_backward replaces  `loss.backward()` through the same lines.  One launch.
+ *   d_e [R * sample_size][embedding_dim]: the gradient at `last`'s input (tsm_mlp_input_grad).
+ *   out: d_f[b] = g'(f[b]) sum_s d_e[b,s] * phi[b,s] (s in order) for tsm_mlp_backward of the preprocess net; into slab z of n_split
+ *   (the batch rows ceil(R / n_split) z ..., all their samples): dWe at w_off = (d_e * g(f) * 1[phi > 0])^T c on f32 MFMA with
+ *   the cosines formed again, dbe at b_off its column sums.  Every slab is written in full.
+ * tsm_iqn_values replaces  QRDQNPolicy.compute_q_value's `logits.mean(2)` (qrdqn.py:20) on out [R][sample_size][n_act]:
+ *   q f32 [R][n_act], the sum over s in order / sample_size.  q feeds tsm_dqn_egreedy and tsm_iqn_head.
+ * tsm_iqn_head replaces  QRDQN._target_q after its forwards (qrdqn.py:94-106), `_nstep_return`'s last line
+ *           (algorithm_base.py:796, 1213-1215) and IQN._update_with_batch between `self.policy(batch)` and
+ *           `optim.step(loss)` (iqn.py:160-181).  One launch.
+ *   out [B][n_online][n_act]: the online net on obs, drawn with taus [B][n_online].  q_next [B][n_act]: tsm_iqn_values of the
+ *   ONLINE net on the successor rows; a* = its first argmax under mask_next (nullable), as tsm_dqn_td_head.
+ *   out_next [B][n_target][n_act]: the lagged net there, or that same online forward when there is no lagged net.
+ *   returns[b][j] = (float)((double)(out_next[b][j][a*] * vmask) * gpow + mc);  u_ij = returns[j] - out[b][i][act];
+ *   loss_b = (1 / n_online) sum_i sum_j smooth_l1(u_ij) |taus[b][i] - 1[u_ij <= 0]|;  loss = mean(loss_b * weight);
+ *   prio[b] = (1 / n_online) sum_i sum_j |smooth_l1(u_ij)|.
+ *   out: returns f32 [B][n_target]; prio f32 [B]; d_out f32 [B][n_online][n_act], exactly zero off the taken action; partial
+ *        f64 [2 * ceil(B / TSM_IQN_ROWS_PER_BLOCK)] = per workgroup {sum loss_b weight, sum mean_i out[b][i][act]} for
+ *        tsm_qmix_finalize.  An action outside [0, n_act) reads nothing: the row's loss, prio and q are NaN, its gradient zero.
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_IQN_ROWS_PER_BLOCK 16
+int tsm_iqn_check(int32_t num_cosines, int32_t embedding_dim, int32_t sample_size, int32_t n_act);
+int tsm_iqn_taus(int64_t R, int32_t sample_size, uint64_t seed, uint64_t offset, const uint64_t *offset_dev, float *taus,
+                 void *stream);
+int tsm_iqn_embed_forward(const float *f, const float *taus, const float *We, const float *be, int64_t R,
+                          int32_t sample_size, int32_t num_cosines, int32_t embedding_dim, int relu_f, float *e, float *phi,
+                          void *stream);
+int tsm_iqn_embed_backward(const float *d_e, const float *f, const float *phi, const float *taus, int64_t R,
+                           int32_t sample_size, int32_t num_cosines, int32_t embedding_dim, int relu_f, float *d_f, int32_t n_split,
+                           float *slabs, int64_t slab_stride, int64_t w_off, int64_t b_off, void *stream);
+int tsm_iqn_values(const float *out, int64_t R, int32_t sample_size, int32_t n_act, float *q, void *stream);
+int tsm_iqn_head(const float *out, const float *q_next, const float *out_next, const uint8_t *mask_next, const float *taus,
+                 const int64_t *act, const float *mc, const float *gpow, const uint8_t *vmask, const float *weight, int64_t B,
+                 int32_t n_act, int32_t n_online, int32_t n_target, float *returns_out, float *prio, float *d_out,
+                 double *partial, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

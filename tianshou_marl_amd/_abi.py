@@ -19,6 +19,7 @@ MAX_GATHER_FIELDS = 12  # include/tsmarl.h TSM_MAX_GATHER_FIELDS
 ABI_VERSION = 4  # include/tsmarl.h TSM_ABI_VERSION: bumped whenever a signature or a struct layout changes
 DISTQ_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_DISTQ_ROWS_PER_BLOCK: rows per workgroup of the C51 / QR-DQN heads
 DSAC_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_DSAC_ROWS_PER_BLOCK: rows per workgroup of the Discrete SAC heads
+IQN_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_IQN_ROWS_PER_BLOCK: rows per workgroup of the IQN head
 TSM_OK, TSM_ERR_INVALID, TSM_ERR_HIP, TSM_ERR_MALFORMED_BUFFER, TSM_ERR_UNSUPPORTED = range(5)
 
 
@@ -274,6 +275,12 @@ SIGNATURES = {
     "tsm_dsac_critic_head": (_int, [_p] * 5 + [_i64, _i32, _p, _p, _p, _p, _p]),
     "tsm_dsac_actor_head": (_int, [_p] * 4 + [_i64, _i32, _p, _p, _p, _p]),
     "tsm_dsac_alpha_step": (_int, [_p, _i32, _i64, _p, _p, _p, _p] + [_f64] * 6 + [_p, _p, _p]),
+    "tsm_iqn_check": (_int, [_i32, _i32, _i32, _i32]),
+    "tsm_iqn_taus": (_int, [_i64, _i32, _u64, _u64, _p, _p, _p]),
+    "tsm_iqn_embed_forward": (_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i32, _int, _p, _p, _p]),
+    "tsm_iqn_embed_backward": (_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i32, _int, _p, _i32, _p, _i64, _i64, _i64, _p]),
+    "tsm_iqn_values": (_int, [_p, _i64, _i32, _i32, _p, _p]),
+    "tsm_iqn_head": (_int, [_p] * 10 + [_i64, _i32, _i32, _i32, _p, _p, _p, _p, _p]),
     "tsm_segtree_bound": (_i64, [_i64]),
     "tsm_segtree_set": (_int, [_p, _p, _i64, _p, _i64, _p, _i64, _p, _p]),
     "tsm_segtree_prefix_sum_idx": (_int, [_p, _i64, _p, _i64, _p, _p]),

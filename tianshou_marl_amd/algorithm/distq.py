@@ -202,14 +202,18 @@ class QRDQN(_DistributionalQLearning):
     def __init__(self, *, policy: QRDQNPolicy, optim: Any, gamma: float = 0.99, num_quantiles: int = 200,
                  n_step_return_horizon: int = 1, target_update_freq: int = 0) -> None:
         assert num_quantiles > 1, f"num_quantiles should be greater than 1 but got: {num_quantiles}"
-        if isinstance(policy, QRDQNPolicy) and policy.num_quantiles != num_quantiles:
-            raise ValueError(f"QRDQN: num_quantiles = {num_quantiles}, but the policy's net emits {policy.num_quantiles} "
-                             "quantiles per action")
+        self._check_quantiles(policy, num_quantiles)
         super().__init__(policy=policy, optim=optim, gamma=gamma, n_step_return_horizon=n_step_return_horizon,
                          target_update_freq=target_update_freq)
         self.num_quantiles = int(num_quantiles)
         tau = torch.linspace(0, 1, self.num_quantiles + 1)   # qrdqn.py:87-90, in float32 on the host as there
         self.tau_hat = ((tau[:-1] + tau[1:]) / 2).view(1, -1, 1).to(self.device)
+
+    @staticmethod
+    def _check_quantiles(policy, num_quantiles: int) -> None:
+        if isinstance(policy, QRDQNPolicy) and policy.num_quantiles != num_quantiles:
+            raise ValueError(f"QRDQN: num_quantiles = {num_quantiles}, but the policy's net emits {policy.num_quantiles} "
+                             "quantiles per action")
 
     def _head(self, batch: Batch, q, act, weight):
         head = ops.qrdqn_head(q, batch.q_next_online, batch.raw_next, act, batch.mc, batch.gpow, batch.vmask, self.tau_hat,

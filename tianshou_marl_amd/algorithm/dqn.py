@@ -52,13 +52,15 @@ def _obs_rows(obs):
 class DiscreteQLearningPolicy(nn.Module):
     """dqn.py:39-174 with a `FlatMLP` Q-network (obs -> ... -> n actions)."""
 
+    _model_cls: type = FlatMLP   # the network class the update kernels of this policy's learner run on
+
     def __init__(self, *, model: FlatMLP, action_space: Any, observation_space: Any = None, eps_training: float = 0.0,
                  eps_inference: float = 0.0, seed: int = 0, atoms: int = 1) -> None:
         """`atoms`: outputs per action -- 1 here; the distributional policies (algorithm/distq.py) pass their N."""
         super().__init__()
-        if not isinstance(model, FlatMLP):
-            raise TypeError("DiscreteQLearningPolicy needs a FlatMLP Q-network: the update runs in HIP, there is no "
-                            f"autograd fallback (got {type(model).__name__})")
+        if not isinstance(model, self._model_cls):
+            raise TypeError(f"DiscreteQLearningPolicy needs a {self._model_cls.__name__} Q-network: the update runs in HIP, "
+                            f"there is no autograd fallback (got {type(model).__name__})")
         n = getattr(action_space, "n", None)
         if n is None or int(n) * int(atoms) != model.dims[-1]:
             raise ValueError(f"DiscreteQLearningPolicy: the model has {model.dims[-1]} outputs, the action space "
@@ -279,9 +281,17 @@ class DQN(DeviceOffPolicyRows, nn.Module):
             # one flat copy viewed by a net of the same shape; its constructor draws from a private generator (seed given)
             # and the copy overwrites that: the global torch RNG is not drawn from, as the reference's deepcopy draws nothing
             self.target_flat = model.flat.data.clone()
-            self.model_old = FlatMLP(model.dims, model.act, device=model.flat.device, seed=0, storage=self.target_flat)
+            self.model_old = self._lagged_net(model, self.target_flat)
             self.target_flat.copy_(model.flat.data)
         self._ws: dict = {}
+
+    @staticmethod
+    def _lagged_net(model, storage: torch.Tensor):
+        """A net of `model`'s shape over the lagged flat vector: a composite network (`ImplicitQuantileNet`) clones itself."""
+        clone = getattr(model, "clone_over", None)
+        if clone is not None:
+            return clone(storage)
+        return FlatMLP(model.dims, model.act, device=model.flat.device, seed=0, storage=storage)
 
     @property
     def device(self) -> torch.device:
@@ -336,7 +346,7 @@ class DQN(DeviceOffPolicyRows, nn.Module):
             n_split = ops.mlp_n_split(B)
             w = self._ws[B] = dict(n_split=n_split,
                                    slabs=torch.empty(n_split, model.flat.numel(), dtype=torch.float32, device=dev))
-        q = FlatMLP.forward(model, x, save=True)
+        q = self._online_forward(batch, x)
         d_out, partial, returns, prio = self._head(batch, q, act, None if weight is None else
                                                    to_tensor(weight, dev, torch.float32).reshape(-1))
         model.backward(d_out, w["n_split"], slabs=w["slabs"])
@@ -348,6 +358,10 @@ class DQN(DeviceOffPolicyRows, nn.Module):
         batch.weight = prio  # prio-buffer
         slot["event"].synchronize()
         return self._stats(float(slot["h"][0]))
+
+    def _online_forward(self, batch: Batch, x: torch.Tensor) -> torch.Tensor:
+        """The online net on the sampled rows, activations kept for `model.backward`."""
+        return FlatMLP.forward(self.policy.model, x, save=True)
 
     def _after_lagged_copy(self, batch: Batch) -> None:
         """What a learner computes between the lagged copy and its loss (C51's successor forwards); nothing here."""

@@ -1205,6 +1205,134 @@ def qrdqn_head(raw, q_next, raw_next, act, mc, gpow, vmask, tau_hat, mask_next=N
 
 
 # --------------------------------------------------------------------------------------------
+# Implicit Quantile Network (iqn.py; utils/net/discrete.py:127-217; csrc/iqn.hip)
+# --------------------------------------------------------------------------------------------
+def iqn_check(num_cosines: int, embedding_dim: int, sample_size: int = 2, n_act: int = 1) -> None:
+    """The bounds of the IQN kernels (include/tsmarl.h): ValueError naming the limit."""
+    call("tsm_iqn_check", int(num_cosines), int(embedding_dim), int(sample_size), int(n_act))
+
+
+def iqn_taus(R: int, sample_size: int, seed: int, device, offset: int = 0, offset_dev=None, out=None):
+    """`torch.rand(R, sample_size)` of ImplicitQuantileNetwork.forward (discrete.py:211) from Philox on the device: row r
+    draws at counter offset + *offset_dev + r under a key of its own.  -> taus f32 [R, sample_size] in [0, 1)."""
+    R, S = int(R), int(sample_size)
+    iqn_check(4, 16, S)
+    if out is None:
+        out = torch.empty(R, S, dtype=torch.float32, device=device)
+    elif tuple(out.shape) != (R, S):
+        raise ValueError(f"iqn_taus: out must be [{R}, {S}]")
+    _dev_only("iqn_taus", out, offset_dev)
+    call("tsm_iqn_taus", R, S, seed & (2**64 - 1), offset & (2**64 - 1), ptr(offset_dev), ptr(_chk(out, torch.float32, "out")),
+         stream_ptr())
+    return out
+
+
+def _iqn_embed_shapes(name: str, f, taus, We, be):
+    if f.dim() != 2 or taus.dim() != 2 or We.dim() != 2 or f.shape[0] != taus.shape[0]:
+        raise ValueError(f"{name}: f must be [R, H], taus [R, S] and We [H, C]")
+    (R, H), S, C = f.shape, taus.shape[1], We.shape[1]
+    iqn_check(C, H, S)
+    if We.shape[0] != H or be.numel() != H:
+        raise ValueError(f"{name}: We must be [{H}, C] and be [{H}]")
+    if R < 1:
+        raise ValueError(f"{name}: empty batch")
+    return R, S, C, H
+
+
+def iqn_embed_forward(f, taus, We, be, relu_f: bool = False):
+    """CosineEmbeddingNetwork.forward and its product with the features (discrete.py:145-161, 212-215) in one launch:
+    f [R, H], taus [R, S], We [H, C], be [H] -> (e [R * S, H] = g(f[b]) * phi[b, s], phi [R * S, H] = relu(We cos + be));
+    g = relu with relu_f (a preprocess net that ends in its activation, as the reference's Net), else the identity."""
+    _dev_only("iqn_embed_forward", f, taus, We, be)
+    R, S, C, H = _iqn_embed_shapes("iqn_embed_forward", f, taus, We, be)
+    e = torch.empty(R * S, H, dtype=torch.float32, device=f.device)
+    phi = torch.empty_like(e)
+    call("tsm_iqn_embed_forward", ptr(_chk(f, torch.float32, "f")), ptr(_chk(taus, torch.float32, "taus")),
+         ptr(_chk(We, torch.float32, "We")), ptr(_chk(be, torch.float32, "be")), R, S, C, H, int(bool(relu_f)), ptr(e), ptr(phi), stream_ptr())
+    return e, phi
+
+
+def iqn_embed_backward(d_e, f, phi, taus, We, be, n_split: int = 0, slabs=None, slab_stride: int = 0, w_off: int = 0,
+                       b_off: int | None = None, relu_f: bool = False):
+    """The backward of `iqn_embed_forward` in one launch: d_e [R * S, H] -> (d_f [R, H], slabs).  dWe / dbe fill n_split
+    slabs at w_off / b_off of rows `slab_stride` apart (default: slabs of their own, [n_split, H * C + H])."""
+    _dev_only("iqn_embed_backward", d_e, f, phi, taus, We, be, slabs)
+    R, S, C, H = _iqn_embed_shapes("iqn_embed_backward", f, taus, We, be)
+    if tuple(d_e.shape) != (R * S, H) or tuple(phi.shape) != (R * S, H):
+        raise ValueError(f"iqn_embed_backward: d_e and phi must be [{R * S}, {H}]")
+    if n_split <= 0:
+        n_split = mlp_n_split(R)
+    if b_off is None:
+        b_off = w_off + H * C
+    if slabs is None:
+        slab_stride = slab_stride or H * C + H
+        slabs = torch.empty(n_split, slab_stride, dtype=torch.float32, device=f.device)
+    elif slab_stride <= 0:
+        slab_stride = slabs.stride(0)
+    if slabs.dim() != 2 or slabs.shape[0] < n_split or slabs.stride(1) != 1 or slabs.stride(0) != slab_stride \
+            or slabs.dtype != torch.float32 or max(w_off + H * C, b_off + H) > slabs.shape[1]:
+        raise ValueError("iqn_embed_backward: slabs must be f32 [n_split, >= the end of both blocks] with rows slab_stride apart")
+    d_f = torch.empty(R, H, dtype=torch.float32, device=f.device)
+    call("tsm_iqn_embed_backward", ptr(_chk(d_e, torch.float32, "d_e")), ptr(_chk(f, torch.float32, "f")),
+         ptr(_chk(phi, torch.float32, "phi")), ptr(_chk(taus, torch.float32, "taus")), R, S, C, H, int(bool(relu_f)), ptr(d_f), int(n_split),
+         slabs.data_ptr(), int(slab_stride), int(w_off), int(b_off), stream_ptr())
+    return d_f, slabs
+
+
+def iqn_values(out, sample_size: int, n_act: int):
+    """QRDQNPolicy.compute_q_value's mean over the fractions (qrdqn.py:20) on the sample-major output: out [R * S, A] or
+    [R, S, A] -> q [R, A], before the action mask."""
+    _dev_only("iqn_values", out)
+    S, A = int(sample_size), int(n_act)
+    iqn_check(4, 16, S, A)
+    out = _chk(out, torch.float32, "out")
+    if out.numel() % (S * A) != 0 or out.shape[-1] != A:
+        raise ValueError(f"iqn_values: out must be [R, {S}, {A}]")
+    R = out.numel() // (S * A)
+    q = torch.empty(R, A, dtype=torch.float32, device=out.device)
+    call("tsm_iqn_values", ptr(out), R, S, A, ptr(q), stream_ptr())
+    return q
+
+
+def iqn_head(out, q_next, out_next, taus, act, mc, gpow, vmask, mask_next=None, weight=None):
+    """QRDQN._target_q after its forwards + the quantile Huber loss of IQN._update_with_batch over per-row fractions and its
+    gradient (qrdqn.py:94-106, iqn.py:160-181) in one launch.  out [B, N, A]: the online net on obs under taus [B, N];
+    q_next [B, A]: `iqn_values` of the online net on the successor rows; out_next [B, N', A]: the lagged net there (that same
+    online forward when there is none); act i64 [B]; mc, gpow, vmask from nstep_return; mask_next u8 / bool [B, A] or None;
+    weight f32 [B] or None.  -> dict(returns [B, N'], prio [B], d_out [B, N, A], partial f64): `qmix_finalize(partial, B,
+    out)` gives {loss, mean value of the taken action}."""
+    _dev_only("iqn_head", out, q_next, out_next, taus, act, mc, gpow, vmask, mask_next, weight)
+    if q_next.dim() != 2 or taus.dim() != 2 or out.dim() != 3 or out_next.dim() != 3:
+        raise ValueError("iqn_head: out must be [B, N, A], out_next [B, N', A], q_next [B, A] and taus [B, N]")
+    B, A = q_next.shape
+    N, Np = taus.shape[1], out_next.shape[1]
+    iqn_check(4, 16, N, A)
+    iqn_check(4, 16, Np, A)
+    if B < 1:
+        raise ValueError("iqn_head: empty batch")
+    for nm, x, shape in (("out", out, (B, N, A)), ("out_next", out_next, (B, Np, A)), ("taus", taus, (B, N)),
+                         ("mask_next", mask_next, (B, A))):
+        if x is not None and tuple(x.shape) != shape:
+            raise ValueError(f"iqn_head: {nm} must be {list(shape)}")
+    for nm, x in (("act", act), ("mc", mc), ("gpow", gpow), ("vmask", vmask), ("weight", weight)):
+        if x is not None and x.numel() != B:
+            raise ValueError(f"iqn_head: {nm} must have {B} entries")
+    u8 = lambda x, n: x.contiguous().view(torch.uint8) if x.dtype == torch.bool else _chk(x, torch.uint8, n)  # noqa: E731
+    dev = out.device
+    n_blocks = -(-B // _abi.IQN_ROWS_PER_BLOCK)
+    res = dict(returns=torch.empty(B, Np, dtype=torch.float32, device=dev), prio=torch.empty(B, dtype=torch.float32, device=dev),
+               d_out=torch.empty(B, N, A, dtype=torch.float32, device=dev),
+               partial=torch.empty(2 * n_blocks, dtype=torch.float64, device=dev))
+    call("tsm_iqn_head", ptr(_chk(out, torch.float32, "out")), ptr(_chk(q_next, torch.float32, "q_next")),
+         ptr(_chk(out_next, torch.float32, "out_next")), ptr(None if mask_next is None else u8(mask_next, "mask_next")),
+         ptr(_chk(taus, torch.float32, "taus")), ptr(_chk(act, torch.int64, "act").reshape(-1)),
+         ptr(_chk(mc, torch.float32, "mc").reshape(-1)), ptr(_chk(gpow, torch.float32, "gpow").reshape(-1)),
+         ptr(u8(vmask, "vmask").reshape(-1)), ptr(None if weight is None else _chk(weight, torch.float32, "weight").reshape(-1)),
+         B, A, N, Np, ptr(res["returns"]), ptr(res["prio"]), ptr(res["d_out"]), ptr(res["partial"]), stream_ptr())
+    return res
+
+
+# --------------------------------------------------------------------------------------------
 # Discrete SAC (discrete_sac.py; sac.py Alpha / AutoAlpha; csrc/dsac.hip)
 # --------------------------------------------------------------------------------------------
 def dsac_check(n_act: int, n_step: int = 1) -> None:

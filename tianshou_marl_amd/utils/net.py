@@ -235,6 +235,127 @@ class FlatMLP(nn.Module):
         self.load_layers([(sd[f"fc{i + 1}.weight"], sd[f"fc{i + 1}.bias"]) for i in range(self.n_layers)])
 
 
+class ImplicitQuantileNet(nn.Module):
+    """ImplicitQuantileNetwork (discrete.py:164-217) on ONE flat f32 parameter vector in the reference module's
+    `parameters()` order: the preprocess layers, the `last` layers, then the cosine embedding's weight [H, C] and bias [H].
+    `preprocess` (obs -> ... -> H) and `last` (H -> hidden_sizes -> A) are `FlatMLP`s over slices of the vector (csrc/dense.hip);
+    the embedding and its product with the features are csrc/iqn.hip.  `feature_act`: the preprocess net ends in its
+    activation, as the reference's `Net` does (every hidden layer is followed by one); the ReLU is then applied inside the
+    embedding kernels.  A network row is (b, s): `forward` returns out [R * S, A], the reference's [R, A, S] logits being
+    `out.view(R, S, A).transpose(1, 2)`."""
+
+    def __init__(self, preprocess_dims, n_act: int, hidden_sizes=(), num_cosines: int = 64, act: str = "relu",
+                 feature_act: bool = True, device: str | torch.device = "cuda", seed: int | None = None,
+                 storage: torch.Tensor | None = None) -> None:
+        super().__init__()
+        if act != "relu":
+            raise ValueError("ImplicitQuantileNet: the embedding kernels carry the ReLU of the reference; act must be 'relu'")
+        self.pre_dims = [int(d) for d in preprocess_dims]
+        self.n_act, self.hidden_sizes, self.num_cosines = int(n_act), tuple(int(h) for h in hidden_sizes), int(num_cosines)
+        self.act, self.feature_act = act, bool(feature_act)
+        H = self.embedding_dim = self.pre_dims[-1]
+        ops.iqn_check(self.num_cosines, H, 2, self.n_act)
+        self.last_dims = [H, *self.hidden_sizes, self.n_act]
+        n_pre = ops.mlp_param_count(ops.mlp_desc(self.pre_dims, act))
+        n_last = ops.mlp_param_count(ops.mlp_desc(self.last_dims, act))
+        self.w_off, self.b_off = n_pre + n_last, n_pre + n_last + H * self.num_cosines
+        n = self.b_off + H
+        if storage is None:
+            storage = torch.zeros(n, dtype=torch.float32, device=device)
+        elif storage.numel() != n or storage.dtype != torch.float32 or not storage.is_contiguous():
+            raise ValueError(f"ImplicitQuantileNet: storage must be a contiguous f32 vector of {n} elements")
+        self.flat = nn.Parameter(storage, requires_grad=False)
+        self.n_pre, self.n_last = n_pre, n_last
+        self.preprocess = FlatMLP(self.pre_dims, act, device=storage.device, seed=seed, storage=storage[:n_pre])
+        self.last = FlatMLP(self.last_dims, act, device=storage.device, seed=None if seed is None else seed + 1,
+                            storage=storage[n_pre:n_pre + n_last])
+        self.dims = [self.pre_dims[0], self.n_act]   # what the policies ask of a Q-network: input width, outputs per sample
+        self._saved = None
+        self.reset_embedding(None if seed is None else seed + 2)
+
+    @property
+    def We(self) -> torch.Tensor:
+        return self.flat.data[self.w_off:self.b_off].view(self.embedding_dim, self.num_cosines)
+
+    @property
+    def be(self) -> torch.Tensor:
+        return self.flat.data[self.b_off:]
+
+    @torch.no_grad()
+    def reset_embedding(self, seed: int | None = None) -> None:
+        """torch nn.Linear default init of the embedding layer."""
+        gen = torch.Generator().manual_seed(seed) if seed is not None else None
+        bound = 1.0 / math.sqrt(self.num_cosines)
+        self.We.copy_(torch.empty(self.We.shape).uniform_(-bound, bound, generator=gen))
+        self.be.copy_(torch.empty(self.be.shape).uniform_(-bound, bound, generator=gen))
+
+    def clone_over(self, storage: torch.Tensor) -> "ImplicitQuantileNet":
+        """A net of the same shape viewing `storage` (the lagged copy of an off-policy learner); `storage` keeps what the
+        constructor's init wrote until the caller copies over it."""
+        return ImplicitQuantileNet(self.pre_dims, self.n_act, self.hidden_sizes, self.num_cosines, self.act, self.feature_act,
+                                   device=storage.device, seed=0, storage=storage)
+
+    def forward(self, x: torch.Tensor, sample_size: int, taus: torch.Tensor | None = None, save: bool = True, seed: int = 0,
+                offset: int = 0, offset_dev: torch.Tensor | None = None):
+        """x [R, D] -> (out [R * S, A], taus [R, S]).  taus None: drawn on the device (tsm_iqn_taus at `seed`, `offset`,
+        `offset_dev`); given: used as they are."""
+        x = x.to(self.flat.device, torch.float32).contiguous().reshape(-1, self.pre_dims[0])
+        R, S = x.shape[0], int(sample_size)
+        ops.iqn_check(self.num_cosines, self.embedding_dim, S, self.n_act)
+        if taus is None:
+            taus = ops.iqn_taus(R, S, seed, x.device, offset=offset, offset_dev=offset_dev)
+        elif tuple(taus.shape) != (R, S):
+            raise ValueError(f"ImplicitQuantileNet: taus must be [{R}, {S}]")
+        taus = taus.to(self.flat.device, torch.float32).contiguous()
+        f = FlatMLP.forward(self.preprocess, x, save=save)
+        e, phi = ops.iqn_embed_forward(f, taus, self.We, self.be, relu_f=self.feature_act)
+        out = FlatMLP.forward(self.last, e, save=save)
+        if save:
+            self._saved = (f, phi, taus)
+        return out, taus
+
+    def backward(self, d_out: torch.Tensor, n_split: int = 0, slabs: torch.Tensor | None = None) -> torch.Tensor:
+        """Gradient slabs [n_split, n_param] of the whole flat vector for the last `forward(save=True)`, in one pass:
+        `last`'s weight slabs, its input gradient (a second walk of its dgrad chain: `FlatMLP.input_grad`), the embedding's
+        backward, the preprocess net's slabs."""
+        if self._saved is None:
+            raise RuntimeError("ImplicitQuantileNet.backward called before forward")
+        f, phi, taus = self._saved
+        R, S = taus.shape
+        P = self.flat.numel()
+        if n_split <= 0:
+            n_split = ops.mlp_n_split(R)
+        if slabs is None:
+            slabs = torch.empty(n_split, P, dtype=torch.float32, device=self.flat.device)
+        elif tuple(slabs.shape) != (n_split, P) or not slabs.is_contiguous():
+            raise ValueError(f"ImplicitQuantileNet.backward: slabs must be a contiguous [{n_split}, {P}]")
+        d_out = d_out.reshape(R * S, self.n_act).contiguous()
+        self.last.backward(d_out, n_split, slabs=slabs[:, self.n_pre:], slab_stride=P)
+        d_e = self.last.input_grad(d_out, 0, self.embedding_dim)
+        d_f, _ = ops.iqn_embed_backward(d_e, f, phi, taus, self.We, self.be, n_split, slabs=slabs, slab_stride=P,
+                                        w_off=self.w_off, b_off=self.b_off, relu_f=self.feature_act)
+        self.preprocess.backward(d_f, n_split, slabs=slabs, slab_stride=P)
+        return slabs
+
+    # ---- reference checkpoint compatibility ---------------------------------------------------------------------------
+    def reference_named_views(self) -> list[tuple[str, torch.Tensor]]:
+        """[(key, view)] in `parameters()` order under the reference's names: `preprocess.model.model.{2 i}` (Net: Linear,
+        activation, ...), `last.model.{2 i}` (MLP), `embed_model.net.0` (tests/golden/iqn.npz, sd_*)."""
+        out = []
+        for stem, net in (("preprocess.model.model", self.preprocess), ("last.model", self.last)):
+            for i in range(net.n_layers):
+                out += [(f"{stem}.{2 * i}.weight", net.weight(i)), (f"{stem}.{2 * i}.bias", net.bias(i))]
+        return out + [("embed_model.net.0.weight", self.We), ("embed_model.net.0.bias", self.be)]
+
+    def to_reference_state_dict(self) -> OrderedDict:
+        return OrderedDict((k, v.detach().clone().cpu()) for k, v in self.reference_named_views())
+
+    @torch.no_grad()
+    def load_reference_state_dict(self, sd, prefix: str = "") -> None:
+        for k, v in self.reference_named_views():
+            v.copy_(torch.as_tensor(np.asarray(sd[prefix + k])).to(v.device, v.dtype).reshape(v.shape))
+
+
 class MLPActorCritic(nn.Module):
     """Actor and critic MLPs of ARBITRARY widths under one flat parameter vector (`ActorCritic(actor, critic)`,
     common.py:461-474: one optimizer, one global gradient-norm clip).  Layout = actor parameters then critic parameters,
