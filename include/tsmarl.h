@@ -275,6 +275,18 @@ typedef struct {
  * stats_out [n_mb][2] f32 = {mean, std}.  One launch serves every minibatch of an epoch. */
 int tsm_ppo_adv_stats(const float *adv, const int64_t *perm, const int64_t *mb_start,
                       int32_t n_mb, float *stats_out, void *stream);
+/* The statistics above AND the minibatches' rows, gathered once per update, in ONE launch (minibatches of up to 8192 rows:
+ * max_rows >= the longest one, host knowledge).  packed_out receives one record per 16-row tile, tiles in order within a
+ * minibatch, minibatch k's first record at index tile_start[k] (device i64[n_mb], in records; minibatch k takes
+ * ceil(rows / 16) of them).  A record is tsm_ppo_packed_record_elems(obs_dim) = 16 * obs_dim + 80 four-byte words:
+ * obs rows [16][obs_dim] | act[16] (i32) | logp_old[16] | adv[16] | returns[16] | v_old[16]; rows past the end of a ragged
+ * last tile are zero.  v_old: v_s_old when the loss clips the value, else returns (any readable array of the same length).
+ * stats_out is nullable (no advantage normalisation: rows only).  tsm_ppo_update_fused_packed reads the records. */
+int64_t tsm_ppo_packed_record_elems(int32_t obs_dim);
+int tsm_ppo_pack_minibatches(const float *adv, const int64_t *perm, const int64_t *mb_start, int32_t n_mb,
+                             int64_t max_rows, float *stats_out, const float *obs, int32_t obs_dim,
+                             const int32_t *act, const float *logp_old, const float *returns, const float *v_old,
+                             const int64_t *tile_start, float *packed_out, void *stream);
 /* The same statistics for long minibatches: every 8192-row chunk of a minibatch is reduced by its own workgroup
  * (shifted f64 sums), a second launch folds the chunks in chunk order (deterministic; independent of the grid).
  * max_rows >= the longest minibatch (host knowledge: mb_start lives in HBM); a longer minibatch gets {NaN, NaN};
@@ -404,6 +416,18 @@ int tsm_ppo_update_fused(const float *params, const float *param_image, int32_t 
                          const tsm_ppo_cfg *cfg_host, int32_t n_blocks, float *grad_slabs_out,
                          double *loss_partial_out, float *scalars_out, int64_t *opt_step_dev,
                          void *stream);
+/* The same step with the minibatch's rows also given as tile records (`packed`: the minibatch's first record, as written by
+ * tsm_ppo_pack_minibatches from these very arrays and this perm): the kernel reads its tile's record in the same batch of loads
+ * as the weight image instead of row ids first and the rows behind them.  Same bits.  packed == NULL, or no param_image: the
+ * rows are read through perm / first_row, which must describe them either way. */
+int tsm_ppo_update_fused_packed(const float *params, const float *param_image, int32_t obs_dim, int32_t hidden,
+                                int32_t n_act,
+                                const float *obs, const int32_t *act, const float *logp_old, const float *adv,
+                                const float *returns, const float *v_s_old, const int64_t *perm,
+                                int64_t first_row, int64_t M, const float *adv_stats,
+                                const tsm_ppo_cfg *cfg_host, int32_t n_blocks, float *grad_slabs_out,
+                                double *loss_partial_out, float *scalars_out, int64_t *opt_step_dev,
+                                const float *packed, void *stream);
 
 /* Loss statistics of many gradient steps in ONE launch (pass scalars_out = NULL to tsm_ppo_update_fused):
  * step k reads loss partials at partial + k*stride_elems (n_blocks_dev[k] rows of 4 f64) and M_dev[k];

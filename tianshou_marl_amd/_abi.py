@@ -261,6 +261,10 @@ SIGNATURES = {
     "tsm_ppo_finalize_many": (_int, [_p, _i64, _p, _p, _i32, C.POINTER(tsm_ppo_cfg), _p, _p]),
     "tsm_ppo_update_fused": (_int, [_p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p,
                                     C.POINTER(tsm_ppo_cfg), _i32, _p, _p, _p, _p, _p]),
+    "tsm_ppo_update_fused_packed": (_int, [_p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p,
+                                           C.POINTER(tsm_ppo_cfg), _i32, _p, _p, _p, _p, _p, _p]),
+    "tsm_ppo_packed_record_elems": (_i64, [_i32]),
+    "tsm_ppo_pack_minibatches": (_int, [_p, _p, _p, _i32, _i64, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "tsm_nstep_return": (_int, [_p, _i64, _i64, _p, _p, _i64, _i32, _p, _i64, _i32, _p, _i64, _i32, _f64, _p, _p, _p, _p, _p]),
     "tsm_dqn_check": (_int, [_i32, _i32]),
     "tsm_dqn_partial_elems": (_i64, [_i64]),
@@ -294,7 +298,7 @@ SIGNATURES = {
 
 _NO_STATUS = {"tsm_critic_rows_w1_image_kj", "tsm_critic_rows_w1_image_elems", "tsm_p2p_ipc_handle_bytes", "tsm_p2p_failed", "tsm_critic_rows_forward_supported", "tsm_critic_rows_param_count", "tsm_critic_rows_grad_grid", "tsm_critic_rows_dw1_chunks", "tsm_ppo_critic_rows_supported", "tsm_ppo_critic_rows_param_count", "tsm_ppo_critic_rows_grid",
               "tsm_ppo_actor_rows_supported", "tsm_ppo_actor_rows_param_count", "tsm_ppo_actor_rows_grid",
-              "tsm_rms_update_work_elems", "tsm_ppo_adv_stats_work_elems", "tsm_abi_version", "tsm_last_error", "tsm_stream_abort_capture", "tsm_vrb_state_bytes", "tsm_ppo_loss_partial_elems",
+              "tsm_rms_update_work_elems", "tsm_ppo_adv_stats_work_elems", "tsm_ppo_packed_record_elems", "tsm_abi_version", "tsm_last_error", "tsm_stream_abort_capture", "tsm_vrb_state_bytes", "tsm_ppo_loss_partial_elems",
               "tsm_policy_param_count", "tsm_ppo_update_grid", "tsm_adam_work_elems", "tsm_policy_image_elems",
               "tsm_mlp_param_count", "tsm_mlp_act_elems", "tsm_ctde_head_partial_elems", "tsm_mpe_tag_obs_dim",
               "tsm_gae_scan_workspace_bytes", "tsm_qmix_partial_elems", "tsm_maddpg_partial_elems", "tsm_dqn_partial_elems",

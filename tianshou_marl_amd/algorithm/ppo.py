@@ -97,6 +97,7 @@ class PPO(nn.Module):
         self.betas, self.adam_eps, self.weight_decay = betas, adam_eps, weight_decay
         self.eps_clip, self.dual_clip, self.value_clip = eps_clip, dual_clip, value_clip
         self.advantage_normalization, self.recompute_adv = advantage_normalization, recompute_advantage
+        self.pack_rows = True  # the statistics launch also gathers the minibatches' rows for the gradient steps (`_minibatch_plan`)
         self.vf_coef, self.ent_coef, self.max_grad_norm = vf_coef, ent_coef, max_grad_norm
         self.gae_lambda, self.gamma, self.max_batchsize = gae_lambda, gamma, max_batchsize
         self.return_scaling, self.ret_rms, self._eps = return_scaling, DeviceRunningMeanStd(net.flat.device), 1e-8
@@ -354,13 +355,18 @@ class PPO(nn.Module):
         ops.call("tsm_u64_add", ops.ptr(self._perm_ctr), 1, ops.stream_ptr())
         return perm
 
-    def _minibatch_plan(self, n: int, batch_size: int | None, reps: int, defer: bool, agree: bool = True) -> dict:
+    def _minibatch_plan(self, n: int, batch_size: int | None, reps: int, defer: bool, agree: bool = True,
+                        pack_reps: int = 0) -> dict:
         """What the gradient steps of `reps` passes over n rows need besides the rows: the minibatch `bounds` (Batch.split's
         merge-last rule) and their starts on the device, and where the steps write -- the gradient slabs, the flat gradient
         of a data-parallel replica, and the loss partials.  defer: the partials of EVERY step stay (one row per step) until
         ONE `ppo_finalize_many` launch behind the captured sequence folds them, which reads `nb_dev` / `M_dev`; otherwise
         each step folds its own.  agree: data-parallel replicas make sure here that they take the same number of steps
-        (a collective -- on every eager update, at capture time for a graph: `GradSync.require_equal`)."""
+        (a collective -- on every eager update, at capture time for a graph: `GradSync.require_equal`).
+        pack_reps > 0: ONE statistics launch serves that many passes (all of a captured update, one of an eager one) -- it
+        then also gathers their minibatches' rows into `plan["packed"]` (`ops.ppo_pack_minibatches`), which the gradient steps
+        read instead of chasing the permutation; None where that launch does not exist (no advantage normalisation, minibatches
+        above 8192 rows) or `pack_rows` is off."""
         dev, P = self.device, self.net.flat.data
         bounds = split_bounds(n, batch_size or -1, merge_last=True)
         n_steps = reps * len(bounds)
@@ -370,7 +376,14 @@ class PPO(nn.Module):
         # the grid is not monotone in the minibatch size (ops.ppo_update_grid): size the slabs / partials for the largest grid
         nb_max = max(grids)
         plan = dict(bounds=bounds, n_steps=n_steps, nb_max=nb_max, max_rows=max(e - s for s, e in bounds),
-                    mb_start=torch.as_tensor([b[0] for b in bounds] + [n], dtype=torch.int64, device=dev))
+                    mb_start=torch.as_tensor([b[0] for b in bounds] + [n], dtype=torch.int64, device=dev), packed=None)
+        if pack_reps and self.pack_rows and self.advantage_normalization and plan["max_rows"] <= 8192:
+            key = ("packed", n, batch_size, pack_reps)   # (eager updates: one allocation per shape, as the slabs)
+            plan["packed"] = self._ws.get(key) if not defer else None
+            if plan["packed"] is None:
+                plan["packed"] = ops.ppo_pack_workspace([e - s for s, e in bounds] * pack_reps, self.net.obs_dim, dev)
+                if not defer:
+                    self._ws[key] = plan["packed"]
         if defer:  # static allocations of one captured sequence
             plan.update(slabs=torch.zeros(nb_max, P.numel(), dtype=torch.float32, device=dev),
                         partial=torch.zeros(n_steps, nb_max * 4, dtype=torch.float64, device=dev),
@@ -386,7 +399,8 @@ class PPO(nn.Module):
         return plan
 
     def _grad_step_steps(self, pb: dict, idx: torch.Tensor, adv_stats, step_dev: torch.Tensor | None = None, *, plan: dict,
-                         partial: torch.Tensor, image: torch.Tensor | None, scalars: torch.Tensor | None = None):
+                         partial: torch.Tensor, image: torch.Tensor | None, scalars: torch.Tensor | None = None,
+                         packed: torch.Tensor | None = None):
         """One gradient step of the fused 64-wide net: forward, loss and backward into the slabs in ONE launch, then the
         optimizer.  A generator: a data-parallel replica YIELDS the flat gradient (scaled by 1 / world) where it has to be
         summed over the ranks and continues with Adam once the caller has reduced it in place (`drive_steps`: one
@@ -396,14 +410,14 @@ class PPO(nn.Module):
         partials.  step_dev: the device-resident optimizer step count (captured sequences), None = the host counter.
         image: the padded parameter image the kernel reads, None = read `flat` itself (the first step of a captured
         sequence: the image may be stale).  scalars: where the step's 4 loss statistics go; None = deferred (see
-        `_minibatch_plan`)."""
+        `_minibatch_plan`).  packed: this minibatch's rows in `plan["packed"]` (None: read through idx)."""
         P, gs = self.net.flat.data, self._grad_sync
         M = idx.numel()
         nb = ops.ppo_update_grid(M)
         ops.ppo_update_fused(P, pb["obs"], pb["act"], pb["logp_old"], pb["adv"], pb["ret"], self._cfg, self.net.n_act,
                              self.net.hidden, adv_stats=adv_stats, v_s_old=pb["v_s"] if self.value_clip else None, perm=idx,
                              image=image, M=M, n_blocks=nb, slabs=plan["slabs"][:nb], partial=partial, scalars=scalars,
-                             want_scalars=scalars is not None, opt_step_dev=step_dev)
+                             want_scalars=scalars is not None, opt_step_dev=step_dev, packed=packed)
         if step_dev is None:
             self.opt_step += 1
         grads = plan["slabs"][:nb]
@@ -431,8 +445,8 @@ class PPO(nn.Module):
         ids = self._sample_ids(pb, agent)
         n = ids.numel() if ids is not None else pb["obs"].shape[0]
         dev = self.device
-        plan = self._minibatch_plan(n, batch_size, repeat, defer=False)
-        bounds, mb_start = plan["bounds"], plan["mb_start"]
+        plan = self._minibatch_plan(n, batch_size, repeat, defer=False, pack_reps=1)
+        bounds, mb_start, pk = plan["bounds"], plan["mb_start"], plan["packed"]
         scal = torch.zeros(plan["n_steps"], 4, dtype=torch.float32, device=dev)
         k = 0
         for step in range(repeat):
@@ -443,12 +457,17 @@ class PPO(nn.Module):
             else:
                 perm_local = self._device_perm(n, perm_base, agent, repeat, step)
             perm = perm_local if ids is None else ids[perm_local]
-            stats = (ops.ppo_adv_stats(pb["adv"], mb_start, perm=perm, max_rows=plan["max_rows"])
-                     if self.advantage_normalization else None)
+            if pk is not None:  # (every pass re-packs in its statistics launch: recompute_advantage's new values ride along)
+                stats = ops.ppo_pack_minibatches(pk, pb["adv"], mb_start, perm, pb["obs"], pb["act"], pb["logp_old"], pb["ret"],
+                                                 pb["v_s"] if self.value_clip else None)
+            else:
+                stats = (ops.ppo_adv_stats(pb["adv"], mb_start, perm=perm, max_rows=plan["max_rows"])
+                         if self.advantage_normalization else None)
             self._global_adv_stats(stats, mb_start)
             for j, (s, e) in enumerate(bounds):
                 yield from self._grad_step_steps(pb, perm[s:e], None if stats is None else stats[j], plan=plan,
-                                                 partial=plan["partial"], image=self.net.image, scalars=scal[k])
+                                                 partial=plan["partial"], image=self.net.image, scalars=scal[k],
+                                                 packed=None if pk is None else pk["rows"](j))
                 k += 1
         self.param_version += 1
         if self._grad_sync is not None:
@@ -472,6 +491,10 @@ class PPO(nn.Module):
         ops.policy_forward(P, obs, A, H, mode="given", act=act)
         st = ops.ppo_adv_stats(z + torch.arange(32, device=dev), torch.tensor([0, 32], device=dev))
         slabs, _ = ops.ppo_update_fused(P, obs, act, z, z, z, self._cfg, A, H, adv_stats=st[0], v_s_old=z)
+        pk = ops.ppo_pack_workspace([32], D, dev)
+        ops.ppo_pack_minibatches(pk, z, torch.tensor([0, 32], device=dev), None, obs, act, z, z)
+        ops.ppo_update_fused(P, obs, act, z, z, z, self._cfg, A, H, adv_stats=st[0], v_s_old=z, image=self.net.image.clone(),
+                             packed=pk["rows"](0))
         ops.adam_step(P, slabs, torch.zeros_like(P), torch.zeros_like(P), 1, max_grad_norm=self.max_grad_norm,
                       work=self._adam_work)
         ops.gae_lanes(z.view(32, 1), z.view(32, 1), z.view(32, 1), act.view(32, 1).to(torch.uint8),
@@ -536,12 +559,14 @@ class PPO(nn.Module):
         # (the rollout's stored V(obs_next) is that of the TRUE next observation: not what an ignore_obs_next buffer hands out)
         stored = buffer.vnext_store is not None and buffer.policy_outputs_version == self.param_version and not no_next
         key = ("graph", buffer.storage_key(), T, batch_size, repeat, self.dispatch, self.max_grad_norm, stored,
-               self._grad_sync is not None, self.graph_collectives, ops.kernel_options())
+               self._grad_sync is not None, self.graph_collectives, ops.kernel_options(), self.pack_rows)
         g = self._ws.get(key)
         P, A, H = self.net.flat.data, self.net.n_act, self.net.hidden
         if g is None:
             self._warm_kernels(buffer)
-            w = self._minibatch_plan(n_g, batch_size, len(groups) * repeat, defer=True)
+            # (recompute_advantage changes adv / returns / v_s between the passes: its steps keep reading through the permutation)
+            w = self._minibatch_plan(n_g, batch_size, len(groups) * repeat, defer=True,
+                                     pack_reps=0 if self.recompute_adv else len(groups) * repeat)
             bounds, n_steps = w["bounds"], w["n_steps"]
             f = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)  # noqa: E731
             w.update(perm=torch.zeros(len(groups), repeat, n_g, dtype=torch.int64, device=dev),
@@ -601,7 +626,12 @@ class PPO(nn.Module):
                                             scale=N if per_agent else 1, group_size=repeat,
                                             offset_mul=1 if per_agent else 0, out=w["perm"])
                 preprocess()
-                if "mb_start_all" in w:
+                if "mb_start_all" in w and w["packed"] is not None:
+                    ops.ppo_pack_minibatches(w["packed"], w["adv"], w["mb_start_all"], w["perm"].view(-1), obs, act, w["logp"],
+                                             w["ret"].view(-1), w["v_s"].view(-1) if self.value_clip else None,
+                                             out=w["stats"].view(-1, 2))
+                    yield from self._global_adv_stats_steps(w["stats"].view(-1, 2), w["mb_start_all"])
+                elif "mb_start_all" in w:
                     ops.ppo_adv_stats(w["adv"], w["mb_start_all"], perm=w["perm"].view(-1), out=w["stats"].view(-1, 2),
                                       max_rows=w["max_rows"])
                     yield from self._global_adv_stats_steps(w["stats"].view(-1, 2), w["mb_start_all"])
@@ -620,7 +650,8 @@ class PPO(nn.Module):
                         for j, (s, e) in enumerate(bounds):
                             yield from self._grad_step_steps(
                                 pb, perm[s:e], w["stats"][gi, r, j] if self.advantage_normalization else None, w["step_dev"],
-                                plan=w, partial=w["partial"][k], image=self.net.image if k > 0 else None)  # k == 0: image may be stale
+                                plan=w, partial=w["partial"][k], image=self.net.image if k > 0 else None,  # k == 0: image may be stale
+                                packed=None if w["packed"] is None else w["packed"]["rows"](k))
                             k += 1
                 # (the 4 loss statistics of every gradient step are folded from w["partial"] by ONE launch after the
                 # replay, straight into the pinned slot the host will read)

@@ -64,6 +64,12 @@ static inline hipError_t tsm_allow_max_lds(const void *kernel) {
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Packed minibatch rows (written once per update by tsm_ppo_pack_minibatches, read by tsm_ppo_update_fused_packed): ONE record per
+// 16-row tile, tiles in order within a minibatch, a record = X[16][D] | act[16] (i32) | logp_old[16] | adv[16] | returns[16] |
+// v_old[16] in 4-byte words -- 16 D + 80 of them, a multiple of 16 B.  Rows past the end of a ragged last tile hold zeros.
+constexpr int kPackRows = 16;
+__host__ __device__ constexpr int pack_rec_words(int D) { return kPackRows * D + 5 * kPackRows; }
+
 // Stage a row-major global matrix (rows_ok x cols_ok, row pitch src_ld) into an LDS array of n_dst floats laid out in rows of
 // `ld` floats; everything outside the matrix is zeroed.  EIGHT loads per thread are in flight before the first LDS store: the
 // plain `for (e = tid; ...) lds[e] = src[...]` form of this loop pays one memory round trip per iteration (the compiler cannot

@@ -577,13 +577,15 @@ __device__ __forceinline__ float column_sum(const float *col, int ld) {
     return s;
 }
 
-template <int H, int NET, int ST, bool PUB = false>
+// PK: the minibatch's rows come from `packed` (common.h: pack_rec_words; tile t's record is packed + t * pack_rec_words(D)) instead of
+// through `perm`: the host picks these instantiations when it has the records AND the weight image.
+template <int H, int NET, int ST, bool PUB = false, bool PK = false>
 __device__ __forceinline__ void ppo_update_net(
     float *lds, const float *__restrict__ P, const float *__restrict__ img, const Dims &d, const float *__restrict__ obs,
     const int32_t *__restrict__ act, const float *__restrict__ logp_old, const float *__restrict__ adv,
     const float *__restrict__ returns, const float *__restrict__ v_s_old, const int64_t *__restrict__ perm, int64_t first,
     int64_t M, const float *__restrict__ adv_stats, const LossCfg &cfg, float *__restrict__ slabs,
-    double *__restrict__ loss_partial, long long *stamps) {
+    double *__restrict__ loss_partial, long long *stamps, const float *__restrict__ packed = nullptr) {
     // diagnostics (tsm_debug_set_stamps, >= 2048 slots): [16 + 24 NET + k] = phase k of workgroup (0, NET);
     // [1024 + 2 (b + 256 NET)], [.. + 1] = start / end of workgroup (b, NET)   (tools/stamp_update.py)
 #define NSTAMP(k) do { if (stamps && blockIdx.x == 0 && threadIdx.x == 0) stamps[16 + 24 * NET + (k)] = (long long)wall_clock64(); } while (0)
@@ -614,12 +616,42 @@ __device__ __forceinline__ void ppo_update_net(
             rin.v_old = on && cfg.value_clip ? vo_ : 0.f;
         }
     };
+    // The same inputs from tile t's packed record: nothing depends on a row id, so all of it is ONE batch of loads.  xr[] and rin get
+    // the values the two functions above would hand over (the record's pad rows hold the zeros of their selects).
+    auto prefetch_packed = [&](int64_t t) {
+        const float *rec = packed + t * pack_rec_words(d.D);
+#pragma unroll
+        for (int it = 0; it < kXRegs; ++it) {   // (unconditional loads at a clamped offset + a select)
+            const int e = threadIdx.x + it * NT, r = e / d.ld1, c = e - r * d.ld1;
+            const bool ok = e < R * d.ld1 && c < d.D;
+            const float v = rec[ok ? r * d.D + c : 0];
+            xr[it] = ok ? v : 0.f;
+        }
+        const float *row = rec + R * d.D + (threadIdx.x >> 4);
+        rin.a_idx = 0; rin.adv = 0.f; rin.logp_old = 0.f; rin.ret = 0.f; rin.v_old = 0.f;
+        if (NET == 0) {
+            rin.a_idx = __float_as_int(row[0]); rin.logp_old = row[R]; rin.adv = row[2 * R];
+        } else {
+            rin.ret = row[3 * R];
+            const float vo_ = row[4 * R];
+            rin.v_old = cfg.value_clip ? vo_ : 0.f;
+        }
+    };
     // Two dependent memory round trips in front of the first tile (round 5; five before): (1) the row ids AND the weight image,
     // which depends on nothing, in one batch; (2) the id-dependent gathers.  Loads return in issue order, so the ids -- issued
     // first -- are usable while the image is still in flight.
     // The common case -- a permutation, the weight image, a first tile for every workgroup -- as ONE straight-line sequence: any
     // branch between a load and its first use makes hipcc's wait conservative (it waited for the image before it used the ids).
-    if (perm && img && (int64_t)blockIdx.x < n_tiles) {
+    // PK: ONE round trip -- the tile's record and the weight image in one batch, no row id in front of either.
+    if constexpr (PK) {
+        static_assert(R == kPackRows, "a record is one tile");
+        prefetch_packed(blockIdx.x);   // (no branch in front of it: the host launches at most n_tiles workgroups per net)
+        NetImageRegs<H> wq;
+        const Lay<H> ly_img(d, true);
+        stage_net_image_load<H, NET>(wq, ly_img, d, img);
+        __builtin_amdgcn_sched_barrier(0);
+        stage_net_image_store<H, NET>(lds, wq, ln, d);
+    } else if (perm && img && (int64_t)blockIdx.x < n_tiles) {
         int64_t xs[kXRegs], id0[kXRegs + 1];
         prefetch_tile_ids_load<1>(id0, d, perm, first, (int64_t)blockIdx.x * R, M);
         NetImageRegs<H> wq;
@@ -828,8 +860,11 @@ __device__ __forceinline__ void ppo_update_net(
         NSTAMP(6);
 
         if (t + gridDim.x < n_tiles) {  // next tile's gathers fly under this tile's backward pass
-            prefetch_tile_x(xr, d, obs, perm, first, (t + gridDim.x) * R, M);
-            prefetch_row(row_id((t + gridDim.x) * R));
+            if constexpr (PK) prefetch_packed(t + gridDim.x);
+            else {
+                prefetch_tile_x(xr, d, obs, perm, first, (t + gridDim.x) * R, M);
+                prefetch_row(row_id((t + gridDim.x) * R));
+            }
         }
         // ---- output-layer gradients + dh2 ----
         if (NET == 0) {
@@ -971,24 +1006,24 @@ __device__ __forceinline__ void ppo_update_net(
 // DS: 0 = dimensions from the launch arguments; else the observation width this instantiation is compiled for (5 actions): the
 // headline job's 18 -- its index arithmetic (divisions by ld1 and D, layout offsets) then costs constants instead of ~35-instruction
 // integer divisions and scalar registers.
-template <int H, int ST, int DS, bool PUB = false>
+template <int H, int ST, int DS, bool PUB = false, bool PK = false>
 __global__ __launch_bounds__(NT, 2) void ppo_update_split_kernel(   // (2: waves per SIMD at least -- both nets' workgroups of a tile share a CU)
 
     const float *__restrict__ P, const float *__restrict__ img, Dims d_arg, const float *__restrict__ obs,
     const int32_t *__restrict__ act, const float *__restrict__ logp_old, const float *__restrict__ adv,
     const float *__restrict__ returns, const float *__restrict__ v_s_old, const int64_t *__restrict__ perm, int64_t first,
     int64_t M, const float *__restrict__ adv_stats, LossCfg cfg, float *__restrict__ slabs,
-    double *__restrict__ loss_partial, int64_t *__restrict__ opt_step_dev, long long *stamps) {
+    double *__restrict__ loss_partial, int64_t *__restrict__ opt_step_dev, long long *stamps, const float *__restrict__ packed) {
     extern __shared__ float lds[];
     const Dims d = DS ? dims_const(DS, 5) : d_arg;
     // device-resident optimizer step count (hipGraph replay): bumped here, read by the Adam kernel that follows
     if (opt_step_dev && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *opt_step_dev += 1;
     if (blockIdx.y == 0)
-        ppo_update_net<H, 0, ST, PUB>(lds, P, img, d, obs, act, logp_old, adv, returns, v_s_old, perm, first, M, adv_stats, cfg, slabs,
-                                      loss_partial, stamps);
+        ppo_update_net<H, 0, ST, PUB, PK>(lds, P, img, d, obs, act, logp_old, adv, returns, v_s_old, perm, first, M, adv_stats, cfg,
+                                          slabs, loss_partial, stamps, packed);
     else
-        ppo_update_net<H, 1, ST, PUB>(lds, P, img, d, obs, act, logp_old, adv, returns, v_s_old, perm, first, M, adv_stats, cfg, slabs,
-                                      loss_partial, stamps);
+        ppo_update_net<H, 1, ST, PUB, PK>(lds, P, img, d, obs, act, logp_old, adv, returns, v_s_old, perm, first, M, adv_stats, cfg,
+                                          slabs, loss_partial, stamps, packed);
 }
 
 __global__ __launch_bounds__(256) void update_finalize_kernel(const double *__restrict__ partial, int n_blocks,
@@ -1151,14 +1186,17 @@ TSM_EXPORT int tsm_ppo_update_grid(int64_t M, int32_t max_blocks) {
     return (int)g;
 }
 
-TSM_EXPORT int tsm_ppo_update_fused(const float *params, const float *param_image, int32_t obs_dim, int32_t hidden,
-                                    int32_t n_act,
-                                    const float *obs, const int32_t *act, const float *logp_old, const float *adv,
-                                    const float *returns, const float *v_s_old, const int64_t *perm,
-                                    int64_t first_row, int64_t M, const float *adv_stats,
-                                    const tsm_ppo_cfg *cfg_host, int32_t n_blocks, float *grad_slabs_out,
-                                    double *loss_partial_out, float *scalars_out, int64_t *opt_step_dev,
-                                    void *stream) {
+// `packed` (nullable): the minibatch's rows as tile records (tsm_ppo_pack_minibatches).  perm / first_row still describe the same
+// rows: whoever cannot use the records -- no weight image (the first step of a captured update), the both-nets kernel, the slab-store
+// and kernel-A diagnostics -- reads through them as before, and gets the same bits.
+TSM_EXPORT int tsm_ppo_update_fused_packed(const float *params, const float *param_image, int32_t obs_dim, int32_t hidden,
+                                           int32_t n_act,
+                                           const float *obs, const int32_t *act, const float *logp_old, const float *adv,
+                                           const float *returns, const float *v_s_old, const int64_t *perm,
+                                           int64_t first_row, int64_t M, const float *adv_stats,
+                                           const tsm_ppo_cfg *cfg_host, int32_t n_blocks, float *grad_slabs_out,
+                                           double *loss_partial_out, float *scalars_out, int64_t *opt_step_dev,
+                                           const float *packed, void *stream) {
     Dims d;
     if (int rc = make_dims(obs_dim, hidden, n_act, &d)) return rc;
     TSM_REQUIRE(M >= 1, "tsm_ppo_update_fused: M must be >= 1");
@@ -1194,19 +1232,24 @@ TSM_EXPORT int tsm_ppo_update_fused(const float *params, const float *param_imag
         const LayN<64> ln(d);
         hipLaunchKernelGGL((ppo_update_split_kernel<64, 0, 18, true>), dim3((unsigned)n_blocks, 2), dim3(NT),
                            (size_t)ln.total * sizeof(float), st, params, param_image, d, obs, act, logp_old, adv, returns,
-                           v_s_old, perm, first_row, M, adv_stats, cfg, grad_slabs_out, loss_partial_out, opt_step_dev, g_tsm_stamps);
+                           v_s_old, perm, first_row, M, adv_stats, cfg, grad_slabs_out, loss_partial_out, opt_step_dev, g_tsm_stamps,
+                           (const float *)nullptr);
     } else if (g_update_variant == 0) {
         // one net per workgroup (grid.y = actor | critic): see ppo_update_split_kernel
         const LayN<64> ln(d);
         const bool spec = d.A == 5 && !tsm_opt(TSM_OPT_GENERIC);   // ("generic_kernels": the generic instantiation)
+        const bool pk = packed && param_image && g_slab_store == 0;
         auto kern = g_slab_store == 1 ? ppo_update_split_kernel<64, 1, 0>
                     : g_slab_store == 2 ? ppo_update_split_kernel<64, 2, 0>
-                    : (spec && d.D == 18) ? ppo_update_split_kernel<64, 0, 18>     // BASELINE configs[1] (simple_spread, N = 3)
-                    : (spec && d.D == 16) ? ppo_update_split_kernel<64, 0, 16>     // configs[4] (simple_tag 3 v 1)
-                    : ppo_update_split_kernel<64, 0, 0>;
+                    : (spec && d.D == 18) ? (pk ? ppo_update_split_kernel<64, 0, 18, false, true>
+                                                : ppo_update_split_kernel<64, 0, 18>)   // BASELINE configs[1] (simple_spread, N = 3)
+                    : (spec && d.D == 16) ? (pk ? ppo_update_split_kernel<64, 0, 16, false, true>
+                                                : ppo_update_split_kernel<64, 0, 16>)   // configs[4] (simple_tag 3 v 1)
+                    : pk ? ppo_update_split_kernel<64, 0, 0, false, true> : ppo_update_split_kernel<64, 0, 0>;
         hipLaunchKernelGGL(kern, dim3((unsigned)n_blocks, 2), dim3(NT),
                            (size_t)ln.total * sizeof(float), st, params, param_image, d, obs, act, logp_old, adv, returns,
-                           v_s_old, perm, first_row, M, adv_stats, cfg, grad_slabs_out, loss_partial_out, opt_step_dev, g_tsm_stamps);
+                           v_s_old, perm, first_row, M, adv_stats, cfg, grad_slabs_out, loss_partial_out, opt_step_dev, g_tsm_stamps,
+                           pk ? packed : nullptr);
     } else {  // both nets in one workgroup (update variant 1: an A/B reference, tools/ab_update_variant.py)
         hipLaunchKernelGGL((ppo_update_kernel<64>), dim3((unsigned)n_blocks), dim3(NT), shmem, st, params, param_image, d,
                            obs, act,
@@ -1220,6 +1263,19 @@ TSM_EXPORT int tsm_ppo_update_fused(const float *params, const float *param_imag
         TSM_LAUNCH_CHECK();
     }
     return TSM_OK;
+}
+
+TSM_EXPORT int tsm_ppo_update_fused(const float *params, const float *param_image, int32_t obs_dim, int32_t hidden,
+                                    int32_t n_act,
+                                    const float *obs, const int32_t *act, const float *logp_old, const float *adv,
+                                    const float *returns, const float *v_s_old, const int64_t *perm,
+                                    int64_t first_row, int64_t M, const float *adv_stats,
+                                    const tsm_ppo_cfg *cfg_host, int32_t n_blocks, float *grad_slabs_out,
+                                    double *loss_partial_out, float *scalars_out, int64_t *opt_step_dev,
+                                    void *stream) {
+    return tsm_ppo_update_fused_packed(params, param_image, obs_dim, hidden, n_act, obs, act, logp_old, adv, returns, v_s_old, perm,
+                                       first_row, M, adv_stats, cfg_host, n_blocks, grad_slabs_out, loss_partial_out, scalars_out,
+                                       opt_step_dev, nullptr, stream);
 }
 
 // Loss statistics of many gradient steps in ONE launch (the per-step finalize of tsm_ppo_update_fused is

@@ -19,12 +19,12 @@ namespace {
 // the plain strided order in both passes.
 constexpr int kStatRegs = 8;
 
-__global__ __launch_bounds__(1024) void adv_stats_kernel(const float *__restrict__ adv,
-                                                         const int64_t *__restrict__ perm,
-                                                         const int64_t *__restrict__ mb_start,
-                                                         float *__restrict__ stats_out) {
+// (minibatch `mb` on the calling 1024-thread workgroup: the body of adv_stats_kernel, shared with adv_stats_pack_rows_kernel)
+__device__ __forceinline__ void adv_stats_block(const float *__restrict__ adv, const int64_t *__restrict__ perm,
+                                                const int64_t *__restrict__ mb_start, float *__restrict__ stats_out,
+                                                const unsigned mb) {
     __shared__ double sm[1024 / 64];
-    const int64_t s0 = mb_start[blockIdx.x], s1 = mb_start[blockIdx.x + 1];
+    const int64_t s0 = mb_start[mb], s1 = mb_start[mb + 1];
     const int64_t M = s1 - s0;
     int64_t src[kStatRegs];
     float vals[kStatRegs];
@@ -54,8 +54,51 @@ __global__ __launch_bounds__(1024) void adv_stats_kernel(const float *__restrict
     }
     const double ss = block_sum<double, 1024>(acc, sm);
     if (threadIdx.x == 0) {
-        stats_out[2 * blockIdx.x + 0] = (float)mean;
-        stats_out[2 * blockIdx.x + 1] = M > 1 ? (float)sqrt(ss / (double)(M - 1)) : NAN;  // torch.std
+        stats_out[2 * mb + 0] = (float)mean;
+        stats_out[2 * mb + 1] = M > 1 ? (float)sqrt(ss / (double)(M - 1)) : NAN;  // torch.std
+    }
+}
+
+__global__ __launch_bounds__(1024) void adv_stats_kernel(const float *__restrict__ adv,
+                                                         const int64_t *__restrict__ perm,
+                                                         const int64_t *__restrict__ mb_start,
+                                                         float *__restrict__ stats_out) {
+    adv_stats_block(adv, perm, mb_start, stats_out, blockIdx.x);
+}
+
+// ---- the statistics AND the minibatches' rows, packed, in one launch: grid (n_mb, 1 + chunks) ----
+// The permutation is fixed for the whole update, yet every workgroup of every gradient step resolved it again: row ids from `perm`,
+// then -- a second, dependent memory round trip in front of its first MFMA -- the gathers of obs, act, logp_old, adv, returns, v_s_old.
+// Here that chain is walked ONCE per update, off the gradient steps' critical path: workgroup (k, 0) computes minibatch k's statistics
+// exactly as adv_stats_kernel does (the same code), workgroup (k, 1 + c) writes the records (common.h: pack_rec_words) of tiles
+// 4c .. 4c + 3 of minibatch k -- 64 rows, 16 lanes a row: lane j copies obs columns j, j + 16, ...; lanes 0-4 one of the five scalars.
+// Minibatch k's records start at record tile_start[k] (the host knows the bounds).  No barrier on the packing side.
+__global__ __launch_bounds__(1024) void adv_stats_pack_rows_kernel(
+    const float *__restrict__ adv, const int64_t *__restrict__ perm, const int64_t *__restrict__ mb_start,
+    float *__restrict__ stats_out, const float *__restrict__ obs, int D, const int32_t *__restrict__ act,
+    const float *__restrict__ logp_old, const float *__restrict__ returns, const float *__restrict__ v_old,
+    const int64_t *__restrict__ tile_start, float *__restrict__ packed) {
+    if (blockIdx.y == 0) {
+        if (stats_out) adv_stats_block(adv, perm, mb_start, stats_out, blockIdx.x);
+        return;
+    }
+    const int64_t s0 = mb_start[blockIdx.x], M = mb_start[blockIdx.x + 1] - s0;
+    const int64_t i = (int64_t)(blockIdx.y - 1) * (1024 / 16) + (threadIdx.x >> 4);   // row of the minibatch, pad rows included
+    if (i >= (M + kPackRows - 1) / kPackRows * kPackRows) return;                      // (so M >= 1 below)
+    const int j = threadIdx.x & 15, r = (int)(i & (kPackRows - 1));
+    const bool on = i < M;
+    const int64_t at = s0 + (on ? i : M - 1);      // (unconditional loads at a clamped row + selects, as the update kernels do)
+    const int64_t id = perm ? perm[at] : at;
+    float *rec = packed + (tile_start[blockIdx.x] + i / kPackRows) * pack_rec_words(D);
+    for (int c = j; c < D; c += 16) {
+        const float v = obs[id * D + c];
+        rec[r * D + c] = on ? v : 0.f;
+    }
+    if (j < 5) {
+        float v;
+        if (j == 0) v = __int_as_float(act[id]);
+        else v = (j == 1 ? logp_old : j == 2 ? adv : j == 3 ? returns : v_old)[id];
+        rec[kPackRows * D + j * kPackRows + r] = on ? v : 0.f;
     }
 }
 
@@ -351,6 +394,27 @@ TSM_EXPORT int tsm_ppo_adv_stats(const float *adv, const int64_t *perm, const in
     TSM_REQUIRE(adv && mb_start && stats_out, "tsm_ppo_adv_stats: null pointer");
     hipLaunchKernelGGL(adv_stats_kernel, dim3((unsigned)n_mb), dim3(1024), 0, tsm_stream(stream), adv, perm,
                        mb_start, stats_out);
+    TSM_LAUNCH_CHECK();
+    return TSM_OK;
+}
+
+TSM_EXPORT int64_t tsm_ppo_packed_record_elems(int32_t obs_dim) { return obs_dim >= 1 ? pack_rec_words(obs_dim) : -1; }
+
+TSM_EXPORT int tsm_ppo_pack_minibatches(const float *adv, const int64_t *perm, const int64_t *mb_start, int32_t n_mb,
+                                        int64_t max_rows, float *stats_out, const float *obs, int32_t obs_dim,
+                                        const int32_t *act, const float *logp_old, const float *returns, const float *v_old,
+                                        const int64_t *tile_start, float *packed_out, void *stream) {
+    TSM_REQUIRE(n_mb >= 0 && max_rows >= 0 && obs_dim >= 1, "tsm_ppo_pack_minibatches: bad sizes n_mb=%d max_rows=%lld obs_dim=%d",
+                n_mb, (long long)max_rows, obs_dim);
+    if (n_mb == 0) return TSM_OK;
+    TSM_REQUIRE(adv && mb_start && obs && act && logp_old && returns && v_old && tile_start && packed_out,
+                "tsm_ppo_pack_minibatches: null pointer");
+    // (one statistics workgroup per minibatch holds 8192 rows in registers: longer minibatches take tsm_ppo_adv_stats_wide and `perm`)
+    TSM_REQUIRE(max_rows <= kStatChunk, "tsm_ppo_pack_minibatches: minibatches of up to %lld rows (got max_rows = %lld)",
+                (long long)kStatChunk, (long long)max_rows);
+    const int64_t chunks = ceil_div(ceil_div(max_rows > 0 ? max_rows : 1, kPackRows) * kPackRows, 1024 / 16);
+    hipLaunchKernelGGL(adv_stats_pack_rows_kernel, dim3((unsigned)n_mb, (unsigned)(1 + chunks)), dim3(1024), 0, tsm_stream(stream),
+                       adv, perm, mb_start, stats_out, obs, obs_dim, act, logp_old, returns, v_old, tile_start, packed_out);
     TSM_LAUNCH_CHECK();
     return TSM_OK;
 }

@@ -306,6 +306,60 @@ def ppo_adv_stats(adv, mb_start, perm=None, out=None, max_rows: int = 0, work=No
     return stats
 
 
+def ppo_packed_record_elems(obs_dim: int) -> int:
+    """4-byte words of one packed 16-row tile record (include/tsmarl.h: tsm_ppo_pack_minibatches)."""
+    return call("tsm_ppo_packed_record_elems", int(obs_dim))
+
+
+def ppo_pack_workspace(sizes, obs_dim: int, device) -> dict:
+    """Where `ppo_pack_minibatches` puts the rows of minibatches of `sizes` rows (host ints, in launch order), allocated once:
+    `packed` [records, record words] f32, `tile_start` (device i64, first record of each minibatch) and the same on the host
+    (`tile_start_host`, one entry more: the total).  `rows(k)` is minibatch k's slice of `packed`, the `packed=` argument of
+    `ppo_update_fused`."""
+    sizes = [int(m) for m in sizes]
+    if not sizes or min(sizes) < 1 or max(sizes) > 8192:
+        raise ValueError(f"ppo_pack_workspace: minibatches of 1..8192 rows (got {sizes[:4]}...)")
+    starts = [0]
+    for m in sizes:
+        starts.append(starts[-1] + (m + 15) // 16)
+    ws = dict(sizes=sizes, obs_dim=int(obs_dim), max_rows=max(sizes), tile_start_host=starts,
+              tile_start=torch.as_tensor(starts[:-1], dtype=torch.int64, device=device),
+              packed=torch.zeros(starts[-1], ppo_packed_record_elems(obs_dim), dtype=torch.float32, device=device))
+    ws["rows"] = lambda k: ws["packed"][starts[k]:starts[k + 1]]
+    return ws
+
+
+def ppo_pack_minibatches(ws: dict, adv, mb_start, perm, obs, act, logp_old, returns, v_old=None, out=None, stats=True):
+    """`ppo_adv_stats` of every minibatch AND the minibatches' rows gathered into `ws` (`ppo_pack_workspace`) in ONE launch:
+    the gradient steps then read their 16-row tiles as contiguous records instead of chasing `perm` (`ppo_update_fused(packed=)`).
+    v_old: v_s_old when the loss clips the value (None: the returns, which the kernel then ignores).  stats=False: rows only.
+    Returns the statistics [n_mb, 2] (None without)."""
+    adv = _chk(adv, torch.float32, "adv").reshape(-1)
+    obs = _chk(obs, torch.float32, "obs")
+    mb_start = _chk(mb_start, torch.int64, "mb_start")
+    n_mb = mb_start.numel() - 1
+    if n_mb != len(ws["sizes"]) or obs.shape[-1] != ws["obs_dim"]:
+        raise ValueError(f"ppo_pack_minibatches: the workspace was made for {len(ws['sizes'])} minibatches of obs_dim "
+                         f"{ws['obs_dim']}, got {n_mb} and {obs.shape[-1]}")
+    n = obs.numel() // obs.shape[-1]
+    returns = _chk(returns, torch.float32, "returns")
+    v_old = returns if v_old is None else _chk(v_old, torch.float32, "v_old")
+    for name, t in (("adv", adv), ("act", act), ("logp_old", logp_old), ("returns", returns), ("v_old", v_old)):
+        if t.numel() != n:
+            raise ValueError(f"ppo_pack_minibatches: {name} holds {t.numel()} values for {n} rows of obs")
+    if perm is not None and _chk(perm, torch.int64, "perm").numel() < sum(ws["sizes"]):
+        raise ValueError(f"ppo_pack_minibatches: perm holds {perm.numel()} row ids, the minibatches {sum(ws['sizes'])}")
+    st = None
+    if stats:
+        st = out if out is not None else torch.empty(n_mb, 2, dtype=torch.float32, device=adv.device)
+        if st.numel() < 2 * n_mb:
+            raise ValueError(f"ppo_pack_minibatches: out holds {st.numel()} values, {n_mb} minibatches need {2 * n_mb}")
+    call("tsm_ppo_pack_minibatches", ptr(adv), ptr(perm), ptr(mb_start), n_mb, ws["max_rows"], ptr(st), ptr(obs), ws["obs_dim"],
+         ptr(_chk(act, torch.int32, "act")), ptr(_chk(logp_old, torch.float32, "logp_old")), ptr(returns), ptr(v_old),
+         ptr(ws["tile_start"]), ptr(ws["packed"]), stream_ptr())
+    return st
+
+
 def ppo_adv_stats_pack(stats, mb_start, out=None):
     """This rank's per-minibatch (mean, unbiased std) + row counts -> f64 [n_mb, 3] = (n, sum x, sum x^2): the additive
     form one all-reduce sums over data-parallel ranks (parallel.GradSync.merge_adv_stats_)."""
@@ -531,8 +585,10 @@ def ppo_update_grid(M: int, max_blocks: int = 0) -> int:
 
 def ppo_update_fused(params, obs, act, logp_old, adv, returns, cfg: tsm_ppo_cfg, n_act: int, hidden: int = 64,
                      adv_stats=None, v_s_old=None, perm=None, first_row=0, M=None, n_blocks=None,
-                     slabs=None, partial=None, scalars=None, opt_step_dev=None, image=None, want_scalars=True):
-    """One PPO gradient step up to the gradients -> (grad_slabs[n_blocks, P], scalars[4])."""
+                     slabs=None, partial=None, scalars=None, opt_step_dev=None, image=None, want_scalars=True, packed=None):
+    """One PPO gradient step up to the gradients -> (grad_slabs[n_blocks, P], scalars[4]).
+    packed: the minibatch's rows as tile records (`ppo_pack_workspace(...)["rows"](k)`, written by `ppo_pack_minibatches` from
+    these arrays and this perm) -- read instead of perm's rows when `image` is given; same bits."""
     obs = _chk(obs, torch.float32, "obs")
     D = obs.shape[-1]
     if M is None:
@@ -553,11 +609,18 @@ def ppo_update_fused(params, obs, act, logp_old, adv, returns, cfg: tsm_ppo_cfg,
         raise ValueError(f"ppo_update_fused: perm holds {perm.numel()} row ids, M = {M}")
     if scalars is None and want_scalars:
         scalars = torch.empty(4, dtype=torch.float32, device=dev)
-    call("tsm_ppo_update_fused", ptr(_chk(params, torch.float32, "params")), ptr(image), D, hidden, n_act, ptr(obs),
-         ptr(_chk(act, torch.int32, "act")), ptr(_chk(logp_old, torch.float32, "logp_old")),
-         ptr(_chk(adv, torch.float32, "adv")), ptr(_chk(returns, torch.float32, "returns")), ptr(v_s_old),
-         ptr(perm), first_row, M, ptr(adv_stats), C.byref(cfg), n_blocks, ptr(slabs), ptr(partial), ptr(scalars),
-         ptr(opt_step_dev), stream_ptr())
+    args = (ptr(_chk(params, torch.float32, "params")), ptr(image), D, hidden, n_act, ptr(obs),
+            ptr(_chk(act, torch.int32, "act")), ptr(_chk(logp_old, torch.float32, "logp_old")),
+            ptr(_chk(adv, torch.float32, "adv")), ptr(_chk(returns, torch.float32, "returns")), ptr(v_s_old),
+            ptr(perm), first_row, M, ptr(adv_stats), C.byref(cfg), n_blocks, ptr(slabs), ptr(partial), ptr(scalars),
+            ptr(opt_step_dev))
+    if packed is None:
+        call("tsm_ppo_update_fused", *args, stream_ptr())
+        return slabs, scalars
+    need = (M + 15) // 16 * ppo_packed_record_elems(D)
+    if _chk(packed, torch.float32, "packed").numel() < need:  # the kernel reads ceil(M / 16) records: never launch onto fewer
+        raise ValueError(f"ppo_update_fused: packed holds {packed.numel()} words, {M} rows of width {D} need {need}")
+    call("tsm_ppo_update_fused_packed", *args, ptr(packed), stream_ptr())
     return slabs, scalars
 
 

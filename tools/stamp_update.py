@@ -16,11 +16,14 @@ st = torch.zeros(2048, dtype=torch.int64, device=dev)
 lib = _abi.load(); lib.tsm_debug_set_stamps.argtypes = [ctypes.c_void_p]; lib.tsm_debug_set_stamps(st.data_ptr())
 import numpy as np
 names = ["prologue (ids + image, gathers, image -> LDS)", "commit X", "L1", "L2", "L3", "loss head", "dW3 / dH2", "dW2 / dH1", "dW1", "slab stores", "loss sums"]
-for label, pm in (("perm gather", perm),):
+ws = ops.ppo_pack_workspace([M], D, dev)
+ops.ppo_pack_minibatches(ws, adv, torch.tensor([0, M], device=dev), perm, obs, act, logp, ret)
+for label, pk in (("perm gather", None), ("packed records", ws["rows"](0))):
     for _ in range(3000):   # (the stamps kept are the last launch's: the clock the part settles to under this load)
-        ops.ppo_update_fused(P, obs, act, logp, adv, ret, cfg, A, H, adv_stats=stats[0], perm=pm, M=M, image=net.image)
+        ops.ppo_update_fused(P, obs, act, logp, adv, ret, cfg, A, H, adv_stats=stats[0], perm=perm, M=M, image=net.image, packed=pk)
     torch.cuda.synchronize()
     s = st.cpu().numpy()
+    print(f"-- rows through: {label}")
     for net_i, nm in ((0, "actor"), (1, "critic")):
         b = s[16 + 24 * net_i: 16 + 24 * net_i + 12]
         print(f"workgroup (0, {nm}): " + ", ".join(f"{names[k]} {(b[k + 1] - b[k]) / 100.0:.2f}" for k in range(11)) + f"; total {(b[11] - b[0]) / 100.0:.2f} us")
