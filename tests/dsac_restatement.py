@@ -18,33 +18,34 @@ import torch
 from dqn_restatement import DqnRestatement
 
 
-def categorical(logits):
-    x = np.asarray(logits, np.float64)
+def categorical(logits, dtype=np.float64):
+    x = np.asarray(logits, dtype)
     mx = x.max(-1, keepdims=True)
     ln = x - (mx + np.log(np.exp(x - mx).sum(-1, keepdims=True)))
     p = np.exp(ln)
-    H = -(np.maximum(ln, np.finfo(np.float64).min) * p).sum(-1)
+    H = -(np.maximum(ln, np.finfo(dtype).min) * p).sum(-1)
     return p, ln, H
 
 
-def target(logits_next, q1, q2, alpha, mc, gpow, vmask) -> np.ndarray:
-    p, _, H = categorical(logits_next)
-    tq = (p * np.minimum(np.asarray(q1, np.float64), np.asarray(q2, np.float64))).sum(-1) + float(alpha) * H
-    return tq * np.asarray(vmask, bool) * np.asarray(gpow, np.float64) + np.asarray(mc, np.float64)
+def target(logits_next, q1, q2, alpha, mc, gpow, vmask, dtype=np.float64) -> np.ndarray:
+    """`dtype`: the precision every step runs in (float64: the yardstick; float32: what the reference's own run costs)."""
+    p, _, H = categorical(logits_next, dtype)
+    tq = (p * np.minimum(np.asarray(q1, dtype), np.asarray(q2, dtype))).sum(-1) + dtype(alpha) * H
+    return tq * np.asarray(vmask, bool).astype(dtype) * np.asarray(gpow, dtype) + np.asarray(mc, dtype)
 
 
-def critic_head(q1, q2, act, returns, weight=None) -> dict:
-    q1, q2, ret = (np.asarray(v, np.float64) for v in (q1, q2, returns))
+def critic_head(q1, q2, act, returns, weight=None, dtype=np.float64) -> dict:
+    q1, q2, ret = (np.asarray(v, dtype) for v in (q1, q2, returns))
     B = q1.shape[0]
     rows, a = np.arange(B), np.asarray(act, np.int64)
-    w = np.ones(B) if weight is None else np.asarray(weight, np.float64)
+    w = np.ones(B, dtype) if weight is None else np.asarray(weight, dtype)
     out = {}
     for k, q in ((1, q1), (2, q2)):
         td = q[rows, a] - ret
         d = np.zeros_like(q)
-        d[rows, a] = 2.0 * td * w / B
+        d[rows, a] = dtype(2.0) * td * w / dtype(B)
         out.update({f"td{k}": td, f"loss{k}": float((td * td * w).mean()), f"dq{k}": d})
-    out["prio"] = (out["td1"] + out["td2"]) / 2.0
+    out["prio"] = (out["td1"] + out["td2"]) / dtype(2.0)
     return out
 
 
@@ -54,16 +55,16 @@ def actor_loss(logits, q1, q2, alpha) -> float:
     return float(-(float(alpha) * H + (p * q).sum(-1)).mean())
 
 
-def actor_head(logits, q1, q2, alpha) -> dict:
+def actor_head(logits, q1, q2, alpha, dtype=np.float64) -> dict:
     """d loss / d logits[b][j] = p[j] (alpha (ln[j] + H) - (q[j] - V)) / B,  V = sum_a p[a] q[a]:
     dV/dx[j] = p[j] (q[j] - V) and dH/dx[j] = -p[j] (ln[j] + H) from dp[a]/dx[j] = p[a] (1[a = j] - p[j])."""
-    p, ln, H = categorical(logits)
-    q = np.minimum(np.asarray(q1, np.float64), np.asarray(q2, np.float64))
+    p, ln, H = categorical(logits, dtype)
+    q = np.minimum(np.asarray(q1, dtype), np.asarray(q2, dtype))
     V = (p * q).sum(-1)
     B = p.shape[0]
-    d = p * (float(alpha) * (ln + H[:, None]) - (q - V[:, None])) / B
-    return dict(entropy=H, d_logits=d, loss=float(-(float(alpha) * H + V).mean()), mean_entropy=float(H.mean()),
-                gap=float(np.abs(np.asarray(q1, np.float64) - np.asarray(q2, np.float64)).min()))
+    d = p * (dtype(alpha) * (ln + H[:, None]) - (q - V[:, None])) / dtype(B)
+    return dict(entropy=H, d_logits=d, loss=float(-(dtype(alpha) * H + V).mean()), mean_entropy=float(H.mean()),
+                gap=float(np.abs(np.asarray(q1, dtype) - np.asarray(q2, dtype)).min()))
 
 
 def alpha_state(log_alpha: float) -> dict:
