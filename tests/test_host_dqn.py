@@ -86,6 +86,8 @@ def test_entry_points_reject_bad_arguments_without_a_device():
     ops.dqn_check(64, 1)
     assert _abi.call("tsm_dqn_partial_elems", 0) == -1
     assert _abi.call("tsm_dqn_partial_elems", 257) == 2 * 2  # 256 rows per workgroup
+    for B in (1, 256, 257):   # ops.dqn_td_head allocates its partials by _abi.DQN_ROWS_PER_BLOCK
+        assert _abi.call("tsm_dqn_partial_elems", B) == 2 * -(-B // _abi.DQN_ROWS_PER_BLOCK)
 
 
 def test_ops_refuse_cpu_tensors():

@@ -17,6 +17,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "tsmarl.h")
 
 MAX_GATHER_FIELDS = 12  # include/tsmarl.h TSM_MAX_GATHER_FIELDS
 ABI_VERSION = 4  # include/tsmarl.h TSM_ABI_VERSION: bumped whenever a signature or a struct layout changes
+DQN_ROWS_PER_BLOCK = 256  # csrc/dqn.hip: one row per thread of the TD head (tsm_dqn_partial_elems counts by it)
 DISTQ_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_DISTQ_ROWS_PER_BLOCK: rows per workgroup of the C51 / QR-DQN heads
 DSAC_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_DSAC_ROWS_PER_BLOCK: rows per workgroup of the Discrete SAC heads
 IQN_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_IQN_ROWS_PER_BLOCK: rows per workgroup of the IQN head

@@ -18,7 +18,6 @@ from __future__ import annotations
 from collections import OrderedDict
 from typing import Any
 
-import numpy as np
 import torch
 
 from .. import ops
@@ -26,7 +25,7 @@ from ..data.batch import Batch
 from ..data.stats import TrainingStats
 from ..utils.net import FlatMLP
 from ..utils.tensor import to_tensor
-from .dqn import DQN, DiscreteQLearningPolicy, SimpleLossTrainingStats, _obs_rows
+from .dqn import DQN, DiscreteQLearningPolicy, SimpleLossTrainingStats
 from .pg import LossSequenceTrainingStats
 
 
@@ -59,34 +58,13 @@ class _DistributionalPolicy(DiscreteQLearningPolicy):
         """-> (q [R, A], `Batch.logits` [R, A, N])."""
         return self.values(raw), raw.view(-1, self.n_act, self.n_atoms)
 
-    def forward(self, batch: Batch, state: Any = None, model: FlatMLP | None = None) -> Batch:
-        """-> Batch(logits [B, A, N] in HBM, act = the first argmax of the masked value per action (numpy i64), state)."""
-        model = self.model if model is None else model
-        obs, mask = _obs_rows(batch.obs)
-        x = to_tensor(obs, self.device, torch.float32)
-        q, logits = self._logits(FlatMLP.forward(model, x.reshape(-1, model.dims[0]), save=False))
-        m = None if mask is None else to_tensor(np.asarray(mask, bool) if not isinstance(mask, torch.Tensor) else mask,
-                                                 self.device, torch.uint8).reshape(q.shape)
-        act = ops.dqn_egreedy(q, self._zero_dev, 0, mask=m)
-        return Batch(logits=logits, act=act.to(torch.int64).cpu().numpy(), state=state)
+    def _forward_values(self, x: torch.Tensor, model):
+        """`Batch.logits` is [B, A, N] (C51: the probabilities)."""
+        q, logits = self._logits(super()._forward_values(x, model)[0])
+        return q, logits, {}
 
-    def act_device(self, obs: torch.Tensor, out: dict | None = None, offset_dev: torch.Tensor | None = None,
-                   row_offset: int = 0, mask: torch.Tensor | None = None) -> dict:
-        """As `DiscreteQLearningPolicy.act_device`, with tsm_distq_values between the net and tsm_dqn_egreedy."""
-        rows = obs.reshape(-1, self.model.dims[0])
-        R = rows.shape[0]
-        q = self.values(FlatMLP.forward(self.model, rows, save=False))
-        m = None if mask is None else mask.reshape(R, self.n_act)
-        act = ops.dqn_egreedy(q, self._eps_dev, self.seed, offset=self._sample_ctr + row_offset, offset_dev=offset_dev,
-                              mask=m, out=None if out is None else out["act"].view(-1))
-        if offset_dev is None:
-            self._sample_ctr += R
-        if out is not None:
-            out["logp"].zero_()
-            out["value"].zero_()
-            return out
-        z = torch.zeros(R, dtype=torch.float32, device=self.device)
-        return dict(act=act, logp=z, value=z.clone(), q=q)
+    def _act_values(self, rows: torch.Tensor, ctr: int, offset_dev) -> torch.Tensor:
+        return self.values(super()._act_values(rows, ctr, offset_dev))
 
 
 class C51Policy(_DistributionalPolicy):

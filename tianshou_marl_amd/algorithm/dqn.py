@@ -113,16 +113,27 @@ class DiscreteQLearningPolicy(nn.Module):
             logits = logits + (1 - to_tensor(mask, logits.device, logits.dtype)) * min_value
         return logits
 
-    def forward(self, batch: Batch, state: Any = None, model: FlatMLP | None = None) -> Batch:
-        """-> Batch(logits [B, A] in HBM, act = the first argmax of the masked Q (numpy i64), state)."""
+    # The two hooks a subclass overrides: what its network says about rows, as `forward` and `act_device` need it.
+    def _forward_values(self, x: torch.Tensor, model):
+        """x [..., D] in HBM, `model` as `forward` got it (None: the online net)
+        -> (value per action [R, A], `Batch.logits`, further fields of the returned Batch)."""
         model = self.model if model is None else model
-        obs, mask = _obs_rows(batch.obs)
-        x = to_tensor(obs, self.device, torch.float32)
         logits = FlatMLP.forward(model, x.reshape(-1, model.dims[0]), save=False)
+        return logits, logits, {}
+
+    def _act_values(self, rows: torch.Tensor, ctr: int, offset_dev) -> torch.Tensor:
+        """rows [R, D] in HBM, (ctr, offset_dev) the Philox counter of the epsilon draw -> value per action [R, A]."""
+        return FlatMLP.forward(self.model, rows, save=False)
+
+    def forward(self, batch: Batch, state: Any = None, model: FlatMLP | None = None) -> Batch:
+        """-> Batch(logits in HBM ([B, A]; a subclass: its distribution per action), act = the first argmax of the masked
+        value per action (numpy i64), state)."""
+        obs, mask = _obs_rows(batch.obs)
+        q, logits, extra = self._forward_values(to_tensor(obs, self.device, torch.float32), model)
         m = None if mask is None else to_tensor(np.asarray(mask, bool) if not isinstance(mask, torch.Tensor) else mask,
-                                                 self.device, torch.uint8).reshape(logits.shape)
-        act = ops.dqn_egreedy(logits, self._zero_dev, 0, mask=m)
-        return Batch(logits=logits, act=act.to(torch.int64).cpu().numpy(), state=state)
+                                                 self.device, torch.uint8).reshape(q.shape)
+        act = ops.dqn_egreedy(q, self._zero_dev, 0, mask=m)
+        return Batch(logits=logits, act=act.to(torch.int64).cpu().numpy(), state=state, **extra)
 
     def add_exploration_noise(self, act, batch):
         """dqn.py:153-171 on the host RNG: `np.random.rand` for the row coins, then for the candidate actions."""
@@ -142,15 +153,16 @@ class DiscreteQLearningPolicy(nn.Module):
 
     def act_device(self, obs: torch.Tensor, out: dict | None = None, offset_dev: torch.Tensor | None = None,
                    row_offset: int = 0, mask: torch.Tensor | None = None) -> dict:
-        """obs [..., D] in HBM -> act i32 [rows] (the Q-net, then tsm_dqn_egreedy with the epsilon of the current phase);
-        logp, value = 0.  The Philox counter is offset_dev (the env's device tick: captured graphs advance it) or the
-        policy's own."""
+        """obs [..., D] in HBM -> act i32 [rows] (`_act_values`, then tsm_dqn_egreedy with the epsilon of the current
+        phase); logp, value = 0.  The Philox counter is offset_dev (the env's device tick: captured graphs advance it) or
+        the policy's own."""
         rows = obs.reshape(-1, self.model.dims[0])
         R = rows.shape[0]
-        q = FlatMLP.forward(self.model, rows, save=False)
+        ctr = self._sample_ctr + row_offset
+        q = self._act_values(rows, ctr, offset_dev)
         m = None if mask is None else mask.reshape(R, self.n_act)
-        act = ops.dqn_egreedy(q, self._eps_dev, self.seed, offset=self._sample_ctr + row_offset, offset_dev=offset_dev,
-                              mask=m, out=None if out is None else out["act"].view(-1))
+        act = ops.dqn_egreedy(q, self._eps_dev, self.seed, offset=ctr, offset_dev=offset_dev, mask=m,
+                              out=None if out is None else out["act"].view(-1))
         if offset_dev is None:
             self._sample_ctr += R
         if out is not None:
@@ -398,12 +410,15 @@ class DQN(DeviceOffPolicyRows, nn.Module):
         L = self.policy.model.n_layers
         return [f"{prefix}model.model.{2 * i}.{p}" for i in range(L) for p in ("weight", "bias")]
 
+    def _ref_nets(self) -> list:
+        """(prefix, net) of a reference checkpoint: `policy.model.`, then `model_old.module.` with a target network."""
+        return [("policy.model.", self.policy.model)] + ([("model_old.module.", self.model_old)] if self.use_target_network else [])
+
     def to_reference_state_dict(self) -> OrderedDict:
         """The module state_dict of the reference's DQN around a `Net`: `policy.model.*`, then `model_old.module.*` when
         a target network is used (lagged_network.py wraps it in an EvalModeModuleWrapper)."""
         sd = OrderedDict()
-        nets = [("policy.model.", self.policy.model)] + ([("model_old.module.", self.model_old)] if self.use_target_network else [])
-        for prefix, net in nets:
+        for prefix, net in self._ref_nets():
             keys = self._ref_keys(prefix)
             for i in range(net.n_layers):
                 sd[keys[2 * i]] = net.weight(i).detach().clone().cpu()
@@ -412,7 +427,6 @@ class DQN(DeviceOffPolicyRows, nn.Module):
 
     @torch.no_grad()
     def load_reference_state_dict(self, sd) -> None:
-        nets = [("policy.model.", self.policy.model)] + ([("model_old.module.", self.model_old)] if self.use_target_network else [])
-        for prefix, net in nets:
+        for prefix, net in self._ref_nets():
             keys = self._ref_keys(prefix)
             net.load_layers([(sd[keys[2 * i]], sd[keys[2 * i + 1]]) for i in range(net.n_layers)])

@@ -19,7 +19,6 @@ from __future__ import annotations
 from collections import OrderedDict
 from typing import Any
 
-import numpy as np
 import torch
 
 from .. import ops
@@ -27,7 +26,7 @@ from ..data.batch import Batch
 from ..utils.net import ImplicitQuantileNet
 from ..utils.tensor import to_tensor
 from .distq import QRDQN, QRDQNPolicy
-from .dqn import DiscreteQLearningPolicy, _obs_rows
+from .dqn import DiscreteQLearningPolicy
 
 _UPDATE_STREAM = 0x9E3779B97F4A7C15   # added to the seed for the learner's draws: acting and updating never share fractions
 
@@ -89,39 +88,16 @@ class IQNPolicy(QRDQNPolicy):
         q = self.values(logits.transpose(1, 2).contiguous(), logits.shape[2])
         return DiscreteQLearningPolicy.compute_q_value(self, q, mask)
 
-    def forward(self, batch: Batch, state: Any = None, model: ImplicitQuantileNet | None = None) -> Batch:
-        """-> Batch(logits [B, A, S] view in HBM, act = the first argmax of the masked mean (numpy i64), state, taus)."""
-        obs, mask = _obs_rows(batch.obs)
-        x = to_tensor(obs, self.device, torch.float32)
+    def _forward_values(self, x: torch.Tensor, model):
+        """`Batch.logits` is the [B, A, S] view of the net's output; the Batch also carries `taus`."""
         out, taus, S = self.net_forward(x, model=model)
-        q = self.values(out, S)
-        m = None if mask is None else to_tensor(np.asarray(mask, bool) if not isinstance(mask, torch.Tensor) else mask,
-                                                 self.device, torch.uint8).reshape(q.shape)
-        act = ops.dqn_egreedy(q, self._zero_dev, 0, mask=m)
-        return Batch(logits=out.view(-1, S, self.n_act).transpose(1, 2), act=act.to(torch.int64).cpu().numpy(), state=state,
-                     taus=taus)
+        return self.values(out, S), out.view(-1, S, self.n_act).transpose(1, 2), dict(taus=taus)
 
-    def act_device(self, obs: torch.Tensor, out: dict | None = None, offset_dev: torch.Tensor | None = None,
-                   row_offset: int = 0, mask: torch.Tensor | None = None) -> dict:
-        """As `DiscreteQLearningPolicy.act_device`: the net under fresh fractions (tsm_iqn_taus at the counter the epsilon draw
-        uses, under its own key), tsm_iqn_values, tsm_dqn_egreedy."""
-        rows = obs.reshape(-1, self.model.dims[0])
-        R = rows.shape[0]
+    def _act_values(self, rows: torch.Tensor, ctr: int, offset_dev) -> torch.Tensor:
+        """The net under fresh fractions: tsm_iqn_taus at the counter the epsilon draw uses, under its own key."""
         S = self._sample_count(False)
-        ctr = self._sample_ctr + row_offset
         o, _ = self.model.forward(rows, S, save=False, seed=self.seed, offset=ctr, offset_dev=offset_dev)
-        q = self.values(o, S)
-        m = None if mask is None else mask.reshape(R, self.n_act)
-        act = ops.dqn_egreedy(q, self._eps_dev, self.seed, offset=ctr, offset_dev=offset_dev, mask=m,
-                              out=None if out is None else out["act"].view(-1))
-        if offset_dev is None:
-            self._sample_ctr += R
-        if out is not None:
-            out["logp"].zero_()
-            out["value"].zero_()
-            return out
-        z = torch.zeros(R, dtype=torch.float32, device=self.device)
-        return dict(act=act, logp=z, value=z.clone(), q=q)
+        return self.values(o, S)
 
 
 class IQN(QRDQN):
@@ -172,9 +148,6 @@ class IQN(QRDQN):
     def load_state_dict(self, sd, *args, **kwargs):  # type: ignore[override]
         super().load_state_dict(sd, *args, **kwargs)
         self.policy._tau_ctr = int(sd.get("tau_ctr", 0))
-
-    def _ref_nets(self):
-        return [("policy.model.", self.policy.model)] + ([("model_old.module.", self.model_old)] if self.use_target_network else [])
 
     def to_reference_state_dict(self) -> OrderedDict:
         """`tau_hat`, then `policy.model.*` and `model_old.module.*` under ImplicitQuantileNetwork's names."""

@@ -154,6 +154,12 @@ __device__ __forceinline__ T wave_sum(T v) {
     return v;
 }
 
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
+    return v;
+}
+
 // sum over a block of NT threads (NT multiple of 64, <= 1024); result valid in every thread
 template <typename T, int NT>
 __device__ __forceinline__ T block_sum(T v, T *smem /* NT/64 entries */) {

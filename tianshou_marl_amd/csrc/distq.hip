@@ -12,9 +12,9 @@
 // N-float rows in LDS, k = 0 .. N - 1 in order, and never leave the workgroup.  So two runs give the same bits.
 //
 // Per row b, both heads:
-//   a*      = first argmax_a (q_next[b][a] + (1 - mask[b][a]) * mv), mv over the whole q_next tensor (qargmax.h, quirk Q15)
+//   a*      = first argmax_a (q_next[b][a] + (1 - mask[b][a]) * mv), mv over the whole q_next tensor (q_head_dev.h, quirk Q15)
 //   nxt[k]  = raw_next[b][a*][k]                      (the lagged net's output when there is one, else the online net's)
-//   ret(x)  = (float)((double)(x * vmask) * (double)gpow + (double)mc)           (the DQN head's rounding rule, per atom)
+//   ret(x)  = (float)((double)(x * vmask) * (double)gpow + (double)mc)           (tsm_nstep_ret, per atom)
 // C51:     nd = softmax(nxt);  returns[k] = ret(support[k]);  Tz = clamp(returns, v_min, v_max)
 //          m[j] = sum_k clamp(1 - |Tz[k] - z[j]| / dz, 0, 1) nd[k];   p = softmax(raw[b][act]);   ce = -sum_j m[j] log(p[j] + 1e-8)
 //          g[j] = -m[j] / (p[j] + 1e-8);   d raw[b][act][k] = p[k] (g[k] - sum_j g[j] p[j]) w / B;   prio = ce;  q = sum p z
@@ -24,22 +24,15 @@
 // An action outside [0, A) reads nothing: the row's loss, prio and q are NaN and its gradient zero, as in the DQN head.
 // Loss and q leave as per-workgroup f64 partials {sum loss_b w_b, sum q} for tsm_qmix_finalize.
 #include "common.h"
-#include "qargmax.h"
+#include "q_head_dev.h"
 
 namespace {
 constexpr int kZThreads = 256;
 constexpr int kZWaves = kZThreads / kWave;
 constexpr int kZRowsPerWave = TSM_DISTQ_ROWS_PER_BLOCK / kZWaves;
-constexpr int kZMaxA = 64;    // kDMaxA of csrc/dqn.hip: the actions feed tsm_dqn_egreedy
 constexpr int kZMaxN = 256;
 constexpr int kZPer = kZMaxN / kWave;
 static_assert(kZRowsPerWave * kZWaves == TSM_DISTQ_ROWS_PER_BLOCK, "rows per workgroup");
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
-    return v;
-}
 
 // softmax over row[0 .. N) as torch: exp(x - max) / sum.  p[i] belongs to atom lane + 64 i (0 past N).
 __device__ __forceinline__ void wave_softmax(const float *__restrict__ row, int N, int lane, float p[kZPer]) {
@@ -60,12 +53,6 @@ __device__ __forceinline__ void wave_softmax(const float *__restrict__ row, int 
     s = wave_sum(s);
 #pragma unroll
     for (int i = 0; i < kZPer; ++i) p[i] = p[i] / s;
-}
-
-// target_q *= value_mask; returns = target_q * gamma^m + mc in float64, rounded once (algorithm_base.py:796, 1213-1215)
-__device__ __forceinline__ float nstep_ret(float x, bool vm, float gp, float mcv) {
-    const float tm = vm ? x : x * 0.f;
-    return (float)((double)tm * (double)gp + (double)mcv);
 }
 
 __global__ __launch_bounds__(kZThreads) void distq_values_kernel(const float *__restrict__ raw,
@@ -144,7 +131,7 @@ __global__ __launch_bounds__(kZThreads) void distq_head_kernel(
                 for (int i = 0; i < kZPer; ++i) {
                     const int j = lane + kWave * i;
                     if (j < N) {
-                        const float ret = nstep_ret(x[i], vm, gp, mcv);
+                        const float ret = tsm_nstep_ret(x[i], vm, gp, mcv);
                         returns_out[b * N + j] = ret;
                         s_a[w][j] = ret != ret ? ret : fminf(fmaxf(ret, v_min), v_max);   // clamp keeps a NaN
                         s_b[w][j] = nd[i];
@@ -155,7 +142,7 @@ __global__ __launch_bounds__(kZThreads) void distq_head_kernel(
                 for (int i = 0; i < kZPer; ++i) {
                     const int j = lane + kWave * i;
                     if (j < N) {
-                        const float ret = nstep_ret(nrow[j], vm, gp, mcv);
+                        const float ret = tsm_nstep_ret(nrow[j], vm, gp, mcv);
                         returns_out[b * N + j] = ret;
                         s_a[w][j] = ret;
                     }
@@ -203,14 +190,7 @@ __global__ __launch_bounds__(kZThreads) void distq_head_kernel(
                 for (int k = 0; k < N; ++k) {
                     const float tk = s_a[w][k];
 #pragma unroll
-                    for (int i = 0; i < kZPer; ++i) {
-                        const float u = tk - c[i], au = fabsf(u);
-                        const float h = au < 1.f ? 0.5f * u * u : au - 0.5f;
-                        const float kq = fabsf(x[i] - (u <= 0.f ? 1.f : 0.f));
-                        ls[i] += h * kq;
-                        ps[i] += fabsf(h);
-                        gs[i] += kq * (u != u ? u : fminf(fmaxf(u, -1.f), 1.f));
-                    }
+                    for (int i = 0; i < kZPer; ++i) tsm_quantile_huber(tk - c[i], x[i], ls[i], ps[i], gs[i]);
                 }
                 float l = 0.f, pr = 0.f, cm = 0.f;
 #pragma unroll
@@ -245,17 +225,11 @@ __global__ __launch_bounds__(kZThreads) void distq_head_kernel(
         }
         __syncthreads();   // the LDS rows are rewritten by the next row
     }
-    if (lane == 0) { s_red[0][w] = acc_l; s_red[1][w] = acc_q; }
-    __syncthreads();
-    if (t < 2) {
-        double acc = 0.0;
-        for (int k = 0; k < kZWaves; ++k) acc += s_red[t][k];
-        partial[(int64_t)blockIdx.x * 2 + t] = acc;
-    }
+    tsm_store_partials(acc_l, acc_q, t, lane, w, s_red, partial);
 }
 
 int distq_check(const char *who, int32_t A, int32_t N) {
-    TSM_REQUIRE(A >= 1 && A <= kZMaxA, "%s: n_act = %d outside [1, %d]", who, A, kZMaxA);
+    if (int rc = tsm_q_check_act(who, A)) return rc;
     TSM_REQUIRE(N >= 2 && N <= kZMaxN, "%s: n_atoms = %d outside [2, %d]", who, N, kZMaxN);
     return TSM_OK;
 }
@@ -266,8 +240,7 @@ int distq_head(const char *who, const float *raw, const float *q_next, const flo
                const float *aux, int64_t B, int32_t A, int32_t N, double v_min, double v_max, float *returns_out, float *prio,
                float *d_out, double *partial, void *stream) {
     if (int rc = distq_check(who, A, N)) return rc;
-    // B * A * N stays below 2^31 * 256: the row offsets are 64-bit; the bound is that of tsm_dqn_td_head
-    TSM_REQUIRE(B >= 1 && B <= ((int64_t)1 << 31) / kZMaxA, "%s: B = %lld out of range", who, (long long)B);
+    if (int rc = tsm_q_check_rows(who, B)) return rc;   // B * A * N stays below 2^31 * 256: the row offsets are 64-bit
     if (CAT) TSM_REQUIRE(v_min < v_max, "%s: v_max should be larger than v_min, but got v_min=%g and v_max=%g", who, v_min, v_max);
     TSM_REQUIRE(raw && q_next && raw_next && act && mc && gpow && vmask && aux && returns_out && prio && d_out && partial,
                 "%s: null pointer", who);
@@ -285,7 +258,7 @@ TSM_EXPORT int tsm_distq_check(int32_t n_act, int32_t n_atoms) { return distq_ch
 TSM_EXPORT int tsm_distq_values(const float *raw, const float *support, int64_t R, int32_t n_act, int32_t n_atoms,
                                 int categorical, float *q, float *probs, void *stream) {
     if (int rc = distq_check("tsm_distq_values", n_act, n_atoms)) return rc;
-    TSM_REQUIRE(R >= 0 && R <= ((int64_t)1 << 31) / kZMaxA, "tsm_distq_values: R = %lld out of range", (long long)R);
+    TSM_REQUIRE(R >= 0 && R <= ((int64_t)1 << 31) / kQHeadMaxA, "tsm_distq_values: R = %lld out of range", (long long)R);
     TSM_REQUIRE(categorical || !probs, "tsm_distq_values: probabilities belong to the categorical mode");
     if (R == 0) return TSM_OK;
     TSM_REQUIRE(raw && q && (!categorical || support), "tsm_distq_values: null pointer");

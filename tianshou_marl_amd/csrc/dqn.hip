@@ -21,11 +21,10 @@
 // tsm_qmix_finalize turns them into {loss, mean q} in a pinned slot.
 #include "common.h"
 #include "philox.h"
-#include "qargmax.h"
+#include "q_head_dev.h"
 
 namespace {
 constexpr int kDThreads = 256;
-constexpr int kDMaxA = 64;
 
 __global__ __launch_bounds__(kDThreads) void dqn_td_head_kernel(
     const float *__restrict__ q, const float *__restrict__ qn_on, const float *__restrict__ qn_tg,
@@ -38,7 +37,7 @@ __global__ __launch_bounds__(kDThreads) void dqn_td_head_kernel(
     const int t = threadIdx.x, lane = t & (kWave - 1), w = t / kWave;
     const bool masked = is_double && mask_next != nullptr;
 
-    // logits.min() - logits.max() - 1 over the whole tensor (qargmax.h)
+    // logits.min() - logits.max() - 1 over the whole tensor (q_head_dev.h)
     const float mv = masked ? tsm_q_mask_offset<kDThreads>(qn_on, B * A, s_min, s_max) : 0.f;
 
     const int64_t b = (int64_t)blockIdx.x * kDThreads + t;
@@ -55,8 +54,7 @@ __global__ __launch_bounds__(kDThreads) void dqn_td_head_kernel(
             target = qt[0];
             for (int a = 1; a < A; ++a) target = fmaxf(target, qt[a]);
         }
-        const float tm = vmask[b] ? target : target * 0.f;  // target_q *= value_mask (a NaN stays a NaN)
-        const float ret = (float)((double)tm * (double)gpow[b] + (double)mc[b]);
+        const float ret = tsm_nstep_ret(target, vmask[b] != 0, gpow[b], mc[b]);
         const int64_t ac = act[b];
         const bool ok = ac >= 0 && ac < A;  // an action outside [0, A) reads nothing and poisons the loss
         const float qs = ok ? q[b * A + ac] : __builtin_nanf("");
@@ -80,29 +78,11 @@ __global__ __launch_bounds__(kDThreads) void dqn_td_head_kernel(
     }
     p_l = wave_sum(p_l);
     p_q = wave_sum(p_q);
-    if (lane == 0) { s_red[0][w] = p_l; s_red[1][w] = p_q; }
-    __syncthreads();
-    if (t < 2) {
-        double acc = 0.0;
-        for (int k = 0; k < kDThreads / kWave; ++k) acc += s_red[t][k];
-        partial[(int64_t)blockIdx.x * 2 + t] = acc;
-    }
+    tsm_store_partials(p_l, p_q, t, lane, w, s_red, partial);
 }
 
-// Draws of row r are words of Philox4x32-10 at (seed, counter c + r): the coin is word 0; uniform[a] is word a % 4 of the
-// block whose third counter word is 1 + a / 4 (tsm_philox4 keeps that word zero, so these blocks belong to no other site).
-__device__ __forceinline__ void philox4_sub(uint64_t seed, uint64_t counter, uint32_t sub, uint32_t out[4]) {
-    uint32_t c0 = (uint32_t)counter, c1 = (uint32_t)(counter >> 32), c2 = sub, c3 = 0;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        tsm_philox_round(c0, c1, c2, c3, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
+// Draws of row r are words of Philox4x32-10 at (seed, counter c + r): the coin is word 0 of tsm_philox4; uniform[a] is word
+// a % 4 of the block whose third counter word is 1 + a / 4 (philox.h).
 __global__ __launch_bounds__(kDThreads) void dqn_egreedy_kernel(const float *__restrict__ q,
                                                                 const uint8_t *__restrict__ mask, int64_t R, int32_t A,
                                                                 const float *__restrict__ eps_dev, uint64_t seed,
@@ -119,7 +99,7 @@ __global__ __launch_bounds__(kDThreads) void dqn_egreedy_kernel(const float *__r
     if (tsm_u01(bits[0]) < eps) {  // rand_act = (uniform[A] + mask).argmax()   (dqn.py:166-169)
         float best = 0.f;
         for (int a = 0; a < A; ++a) {
-            if ((a & 3) == 0) philox4_sub(seed, c, 1u + (uint32_t)(a >> 2), bits);
+            if ((a & 3) == 0) tsm_philox4_sub(seed, c, 1u + (uint32_t)(a >> 2), bits);
             const float v = tsm_u01(bits[a & 3]) + ((mrow && mrow[a]) ? 1.f : 0.f);
             if (a == 0 || v > best) { best = v; a_sel = a; }
         }
@@ -140,14 +120,10 @@ __global__ __launch_bounds__(kDThreads) void dqn_egreedy_kernel(const float *__r
     act[r] = a_sel;
 }
 
-int dqn_check_act(const char *who, int32_t A) {
-    TSM_REQUIRE(A >= 1 && A <= kDMaxA, "%s: n_act = %d outside [1, %d]", who, A, kDMaxA);
-    return TSM_OK;
-}
 }  // namespace
 
 TSM_EXPORT int tsm_dqn_check(int32_t n_act, int32_t n_step) {
-    if (int rc = dqn_check_act("tsm_dqn_check", n_act)) return rc;
+    if (int rc = tsm_q_check_act("tsm_dqn_check", n_act)) return rc;
     TSM_REQUIRE(n_step >= 1, "tsm_dqn_check: n_step_return_horizon should be greater than 0 but got: %d", n_step);
     return TSM_OK;
 }
@@ -162,11 +138,11 @@ TSM_EXPORT int tsm_dqn_td_head(const float *q, const float *q_next_online, const
                                const uint8_t *vmask, const float *weight, int64_t B, int32_t n_act, int is_double,
                                float huber_delta, float *returns_out, float *td_error, float *dq, double *partial,
                                void *stream) {
-    if (int rc = dqn_check_act("tsm_dqn_td_head", n_act)) return rc;
+    if (int rc = tsm_q_check_act("tsm_dqn_td_head", n_act)) return rc;
     // (With a mask and is_double every workgroup of 256 rows reads all B * n_act logits for the batch-wide offset: B^2 n_act /
     //  256 loads in all -- 16 MB of L2 reads at B = 4096, n_act = 9, but quadratic in B.  The bound below is the index range,
     //  not a promise of speed: a replay batch far beyond 10^5 masked rows wants a reduction launch of its own.)
-    TSM_REQUIRE(B >= 1 && B <= ((int64_t)1 << 31) / kDMaxA, "tsm_dqn_td_head: B = %lld out of range", (long long)B);
+    if (int rc = tsm_q_check_rows("tsm_dqn_td_head", B)) return rc;
     TSM_REQUIRE(q && q_next_online && act && mc && gpow && vmask && returns_out && td_error && dq && partial,
                 "tsm_dqn_td_head: null pointer");
     hipLaunchKernelGGL(dqn_td_head_kernel, dim3((unsigned)ceil_div(B, kDThreads)), dim3(kDThreads), 0, tsm_stream(stream),
@@ -179,7 +155,7 @@ TSM_EXPORT int tsm_dqn_td_head(const float *q, const float *q_next_online, const
 TSM_EXPORT int tsm_dqn_egreedy(const float *q, const uint8_t *mask, int64_t R, int32_t n_act, const float *eps_dev,
                                uint64_t seed, uint64_t offset, const uint64_t *offset_dev, int32_t *act_out,
                                void *stream) {
-    if (int rc = dqn_check_act("tsm_dqn_egreedy", n_act)) return rc;
+    if (int rc = tsm_q_check_act("tsm_dqn_egreedy", n_act)) return rc;
     TSM_REQUIRE(R >= 0, "tsm_dqn_egreedy: R = %lld is negative", (long long)R);
     if (R == 0) return TSM_OK;
     TSM_REQUIRE(q && eps_dev && act_out, "tsm_dqn_egreedy: null pointer");

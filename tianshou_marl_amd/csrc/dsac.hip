@@ -15,7 +15,7 @@
 //    of -inf: finite logits give ln > -104 + (min - max) and a positive or denormal p, so the clamp is never reached and
 //    the kernels do not branch on it.)
 // target:  V = sum_a p[a] min(q1[b][a], q2[b][a]);   tq = V + alpha H;   returns = (float)((double)(tq vmask) gpow + mc)
-//          (the DQN head's rounding rule: numpy's f32 * f64 + f64, rounded once)
+//          (tsm_nstep_ret: numpy's f32 * f64 + f64, rounded once)
 // critics: td_i = q_i[b][act] - returns;   l_i = td_i^2 w;   d q_i[b][act] = 2 td_i w / B;   prio = (td_1 + td_2) / 2
 //          (the reference's sign, the opposite of the DQN head's td_error; a prioritized buffer takes |.|)
 // actor:   loss_b = -(alpha H + V) with q1, q2 constants.  With dp[a]/dx[j] = p[a] (1[a = j] - p[j]):
@@ -26,19 +26,14 @@
 // and distributional heads.  Losses leave as per-workgroup f64 partials in tsm_qmix_mix_td's layout for tsm_qmix_finalize.
 #include "adam_dev.h"
 #include "common.h"
+#include "q_head_dev.h"
 
 namespace {
 constexpr int kSThreads = 256;
 constexpr int kSWaves = kSThreads / kWave;
 constexpr int kSRowsPerWave = TSM_DSAC_ROWS_PER_BLOCK / kSWaves;
-constexpr int kSMaxA = 64;   // kDMaxA of csrc/dqn.hip; one lane per action
+static_assert(kQHeadMaxA <= kWave, "one lane per action");
 static_assert(kSRowsPerWave * kSWaves == TSM_DSAC_ROWS_PER_BLOCK, "rows per workgroup");
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
-    return v;
-}
 
 // Categorical(logits = row): this lane's probability and normalised logit (0 past A), the row's entropy in every lane.
 // exp, log and the sums run in f64.  The f32 forms (expf / logf to about an ulp) are not enough for the alpha step: an
@@ -58,18 +53,6 @@ __device__ __forceinline__ void wave_categorical(const float *__restrict__ row, 
     H = -wave_sum(p * ln);
 }
 
-// the four waves' f64 sums, in wave order, into the workgroup's two partials
-__device__ __forceinline__ void store_partials(double a0, double a1, int t, int lane, int w, double (*s_red)[kSWaves],
-                                               double *__restrict__ partial) {
-    if (lane == 0) { s_red[0][w] = a0; s_red[1][w] = a1; }
-    __syncthreads();
-    if (t < 2) {
-        double acc = 0.0;
-        for (int k = 0; k < kSWaves; ++k) acc += s_red[t][k];
-        partial[(int64_t)blockIdx.x * 2 + t] = acc;
-    }
-}
-
 __global__ __launch_bounds__(kSThreads) void dsac_target_kernel(const float *__restrict__ logits_next,
                                                                 const float *__restrict__ q1, const float *__restrict__ q2,
                                                                 const float *__restrict__ alpha_dev,
@@ -85,10 +68,7 @@ __global__ __launch_bounds__(kSThreads) void dsac_target_kernel(const float *__r
         wave_categorical(logits_next + b * A, A, lane, p, ln, H);
         const float q = lane < A ? fminf(q1[b * A + lane], q2[b * A + lane]) : 0.f;
         const float tq = (float)(wave_sum(p * (double)q) + (double)alpha * H);
-        if (lane == 0) {
-            const float tm = vmask[b] ? tq : tq * 0.f;   // target_q *= value_mask (a NaN stays a NaN)
-            returns_out[b] = (float)((double)tm * (double)gpow[b] + (double)mc[b]);
-        }
+        if (lane == 0) returns_out[b] = tsm_nstep_ret(tq, vmask[b] != 0, gpow[b], mc[b]);
     }
 }
 
@@ -121,7 +101,7 @@ __global__ __launch_bounds__(kSThreads) void dsac_critic_head_kernel(const float
             acc2 += (double)(td2 * td2 * wt);
         }
     }
-    store_partials(acc1, acc2, t, lane, w, s_red, partial);
+    tsm_store_partials(acc1, acc2, t, lane, w, s_red, partial);
 }
 
 __global__ __launch_bounds__(kSThreads) void dsac_actor_head_kernel(const float *__restrict__ logits,
@@ -147,7 +127,7 @@ __global__ __launch_bounds__(kSThreads) void dsac_actor_head_kernel(const float 
             acc_h += H;   // before the rounding to f32: the alpha step reads this sum
         }
     }
-    store_partials(acc_l, acc_h, t, lane, w, s_red, partial);
+    tsm_store_partials(acc_l, acc_h, t, lane, w, s_red, partial);
 }
 
 // AutoAlpha.update on device scalars: one wave.  The mean entropy is formed in f64 from the actor head's partials (lane l takes
@@ -180,16 +160,14 @@ __global__ __launch_bounds__(kWave) void dsac_alpha_step_kernel(const double *__
 }
 
 int dsac_check(const char *who, int32_t A, int32_t n_step) {
-    TSM_REQUIRE(A >= 1 && A <= kSMaxA, "%s: n_act = %d outside [1, %d]", who, A, kSMaxA);
+    if (int rc = tsm_q_check_act(who, A)) return rc;
     TSM_REQUIRE(n_step >= 1, "%s: n_step_return_horizon should be greater than 0 but got: %d", who, n_step);
     return TSM_OK;
 }
 
 int dsac_check_rows(const char *who, int64_t B, int32_t A) {
-    if (int rc = dsac_check(who, A, 1)) return rc;
-    // B * n_act stays below 2^31: the bound of tsm_dqn_td_head
-    TSM_REQUIRE(B >= 1 && B <= ((int64_t)1 << 31) / kSMaxA, "%s: B = %lld out of range", who, (long long)B);
-    return TSM_OK;
+    if (int rc = tsm_q_check_act(who, A)) return rc;
+    return tsm_q_check_rows(who, B);
 }
 
 inline dim3 dsac_grid(int64_t B) { return dim3((unsigned)ceil_div(B, TSM_DSAC_ROWS_PER_BLOCK)); }

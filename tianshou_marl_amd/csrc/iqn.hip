@@ -17,14 +17,14 @@
 // the same bits.
 #include "common.h"
 #include "philox.h"
-#include "qargmax.h"
+#include "q_head_dev.h"
 
 namespace {
 typedef float f4 __attribute__((ext_vector_type(4)));
 
 constexpr int kIThreads = 256;
 constexpr int kIWaves = kIThreads / kWave;
-constexpr int kIMaxA = 64, kIMaxS = 64, kIMaxC = 64, kIMaxH = 512;
+constexpr int kIMaxS = 64, kIMaxC = 64, kIMaxH = 512;
 constexpr int kIRowsPerWave = TSM_IQN_ROWS_PER_BLOCK / kIWaves;
 constexpr int kCosLd = kIMaxC + 2;   // 2 x odd: the operand reads [lane & 15][k + (lane >> 4)] meet no bank twice
 constexpr uint64_t kTauKey = 0x5355415451495F4Eull;   // folded into the seed: a Philox key no epsilon draw uses
@@ -37,8 +37,7 @@ __device__ __forceinline__ float iqn_cos(float tau, int i) {
 }
 
 // ---- tsm_iqn_taus ---------------------------------------------------------------------------------------------------
-// Row r draws at Philox counter c + r under the key seed ^ kTauKey; fraction s is word s % 4 of the block whose third
-// counter word is s / 4.
+// Row r draws at Philox counter c + r under the key seed ^ kTauKey; fraction s is word s % 4 of block s / 4 (philox.h).
 __global__ __launch_bounds__(kIThreads) void iqn_taus_kernel(int64_t R, int32_t S, uint64_t seed, uint64_t offset,
                                                              const uint64_t *__restrict__ offset_dev,
                                                              float *__restrict__ taus) {
@@ -48,16 +47,8 @@ __global__ __launch_bounds__(kIThreads) void iqn_taus_kernel(int64_t R, int32_t 
     const int64_t r = g / per;
     const int q = (int)(g - r * per);
     const uint64_t counter = offset + (offset_dev ? *offset_dev : 0ull) + (uint64_t)r;
-    const uint64_t key = seed ^ kTauKey;
-    uint32_t c0 = (uint32_t)counter, c1 = (uint32_t)(counter >> 32), c2 = (uint32_t)q, c3 = 0;
-    uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        tsm_philox_round(c0, c1, c2, c3, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    const uint32_t bits[4] = {c0, c1, c2, c3};
+    uint32_t bits[4];
+    tsm_philox4_sub(seed ^ kTauKey, counter, (uint32_t)q, bits);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
         if (q * 4 + j < S) taus[r * S + q * 4 + j] = tsm_u01(bits[j]);
@@ -168,12 +159,6 @@ __global__ __launch_bounds__(kIThreads) void iqn_values_kernel(const float *__re
     q[g] = acc / (float)S;
 }
 
-// target_q *= value_mask; returns = target_q * gamma^m + mc in float64, rounded once (algorithm_base.py:796, 1213-1215)
-__device__ __forceinline__ float iqn_nstep_ret(float x, bool vm, float gp, float mcv) {
-    const float tm = vm ? x : x * 0.f;
-    return (float)((double)tm * (double)gp + (double)mcv);
-}
-
 // ---- tsm_iqn_head ----------------------------------------------------------------------------------------------------
 // One wave per row, kIRowsPerWave rows after one another, 4 waves per workgroup (the shape of distq_head_kernel<false>).  Lane
 // i holds online sample i; the N' targets of the row sit in LDS and are walked j = 0 .. N' - 1 in order.
@@ -206,7 +191,7 @@ __global__ __launch_bounds__(kIThreads) void iqn_head_kernel(
             ok = ac >= 0 && ac < A;
             wt = weight ? weight[b] : 1.f;
             if (lane < Np) {
-                const float ret = iqn_nstep_ret(out_next[(b * Np + lane) * A + a_star], vm, gp, mcv);
+                const float ret = tsm_nstep_ret(out_next[(b * Np + lane) * A + a_star], vm, gp, mcv);
                 returns_out[b * Np + lane] = ret;
                 s_ret[w][lane] = ret;
             }
@@ -217,14 +202,7 @@ __global__ __launch_bounds__(kIThreads) void iqn_head_kernel(
             const float c = (in && ok) ? out[(b * N + lane) * A + ac] : 0.f;
             const float tau = in ? taus[b * N + lane] : 0.f;
             float ls = 0.f, ps = 0.f, gs = 0.f;
-            for (int j = 0; j < Np; ++j) {
-                const float u = s_ret[w][j] - c, au = fabsf(u);
-                const float h = au < 1.f ? 0.5f * u * u : au - 0.5f;
-                const float kq = fabsf(tau - (u <= 0.f ? 1.f : 0.f));
-                ls += h * kq;
-                ps += fabsf(h);
-                gs += kq * (u != u ? u : fminf(fmaxf(u, -1.f), 1.f));
-            }
+            for (int j = 0; j < Np; ++j) tsm_quantile_huber(s_ret[w][j] - c, tau, ls, ps, gs);
             l_row = wave_sum(in ? ls : 0.f) / (float)N * wt;
             p_row = wave_sum(in ? ps : 0.f) / (float)N;
             q_row = wave_sum(c) / (float)N;
@@ -248,13 +226,7 @@ __global__ __launch_bounds__(kIThreads) void iqn_head_kernel(
         }
         __syncthreads();   // the LDS rows are rewritten by the next row
     }
-    if (lane == 0) { s_red[0][w] = acc_l; s_red[1][w] = acc_q; }
-    __syncthreads();
-    if (t < 2) {
-        double acc = 0.0;
-        for (int k = 0; k < kIWaves; ++k) acc += s_red[t][k];
-        partial[(int64_t)blockIdx.x * 2 + t] = acc;
-    }
+    tsm_store_partials(acc_l, acc_q, t, lane, w, s_red, partial);
 }
 
 int iqn_check(const char *who, int32_t C, int32_t H, int32_t S, int32_t A) {
@@ -262,8 +234,7 @@ int iqn_check(const char *who, int32_t C, int32_t H, int32_t S, int32_t A) {
     TSM_REQUIRE(H >= 16 && H <= kIMaxH && H % 16 == 0, "%s: embedding_dim = %d is not a multiple of 16 in [16, %d]", who, H,
                 kIMaxH);
     TSM_REQUIRE(S >= 2 && S <= kIMaxS, "%s: sample_size = %d outside [2, %d]", who, S, kIMaxS);
-    TSM_REQUIRE(A >= 1 && A <= kIMaxA, "%s: n_act = %d outside [1, %d]", who, A, kIMaxA);
-    return TSM_OK;
+    return tsm_q_check_act(who, A);
 }
 constexpr int64_t kIMaxRows = ((int64_t)1 << 31) / kIMaxH;   // R * S * H stays inside 64-bit offsets with room; grid.y too
 }  // namespace
@@ -340,7 +311,7 @@ TSM_EXPORT int tsm_iqn_head(const float *out, const float *q_next, const float *
                             float *returns_out, float *prio, float *d_out, double *partial, void *stream) {
     if (int rc = iqn_check("tsm_iqn_head", 4, 16, n_online, n_act)) return rc;
     TSM_REQUIRE(n_target >= 2 && n_target <= kIMaxS, "tsm_iqn_head: target sample_size = %d outside [2, %d]", n_target, kIMaxS);
-    TSM_REQUIRE(B >= 1 && B <= ((int64_t)1 << 31) / kIMaxA, "tsm_iqn_head: B = %lld out of range", (long long)B);
+    if (int rc = tsm_q_check_rows("tsm_iqn_head", B)) return rc;
     TSM_REQUIRE(out && q_next && out_next && taus && act && mc && gpow && vmask && returns_out && prio && d_out && partial,
                 "tsm_iqn_head: null pointer");
     hipLaunchKernelGGL(iqn_head_kernel, dim3((unsigned)ceil_div(B, TSM_IQN_ROWS_PER_BLOCK)), dim3(kIThreads), 0,

@@ -1099,6 +1099,38 @@ def _dev_only(name: str, *tensors) -> None:
             raise RuntimeError(f"{name} needs device (HIP) tensors; there is no CPU path")
 
 
+def _head_args(name: str, B: int, shaped: tuple, per_row: tuple, note: str = "") -> list:
+    """The host checks every value-based head shares.  Each (nm, x, shape, dtype) of `shaped` must have that shape, each
+    (nm, x, dtype) of `per_row` B entries; None is an argument left out.  dtype uint8 also takes bool, viewed as bytes.
+    -> what call(...) needs, as `*map(ptr, args)`: the contiguous tensors, `shaped` then `per_row` (flattened), in the order
+    given.  The list keeps a copy made here alive until the launch is queued."""
+    for nm, x, shape, _ in shaped:
+        if x is not None and tuple(x.shape) != tuple(shape):
+            raise ValueError(f"{name}: {nm} must be {list(shape)}{note}")
+    for nm, x, _ in per_row:
+        if x is not None and x.numel() != B:
+            raise ValueError(f"{name}: {nm} must have {B} entries")
+
+    def conv(nm, x, dtype):
+        if x is None:
+            return None
+        return x.contiguous().view(torch.uint8) if dtype == torch.uint8 and x.dtype == torch.bool else _chk(x, dtype, nm)
+
+    return [conv(nm, x, dt) for nm, x, _, dt in shaped] + \
+           [None if x is None else conv(nm, x, dt).reshape(-1) for nm, x, dt in per_row]
+
+
+def _target_rows(act, mc, gpow, vmask, weight) -> tuple:
+    """The per-row arguments of a head that forms the n-step target itself, in the entry points' order."""
+    return (("act", act, torch.int64), ("mc", mc, torch.float32), ("gpow", gpow, torch.float32),
+            ("vmask", vmask, torch.uint8), ("weight", weight, torch.float32))
+
+
+def _head_partial(B: int, rows_per_block: int, dev) -> torch.Tensor:
+    """f64 [2 * ceil(B / rows_per_block)]: a head's pair of sums per workgroup, for `qmix_finalize`."""
+    return torch.empty(2 * -(-B // rows_per_block), dtype=torch.float64, device=dev)
+
+
 def dqn_check(n_act: int, n_step: int = 1) -> None:
     """The bounds of the DQN kernels (include/tsmarl.h): ValueError naming the limit."""
     call("tsm_dqn_check", int(n_act), int(n_step))
@@ -1141,23 +1173,15 @@ def dqn_td_head(q, q_next_online, q_next_target, act, mc, gpow, vmask, mask_next
     dqn_check(A)
     if B < 1:
         raise ValueError("dqn_td_head: empty batch")
-    for name, x in (("q_next_online", q_next_online), ("q_next_target", q_next_target), ("mask_next", mask_next)):
-        if x is not None and tuple(x.shape) != (B, A):
-            raise ValueError(f"dqn_td_head: {name} must be [{B}, {A}]")
-    for name, x in (("act", act), ("mc", mc), ("gpow", gpow), ("vmask", vmask), ("weight", weight)):
-        if x is not None and x.numel() != B:
-            raise ValueError(f"dqn_td_head: {name} must have {B} entries")
-    u8 = lambda x, n: x.contiguous().view(torch.uint8) if x.dtype == torch.bool else _chk(x, torch.uint8, n)  # noqa: E731
+    args = _head_args("dqn_td_head", B, (("q_next_online", q_next_online, (B, A), torch.float32),
+                                         ("q_next_target", q_next_target, (B, A), torch.float32),
+                                         ("mask_next", mask_next, (B, A), torch.uint8)),
+                      _target_rows(act, mc, gpow, vmask, weight))
     dev = q.device
     out = dict(returns=torch.empty(B, dtype=torch.float32, device=dev), td_error=torch.empty(B, dtype=torch.float32, device=dev),
-               dq=torch.empty(B, A, dtype=torch.float32, device=dev),
-               partial=torch.empty(call("tsm_dqn_partial_elems", B), dtype=torch.float64, device=dev))
-    call("tsm_dqn_td_head", ptr(q), ptr(_chk(q_next_online, torch.float32, "q_next_online")),
-         ptr(None if q_next_target is None else _chk(q_next_target, torch.float32, "q_next_target")),
-         ptr(None if mask_next is None else u8(mask_next, "mask_next")), ptr(_chk(act, torch.int64, "act").reshape(-1)),
-         ptr(_chk(mc, torch.float32, "mc").reshape(-1)), ptr(_chk(gpow, torch.float32, "gpow").reshape(-1)),
-         ptr(u8(vmask, "vmask").reshape(-1)), ptr(None if weight is None else _chk(weight, torch.float32, "weight").reshape(-1)),
-         B, A, int(bool(is_double)), float(huber_delta) if huber_delta is not None else 0.0, ptr(out["returns"]),
+               dq=torch.empty(B, A, dtype=torch.float32, device=dev), partial=_head_partial(B, _abi.DQN_ROWS_PER_BLOCK, dev))
+    call("tsm_dqn_td_head", ptr(q), *map(ptr, args), B, A, int(bool(is_double)),
+         float(huber_delta) if huber_delta is not None else 0.0, ptr(out["returns"]),
          ptr(out["td_error"]), ptr(out["dq"]), ptr(out["partial"]), stream_ptr())
     return out
 
@@ -1171,10 +1195,7 @@ def dqn_egreedy(q, eps_dev, seed: int, offset: int = 0, offset_dev=None, mask=No
         raise ValueError("dqn_egreedy: q must be [R, A]")
     R, A = q.shape
     dqn_check(A)
-    if mask is not None:
-        if tuple(mask.shape) != (R, A):
-            raise ValueError(f"dqn_egreedy: mask must be [{R}, {A}]")
-        mask = mask.contiguous().view(torch.uint8) if mask.dtype == torch.bool else _chk(mask, torch.uint8, "mask")
+    mask, = _head_args("dqn_egreedy", R, (("mask", mask, (R, A), torch.uint8),), ())
     if out is None:
         out = torch.empty(R, dtype=torch.int32, device=q.device)
     elif out.numel() < R or not out.is_contiguous():
@@ -1225,23 +1246,14 @@ def _distq_head(name: str, entry: str, raw, q_next, raw_next, act, mc, gpow, vma
     distq_check(A, N)
     if B < 1:
         raise ValueError(f"{name}: empty batch")
-    for nm, x, shape in (("raw", raw, (B, A * N)), ("raw_next", raw_next, (B, A * N)), ("mask_next", mask_next, (B, A))):
-        if x is not None and tuple(x.shape) != shape:
-            raise ValueError(f"{name}: {nm} must be [{shape[0]}, {shape[1]}] ({aux_name} has {N} entries)")
-    for nm, x in (("act", act), ("mc", mc), ("gpow", gpow), ("vmask", vmask), ("weight", weight)):
-        if x is not None and x.numel() != B:
-            raise ValueError(f"{name}: {nm} must have {B} entries")
-    u8 = lambda x, n: x.contiguous().view(torch.uint8) if x.dtype == torch.bool else _chk(x, torch.uint8, n)  # noqa: E731
+    args = _head_args(name, B, (("raw", raw, (B, A * N), torch.float32), ("q_next", q_next, (B, A), torch.float32),
+                                ("raw_next", raw_next, (B, A * N), torch.float32), ("mask_next", mask_next, (B, A), torch.uint8)),
+                      _target_rows(act, mc, gpow, vmask, weight), note=f" ({aux_name} has {N} entries)")
     dev = raw.device
-    n_blocks = -(-B // _abi.DISTQ_ROWS_PER_BLOCK)
     out = dict(returns=torch.empty(B, N, dtype=torch.float32, device=dev), prio=torch.empty(B, dtype=torch.float32, device=dev),
                d_out=torch.empty(B, A * N, dtype=torch.float32, device=dev),
-               partial=torch.empty(2 * n_blocks, dtype=torch.float64, device=dev))
-    call(entry, ptr(raw), ptr(_chk(q_next, torch.float32, "q_next")), ptr(_chk(raw_next, torch.float32, "raw_next")),
-         ptr(None if mask_next is None else u8(mask_next, "mask_next")), ptr(_chk(act, torch.int64, "act").reshape(-1)),
-         ptr(_chk(mc, torch.float32, "mc").reshape(-1)), ptr(_chk(gpow, torch.float32, "gpow").reshape(-1)),
-         ptr(u8(vmask, "vmask").reshape(-1)), ptr(None if weight is None else _chk(weight, torch.float32, "weight").reshape(-1)),
-         ptr(_chk(aux, torch.float32, aux_name).reshape(-1)), B, A, N, *extra, ptr(out["returns"]), ptr(out["prio"]),
+               partial=_head_partial(B, _abi.DISTQ_ROWS_PER_BLOCK, dev))
+    call(entry, *map(ptr, args), ptr(_chk(aux, torch.float32, aux_name).reshape(-1)), B, A, N, *extra, ptr(out["returns"]), ptr(out["prio"]),
          ptr(out["d_out"]), ptr(out["partial"]), stream_ptr())
     return out
 
@@ -1373,25 +1385,14 @@ def iqn_head(out, q_next, out_next, taus, act, mc, gpow, vmask, mask_next=None, 
     iqn_check(4, 16, Np, A)
     if B < 1:
         raise ValueError("iqn_head: empty batch")
-    for nm, x, shape in (("out", out, (B, N, A)), ("out_next", out_next, (B, Np, A)), ("taus", taus, (B, N)),
-                         ("mask_next", mask_next, (B, A))):
-        if x is not None and tuple(x.shape) != shape:
-            raise ValueError(f"iqn_head: {nm} must be {list(shape)}")
-    for nm, x in (("act", act), ("mc", mc), ("gpow", gpow), ("vmask", vmask), ("weight", weight)):
-        if x is not None and x.numel() != B:
-            raise ValueError(f"iqn_head: {nm} must have {B} entries")
-    u8 = lambda x, n: x.contiguous().view(torch.uint8) if x.dtype == torch.bool else _chk(x, torch.uint8, n)  # noqa: E731
+    args = _head_args("iqn_head", B, (("out", out, (B, N, A), torch.float32), ("q_next", q_next, (B, A), torch.float32),
+                                      ("out_next", out_next, (B, Np, A), torch.float32),
+                                      ("mask_next", mask_next, (B, A), torch.uint8), ("taus", taus, (B, N), torch.float32)),
+                      _target_rows(act, mc, gpow, vmask, weight))
     dev = out.device
-    n_blocks = -(-B // _abi.IQN_ROWS_PER_BLOCK)
     res = dict(returns=torch.empty(B, Np, dtype=torch.float32, device=dev), prio=torch.empty(B, dtype=torch.float32, device=dev),
-               d_out=torch.empty(B, N, A, dtype=torch.float32, device=dev),
-               partial=torch.empty(2 * n_blocks, dtype=torch.float64, device=dev))
-    call("tsm_iqn_head", ptr(_chk(out, torch.float32, "out")), ptr(_chk(q_next, torch.float32, "q_next")),
-         ptr(_chk(out_next, torch.float32, "out_next")), ptr(None if mask_next is None else u8(mask_next, "mask_next")),
-         ptr(_chk(taus, torch.float32, "taus")), ptr(_chk(act, torch.int64, "act").reshape(-1)),
-         ptr(_chk(mc, torch.float32, "mc").reshape(-1)), ptr(_chk(gpow, torch.float32, "gpow").reshape(-1)),
-         ptr(u8(vmask, "vmask").reshape(-1)), ptr(None if weight is None else _chk(weight, torch.float32, "weight").reshape(-1)),
-         B, A, N, Np, ptr(res["returns"]), ptr(res["prio"]), ptr(res["d_out"]), ptr(res["partial"]), stream_ptr())
+               d_out=torch.empty(B, N, A, dtype=torch.float32, device=dev), partial=_head_partial(B, _abi.IQN_ROWS_PER_BLOCK, dev))
+    call("tsm_iqn_head", *map(ptr, args), B, A, N, Np, ptr(res["returns"]), ptr(res["prio"]), ptr(res["d_out"]), ptr(res["partial"]), stream_ptr())
     return res
 
 
@@ -1403,8 +1404,9 @@ def dsac_check(n_act: int, n_step: int = 1) -> None:
     call("tsm_dsac_check", int(n_act), int(n_step))
 
 
-def _dsac_rows(name: str, first, others: tuple, per_row: tuple):
-    """[B, A] of `first`; every tensor of `others` must have that shape, every one of `per_row` B entries."""
+def _dsac_rows(name: str, first, others: dict, per_row: tuple = ()):
+    """[B, A] of `first`; every f32 tensor of `others` must have that shape, every (nm, x, dtype) of `per_row` B entries.
+    -> (B, A, the contiguous tensors of first, others and per_row in that order, as `_head_args`)."""
     first = _chk(first, torch.float32, "logits / q")
     if first.dim() != 2:
         raise ValueError(f"{name}: logits and Q values must be [B, A]")
@@ -1412,17 +1414,7 @@ def _dsac_rows(name: str, first, others: tuple, per_row: tuple):
     dsac_check(A)
     if B < 1:
         raise ValueError(f"{name}: empty batch")
-    for nm, x in others:
-        if x is not None and tuple(x.shape) != (B, A):
-            raise ValueError(f"{name}: {nm} must be [{B}, {A}]")
-    for nm, x in per_row:
-        if x is not None and x.numel() != B:
-            raise ValueError(f"{name}: {nm} must have {B} entries")
-    return first, B, A
-
-
-def _dsac_partial(B: int, dev) -> torch.Tensor:
-    return torch.empty(2 * -(-B // _abi.DSAC_ROWS_PER_BLOCK), dtype=torch.float64, device=dev)
+    return B, A, [first] + _head_args(name, B, tuple((nm, x, (B, A), torch.float32) for nm, x in others.items()), per_row)
 
 
 def dsac_target(logits_next, q1_next_old, q2_next_old, alpha_dev, mc, gpow, vmask):
@@ -1430,14 +1422,11 @@ def dsac_target(logits_next, q1_next_old, q2_next_old, alpha_dev, mc, gpow, vmas
     algorithm_base.py:1213-1215) in one launch.  logits_next [B, A]: the online actor on obs_next[idx_n]; q1_next_old,
     q2_next_old [B, A]: the lagged critics there; alpha_dev f32 [1]; mc, gpow, vmask from nstep_return.  -> returns f32 [B]."""
     _dev_only("dsac_target", logits_next, q1_next_old, q2_next_old, alpha_dev, mc, gpow, vmask)
-    logits_next, B, A = _dsac_rows("dsac_target", logits_next, (("q1_next_old", q1_next_old), ("q2_next_old", q2_next_old)),
-                                   (("mc", mc), ("gpow", gpow), ("vmask", vmask)))
-    vm = vmask.contiguous().view(torch.uint8) if vmask.dtype == torch.bool else _chk(vmask, torch.uint8, "vmask")
+    B, A, args = _dsac_rows("dsac_target", logits_next, dict(q1_next_old=q1_next_old, q2_next_old=q2_next_old),
+                            (("mc", mc, torch.float32), ("gpow", gpow, torch.float32), ("vmask", vmask, torch.uint8)))
     returns = torch.empty(B, dtype=torch.float32, device=logits_next.device)
-    call("tsm_dsac_target", ptr(logits_next), ptr(_chk(q1_next_old, torch.float32, "q1_next_old")),
-         ptr(_chk(q2_next_old, torch.float32, "q2_next_old")), ptr(_chk(alpha_dev, torch.float32, "alpha_dev")),
-         ptr(_chk(mc, torch.float32, "mc").reshape(-1)), ptr(_chk(gpow, torch.float32, "gpow").reshape(-1)), ptr(vm.reshape(-1)),
-         B, A, ptr(returns), stream_ptr())
+    call("tsm_dsac_target", *map(ptr, args[:3]), ptr(_chk(alpha_dev, torch.float32, "alpha_dev")), *map(ptr, args[3:]), B, A,
+         ptr(returns), stream_ptr())
     return returns
 
 
@@ -1447,14 +1436,13 @@ def dsac_critic_head(q1, q2, act, returns, weight=None):
     -> dict(dq1, dq2 [B, A], prio [B] = (td1 + td2) / 2 with td = q[act] - returns, partial f64):
     `qmix_finalize(partial, B, out)` gives {critic1_loss, critic2_loss}."""
     _dev_only("dsac_critic_head", q1, q2, act, returns, weight)
-    q1, B, A = _dsac_rows("dsac_critic_head", q1, (("q2", q2),), (("act", act), ("returns", returns), ("weight", weight)))
+    B, A, args = _dsac_rows("dsac_critic_head", q1, dict(q2=q2), (("act", act, torch.int64), ("returns", returns, torch.float32),
+                                                                  ("weight", weight, torch.float32)))
     dev = q1.device
     out = dict(dq1=torch.empty(B, A, dtype=torch.float32, device=dev), dq2=torch.empty(B, A, dtype=torch.float32, device=dev),
-               prio=torch.empty(B, dtype=torch.float32, device=dev), partial=_dsac_partial(B, dev))
-    call("tsm_dsac_critic_head", ptr(q1), ptr(_chk(q2, torch.float32, "q2")), ptr(_chk(act, torch.int64, "act").reshape(-1)),
-         ptr(_chk(returns, torch.float32, "returns").reshape(-1)),
-         ptr(None if weight is None else _chk(weight, torch.float32, "weight").reshape(-1)), B, A, ptr(out["dq1"]),
-         ptr(out["dq2"]), ptr(out["prio"]), ptr(out["partial"]), stream_ptr())
+               prio=torch.empty(B, dtype=torch.float32, device=dev), partial=_head_partial(B, _abi.DSAC_ROWS_PER_BLOCK, dev))
+    call("tsm_dsac_critic_head", *map(ptr, args), B, A, ptr(out["dq1"]), ptr(out["dq2"]), ptr(out["prio"]), ptr(out["partial"]),
+         stream_ptr())
     return out
 
 
@@ -1464,13 +1452,12 @@ def dsac_actor_head(logits, q1, q2, alpha_dev):
     their steps; alpha_dev f32 [1].  -> dict(entropy [B], d_logits [B, A], partial f64): `qmix_finalize(partial, B, out)`
     gives {actor_loss, mean entropy}."""
     _dev_only("dsac_actor_head", logits, q1, q2, alpha_dev)
-    logits, B, A = _dsac_rows("dsac_actor_head", logits, (("q1", q1), ("q2", q2)), ())
+    B, A, args = _dsac_rows("dsac_actor_head", logits, dict(q1=q1, q2=q2))
     dev = logits.device
     out = dict(entropy=torch.empty(B, dtype=torch.float32, device=dev), d_logits=torch.empty(B, A, dtype=torch.float32, device=dev),
-               partial=_dsac_partial(B, dev))
-    call("tsm_dsac_actor_head", ptr(logits), ptr(_chk(q1, torch.float32, "q1")), ptr(_chk(q2, torch.float32, "q2")),
-         ptr(_chk(alpha_dev, torch.float32, "alpha_dev")), B, A, ptr(out["entropy"]), ptr(out["d_logits"]), ptr(out["partial"]),
-         stream_ptr())
+               partial=_head_partial(B, _abi.DSAC_ROWS_PER_BLOCK, dev))
+    call("tsm_dsac_actor_head", *map(ptr, args), ptr(_chk(alpha_dev, torch.float32, "alpha_dev")), B, A, ptr(out["entropy"]),
+         ptr(out["d_logits"]), ptr(out["partial"]), stream_ptr())
     return out
 
 
