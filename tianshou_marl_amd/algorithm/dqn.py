@@ -28,10 +28,11 @@ from torch import nn
 
 from .. import ops
 from ..data.batch import Batch
-from ..data.stats import ResultRing, TrainingStats, pinned_slot
-from ..utils.net import FlatAdam, FlatMLP
+from ..data.stats import TrainingStats
+from ..utils.learner import act_result, result_slot, sample_counter, slab_workspace
+from ..utils.net import FlatMLP, lagged_copy, ref_layer_keys
 from ..utils.tensor import to_tensor
-from .optim import AdamOptimizerFactory
+from .optim import flat_adam_of
 
 log = logging.getLogger(__name__)
 
@@ -158,19 +159,12 @@ class DiscreteQLearningPolicy(nn.Module):
         the policy's own."""
         rows = obs.reshape(-1, self.model.dims[0])
         R = rows.shape[0]
-        ctr = self._sample_ctr + row_offset
+        ctr = sample_counter(self, R, row_offset, offset_dev)
         q = self._act_values(rows, ctr, offset_dev)
         m = None if mask is None else mask.reshape(R, self.n_act)
         act = ops.dqn_egreedy(q, self._eps_dev, self.seed, offset=ctr, offset_dev=offset_dev, mask=m,
                               out=None if out is None else out["act"].view(-1))
-        if offset_dev is None:
-            self._sample_ctr += R
-        if out is not None:
-            out["logp"].zero_()
-            out["value"].zero_()
-            return out
-        z = torch.zeros(R, dtype=torch.float32, device=self.device)
-        return dict(act=act, logp=z, value=z.clone(), q=q)
+        return act_result(out, act, q=q)
 
 
 class DeviceOffPolicyRows:
@@ -228,6 +222,15 @@ class DeviceOffPolicyRows:
             batch.weight = buffer.batch_weight_device(indices)[0]
         return batch
 
+    @staticmethod
+    def _pop_weight(batch: Batch):
+        """`batch.weight`, taken off the batch, as the heads take it: None, or one weight per row.  A scalar (a batch that did
+        not come from a prioritized buffer) is None when it is 1, else that value for every row."""
+        weight = batch.pop("weight", None) if "weight" in batch else None
+        if weight is not None and not isinstance(weight, (torch.Tensor, np.ndarray)):
+            weight = None if float(weight) == 1.0 else np.full(len(batch.mc), float(weight), np.float32)
+        return weight
+
     def _postprocess_batch(self, batch: Batch, buffer, indices) -> None:
         """Algorithm._postprocess_batch (algorithm_base.py:560-582): a prioritized buffer takes `batch.weight` -- after
         `_update_with_batch` the TD errors, still in HBM -- as the new priorities of `indices`."""
@@ -269,19 +272,7 @@ class DQN(DeviceOffPolicyRows, nn.Module):
         ops.dqn_check(policy.n_act, int(n_step_return_horizon))
         self.policy = policy
         model = policy.model
-        self.lr_scheduler = None
-        if isinstance(optim, AdamOptimizerFactory):
-            kw = optim.adam_kwargs()
-            self.optim = FlatAdam(model, lr=kw["lr"], betas=kw["betas"], eps=kw["adam_eps"], weight_decay=kw["weight_decay"],
-                                  coef64=True)
-            if optim.lr_scheduler_factory is not None:
-                self.lr_scheduler = optim.lr_scheduler_factory.create_scheduler(self.optim)
-        elif isinstance(optim, FlatAdam):
-            if optim.param.data_ptr() != model.flat.data.data_ptr() or optim.param.numel() != model.flat.numel():
-                raise ValueError("DQN: the FlatAdam must step the policy model's own flat parameter vector")
-            self.optim = optim
-        else:
-            raise TypeError(f"DQN: optim must be an AdamOptimizerFactory or a FlatAdam, got {type(optim).__name__}")
+        self.optim, self.lr_scheduler = flat_adam_of(optim, model, "DQN: optim", True, ("factory", "flat"))
         self.gamma = gamma
         self.n_step = int(n_step_return_horizon)
         self.target_update_freq = int(target_update_freq)
@@ -290,20 +281,9 @@ class DQN(DeviceOffPolicyRows, nn.Module):
         self._iter = 0
         self.model_old: FlatMLP | None = None
         if self.use_target_network:
-            # one flat copy viewed by a net of the same shape; its constructor draws from a private generator (seed given)
-            # and the copy overwrites that: the global torch RNG is not drawn from, as the reference's deepcopy draws nothing
-            self.target_flat = model.flat.data.clone()
-            self.model_old = self._lagged_net(model, self.target_flat)
-            self.target_flat.copy_(model.flat.data)
+            self.model_old = lagged_copy(model)
+            self.target_flat = self.model_old.flat.data
         self._ws: dict = {}
-
-    @staticmethod
-    def _lagged_net(model, storage: torch.Tensor):
-        """A net of `model`'s shape over the lagged flat vector: a composite network (`ImplicitQuantileNet`) clones itself."""
-        clone = getattr(model, "clone_over", None)
-        if clone is not None:
-            return clone(storage)
-        return FlatMLP(model.dims, model.act, device=model.flat.device, seed=0, storage=storage)
 
     @property
     def device(self) -> torch.device:
@@ -345,25 +325,19 @@ class DQN(DeviceOffPolicyRows, nn.Module):
         self._periodically_update_lagged_network_weights()
         self._after_lagged_copy(batch)
         dev = self.device
-        weight = batch.pop("weight", None) if "weight" in batch else None
-        if weight is not None and not isinstance(weight, (torch.Tensor, np.ndarray)):
-            weight = None if float(weight) == 1.0 else np.full(len(batch.mc), float(weight), np.float32)
+        weight = self._pop_weight(batch)
         obs, _ = _obs_rows(batch.obs)
         model = self.policy.model
         x = to_tensor(obs, dev, torch.float32).reshape(-1, model.dims[0])
         B = x.shape[0]
         act = to_tensor(batch.act, dev, torch.int64).reshape(-1)
-        w = self._ws.get(B)
-        if w is None:
-            n_split = ops.mlp_n_split(B)
-            w = self._ws[B] = dict(n_split=n_split,
-                                   slabs=torch.empty(n_split, model.flat.numel(), dtype=torch.float32, device=dev))
+        w = slab_workspace(self._ws, B, dev, slabs=model.flat.numel())
         q = self._online_forward(batch, x)
         d_out, partial, returns, prio = self._head(batch, q, act, None if weight is None else
                                                    to_tensor(weight, dev, torch.float32).reshape(-1))
         model.backward(d_out, w["n_split"], slabs=w["slabs"])
         self.optim.step(w["slabs"])
-        slot = ResultRing.of(w, lambda: pinned_slot(2)).take("resolve", wait=False)
+        slot = result_slot(w, 2)
         ops.qmix_finalize(partial, B, slot["h"])
         slot["event"].record()
         batch.returns = returns
@@ -404,29 +378,19 @@ class DQN(DeviceOffPolicyRows, nn.Module):
         self.optim.load_state_dict(sd["optim"])
         self._iter = int(sd["iter"])
 
-    def _ref_keys(self, prefix: str) -> list[str]:
-        """The reference's parameter names of a `Net(hidden_sizes=[...])` Q-network below `prefix`: hidden layer i is
-        `model.model.{2 i}` (Linear, activation, Linear, ...), as is the output layer."""
-        L = self.policy.model.n_layers
-        return [f"{prefix}model.model.{2 * i}.{p}" for i in range(L) for p in ("weight", "bias")]
-
     def _ref_nets(self) -> list:
         """(prefix, net) of a reference checkpoint: `policy.model.`, then `model_old.module.` with a target network."""
         return [("policy.model.", self.policy.model)] + ([("model_old.module.", self.model_old)] if self.use_target_network else [])
 
     def to_reference_state_dict(self) -> OrderedDict:
         """The module state_dict of the reference's DQN around a `Net`: `policy.model.*`, then `model_old.module.*` when
-        a target network is used (lagged_network.py wraps it in an EvalModeModuleWrapper)."""
+        a target network is used (lagged_network.py wraps it in an EvalModeModuleWrapper); the Q-network is a
+        `Net(hidden_sizes=[...])` used whole (`ref_layer_keys`: "body")."""
         sd = OrderedDict()
         for prefix, net in self._ref_nets():
-            keys = self._ref_keys(prefix)
-            for i in range(net.n_layers):
-                sd[keys[2 * i]] = net.weight(i).detach().clone().cpu()
-                sd[keys[2 * i + 1]] = net.bias(i).detach().clone().cpu()
+            net.export_layers(ref_layer_keys(net.n_layers, "body"), prefix, sd)
         return sd
 
-    @torch.no_grad()
     def load_reference_state_dict(self, sd) -> None:
         for prefix, net in self._ref_nets():
-            keys = self._ref_keys(prefix)
-            net.load_layers([(sd[keys[2 * i]], sd[keys[2 * i + 1]]) for i in range(net.n_layers)])
+            net.import_layers(sd, ref_layer_keys(net.n_layers, "body"), prefix)

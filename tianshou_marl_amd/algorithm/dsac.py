@@ -19,17 +19,17 @@ from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Any, Union
 
-import numpy as np
 import torch
 from torch import nn
 
 from .. import ops
 from ..data.batch import Batch
-from ..data.stats import ResultRing, TrainingStats, pinned_slot
-from ..utils.net import FlatAdam, FlatMLP
+from ..data.stats import TrainingStats
+from ..utils.learner import act_result, result_slot, sample_counter, slab_workspace
+from ..utils.net import FlatMLP, lagged_copy, ref_layer_keys
 from ..utils.tensor import to_tensor
 from .dqn import DeviceOffPolicyRows, _obs_rows
-from .optim import AdamOptimizerFactory
+from .optim import AdamOptimizerFactory, flat_adam_of
 
 _NO_MASK = ("action masks are not part of the reference's Discrete SAC (discrete_sac.py builds Categorical(logits) from the "
             "actor's raw output): {what} carries a mask, which would be ignored")
@@ -215,17 +215,11 @@ class DiscreteSACPolicy(nn.Module):
         if mask is not None:
             raise NotImplementedError(_NO_MASK.format(what="act_device"))
         rows = obs.reshape(-1, self.actor.dims[0])
-        R = rows.shape[0]
         logits = FlatMLP.forward(self.actor, rows, save=False)
-        act, logp = ops.categorical_sample(logits, self.seed, offset=self._sample_ctr + row_offset,
+        act, logp = ops.categorical_sample(logits, self.seed, offset=sample_counter(self, rows.shape[0], row_offset, offset_dev),
                                            deterministic=self._deterministic, offset_dev=offset_dev,
                                            out=None if out is None else (out["act"].view(-1), out["logp"].view(-1)))
-        if offset_dev is None:
-            self._sample_ctr += R
-        if out is not None:
-            out["value"].zero_()
-            return out
-        return dict(act=act, logp=logp, value=torch.zeros(R, dtype=torch.float32, device=self.device), logits=logits)
+        return act_result(out, act, logp, logits=logits)
 
 
 # ---- the learner (discrete_sac.py:83-196) -------------------------------------------------------------------------------
@@ -265,38 +259,21 @@ class DiscreteSAC(DeviceOffPolicyRows, nn.Module):
                                  f"{actor.dims[0]} -> {policy.n_act} on {dev}")
         self.policy = policy
         self.critic = critic
-        # critic2 or deepcopy(critic) (td3.py:90): the same weights in storage of its own; like the lagged copies below, the
-        # constructor's draw comes from a private generator and is overwritten, so the global torch RNG is not drawn from
-        self.critic2 = critic2 if critic2 is not None else self._copy_of(critic)
-        self.critic_old = self._copy_of(self.critic)
-        self.critic2_old = self._copy_of(self.critic2)
-        scheds = []
-        self.policy_optim = self._optimizer(actor, policy_optim, "policy_optim", scheds)
-        self.critic_optim = self._optimizer(self.critic, critic_optim, "critic_optim", scheds)
-        self.critic2_optim = self._optimizer(self.critic2, critic2_optim or critic_optim, "critic2_optim", scheds)
+        # critic2 or deepcopy(critic) (td3.py:90): the same weights in storage of its own, made as the lagged copies are
+        self.critic2 = critic2 if critic2 is not None else lagged_copy(critic)
+        self.critic_old = lagged_copy(self.critic)
+        self.critic2_old = lagged_copy(self.critic2)
+        adams = [flat_adam_of(given, net, f"DiscreteSAC: {name}", True, ("factory",)) for name, net, given in (
+            ("policy_optim", actor, policy_optim), ("critic_optim", self.critic, critic_optim),
+            ("critic2_optim", self.critic2, critic2_optim or critic_optim))]
+        (self.policy_optim, self.critic_optim, self.critic2_optim), scheds = zip(*adams)
+        scheds = [s for s in scheds if s is not None]
         self.lr_scheduler = _Schedulers(scheds) if scheds else None
         self.tau, self.gamma = tau, gamma
         self.n_step = self.n_step_return_horizon = int(n_step_return_horizon)
         self.alpha = Alpha.from_float_or_instance(alpha)
         self.alpha.device_scalar(dev)
         self._ws: dict = {}
-
-    @staticmethod
-    def _copy_of(net: FlatMLP) -> FlatMLP:
-        flat = net.flat.data.clone()
-        twin = FlatMLP(net.dims, net.act, device=net.flat.device, seed=0, storage=flat)
-        flat.copy_(net.flat.data)
-        return twin
-
-    @staticmethod
-    def _optimizer(net: FlatMLP, factory, name: str, scheds: list) -> FlatAdam:
-        if not isinstance(factory, AdamOptimizerFactory):
-            raise TypeError(f"DiscreteSAC: {name} must be an AdamOptimizerFactory, got {type(factory).__name__}")
-        kw = factory.adam_kwargs()
-        opt = FlatAdam(net, lr=kw["lr"], betas=kw["betas"], eps=kw["adam_eps"], weight_decay=kw["weight_decay"], coef64=True)
-        if factory.lr_scheduler_factory is not None:
-            scheds.append(factory.lr_scheduler_factory.create_scheduler(opt))
-        return opt
 
     @property
     def device(self) -> torch.device:
@@ -330,9 +307,7 @@ class DiscreteSAC(DeviceOffPolicyRows, nn.Module):
         """Both critics' steps, the actor's step against the updated critics (quirk Q25), the alpha step (Q26), the Polyak
         move of the lagged critics; every statistic lands in one pinned slot, read after the one synchronisation."""
         dev = self.device
-        weight = batch.pop("weight", None) if "weight" in batch else None
-        if weight is not None and not isinstance(weight, (torch.Tensor, np.ndarray)):
-            weight = None if float(weight) == 1.0 else np.full(len(batch.mc), float(weight), np.float32)
+        weight = self._pop_weight(batch)
         obs, mask = _obs_rows(batch.obs)
         if mask is not None:
             raise NotImplementedError(_NO_MASK.format(what="batch.obs"))
@@ -341,11 +316,8 @@ class DiscreteSAC(DeviceOffPolicyRows, nn.Module):
         B = x.shape[0]
         act = to_tensor(batch.act, dev, torch.int64).reshape(-1)
         returns = to_tensor(batch.returns, dev, torch.float32).reshape(-1)
-        w = self._ws.get(B)
-        if w is None:
-            n_split = ops.mlp_n_split(B)
-            slab = lambda net: torch.empty(n_split, net.flat.numel(), dtype=torch.float32, device=dev)  # noqa: E731
-            w = self._ws[B] = dict(n_split=n_split, slabs_a=slab(actor), slabs_c1=slab(self.critic), slabs_c2=slab(self.critic2))
+        w = slab_workspace(self._ws, B, dev, slabs_a=actor.flat.numel(), slabs_c1=self.critic.flat.numel(),
+                           slabs_c2=self.critic2.flat.numel())
         alpha_dev = alpha.device_scalar(dev)
         # critics (discrete_sac.py:162-174)
         q1 = FlatMLP.forward(self.critic, x, save=True)
@@ -363,7 +335,7 @@ class DiscreteSAC(DeviceOffPolicyRows, nn.Module):
         ah = ops.dsac_actor_head(logits, q1a, q2a, alpha_dev)
         actor.backward(ah["d_logits"], w["n_split"], slabs=w["slabs_a"])
         self.policy_optim.step(w["slabs_a"])
-        slot = ResultRing.of(w, lambda: pinned_slot(3, 2)).take("resolve", wait=False)
+        slot = result_slot(w, 3, 2)
         h = slot["h"]   # {critic1_loss, critic2_loss}, {actor_loss, mean entropy}, {alpha_loss, alpha}
         ops.qmix_finalize(ch["partial"], B, h[0])
         auto = isinstance(alpha, AutoAlpha)
@@ -403,24 +375,14 @@ class DiscreteSAC(DeviceOffPolicyRows, nn.Module):
             self.alpha.set_log_alpha(sd["alpha"]["log_alpha"])
             self.alpha.load_adam_state(sd["alpha"])
 
-    @staticmethod
-    def _ref_keys(prefix: str, net: FlatMLP) -> list[str]:
-        """The reference's parameter names of a `DiscreteActor` / `DiscreteCritic` around `Net(hidden_sizes=[...])` below
-        `prefix`: hidden layer i is `preprocess.model.model.{2 i}` (Linear, activation, Linear, ...), the output layer
-        `last.model.0`."""
-        stems = [f"preprocess.model.model.{2 * i}" for i in range(net.n_layers - 1)] + ["last.model.0"]
-        return [f"{prefix}{s}.{p}" for s in stems for p in ("weight", "bias")]
-
     def to_reference_state_dict(self) -> OrderedDict:
         """The module state_dict of the reference's DiscreteSAC: `policy.actor.*`, `critic.*`, `critic_old.module.*`,
         `critic2.*`, `critic2_old.module.*` (lagged_network.py wraps the copies in an EvalModeModuleWrapper), and
-        `alpha._log_alpha` when alpha is auto-tuned."""
+        `alpha._log_alpha` when alpha is auto-tuned.  Every net is a `DiscreteActor` / `DiscreteCritic` around a
+        `Net(hidden_sizes=[...])` (`ref_layer_keys`: "head")."""
         sd = OrderedDict()
         for prefix, net in self._nets():
-            keys = self._ref_keys(prefix, net)
-            for i in range(net.n_layers):
-                sd[keys[2 * i]] = net.weight(i).detach().clone().cpu()
-                sd[keys[2 * i + 1]] = net.bias(i).detach().clone().cpu()
+            net.export_layers(ref_layer_keys(net.n_layers, "head"), prefix, sd)
         if isinstance(self.alpha, AutoAlpha):
             sd["alpha._log_alpha"] = self.alpha._log_alpha.detach().clone().cpu()
         return sd
@@ -428,7 +390,6 @@ class DiscreteSAC(DeviceOffPolicyRows, nn.Module):
     @torch.no_grad()
     def load_reference_state_dict(self, sd) -> None:
         for prefix, net in self._nets():
-            keys = self._ref_keys(prefix, net)
-            net.load_layers([(sd[keys[2 * i]], sd[keys[2 * i + 1]]) for i in range(net.n_layers)])
+            net.import_layers(sd, ref_layer_keys(net.n_layers, "head"), prefix)
         if isinstance(self.alpha, AutoAlpha):
             self.alpha.set_log_alpha(sd["alpha._log_alpha"])

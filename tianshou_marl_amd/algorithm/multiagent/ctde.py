@@ -29,6 +29,7 @@ from torch import nn
 from ... import ops
 from ...data.batch import Batch
 from ...data.stats import LazyDict, ResultRing, pinned_slot, recycle
+from ...utils.learner import act_result, sample_counter
 from ...utils.net import FlatAdam, FlatMLP
 from ...utils.tensor import to_tensor
 
@@ -139,14 +140,9 @@ class CTDEPolicy(nn.Module):
         logits = FlatMLP.forward(self.actor, rows, save=False)
         greedy = bool(getattr(self, "deterministic_eval", False) and not self.is_within_training_step)
         res = (out["act"], out["logp"]) if out is not None else None
-        act, logp = ops.categorical_sample(logits, self.seed, offset=self._sample_ctr + row_offset, deterministic=greedy,
-                                           offset_dev=offset_dev, out=res)
-        if offset_dev is None:
-            self._sample_ctr += rows.shape[0]
-        if out is not None:
-            out["value"].zero_()
-            return out
-        return dict(act=act, logp=logp, value=torch.zeros_like(logp), logits=logits)
+        act, logp = ops.categorical_sample(logits, self.seed, offset=sample_counter(self, rows.shape[0], row_offset, offset_dev),
+                                           deterministic=greedy, offset_dev=offset_dev, out=res)
+        return act_result(out, act, logp, logits=logits)
 
     # ---- fused learn: the stores read in place, 8 launches, no activation ever in HBM ------------------------------
     def _store_path(self, batch: Batch):

@@ -30,9 +30,10 @@ from torch import nn
 
 from ... import ops
 from ...data.batch import Batch
-from ...data.stats import ResultRing, pinned_slot
-from ...utils.net import FlatAdam, FlatMLP
+from ...utils.learner import act_result, result_slot, sample_counter, slab_workspace
+from ...utils.net import FlatMLP, join_nets, lagged_twins, ref_layer_keys
 from ...utils.tensor import to_tensor
+from ..optim import flat_adam_of
 from .ctde import LazyScalars
 
 
@@ -53,29 +54,6 @@ class MADDPGScalars(LazyScalars):
         return self
 
     _force = resolve
-
-
-def _adam_of(optimizers, flat: torch.Tensor, what: str) -> FlatAdam:
-    """None -> FlatAdam(lr 1e-3); a list of torch.optim.Adam with equal hyper-parameters -> taken over.  coef64: the actor
-    loss is a mean over the outputs of the critic that was just stepped, where the one-sided error of the f32 difference
-    1.f - beta2 in the step length shows (include/tsmarl.h: tsm_adam_step_coef64)."""
-    if optimizers is None:
-        return FlatAdam(flat, lr=1e-3, coef64=True)
-    opts = list(optimizers) if isinstance(optimizers, (list, tuple)) else [optimizers]
-    if not opts or not all(isinstance(o, torch.optim.Adam) for o in opts):
-        raise TypeError(f"MADDPGPolicy: {what} must be None or a list of torch.optim.Adam (their hyper-parameters drive the "
-                        "HIP Adam over that half of the joint parameter vector)")
-    hyper = []
-    for o in opts:
-        for g in o.param_groups:
-            if g.get("amsgrad") or g.get("maximize"):
-                raise ValueError(f"MADDPGPolicy: {what}: amsgrad / maximize Adam is not served by the HIP optimizer")
-            hyper.append((float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"]), float(g["weight_decay"])))
-    if any(h != hyper[0] for h in hyper):
-        raise ValueError(f"MADDPGPolicy: {what} differ in their hyper-parameters; one HIP Adam steps the whole half, so lr, "
-                         "betas, eps and weight_decay must agree across the list")
-    lr, betas, eps, wd = hyper[0]
-    return FlatAdam(flat, lr=lr, betas=betas, eps=eps, weight_decay=wd, coef64=True)
 
 
 class MADDPGPolicy(nn.Module):
@@ -118,26 +96,18 @@ class MADDPGPolicy(nn.Module):
         self.clip_actions = bool(kwargs.pop("clip_actions", False))
         self._sample_ctr = 0
         dev = actors[0].flat.device
-        # ONE joint parameter vector: [actor_0 .. actor_{N-1} | critic_0 .. critic_{N-1}]
-        nets = actors + critics
-        self._offs = np.concatenate([[0], np.cumsum([m.flat.numel() for m in nets])]).astype(np.int64).tolist()
-        self.n_actor_params = self._offs[n_agents]
-        self.flat = torch.zeros(self._offs[-1], dtype=torch.float32, device=dev)
-        for k, m in enumerate(nets):
-            view = self.flat[self._offs[k]:self._offs[k + 1]]
-            view.copy_(m.flat.data.to(dev))
-            m.flat = nn.Parameter(view, requires_grad=False)
+        # ONE joint parameter vector: [actor_0 .. actor_{N-1} | critic_0 .. critic_{N-1}], and the targets over a copy of it
+        self.flat, self._offs = join_nets(actors + critics, dev)
+        na = self.n_actor_params = self._offs[n_agents]
         self.actors, self.critics = actors, critics  # plain lists, as upstream: not registered (quirk Q13)
-        # targets: one flat copy viewed by nets of the same shapes; their constructors draw from private generators (seed
-        # given) and the copy overwrites the draw, so the global torch RNG is untouched (the reference deep-copies)
-        self.target_flat = self.flat.clone()
-        targets = [FlatMLP(m.dims, m.act, device=dev, seed=0, storage=self.target_flat[self._offs[k]:self._offs[k + 1]])
-                   for k, m in enumerate(nets)]
+        self.target_flat, targets = lagged_twins(actors + critics, self.flat, self._offs)
         self.target_actors, self.target_critics = targets[:n_agents], targets[n_agents:]
-        self.target_flat.copy_(self.flat)
-        na = self.n_actor_params
-        self.optimizer_actors = _adam_of(optimizer_actors, self.flat[:na], "optimizer_actors")
-        self.optimizer_critics = _adam_of(optimizer_critics, self.flat[na:], "optimizer_critics")
+        # coef64: the actor loss is a mean over the outputs of the critic that was just stepped, where the one-sided error of
+        # the f32 difference 1.f - beta2 in the step length shows (include/tsmarl.h: tsm_adam_step_coef64)
+        self.optimizer_actors, _ = flat_adam_of(optimizer_actors, self.flat[:na], "MADDPGPolicy: optimizer_actors", True,
+                                                ("none", "adams"))
+        self.optimizer_critics, _ = flat_adam_of(optimizer_critics, self.flat[na:], "MADDPGPolicy: optimizer_critics", True,
+                                                 ("none", "adams"))
         self._sigma_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         self.noise_std = float(kwargs.pop("noise_std", 0.0))
         # the Box bounds as device vectors (act_device's clamp)
@@ -185,32 +155,19 @@ class MADDPGPolicy(nn.Module):
         E = rows.shape[0]
         mu = [FlatMLP.forward(self.actors[i], rows[:, i], save=False) for i in range(N)]
         lo, hi = (self._low, self._high) if self.clip_actions else (None, None)
-        act = ops.maddpg_act(mu, self._sigma_dev, self.seed, offset=self._sample_ctr + row_offset, offset_dev=offset_dev,
-                             low=lo, high=hi, out=None if out is None else out["act"])
-        if offset_dev is None:
-            self._sample_ctr += E * N * Ad
-        if out is not None:
-            out["logp"].zero_()
-            out["value"].zero_()
-            return out
-        z = torch.zeros(E * N, dtype=torch.float32, device=self.device)
-        return dict(act=act.view(E * N, Ad), logp=z, value=z.clone(), mu=mu)
+        act = ops.maddpg_act(mu, self._sigma_dev, self.seed, offset=sample_counter(self, E * N * Ad, row_offset, offset_dev),
+                             offset_dev=offset_dev, low=lo, high=hi, out=None if out is None else out["act"])
+        return act_result(out, act, mu=mu)
 
     # ---- learn (ctde.py:817-934) ------------------------------------------------------------------------
     def _workspace(self, B: int) -> dict:
-        w = self._ws.get(B)
-        if w is None:
-            N, W, dev = self.n_agents, self.joint_dim, self.device
-            ns = ops.mlp_n_split(B)
-            na = self.n_actor_params
-            f32 = dict(dtype=torch.float32, device=dev)
-            w = self._ws[B] = dict(
-                n_split=ns, slabs_actor=torch.empty(ns, na, **f32), slabs_critic=torch.empty(ns, self.flat.numel() - na, **f32),
-                x=torch.empty(B, W, **f32), x_next=torch.empty(B, W, **f32), x_pi=torch.empty(N, B, W, **f32),
-                dq=[torch.empty(B, **f32) for _ in range(N)], d_act=[torch.empty(B, self.act_dim, **f32) for _ in range(N)],
-                partial=torch.empty(ops.maddpg_partial_elems(B, N), dtype=torch.float64, device=dev),
-                d_pi=torch.full((B, 1), -1.0 / B, **f32))  # d (-mean Q) / d Q
-        return w
+        N, W, na, dev = self.n_agents, self.joint_dim, self.n_actor_params, self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        return slab_workspace(self._ws, B, dev, slabs_actor=na, slabs_critic=self.flat.numel() - na, more=lambda: dict(
+            x=torch.empty(B, W, **f32), x_next=torch.empty(B, W, **f32), x_pi=torch.empty(N, B, W, **f32),
+            dq=[torch.empty(B, **f32) for _ in range(N)], d_act=[torch.empty(B, self.act_dim, **f32) for _ in range(N)],
+            partial=torch.empty(ops.maddpg_partial_elems(B, N), dtype=torch.float64, device=dev),
+            d_pi=torch.full((B, 1), -1.0 / B, **f32)))  # d (-mean Q) / d Q
 
     def learn(self, batch: Batch, **kwargs: Any) -> dict[str, float]:
         """One MADDPG step for every agent, phase by phase (the agents are independent within a call, see the module
@@ -254,7 +211,7 @@ class MADDPGPolicy(nn.Module):
             self.actors[i].backward(w["d_act"][i], ns, slabs=slabs_a[:, self._offs[i]:], slab_stride=na)
         self.optimizer_actors.step(slabs_a)
         # 10: the 2 N losses into the pinned slot
-        slot = ResultRing.of(w, lambda: pinned_slot(2 * N)).take("resolve", wait=False)
+        slot = result_slot(w, 2 * N)
         ops.maddpg_finalize(partial, q_pi, B, slot["h"])
         slot["event"].record()
         res = MADDPGScalars(slot, N)
@@ -284,11 +241,9 @@ class MADDPGPolicy(nn.Module):
         """Every net under `actors.{i}.fc{k}.weight` style keys (critics, target_actors, target_critics alike)."""
         sd = OrderedDict()
         for prefix, m in self._named_nets():
-            for k, v in m.to_reference_state_dict().items():
-                sd[f"{prefix}.{k}"] = v
+            m.export_layers(ref_layer_keys(m.n_layers, "fc"), prefix + ".", sd)
         return sd
 
-    @torch.no_grad()
     def load_reference_state_dict(self, sd) -> None:
         for prefix, m in self._named_nets():
-            m.load_reference_state_dict({k[len(prefix) + 1:]: v for k, v in sd.items() if k.startswith(prefix + ".")})
+            m.import_layers(sd, ref_layer_keys(m.n_layers, "fc"), prefix + ".")

@@ -25,9 +25,10 @@ from torch import nn
 
 from ... import ops
 from ...data.batch import Batch
-from ...data.stats import ResultRing, pinned_slot
-from ...utils.net import FlatAdam, FlatMLP
+from ...utils.learner import act_result, result_slot, sample_counter, slab_workspace
+from ...utils.net import FlatMLP, join_nets, lagged_twins, ref_layer_keys
 from ...utils.tensor import to_tensor
+from ..optim import flat_adam_of
 from .ctde import LazyScalars
 
 _HYPER = ("hyper_w1", "hyper_w2", "hyper_b1", "hyper_b2")
@@ -67,14 +68,18 @@ class QMIXMixer(nn.Module):
     def nets(self) -> list[FlatMLP]:
         return [getattr(self, k) for k in _HYPER]
 
+    def clone_over(self, storage: torch.Tensor) -> "QMIXMixer":
+        """As `FlatMLP.clone_over`."""
+        return QMIXMixer(self.n_agents, self.state_dim, self.embed_dim, self.hypernet_embed_dim, self.enforce_monotonic,
+                         device=storage.device, seed=0, storage=storage)
+
     def rebind(self, storage: torch.Tensor) -> None:
-        """Move the parameters into `storage` (a slice of a joint vector) and view them there."""
-        storage.copy_(self.flat.data)
+        """Move the parameters into `storage` (a slice of a joint vector) and view them there, hypernetwork by hypernetwork."""
         self.flat = nn.Parameter(storage, requires_grad=False)
         o = 0
         for net in self.nets:
             c = net.flat.numel()
-            net.flat = nn.Parameter(storage[o:o + c], requires_grad=False)
+            net.rebind(storage[o:o + c])
             o += c
 
     def hyper_forward(self, state: torch.Tensor, save: bool = False) -> tuple:
@@ -98,23 +103,22 @@ class QMIXMixer(nn.Module):
         return out.view(B, 1)
 
     # reference module keys (nn.Sequential indices 0 / 2; hyper_b1 is a bare Linear)
-    def _ref_layer_keys(self, name: str) -> list[str]:
-        if name == "hyper_b1":
-            return [""]
-        return ["0.", "2."]
+    @staticmethod
+    def _layer_keys(name: str) -> list[tuple[str, str]]:
+        return [("weight", "bias")] if name == "hyper_b1" else ref_layer_keys(2, "seq")
 
-    def state_dict(self, *args, **kwargs):  # type: ignore[override]
-        sd = OrderedDict()
+    def state_dict(self, *args, destination: OrderedDict | None = None, prefix: str = "", **kwargs):  # type: ignore[override]
+        sd = OrderedDict() if destination is None else destination
         for name, net in zip(_HYPER, self.nets):
-            for i, pre in enumerate(self._ref_layer_keys(name)):
-                sd[f"{name}.{pre}weight"] = net.weight(i).detach().clone().cpu()
-                sd[f"{name}.{pre}bias"] = net.bias(i).detach().clone().cpu()
+            net.export_layers(self._layer_keys(name), f"{prefix}{name}.", sd)
         return sd
 
-    @torch.no_grad()
     def load_state_dict(self, sd, *args, **kwargs):  # type: ignore[override]
+        self._load(sd, "")
+
+    def _load(self, sd, prefix: str) -> None:
         for name, net in zip(_HYPER, self.nets):
-            net.load_layers([(sd[f"{name}.{pre}weight"], sd[f"{name}.{pre}bias"]) for pre in self._ref_layer_keys(name)])
+            net.import_layers(sd, self._layer_keys(name), f"{prefix}{name}.")
 
 
 class QMIXPolicy(nn.Module):
@@ -145,40 +149,13 @@ class QMIXPolicy(nn.Module):
         self.async_stats = bool(kwargs.pop("async_stats", False))
         self._sample_ctr = 0
         dev = mixer.flat.device
-        # ONE joint parameter vector: [actor_0 .. actor_{N-1} | mixer]
-        sizes = [a.flat.numel() for a in actors] + [mixer.flat.numel()]
-        self._offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64).tolist()
-        self.flat = torch.zeros(self._offs[-1], dtype=torch.float32, device=dev)
-        for i, a in enumerate(actors):
-            view = self.flat[self._offs[i]:self._offs[i + 1]]
-            view.copy_(a.flat.data.to(dev))
-            a.flat = nn.Parameter(view, requires_grad=False)
-        mixer.rebind(self.flat[self._offs[n_agents]:])
+        # ONE joint parameter vector: [actor_0 .. actor_{N-1} | mixer], and the targets over a copy of it
+        self.flat, self._offs = join_nets(actors + [mixer], dev)
         self.actors = actors  # a plain list, as upstream: not registered (quirk Q11)
         self.mixer = mixer
-        # targets: one flat copy, viewed by nets of the same shapes.  Their constructors initialise the views from private
-        # generators (seed given), which the copy then overwrites: the global torch RNG is not drawn from, as the
-        # reference's deepcopy draws nothing (a seeded script's later torch.randint / nn.Linear init stays the reference's)
-        self.target_flat = self.flat.clone()
-        self.target_actors = []
-        for i, a in enumerate(actors):
-            t = FlatMLP(a.dims, a.act, device=dev, seed=0, storage=self.target_flat[self._offs[i]:self._offs[i + 1]])
-            self.target_actors.append(t)
-        self.target_mixer = QMIXMixer(n_agents, mixer.state_dim, mixer.embed_dim, mixer.hypernet_embed_dim,
-                                      mixer.enforce_monotonic, device=dev, seed=0,
-                                      storage=self.target_flat[self._offs[n_agents]:])
-        self.target_flat.copy_(self.flat)
-        if optimizer is None:
-            self.optimizer = FlatAdam(self.flat, lr=1e-3)
-        elif isinstance(optimizer, torch.optim.Adam):
-            g = optimizer.param_groups[0]
-            if g.get("amsgrad") or g.get("maximize"):
-                raise ValueError("QMIXPolicy: amsgrad / maximize Adam is not served by the HIP optimizer")
-            self.optimizer = FlatAdam(self.flat, lr=float(g["lr"]), betas=tuple(g["betas"]), eps=float(g["eps"]),
-                                      weight_decay=float(g["weight_decay"]))
-        else:
-            raise TypeError("QMIXPolicy: optimizer must be None or a torch.optim.Adam (its hyper-parameters drive the HIP "
-                            f"Adam over the joint parameter vector), got {type(optimizer).__name__}")
+        self.target_flat, twins = lagged_twins(actors + [mixer], self.flat, self._offs)
+        self.target_actors, self.target_mixer = twins[:-1], twins[-1]
+        self.optimizer, _ = flat_adam_of(optimizer, self.flat, "QMIXPolicy: optimizer", False, ("none", "adam"))
         self._eps_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         self.epsilon = epsilon
         self._ws: dict = {}
@@ -230,16 +207,9 @@ class QMIXPolicy(nn.Module):
         B = rows.shape[0]
         q = [FlatMLP.forward(self.actors[i], rows[:, i], save=False) for i in range(N)]
         act = out["act"].view(B, N) if out is not None else None
-        act = ops.qmix_egreedy(q, self._eps_dev, self.seed, offset=self._sample_ctr + row_offset, offset_dev=offset_dev,
-                               out=act)
-        if offset_dev is None:
-            self._sample_ctr += B * N
-        if out is not None:
-            out["logp"].zero_()
-            out["value"].zero_()
-            return out
-        z = torch.zeros(B * N, dtype=torch.float32, device=self.device)
-        return dict(act=act.view(-1), logp=z, value=z.clone(), q=q)
+        act = ops.qmix_egreedy(q, self._eps_dev, self.seed, offset=sample_counter(self, B * N, row_offset, offset_dev),
+                               offset_dev=offset_dev, out=act)
+        return act_result(out, act.view(-1), q=q)
 
     # ---- learn (ctde.py:618-702) ------------------------------------------------------------------------
     def learn(self, batch: Batch, **kwargs: Any) -> dict[str, float]:
@@ -257,11 +227,7 @@ class QMIXPolicy(nn.Module):
         gsn = self._t(batch.global_obs_next, torch.float32)
         B = obs[0].shape[0]
         P = self.flat.numel()
-        w = self._ws.get(B)
-        if w is None:
-            n_split = ops.mlp_n_split(B)
-            w = self._ws[B] = dict(n_split=n_split,
-                                   slabs=torch.empty(n_split, P, dtype=torch.float32, device=self.device))
+        w = slab_workspace(self._ws, B, self.device, slabs=P)
         q = [FlatMLP.forward(self.actors[i], obs[i], save=True) for i in range(N)]
         qn = [FlatMLP.forward(self.target_actors[i], obs_next[i], save=False) for i in range(N)]
         hyper = self.mixer.hyper_forward(gs, save=True)
@@ -276,7 +242,7 @@ class QMIXPolicy(nn.Module):
             net.backward(d, ns, slabs=slabs[:, o:], slab_stride=P)
             o += net.flat.numel()
         self.optimizer.step(slabs)
-        slot = ResultRing.of(w, lambda: pinned_slot(2)).take("resolve", wait=False)
+        slot = result_slot(w, 2)
         ops.qmix_finalize(partial, B, slot["h"])
         slot["event"].record()
         res = LazyScalars(slot, ("loss", "q_values"))
@@ -293,10 +259,9 @@ class QMIXPolicy(nn.Module):
         """`mixer.*` and `target_mixer.*` only (quirk Q11: the reference's actors live in a plain list)."""
         sd = OrderedDict()
         for name, m in (("mixer", self.mixer), ("target_mixer", self.target_mixer)):
-            for k, v in m.state_dict().items():
-                sd[f"{name}.{k}"] = v
+            m.state_dict(destination=sd, prefix=name + ".")
         return sd
 
     def load_state_dict(self, sd, *args, **kwargs):  # type: ignore[override]
         for name, m in (("mixer", self.mixer), ("target_mixer", self.target_mixer)):
-            m.load_state_dict({k[len(name) + 1:]: v for k, v in sd.items() if k.startswith(name + ".")})
+            m._load(sd, name + ".")

@@ -10,6 +10,9 @@ captured update graph follows the schedule without being re-captured.
 from __future__ import annotations
 
 import numpy as np
+import torch
+
+from ..utils.net import FlatAdam
 
 
 class LambdaLR:
@@ -78,3 +81,49 @@ class AdamOptimizerFactory(OptimizerFactory):
 
     def adam_kwargs(self) -> dict:
         return dict(lr=self.lr, betas=tuple(self.betas), adam_eps=self.eps, weight_decay=self.weight_decay)
+
+
+_ADAM_KINDS = {"none": "None", "factory": "an AdamOptimizerFactory", "flat": "a FlatAdam",
+               "adam": "a torch.optim.Adam (its hyper-parameters drive the HIP Adam over the vector)",
+               "adams": "a list of torch.optim.Adam (their hyper-parameters drive the HIP Adam over the vector)"}
+
+
+def flat_adam_of(given, target, who: str, coef64: bool, kinds: tuple) -> tuple[FlatAdam, LambdaLR | None]:
+    """What a learner's caller passed as optimizer -> (the `FlatAdam` over `target`, a module with `flat` or a vector; its
+    lr scheduler or None).  `kinds`: what this learner accepts, of
+      "none"     None: lr 1e-3, Adam's defaults
+      "factory"  an `AdamOptimizerFactory`: its hyper-parameters, and the scheduler of its scheduler factory
+      "flat"     a `FlatAdam`, used as it is: it must step `target`'s own vector
+      "adam"     a torch.optim.Adam: the hyper-parameters of its `param_groups[0]` are taken over
+      "adams"    one or a list of them: every group of every one must agree, since one HIP Adam steps the whole vector
+    Anything else is a TypeError naming `who`.  `coef64`: `FlatAdam`'s; it decides the bits of every step, per learner."""
+    if isinstance(given, FlatAdam) and "flat" in kinds:
+        param = target.flat.data if hasattr(target, "flat") else target
+        if given.param.data_ptr() != param.data_ptr() or given.param.numel() != param.numel():
+            raise ValueError(f"{who}: the FlatAdam must step the policy model's own flat parameter vector")
+        return given, None
+    groups = None   # of the torch Adams whose hyper-parameters are taken over
+    if isinstance(given, torch.optim.Adam) and "adam" in kinds:
+        groups = given.param_groups[:1]
+    elif given is not None and "adams" in kinds:
+        opts = list(given) if isinstance(given, (list, tuple)) else [given]
+        if opts and all(isinstance(o, torch.optim.Adam) for o in opts):
+            groups = [g for o in opts for g in o.param_groups]
+    if given is None and "none" in kinds:
+        hyper = dict(lr=1e-3)
+    elif isinstance(given, AdamOptimizerFactory) and "factory" in kinds:
+        hyper = dict(lr=given.lr, betas=tuple(given.betas), eps=given.eps, weight_decay=given.weight_decay)
+    elif groups is not None:
+        if any(g.get("amsgrad") or g.get("maximize") for g in groups):
+            raise ValueError(f"{who}: amsgrad / maximize Adam is not served by the HIP optimizer")
+        hypers = [dict(lr=float(g["lr"]), betas=tuple(float(b) for b in g["betas"]), eps=float(g["eps"]),
+                       weight_decay=float(g["weight_decay"])) for g in groups]
+        if any(h != hypers[0] for h in hypers):
+            raise ValueError(f"{who} differ in their hyper-parameters; one HIP Adam steps the whole vector, so lr, betas, eps "
+                             "and weight_decay must agree across the list")
+        hyper = hypers[0]
+    else:
+        raise TypeError(f"{who} must be {' or '.join(_ADAM_KINDS[k] for k in kinds)}, got {type(given).__name__}")
+    opt = FlatAdam(target, coef64=coef64, **hyper)
+    factory = getattr(given, "lr_scheduler_factory", None)
+    return opt, (None if factory is None else factory.create_scheduler(opt))

@@ -28,6 +28,7 @@ from .. import ops
 from ..data.batch import Batch, split_bounds
 from ..data.buffer import DeviceVectorReplayBuffer
 from ..data.stats import ResultRing, lazy_training_stats, pinned_slot, training_stats_from_steps
+from ..utils.learner import act_result, sample_counter
 from ..utils.net import FlatMLP, MLPActorCritic
 from ..utils.tensor import to_tensor
 from .ppo import PPO, ref_order_rows
@@ -155,14 +156,11 @@ class GenericPPO(PPO):
         value = self._values(rows, joint)
         greedy = bool(self.deterministic_eval and not self.is_within_training_step)
         res = (out["act"], out["logp"]) if out is not None else None
-        act, logp = ops.categorical_sample(logits, self.seed, offset=self._sample_ctr + row_offset, deterministic=greedy,
-                                           offset_dev=offset_dev, out=res)
-        if offset_dev is None:
-            self._sample_ctr += rows.shape[0]
+        act, logp = ops.categorical_sample(logits, self.seed, offset=sample_counter(self, rows.shape[0], row_offset, offset_dev),
+                                           deterministic=greedy, offset_dev=offset_dev, out=res)
         if out is not None:
             out["value"].copy_(value)
-            return out
-        return dict(act=act, logp=logp, value=value, logits=logits)
+        return act_result(out, act, logp, value, logits=logits)
 
     # ---- update side ------------------------------------------------------------------------------------------------
     def _preprocess_batch(self, buffer: DeviceVectorReplayBuffer, uniform_T: int | None = None,

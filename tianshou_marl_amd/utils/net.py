@@ -20,6 +20,18 @@ from torch import nn
 from .. import ops
 
 
+def ref_layer_keys(n_layers: int, scheme: str) -> list[tuple[str, str]]:
+    """[(weight key, bias key)] per layer of a `FlatMLP` under the names the reference's modules give its parameters:
+      "body"  a `Net(hidden_sizes=[...])` used whole: `model.model.{2 i}` (Linear, activation, Linear, ...)
+      "head"  such a `Net` under a DiscreteActor / DiscreteCritic: `preprocess.model.model.{2 i}`, the output `last.model.0`
+      "fc"    the CTDE nets (ctde.py:362-364, 398-400): `fc{i + 1}`
+      "seq"   a bare `nn.Sequential` of Linear and activation: `{2 i}`"""
+    stems = {"body": [f"model.model.{2 * i}" for i in range(n_layers)],
+             "head": [f"preprocess.model.model.{2 * i}" for i in range(n_layers - 1)] + ["last.model.0"],
+             "fc": [f"fc{i + 1}" for i in range(n_layers)], "seq": [str(2 * i) for i in range(n_layers)]}[scheme]
+    return [(s + ".weight", s + ".bias") for s in stems]
+
+
 def _layer_shapes(obs_dim: int, hidden: int, n_out: int):
     return [("w0", (hidden, obs_dim)), ("b0", (hidden,)), ("w1", (hidden, hidden)), ("b1", (hidden,)),
             ("w2", (n_out, hidden)), ("b2", (n_out,))]
@@ -82,40 +94,33 @@ class DiscreteActorCritic(nn.Module):
         self.sync_image()
 
     # ---- reference checkpoint compatibility (SURVEY 8f-3) --------------------------------------
-    _REF_KEYS = {
-        "w0": "preprocess.model.model.0.weight", "b0": "preprocess.model.model.0.bias",
-        "w1": "preprocess.model.model.2.weight", "b1": "preprocess.model.model.2.bias",
-        "w2": "last.model.0.weight", "b2": "last.model.0.bias",
-    }
-
     def reference_named_views(self) -> list[tuple[str, torch.Tensor]]:
         """[(key, view)] in ActorCritic.parameters() order with the key names `Algorithm.state_dict()` gives the
         reference's PPO over DiscreteActor/DiscreteCritic(Net(hidden_sizes=[H, H])): `policy.actor.<...>`, `critic.<...>`
         (algorithm_base.py:521-541; verified by tests/golden/checkpoint.npz)."""
-        keys = getattr(self, "_ref_keys", None)
+        keys = getattr(self, "_ref_keys", None) or {"actor": ref_layer_keys(3, "head"), "critic": ref_layer_keys(3, "head")}
         out = []
-        for i, (name, v) in enumerate(self.named_views()):
+        for name, v in self.named_views():
             net, layer = name.split(".")
-            if keys is not None:
-                k = keys[net][int(layer[1])][0 if layer[0] == "w" else 1]
-            else:
-                k = self._REF_KEYS[layer]
-            out.append((("policy.actor." if net == "actor" else "critic.") + k, v))
+            out.append((("policy.actor." if net == "actor" else "critic.") + keys[net][int(layer[1])][layer[0] == "b"], v))
         return out
+
+    def _ref_named_views(self):
+        """(net, key of DiscreteActor/DiscreteCritic over Net, view) of every parameter."""
+        keys = ref_layer_keys(3, "head")
+        return [(name.split(".")[0], keys[int(name[-1])][name[-2] == "b"], v) for name, v in self.named_views()]
 
     def to_reference_state_dict(self) -> dict[str, OrderedDict]:
         """{'actor': ..., 'critic': ...} with the key names of DiscreteActor/DiscreteCritic over Net."""
         out = {"actor": OrderedDict(), "critic": OrderedDict()}
-        for name, v in self.named_views():
-            net, layer = name.split(".")
-            out[net][self._REF_KEYS[layer]] = v.detach().clone().cpu()
+        for net, key, v in self._ref_named_views():
+            out[net][key] = v.detach().clone().cpu()
         return out
 
     @torch.no_grad()
     def load_reference_state_dict(self, sd: dict) -> None:
-        for name, v in self.named_views():
-            net, layer = name.split(".")
-            v.copy_(torch.as_tensor(sd[net][self._REF_KEYS[layer]]).to(v.device, v.dtype).reshape(v.shape))
+        for net, key, v in self._ref_named_views():
+            v.copy_(torch.as_tensor(sd[net][key]).to(v.device, v.dtype).reshape(v.shape))
         self.sync_image()
 
     @torch.no_grad()
@@ -178,6 +183,17 @@ class FlatMLP(nn.Module):
             self.weight(i).copy_(torch.empty(self.weight(i).shape).uniform_(-bound, bound, generator=gen))
             self.bias(i).copy_(torch.empty(self.bias(i).shape).uniform_(-bound, bound, generator=gen))
 
+    def clone_over(self, storage: torch.Tensor) -> "FlatMLP":
+        """A net of the same shape viewing `storage`, which holds the init of a private generator until the caller copies
+        over it (`lagged_copy`)."""
+        return FlatMLP(self.dims, self.act, device=storage.device, seed=0, storage=storage)
+
+    @torch.no_grad()
+    def rebind(self, storage: torch.Tensor) -> None:
+        """Move the parameters into `storage` (a slice of a joint vector) and view them there."""
+        storage.copy_(self.flat.data)
+        self.flat = nn.Parameter(storage, requires_grad=False)
+
     @torch.no_grad()
     def load_layers(self, layers) -> None:
         """layers: [(W [out, in], b [out])] per layer (numpy or tensors), torch nn.Linear layout."""
@@ -222,17 +238,26 @@ class FlatMLP(nn.Module):
         return ops.mlp_input_grad(self.desc, self.flat.data, x2, acts, d_out.reshape(x2.shape[0], self.dims[-1]), col0, n_col,
                                   out=out)
 
-    # reference module key names: fc1/fc2/fc3 (ctde.py:362-364, 398-400)
-    def to_reference_state_dict(self) -> OrderedDict:
-        sd = OrderedDict()
-        for i in range(self.n_layers):
-            sd[f"fc{i + 1}.weight"] = self.weight(i).detach().clone().cpu()
-            sd[f"fc{i + 1}.bias"] = self.bias(i).detach().clone().cpu()
+    # ---- checkpoints under the reference's key names (`ref_layer_keys`) -----------------------------------------------
+    def named_layers(self, keys, prefix: str = "") -> list[tuple[str, torch.Tensor]]:
+        """[(prefix + key, view)]: every layer's weight, then its bias, under `keys` = [(weight key, bias key)]."""
+        return [(prefix + k, v) for i, kk in enumerate(keys) for k, v in zip(kk, (self.weight(i), self.bias(i)))]
+
+    def export_layers(self, keys, prefix: str = "", sd: OrderedDict | None = None) -> OrderedDict:
+        """The layers as host copies under prefix + `keys`, added to `sd` (None: a new OrderedDict)."""
+        sd = OrderedDict() if sd is None else sd
+        sd.update((k, v.detach().clone().cpu()) for k, v in self.named_layers(keys, prefix))
         return sd
 
-    @torch.no_grad()
+    def import_layers(self, sd, keys, prefix: str = "") -> None:
+        """`load_layers` from the entries of `sd` under prefix + `keys`."""
+        self.load_layers([(sd[prefix + kw], sd[prefix + kb]) for kw, kb in keys])
+
+    def to_reference_state_dict(self) -> OrderedDict:
+        return self.export_layers(ref_layer_keys(self.n_layers, "fc"))
+
     def load_reference_state_dict(self, sd) -> None:
-        self.load_layers([(sd[f"fc{i + 1}.weight"], sd[f"fc{i + 1}.bias"]) for i in range(self.n_layers)])
+        self.import_layers(sd, ref_layer_keys(self.n_layers, "fc"))
 
 
 class ImplicitQuantileNet(nn.Module):
@@ -290,8 +315,7 @@ class ImplicitQuantileNet(nn.Module):
         self.be.copy_(torch.empty(self.be.shape).uniform_(-bound, bound, generator=gen))
 
     def clone_over(self, storage: torch.Tensor) -> "ImplicitQuantileNet":
-        """A net of the same shape viewing `storage` (the lagged copy of an off-policy learner); `storage` keeps what the
-        constructor's init wrote until the caller copies over it."""
+        """As `FlatMLP.clone_over`."""
         return ImplicitQuantileNet(self.pre_dims, self.n_act, self.hidden_sizes, self.num_cosines, self.act, self.feature_act,
                                    device=storage.device, seed=0, storage=storage)
 
@@ -341,11 +365,9 @@ class ImplicitQuantileNet(nn.Module):
     def reference_named_views(self) -> list[tuple[str, torch.Tensor]]:
         """[(key, view)] in `parameters()` order under the reference's names: `preprocess.model.model.{2 i}` (Net: Linear,
         activation, ...), `last.model.{2 i}` (MLP), `embed_model.net.0` (tests/golden/iqn.npz, sd_*)."""
-        out = []
-        for stem, net in (("preprocess.model.model", self.preprocess), ("last.model", self.last)):
-            for i in range(net.n_layers):
-                out += [(f"{stem}.{2 * i}.weight", net.weight(i)), (f"{stem}.{2 * i}.bias", net.bias(i))]
-        return out + [("embed_model.net.0.weight", self.We), ("embed_model.net.0.bias", self.be)]
+        return (self.preprocess.named_layers(ref_layer_keys(self.preprocess.n_layers, "body"), "preprocess.")
+                + self.last.named_layers(ref_layer_keys(self.last.n_layers, "seq"), "last.model.")
+                + [("embed_model.net.0.weight", self.We), ("embed_model.net.0.bias", self.be)])
 
     def to_reference_state_dict(self) -> OrderedDict:
         return OrderedDict((k, v.detach().clone().cpu()) for k, v in self.reference_named_views())
@@ -386,17 +408,9 @@ class MLPActorCritic(nn.Module):
     def reference_named_views(self) -> list[tuple[str, torch.Tensor]]:
         """As DiscreteActorCritic.reference_named_views, for Net(hidden_sizes=[...]) of any depth: hidden layer i is
         `preprocess.model.model.{2 i}` (Linear, activation, Linear, ...), the output layer `last.model.0`."""
-        keys = getattr(self, "_ref_keys", None)
-        out = []
-        for net_name, net, prefix in (("actor", self.actor, "policy.actor."), ("critic", self.critic, "critic.")):
-            for i in range(net.n_layers):
-                if keys is not None:
-                    kw, kb = keys[net_name][i]
-                else:
-                    stem = f"preprocess.model.model.{2 * i}" if i < net.n_layers - 1 else "last.model.0"
-                    kw, kb = stem + ".weight", stem + ".bias"
-                out += [(prefix + kw, net.weight(i)), (prefix + kb, net.bias(i))]
-        return out
+        keys = getattr(self, "_ref_keys", None) or {}
+        return [kv for name, net, prefix in (("actor", self.actor, "policy.actor."), ("critic", self.critic, "critic."))
+                for kv in net.named_layers(keys.get(name) or ref_layer_keys(net.n_layers, "head"), prefix)]
 
     @torch.no_grad()
     def reset_parameters(self, init: str = "orthogonal", seed: int | None = None) -> None:
@@ -486,6 +500,38 @@ class FlatAdam:
         g = sd["param_groups"][0]
         self.step_count, self.lr = step, float(g["lr"])
         self.betas, self.eps, self.weight_decay = tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"])
+
+
+# ---- lagged copies and joint parameter vectors -------------------------------------------------------------------------------
+def lagged_copy(net, storage: torch.Tensor | None = None):
+    """A twin of `net` over storage of its own (None: a clone of the flat vector), holding the same weights: a lagged or
+    target network, or a second critic.  The twin's constructor draws its init from a private generator (`clone_over` gives a
+    seed) and the copy overwrites that draw, so the global torch RNG is not drawn from -- as the reference's deepcopy draws
+    nothing, and a seeded script's later torch.randint / nn.Linear init stays the reference's."""
+    if storage is None:
+        storage = net.flat.data.clone()
+    twin = net.clone_over(storage)
+    storage.copy_(net.flat.data)
+    return twin
+
+
+def join_nets(nets, device) -> tuple[torch.Tensor, list[int]]:
+    """ONE flat parameter vector [net_0 | net_1 | ...] on `device`: every net's parameters move into its slice (`rebind`) and
+    are viewed there.  -> (flat, offsets): net k occupies flat[offsets[k]:offsets[k + 1]]."""
+    offsets = np.concatenate([[0], np.cumsum([n.flat.numel() for n in nets])]).astype(np.int64).tolist()
+    flat = torch.zeros(offsets[-1], dtype=torch.float32, device=device)
+    for n, o, e in zip(nets, offsets, offsets[1:]):
+        n.rebind(flat[o:e])
+    return flat, offsets
+
+
+def lagged_twins(nets, flat: torch.Tensor, offsets) -> tuple[torch.Tensor, list]:
+    """The targets of the nets that `join_nets` joined: -> (target_flat, a copy of `flat`; a twin of every net over its slice
+    of it).  One copy fills all of them, RNG-neutral as `lagged_copy`."""
+    target_flat = flat.clone()
+    twins = [n.clone_over(target_flat[o:e]) for n, o, e in zip(nets, offsets, offsets[1:])]
+    target_flat.copy_(flat)
+    return target_flat, twins
 
 
 class RunningMeanStd:
