@@ -18,28 +18,15 @@
 // Same k order per output as the 32-sample kernel for layers 1 and 2 and every gradient; the logits are summed as two
 // 64-long halves on all eight waves (instead of one 128-long chain on two).
 #include "actor_rows_dev.h"
+#include "rows128_dev.h"
 
 extern long long *g_tsm_stamps;  // abi.hip (diagnostics, tools/stamp_actor_rows.py)
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-constexpr int kH = 128;        // hidden width
 constexpr int kRows = 64;      // samples per tile (four 16-row MFMA tiles)
 constexpr int kRT = 4;
-constexpr int kThreads = 512;  // 8 waves
-constexpr int kLdh = kH + 2;   // 130 = 2 x odd: conflict-free [lane & 15][lane >> 4] operand reads
-constexpr int kLdo = 18;
 constexpr int kPF = 1;         // steps (of <= 4 MFMAs) an MFMA stream's LDS operands are read ahead, mfma_stream
-
-__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// LDS offsets above 64 KB as opaque scalars (critic_rows_dev.h has the story: one address VGPR per access otherwise)
-__device__ __forceinline__ int opaque_s(int x) {
-    asm volatile("" : "+s"(x));
-    return x;
-}
 
 // An MFMA stream whose LDS operands are fetched PF steps ahead of the MFMAs that use them (round 5).  Written as the plain loop
 // "read the step's operands, issue its MFMAs", hipcc emits ds_read -> s_waitcnt lgkmcnt(0) -> MFMAs per step: the wave sits out one
@@ -120,23 +107,10 @@ __global__ __launch_bounds__(kThreads) void actor_rows64_kernel(TsmActorArgs g) 
         const float v = g.P[ok ? oW3 + r * kH + c : 0];
         w3q[u] = ok ? v : 0.f;
     }
-    {
-        float *dst = lds + ly.U;
-        const float *src = g.P + oW2;
-        if ((oW2 & 3) == 0) {
-            float4 q[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) q[u] = reinterpret_cast<const float4 *>(src)[tid + u * kThreads];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int e4 = tid + u * kThreads, r = e4 >> 5, c = (e4 & 31) * 4;
-                float *p = dst + r * kLdh + c;
-                *reinterpret_cast<float2 *>(p) = make_float2(q[u].x, q[u].y);
-                *reinterpret_cast<float2 *>(p + 2) = make_float2(q[u].z, q[u].w);
-            }
-        } else {
-            for (int e = tid; e < kH * kH; e += kThreads) dst[(e >> 7) * kLdh + (e & 127)] = src[e];
-        }
+    {   // (the pad columns of W2 are never read here: no w2_zero_pads)
+        float4 q[8];
+        w2_load(q, g.P + oW2);
+        w2_store(lds + ly.U, q);
     }
 #pragma unroll
     for (int u = 0; u < kN1; ++u) {

@@ -47,6 +47,18 @@ static inline hipStream_t tsm_stream(void *s) { return reinterpret_cast<hipStrea
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+typedef float f4 __attribute__((ext_vector_type(4)));  // an MFMA accumulator tile / four floats in consecutive registers
+
+// 16-B global accesses (the address must be 16-B aligned where the caller has not said otherwise)
+__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
+
+// Python's a % m for m > 0: the result has the sign of m (ring-buffer index arithmetic)
+__device__ __forceinline__ int64_t pymod(int64_t a, int64_t m) {
+    int64_t r = a % m;
+    return r < 0 ? r + m : r;
+}
+
 // Dynamic LDS of a workgroup on gfx950: 160 KB.  ONE constant for the host-side layout checks and for the value handed to
 // hipFuncAttributeMaxDynamicSharedMemorySize (a layout that passes the check can always be launched).
 constexpr size_t kTsmMaxLds = 160 * 1024;

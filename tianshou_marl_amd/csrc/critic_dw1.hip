@@ -16,7 +16,7 @@
 // bytes is the one kept: half the writes here and half the optimizer's reads of them (12.6 -> 6.3 MB each).  32-row sub-chunks
 // (33 KB of LDS: four workgroups per CU, more room for the side reductions below) were measured too: 17.2 vs 14.6 us alone,
 // 22.5 vs 20.3 us in situ -- twice the barriers per row cost more than the extra residency gives.
-#include "critic_rows_dev.h"
+#include "rows128_dev.h"
 #include "adam_dev.h"
 
 namespace {
@@ -87,16 +87,6 @@ __device__ __forceinline__ void dw1_side_reduce(const Dw1Args &g, int b, float *
     if (active) sm[sl * 64 + lane] = acc;
     __syncthreads();
     if (active && sl == 0 && i < sr.n) sr.out[i] = sm[lane] + sm[64 + lane] + sm[128 + lane] + sm[192 + lane];
-}
-
-__device__ __forceinline__ int64_t dw1_row_of(const Dw1Args &g, int64_t i) {
-    const int64_t ic = i < g.Mr ? i : g.Mr - 1;
-    if (g.rows) return g.rows[ic];
-    if (g.tm_T > 0) {   // env-major view of a time-major store (32-bit arithmetic, Mr < 2^31: a 64-bit division is ~100 instructions)
-        const int t_ = (int)g.tm_T, ii = (int)ic;
-        return (int64_t)(ii % t_) * g.tm_E + ii / t_;
-    }
-    return g.first_row + ic;
 }
 
 template <bool VEC, int NT>
@@ -176,7 +166,7 @@ __global__ __launch_bounds__(kThreads) void critic_dw1_kernel(Dw1Args g) {
     // B-operand row of minibatch row i: the observation row it names (first product), or i itself (H1 is in minibatch order)
     auto row_id = [&](int64_t i) -> int64_t {
         const int64_t ic = i < i_hi ? i : i_hi - 1;
-        return second ? ic : dw1_row_of(g, ic);
+        return second ? ic : rows_row_of(g, ic);
     };
     int64_t my_id = 0;
     if (tid < kSub) rid[tid] = row_id(i_lo + tid);
@@ -239,13 +229,13 @@ int tsm_critic_dw1_init() {
 // whatever the split, so 48-column blocks -- half the slabs.  Many rows (CTDEPolicy.learn: 102 400): the MFMA loop is what
 // counts, and 96-column blocks reuse every dH1 operand read for six products instead of three (117.8 vs 143.4 us).
 static int dw1_nt(int64_t Mr, int32_t in_dim) {
-    const int64_t chunks6 = n_cu_dev() / ceil_div(in_dim, 96) > 0 ? n_cu_dev() / ceil_div(in_dim, 96) : 1;
+    const int64_t chunks6 = rows_n_cu() / ceil_div(in_dim, 96) > 0 ? rows_n_cu() / ceil_div(in_dim, 96) : 1;
     return Mr / chunks6 >= 512 ? 6 : 3;
 }
 
 static void dw1_plan(int64_t Mr, int32_t in_dim, int64_t *RC, int *n_chunk) {
     const int ncb = (int)ceil_div(in_dim, 16 * dw1_nt(Mr, in_dim));
-    int64_t want = (int64_t)n_cu_dev() / ncb;
+    int64_t want = (int64_t)rows_n_cu() / ncb;
     if (want < 1) want = 1;
     const int64_t subs = ceil_div(Mr, kSub);
     if (want > subs) want = subs;

@@ -23,10 +23,12 @@
 //     lane multiplies its relu(h2) by w3[col], 16-lane DPP row sums, then the 8 waves' partial sums in wave order.
 //     Two barriers per tile.
 // Algorithmic HBM traffic: 4 K1 B read + 4 B written per row.
-#include "critic_rows_dev.h"
+#include "rows128_dev.h"
 #include <stdlib.h>
 
 namespace {
+
+constexpr int kRows = 32;      // rows per tile (two 16-row MFMA tiles)
 
 struct FwdLay {  // LDS layout in floats
     int ldx, W2, X, H1, B1, B2, W3, RED, RID, total;
@@ -43,7 +45,7 @@ struct FwdLay {  // LDS layout in floats
         RID = o; o += 2 * kRows;  // row ids of the tile being fetched (int64)
         total = o;
     }
-    __device__ void launder() {   // (critic_rows_dev.h: opaque_s)
+    __device__ void launder() {   // (rows128_dev.h: opaque_s)
         W2 = opaque_s(W2); X = opaque_s(X); H1 = opaque_s(H1); B1 = opaque_s(B1); B2 = opaque_s(B2); W3 = opaque_s(W3);
         RED = opaque_s(RED); RID = opaque_s(RID);
     }
@@ -214,7 +216,7 @@ template <int KJ, bool VEC>
 int launch_forward_v(const FwdArgs &g, int grid, hipStream_t st) {
     const FwdLay ly(KJ);
     const size_t shmem = (size_t)ly.total * sizeof(float);
-    TSM_REQUIRE(shmem <= kMaxLds, "tsm_critic_rows_forward: LDS layout of %zu bytes does not fit", shmem);
+    TSM_REQUIRE(shmem <= kTsmMaxLds, "tsm_critic_rows_forward: LDS layout of %zu bytes does not fit", shmem);
     static bool attr_set = false;  // (set before any capture: tsm_critic_rows_init)
     if (!attr_set) {
         TSM_HIP(tsm_allow_max_lds(reinterpret_cast<const void *>(critic_rows_forward_kernel<KJ, VEC>)));
@@ -447,7 +449,7 @@ template <int KJ2>
 int launch_forward_bf16(const FwdArgs &g, int grid, hipStream_t st) {
     const FwdLayB ly(KJ2);
     const size_t shmem = (size_t)ly.total * sizeof(float);
-    TSM_REQUIRE(shmem <= kMaxLds, "tsm_critic_rows_forward (bf16 x 6): LDS layout of %zu bytes does not fit", shmem);
+    TSM_REQUIRE(shmem <= kTsmMaxLds, "tsm_critic_rows_forward (bf16 x 6): LDS layout of %zu bytes does not fit", shmem);
     static bool attr_set = false;
     if (!attr_set) {
         TSM_HIP(tsm_allow_max_lds(reinterpret_cast<const void *>(critic_rows_forward_bf16x6_kernel<KJ2>)));
@@ -525,9 +527,8 @@ TSM_EXPORT int tsm_critic_rows_forward(const float *critic_params, int32_t in_di
     FwdArgs g{};
     g.P = critic_params; g.obs = obs_rows; g.rows = rows; g.first_row = first_row; g.Mr = Mr; g.K1 = in_dim;
     g.out = values_out; g.run_if = run_if; g.n_out = n_out;
-    const int64_t tiles = ceil_div(Mr, kRows);
-    const int cu = n_cu_dev();
+    const int grid = rows_grid(ceil_div(Mr, kRows));
     if (const int kj2 = split_bf16_kj2(in_dim))   // experimental, opt-in (TSM_SPLIT_BF16=1)
-        return dispatch_forward_bf16(kj2, g, (int)(tiles < cu ? tiles : cu), tsm_stream(stream));
-    return dispatch_forward(pick_kj(in_dim), g, (int)(tiles < cu ? tiles : cu), tsm_stream(stream));
+        return dispatch_forward_bf16(kj2, g, grid, tsm_stream(stream));
+    return dispatch_forward(pick_kj(in_dim), g, grid, tsm_stream(stream));
 }

@@ -23,13 +23,13 @@
 //   * LOSS 1 needs V of a row's SUCCESSOR: a tile owns 31 consecutive env-major rows and computes the 32nd as a halo, so
 //     the target of every owned row comes out of the same forward pass (3 % redundant rows instead of a second pass over
 //     all of them); the last row of an env's block takes V(obs_next) from `v_last` (tsm_critic_rows_forward on those rows).
-#include "critic_rows_dev.h"
+#include "rows128_dev.h"
 
 extern long long *g_tsm_stamps;  // abi.hip (diagnostics, tools/stamp_critic_train.py)
 
 namespace {
 
-constexpr int kLdo = 18;
+constexpr int kRows = 32;      // rows per tile (two 16-row MFMA tiles)
 
 struct TrainLay {  // LDS layout in floats
     int ldx, W2, W3, X, H1, H2, B1, B2, B3, Q, V, DV, RID, RIDC, RED, PV, total;
@@ -54,7 +54,7 @@ struct TrainLay {  // LDS layout in floats
         RED = DV;
         total = o;
     }
-    __device__ void launder() {         // (critic_rows_dev.h: opaque_s)
+    __device__ void launder() {         // (rows128_dev.h: opaque_s)
         W2 = opaque_s(W2); W3 = opaque_s(W3); X = opaque_s(X); H1 = opaque_s(H1); H2 = opaque_s(H2); B1 = opaque_s(B1);
         B2 = opaque_s(B2); B3 = opaque_s(B3); Q = opaque_s(Q); V = opaque_s(V); DV = opaque_s(DV); RID = opaque_s(RID);
         RIDC = opaque_s(RIDC); PV = Q; RED = DV;
@@ -93,23 +93,6 @@ struct TrainArgs {
 
 #define TSTAMP(k) do { if (g.stamps && blockIdx.x == 0 && tid == 0 && it < 3) g.stamps[300 + 16 * it + (k)] = (long long)wall_clock64(); } while (0)
 
-// Store row of minibatch row i (clamped to a valid row; masked by the caller).  LOSS 1 walks the env-major view of a
-// time-major store: computed, no load (32-bit arithmetic: Mr < 2^31).  LOSS 0: an id list or a contiguous range -- written
-// as a uniform BRANCH, not a select, so that the loaded id is not consumed (and waited for) where it is requested.
-template <int LOSS>
-__device__ __forceinline__ int64_t row_of(const TrainArgs &g, int64_t i) {
-    const int64_t ic = i < g.Mr ? i : g.Mr - 1;  // (Mr >= 1)
-    if constexpr (LOSS == 1) {
-        const int t_ = (int)g.tm_T, ii = (int)ic;
-        return (int64_t)(ii % t_) * g.tm_E + ii / t_;
-    } else {
-        int64_t r;
-        if (g.rows) r = g.rows[ic];
-        else r = g.first_row + ic;
-        return r;
-    }
-}
-
 template <int KJ, bool VEC, int LOSS, bool PUB>
 __global__ __launch_bounds__(kThreads) void critic_rows_train_kernel(TrainArgs g) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -132,12 +115,12 @@ __global__ __launch_bounds__(kThreads) void critic_rows_train_kernel(TrainArgs g
     const int64_t gs = gridDim.x;
     int64_t tile = blockIdx.x;
     int64_t id0 = 0, id1 = 0, id2 = 0, id3 = 0;   // (LOSS 0 only: LOSS 1 computes its row ids where it needs them)
-    if (tid < kRows) {
-        id0 = row_of<LOSS>(g, tile * OWN + tid);
-        id1 = row_of<LOSS>(g, (tile + gs) * OWN + tid);
+    if (tid < kRows) {   // (rows_row_of's TM = LOSS: the TD form always walks the time-major view, the PPO form never does)
+        id0 = rows_row_of<LOSS>(g, tile * OWN + tid);
+        id1 = rows_row_of<LOSS>(g, (tile + gs) * OWN + tid);
         if constexpr (LOSS == 0) {
-            id2 = row_of<LOSS>(g, (tile + 2 * gs) * OWN + tid);
-            id3 = row_of<LOSS>(g, (tile + 3 * gs) * OWN + tid);
+            id2 = rows_row_of<LOSS>(g, (tile + 2 * gs) * OWN + tid);
+            id3 = rows_row_of<LOSS>(g, (tile + 3 * gs) * OWN + tid);
         }
     }
     // ---- this wave's fragment of W1, once, into registers: from the fragment image when there is one (1 KB of consecutive
@@ -224,6 +207,7 @@ __global__ __launch_bounds__(kThreads) void critic_rows_train_kernel(TrainArgs g
     fetch_tile(tile, 0);      // the first tile's rows are in flight behind the weights ...
     // ---- resident weights: W2, W3 (rows >= n_out zero), biases ----
     w2_store(lds + ly.W2, w2q);
+    w2_zero_pads(lds + ly.W2);
 #pragma unroll
     for (int u = 0; u < kN3; ++u) {
         const int e = tid + u * kThreads;
@@ -250,8 +234,8 @@ __global__ __launch_bounds__(kThreads) void critic_rows_train_kernel(TrainArgs g
                 rid[(it & 1) * kRows + tid] = id2;
                 id0 = id1; id1 = id2; id2 = id3;
             } else {
-                ridc[tid] = row_of<LOSS>(g, tile * OWN + tid);
-                rid[(it & 1) * kRows + tid] = row_of<LOSS>(g, (tile + 2 * gs) * OWN + tid);
+                ridc[tid] = rows_row_of<LOSS>(g, tile * OWN + tid);
+                rid[(it & 1) * kRows + tid] = rows_row_of<LOSS>(g, (tile + 2 * gs) * OWN + tid);
             }
         }
         // ---- P1: H1 = relu(X W1^T + b1); W1 from registers, X by ds_read_b128 ----
@@ -287,7 +271,7 @@ __global__ __launch_bounds__(kThreads) void critic_rows_train_kernel(TrainArgs g
         TSTAMP(1);
         if (LOSS != 0 || tile + gs < n_tiles) commit_tile();   // the next tile's rows: requested at the end of the previous tile, they flew during L1
         if constexpr (LOSS == 0) {
-            if (tid < kRows) id3 = row_of<LOSS>(g, (tile + 4 * gs) * OWN + tid);  // (three tiles ahead)
+            if (tid < kRows) id3 = rows_row_of<LOSS>(g, (tile + 4 * gs) * OWN + tid);  // (three tiles ahead)
         }
         // loss inputs of this tile: row id -> scalars are dependent global loads; they fly during layers 2 and 3
         float pf_a = 0.f, pf_b = 0.f;
@@ -599,7 +583,7 @@ template <int KJ, bool VEC, int LOSS, bool PUB = false>
 int launch_train_v(const TrainArgs &g, int grid, hipStream_t st) {
     const TrainLay ly(KJ);
     const size_t shmem = (size_t)ly.total * sizeof(float);
-    TSM_REQUIRE(shmem <= kMaxLds, "critic gradient step: LDS layout of %zu bytes does not fit", shmem);
+    TSM_REQUIRE(shmem <= kTsmMaxLds, "critic gradient step: LDS layout of %zu bytes does not fit", shmem);
     static bool attr_set = false;  // (set before any capture: tsm_critic_rows_init)
     if (!attr_set) {
         TSM_HIP(tsm_allow_max_lds(reinterpret_cast<const void *>(critic_rows_train_kernel<KJ, VEC, LOSS, PUB>)));
@@ -672,9 +656,7 @@ TSM_EXPORT int64_t tsm_critic_rows_param_count(int32_t in_dim, int32_t hidden, i
 // workgroups of kernel A (= slabs of the b1 | W2 | b2 | W3 | b3 part) for Mr rows; td: tiles own 31 rows
 TSM_EXPORT int tsm_critic_rows_grad_grid(int64_t Mr, int32_t td) {
     if (Mr <= 0) return 0;
-    const int64_t tiles = ceil_div(Mr, td ? kRows - 1 : kRows);
-    const int cu = n_cu_dev();
-    return (int)(tiles < cu ? tiles : cu);
+    return rows_grid(ceil_div(Mr, td ? kRows - 1 : kRows));
 }
 
 // ---- W1 in fragment order (see TrainArgs::w1_img) ----

@@ -22,8 +22,6 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 constexpr int BM = 64, BN = 64, BK = 16, LDT = BK + 2, NT = 256;  // a k tile = BK / 16 sub-tiles of 16, staged side by side
 // (BK = 32 measured slower on MI355X: 29.6 % vs 34.3 % of the f32-MFMA peak on the 384-128-128-8 critic forward)
 constexpr int KS = BK / 16;

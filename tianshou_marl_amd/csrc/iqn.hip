@@ -20,7 +20,6 @@
 #include "q_head_dev.h"
 
 namespace {
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 constexpr int kIThreads = 256;
 constexpr int kIWaves = kIThreads / kWave;

@@ -23,8 +23,6 @@ struct JoinPtrs { const float *obs[kMMaxN]; const float *act[kMMaxN]; const floa
 struct ActPtrs { const float *mu[kMMaxN]; };
 struct FinPtrs { const float *q_pi[kMMaxN]; };
 
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // One region of the joint rows: n_seg segments of `w` floats per row, segment j of row b read from src_j[b * w ..] and

@@ -5,8 +5,6 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 constexpr int R = 16;      // rows per tile
 constexpr int NT = 256;    // threads per workgroup (4 waves)
 constexpr int kMaxJ = 4;   // obs_dim <= 64

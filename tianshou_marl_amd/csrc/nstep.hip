@@ -19,11 +19,6 @@
 
 namespace {
 
-__device__ __forceinline__ int64_t pymod(int64_t a, int64_t m) {
-    int64_t r = a % m;
-    return r < 0 ? r + m : r;
-}
-
 __global__ __launch_bounds__(256) void nstep_kernel(const void *state, int64_t B, int64_t S,
                                                     const uint8_t *__restrict__ done_store,
                                                     const uint8_t *__restrict__ term_store, int64_t term_stride,

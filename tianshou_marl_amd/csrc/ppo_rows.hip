@@ -20,40 +20,14 @@
 // Algorithmic HBM traffic per sample and step: obs 4 D + act 4 + logp_old 4 + adv 4 + id 8; activations
 // never touch HBM (the dense path writes and re-reads 4 x 512 B per sample).
 #include "actor_rows_dev.h"
+#include "rows128_dev.h"
 #include <stdlib.h>
 
 extern long long *g_tsm_stamps;  // abi.hip (diagnostics, tools/stamp_actor_rows.py)
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-constexpr int kH = 128;        // hidden width
 constexpr int kRows = 32;      // samples per tile (two 16-row MFMA tiles)
-constexpr int kThreads = 512;  // 8 waves
-constexpr int kLdh = kH + 2;   // 130 = 2 x odd: conflict-free [lane & 15][lane >> 4] operand reads
-constexpr int kLdo = 18;
-
-__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// W2 [128][128] -> LDS rows of kLdh floats: 16-B global loads (8 per thread, all in flight), 8-B LDS stores
-__device__ __forceinline__ void stage_w2(float *dst, const float *__restrict__ src, bool aligned) {
-    if (aligned) {
-        float4 q[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) q[u] = reinterpret_cast<const float4 *>(src)[threadIdx.x + u * kThreads];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int e4 = threadIdx.x + u * kThreads, r = e4 >> 5, c = (e4 & 31) * 4;
-            float *p = dst + r * kLdh + c;
-            *reinterpret_cast<float2 *>(p) = make_float2(q[u].x, q[u].y);
-            *reinterpret_cast<float2 *>(p + 2) = make_float2(q[u].z, q[u].w);
-        }
-    } else {
-        for (int e = threadIdx.x; e < kH * kH; e += kThreads) dst[(e >> 7) * kLdh + (e & 127)] = src[e];
-    }
-    for (int e = threadIdx.x; e < kH * 2; e += kThreads) dst[(e >> 1) * kLdh + kH + (e & 1)] = 0.f;  // the two pad columns
-}
 
 struct RowsLay {  // LDS layout in floats
     int nJ, ld1, W1, W2, W3, B1, B2, B3, X, H1, H2, LG, total;
@@ -92,7 +66,7 @@ __global__ __launch_bounds__(kThreads) void ppo_actor_rows_kernel(ActorArgs g) {
     // ---- stage the weights once (zero pads: W1 columns >= D, W3 rows >= A) ----
     const int oW1 = 0, oB1 = kH * D, oW2 = oB1 + kH, oB2 = oW2 + kH * kH, oW3 = oB2 + kH, oB3 = oW3 + A * kH;
     tsm_stage_padded<kThreads>(lds + ly.W1, g.P + oW1, kH * ld1, ld1, kH, D, D);
-    stage_w2(lds + ly.W2, g.P + oW2, (oW2 & 3) == 0);
+    stage_w2_rows(lds + ly.W2, g.P + oW2);
     tsm_stage_padded<kThreads>(lds + ly.W3, g.P + oW3, 16 * kLdh, kLdh, A, kH, kH);
     if (tid < kH) { lds[ly.B1 + tid] = g.P[oB1 + tid]; lds[ly.B2 + tid] = g.P[oB2 + tid]; }
     if (tid < 16) lds[ly.B3 + tid] = tid < A ? g.P[oB3 + tid] : 0.f;
@@ -411,7 +385,7 @@ __global__ __launch_bounds__(kThreads) void ppo_critic_rows_kernel(CriticArgs g)
     const int K1 = g.K1, N = g.N;
     const int64_t n_blocks = (g.Mr + kRows - 1) / kRows;
     const int oB1 = kH * K1, oW2 = oB1 + kH, oB2 = oW2 + kH * kH, oW3 = oB2 + kH, oB3 = oW3 + kH;
-    stage_w2(lds + ly.W2, g.P + oW2, (oW2 & 3) == 0);
+    stage_w2_rows(lds + ly.W2, g.P + oW2);
     if (tid < kH) { lds[ly.W3 + tid] = g.P[oW3 + tid]; lds[ly.B1 + tid] = g.P[oB1 + tid]; lds[ly.B2 + tid] = g.P[oB2 + tid]; }
     const float b3 = g.P[oB3];
     CSTAMP(0);
@@ -726,17 +700,6 @@ __global__ __launch_bounds__(kThreads) void ppo_critic_rows_kernel(CriticArgs g)
 
 int rows_supported(int32_t D, int32_t H, int32_t A) { return H == kH && D >= 1 && D <= 64 && A >= 1 && A <= 16; }
 
-int n_cu() {
-    static int cached = 0;
-    if (!cached) {
-        hipDeviceProp_t p;
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cached = p.multiProcessorCount;
-        if (cached <= 0) cached = 256;
-    }
-    return cached;
-}
-
 }  // namespace
 
 TSM_EXPORT int tsm_ppo_actor_rows_supported(int32_t obs_dim, int32_t hidden, int32_t n_act) {
@@ -754,15 +717,13 @@ TSM_EXPORT int64_t tsm_ppo_actor_rows_param_count(int32_t obs_dim, int32_t hidde
 // fixtures through both, tools time them A/B.
 static bool actor_tile64(int64_t M) {
     if (const int forced = tsm_opt(TSM_OPT_ACTOR_TILE)) return forced == 64;
-    return ceil_div(M, 64) >= n_cu();
+    return ceil_div(M, 64) >= rows_n_cu();
 }
 
 // workgroups (= gradient slabs) for a minibatch of M samples: one per CU, never more than there are tiles
 TSM_EXPORT int tsm_ppo_actor_rows_grid(int64_t M) {
     if (M <= 0) return 0;
-    const int64_t tiles = ceil_div(M, actor_tile64(M) ? 64 : kRows);
-    const int cu = n_cu();
-    return (int)(tiles < cu ? tiles : cu);
+    return rows_grid(ceil_div(M, actor_tile64(M) ? 64 : kRows));
 }
 
 // Raise the dynamic-LDS limit of EVERY instantiation of the two kernels (once per process: one process drives one GPU).  Hosts
@@ -847,9 +808,7 @@ TSM_EXPORT int64_t tsm_ppo_critic_rows_param_count(int32_t in_dim, int32_t hidde
 // workgroup writes a 264 KB slab for the 384-wide critic)
 TSM_EXPORT int tsm_ppo_critic_rows_grid(int64_t Mr) {
     if (Mr <= 0) return 0;
-    const int64_t blocks = ceil_div(Mr, kRows);
-    const int cap = n_cu();
-    return (int)(blocks < cap ? blocks : cap);
+    return rows_grid(ceil_div(Mr, kRows));
 }
 
 TSM_EXPORT int tsm_ppo_critic_rows_update(const float *critic_params, int32_t in_dim, int32_t hidden, int32_t n_agent,

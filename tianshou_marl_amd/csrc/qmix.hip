@@ -28,8 +28,6 @@ constexpr int kGreedyRows = 16;  // rows per workgroup of the epsilon-greedy ker
 
 struct QPtrs { const float *q[kQMaxN]; };
 
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
 __device__ __forceinline__ float sgnf(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
 __device__ __forceinline__ float eluf(float x) { return x > 0.f ? x : expm1f(x); }
 

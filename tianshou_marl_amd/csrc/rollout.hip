@@ -580,7 +580,7 @@ __global__ __launch_bounds__(NT) void rollout_wave64_kernel(RolloutArgs a) {
     // V(row) of the wave's samples from the observation fragments: layers 1, 2 as products, layer 3 as mlp_tile.h's fmaf chain
     // (s = fmaf(h[j], w3[j], s), j = 0 .. 63, + b3) on lane `row`; returned on lanes < 16
     auto critic_value = [&](const float (&x)[KB1]) -> float {
-        wf4 acc[MB];
+        f4 acc[MB];
         float hb[4 * MB];
         wave_layer<MB, KB1>(w1c, ld1, x, kb1_n, acc);
         wave_bias_relu<MB, true>(lds + ly.B1 + H + 4 * kq, acc);
@@ -588,14 +588,14 @@ __global__ __launch_bounds__(NT) void rollout_wave64_kernel(RolloutArgs a) {
         wave_layer<MB, KBH>(w2c, ly.ldh, hb, KBH, acc);
         wave_bias_relu<MB, true>(lds + ly.B2 + H + 4 * kq, acc);
 #pragma unroll
-        for (int mb = 0; mb < MB; ++mb) *reinterpret_cast<wf4 *>(s_h2c + c16 * Rw64Lay::kLdc + 16 * mb + 4 * kq) = acc[mb];
+        for (int mb = 0; mb < MB; ++mb) *reinterpret_cast<f4 *>(s_h2c + c16 * Rw64Lay::kLdc + 16 * mb + 4 * kq) = acc[mb];
         float s = 0.f;
         if (lane < R) {
-            wf4 hv[H / 4], wq[H / 4];
+            f4 hv[H / 4], wq[H / 4];
 #pragma unroll
             for (int q = 0; q < H / 4; ++q) {
-                hv[q] = *reinterpret_cast<const wf4 *>(s_h2c + lane * Rw64Lay::kLdc + 4 * q);
-                wq[q] = *reinterpret_cast<const wf4 *>(lds + ly.W3c + 4 * q);
+                hv[q] = *reinterpret_cast<const f4 *>(s_h2c + lane * Rw64Lay::kLdc + 4 * q);
+                wq[q] = *reinterpret_cast<const f4 *>(lds + ly.W3c + 4 * q);
             }
 #pragma unroll
             for (int j = 0; j < H; ++j) s = fmaf(hv[j >> 2][j & 3], wq[j >> 2][j & 3], s);
@@ -634,7 +634,7 @@ __global__ __launch_bounds__(NT) void rollout_wave64_kernel(RolloutArgs a) {
         if (lane_live && !p_done && a.b.vnext_store) a.b.vnext_store[p_row * N + ai] = val;
         if (last) break;
         {
-            wf4 acc[MB];
+            f4 acc[MB];
             float hb[4 * MB];
             wave_layer<MB, KB1>(w1a, ld1, xb, kb1_n, acc);
             wave_bias_relu<MB, true>(lds + ly.B1 + 4 * kq, acc);
@@ -642,19 +642,19 @@ __global__ __launch_bounds__(NT) void rollout_wave64_kernel(RolloutArgs a) {
             wave_layer<MB, KBH>(w2a, ly.ldh, hb, KBH, acc);
             wave_bias_relu<MB, true>(lds + ly.B2 + 4 * kq, acc);
             wave_to_frags<MB>(acc, hb);
-            wf4 lg = wf4{0.f, 0.f, 0.f, 0.f};   // logits (A padded to 16): lane holds actions 4 kq + i of sample c16
+            f4 lg = f4{0.f, 0.f, 0.f, 0.f};   // logits (A padded to 16): lane holds actions 4 kq + i of sample c16
 #pragma unroll
             for (int kb = 0; kb < KBH; ++kb) lg = wave_mfma4(w3a[4 * kb], hb[kb], lg);
-            const wf4 b = *reinterpret_cast<const wf4 *>(lds + ly.B3a + 4 * kq);
+            const f4 b = *reinterpret_cast<const f4 *>(lds + ly.B3a + 4 * kq);
             // (row 15 / column 15 holds the zero cell: never a live logit -- A <= 8 here; the write below keeps it 0 + 0)
             if (!(c16 == 15 && kq == 3))
-                *reinterpret_cast<wf4 *>(s_lg + c16 * 16 + 4 * kq) = wf4{lg[0] + b[0], lg[1] + b[1], lg[2] + b[2], lg[3] + b[3]};
+                *reinterpret_cast<f4 *>(s_lg + c16 * 16 + 4 * kq) = f4{lg[0] + b[0], lg[1] + b[1], lg[2] + b[2], lg[3] + b[3]};
         }
         // ---- C. heads: one lane per row, the arithmetic of categorical.hip ----
         if (lane_live) {
             float lgv[8], ex[8];
             {
-                const wf4 l0 = *reinterpret_cast<const wf4 *>(s_lg + lane * 16), l1 = *reinterpret_cast<const wf4 *>(s_lg + lane * 16 + 4);
+                const f4 l0 = *reinterpret_cast<const f4 *>(s_lg + lane * 16), l1 = *reinterpret_cast<const f4 *>(s_lg + lane * 16 + 4);
                 lgv[0] = l0[0]; lgv[1] = l0[1]; lgv[2] = l0[2]; lgv[3] = l0[3]; lgv[4] = l1[0]; lgv[5] = l1[1]; lgv[6] = l1[2]; lgv[7] = l1[3];
             }
             float m = -INFINITY;

@@ -19,6 +19,7 @@
 #include "mpe_dev.h"
 #include "philox.h"
 #include "rollout_dev.h"
+#include "rows128_dev.h"
 #include "wave_mlp.h"
 
 int tsm_mpe_check_cfg(const tsm_mpe_cfg *h, MpeCfg *c);  // mpe.hip
@@ -26,11 +27,7 @@ extern long long *g_tsm_stamps;                               // abi.hip (diagno
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-constexpr int kH = 128, kTile = 32, kThreads = 512, kLdh = kH + 2, kLdo = 8, kRowsWg = 128;  // kLdo: logits row (A <= 8)
-
-__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+constexpr int kTile = 32, kLdLg = 8, kRowsWg = 128;  // kLdLg: logits row (A <= 8; the gradient-step kernels' kLdo holds 16)
 
 struct RrLay {  // LDS layout in floats
     int nJ, ld1, W1, W2, W3, B1, B2, B3, X, H1, H2, LG, AP, AV, LP, REW, LOGP, MIN, ACT, STEPS, DONE, ROW, EP, total;
@@ -47,7 +44,7 @@ struct RrLay {  // LDS layout in floats
         X = o; o += kTile * ld1;
         H1 = o; o += kTile * kLdh;
         H2 = o; o += kTile * kLdh;
-        LG = o; o += kRowsWg * kLdo;  // logits of ALL rows of the step: the heads run once, after the last tile
+        LG = o; o += kRowsWg * kLdLg;  // logits of ALL rows of the step: the heads run once, after the last tile
         AP = o; o += kRowsWg * 2;
         AV = o; o += kRowsWg * 2;
         LP = o; o += kRowsWg * 2;
@@ -262,9 +259,9 @@ __global__ __launch_bounds__(kThreads) void rollout_rows_kernel(RrArgs a) {
 #pragma unroll
                 for (int k0 = 0; k0 < kH; k0 += 4) acc = mfma4(pa[k0], pb[k0], acc);
                 const float bb = lds[ly.B3 + c16];
-                if (c16 < kLdo)
+                if (c16 < kLdLg)
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) lds[ly.LG + (r0 + 16 * w + kq * 4 + q) * kLdo + c16] = acc[q] + bb;
+                    for (int q = 0; q < 4; ++q) lds[ly.LG + (r0 + 16 * w + kq * 4 + q) * kLdLg + c16] = acc[q] + bb;
             }
             // no barrier here: the next tile's layer 1 reads X (written before the last barrier) and writes H1 (its
             // readers passed that barrier); its layer 2 overwrites H2 only behind the barrier that follows layer 1, which
@@ -273,7 +270,7 @@ __global__ __launch_bounds__(kThreads) void rollout_rows_kernel(RrArgs a) {
         }
         __syncthreads();  // LG complete
         if (tid < rows_here) {  // heads: one lane per row, the arithmetic of categorical.hip
-            const float *lg = lds + ly.LG + tid * kLdo;
+            const float *lg = lds + ly.LG + tid * kLdLg;
             float m = -INFINITY;
             int arg = 0;
             for (int j = 0; j < A; ++j) { const float v = lg[j]; if (v > m) { m = v; arg = j; } }
@@ -421,7 +418,7 @@ struct RwLay {  // LDS layout in floats: weights as in RrLay, then one private b
         AP = q; q += 2 * kRowsWave;
         AV = q; q += 2 * kRowsWave;
         LP = q; q += 2 * kRowsWave;
-        LG = q; q += kRowsWave * kLdo;
+        LG = q; q += kRowsWave * kLdLg;
         CX = q; q += kRowsWave * 8;
         CY = q; q += kRowsWave * 8;
         CV = q; q += kRowsWave * 8;   // int
@@ -555,26 +552,26 @@ __global__ __launch_bounds__(kThreads) void rollout_wave_kernel(RrArgs a) {
             f4 lg = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kb = 0; kb < 32; ++kb) lg = mfma4(w3f[4 * kb], hb[kb], lg);
-            if (kq < kLdo / 4) {
+            if (kq < kLdLg / 4) {
                 const f4 b = *reinterpret_cast<const f4 *>(lds + ly.B3 + 4 * kq);
-                *reinterpret_cast<f4 *>(s_lg + c16 * kLdo + 4 * kq) = f4{lg[0] + b[0], lg[1] + b[1], lg[2] + b[2], lg[3] + b[3]};
+                *reinterpret_cast<f4 *>(s_lg + c16 * kLdLg + 4 * kq) = f4{lg[0] + b[0], lg[1] + b[1], lg[2] + b[2], lg[3] + b[3]};
             }
         }
         WSTAMP(4);
         if (lane_live) {  // heads: one lane per row, the arithmetic of categorical.hip (all logits in registers first; the
                           // sampler re-uses the exponentials of the normaliser: the same inputs, the same values)
-            float lg[kLdo], ex[kLdo];
+            float lg[kLdLg], ex[kLdLg];
             {
-                const f4 l0 = *reinterpret_cast<const f4 *>(s_lg + lane * kLdo), l1 = *reinterpret_cast<const f4 *>(s_lg + lane * kLdo + 4);
+                const f4 l0 = *reinterpret_cast<const f4 *>(s_lg + lane * kLdLg), l1 = *reinterpret_cast<const f4 *>(s_lg + lane * kLdLg + 4);
                 lg[0] = l0[0]; lg[1] = l0[1]; lg[2] = l0[2]; lg[3] = l0[3]; lg[4] = l1[0]; lg[5] = l1[1]; lg[6] = l1[2]; lg[7] = l1[3];
             }
             float m = -INFINITY;
             int arg = 0;
 #pragma unroll
-            for (int j = 0; j < kLdo; ++j) if (j < A && lg[j] > m) { m = lg[j]; arg = j; }
+            for (int j = 0; j < kLdLg; ++j) if (j < A && lg[j] > m) { m = lg[j]; arg = j; }
             float s = 0.f;
 #pragma unroll
-            for (int j = 0; j < kLdo; ++j) { ex[j] = 0.f; if (j < A) { ex[j] = expf(lg[j] - m); s += ex[j]; } }
+            for (int j = 0; j < kLdLg; ++j) { ex[j] = 0.f; if (j < A) { ex[j] = expf(lg[j] - m); s += ex[j]; } }
             const float lse = m + logf(s);
             int act = arg;
             if (a.mode == 1) {
@@ -584,7 +581,7 @@ __global__ __launch_bounds__(kThreads) void rollout_wave_kernel(RrArgs a) {
                 bool found = false;
                 act = A - 1;
 #pragma unroll
-                for (int j = 0; j < kLdo; ++j)
+                for (int j = 0; j < kLdLg; ++j)
                     if (j < A) {
                         cs += ex[j];
                         if (!found && u < cs) { act = j; found = true; }
@@ -592,7 +589,7 @@ __global__ __launch_bounds__(kThreads) void rollout_wave_kernel(RrArgs a) {
             }
             float la = lg[0];
 #pragma unroll
-            for (int j = 1; j < kLdo; ++j) la = act == j ? lg[j] : la;
+            for (int j = 1; j < kLdLg; ++j) la = act == j ? lg[j] : la;
             s_act[lane] = act;
             s_logp[lane] = la - lse;
         }

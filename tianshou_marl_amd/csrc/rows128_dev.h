@@ -1,15 +1,16 @@
-// critic_rows_dev.h -- pieces shared by the one-launch critic kernels (critic_rows.hip: forward; critic_train.hip: gradient step)
+// rows128_dev.h -- what the 128-wide "rows" kernels share (ppo_rows.hip, actor_rows64.hip: actor gradient step; critic_rows.hip,
+// critic_train.hip, critic_dw1.hip: critic forward / gradient step / dW1; rollout_rows.hip: actor-only rollout): the tile constants,
+// the MFMA wrapper, laundered LDS offsets, the swizzled X tile, the W1 / W2 staging, the row-id rule and the grid rule.
+// Constants that differ per kernel (rows per tile, the Lay* structs) stay in the kernels' own files.
 #pragma once
 #include "common.h"
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 constexpr int kH = 128;        // hidden width
-constexpr int kRows = 32;      // rows per tile (two 16-row MFMA tiles)
 constexpr int kThreads = 512;  // 8 waves
 constexpr int kLdh = kH + 2;   // 130 = 2 x odd: conflict-free [lane & 15][lane >> 4] operand reads
+constexpr int kLdo = 18;       // row of <= 16 layer-3 outputs (gradient-step kernels)
 
 __device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
@@ -17,6 +18,7 @@ __device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_a
 // the compiler folds each region offset with every access's own constant and then keeps ONE address register PER ACCESS
 // (hundreds of them, hoisted out of the tile loop: 230 VGPRs for the smallest instantiation).  Passing the offsets through an
 // empty asm makes them opaque scalar values: region base + lane part is one add, the per-access constants stay immediates.
+// (The launder() of a kernel's Lay* struct does this to every region offset it holds.)
 __device__ __forceinline__ int opaque_s(int x) {
     asm volatile("" : "+s"(x));
     return x;
@@ -62,9 +64,11 @@ __device__ __forceinline__ f4 load_w1_frag(const float *__restrict__ src, int k,
     }
 }
 
-// W2 [128][128] -> LDS rows of kLdh floats: 8 16-B loads per thread, all in flight (global memory takes them at any
-// 4-B alignment), 8-B LDS stores (kLdh is even); pad columns zeroed.  Two halves, so that a caller can put other loads
-// between the request and the use.
+// W2 [128][128] -> LDS rows of kLdh floats: 8 16-B loads per thread, ALL in flight before the first LDS store (the compiler
+// cannot hoist a load over an LDS store it cannot prove disjoint: a load -> store loop pays one memory round trip per
+// iteration), then 8-B LDS stores (kLdh is even) and the two pad columns zeroed.  W2 sits 128 (K1 + 1) floats into the
+// parameter vector, which is only known to be 4-B aligned: the 16-B loads rely on gfx950 global memory taking them at any
+// 4-B alignment.  Separate pieces, so that a caller can put other loads between the request and the use.
 __device__ __forceinline__ void w2_load(float4 (&q)[8], const float *__restrict__ src) {
 #pragma unroll
     for (int u = 0; u < 8; ++u) q[u] = reinterpret_cast<const float4 *>(src)[threadIdx.x + u * kThreads];
@@ -77,15 +81,39 @@ __device__ __forceinline__ void w2_store(float *dst, const float4 (&q)[8]) {
         *reinterpret_cast<float2 *>(p) = make_float2(q[u].x, q[u].y);
         *reinterpret_cast<float2 *>(p + 2) = make_float2(q[u].z, q[u].w);
     }
+}
+__device__ __forceinline__ void w2_zero_pads(float *dst) {
     for (int e = threadIdx.x; e < kH * 2; e += kThreads) dst[(e >> 1) * kLdh + kH + (e & 1)] = 0.f;
 }
 __device__ __forceinline__ void stage_w2_rows(float *dst, const float *__restrict__ src) {
     float4 q[8];
     w2_load(q, src);
     w2_store(dst, q);
+    w2_zero_pads(dst);
 }
 
-int n_cu_dev() {
+// Store row of minibatch row i of a kernel whose arguments G name their rows by {rows, first_row, Mr, tm_T, tm_E}: clamped
+// to a valid row (Mr >= 1; the caller masks), then the id list, or the env-major view of a time-major store (row
+// (i % tm_T) * tm_E + i / tm_T: computed, no load; 32-bit arithmetic, Mr < 2^31 -- a 64-bit division is ~100 instructions),
+// or first_row + i.  TM = 1 / 0: the kernel knows at compile time that it walks / never walks the time-major view;
+// TM = -1: tm_T > 0 decides at run time.  The id list is a uniform BRANCH, not a select, so that the loaded id is not
+// consumed (and waited for) where it is requested.
+template <int TM = -1, typename G>
+__device__ __forceinline__ int64_t rows_row_of(const G &g, int64_t i) {
+    const int64_t ic = i < g.Mr ? i : g.Mr - 1;
+    if constexpr (TM != 1) {
+        if (g.rows) return g.rows[ic];
+    }
+    if (TM == 1 || (TM < 0 && g.tm_T > 0)) {
+        const int t_ = (int)g.tm_T, ii = (int)ic;
+        return (int64_t)(ii % t_) * g.tm_E + ii / t_;
+    }
+    return g.first_row + ic;
+}
+
+// CUs of the current device (cached: one process drives one GPU), and the grid of a persistent rows kernel: one workgroup
+// per CU, never more than there are tiles
+int rows_n_cu() {
     static int cached = 0;
     if (!cached) {
         hipDeviceProp_t p;
@@ -95,10 +123,12 @@ int n_cu_dev() {
     }
     return cached;
 }
+int rows_grid(int64_t tiles) {
+    const int cu = rows_n_cu();
+    return (int)(tiles < cu ? tiles : cu);
+}
 
-constexpr size_t kMaxLds = kTsmMaxLds;
-
-// smallest instantiated KJ (k-groups of 16) covering in_dim; 0 = unsupported
+// smallest instantiated KJ (k-groups of 16) of the critic kernels covering in_dim; 0 = unsupported
 int pick_kj(int in_dim) {
     static const int inst[] = {1, 2, 3, 4, 6, 8, 12, 16, 24};
     for (int kj : inst)

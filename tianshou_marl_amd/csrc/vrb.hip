@@ -148,11 +148,6 @@ __global__ __launch_bounds__(1024) void vrb_unfinished_kernel(const void *state,
     if (threadIdx.x == 0) *n_out = base;
 }
 
-__device__ __forceinline__ int64_t pymod(int64_t a, int64_t m) {
-    int64_t r = a % m;
-    return r < 0 ? r + m : r;
-}
-
 // manager.py:306-331 (prev) / :334-358 (next)
 template <bool NEXT>
 __global__ void vrb_prevnext_kernel(const void *state, int64_t B, int64_t S, int64_t D,

@@ -10,20 +10,18 @@
 // 4 kb + (lane >> 4)) by a 4 x 4 transpose between register index and lane group: v_permlane32_swap + v_permlane16_swap
 // (gfx950), four instructions per 16 units, no LDS round trip (tools/probes/permlane_swap.hip).
 #pragma once
-#include <hip/hip_runtime.h>
+#include "common.h"
 
-typedef float wf4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ wf4 wave_mfma4(float a, float b, wf4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f4 wave_mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // 4 x 4 transpose between the register index and the lane group (lane >> 4): afterwards r[j] of group g holds what r[g] of
 // group j held.  (Inline asm: with this compiler the second result of __builtin_amdgcn_permlane*_swap aliases the first.)
-__device__ __forceinline__ void lane_group_transpose(wf4 &r) {
+__device__ __forceinline__ void lane_group_transpose(f4 &r) {
     float r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %1, %3\n\ts_nop 1\n\t"
                  "v_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3\n\ts_nop 1"
                  : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));
-    r = wf4{r0, r1, r2, r3};
+    r = f4{r0, r1, r2, r3};
 }
 
 // The layer-1 B fragments of the wave's samples straight from LDS-resident env state: fragment kb is element k = 4 kb + (lane >> 4)
@@ -53,9 +51,9 @@ __device__ __forceinline__ void wave_obs_rows_out(float *dst, const float (&x)[K
 // first kb_n (wave-uniform, <= KB) k-steps are issued
 template <int MB, int KB>
 __device__ __forceinline__ void wave_layer(const float *__restrict__ wfrag /* W + (lane & 15) * ld + (lane >> 4) */, int ld,
-                                           const float (&xb)[KB], int kb_n, wf4 (&acc)[MB]) {
+                                           const float (&xb)[KB], int kb_n, f4 (&acc)[MB]) {
 #pragma unroll
-    for (int mb = 0; mb < MB; ++mb) acc[mb] = wf4{0.f, 0.f, 0.f, 0.f};
+    for (int mb = 0; mb < MB; ++mb) acc[mb] = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) {
         if (kb < kb_n) {
@@ -67,10 +65,10 @@ __device__ __forceinline__ void wave_layer(const float *__restrict__ wfrag /* W 
 
 // bias + ReLU in the accumulator layout (FMAX: fmaxf(v, 0) as mlp_tile.h writes it, else v > 0 ? v : 0 as rollout_rows.hip does)
 template <int MB, bool FMAX>
-__device__ __forceinline__ void wave_bias_relu(const float *__restrict__ bias /* b + 4 * (lane >> 4) */, wf4 (&acc)[MB]) {
+__device__ __forceinline__ void wave_bias_relu(const float *__restrict__ bias /* b + 4 * (lane >> 4) */, f4 (&acc)[MB]) {
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
-        const wf4 b = *reinterpret_cast<const wf4 *>(bias + 16 * mb);
+        const f4 b = *reinterpret_cast<const f4 *>(bias + 16 * mb);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float v = acc[mb][i] + b[i];
@@ -81,7 +79,7 @@ __device__ __forceinline__ void wave_bias_relu(const float *__restrict__ bias /*
 
 // ... then the accumulators of 16 units become four B fragments of the next layer
 template <int MB>
-__device__ __forceinline__ void wave_to_frags(wf4 (&acc)[MB], float (&hb)[4 * MB]) {
+__device__ __forceinline__ void wave_to_frags(f4 (&acc)[MB], float (&hb)[4 * MB]) {
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
         lane_group_transpose(acc[mb]);

@@ -624,10 +624,48 @@ def ppo_update_fused(params, obs, act, logp_old, adv, returns, cfg: tsm_ppo_cfg,
     return slabs, scalars
 
 
+# ---- the 128-wide "rows" kernels (csrc/rows128_dev.h): what their wrappers check and allocate alike ----
+def _two_layer_relu(hidden_sizes, act: str) -> int:
+    """The width of two equal hidden layers under ReLU -- the only net the rows kernels are written for -- else 0."""
+    hs = list(hidden_sizes)
+    return hs[0] if act == "relu" and len(hs) == 2 and hs[0] == hs[1] else 0
+
+
+def _mlp3_param_count(in_dim: int, hidden: int, n_out: int) -> int:
+    """w0[H][in] b0[H] w1[H][H] b1[H] w2[n_out][H] b2[n_out]"""
+    return hidden * in_dim + hidden + hidden * hidden + hidden + n_out * hidden + n_out
+
+
+def _rows_ids(name: str, ids_name: str, ids, count_name: str, count, first_row: int, n_rows: int):
+    """(count, ids) of a rows kernel's minibatch: the ids given (i64, at least `count` of them) or rows first_row + i;
+    `count` defaults to every id, or to every row from first_row on."""
+    if count is None:
+        count = ids.numel() if ids is not None else n_rows - first_row
+    if ids is not None:
+        ids = _chk(ids, torch.int64, ids_name)
+        if ids.numel() < count:
+            raise ValueError(f"{name}: {ids_name} holds {ids.numel()} ids, {count_name} = {count}")
+    return count, ids
+
+
+def _rows_slabs(name: str, n_blocks: int, P: int, dev, slabs=None, partial=None):
+    """(grad slabs f32 [n_blocks, P], loss partials f64 [n_blocks * 4]) of a gradient step: the caller's, if they are large
+    enough, else new ones.  P = 0: the partials alone (the slabs live in the step's workspace)."""
+    if slabs is None and P:
+        slabs = torch.empty(n_blocks, P, dtype=torch.float32, device=dev)
+    elif P and slabs.numel() < n_blocks * P:
+        raise ValueError(f"{name}: slabs holds {slabs.numel()} floats, {n_blocks} slabs of {P} need {n_blocks * P}")
+    if partial is None:
+        partial = torch.empty(n_blocks * 4, dtype=torch.float64, device=dev)
+    elif partial.numel() < n_blocks * 4:
+        raise ValueError(f"{name}: partial is too small ({partial.numel()} doubles, {n_blocks} workgroups need {n_blocks * 4})")
+    return slabs, partial
+
+
 def ppo_actor_rows_supported(obs_dim: int, hidden_sizes, n_act: int, act: str = "relu") -> bool:
     """Does the one-launch actor step (csrc/ppo_rows.hip) cover this actor?  obs -> 128 -> 128 -> n_act, ReLU."""
-    hs = list(hidden_sizes)
-    ok = act == "relu" and len(hs) == 2 and hs[0] == hs[1] and bool(call("tsm_ppo_actor_rows_supported", obs_dim, hs[0], n_act))
+    H = _two_layer_relu(hidden_sizes, act)
+    ok = bool(H) and bool(call("tsm_ppo_actor_rows_supported", obs_dim, H, n_act))
     if ok:
         _ppo_rows_init()
     return ok
@@ -656,24 +694,13 @@ def ppo_actor_rows_update(actor_params, obs, act, logp_old, adv, cfg: tsm_ppo_cf
     [n_blocks, 4] = {sum clip objective, 0, sum entropy, 0}).  opt_step_dev (device i64[1]): advanced by one."""
     obs = _chk(obs, torch.float32, "obs")
     D = obs.shape[-1]
-    if M is None:
-        M = perm.numel() if perm is not None else obs.shape[0] - first_row
+    M, perm = _rows_ids("ppo_actor_rows_update", "perm", perm, "M", M, first_row, obs.shape[0])
     if n_blocks is None:
         n_blocks = ppo_actor_rows_grid(M)
     P = actor_params.numel()
     if P != call("tsm_ppo_actor_rows_param_count", D, hidden, n_act):
         raise ValueError(f"ppo_actor_rows_update: {P} actor parameters do not match obs {D} -> {hidden} -> {hidden} -> {n_act}")
-    dev = obs.device
-    if slabs is None:
-        slabs = torch.empty(n_blocks, P, dtype=torch.float32, device=dev)
-    elif slabs.numel() < n_blocks * P:
-        raise ValueError(f"ppo_actor_rows_update: slabs holds {slabs.numel()} floats, {n_blocks} slabs of {P} need {n_blocks * P}")
-    if partial is None:
-        partial = torch.empty(n_blocks * 4, dtype=torch.float64, device=dev)
-    elif partial.numel() < n_blocks * 4:
-        raise ValueError("ppo_actor_rows_update: partial is too small")
-    if perm is not None and perm.numel() < M:
-        raise ValueError(f"ppo_actor_rows_update: perm holds {perm.numel()} sample ids, M = {M}")
+    slabs, partial = _rows_slabs("ppo_actor_rows_update", n_blocks, P, obs.device, slabs, partial)
     call("tsm_ppo_actor_rows_update", ptr(_chk(actor_params, torch.float32, "actor_params")), D, hidden, n_act, ptr(obs),
          ptr(_chk(act, torch.int32, "act")), ptr(None if logp_old is None else _chk(logp_old, torch.float32, "logp_old")),
          ptr(None if adv is None else _chk(adv, torch.float32, "adv")), ptr(perm), first_row, M, ptr(adv_stats), C.byref(cfg),
@@ -683,10 +710,9 @@ def ppo_actor_rows_update(actor_params, obs, act, logp_old, adv, cfg: tsm_ppo_cf
 
 def ppo_critic_rows_supported(in_dim: int, hidden_sizes, n_agent: int, act: str = "relu") -> bool:
     """Does the one-launch critic step (csrc/ppo_rows.hip) cover this critic?  in_dim -> 128 -> 128 -> 1, ReLU."""
-    hs = list(hidden_sizes)
+    H = _two_layer_relu(hidden_sizes, act)
     n_slice = -(-in_dim // 32)
-    ok = (act == "relu" and len(hs) == 2 and hs[0] == hs[1] and n_slice in (1, 2, 3)
-          and bool(call("tsm_ppo_critic_rows_supported", in_dim, hs[0], n_agent)))
+    ok = bool(H) and n_slice in (1, 2, 3) and bool(call("tsm_ppo_critic_rows_supported", in_dim, H, n_agent))
     if ok:
         _ppo_rows_init()
     return ok
@@ -702,24 +728,13 @@ def ppo_critic_rows_update(critic_params, obs_rows, returns, cfg: tsm_ppo_cfg, n
     [n_blocks, 4] = {0, sum vf, 0, 0}).  obs_rows [n, in_dim]: the joint rows (in_dim = n_agent * obs_dim)."""
     obs_rows = _chk(obs_rows, torch.float32, "obs_rows")
     K1 = obs_rows.shape[-1]
-    if Mr is None:
-        Mr = rows.numel() if rows is not None else obs_rows.shape[0] - first_row
+    Mr, rows = _rows_ids("ppo_critic_rows_update", "rows", rows, "Mr", Mr, first_row, obs_rows.shape[0])
     if n_blocks is None:
         n_blocks = ppo_critic_rows_grid(Mr)
     P = critic_params.numel()
     if P != call("tsm_ppo_critic_rows_param_count", K1, hidden):
         raise ValueError(f"ppo_critic_rows_update: {P} critic parameters do not match {K1} -> {hidden} -> {hidden} -> 1")
-    dev = obs_rows.device
-    if slabs is None:
-        slabs = torch.empty(n_blocks, P, dtype=torch.float32, device=dev)
-    elif slabs.numel() < n_blocks * P:
-        raise ValueError("ppo_critic_rows_update: slabs is too small")
-    if partial is None:
-        partial = torch.empty(n_blocks * 4, dtype=torch.float64, device=dev)
-    elif partial.numel() < n_blocks * 4:
-        raise ValueError("ppo_critic_rows_update: partial is too small")
-    if rows is not None and rows.numel() < Mr:
-        raise ValueError("ppo_critic_rows_update: rows holds fewer ids than Mr")
+    slabs, partial = _rows_slabs("ppo_critic_rows_update", n_blocks, P, obs_rows.device, slabs, partial)
     _critic_rows_init(K1, hidden)
     call("tsm_ppo_critic_rows_update", ptr(_chk(critic_params, torch.float32, "critic_params")), K1, hidden, n_agent,
          ptr(obs_rows), ptr(_chk(returns, torch.float32, "returns")), ptr(v_s_old), ptr(rows), first_row, Mr, C.byref(cfg),
@@ -730,9 +745,8 @@ def ppo_critic_rows_update(critic_params, obs_rows, returns, cfg: tsm_ppo_cfg, n
 def critic_rows_forward_supported(in_dim: int, hidden_sizes, n_out: int = 1, act: str = "relu") -> bool:
     """Does the one-launch critic forward (csrc/critic_rows.hip) cover this critic?  in -> 128 -> 128 -> n_out <= 16, ReLU
     (n_out > 1: the value is the mean of the outputs)."""
-    hs = list(hidden_sizes)
-    return (act == "relu" and 1 <= n_out <= 16 and len(hs) == 2 and hs[0] == hs[1]
-            and bool(call("tsm_critic_rows_forward_supported", in_dim, hs[0])))
+    H = _two_layer_relu(hidden_sizes, act)
+    return bool(H) and 1 <= n_out <= 16 and bool(call("tsm_critic_rows_forward_supported", in_dim, H))
 
 
 _critic_rows_ready: set = set()
@@ -757,13 +771,10 @@ def critic_rows_forward(critic_params, obs_rows, hidden: int = 128, rows=None, f
     as it is) when it holds 0."""
     obs_rows = _chk(obs_rows, torch.float32, "obs_rows")
     K1 = obs_rows.shape[-1]
-    if Mr is None:
-        Mr = rows.numel() if rows is not None else obs_rows.shape[0] - first_row
-    if rows is not None and rows.numel() < Mr:
-        raise ValueError(f"critic_rows_forward: rows holds {rows.numel()} ids, Mr = {Mr}")
+    Mr, rows = _rows_ids("critic_rows_forward", "rows", rows, "Mr", Mr, first_row, obs_rows.shape[0])
     if rows is None and first_row + Mr > obs_rows.shape[0]:
         raise ValueError(f"critic_rows_forward: rows [{first_row}, {first_row + Mr}) exceed the {obs_rows.shape[0]} given")
-    if critic_params.numel() != hidden * K1 + hidden + hidden * hidden + hidden + n_out * hidden + n_out:
+    if critic_params.numel() != _mlp3_param_count(K1, hidden, n_out):
         raise ValueError(f"critic_rows_forward: {critic_params.numel()} parameters do not match {K1} -> {hidden} -> {hidden} -> {n_out}")
     _critic_rows_init(K1, hidden)
     if out is None:
@@ -771,7 +782,7 @@ def critic_rows_forward(critic_params, obs_rows, hidden: int = 128, rows=None, f
     elif out.numel() < Mr:
         raise ValueError("critic_rows_forward: out is too small")
     call("tsm_critic_rows_forward", ptr(_chk(critic_params, torch.float32, "critic_params")), K1, hidden, n_out, ptr(obs_rows),
-         ptr(None if rows is None else _chk(rows, torch.int64, "rows")), first_row, Mr,
+         ptr(rows), first_row, Mr,
          ptr(None if run_if is None else _chk(run_if, torch.int32, "run_if")), ptr(out), stream_ptr())
     return out
 
@@ -790,7 +801,7 @@ def _critic_grad_ws(K1: int, hidden: int, n_out: int, Mr: int, td: bool, dev, ws
     key = ("critic_grad", K1, hidden, n_out, Mr, td, bool(split_dw2))
     w = None if ws is None else ws.get(key)
     if w is None:
-        n_rest = hidden + hidden * hidden + hidden + n_out * hidden + n_out
+        n_rest = _mlp3_param_count(K1, hidden, n_out) - hidden * K1
         w = dict(nb=nb, nc=nc, dh1=torch.empty(Mr, hidden, dtype=torch.float32, device=dev),
                  rest=(torch.zeros if split_dw2 else torch.empty)(nb, n_rest, dtype=torch.float32, device=dev),
                  w1=torch.empty(nc, hidden * K1, dtype=torch.float32, device=dev),
@@ -834,17 +845,12 @@ def critic_rows_grad_ppo(critic_params, obs_rows, returns, cfg: tsm_ppo_cfg, n_a
     W2 columns of `rest` stay zero -- `critic_grad_segs` lists the optimizer's segments for either mode."""
     obs_rows = _chk(obs_rows, torch.float32, "obs_rows")
     K1 = obs_rows.shape[-1]
-    if Mr is None:
-        Mr = rows.numel() if rows is not None else obs_rows.shape[0] - first_row
+    Mr, rows = _rows_ids("critic_rows_grad_ppo", "rows", rows, "Mr", Mr, first_row, obs_rows.shape[0])
     if critic_params.numel() != call("tsm_critic_rows_param_count", K1, hidden, 1):
         raise ValueError(f"critic_rows_grad_ppo: {critic_params.numel()} parameters do not match {K1} -> {hidden} -> {hidden} -> 1")
-    if rows is not None and rows.numel() < Mr:
-        raise ValueError("critic_rows_grad_ppo: rows holds fewer ids than Mr")
     _critic_rows_init(K1, hidden)
     w = _critic_grad_ws(K1, hidden, 1, Mr, False, obs_rows.device, ws, split_dw2)
-    part = w["partial"] if partial is None else partial
-    if part.numel() < w["nb"] * 4:
-        raise ValueError("critic_rows_grad_ppo: partial is too small")
+    _, part = _rows_slabs("critic_rows_grad_ppo", w["nb"], 0, None, None, w["partial"] if partial is None else partial)
     call("tsm_critic_rows_grad_ppo", ptr(_chk(critic_params, torch.float32, "critic_params")), ptr(w1_image), K1, hidden, n_agent,
          ptr(obs_rows), ptr(_chk(returns, torch.float32, "returns")), ptr(v_s_old), ptr(rows), first_row, Mr, C.byref(cfg),
          w["nb"], ptr(w["dh1"]), ptr(w.get("h1")), ptr(w.get("dh2")), ptr(w["rest"]), ptr(part), stream_ptr())
@@ -885,7 +891,7 @@ def critic_rows_grad_td(critic_params, joint_store, T: int, E: int, rew, termina
         raise ValueError(f"critic_rows_grad_td: {critic_params.numel()} parameters do not match {K1} -> {hidden} -> {hidden} -> {n_out}")
     _critic_rows_init(K1, hidden)
     w = _critic_grad_ws(K1, hidden, n_out, B, True, joint_store.device, ws)
-    part = w["partial"] if partial is None else partial
+    _, part = _rows_slabs("critic_rows_grad_td", w["nb"], 0, None, None, w["partial"] if partial is None else partial)
     term = terminated.view(torch.uint8) if terminated.dtype == torch.bool else _chk(terminated, torch.uint8, "terminated")
     call("tsm_critic_rows_grad_td", ptr(_chk(critic_params, torch.float32, "critic_params")), None, K1, hidden, n_out,
          ptr(joint_store), T, E, ptr(_chk(rew, torch.float32, "rew")), ptr(term), n_agent, agent,
