@@ -1195,6 +1195,64 @@ int tsm_iqn_head(const float *out, const float *q_next, const float *out_next, c
                  int32_t n_act, int32_t n_online, int32_t n_target, float *returns_out, float *prio, float *d_out,
                  double *partial, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Fully parameterized Quantile Function  (tianshou/algorithm/modelfree/fqf.py; utils/net/discrete.py:220-315; csrc/fqf.hip)
+ * Conventions of the IQN block: a network row is (b, i) = b * num_fractions + i, out f32 [R][num_fractions][n_act]; f [R]
+ * [embedding_dim] is the preprocess net's last LINEAR output and relu_f != 0 applies its ReLU inside the kernel.  The embedding
+ * at the proposed fractions is tsm_iqn_embed_forward / _backward.  Arithmetic is f32 unless said otherwise.
+ * tsm_fqf_check: the bounds of the kernels (num_fractions in [3, 64] -- the interior forward has num_fractions - 1 fractions,
+ *   the embedding takes 2 .. 64 --, embedding_dim a multiple of 16 in [16, 512], n_act in [1, 64]): TSM_ERR_INVALID naming the
+ *   limit.  Needs no device.
+ * tsm_fqf_propose replaces  FractionProposalNetwork.forward (discrete.py:240-253).  One launch.
+ *   Wf [num_fractions][embedding_dim], bf [num_fractions].  logits = Wf g(f) + bf on f32 MFMA (k = 0 .. embedding_dim - 1 in
+ *   order, then the bias), f32.  From there on the row is carried in float64 and every output rounded to f32 once (as
+ *   tsm_dsac_* form their probabilities): e[n] = exp(x[n] - max x), se = sum_k e[k] (k in order), p[n] = e[n] / se,
+ *   logp[n] = (x[n] - max x) - log(se);  taus[0] = 0, taus[k + 1] = taus[k] + p[k], k in order (taus[num_fractions] is what
+ *   the sum gives, not forced to 1);  tau_hats[i] = (taus[i] + taus[i + 1]) / 2;  entropies = -(sum_n p[n] logp[n]), n in order.
+ *   out: taus [R][num_fractions + 1], tau_hats [R][num_fractions], logp [R][num_fractions] (for the head), entropies [R].
+ *   The features are detached (discrete.py:305): there is no d_f.
+ * tsm_fqf_propose_backward replaces  `fraction_optim.step(...)`'s backward through the same lines.  One launch.
+ *   d_logits [R][num_fractions] (tsm_fqf_head).  Into slab z of n_split (the rows ceil(R / n_split) z ..., the partition of
+ *   tsm_iqn_embed_backward): dWf at w_off = d_logits^T g(f) on f32 MFMA, four rows per step in row order; dbf at b_off its column
+ *   sums.  Every slab is written in full, an empty one as zeros.
+ * tsm_fqf_values replaces  `((taus[:, 1:] - taus[:, :-1]).unsqueeze(1) * logits).sum(2)` of FQFPolicy.forward (fqf.py:94-97):
+ *   q[r][a] = sum_i (taus[r][i + 1] - taus[r][i]) * out[r][i][a], i in order, each product rounded (no fma).  q feeds
+ *   tsm_dqn_egreedy and tsm_fqf_head.
+ * tsm_fqf_head replaces  FQF._target_q after its forwards (fqf.py:178-193), `_nstep_return`'s last line
+ *           (algorithm_base.py:796, 1213-1215) and FQF._update_with_batch between `self.policy(batch)` and the two optimizer
+ *           steps (fqf.py:201-247).  One launch.
+ *   out [B][N][n_act]: the online net on obs at tau_hats;  out_tau [B][N - 1][n_act]: the same net at taus[:, 1:-1];
+ *   q_next [B][n_act]: tsm_fqf_values of the ONLINE net on the successor rows;  out_next [B][N][n_act]: the lagged net there
+ *   at the online proposal's tau_hats, or that same online forward when there is no lagged net.
+ *   Quantile part: returns, loss, prio and d_out are tsm_iqn_head's with n_online = n_target = N and fraction tau_hats[b][i],
+ *   in its rounding order; d_out is exactly zero off the taken action.
+ *   Fraction part (fqf.py:227-243), Qh_i = out[b][i][act], Q_i = out_tau[b][i][act], i = 0 .. N - 2:
+ *     v1 = Q_i - Qh_i, s1 = Q_i > (i == 0 ? Qh_0 : Q_{i-1});  v2 = Q_i - Qh_{i+1}, s2 = Q_i < (i == N - 2 ? Qh_{N-1} : Q_{i+1});
+ *     g_{i+1} = (s1 ? v1 : -v1) + (s2 ? v2 : -v2);  with p = expf(logp) and taus [B][N + 1] as tsm_fqf_propose wrote them
+ *     (the fractions at which out_tau was evaluated):
+ *     fraction_loss_b = sum_k g_k taus_k (xor butterfly over the lanes);  G_m = g_{N-1} + g_{N-2} + ... + g_{m+1} in that order;
+ *     Gbar = sum_n p_n G_n (butterfly);  d_logits[b][m] = (p_m (G_m - Gbar) + ent_coef * (p_m (logp_m + entropies[b]))) / B:
+ *     the gradient of mean_b fraction_loss_b - ent_coef * mean_b entropies[b] with respect to the fraction layer's logits.
+ *     The importance weight does not enter the fraction part.
+ *   out: returns f32 [B][N]; prio f32 [B]; d_out f32 [B][N][n_act]; d_logits f32 [B][N]; partial and partial_frac f64
+ *        [2 * ceil(B / TSM_IQN_ROWS_PER_BLOCK)] each = per workgroup {sum loss_b weight, sum mean_i Qh_i} and {sum
+ *        fraction_loss_b, sum entropies[b]}, each for tsm_qmix_finalize.  An action outside [0, n_act) reads nothing: the
+ *        row's quantile loss, prio, q and fraction loss are NaN, its d_out and d_logits rows zero.
+ * ------------------------------------------------------------------------------------------- */
+int tsm_fqf_check(int32_t num_fractions, int32_t embedding_dim, int32_t n_act);
+int tsm_fqf_propose(const float *f, const float *Wf, const float *bf, int64_t R, int32_t num_fractions, int32_t embedding_dim,
+                    int relu_f, float *taus, float *tau_hats, float *logp, float *entropies, void *stream);
+int tsm_fqf_propose_backward(const float *d_logits, const float *f, int64_t R, int32_t num_fractions, int32_t embedding_dim,
+                             int relu_f, int32_t n_split, float *slabs, int64_t slab_stride, int64_t w_off, int64_t b_off,
+                             void *stream);
+int tsm_fqf_values(const float *out, const float *taus, int64_t R, int32_t num_fractions, int32_t n_act, float *q,
+                   void *stream);
+int tsm_fqf_head(const float *out, const float *out_tau, const float *q_next, const float *out_next, const uint8_t *mask_next,
+                 const float *taus, const float *tau_hats, const float *logp, const float *entropies, const int64_t *act, const float *mc,
+                 const float *gpow, const uint8_t *vmask, const float *weight, double ent_coef, int64_t B, int32_t n_act,
+                 int32_t num_fractions, float *returns_out, float *prio, float *d_out, float *d_logits, double *partial,
+                 double *partial_frac, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

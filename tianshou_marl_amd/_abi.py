@@ -286,6 +286,11 @@ SIGNATURES = {
     "tsm_iqn_embed_backward": (_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i32, _int, _p, _i32, _p, _i64, _i64, _i64, _p]),
     "tsm_iqn_values": (_int, [_p, _i64, _i32, _i32, _p, _p]),
     "tsm_iqn_head": (_int, [_p] * 10 + [_i64, _i32, _i32, _i32, _p, _p, _p, _p, _p]),
+    "tsm_fqf_check": (_int, [_i32, _i32, _i32]),
+    "tsm_fqf_propose": (_int, [_p, _p, _p, _i64, _i32, _i32, _int, _p, _p, _p, _p, _p]),
+    "tsm_fqf_propose_backward": (_int, [_p, _p, _i64, _i32, _i32, _int, _i32, _p, _i64, _i64, _i64, _p]),
+    "tsm_fqf_values": (_int, [_p, _p, _i64, _i32, _i32, _p, _p]),
+    "tsm_fqf_head": (_int, [_p] * 14 + [_f64, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "tsm_segtree_bound": (_i64, [_i64]),
     "tsm_segtree_set": (_int, [_p, _p, _i64, _p, _i64, _p, _i64, _p, _p]),
     "tsm_segtree_prefix_sum_idx": (_int, [_p, _i64, _p, _i64, _p, _p]),

@@ -336,14 +336,28 @@ class DQN(DeviceOffPolicyRows, nn.Module):
         d_out, partial, returns, prio = self._head(batch, q, act, None if weight is None else
                                                    to_tensor(weight, dev, torch.float32).reshape(-1))
         model.backward(d_out, w["n_split"], slabs=w["slabs"])
+        self._before_step(batch, w)
         self.optim.step(w["slabs"])
-        slot = result_slot(w, 2)
-        ops.qmix_finalize(partial, B, slot["h"])
+        slot = result_slot(w, self._n_results)
+        self._finalize(batch, partial, B, slot["h"])
         slot["event"].record()
         batch.returns = returns
         batch.weight = prio  # prio-buffer
         slot["event"].synchronize()
-        return self._stats(float(slot["h"][0]))
+        return self._stats_of(slot["h"])
+
+    # What a learner with a second loss changes (FQF): its other gradient and step, the slot's size and what lands in it.
+    _n_results = 2
+
+    def _before_step(self, batch: Batch, w: dict) -> None:
+        """Between the model's backward and its Adam step: nothing here."""
+
+    def _finalize(self, batch: Batch, partial, B: int, h) -> None:
+        """The head's partials into the pinned slot `h`: {loss, mean q}."""
+        ops.qmix_finalize(partial, B, h)
+
+    def _stats_of(self, h) -> TrainingStats:
+        return self._stats(float(h[0]))
 
     def _online_forward(self, batch: Batch, x: torch.Tensor) -> torch.Tensor:
         """The online net on the sampled rows, activations kept for `model.backward`."""

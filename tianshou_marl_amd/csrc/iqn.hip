@@ -200,23 +200,13 @@ __global__ __launch_bounds__(kIThreads) void iqn_head_kernel(
             const bool in = lane < N;
             const float c = (in && ok) ? out[(b * N + lane) * A + ac] : 0.f;
             const float tau = in ? taus[b * N + lane] : 0.f;
-            float ls = 0.f, ps = 0.f, gs = 0.f;
-            for (int j = 0; j < Np; ++j) tsm_quantile_huber(s_ret[w][j] - c, tau, ls, ps, gs);
-            l_row = wave_sum(in ? ls : 0.f) / (float)N * wt;
-            p_row = wave_sum(in ? ps : 0.f) / (float)N;
-            q_row = wave_sum(c) / (float)N;
-            d = -(wt / ((float)N * (float)B)) * gs;
+            tsm_quantile_row(s_ret[w], Np, N, lane, c, tau, wt, B, l_row, p_row, q_row, d);
             if (!ok) l_row = p_row = q_row = nanv;
             if (in) s_d[w][lane] = ok ? d : 0.f;
         }
         __syncthreads();
         if (live) {
-            // the gradient: zero in every other action's slots (and in all of a poisoned row's)
-            float *drow = d_out + b * N * A;
-            for (int x = lane; x < N * A; x += kWave) {
-                const int i = x / A, a = x - i * A;
-                drow[x] = (ok && a == (int)ac) ? s_d[w][i] : 0.f;
-            }
+            tsm_taken_action_scatter(d_out + b * N * A, s_d[w], N, A, ac, ok, lane);
             if (lane == 0) {
                 prio[b] = p_row;
                 acc_l += (double)l_row;

@@ -1,6 +1,7 @@
 // q_head_dev.h -- what the value-based heads share (csrc/dqn.hip, csrc/distq.hip, csrc/iqn.hip, csrc/dsac.hip): the action
 // limit and the row-range check, the greedy action of DiscreteQLearningPolicy.compute_q_value + argmax (dqn.py:140-151), the
-// n-step return rule, the quantile-Huber term and the workgroup's two f64 partials.  One definition each, so every head picks
+// n-step return rule, the quantile-Huber term, the per-row walk and gradient scatter of the heads over per-row fractions and the
+// workgroup's two f64 partials.  One definition each, so every head picks
 // the same a* and rounds the same way, bit for bit.
 #pragma once
 #include "common.h"
@@ -85,6 +86,30 @@ __device__ __forceinline__ void tsm_quantile_huber(float u, float tau, float &ls
     ls += h * kq;
     ps += fabsf(h);
     gs += kq * (u != u ? u : fminf(fmaxf(u, -1.f), 1.f));
+}
+
+// One row of a quantile head over per-row fractions (csrc/iqn.hip, csrc/fqf.hip), one wave per row: lane i < N holds the taken
+// action's online sample c at the fraction tau, s_ret the row's Np targets, walked j = 0 .. Np - 1 in order.  All 64 lanes
+// call it.  -> the row's loss (times its weight wt), priority and mean sample, and this lane's d loss / d c for a batch of B.
+__device__ __forceinline__ void tsm_quantile_row(const float *s_ret, int Np, int N, int lane, float c, float tau, float wt,
+                                                 int64_t B, float &l_row, float &p_row, float &q_row, float &d) {
+    const bool in = lane < N;
+    float ls = 0.f, ps = 0.f, gs = 0.f;
+    for (int j = 0; j < Np; ++j) tsm_quantile_huber(s_ret[j] - c, tau, ls, ps, gs);
+    l_row = wave_sum(in ? ls : 0.f) / (float)N * wt;
+    p_row = wave_sum(in ? ps : 0.f) / (float)N;
+    q_row = wave_sum(c) / (float)N;
+    d = -(wt / ((float)N * (float)B)) * gs;
+}
+
+// The row's gradient drow [N][A] from the N per-sample values s_d: zero in every other action's slots (and, with ok false, in
+// all of a poisoned row's).
+__device__ __forceinline__ void tsm_taken_action_scatter(float *__restrict__ drow, const float *s_d, int N, int A, int64_t ac,
+                                                         bool ok, int lane) {
+    for (int x = lane; x < N * A; x += kWave) {
+        const int i = x / A, a = x - i * A;
+        drow[x] = (ok && a == (int)ac) ? s_d[i] : 0.f;
+    }
 }
 
 // The workgroup's two f64 sums into partial[2 * block + {0, 1}] (tsm_qmix_mix_td's layout, read by tsm_qmix_finalize): lane 0

@@ -1403,6 +1403,119 @@ def iqn_head(out, q_next, out_next, taus, act, mc, gpow, vmask, mask_next=None, 
 
 
 # --------------------------------------------------------------------------------------------
+# Fully parameterized Quantile Function (fqf.py; utils/net/discrete.py:220-315; csrc/fqf.hip)
+# --------------------------------------------------------------------------------------------
+def fqf_check(num_fractions: int, embedding_dim: int = 16, n_act: int = 1) -> None:
+    """The bounds of the FQF kernels (include/tsmarl.h): ValueError naming the limit."""
+    call("tsm_fqf_check", int(num_fractions), int(embedding_dim), int(n_act))
+
+
+def _fqf_propose_shapes(name: str, f, N: int):
+    if f.dim() != 2:
+        raise ValueError(f"{name}: f must be [R, H]")
+    R, H = f.shape
+    fqf_check(N, H)
+    if R < 1:
+        raise ValueError(f"{name}: empty batch")
+    return R, H
+
+
+def fqf_propose(f, Wf, bf, relu_f: bool = False):
+    """FractionProposalNetwork.forward (discrete.py:240-253) in one launch: f [R, H], Wf [N, H], bf [N] ->
+    (taus [R, N + 1], tau_hats [R, N], logp [R, N], entropies [R]); g = relu with relu_f, else the identity."""
+    _dev_only("fqf_propose", f, Wf, bf)
+    if Wf.dim() != 2:
+        raise ValueError("fqf_propose: Wf must be [N, H]")
+    N = Wf.shape[0]
+    R, H = _fqf_propose_shapes("fqf_propose", f, N)
+    f, Wf, bf = _head_args("fqf_propose", R, (("f", f, (R, H), torch.float32), ("Wf", Wf, (N, H), torch.float32),
+                                              ("bf", bf, (N,), torch.float32)), ())
+    dev = f.device
+    taus = torch.empty(R, N + 1, dtype=torch.float32, device=dev)
+    tau_hats, logp = (torch.empty(R, N, dtype=torch.float32, device=dev) for _ in range(2))
+    entropies = torch.empty(R, dtype=torch.float32, device=dev)
+    call("tsm_fqf_propose", ptr(f), ptr(Wf), ptr(bf), R, N, H, int(bool(relu_f)), ptr(taus), ptr(tau_hats), ptr(logp),
+         ptr(entropies), stream_ptr())
+    return taus, tau_hats, logp, entropies
+
+
+def fqf_propose_backward(d_logits, f, n_split: int = 0, slabs=None, slab_stride: int = 0, w_off: int = 0,
+                         b_off: int | None = None, relu_f: bool = False):
+    """The backward of `fqf_propose` from d_logits [R, N] in one launch -> slabs: dWf / dbf fill n_split slabs at w_off /
+    b_off of rows `slab_stride` apart (default: slabs of their own, [n_split, N * H + N])."""
+    _dev_only("fqf_propose_backward", d_logits, f, slabs)
+    if d_logits.dim() != 2:
+        raise ValueError("fqf_propose_backward: d_logits must be [R, N]")
+    N = d_logits.shape[1]
+    R, H = _fqf_propose_shapes("fqf_propose_backward", f, N)
+    d_logits, f = _head_args("fqf_propose_backward", R, (("d_logits", d_logits, (R, N), torch.float32),
+                                                         ("f", f, (R, H), torch.float32)), ())
+    if n_split <= 0:
+        n_split = mlp_n_split(R)
+    if b_off is None:
+        b_off = w_off + N * H
+    if slabs is None:
+        slab_stride = slab_stride or N * H + N
+        slabs = torch.empty(n_split, slab_stride, dtype=torch.float32, device=f.device)
+    elif slab_stride <= 0:
+        slab_stride = slabs.stride(0)
+    if slabs.dim() != 2 or slabs.shape[0] < n_split or slabs.stride(1) != 1 or slabs.stride(0) != slab_stride \
+            or slabs.dtype != torch.float32 or max(w_off + N * H, b_off + N) > slabs.shape[1]:
+        raise ValueError("fqf_propose_backward: slabs must be f32 [n_split, >= the end of both blocks] with rows slab_stride apart")
+    call("tsm_fqf_propose_backward", ptr(d_logits), ptr(f), R, N, H, int(bool(relu_f)), int(n_split), slabs.data_ptr(),
+         int(slab_stride), int(w_off), int(b_off), stream_ptr())
+    return slabs
+
+
+def fqf_values(out, taus, n_act: int):
+    """The fraction-weighted sum of FQFPolicy.forward (fqf.py:94-97) on the sample-major output: out [R * N, A] or [R, N, A],
+    taus [R, N + 1] -> q [R, A], before the action mask."""
+    _dev_only("fqf_values", out, taus)
+    if taus.dim() != 2:
+        raise ValueError("fqf_values: taus must be [R, N + 1]")
+    R, N, A = taus.shape[0], taus.shape[1] - 1, int(n_act)
+    fqf_check(N, 16, A)
+    if out.numel() != R * N * A or out.shape[-1] != A:
+        raise ValueError(f"fqf_values: out must be [{R}, {N}, {A}]")
+    out, taus = _head_args("fqf_values", R, (("out", out.reshape(R, N, A), (R, N, A), torch.float32),
+                                             ("taus", taus, (R, N + 1), torch.float32)), ())
+    q = torch.empty(R, A, dtype=torch.float32, device=out.device)
+    call("tsm_fqf_values", ptr(out), ptr(taus), R, N, A, ptr(q), stream_ptr())
+    return q
+
+
+def fqf_head(out, out_tau, q_next, out_next, taus, tau_hats, logp, entropies, act, mc, gpow, vmask, mask_next=None, weight=None,
+             ent_coef: float = 0.0):
+    """FQF._target_q after its forwards + both losses of FQF._update_with_batch and their gradients (fqf.py:178-193, 201-247) in
+    one launch.  out [B, N, A]: the online net on obs at tau_hats [B, N]; out_tau [B, N - 1, A]: at the interior fractions taus[:, 1:-1] of
+    taus [B, N + 1];
+    q_next [B, A]: `fqf_values` of the online net on the successor rows; out_next [B, N, A]: the lagged net there (that same
+    online forward when there is none); logp [B, N], entropies [B] from `fqf_propose`; the rest as `iqn_head`.
+    -> dict(returns [B, N], prio [B], d_out [B, N, A], d_logits [B, N], partial, partial_frac f64): `qmix_finalize` gives
+    {quantile loss, mean value of the taken action} and {fraction loss, entropy loss}."""
+    _dev_only("fqf_head", out, out_tau, q_next, out_next, taus, tau_hats, logp, entropies, act, mc, gpow, vmask, mask_next, weight)
+    if q_next.dim() != 2 or tau_hats.dim() != 2:
+        raise ValueError("fqf_head: q_next must be [B, A] and tau_hats [B, N]")
+    (B, A), N = q_next.shape, tau_hats.shape[1]
+    fqf_check(N, 16, A)
+    if B < 1:
+        raise ValueError("fqf_head: empty batch")
+    args = _head_args("fqf_head", B, (("out", out, (B, N, A), torch.float32), ("out_tau", out_tau, (B, N - 1, A), torch.float32),
+                                      ("q_next", q_next, (B, A), torch.float32), ("out_next", out_next, (B, N, A), torch.float32),
+                                      ("mask_next", mask_next, (B, A), torch.uint8), ("taus", taus, (B, N + 1), torch.float32),
+                                      ("tau_hats", tau_hats, (B, N), torch.float32),
+                                      ("logp", logp, (B, N), torch.float32)),
+                      (("entropies", entropies, torch.float32),) + _target_rows(act, mc, gpow, vmask, weight))
+    dev = q_next.device
+    res = dict(returns=torch.empty(B, N, dtype=torch.float32, device=dev), prio=torch.empty(B, dtype=torch.float32, device=dev),
+               d_out=torch.empty(B, N, A, dtype=torch.float32, device=dev), d_logits=torch.empty(B, N, dtype=torch.float32, device=dev),
+               partial=_head_partial(B, _abi.IQN_ROWS_PER_BLOCK, dev), partial_frac=_head_partial(B, _abi.IQN_ROWS_PER_BLOCK, dev))
+    call("tsm_fqf_head", *map(ptr, args), float(ent_coef), B, A, N, ptr(res["returns"]), ptr(res["prio"]), ptr(res["d_out"]),
+         ptr(res["d_logits"]), ptr(res["partial"]), ptr(res["partial_frac"]), stream_ptr())
+    return res
+
+
+# --------------------------------------------------------------------------------------------
 # Discrete SAC (discrete_sac.py; sac.py Alpha / AutoAlpha; csrc/dsac.hip)
 # --------------------------------------------------------------------------------------------
 def dsac_check(n_act: int, n_step: int = 1) -> None:

@@ -18,6 +18,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..data.batch import Batch
 
 
 def ref_layer_keys(n_layers: int, scheme: str) -> list[tuple[str, str]]:
@@ -316,8 +317,8 @@ class ImplicitQuantileNet(nn.Module):
 
     def clone_over(self, storage: torch.Tensor) -> "ImplicitQuantileNet":
         """As `FlatMLP.clone_over`."""
-        return ImplicitQuantileNet(self.pre_dims, self.n_act, self.hidden_sizes, self.num_cosines, self.act, self.feature_act,
-                                   device=storage.device, seed=0, storage=storage)
+        return type(self)(self.pre_dims, self.n_act, self.hidden_sizes, self.num_cosines, self.act, self.feature_act,
+                          device=storage.device, seed=0, storage=storage)
 
     def forward(self, x: torch.Tensor, sample_size: int, taus: torch.Tensor | None = None, save: bool = True, seed: int = 0,
                 offset: int = 0, offset_dev: torch.Tensor | None = None):
@@ -376,6 +377,103 @@ class ImplicitQuantileNet(nn.Module):
     def load_reference_state_dict(self, sd, prefix: str = "") -> None:
         for k, v in self.reference_named_views():
             v.copy_(torch.as_tensor(np.asarray(sd[prefix + k])).to(v.device, v.dtype).reshape(v.shape))
+
+
+class FractionProposalNet(nn.Module):
+    """FractionProposalNetwork (discrete.py:220-253) on ONE flat f32 vector [N * H + N]: the linear layer's weight [N, H], then
+    its bias [N]; softmax, cumulative sum and entropy are csrc/fqf.hip.  `feature_act` as `ImplicitQuantileNet`'s: `forward`
+    takes the preprocess net's last LINEAR output and the kernels apply its ReLU."""
+
+    def __init__(self, num_fractions: int, embedding_dim: int, feature_act: bool = True, device: str | torch.device = "cuda",
+                 seed: int | None = None, storage: torch.Tensor | None = None) -> None:
+        super().__init__()
+        N, H = self.num_fractions, self.embedding_dim = int(num_fractions), int(embedding_dim)
+        ops.fqf_check(N, H)
+        self.feature_act = bool(feature_act)
+        n = N * H + N
+        if storage is None:
+            storage = torch.zeros(n, dtype=torch.float32, device=device)
+        elif storage.numel() != n or storage.dtype != torch.float32 or not storage.is_contiguous():
+            raise ValueError(f"FractionProposalNet: storage must be a contiguous f32 vector of {n} elements")
+        self.flat = nn.Parameter(storage, requires_grad=False)
+        self._saved = None
+        self.reset_parameters(seed)
+
+    @property
+    def Wf(self) -> torch.Tensor:
+        return self.flat.data[:self.num_fractions * self.embedding_dim].view(self.num_fractions, self.embedding_dim)
+
+    @property
+    def bf(self) -> torch.Tensor:
+        return self.flat.data[self.num_fractions * self.embedding_dim:]
+
+    @torch.no_grad()
+    def reset_parameters(self, seed: int | None = None) -> None:
+        """discrete.py:235-236: xavier_uniform_(gain=0.01) weight, zero bias."""
+        gen = torch.Generator().manual_seed(seed) if seed is not None else None
+        bound = 0.01 * math.sqrt(6.0 / (self.embedding_dim + self.num_fractions))
+        self.Wf.copy_(torch.empty(self.Wf.shape).uniform_(-bound, bound, generator=gen))
+        self.bf.zero_()
+
+    def clone_over(self, storage: torch.Tensor) -> "FractionProposalNet":
+        """As `FlatMLP.clone_over`."""
+        return FractionProposalNet(self.num_fractions, self.embedding_dim, self.feature_act, device=storage.device, seed=0,
+                                   storage=storage)
+
+    def forward(self, f: torch.Tensor, save: bool = True):
+        """f [R, H] -> (taus [R, N + 1], tau_hats [R, N], logp [R, N], entropies [R])."""
+        f = f.to(self.flat.device, torch.float32).contiguous().reshape(-1, self.embedding_dim)
+        if save:
+            self._saved = f
+        return ops.fqf_propose(f, self.Wf, self.bf, relu_f=self.feature_act)
+
+    def backward(self, d_logits: torch.Tensor, n_split: int = 0, slabs: torch.Tensor | None = None) -> torch.Tensor:
+        """Gradient slabs [n_split, N * H + N] for the features of the last `forward(save=True)`."""
+        if self._saved is None:
+            raise RuntimeError("FractionProposalNet.backward called before forward")
+        return ops.fqf_propose_backward(d_logits, self._saved, n_split, slabs=slabs, relu_f=self.feature_act)
+
+    # ---- reference checkpoint compatibility ---------------------------------------------------------------------------
+    def reference_named_views(self) -> list[tuple[str, torch.Tensor]]:
+        return [("net.weight", self.Wf), ("net.bias", self.bf)]
+
+    def to_reference_state_dict(self) -> OrderedDict:
+        return OrderedDict((k, v.detach().clone().cpu()) for k, v in self.reference_named_views())
+
+    @torch.no_grad()
+    def load_reference_state_dict(self, sd, prefix: str = "") -> None:
+        for k, v in self.reference_named_views():
+            v.copy_(torch.as_tensor(np.asarray(sd[prefix + k])).to(v.device, v.dtype).reshape(v.shape))
+
+
+class FullQuantileNet(ImplicitQuantileNet):
+    """FullQuantileFunction (discrete.py:256-315): an `ImplicitQuantileNet` evaluated where a `FractionProposalNet` says."""
+
+    def forward(self, x: torch.Tensor, propose_model: FractionProposalNet, fractions: Batch | None = None,  # type: ignore[override]
+                save: bool = True, training: bool = False):
+        """x [R, D] -> (out [R * N, A] at tau_hats, fractions = Batch(taus, tau_hats, entropies, logp), out_tau
+        [R * (N - 1), A] at taus[:, 1:-1] when `training`, else None).  The preprocess net runs once; `fractions` None: proposed
+        on its features.  With `save` the forward at tau_hats is the one `backward` differentiates; the interior pass keeps
+        nothing."""
+        x = x.to(self.flat.device, torch.float32).contiguous().reshape(-1, self.pre_dims[0])
+        f = FlatMLP.forward(self.preprocess, x, save=save)
+        if fractions is None:
+            taus, tau_hats, logp, entropies = propose_model.forward(f, save=save)
+            fractions = Batch(taus=taus, tau_hats=tau_hats, entropies=entropies, logp=logp)
+        taus, tau_hats = fractions.taus, fractions.tau_hats
+        R, N = x.shape[0], tau_hats.shape[1]
+        if tuple(tau_hats.shape) != (R, N) or tuple(taus.shape) != (R, N + 1):
+            raise ValueError(f"FullQuantileNet: fractions must hold taus [{R}, N + 1] and tau_hats [{R}, N]")
+        ops.fqf_check(N, self.embedding_dim, self.n_act)
+        e, phi = ops.iqn_embed_forward(f, tau_hats, self.We, self.be, relu_f=self.feature_act)
+        out = FlatMLP.forward(self.last, e, save=save)
+        if save:
+            self._saved = (f, phi, tau_hats.contiguous())
+        out_tau = None
+        if training:
+            e_tau, _ = ops.iqn_embed_forward(f, taus[:, 1:-1].contiguous(), self.We, self.be, relu_f=self.feature_act)
+            out_tau = FlatMLP.forward(self.last, e_tau, save=False)
+        return out, fractions, out_tau
 
 
 class MLPActorCritic(nn.Module):
