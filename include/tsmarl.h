@@ -1253,6 +1253,61 @@ int tsm_fqf_head(const float *out, const float *out_tau, const float *q_next, co
                  int32_t num_fractions, float *returns_out, float *prio, float *d_out, float *d_logits, double *partial,
                  double *partial_frac, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Rainbow: NoisyLinear layers and dueling streams  (tianshou/algorithm/modelfree/rainbow.py; utils/net/discrete.py:318-375;
+ * utils/net/common.py:319-364; csrc/rainbow.hip)
+ * A net is ONE flat f32 vector [P] in the reference module's `parameters()` order, described by a table of its layers
+ * (tsm_noisy_net, a HOST struct passed by pointer and handed to the kernels by value):
+ *   noisy layer  mu_W [out][in] | sigma_W [out][in] | mu_bias [out] | sigma_bias [out] | eps_p [in] | eps_q [out]   at `off`
+ *   plain layer  weight [out][in] | bias [out]                                                                      at `off`
+ * and its EFFECTIVE vector [P_eff] holds W [out][in] | b [out] per layer at `eff_off`, the layout of tsm_mlp_* (trunk, then
+ * the Q stream, then the V stream).  `slot_off` numbers the layer's noise slots (eps_p then eps_q) among all slots of the net.
+ * All arithmetic is f32, every product rounded (no fma).
+ * tsm_rainbow_check: the table's bounds (1 .. TSM_NOISY_MAX_LAYERS layers, in / out in [1, 65536], the three offsets of every
+ *   layer exactly where the layers before it end, the totals P, P_eff and n_slots): TSM_ERR_INVALID naming the limit.  Every
+ *   entry point below runs it first, so no kernel reads or writes outside [0, P) / [0, P_eff).  Needs no device.
+ * tsm_noisy_sample replaces  NoisyLinear.sample / .f (discrete.py:358-365) for every noisy layer of a net.  One launch.
+ *   Slot s gets sign(x) * sqrtf(|x|), x ~ N(0, 1): Philox block (seed ^ a key of this site's own, counter = offset +
+ *   *offset_dev, sub = s / 4) gives words w0 .. w3; u1 = ((w >> 8) + 1) / 2^24 in (0, 1], u2 = (w >> 8) / 2^24;
+ *   r = sqrtf(-2 logf(u1)); slots 4k, 4k + 1 = r cosf(2 pi u2), r sinf(2 pi u2) of (w0, w1), slots 4k + 2, 4k + 3 of (w2, w3).
+ *   Only the distribution is the reference's (it draws with torch.randn), not the numbers.
+ * tsm_noisy_compose replaces  the weight / bias lines of NoisyLinear.forward (discrete.py:368-373) for every layer.  One launch.
+ *   training != 0: W[o][i] = mu_W[o][i] + sigma_W[o][i] * (eps_q[o] * eps_p[i]),  b[o] = mu_bias[o] + sigma_bias[o] * eps_q[o];
+ *   training == 0: W = mu_W, b = mu_bias.  A plain layer is copied.  eps = 0 gives mu bit for bit (mu + 0 = mu).
+ * tsm_noisy_grad replaces  autograd through the same lines.  One launch.  eff_slabs [n_split][P_eff] -> slabs [n_split][P],
+ *   slab by slab:  d mu_W = dW;  d sigma_W = dW * (eps_q[o] * eps_p[i]);  d mu_bias = db;  d sigma_bias = db * eps_q[o]
+ *   (training == 0: both sigma blocks +0.0);  the eps_p / eps_q slots +0.0;  a plain layer is copied.
+ * tsm_dueling_combine replaces  `q - q.mean(dim=1, keepdim=True) + v` (common.py:360-364) on q [R][n_act][n_atoms],
+ *   v [R][n_atoms]:  s = q[r][0][n] + q[r][1][n] + ... in action order, out[r][a][n] = (q[r][a][n] - s / n_act) + v[r][n].
+ *   out is the raw [R][n_act * n_atoms] of tsm_distq_values / tsm_c51_head (bounds: tsm_distq_check).
+ * tsm_dueling_combine_backward:  s = sum_a d[r][a][n] in action order;  d_q[r][a][n] = d[r][a][n] - s / n_act;  d_v[r][n] = s.
+ * tsm_dueling_features replaces  the last activation of the dueling Net's trunk (`MLP(output_dim=0)` ends in its
+ *   activation, a FlatMLP linearly): f = relu(z), n elements.
+ * tsm_dueling_features_backward joins the two streams' input gradients (tsm_mlp_input_grad):
+ *   d_z = z > 0 ? d_fq + d_fv : 0.
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_NOISY_MAX_LAYERS 24
+typedef struct tsm_noisy_layer {
+    int64_t off, eff_off, slot_off;
+    int32_t in, out, noisy, _pad;
+} tsm_noisy_layer;
+typedef struct tsm_noisy_net {
+    int32_t n_layers, _pad;
+    int64_t P, P_eff, n_slots;
+    tsm_noisy_layer layer[TSM_NOISY_MAX_LAYERS];
+} tsm_noisy_net;
+int tsm_rainbow_check(const tsm_noisy_net *net);
+int tsm_noisy_sample(const tsm_noisy_net *net, float *flat, uint64_t seed, uint64_t offset, const uint64_t *offset_dev,
+                     void *stream);
+int tsm_noisy_compose(const tsm_noisy_net *net, const float *flat, int training, float *eff, void *stream);
+int tsm_noisy_grad(const tsm_noisy_net *net, const float *flat, const float *eff_slabs, int32_t n_split, int training,
+                   float *slabs, void *stream);
+int tsm_dueling_combine(const float *q, const float *v, int64_t R, int32_t n_act, int32_t n_atoms, float *out, void *stream);
+int tsm_dueling_combine_backward(const float *d, int64_t R, int32_t n_act, int32_t n_atoms, float *d_q, float *d_v,
+                                 void *stream);
+int tsm_dueling_features(const float *z, int64_t n, float *f, void *stream);
+int tsm_dueling_features_backward(const float *z, const float *d_fq, const float *d_fv, int64_t n, float *d_z, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

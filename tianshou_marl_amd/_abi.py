@@ -124,6 +124,20 @@ class tsm_mlp_desc(C.Structure):
     _fields_ = [("n_layers", C.c_int32), ("act", C.c_int32), ("dims", C.c_int32 * 9)]
 
 
+NOISY_MAX_LAYERS = 24  # include/tsmarl.h TSM_NOISY_MAX_LAYERS
+
+
+class tsm_noisy_layer(C.Structure):
+    _fields_ = [("off", C.c_int64), ("eff_off", C.c_int64), ("slot_off", C.c_int64), ("n_in", C.c_int32), ("n_out", C.c_int32),
+                ("noisy", C.c_int32), ("_pad", C.c_int32)]
+
+
+class tsm_noisy_net(C.Structure):
+    """include/tsmarl.h: the layer table of a RainbowNet (a host struct; the kernels take it by value)."""
+    _fields_ = [("n_layers", C.c_int32), ("_pad", C.c_int32), ("P", C.c_int64), ("P_eff", C.c_int64), ("n_slots", C.c_int64),
+                ("layer", tsm_noisy_layer * NOISY_MAX_LAYERS)]
+
+
 _p, _i64, _i32, _f64, _int, _u64 = C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int, C.c_uint64
 
 # name -> (restype, argtypes); must list every function declared in include/tsmarl.h
@@ -291,6 +305,14 @@ SIGNATURES = {
     "tsm_fqf_propose_backward": (_int, [_p, _p, _i64, _i32, _i32, _int, _i32, _p, _i64, _i64, _i64, _p]),
     "tsm_fqf_values": (_int, [_p, _p, _i64, _i32, _i32, _p, _p]),
     "tsm_fqf_head": (_int, [_p] * 14 + [_f64, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p]),
+    "tsm_rainbow_check": (_int, [C.POINTER(tsm_noisy_net)]),
+    "tsm_noisy_sample": (_int, [C.POINTER(tsm_noisy_net), _p, _u64, _u64, _p, _p]),
+    "tsm_noisy_compose": (_int, [C.POINTER(tsm_noisy_net), _p, _int, _p, _p]),
+    "tsm_noisy_grad": (_int, [C.POINTER(tsm_noisy_net), _p, _p, _i32, _int, _p, _p]),
+    "tsm_dueling_combine": (_int, [_p, _p, _i64, _i32, _i32, _p, _p]),
+    "tsm_dueling_combine_backward": (_int, [_p, _i64, _i32, _i32, _p, _p, _p]),
+    "tsm_dueling_features": (_int, [_p, _i64, _p, _p]),
+    "tsm_dueling_features_backward": (_int, [_p, _p, _p, _i64, _p, _p]),
     "tsm_segtree_bound": (_i64, [_i64]),
     "tsm_segtree_set": (_int, [_p, _p, _i64, _p, _i64, _p, _i64, _p, _p]),
     "tsm_segtree_prefix_sum_idx": (_int, [_p, _i64, _p, _i64, _p, _p]),

@@ -3,12 +3,13 @@ from .distq import C51, QRDQN, C51Policy, QRDQNPolicy
 from .dqn import DQN, DiscreteQLearningPolicy
 from .iqn import IQN, IQNPolicy
 from .fqf import FQF, FQFPolicy, FQFTrainingStats
+from .rainbow import RainbowDQN, RainbowPolicy
 from .dsac import Alpha, AutoAlpha, DiscreteSAC, DiscreteSACPolicy, DiscreteSACTrainingStats, FixedAlpha
 from .pg import A2C, Reinforce
 from .ppo import PPO, policy_within_training_step
 from .ppo_generic import GenericPPO
 
 __all__ = ["PPO", "A2C", "Reinforce", "GenericPPO", "DQN", "DiscreteQLearningPolicy", "C51", "C51Policy", "QRDQN",
-           "QRDQNPolicy", "IQN", "IQNPolicy", "FQF", "FQFPolicy", "FQFTrainingStats",
+           "QRDQNPolicy", "IQN", "IQNPolicy", "FQF", "FQFPolicy", "FQFTrainingStats", "RainbowDQN", "RainbowPolicy",
            "DiscreteSAC", "DiscreteSACPolicy", "DiscreteSACTrainingStats", "Alpha", "FixedAlpha", "AutoAlpha",
            "policy_within_training_step"]

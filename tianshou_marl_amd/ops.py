@@ -1516,6 +1516,134 @@ def fqf_head(out, out_tau, q_next, out_next, taus, tau_hats, logp, entropies, ac
 
 
 # --------------------------------------------------------------------------------------------
+# Rainbow: NoisyLinear layers and dueling streams (rainbow.py; utils/net/discrete.py:318-375; common.py:319-364;
+# csrc/rainbow.hip)
+# --------------------------------------------------------------------------------------------
+def noisy_net_table(layers) -> _abi.tsm_noisy_net:
+    """The layer table of include/tsmarl.h for `layers` = [(in, out, noisy)] in the net's `parameters()` order: every layer's
+    offsets in the flat vector, in the effective vector and among the noise slots, and the three totals."""
+    layers = [(int(i), int(o), int(bool(z))) for i, o, z in layers]
+    if not 1 <= len(layers) <= _abi.NOISY_MAX_LAYERS:
+        raise ValueError(f"noisy_net_table: {len(layers)} layers outside [1, {_abi.NOISY_MAX_LAYERS}]")
+    t = _abi.tsm_noisy_net()
+    t.n_layers = len(layers)
+    off = eff = slot = 0
+    for l, (i, o, z) in enumerate(layers):
+        L = t.layer[l]
+        L.off, L.eff_off, L.slot_off, L.n_in, L.n_out, L.noisy = off, eff, slot, i, o, z
+        off += 2 * i * o + 3 * o + i if z else i * o + o
+        eff += i * o + o
+        slot += i + o if z else 0
+    t.P, t.P_eff, t.n_slots = off, eff, slot
+    return t
+
+
+def rainbow_check(table: _abi.tsm_noisy_net) -> None:
+    """The bounds of a layer table (include/tsmarl.h: tsm_rainbow_check): ValueError naming the limit.  Needs no device."""
+    call("tsm_rainbow_check", C.byref(table))
+
+
+def _noisy_flat(name: str, table, flat):
+    rainbow_check(table)
+    _dev_only(name, flat)
+    flat = _chk(flat, torch.float32, "flat")
+    if flat.dim() != 1 or flat.numel() != table.P:
+        raise ValueError(f"{name}: flat must be a vector of {table.P} elements")
+    return flat
+
+
+def noisy_sample(table, flat, seed: int, offset: int = 0, offset_dev=None):
+    """NoisyLinear.sample (discrete.py:358-365) for every noisy layer of the net, in place in `flat`: slot s gets
+    sign(x) sqrt(|x|), x ~ N(0, 1) from Philox at counter offset + *offset_dev under a key of its own."""
+    rainbow_check(table)
+    _dev_only("noisy_sample", flat, offset_dev)
+    if flat.dtype != torch.float32 or flat.dim() != 1 or flat.numel() != table.P or not flat.is_contiguous():
+        raise ValueError(f"noisy_sample: flat must be a contiguous f32 vector of {table.P} elements (it is written in place)")
+    call("tsm_noisy_sample", C.byref(table), ptr(flat), seed & (2**64 - 1), offset & (2**64 - 1), ptr(offset_dev), stream_ptr())
+    return flat
+
+
+def noisy_compose(table, flat, training: bool, out=None):
+    """The effective parameters of every layer (discrete.py:368-373) -> eff f32 [P_eff] in `FlatMLP` layout."""
+    flat = _noisy_flat("noisy_compose", table, flat)
+    if out is None:
+        out = torch.empty(table.P_eff, dtype=torch.float32, device=flat.device)
+    elif out.dtype != torch.float32 or out.dim() != 1 or out.numel() != table.P_eff or not out.is_contiguous():
+        raise ValueError(f"noisy_compose: out must be a contiguous f32 vector of {table.P_eff} elements")
+    _dev_only("noisy_compose", out)
+    call("tsm_noisy_compose", C.byref(table), ptr(flat), int(bool(training)), ptr(out), stream_ptr())
+    return out
+
+
+def noisy_grad(table, flat, eff_slabs, training: bool, slabs=None):
+    """Gradient slabs over the effective layout [n_split, P_eff] -> slabs over the flat layout [n_split, P], slab by slab:
+    d mu = d, d sigma = d * noise (zeros when not training), the noise slots +0.0."""
+    flat = _noisy_flat("noisy_grad", table, flat)
+    _dev_only("noisy_grad", eff_slabs, slabs)
+    eff_slabs = _chk(eff_slabs, torch.float32, "eff_slabs")
+    if eff_slabs.dim() != 2 or eff_slabs.shape[1] != table.P_eff or eff_slabs.shape[0] < 1:
+        raise ValueError(f"noisy_grad: eff_slabs must be [n_split, {table.P_eff}]")
+    n_split = eff_slabs.shape[0]
+    if slabs is None:
+        slabs = torch.empty(n_split, table.P, dtype=torch.float32, device=flat.device)
+    elif tuple(slabs.shape) != (n_split, table.P) or slabs.dtype != torch.float32 or not slabs.is_contiguous():
+        raise ValueError(f"noisy_grad: slabs must be a contiguous f32 [{n_split}, {table.P}]")
+    call("tsm_noisy_grad", C.byref(table), ptr(flat), ptr(eff_slabs), n_split, int(bool(training)), ptr(slabs), stream_ptr())
+    return slabs
+
+
+def _dueling_shapes(name: str, x, n_act: int, n_atoms: int):
+    A, N = int(n_act), int(n_atoms)
+    distq_check(A, N)
+    if x.dim() != 2 or x.shape[1] != A * N:
+        raise ValueError(f"{name}: the action stream must be [R, {A} * {N}]")
+    return x.shape[0], A, N
+
+
+def dueling_combine(q, v, n_act: int, n_atoms: int):
+    """`q - q.mean(dim=1, keepdim=True) + v` (common.py:360-364): q [R, A * N], v [R, N] -> out [R, A * N], the raw output the
+    distributional heads take."""
+    R, A, N = _dueling_shapes("dueling_combine", q, n_act, n_atoms)
+    if tuple(v.shape) != (R, N):
+        raise ValueError(f"dueling_combine: v must be [{R}, {N}]")
+    _dev_only("dueling_combine", q, v)
+    out = torch.empty(R, A * N, dtype=torch.float32, device=q.device)
+    call("tsm_dueling_combine", ptr(_chk(q, torch.float32, "q")), ptr(_chk(v, torch.float32, "v")), R, A, N, ptr(out), stream_ptr())
+    return out
+
+
+def dueling_combine_backward(d_out, n_act: int, n_atoms: int):
+    """The backward of `dueling_combine`: d_out [R, A * N] -> (d_q [R, A * N], d_v [R, N])."""
+    R, A, N = _dueling_shapes("dueling_combine_backward", d_out, n_act, n_atoms)
+    _dev_only("dueling_combine_backward", d_out)
+    d_q = torch.empty(R, A * N, dtype=torch.float32, device=d_out.device)
+    d_v = torch.empty(R, N, dtype=torch.float32, device=d_out.device)
+    call("tsm_dueling_combine_backward", ptr(_chk(d_out, torch.float32, "d_out")), R, A, N, ptr(d_q), ptr(d_v), stream_ptr())
+    return d_q, d_v
+
+
+def dueling_features(z):
+    """The last activation of the dueling net's trunk: z [R, H] -> relu(z)."""
+    _dev_only("dueling_features", z)
+    z = _chk(z, torch.float32, "z")
+    f = torch.empty_like(z)
+    call("tsm_dueling_features", ptr(z), z.numel(), ptr(f), stream_ptr())
+    return f
+
+
+def dueling_features_backward(z, d_fq, d_fv):
+    """The two streams' input gradients joined behind the trunk's last activation: d_z = z > 0 ? d_fq + d_fv : 0."""
+    _dev_only("dueling_features_backward", z, d_fq, d_fv)
+    if tuple(d_fq.shape) != tuple(z.shape) or tuple(d_fv.shape) != tuple(z.shape):
+        raise ValueError(f"dueling_features_backward: both gradients must be {list(z.shape)}")
+    z = _chk(z, torch.float32, "z")
+    d_z = torch.empty_like(z)
+    call("tsm_dueling_features_backward", ptr(z), ptr(_chk(d_fq, torch.float32, "d_fq")), ptr(_chk(d_fv, torch.float32, "d_fv")),
+         z.numel(), ptr(d_z), stream_ptr())
+    return d_z
+
+
+# --------------------------------------------------------------------------------------------
 # Discrete SAC (discrete_sac.py; sac.py Alpha / AutoAlpha; csrc/dsac.hip)
 # --------------------------------------------------------------------------------------------
 def dsac_check(n_act: int, n_step: int = 1) -> None:

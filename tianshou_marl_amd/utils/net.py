@@ -476,6 +476,197 @@ class FullQuantileNet(ImplicitQuantileNet):
         return out, fractions, out_tau
 
 
+class RainbowNet(nn.Module):
+    """The reference's `Net(num_atoms=N, dueling_param=(Q, V), linear_layer=NoisyLinear)` (common.py:246-369 around
+    discrete.py:318-375, as test/discrete/test_rainbow.py:97-107 builds it) on ONE flat f32 vector in the module's
+    `parameters()` order: the layers of `model`, then of `Q`, then of `V`; a noisy layer is mu_W, sigma_W, mu_bias, sigma_bias,
+    eps_p, eps_q (the noise vectors are `nn.Parameter(requires_grad=False)` there and so belong to the vector), a plain one
+    weight, bias.  Before every forward `tsm_noisy_compose` writes the EFFECTIVE weights of all layers into a private vector of
+    `FlatMLP` layout; the trunk and the two streams are `FlatMLP`s over slices of it (csrc/dense.hip), joined by the kernels of
+    csrc/rainbow.hip.  The softmax over atoms stays in the head kernels: `forward` returns the raw [R, A * N].
+
+    `noisy_std` None: plain linear layers.  `dueling` False: one chain obs -> hidden -> A * N.  Noise acts only in torch
+    training mode (`self.training`); in eval mode the net is its `mu`."""
+
+    def __init__(self, obs_dim: int, hidden_sizes, n_act: int, num_atoms: int = 51, q_hidden=(), v_hidden=(),
+                 dueling: bool = True, noisy_std: float | None = 0.5, device: str | torch.device = "cuda",
+                 seed: int | None = None, storage: torch.Tensor | None = None) -> None:
+        super().__init__()
+        self.obs_dim, self.n_act, self.num_atoms = int(obs_dim), int(n_act), int(num_atoms)
+        self.hidden_sizes = tuple(int(h) for h in hidden_sizes)
+        self.q_hidden, self.v_hidden = tuple(int(h) for h in q_hidden), tuple(int(h) for h in v_hidden)
+        self.dueling, self.noisy_std = bool(dueling), None if noisy_std is None else float(noisy_std)
+        A, N = self.n_act, self.num_atoms
+        ops.distq_check(A, N)
+        if self.dueling:
+            if not self.hidden_sizes:
+                raise ValueError("RainbowNet: the dueling streams need a trunk: hidden_sizes must not be empty")
+            H = self.hidden_sizes[-1]
+            chains = [[self.obs_dim, *self.hidden_sizes], [H, *self.q_hidden, A * N], [H, *self.v_hidden, N]]
+        else:
+            if self.q_hidden or self.v_hidden:
+                raise ValueError("RainbowNet: q_hidden / v_hidden belong to the dueling streams (dueling=False)")
+            chains = [[self.obs_dim, *self.hidden_sizes, A * N]]
+        self._chains = chains
+        noisy = self.noisy_std is not None
+        self._layers = [(c[i], c[i + 1], noisy) for c in chains for i in range(len(c) - 1)]
+        self.table = ops.noisy_net_table(self._layers)
+        ops.rainbow_check(self.table)
+        P = int(self.table.P)
+        if storage is None:
+            storage = torch.zeros(P, dtype=torch.float32, device=device)
+        elif storage.numel() != P or storage.dtype != torch.float32 or not storage.is_contiguous():
+            raise ValueError(f"RainbowNet: storage must be a contiguous f32 vector of {P} elements")
+        self.flat = nn.Parameter(storage, requires_grad=False)
+        # the effective parameters: not trained, not saved -- rewritten by every forward
+        self.eff = torch.zeros(int(self.table.P_eff), dtype=torch.float32, device=storage.device)
+        self._parts, o = [], 0
+        for c in chains:
+            n = ops.mlp_param_count(ops.mlp_desc(c, "relu"))
+            self._parts.append((o, FlatMLP(c, "relu", device=storage.device, seed=0, storage=self.eff[o:o + n])))
+            o += n
+        self.trunk = self._parts[0][1]
+        self.Q, self.V = (self._parts[1][1], self._parts[2][1]) if self.dueling else (None, None)
+        self.dims = [self.obs_dim, A * N]   # what the policies ask of a Q-network: input width, outputs per sample
+        self._saved = None
+        self._eff_slabs: dict = {}
+        self.reset_parameters(seed)
+
+    # ---- views ------------------------------------------------------------------------------------------------------------
+    @property
+    def n_slots(self) -> int:
+        return int(self.table.n_slots)
+
+    def layer_views(self, flat: torch.Tensor | None = None) -> list[dict]:
+        """Per layer {name: view} of `flat` (None: the net's own vector; else any vector of its layout, e.g. a summed
+        gradient), in `parameters()` order."""
+        flat = self.flat.data if flat is None else flat
+        out = []
+        for l, (i, o, z) in enumerate(self._layers):
+            p = int(self.table.layer[l].off)
+            blocks = ([("mu_W", (o, i)), ("sigma_W", (o, i)), ("mu_bias", (o,)), ("sigma_bias", (o,)), ("eps_p", (i,)), ("eps_q", (o,))]
+                      if z else [("weight", (o, i)), ("bias", (o,))])
+            d = {}
+            for name, shp in blocks:
+                n = int(np.prod(shp))
+                d[name] = flat[p:p + n].view(shp)
+                p += n
+            out.append(d)
+        return out
+
+    def noise(self, flat: torch.Tensor | None = None) -> torch.Tensor:
+        """The noise slots in slot order (per noisy layer eps_p then eps_q), as one vector [n_slots]."""
+        vs = [v[k].reshape(-1) for v in self.layer_views(flat) for k in ("eps_p", "eps_q") if k in v]
+        return torch.cat(vs) if vs else torch.zeros(0, dtype=torch.float32, device=self.flat.device)
+
+    @torch.no_grad()
+    def set_noise(self, eps) -> None:
+        """Load given noise, slot order as `noise()`: for tests and checkpoints."""
+        eps = torch.as_tensor(np.asarray(eps, np.float32) if not isinstance(eps, torch.Tensor) else eps).reshape(-1)
+        if eps.numel() != self.n_slots:
+            raise ValueError(f"RainbowNet.set_noise: {eps.numel()} values for {self.n_slots} noise slots")
+        eps, o = eps.to(self.flat.device, torch.float32), 0
+        for v in self.layer_views():
+            for k in ("eps_p", "eps_q"):
+                if k in v:
+                    v[k].copy_(eps[o:o + v[k].numel()])
+                    o += v[k].numel()
+
+    def sample(self, seed: int, offset: int = 0, offset_dev: torch.Tensor | None = None) -> None:
+        """NoisyLinear.sample of every noisy layer, on the device (tsm_noisy_sample at Philox counter offset + *offset_dev)."""
+        if self.n_slots:
+            ops.noisy_sample(self.table, self.flat.data, seed, offset=offset, offset_dev=offset_dev)
+
+    @torch.no_grad()
+    def reset_parameters(self, seed: int | None = None) -> None:
+        """NoisyLinear.reset (discrete.py:351-356: mu uniform in +-1 / sqrt(in), sigma = noisy_std / sqrt(in)) and a first
+        draw of the noise as `.f` forms it; plain layers get torch's nn.Linear default."""
+        gen = torch.Generator().manual_seed(seed) if seed is not None else None
+        for (i, o, z), v in zip(self._layers, self.layer_views()):
+            bound = 1.0 / math.sqrt(i)
+            for k in ("mu_W", "mu_bias") if z else ("weight", "bias"):
+                v[k].copy_(torch.empty(v[k].shape).uniform_(-bound, bound, generator=gen))
+            if z:
+                v["sigma_W"].fill_(self.noisy_std / math.sqrt(i))
+                v["sigma_bias"].fill_(self.noisy_std / math.sqrt(i))
+                for k in ("eps_p", "eps_q"):
+                    x = torch.randn(v[k].shape, generator=gen)
+                    v[k].copy_(x.sign() * x.abs().sqrt())
+
+    def clone_over(self, storage: torch.Tensor) -> "RainbowNet":
+        """As `FlatMLP.clone_over`."""
+        return RainbowNet(self.obs_dim, self.hidden_sizes, self.n_act, self.num_atoms, self.q_hidden, self.v_hidden, self.dueling,
+                          self.noisy_std, device=storage.device, seed=0, storage=storage)
+
+    # ---- forward / backward -------------------------------------------------------------------------------------------------
+    def forward(self, x: torch.Tensor, save: bool = True) -> torch.Tensor:
+        """x [..., D] -> raw [R, A * N].  The effective weights are composed by `self.training`, then trunk -> features ->
+        Q, V -> combine (without dueling: the one chain)."""
+        x = x.to(self.flat.device, torch.float32).contiguous().reshape(-1, self.obs_dim)
+        training = bool(self.training)
+        ops.noisy_compose(self.table, self.flat.data, training, out=self.eff)
+        z = FlatMLP.forward(self.trunk, x, save=save)
+        if self.dueling:
+            f = ops.dueling_features(z)
+            q = FlatMLP.forward(self.Q, f, save=save)
+            v = FlatMLP.forward(self.V, f, save=save)
+            out = ops.dueling_combine(q, v, self.n_act, self.num_atoms)
+        else:
+            out = z
+        if save:
+            self._saved = (z, training)
+        elif self._saved is not None:
+            self._saved = False   # the effective weights are no longer those of the saved forward
+        return out
+
+    def backward(self, d_out: torch.Tensor, n_split: int = 0, slabs: torch.Tensor | None = None) -> torch.Tensor:
+        """Gradient slabs [n_split, P] of the whole flat vector for the last `forward(save=True)` (`FlatMLP.backward`'s
+        contract): the combine's backward, the streams' weight slabs and input gradients, the feature join, the trunk's slabs
+        -- all over the effective layout --, then `tsm_noisy_grad` onto the flat layout.  No forward may come between."""
+        if self._saved is None:
+            raise RuntimeError("RainbowNet.backward called before forward")
+        if self._saved is False:
+            raise RuntimeError("RainbowNet.backward must follow its forward(save=True): a later forward recomposed the weights")
+        z, training = self._saved
+        R, P, Pe = z.shape[0], int(self.table.P), int(self.table.P_eff)
+        if n_split <= 0:
+            n_split = ops.mlp_n_split(R)
+        if slabs is None:
+            slabs = torch.empty(n_split, P, dtype=torch.float32, device=self.flat.device)
+        elif tuple(slabs.shape) != (n_split, P) or not slabs.is_contiguous():
+            raise ValueError(f"RainbowNet.backward: slabs must be a contiguous [{n_split}, {P}]")
+        eff_slabs = self._eff_slabs.get(n_split)
+        if eff_slabs is None:
+            eff_slabs = self._eff_slabs[n_split] = torch.empty(n_split, Pe, dtype=torch.float32, device=self.flat.device)
+        d_out = d_out.reshape(R, self.dims[-1]).contiguous()
+        if self.dueling:
+            H = self.hidden_sizes[-1]
+            d_q, d_v = ops.dueling_combine_backward(d_out, self.n_act, self.num_atoms)
+            self.Q.backward(d_q, n_split, slabs=eff_slabs[:, self._parts[1][0]:], slab_stride=Pe)
+            self.V.backward(d_v, n_split, slabs=eff_slabs[:, self._parts[2][0]:], slab_stride=Pe)
+            d_z = ops.dueling_features_backward(z, self.Q.input_grad(d_q, 0, H), self.V.input_grad(d_v, 0, H))
+        else:
+            d_z = d_out
+        self.trunk.backward(d_z, n_split, slabs=eff_slabs, slab_stride=Pe)
+        return ops.noisy_grad(self.table, self.flat.data, eff_slabs, training, slabs=slabs)
+
+    # ---- reference checkpoint compatibility ---------------------------------------------------------------------------
+    def reference_named_views(self) -> list[tuple[str, torch.Tensor]]:
+        """[(key, view)] in `parameters()` order under the reference's names: `model.model.{2 i}`, `Q.model.{2 i}`,
+        `V.model.{2 i}` (every MLP is Linear, activation, Linear, ...), each with `.mu_W` ... `.eps_q` or `.weight`, `.bias`
+        (tests/golden/rainbow.npz, sd_*)."""
+        stems = [f"{name}.model.{2 * i}" for name, c in zip(("model", "Q", "V"), self._chains) for i in range(len(c) - 1)]
+        return [(f"{s}.{k}", t) for s, v in zip(stems, self.layer_views()) for k, t in v.items()]
+
+    def to_reference_state_dict(self) -> OrderedDict:
+        return OrderedDict((k, v.detach().clone().cpu()) for k, v in self.reference_named_views())
+
+    @torch.no_grad()
+    def load_reference_state_dict(self, sd, prefix: str = "") -> None:
+        for k, v in self.reference_named_views():
+            v.copy_(torch.as_tensor(np.asarray(sd[prefix + k])).to(v.device, v.dtype).reshape(v.shape))
+
+
 class MLPActorCritic(nn.Module):
     """Actor and critic MLPs of ARBITRARY widths under one flat parameter vector (`ActorCritic(actor, critic)`,
     common.py:461-474: one optimizer, one global gradient-norm clip).  Layout = actor parameters then critic parameters,
