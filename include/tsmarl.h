@@ -1143,7 +1143,71 @@ int tsm_dsac_alpha_step(const double *entropy_partial, int32_t n_blocks, int64_t
                         double eps, double weight_decay, float *alpha_dev, float *out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Implicit Quantile Network  (tianshou/algorithm/modelfree/iqn.py; utils/net/discrete.py:127-217; csrc/iqn.hip)
+ * Continuous-action actor-critics: DDPG, TD3, SAC  (tianshou/algorithm/modelfree/ddpg.py, td3.py, sac.py;
+ * utils/net/continuous.py; csrc/cac.hip)
+ * The actors emit raw (pre-tanh) outputs f32 [B][act_dim]; a critic reads rows [obs | act] of W = D + act_dim floats and emits
+ * one Q value per row.  One launch each, one wave per row with action component k in lane k, no host reads; every stochastic
+ * entry reads its standard normals from a buffer z f32 [B][act_dim] (tsm_cac_normal's, or a recorded draw).  Sums over the
+ * action components are the xor butterfly in float64; loss sums leave as per-workgroup float64 pairs in tsm_qmix_mix_td's
+ * layout, partial f64 [2 * ceil(B / TSM_CAC_ROWS_PER_BLOCK)], for tsm_qmix_finalize.  Two runs give the same bits.
+ * tsm_cac_check: act_dim in [1, TSM_CAC_MAX_ACT_DIM], n_step >= 1: TSM_ERR_INVALID naming the limit.
+ * tsm_cac_normal: z_out f32 [n] <- standard normals, Box-Muller on Philox(seed ^ a key of its own, offset + *offset_dev)
+ *   with the block of four draws as third counter word (offset_dev nullable).
+ * tsm_cac_det_action replaces  `max_action * tanh(.)` of ContinuousActorDeterministic.forward (continuous.py:86-88) and
+ *           TD3's target smoothing (td3.py:196-199).
+ *   rows_out[b * W + col0 + k] = max_action tanh(raw[b][k]) + clamp(policy_noise z[b][k], -noise_clip, noise_clip)
+ *   (z nullable: no noise; noise_clip <= 0: no clamp; the sum is not clamped to the action bounds, as the reference).
+ *   one_minus_tanh2_out f32 [B][act_dim] (nullable) <- 1 - tanh^2(raw), the backward's factor.
+ * tsm_sac_action replaces  the epilogue of ContinuousActorProbabilistic.forward and SACPolicy.forward
+ *           (continuous.py:238-247, sac.py:114-123).
+ *   mu_raw[b * ld_mu + k], sigma_raw[b * ld_sigma + k] (ld_sigma = 0: one state-independent row);
+ *   mu = max_action tanh(mu_raw) (unbounded != 0: mu_raw);  sigma = exp(clamp(sigma_raw, -20, 2));  x = mu + sigma z
+ *   (z nullable: the mode);  a = tanh(x) -> rows_out[b * W + col0 + k];
+ *   logp_out f32 [B] (nullable) = sum_k Normal(mu, sigma).log_prob(x) - sum_k log(1 - a^2 + finfo(float32).eps).
+ * tsm_cac_target replaces  _target_q_compute_value (ddpg.py:314-325, td3.py:94-102, sac.py:298-302) after the forwards, and
+ *           `_nstep_return`'s last line.  target_q = min(q1_next, q2_next) (q2_next nullable: q1_next) - alpha logp_next
+ *   (logp_next nullable: nothing; each step rounded to float32);  returns_out f32 [B] by tsm_dqn_td_head's rounding rule.
+ * tsm_cac_critic_head replaces  _minimize_critic_squared_loss (ddpg.py:267-285) between the forward and optimizer.step, for
+ *           one critic (q2 null) or two.  td_i = q_i - returns in float64;  dq_i f32 [B] = 2 td_i weight / B (weight
+ *   nullable: 1);  prio f32 [B] = td_1, or (td_1 + td_2) / 2;  partial = {sum td_1^2 weight, sum td_2^2 weight}.
+ * tsm_cac_det_actor_head replaces  actor_loss = -critic(obs, actor(obs)).mean() and its backward down to the actor's raw
+ *           output (ddpg.py:406, td3.py:216).  dq_da[b * ld + k] = d Q / d a (tsm_mlp_input_grad with d_out = 1);
+ *   d_raw_out f32 [B][act_dim] = -dq_da max_action one_minus_tanh2 / B;  partial = {sum -q_pi, 0}.
+ * tsm_sac_actor_head replaces  SAC's actor loss and its backward (sac.py:315-322) and the entropy AutoAlpha.update reads
+ *           (:325).  mu_raw / sigma_raw / z as tsm_sac_action took them (the action terms are formed again from them);
+ *   q1a, q2a f32 [B] (q2a nullable): the critics on [obs | a];  dq1_da, dq2_da [b * ld_g + k]: their input gradients with
+ *   d_out = 1.  loss_b = alpha logp - min(q1a, q2a); the minimum's gradient goes to the smaller critic, half to each at a tie
+ *   (torch.min's backward).  d_mu_out / d_sigma_out [b * ld_d + k] = d mean_b(loss_b) / d mu_raw, d sigma_raw (zero past the
+ *   clamp; csrc/cac.hip derives the closed form);  logp_out f32 [B] (nullable);  partial = {sum loss_b, sum -logp}: the pair
+ *   tsm_dsac_alpha_step reads.
+ * tsm_cac_col_sum: the gradient of a state-independent sigma row (`sigma_param`, continuous.py:222) from the head's per-row
+ *   d_sigma: slabs_out[k] = sum_b d[b * ld + k] (float64, fixed order), slabs_out[s * slab_stride + k] = 0 for the slabs
+ *   1 <= s < n_slab (n_slab <= 64): the sigma columns of an actor's gradient slabs, ready for tsm_adam_step.
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_CAC_MAX_ACT_DIM 64
+#define TSM_CAC_ROWS_PER_BLOCK 16
+int tsm_cac_check(int32_t act_dim, int32_t n_step);
+int tsm_cac_normal(float *z_out, int64_t n, uint64_t seed, uint64_t offset, const uint64_t *offset_dev, void *stream);
+int tsm_cac_det_action(const float *raw, const float *z, int64_t B, int32_t act_dim, double max_action, double policy_noise,
+                       double noise_clip, float *rows_out, int64_t W, int32_t col0, float *one_minus_tanh2_out, void *stream);
+int tsm_sac_action(const float *mu_raw, int64_t ld_mu, const float *sigma_raw, int64_t ld_sigma, const float *z, int64_t B,
+                   int32_t act_dim, double max_action, int32_t unbounded, float *rows_out, int64_t W, int32_t col0,
+                   float *logp_out, void *stream);
+int tsm_cac_col_sum(const float *d, int64_t ld, int64_t B, int32_t act_dim, int32_t n_slab, float *slabs_out,
+                    int64_t slab_stride, void *stream);
+int tsm_cac_target(const float *q1_next, const float *q2_next, const float *logp_next, const float *alpha_dev,
+                   const float *mc, const float *gpow, const uint8_t *vmask, int64_t B, float *returns_out, void *stream);
+int tsm_cac_critic_head(const float *q1, const float *q2, const float *returns, const float *weight, int64_t B, float *dq1,
+                        float *dq2, float *prio, double *partial, void *stream);
+int tsm_cac_det_actor_head(const float *dq_da, int64_t ld, const float *one_minus_tanh2, const float *q_pi, int64_t B,
+                           int32_t act_dim, double max_action, float *d_raw_out, double *partial, void *stream);
+int tsm_sac_actor_head(const float *mu_raw, int64_t ld_mu, const float *sigma_raw, int64_t ld_sigma, const float *z,
+                       const float *q1a, const float *q2a, const float *dq1_da, const float *dq2_da, int64_t ld_g,
+                       const float *alpha_dev, int64_t B, int32_t act_dim, double max_action, int32_t unbounded,
+                       float *d_mu_out, float *d_sigma_out, int64_t ld_d, float *logp_out, double *partial, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Implicit Quantile Network (tianshou/algorithm/modelfree/iqn.py; utils/net/discrete.py:127-217; csrc/iqn.hip)
  * A network row is (b, s) = b * sample_size + s: out f32 [R][sample_size][n_act] (the reference's [B, A, S] logits are its
  * transposed view), e / phi f32 [R * sample_size][embedding_dim], taus f32 [R][sample_size].  The MLPs before and after the
  * embedding run through tsm_mlp_forward / tsm_mlp_backward / tsm_mlp_input_grad.

@@ -20,6 +20,8 @@ ABI_VERSION = 4  # include/tsmarl.h TSM_ABI_VERSION: bumped whenever a signature
 DQN_ROWS_PER_BLOCK = 256  # csrc/dqn.hip: one row per thread of the TD head (tsm_dqn_partial_elems counts by it)
 DISTQ_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_DISTQ_ROWS_PER_BLOCK: rows per workgroup of the C51 / QR-DQN heads
 DSAC_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_DSAC_ROWS_PER_BLOCK: rows per workgroup of the Discrete SAC heads
+CAC_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_CAC_ROWS_PER_BLOCK: rows per workgroup of the continuous actor-critic heads
+CAC_MAX_ACT_DIM = 64  # include/tsmarl.h TSM_CAC_MAX_ACT_DIM: one lane per action component
 IQN_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_IQN_ROWS_PER_BLOCK: rows per workgroup of the IQN head
 TSM_OK, TSM_ERR_INVALID, TSM_ERR_HIP, TSM_ERR_MALFORMED_BUFFER, TSM_ERR_UNSUPPORTED = range(5)
 
@@ -294,6 +296,15 @@ SIGNATURES = {
     "tsm_dsac_critic_head": (_int, [_p] * 5 + [_i64, _i32, _p, _p, _p, _p, _p]),
     "tsm_dsac_actor_head": (_int, [_p] * 4 + [_i64, _i32, _p, _p, _p, _p]),
     "tsm_dsac_alpha_step": (_int, [_p, _i32, _i64, _p, _p, _p, _p] + [_f64] * 6 + [_p, _p, _p]),
+    "tsm_cac_check": (_int, [_i32, _i32]),
+    "tsm_cac_normal": (_int, [_p, _i64, _u64, _u64, _p, _p]),
+    "tsm_cac_det_action": (_int, [_p, _p, _i64, _i32, _f64, _f64, _f64, _p, _i64, _i32, _p, _p]),
+    "tsm_sac_action": (_int, [_p, _i64, _p, _i64, _p, _i64, _i32, _f64, _i32, _p, _i64, _i32, _p, _p]),
+    "tsm_cac_col_sum": (_int, [_p, _i64, _i64, _i32, _i32, _p, _i64, _p]),
+    "tsm_cac_target": (_int, [_p] * 7 + [_i64, _p, _p]),
+    "tsm_cac_critic_head": (_int, [_p] * 4 + [_i64, _p, _p, _p, _p, _p]),
+    "tsm_cac_det_actor_head": (_int, [_p, _i64, _p, _p, _i64, _i32, _f64, _p, _p, _p]),
+    "tsm_sac_actor_head": (_int, [_p, _i64, _p, _i64] + [_p] * 5 + [_i64, _p, _i64, _i32, _f64, _i32, _p, _p, _i64, _p, _p, _p]),
     "tsm_iqn_check": (_int, [_i32, _i32, _i32, _i32]),
     "tsm_iqn_taus": (_int, [_i64, _i32, _u64, _u64, _p, _p, _p]),
     "tsm_iqn_embed_forward": (_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i32, _int, _p, _p, _p]),

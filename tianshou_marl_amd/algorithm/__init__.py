@@ -5,6 +5,8 @@ from .iqn import IQN, IQNPolicy
 from .fqf import FQF, FQFPolicy, FQFTrainingStats
 from .rainbow import RainbowDQN, RainbowPolicy
 from .dsac import Alpha, AutoAlpha, DiscreteSAC, DiscreteSACPolicy, DiscreteSACTrainingStats, FixedAlpha
+from .cac import (DDPG, SAC, TD3, ContinuousDeterministicPolicy, DDPGTrainingStats, GaussianNoise, SACPolicy,
+                  SACTrainingStats, TD3TrainingStats)
 from .pg import A2C, Reinforce
 from .ppo import PPO, policy_within_training_step
 from .ppo_generic import GenericPPO
@@ -12,4 +14,6 @@ from .ppo_generic import GenericPPO
 __all__ = ["PPO", "A2C", "Reinforce", "GenericPPO", "DQN", "DiscreteQLearningPolicy", "C51", "C51Policy", "QRDQN",
            "QRDQNPolicy", "IQN", "IQNPolicy", "FQF", "FQFPolicy", "FQFTrainingStats", "RainbowDQN", "RainbowPolicy",
            "DiscreteSAC", "DiscreteSACPolicy", "DiscreteSACTrainingStats", "Alpha", "FixedAlpha", "AutoAlpha",
+           "DDPG", "TD3", "SAC", "ContinuousDeterministicPolicy", "SACPolicy", "DDPGTrainingStats", "TD3TrainingStats",
+           "SACTrainingStats", "GaussianNoise",
            "policy_within_training_step"]

@@ -198,7 +198,8 @@ class DeviceOffPolicyRows:
         batch.idx_n, batch.mc, batch.gpow, batch.vmask = idx_n, mc, gpow, vmask
         if "obs" not in batch:  # rows straight from the device stores (DQN.update)
             batch.obs = buffer._gather(buffer.obs_store, idx)[:, col].contiguous()
-            batch.act = buffer._gather(buffer.act_store, idx)[:, col].contiguous().to(torch.int64)
+            act = buffer._gather(buffer.act_store, idx)[:, col].contiguous()
+            batch.act = act if act.is_floating_point() else act.to(torch.int64)  # a Box store (act_dim): f32 [I, k]
         return idx, idx_n, col
 
     @staticmethod

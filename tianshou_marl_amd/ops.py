@@ -1733,6 +1733,225 @@ def dsac_alpha_step(entropy_partial, B: int, log_alpha, exp_avg, exp_avg_sq, ste
 
 
 # --------------------------------------------------------------------------------------------
+# Continuous-action actor-critics: DDPG, TD3, SAC (ddpg.py, td3.py, sac.py, utils/net/continuous.py; csrc/cac.hip)
+# --------------------------------------------------------------------------------------------
+def cac_check(act_dim: int, n_step: int = 1) -> None:
+    """The bounds of the continuous actor-critic kernels (include/tsmarl.h): ValueError naming the limit."""
+    call("tsm_cac_check", int(act_dim), int(n_step))
+
+
+def cac_normal(n: int, seed: int, offset: int = 0, offset_dev=None, device="cuda", out=None):
+    """n standard normals f32 from Philox (seed, offset + *offset_dev) under this draw's own key."""
+    if out is None:
+        out = torch.empty(int(n), dtype=torch.float32, device=device)
+    _dev_only("cac_normal", out, offset_dev)
+    out = _chk(out, torch.float32, "out")
+    if out.numel() != int(n) or not out.is_contiguous():
+        raise ValueError(f"cac_normal: out must be contiguous with {int(n)} entries")
+    call("tsm_cac_normal", ptr(out), int(n), seed & (2**64 - 1), offset & (2**64 - 1), ptr(offset_dev), stream_ptr())
+    return out
+
+
+def _cac_raw(name: str, raw, width: int | None = None):
+    """raw [B, Ad * k] f32 contiguous in HBM -> (raw, B, width of a row)."""
+    _dev_only(name, raw)
+    if raw.dim() != 2 or raw.shape[0] < 1 or not raw.is_contiguous() or raw.dtype != torch.float32:
+        raise ValueError(f"{name}: the actor's raw output must be a contiguous f32 [B, n] with B >= 1")
+    if width is not None and raw.shape[1] != width:
+        raise ValueError(f"{name}: expected rows of {width} floats, got {raw.shape[1]}")
+    return raw, raw.shape[0], raw.shape[1]
+
+
+def _cac_rows_out(name: str, out, B: int, Ad: int, col0: int):
+    """The critic-input rows an action is written into: out [B, W] (None: a new [B, Ad], col0 = 0) -> (out, W)."""
+    if out is None:
+        if col0 != 0:
+            raise ValueError(f"{name}: col0 needs out")
+        return None, Ad
+    _dev_only(name, out)
+    if out.dim() != 2 or out.shape[0] != B or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous f32 [{B}, W]")
+    if not 0 <= col0 <= out.shape[1] - Ad:
+        raise ValueError(f"{name}: columns [{col0}, {col0 + Ad}) leave the row of {out.shape[1]} floats")
+    return out, out.shape[1]
+
+
+def _cac_z(name: str, z, B: int, Ad: int):
+    if z is None:
+        return None
+    _dev_only(name, z)
+    if tuple(z.shape) != (B, Ad):
+        raise ValueError(f"{name}: z must be [{B}, {Ad}]")
+    return _chk(z, torch.float32, "z")
+
+
+def cac_det_action(raw, max_action: float = 1.0, z=None, policy_noise: float = 0.0, noise_clip: float = 0.0, out=None,
+                   col0: int = 0, want_backward: bool = False):
+    """`max_action * tanh(raw)` (continuous.py:86-88), with z also TD3's smoothing noise clamp(policy_noise * z, +-noise_clip)
+    (td3.py:196-199; noise_clip <= 0: no clamp), written into columns [col0, col0 + Ad) of out [B, W] (None: a new [B, Ad]).
+    -> out, or (out, 1 - tanh^2 [B, Ad]) with want_backward."""
+    raw, B, Ad = _cac_raw("cac_det_action", raw)
+    cac_check(Ad)
+    out, W = _cac_rows_out("cac_det_action", out, B, Ad, col0)
+    if out is None:
+        out = torch.empty(B, Ad, dtype=torch.float32, device=raw.device)
+    z = _cac_z("cac_det_action", z, B, Ad)
+    omt2 = torch.empty(B, Ad, dtype=torch.float32, device=raw.device) if want_backward else None
+    call("tsm_cac_det_action", ptr(raw), ptr(z), B, Ad, float(max_action), float(policy_noise), float(noise_clip), ptr(out), W,
+         int(col0), ptr(omt2), stream_ptr())
+    return (out, omt2) if want_backward else out
+
+
+def _sac_raw(name: str, raw, sigma_param):
+    """The probabilistic actor's output: raw [B, 2 Ad] = [mu_raw | sigma_raw] (conditioned sigma), or raw [B, Ad] beside
+    sigma_param f32 [Ad].  -> (raw, B, Ad, ld, the sigma tensor, its pointer, ld_sigma)."""
+    if sigma_param is None:
+        raw, B, n = _cac_raw(name, raw)
+        if n % 2:
+            raise ValueError(f"{name}: a conditioned-sigma actor emits [mu_raw | sigma_raw], an even number of columns")
+        return raw, B, n // 2, n, raw, raw.data_ptr() + 4 * (n // 2), n
+    raw, B, n = _cac_raw(name, raw)
+    _dev_only(name, sigma_param)
+    sg = _chk(sigma_param, torch.float32, "sigma_param").reshape(-1)
+    if sg.numel() != n:
+        raise ValueError(f"{name}: sigma_param must have {n} entries")
+    return raw, B, n, n, sg, sg.data_ptr(), 0
+
+
+def sac_action(raw, z=None, max_action: float = 1.0, unbounded: bool = False, sigma_param=None, out=None, col0: int = 0):
+    """ContinuousActorProbabilistic.forward's epilogue and SACPolicy.forward (continuous.py:238-247, sac.py:114-123): raw as
+    `_sac_raw` takes it, z [B, Ad] standard normals (None: the mode).  -> (act = tanh(mu + sigma z) in columns
+    [col0, col0 + Ad) of out [B, W] (None: a new [B, Ad]), logp f32 [B])."""
+    raw, B, Ad, ld, sg, sg_ptr, ld_s = _sac_raw("sac_action", raw, sigma_param)
+    cac_check(Ad)
+    out, W = _cac_rows_out("sac_action", out, B, Ad, col0)
+    if out is None:
+        out = torch.empty(B, Ad, dtype=torch.float32, device=raw.device)
+    z = _cac_z("sac_action", z, B, Ad)
+    logp = torch.empty(B, dtype=torch.float32, device=raw.device)
+    call("tsm_sac_action", ptr(raw), ld, sg_ptr, ld_s, ptr(z), B, Ad, float(max_action), int(bool(unbounded)), ptr(out), W,
+         int(col0), ptr(logp), stream_ptr())
+    return out, logp
+
+
+def cac_col_sum(d, slabs):
+    """The gradient of a state-independent sigma row: d f32 [B, Ad] (`sac_actor_head`'s d_sigma) -> slabs [n_split, Ad], a
+    (strided) view of the sigma columns of the actor's gradient slabs: slab 0 <- the column sums, the others zero."""
+    _dev_only("cac_col_sum", d, slabs)
+    if d.dim() != 2 or d.shape[0] < 1:
+        raise ValueError("cac_col_sum: d must be [B, Ad] with B >= 1")
+    B, Ad = d.shape
+    cac_check(Ad)
+    d = _cac_grad("cac_col_sum", d, B, Ad, "d")
+    if slabs.dim() != 2 or slabs.shape[1] != Ad or slabs.dtype != torch.float32 or slabs.stride(1) != 1 or slabs.shape[0] < 1:
+        raise ValueError(f"cac_col_sum: slabs must be f32 [n_split, {Ad}] with unit column stride")
+    call("tsm_cac_col_sum", ptr(d), Ad, B, Ad, slabs.shape[0], slabs.data_ptr(), slabs.stride(0) if slabs.shape[0] > 1 else Ad,
+         stream_ptr())
+    return slabs
+
+
+def cac_target(q1_next, q2_next, mc, gpow, vmask, logp_next=None, alpha_dev=None, out=None):
+    """min of the lagged critics (q2_next None: the single critic), minus alpha * logp_next for SAC, then the n-step line
+    (td3.py:94-102, sac.py:298-302, algorithm_base.py:1213-1215).  -> returns f32 [B]."""
+    _dev_only("cac_target", q1_next, q2_next, mc, gpow, vmask, logp_next, alpha_dev, out)
+    B = q1_next.numel()
+    if B < 1:
+        raise ValueError("cac_target: empty batch")
+    if (logp_next is None) != (alpha_dev is None):
+        raise ValueError("cac_target: logp_next and alpha_dev come together")
+    args = _head_args("cac_target", B, (), (("q1_next", q1_next, torch.float32), ("q2_next", q2_next, torch.float32),
+                                            ("logp_next", logp_next, torch.float32), ("mc", mc, torch.float32),
+                                            ("gpow", gpow, torch.float32), ("vmask", vmask, torch.uint8)))
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=q1_next.device)
+    elif out.numel() != B or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"cac_target: out must be a contiguous f32 [{B}]")
+    call("tsm_cac_target", *map(ptr, args[:3]), ptr(None if alpha_dev is None else _chk(alpha_dev, torch.float32, "alpha_dev")),
+         *map(ptr, args[3:]), B, ptr(out), stream_ptr())
+    return out
+
+
+def cac_critic_head(q1, q2, returns, weight=None):
+    """_minimize_critic_squared_loss between the forward and the step (ddpg.py:267-285) for one critic (q2 None) or two.
+    -> dict(dq1, dq2 [B] (dq2 None with one critic), prio [B] = td1 or (td1 + td2) / 2 with td = q - returns, partial f64):
+    `qmix_finalize(partial, B, out)` gives {critic1_loss, critic2_loss}."""
+    _dev_only("cac_critic_head", q1, q2, returns, weight)
+    B = q1.numel()
+    if B < 1:
+        raise ValueError("cac_critic_head: empty batch")
+    args = _head_args("cac_critic_head", B, (), (("q1", q1, torch.float32), ("q2", q2, torch.float32),
+                                                 ("returns", returns, torch.float32), ("weight", weight, torch.float32)))
+    dev = q1.device
+    out = dict(dq1=torch.empty(B, dtype=torch.float32, device=dev),
+               dq2=None if q2 is None else torch.empty(B, dtype=torch.float32, device=dev),
+               prio=torch.empty(B, dtype=torch.float32, device=dev), partial=_head_partial(B, _abi.CAC_ROWS_PER_BLOCK, dev))
+    call("tsm_cac_critic_head", *map(ptr, args), B, ptr(out["dq1"]), ptr(out["dq2"]), ptr(out["prio"]), ptr(out["partial"]),
+         stream_ptr())
+    return out
+
+
+def _cac_grad(name: str, g, B: int, Ad: int, what: str):
+    _dev_only(name, g)
+    if tuple(g.shape) != (B, Ad):
+        raise ValueError(f"{name}: {what} must be [{B}, {Ad}]")
+    return _chk(g, torch.float32, what)
+
+
+def cac_det_actor_head(dq_da, one_minus_tanh2, q_pi, max_action: float = 1.0, out=None):
+    """actor_loss = -mean Q(s, pi(s)) and its gradient w.r.t. the actor's raw output (ddpg.py:406, td3.py:216): dq_da [B, Ad]
+    = d Q / d a (`mlp_input_grad` with d_out = 1), one_minus_tanh2 from `cac_det_action`, q_pi [B].
+    -> dict(d_raw [B, Ad], partial f64): `qmix_finalize(partial, B, out)` gives {actor_loss, 0}."""
+    _dev_only("cac_det_actor_head", dq_da, one_minus_tanh2, q_pi, out)
+    if dq_da.dim() != 2 or dq_da.shape[0] < 1:
+        raise ValueError("cac_det_actor_head: dq_da must be [B, Ad] with B >= 1")
+    B, Ad = dq_da.shape
+    cac_check(Ad)
+    dq_da = _cac_grad("cac_det_actor_head", dq_da, B, Ad, "dq_da")
+    omt2 = _cac_grad("cac_det_actor_head", one_minus_tanh2, B, Ad, "one_minus_tanh2")
+    (q_pi,) = _head_args("cac_det_actor_head", B, (), (("q_pi", q_pi, torch.float32),))
+    if out is None:
+        out = torch.empty(B, Ad, dtype=torch.float32, device=dq_da.device)
+    elif tuple(out.shape) != (B, Ad) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"cac_det_actor_head: out must be a contiguous f32 [{B}, {Ad}]")
+    partial = _head_partial(B, _abi.CAC_ROWS_PER_BLOCK, dq_da.device)
+    call("tsm_cac_det_actor_head", ptr(dq_da), Ad, ptr(omt2), ptr(q_pi), B, Ad, float(max_action), ptr(out), ptr(partial),
+         stream_ptr())
+    return dict(d_raw=out, partial=partial)
+
+
+def sac_actor_head(raw, z, q1a, q2a, dq1_da, dq2_da, alpha_dev, max_action: float = 1.0, unbounded: bool = False,
+                   sigma_param=None, out=None):
+    """SAC's actor loss mean(alpha logp - min(q1a, q2a)) with its closed-form backward (sac.py:315-322) and the entropy
+    AutoAlpha reads (:325).  raw, z, sigma_param as `sac_action` took them; q1a, q2a [B] (q2a None: one critic) and their
+    input gradients dq1_da, dq2_da [B, Ad] with d_out = 1.  -> dict(d_raw (the shape of raw: [d mu_raw | d sigma_raw] with
+    conditioned sigma), d_sigma ([B, Ad] per row for a sigma_param, else None), logp [B], partial f64):
+    `qmix_finalize` gives {actor_loss, mean -logp}; the partials are what `AutoAlpha.step_device` takes."""
+    raw, B, Ad, ld, sg, sg_ptr, ld_s = _sac_raw("sac_actor_head", raw, sigma_param)
+    cac_check(Ad)
+    _dev_only("sac_actor_head", q1a, q2a, alpha_dev, out)
+    if (q2a is None) != (dq2_da is None):
+        raise ValueError("sac_actor_head: q2a and dq2_da come together")
+    z = _cac_z("sac_actor_head", z, B, Ad)
+    g1 = _cac_grad("sac_actor_head", dq1_da, B, Ad, "dq1_da")
+    g2 = None if dq2_da is None else _cac_grad("sac_actor_head", dq2_da, B, Ad, "dq2_da")
+    q1a, q2a = _head_args("sac_actor_head", B, (), (("q1a", q1a, torch.float32), ("q2a", q2a, torch.float32)))
+    dev = raw.device
+    if out is None:
+        out = torch.empty_like(raw)
+    elif tuple(out.shape) != tuple(raw.shape) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"sac_actor_head: out must be a contiguous f32 {list(raw.shape)}")
+    d_sigma = torch.empty(B, Ad, dtype=torch.float32, device=dev) if sigma_param is not None else None
+    ds_ptr = out.data_ptr() + 4 * Ad if d_sigma is None else d_sigma.data_ptr()
+    logp = torch.empty(B, dtype=torch.float32, device=dev)
+    partial = _head_partial(B, _abi.CAC_ROWS_PER_BLOCK, dev)
+    # one pitch serves d_mu and d_sigma: 2 Ad inside `out`, or Ad in `out` and in d_sigma's own array
+    call("tsm_sac_actor_head", ptr(raw), ld, sg_ptr, ld_s, ptr(z), ptr(q1a), ptr(q2a), ptr(g1), ptr(g2), Ad,
+         ptr(_chk(alpha_dev, torch.float32, "alpha_dev")), B, Ad, float(max_action), int(bool(unbounded)), ptr(out), ds_ptr, ld,
+         ptr(logp), ptr(partial), stream_ptr())
+    return dict(d_raw=out, d_sigma=d_sigma, logp=logp, partial=partial)
+
+
+# --------------------------------------------------------------------------------------------
 # Prioritized replay (data/utils/segtree.py, data/buffer/prio.py; csrc/segtree.hip)
 # --------------------------------------------------------------------------------------------
 def segtree_bound(size: int) -> int:

@@ -261,6 +261,123 @@ class FlatMLP(nn.Module):
         self.import_layers(sd, ref_layer_keys(self.n_layers, "fc"))
 
 
+# ---- the continuous-action nets (utils/net/continuous.py) ---------------------------------------------------------------
+class _ContinuousNet(FlatMLP):
+    """A `FlatMLP` under the reference's `Net(hidden_sizes=[...])` + `last` key names (`ref_layer_keys`: "head")."""
+
+    def _twin_kwargs(self) -> dict:
+        return {}
+
+    def clone_over(self, storage: torch.Tensor):
+        twin = FlatMLP.__new__(type(self))
+        FlatMLP.__init__(twin, self.dims, self.act, device=storage.device, seed=0, storage=storage)
+        twin.__dict__.update(self._twin_kwargs())
+        return twin
+
+    def _ref_keys(self):
+        return ref_layer_keys(self.n_layers, "head")
+
+    def to_reference_state_dict(self, prefix: str = "", sd: OrderedDict | None = None) -> OrderedDict:
+        return self.export_layers(self._ref_keys(), prefix, sd)
+
+    def load_reference_state_dict(self, sd, prefix: str = "") -> None:
+        self.import_layers(sd, self._ref_keys(), prefix)
+
+
+class ContinuousActorDeterministic(_ContinuousNet):
+    """continuous.py:32-88: obs -> hidden ... -> act_dim raw outputs; the action is `max_action * tanh(raw)`
+    (`ops.cac_det_action`), which `forward` does NOT apply: the learners need the raw output for the backward."""
+
+    def __init__(self, obs_dim: int, act_dim: int, hidden_sizes=(64, 64), max_action: float = 1.0, act: str = "relu",
+                 device: str | torch.device = "cuda", seed: int | None = None) -> None:
+        ops.cac_check(int(act_dim))
+        super().__init__([int(obs_dim), *[int(h) for h in hidden_sizes], int(act_dim)], act, device=device, seed=seed)
+        self.max_action = float(max_action)
+        self.act_dim = int(act_dim)
+
+    def _twin_kwargs(self) -> dict:
+        return dict(max_action=self.max_action, act_dim=self.act_dim)
+
+
+class ContinuousCritic(_ContinuousNet):
+    """continuous.py:102-175: rows [obs | act] -> hidden ... -> 1."""
+
+    def __init__(self, obs_dim: int, act_dim: int, hidden_sizes=(64, 64), act: str = "relu",
+                 device: str | torch.device = "cuda", seed: int | None = None) -> None:
+        super().__init__([int(obs_dim) + int(act_dim), *[int(h) for h in hidden_sizes], 1], act, device=device, seed=seed)
+        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
+
+    def _twin_kwargs(self) -> dict:
+        return dict(obs_dim=self.obs_dim, act_dim=self.act_dim)
+
+
+class ContinuousActorProbabilistic(_ContinuousNet):
+    """continuous.py:178-247.  `conditioned_sigma=True`: the reference's `mu` and `sigma` heads (one Linear each on the shared
+    trunk) are ONE last layer of 2 act_dim outputs, [mu_raw | sigma_raw]; a checkpoint carries its two halves as `mu.model.0.*`
+    and `sigma.model.0.*`.  `conditioned_sigma=False` (the reference's default): the net emits mu_raw alone and the
+    state-independent `sigma_param` (zeros at first, continuous.py:222) is the last act_dim entries of the flat parameter, behind
+    the layers, so that one Adam steps both.  The tanh on mu, the clamp and exp on sigma are `ops.sac_action`'s."""
+
+    def __init__(self, obs_dim: int, act_dim: int, hidden_sizes=(64, 64), max_action: float = 1.0, unbounded: bool = False,
+                 conditioned_sigma: bool = False, act: str = "relu", device: str | torch.device = "cuda",
+                 seed: int | None = None, storage: torch.Tensor | None = None) -> None:
+        ops.cac_check(int(act_dim))
+        Ad, cond = int(act_dim), bool(conditioned_sigma)
+        dims = [int(obs_dim), *[int(h) for h in hidden_sizes], 2 * Ad if cond else Ad]
+        n = ops.mlp_param_count(ops.mlp_desc(dims, act))
+        if storage is None:
+            storage = torch.zeros(n + (0 if cond else Ad), dtype=torch.float32, device=device)
+        super().__init__(dims, act, device=device, seed=seed, storage=storage[:n])
+        if not cond:   # the layers view the head of the vector, sigma_param its tail
+            self.flat = nn.Parameter(storage, requires_grad=False)
+            storage[n:].zero_()
+        if unbounded and not np.isclose(max_action, 1.0):
+            max_action = 1.0   # continuous.py:208-210: discarded when unbounded
+        self.max_action, self.unbounded, self.act_dim, self.conditioned_sigma = float(max_action), bool(unbounded), Ad, cond
+        self.n_mlp_params = n
+
+    @property
+    def sigma_param(self) -> torch.Tensor | None:
+        """f32 [act_dim]: a view of the flat parameter's tail (None with conditioned sigma)."""
+        return None if self.conditioned_sigma else self.flat.data[self.n_mlp_params:]
+
+    @property
+    def extra_param_shapes(self) -> list[tuple[int, ...]]:
+        """The parameters behind the layers on the flat vector, as `FlatAdam.state_dict` lists them."""
+        return [] if self.conditioned_sigma else [(self.act_dim, 1)]
+
+    def clone_over(self, storage: torch.Tensor):
+        return ContinuousActorProbabilistic(self.dims[0], self.act_dim, self.dims[1:-1], self.max_action, self.unbounded,
+                                            self.conditioned_sigma, self.act, device=storage.device, seed=0, storage=storage)
+
+    def _heads(self):
+        """[(reference key, view)] of what is not the trunk, in the reference's state_dict order (a module's own parameters
+        come before its submodules': `sigma_param` leads)."""
+        L, Ad = self.n_layers - 1, self.act_dim
+        W, b = self.weight(L), self.bias(L)
+        if self.conditioned_sigma:
+            return [], [("mu.model.0.weight", W[:Ad]), ("mu.model.0.bias", b[:Ad]), ("sigma.model.0.weight", W[Ad:]),
+                        ("sigma.model.0.bias", b[Ad:])]
+        return [("sigma_param", self.sigma_param.view(Ad, 1))], [("mu.model.0.weight", W), ("mu.model.0.bias", b)]
+
+    def to_reference_state_dict(self, prefix: str = "", sd: OrderedDict | None = None) -> OrderedDict:
+        sd = OrderedDict() if sd is None else sd
+        first, last = self._heads()
+        sd.update((prefix + k, v.detach().clone().cpu()) for k, v in first)
+        self.export_layers(self._ref_keys()[:-1], prefix, sd)
+        sd.update((prefix + k, v.detach().clone().cpu()) for k, v in last)
+        return sd
+
+    @torch.no_grad()
+    def load_reference_state_dict(self, sd, prefix: str = "") -> None:
+        for i, (kw, kb) in enumerate(self._ref_keys()[:-1]):
+            self.weight(i).copy_(torch.as_tensor(np.asarray(sd[prefix + kw])).to(self.flat.device, torch.float32))
+            self.bias(i).copy_(torch.as_tensor(np.asarray(sd[prefix + kb])).to(self.flat.device, torch.float32))
+        first, last = self._heads()
+        for k, v in first + last:
+            v.copy_(torch.as_tensor(np.asarray(sd[prefix + k])).to(self.flat.device, torch.float32).reshape(v.shape))
+
+
 class ImplicitQuantileNet(nn.Module):
     """ImplicitQuantileNetwork (discrete.py:164-217) on ONE flat f32 parameter vector in the reference module's
     `parameters()` order: the preprocess layers, the `last` layers, then the cosine embedding's weight [H, C] and bias [H].
@@ -754,8 +871,9 @@ class FlatAdam:
 
     def _shapes(self) -> list[tuple[int, ...]]:
         m = self._module
-        if isinstance(m, FlatMLP):
-            return [s for i in range(m.n_layers) for s in ((m.dims[i + 1], m.dims[i]), (m.dims[i + 1],))]
+        if isinstance(m, FlatMLP):   # the layers, then what the net keeps behind them on the flat vector
+            return [s for i in range(m.n_layers) for s in ((m.dims[i + 1], m.dims[i]), (m.dims[i + 1],))] + \
+                list(getattr(m, "extra_param_shapes", ()))
         return [tuple(self.param.shape)]
 
     def state_dict(self) -> dict:
