@@ -1372,6 +1372,58 @@ int tsm_dueling_combine_backward(const float *d, int64_t R, int32_t n_act, int32
 int tsm_dueling_features(const float *z, int64_t n, float *f, void *stream);
 int tsm_dueling_features_backward(const float *z, const float *d_fq, const float *d_fv, int64_t n, float *d_z, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Grouped ensemble MLP  (EnsembleLinear, tianshou/utils/net/common.py:522-554; csrc/ensemble.hip)
+ * E networks of the shape `desc` as ONE launch per layer and role, the member a grid dimension; f32-input MFMA as
+ * csrc/dense.hip.  params f32 [tsm_ens_mlp_param_count] in the reference's `parameters()` order, per layer
+ * weight [E][dims[l]][dims[l + 1]] then bias_weights [E][1][dims[l + 1]] (a reference checkpoint is a set of views of it).
+ * x f32 [B][dims[0]] is shared by all members; activation blocks are [E][B][dims[l]], layer after layer
+ * (tsm_ens_mlp_act_elems floats); the output is the last block, [E][B][dims[L]].  No alignment is asked of any pointer or
+ * width.  E in [1, TSM_ENS_MAX_MEMBERS] and desc as tsm_mlp_*: anything else is TSM_ERR_INVALID before any launch.
+ * tsm_ens_mlp_backward: d_out [E][B][dims[L]]; d_acts: workspace of tsm_ens_mlp_act_elems floats (n_layers > 1);
+ *   slabs [n_split][slab_stride] (slab_stride 0: the parameter count) receive the gradient in the parameter layout, every
+ *   entry of every slab written: tsm_adam_step sums them.  E * n_split <= 65535 (one grid dimension).
+ * tsm_ens_mlp_input_grad: the dgrad chain without weight gradients, ended by
+ *   dx[b * ldx + j] = sum_e sum_o dZ0_e[b][o] W0_e[col0 + j][o], the members summed in the order e = 0 .. E - 1 inside one
+ *   workgroup's k loop (one writer per element, no atomics).
+ * Every sum has a fixed order: two runs give the same bits.
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_ENS_MAX_MEMBERS 64
+int64_t tsm_ens_mlp_param_count(const tsm_mlp_desc *desc, int32_t E);
+int64_t tsm_ens_mlp_act_elems(const tsm_mlp_desc *desc, int32_t E, int64_t B);
+int tsm_ens_mlp_forward(const tsm_mlp_desc *desc, int32_t E, const float *params, const float *x, int64_t B, float *acts,
+                        void *stream);
+int tsm_ens_mlp_backward(const tsm_mlp_desc *desc, int32_t E, const float *params, const float *x, int64_t B,
+                         const float *acts, const float *d_out, float *d_acts, int32_t n_split, float *slabs,
+                         int64_t slab_stride, void *stream);
+int tsm_ens_mlp_input_grad(const tsm_mlp_desc *desc, int32_t E, const float *params, const float *x, int64_t B,
+                           const float *acts, const float *d_out, float *d_acts, int32_t col0, int32_t n_col, float *dx,
+                           int64_t ldx, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * REDQ  (tianshou/algorithm/modelfree/redq.py; csrc/redq.hip)
+ * q f32 [E][B]: the ensemble critic's output.  One launch each, one thread per row walking the members in order, float64
+ * arithmetic from the float32 inputs; the loss leaves as per-workgroup float64 pairs in tsm_qmix_mix_td's layout,
+ * partial f64 [2 * ceil(B / TSM_REDQ_ROWS_PER_BLOCK)], for tsm_qmix_finalize(partial, n_blocks, E * B, ..).  No atomics.
+ * tsm_redq_target replaces  _target_q_compute_value (redq.py:254-269) after the lagged ensemble's forward, and
+ *           `_nstep_return`'s last line.  subset_mask: bit e set = member e is in the subset (at least one, none >= E);
+ *   target_q = min (TSM_REDQ_MIN) or mean (TSM_REDQ_MEAN) over the subset - alpha logp_next (logp_next nullable: nothing);
+ *   returns_out f32 [B] by tsm_dqn_td_head's rounding rule.
+ * tsm_redq_critic_head replaces  redq.py:273-279 between the forward and optimizer.step.  td_e = q_e - returns;
+ *   dq f32 [E][B] = 2 td_e weight / (E B) (weight [B] nullable: 1);  prio f32 [B] = mean_e td_e (signed);
+ *   partial = {sum_e sum_b td_e^2 weight, 0}.
+ * tsm_redq_mean_q: out f32 [B] = mean_e q[e][b]  (redq.py:287).
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_REDQ_ROWS_PER_BLOCK 256
+#define TSM_REDQ_MIN 0
+#define TSM_REDQ_MEAN 1
+int tsm_redq_target(const float *q_next, int32_t E, uint64_t subset_mask, int32_t mode, const float *logp_next,
+                    const float *alpha_dev, const float *mc, const float *gpow, const uint8_t *vmask, int64_t B,
+                    float *returns_out, void *stream);
+int tsm_redq_critic_head(const float *q, int32_t E, const float *returns, const float *weight, int64_t B, float *dq,
+                         float *prio, double *partial, void *stream);
+int tsm_redq_mean_q(const float *q, int32_t E, int64_t B, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,8 @@ DISTQ_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_DISTQ_ROWS_PER_BLOCK: rows per
 DSAC_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_DSAC_ROWS_PER_BLOCK: rows per workgroup of the Discrete SAC heads
 CAC_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_CAC_ROWS_PER_BLOCK: rows per workgroup of the continuous actor-critic heads
 CAC_MAX_ACT_DIM = 64  # include/tsmarl.h TSM_CAC_MAX_ACT_DIM: one lane per action component
+ENS_MAX_MEMBERS = 64  # include/tsmarl.h TSM_ENS_MAX_MEMBERS: members of a grouped ensemble MLP (a bit each in REDQ's subset mask)
+REDQ_ROWS_PER_BLOCK = 256  # include/tsmarl.h TSM_REDQ_ROWS_PER_BLOCK: one row per thread of the REDQ heads
 IQN_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_IQN_ROWS_PER_BLOCK: rows per workgroup of the IQN head
 TSM_OK, TSM_ERR_INVALID, TSM_ERR_HIP, TSM_ERR_MALFORMED_BUFFER, TSM_ERR_UNSUPPORTED = range(5)
 
@@ -333,6 +335,14 @@ SIGNATURES = {
     "tsm_per_update_weight": (_int, [_p, _p, _i64, _p, _p, _i64, _f64, _p, _p, _p]),
     "tsm_per_init_weight": (_int, [_p, _p, _i64, _p, _i64, _f64, _p, _p, _p]),
     "tsm_per_get_weight": (_int, [_p, _i64, _p, _i64, _f64, _int, _p, _p, _p, _p, _p]),
+    "tsm_ens_mlp_param_count": (_i64, [C.POINTER(tsm_mlp_desc), _i32]),
+    "tsm_ens_mlp_act_elems": (_i64, [C.POINTER(tsm_mlp_desc), _i32, _i64]),
+    "tsm_ens_mlp_forward": (_int, [C.POINTER(tsm_mlp_desc), _i32, _p, _p, _i64, _p, _p]),
+    "tsm_ens_mlp_backward": (_int, [C.POINTER(tsm_mlp_desc), _i32, _p, _p, _i64, _p, _p, _p, _i32, _p, _i64, _p]),
+    "tsm_ens_mlp_input_grad": (_int, [C.POINTER(tsm_mlp_desc), _i32, _p, _p, _i64, _p, _p, _p, _i32, _i32, _p, _i64, _p]),
+    "tsm_redq_target": (_int, [_p, _i32, _u64, _i32, _p, _p, _p, _p, _p, _i64, _p, _p]),
+    "tsm_redq_critic_head": (_int, [_p, _i32, _p, _p, _i64, _p, _p, _p, _p]),
+    "tsm_redq_mean_q": (_int, [_p, _i32, _i64, _p, _p]),
 }
 
 _NO_STATUS = {"tsm_critic_rows_w1_image_kj", "tsm_critic_rows_w1_image_elems", "tsm_p2p_ipc_handle_bytes", "tsm_p2p_failed", "tsm_critic_rows_forward_supported", "tsm_critic_rows_param_count", "tsm_critic_rows_grad_grid", "tsm_critic_rows_dw1_chunks", "tsm_ppo_critic_rows_supported", "tsm_ppo_critic_rows_param_count", "tsm_ppo_critic_rows_grid",
@@ -341,7 +351,7 @@ _NO_STATUS = {"tsm_critic_rows_w1_image_kj", "tsm_critic_rows_w1_image_elems", "
               "tsm_policy_param_count", "tsm_ppo_update_grid", "tsm_adam_work_elems", "tsm_policy_image_elems",
               "tsm_mlp_param_count", "tsm_mlp_act_elems", "tsm_ctde_head_partial_elems", "tsm_mpe_tag_obs_dim",
               "tsm_gae_scan_workspace_bytes", "tsm_qmix_partial_elems", "tsm_maddpg_partial_elems", "tsm_dqn_partial_elems",
-              "tsm_segtree_bound"}
+              "tsm_segtree_bound", "tsm_ens_mlp_param_count", "tsm_ens_mlp_act_elems"}
 
 _lib = None
 

@@ -7,6 +7,7 @@ from .rainbow import RainbowDQN, RainbowPolicy
 from .dsac import Alpha, AutoAlpha, DiscreteSAC, DiscreteSACPolicy, DiscreteSACTrainingStats, FixedAlpha
 from .cac import (DDPG, SAC, TD3, ContinuousDeterministicPolicy, DDPGTrainingStats, GaussianNoise, SACPolicy,
                   SACTrainingStats, TD3TrainingStats)
+from .redq import REDQ, REDQPolicy, REDQTrainingStats
 from .pg import A2C, Reinforce
 from .ppo import PPO, policy_within_training_step
 from .ppo_generic import GenericPPO
@@ -15,5 +16,5 @@ __all__ = ["PPO", "A2C", "Reinforce", "GenericPPO", "DQN", "DiscreteQLearningPol
            "QRDQNPolicy", "IQN", "IQNPolicy", "FQF", "FQFPolicy", "FQFTrainingStats", "RainbowDQN", "RainbowPolicy",
            "DiscreteSAC", "DiscreteSACPolicy", "DiscreteSACTrainingStats", "Alpha", "FixedAlpha", "AutoAlpha",
            "DDPG", "TD3", "SAC", "ContinuousDeterministicPolicy", "SACPolicy", "DDPGTrainingStats", "TD3TrainingStats",
-           "SACTrainingStats", "GaussianNoise",
+           "SACTrainingStats", "GaussianNoise", "REDQ", "REDQPolicy", "REDQTrainingStats",
            "policy_within_training_step"]

@@ -1952,6 +1952,76 @@ def sac_actor_head(raw, z, q1a, q2a, dq1_da, dq2_da, alpha_dev, max_action: floa
 
 
 # --------------------------------------------------------------------------------------------
+# REDQ (redq.py; csrc/redq.hip)
+# --------------------------------------------------------------------------------------------
+def redq_subset_mask(indices, ensemble_size: int) -> int:
+    """The u64 subset mask of `tsm_redq_target`: bit e set for every member index e of `indices` (distinct, in [0, E))."""
+    idx = [int(i) for i in indices]
+    if not idx or len(set(idx)) != len(idx) or min(idx) < 0 or max(idx) >= int(ensemble_size) or ensemble_size > _abi.ENS_MAX_MEMBERS:
+        raise ValueError(f"redq_subset_mask: {idx} is not a set of distinct members of an ensemble of {ensemble_size} "
+                         f"(at most {_abi.ENS_MAX_MEMBERS})")
+    mask = 0
+    for i in idx:
+        mask |= 1 << i
+    return mask
+
+
+def _redq_q(name: str, q):
+    _dev_only(name, q)
+    if q.dim() == 3 and q.shape[2] == 1:
+        q = q[:, :, 0]
+    if q.dim() != 2 or q.shape[1] < 1:
+        raise ValueError(f"{name}: q must be [E, B] (or [E, B, 1]) with B >= 1")
+    return _chk(q, torch.float32, "q"), q.shape[0], q.shape[1]
+
+
+def redq_target(q_next, subset_mask: int, mode: str, mc, gpow, vmask, logp_next=None, alpha_dev=None, out=None):
+    """The subset's min or mean of the lagged ensemble q_next [E, B], minus alpha * logp_next, then the n-step line
+    (redq.py:254-269, algorithm_base.py:1213-1215).  -> returns f32 [B]."""
+    q_next, E, B = _redq_q("redq_target", q_next)
+    _dev_only("redq_target", mc, gpow, vmask, logp_next, alpha_dev, out)
+    if mode not in ("min", "mean"):
+        raise ValueError(f"Unsupported target_mode: {mode}")
+    if (logp_next is None) != (alpha_dev is None):
+        raise ValueError("redq_target: logp_next and alpha_dev come together")
+    args = _head_args("redq_target", B, (), (("logp_next", logp_next, torch.float32), ("mc", mc, torch.float32),
+                                             ("gpow", gpow, torch.float32), ("vmask", vmask, torch.uint8)))
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=q_next.device)
+    elif out.numel() != B or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"redq_target: out must be a contiguous f32 [{B}]")
+    call("tsm_redq_target", ptr(q_next), E, int(subset_mask) & (2**64 - 1), 0 if mode == "min" else 1, ptr(args[0]),
+         ptr(None if alpha_dev is None else _chk(alpha_dev, torch.float32, "alpha_dev")), *map(ptr, args[1:]), B, ptr(out),
+         stream_ptr())
+    return out
+
+
+def redq_critic_head(q, returns, weight=None):
+    """redq.py:273-279 between the forward and the step: q [E, B].  -> dict(dq [E, B] = 2 w td / (E B), prio [B] = the signed
+    ensemble mean of td = q - returns, partial f64): `qmix_finalize(partial, E * B, out)` gives {critic_loss, 0}."""
+    q, E, B = _redq_q("redq_critic_head", q)
+    _dev_only("redq_critic_head", returns, weight)
+    args = _head_args("redq_critic_head", B, (), (("returns", returns, torch.float32), ("weight", weight, torch.float32)))
+    dev = q.device
+    out = dict(dq=torch.empty(E, B, dtype=torch.float32, device=dev), prio=torch.empty(B, dtype=torch.float32, device=dev),
+               partial=_head_partial(B, _abi.REDQ_ROWS_PER_BLOCK, dev))
+    call("tsm_redq_critic_head", ptr(q), E, *map(ptr, args), B, ptr(out["dq"]), ptr(out["prio"]), ptr(out["partial"]),
+         stream_ptr())
+    return out
+
+
+def redq_mean_q(q, out=None):
+    """critic(obs, a).mean(dim=0) (redq.py:287): q [E, B] -> f32 [B], the members summed in order."""
+    q, E, B = _redq_q("redq_mean_q", q)
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=q.device)
+    elif out.numel() != B or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"redq_mean_q: out must be a contiguous f32 [{B}]")
+    call("tsm_redq_mean_q", ptr(q), E, B, ptr(out), stream_ptr())
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # Prioritized replay (data/utils/segtree.py, data/buffer/prio.py; csrc/segtree.hip)
 # --------------------------------------------------------------------------------------------
 def segtree_bound(size: int) -> int:
@@ -2377,6 +2447,74 @@ def mlp_input_grad(desc, params, x, acts, d_out, col0: int, n_col: int, out=None
         d_acts = torch.empty_like(acts)
     call("tsm_mlp_input_grad", C.byref(desc), ptr(_chk(params, torch.float32, "params")), ptr(x), B, ptr(acts), ptr(d_out),
          ptr(d_acts), col0, n_col, ptr(_chk(out, torch.float32, "out")), n_col, stream_ptr())
+    return out
+
+
+# --------------------------------------------------------------------------------------------
+# grouped ensemble MLP: E nets of one shape, one launch per layer and role (utils/net/common.py:522-554; csrc/ensemble.hip)
+# --------------------------------------------------------------------------------------------
+def ens_mlp_param_count(desc, E: int) -> int:
+    """Floats of the flat vector: per layer weight [E, in, out] then bias_weights [E, 1, out].  ValueError naming the limit
+    for a bad descriptor or E outside [1, ENS_MAX_MEMBERS]."""
+    n = call("tsm_ens_mlp_param_count", C.byref(desc), int(E))
+    if n < 0:
+        _abi.check(_abi.TSM_ERR_INVALID)
+    return n
+
+
+def _ens_args(name: str, desc, E: int, params, x):
+    _dev_only(name, params, x)
+    x = _chk(x, torch.float32, "x")
+    if x.dim() != 2 or x.shape[1] != desc.dims[0]:
+        raise ValueError(f"{name}: x must be [B, {desc.dims[0]}], the input all members share")
+    if params.numel() != ens_mlp_param_count(desc, E):
+        raise ValueError(f"{name}: params must hold {ens_mlp_param_count(desc, E)} floats for {E} members")
+    return _chk(params, torch.float32, "params"), x, x.shape[0]
+
+
+def ens_mlp_forward(desc, E: int, params, x, acts=None):
+    """x [B, dims[0]] through all E members -> (out [E, B, dims[-1]] view of the last activation block, acts buffer)."""
+    params, x, B = _ens_args("ens_mlp_forward", desc, E, params, x)
+    n = call("tsm_ens_mlp_act_elems", C.byref(desc), int(E), B)
+    if acts is None:
+        acts = torch.empty(n, dtype=torch.float32, device=x.device)
+    call("tsm_ens_mlp_forward", C.byref(desc), int(E), ptr(params), ptr(x), B, ptr(acts), stream_ptr())
+    O = desc.dims[desc.n_layers]
+    return acts[n - E * B * O:].view(E, B, O), acts
+
+
+def ens_mlp_backward(desc, E: int, params, x, acts, d_out, n_split: int = 0, slabs=None, slab_stride: int = 0):
+    """Gradient slabs [n_split, n_param] of sum(out * d_out), d_out [E, B, dims[-1]], in the parameter layout."""
+    params, x, B = _ens_args("ens_mlp_backward", desc, E, params, x)
+    d_out = _chk(d_out, torch.float32, "d_out")
+    if d_out.numel() != E * B * desc.dims[desc.n_layers]:
+        raise ValueError(f"ens_mlp_backward: d_out must be [{E}, {B}, {desc.dims[desc.n_layers]}]")
+    if n_split <= 0:
+        n_split = mlp_n_split(B)
+    if slabs is None:
+        slabs = torch.empty(n_split, params.numel(), dtype=torch.float32, device=x.device)
+    d_acts = torch.empty_like(acts)
+    call("tsm_ens_mlp_backward", C.byref(desc), int(E), ptr(params), ptr(x), B, ptr(acts), ptr(d_out), ptr(d_acts), n_split,
+         slabs.data_ptr(), slab_stride, stream_ptr())
+    return slabs
+
+
+def ens_mlp_input_grad(desc, E: int, params, x, acts, d_out, col0: int, n_col: int, out=None):
+    """Gradient of sum(out * d_out) w.r.t. the shared input's columns [col0, col0 + n_col) -> [B, n_col]: the sum over the
+    members, in member order; no weight gradients."""
+    params, x, B = _ens_args("ens_mlp_input_grad", desc, E, params, x)
+    d_out = _chk(d_out, torch.float32, "d_out")
+    if not (0 <= col0 and n_col >= 1 and col0 + n_col <= desc.dims[0]):
+        raise ValueError(f"ens_mlp_input_grad: columns [{col0}, {col0 + n_col}) leave the input width {desc.dims[0]}")
+    if d_out.numel() != E * B * desc.dims[desc.n_layers]:
+        raise ValueError(f"ens_mlp_input_grad: d_out must be [{E}, {B}, {desc.dims[desc.n_layers]}]")
+    if out is None:
+        out = torch.empty(B, n_col, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (B, n_col):
+        raise ValueError(f"ens_mlp_input_grad: out must be [{B}, {n_col}]")
+    d_acts = torch.empty_like(acts)
+    call("tsm_ens_mlp_input_grad", C.byref(desc), int(E), ptr(params), ptr(x), B, ptr(acts), ptr(d_out), ptr(d_acts), col0, n_col,
+         ptr(_chk(out, torch.float32, "out")), n_col, stream_ptr())
     return out
 
 

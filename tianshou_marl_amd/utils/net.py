@@ -378,6 +378,115 @@ class ContinuousActorProbabilistic(_ContinuousNet):
             v.copy_(torch.as_tensor(np.asarray(sd[prefix + k])).to(self.flat.device, torch.float32).reshape(v.shape))
 
 
+class EnsembleCritic(nn.Module):
+    """An ensemble of `ensemble_size` critics [obs | act] -> hidden ... -> 1 of one shape, the reference's
+    `ContinuousCritic(preprocess_net=Net(..., linear_layer=EnsembleLinear), linear_layer=EnsembleLinear, flatten_input=False)`
+    (utils/net/common.py:522-554, continuous.py:102-175; examples/mujoco/mujoco_redq.py), as ONE flat HBM vector in the
+    reference's `parameters()` order -- per layer weight [E, in, out], then bias_weights [E, 1, out] -- so a reference
+    checkpoint is a set of views of it.  forward / backward / input_grad run in csrc/ensemble.hip: one grouped launch per
+    layer and role serves all members.  `forward` -> [E, B, 1]."""
+
+    def __init__(self, obs_dim: int, act_dim: int, ensemble_size: int, hidden_sizes=(64, 64), act: str = "relu",
+                 device: str | torch.device = "cuda", seed: int | None = None, storage: torch.Tensor | None = None) -> None:
+        super().__init__()
+        self.obs_dim, self.act_dim, self.ensemble_size = int(obs_dim), int(act_dim), int(ensemble_size)
+        self.dims = [self.obs_dim + self.act_dim, *[int(h) for h in hidden_sizes], 1]
+        self.act = act
+        self.desc = ops.mlp_desc(self.dims, act)
+        n = ops.ens_mlp_param_count(self.desc, self.ensemble_size)
+        if storage is None:
+            storage = torch.zeros(n, dtype=torch.float32, device=device)
+        elif storage.numel() != n or storage.dtype != torch.float32 or not storage.is_contiguous():
+            raise ValueError(f"EnsembleCritic: storage must be a contiguous f32 vector of {n} elements")
+        self.flat = nn.Parameter(storage, requires_grad=False)
+        self._offsets = []
+        o, E = 0, self.ensemble_size
+        for i in range(self.n_layers):
+            k, m = self.dims[i], self.dims[i + 1]
+            self._offsets.append((o, o + E * k * m))
+            o += E * (k * m + m)
+        self._saved = None
+        self.reset_parameters(seed)
+
+    @property
+    def n_layers(self) -> int:
+        return len(self.dims) - 1
+
+    def weight(self, i: int, flat: torch.Tensor | None = None) -> torch.Tensor:
+        """Layer i's weight [E, in, out], a view of the flat vector (or of any vector of its layout, e.g. a gradient)."""
+        o, ob = self._offsets[i]
+        return (self.flat.data if flat is None else flat)[o:ob].view(self.ensemble_size, self.dims[i], self.dims[i + 1])
+
+    def bias(self, i: int, flat: torch.Tensor | None = None) -> torch.Tensor:
+        """Layer i's bias_weights [E, 1, out]."""
+        _, ob = self._offsets[i]
+        E, m = self.ensemble_size, self.dims[i + 1]
+        return (self.flat.data if flat is None else flat)[ob:ob + E * m].view(E, 1, m)
+
+    def param_shapes(self) -> list[tuple[int, ...]]:
+        """The reference's parameter shapes in `parameters()` order (what `FlatAdam.state_dict` splits its moments by)."""
+        return [tuple(t.shape) for i in range(self.n_layers) for t in (self.weight(i), self.bias(i))]
+
+    @torch.no_grad()
+    def reset_parameters(self, seed: int | None = None) -> None:
+        """EnsembleLinear's init (common.py:541-548): uniform +-sqrt(1 / in) for the weight and for the bias."""
+        gen = torch.Generator().manual_seed(seed) if seed is not None else None
+        for i in range(self.n_layers):
+            k = math.sqrt(1.0 / self.dims[i])
+            for v in (self.weight(i), self.bias(i)):
+                v.copy_(torch.rand(v.shape, generator=gen) * 2 * k - k)
+
+    def clone_over(self, storage: torch.Tensor) -> "EnsembleCritic":
+        """A net of the same shape viewing `storage` (`lagged_copy`)."""
+        return EnsembleCritic(self.obs_dim, self.act_dim, self.ensemble_size, self.dims[1:-1], self.act, device=storage.device,
+                              seed=0, storage=storage)
+
+    def forward(self, x: torch.Tensor, save: bool = True) -> torch.Tensor:
+        """x [B, obs_dim + act_dim], shared by all members -> Q [E, B, 1]."""
+        x = x.to(self.flat.device, torch.float32).contiguous()
+        if x.dim() != 2 or x.shape[1] != self.dims[0]:
+            raise ValueError(f"EnsembleCritic: input must be [B, {self.dims[0]}], got {list(x.shape)}")
+        out, acts = ops.ens_mlp_forward(self.desc, self.ensemble_size, self.flat.data, x)
+        if save:
+            self._saved = (x, acts)
+        return out
+
+    def backward(self, d_out: torch.Tensor, n_split: int = 0, slabs: torch.Tensor | None = None,
+                 slab_stride: int = 0) -> torch.Tensor:
+        """Gradient slabs [n_split, n_param] of sum(out * d_out), d_out [E, B(, 1)], for the last `forward(save=True)`."""
+        if self._saved is None:
+            raise RuntimeError("EnsembleCritic.backward called before forward")
+        x, acts = self._saved
+        return ops.ens_mlp_backward(self.desc, self.ensemble_size, self.flat.data, x, acts, d_out.contiguous(), n_split,
+                                    slabs=slabs, slab_stride=slab_stride)
+
+    def input_grad(self, d_out: torch.Tensor, col0: int, n_col: int, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Gradient [B, n_col] of sum(out * d_out) w.r.t. the input columns [col0, col0 + n_col) of the last
+        `forward(save=True)`, summed over the members in order; no weight gradient is computed."""
+        if self._saved is None:
+            raise RuntimeError("EnsembleCritic.input_grad called before forward")
+        x, acts = self._saved
+        return ops.ens_mlp_input_grad(self.desc, self.ensemble_size, self.flat.data, x, acts, d_out.contiguous(), col0, n_col,
+                                      out=out)
+
+    # ---- checkpoints under the reference's key names ------------------------------------------------------------------
+    def _ref_keys(self) -> list[tuple[str, str]]:
+        return [(w, b[:-len("bias")] + "bias_weights") for w, b in ref_layer_keys(self.n_layers, "head")]
+
+    def to_reference_state_dict(self, prefix: str = "", sd: OrderedDict | None = None) -> OrderedDict:
+        sd = OrderedDict() if sd is None else sd
+        for i, (kw, kb) in enumerate(self._ref_keys()):
+            sd[prefix + kw] = self.weight(i).detach().clone().cpu()
+            sd[prefix + kb] = self.bias(i).detach().clone().cpu()
+        return sd
+
+    @torch.no_grad()
+    def load_reference_state_dict(self, sd, prefix: str = "") -> None:
+        for i, (kw, kb) in enumerate(self._ref_keys()):
+            for v, key in ((self.weight(i), kw), (self.bias(i), kb)):
+                v.copy_(torch.as_tensor(sd[prefix + key]).to(v.device, v.dtype).reshape(v.shape))
+
+
 class ImplicitQuantileNet(nn.Module):
     """ImplicitQuantileNetwork (discrete.py:164-217) on ONE flat f32 parameter vector in the reference module's
     `parameters()` order: the preprocess layers, the `last` layers, then the cosine embedding's weight [H, C] and bias [H].
@@ -871,6 +980,8 @@ class FlatAdam:
 
     def _shapes(self) -> list[tuple[int, ...]]:
         m = self._module
+        if hasattr(m, "param_shapes"):   # a net whose flat vector is not a FlatMLP's (EnsembleCritic)
+            return list(m.param_shapes())
         if isinstance(m, FlatMLP):   # the layers, then what the net keeps behind them on the flat vector
             return [s for i in range(m.n_layers) for s in ((m.dims[i + 1], m.dims[i]), (m.dims[i + 1],))] + \
                 list(getattr(m, "extra_param_shapes", ()))
