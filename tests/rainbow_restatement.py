@@ -8,7 +8,7 @@ tests/golden/rainbow.npz.
   `noisy_grad`            the gradient over the effective layout mapped back onto the flat layout
   `dueling_combine` / `_backward`   q - mean_a q + v per atom, and its gradient
   `RainbowNetRestatement` forward and backward of the whole net on one flat vector
-  `philox_normals`        Philox4x32-10 + Box-Muller as tsm_noisy_sample forms its normals, in float64 or float32
+  `philox_normals`        Philox4x32-10 (tests/philox_restatement.py) + Box-Muller as tsm_noisy_sample forms its normals, in float64 or float32
   `RainbowRestatement`    the full update: both draws, the lagged copy of EVERY parameter with the `_iter` rule, C51's head
                           (tests/distq_restatement.py) on the one-step successors, Adam
 """
@@ -17,6 +17,7 @@ from __future__ import annotations
 import numpy as np
 
 from distq_restatement import c51_head, support_of
+from philox_restatement import philox4
 
 
 def net_layers(obs_dim, hidden, A, N, q_hidden=(), v_hidden=(), dueling=True, noisy=True):
@@ -175,20 +176,6 @@ class RainbowNetRestatement:
 
 # ---- Philox4x32-10 + Box-Muller -----------------------------------------------------------------------------------------
 NOISE_KEY = 0x52424E4F4953455F
-
-
-def philox4(seed: int, counter: int, sub: np.ndarray) -> np.ndarray:
-    """-> u32 [len(sub), 4]: the four words of block (counter, sub) under `seed`."""
-    M = np.uint64(0xFFFFFFFF)
-    sub = np.asarray(sub, np.uint64)
-    c = [np.full(sub.shape, counter & 0xFFFFFFFF, np.uint64), np.full(sub.shape, (counter >> 32) & 0xFFFFFFFF, np.uint64), sub.copy(),
-         np.zeros(sub.shape, np.uint64)]
-    k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
-        c = [((p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0)) & M, p1 & M, ((p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1)) & M, p0 & M]
-        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
-    return np.stack(c, 1).astype(np.uint32)
 
 
 def philox_normals(seed: int, counter: int, n: int, dtype=np.float64) -> np.ndarray:
