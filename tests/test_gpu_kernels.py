@@ -485,6 +485,7 @@ def test_ppo_loss_reference_fixture(golden_dir):
 @pytest.mark.parametrize("max_norm", [None, 0.5])
 @pytest.mark.parametrize("n_slab", [1, 7])
 def test_adam_step_matches_torch(max_norm, n_slab):
+    """A coarse float32 comparison; tests/test_gpu_adam.py is where the optimizer is held to float64 Adam and the exact slab tree."""
     torch.manual_seed(0)
     n = 11142
     p0 = torch.randn(n)
