@@ -1424,6 +1424,43 @@ int tsm_redq_critic_head(const float *q, int32_t E, const float *returns, const 
                          float *prio, double *partial, void *stream);
 int tsm_redq_mean_q(const float *q, int32_t E, int64_t B, float *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * BDQN  (tianshou/algorithm/modelfree/bdqn.py, BranchingNet in tianshou/utils/net/common.py:557-678; csrc/bdqn.hip)
+ * K branches of A actions each.  adv f32 [K][B][A]: the grouped ensemble's output block (tsm_ens_mlp_forward with E = K);
+ * v f32 [B]; q f32 [B][K][A]: the reference's logits; act i32 [B][K].  K in [1, TSM_ENS_MAX_MEMBERS], A in [1, 64] (DQN's
+ * bound), B as tsm_dqn_td_head: anything else, or a null pointer where none is allowed, is TSM_ERR_INVALID naming the limit
+ * before any launch (tsm_bdqn_check: the two bounds alone).  Float64 arithmetic from the float32 inputs, every sum in a fixed
+ * order, no atomics: two runs give the same bits.
+ * tsm_bdqn_combine replaces  BranchingNet.forward after its MLPs (common.py:669-677):
+ *   q[b][k][a] = v[b] + (adv[k][b][a] - mean_a' adv[k][b][a']), the mean summed a' = 0 .. A - 1.
+ * tsm_bdqn_head replaces  _target_q after its forwards (bdqn.py:155-171), _compute_return (:173-195) and _update_with_batch
+ *           between `self.policy(batch).logits` and `optim.step` (:211-221), in one launch.
+ *   q_next_target nullable: the online values are the target values.  a*_k = the first maximum of q_next_online[b][k][:]
+ *   (is_double) or of the target values;  tq_b = mean_k target[b][k][a*_k], k in order;
+ *   returns[b] = rew[b] + gamma tq_b (1 - end[b]), rounded to f32 once (tsm_dqn_td_head's rule; end u8: terminated or
+ *   truncated or the sub-buffer's newest row);  td_bk = returns[b] - q[b][k][act[b][k]];
+ *   loss = mean_b(w_b mean_k td_bk^2) (weight [B] nullable: 1);  prio f32 [B] = sum_k td_bk (signed);
+ *   g_bk = -2 w_b td_bk / (K B);  d_adv f32 [K][B][A] = g_bk ((a == act[b][k]) - 1 / A);  d_v f32 [B] = sum_k g_bk: the
+ *   combine's backward is folded in, d_adv feeds tsm_ens_mlp_backward / _input_grad, d_v the value stream.
+ *   partial f64 [2 * ceil(B / TSM_BDQN_ROWS_PER_BLOCK)] = {sum_b w_b mean_k td^2, sum_b mean_k q[b][k][act]} per workgroup in
+ *   tsm_qmix_mix_td's layout, for tsm_qmix_finalize(partial, n_blocks, B, ..).
+ *   An act entry outside [0, A) reads nothing, as in tsm_dqn_td_head: its td is NaN (loss and prio[b] are poisoned), its
+ *   d_adv row and its share of d_v are 0.
+ * tsm_bdqn_egreedy replaces  BDQNPolicy.forward's argmax (:76) and add_exploration_noise (:80-103).  q [R][K][A] ->
+ *   act_out i32 [R][K].  One coin per row: row r draws at Philox counter offset + *offset_dev + r; random where
+ *   u01(word 0 of sub 0) < *eps_dev in float32, then branch k takes (word k % 4 of sub 1 + k / 4) * A >> 32; else every branch
+ *   takes its first maximum.  No word is shared between rows, branches or the coin.  (`rand_act += batch.obs.mask` is not
+ *   reproduced: the Python policy refuses masked observations.)
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_BDQN_ROWS_PER_BLOCK 16
+int tsm_bdqn_check(int32_t K, int32_t A);
+int tsm_bdqn_combine(const float *adv, const float *v, int64_t B, int32_t K, int32_t A, float *q, void *stream);
+int tsm_bdqn_head(const float *q, const float *q_next_online, const float *q_next_target, const int32_t *act,
+                  const float *rew, const uint8_t *end, const float *weight, int64_t B, int32_t K, int32_t A, double gamma,
+                  int is_double, float *returns_out, float *prio, float *d_adv, float *d_v, double *partial, void *stream);
+int tsm_bdqn_egreedy(const float *q, int64_t R, int32_t K, int32_t A, const float *eps_dev, uint64_t seed, uint64_t offset,
+                     const uint64_t *offset_dev, int32_t *act_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

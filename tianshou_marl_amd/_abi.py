@@ -24,6 +24,7 @@ CAC_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_CAC_ROWS_PER_BLOCK: rows per wor
 CAC_MAX_ACT_DIM = 64  # include/tsmarl.h TSM_CAC_MAX_ACT_DIM: one lane per action component
 ENS_MAX_MEMBERS = 64  # include/tsmarl.h TSM_ENS_MAX_MEMBERS: members of a grouped ensemble MLP (a bit each in REDQ's subset mask)
 REDQ_ROWS_PER_BLOCK = 256  # include/tsmarl.h TSM_REDQ_ROWS_PER_BLOCK: one row per thread of the REDQ heads
+BDQN_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_BDQN_ROWS_PER_BLOCK: rows per workgroup of the BDQN head
 IQN_ROWS_PER_BLOCK = 16  # include/tsmarl.h TSM_IQN_ROWS_PER_BLOCK: rows per workgroup of the IQN head
 TSM_OK, TSM_ERR_INVALID, TSM_ERR_HIP, TSM_ERR_MALFORMED_BUFFER, TSM_ERR_UNSUPPORTED = range(5)
 
@@ -343,6 +344,10 @@ SIGNATURES = {
     "tsm_redq_target": (_int, [_p, _i32, _u64, _i32, _p, _p, _p, _p, _p, _i64, _p, _p]),
     "tsm_redq_critic_head": (_int, [_p, _i32, _p, _p, _i64, _p, _p, _p, _p]),
     "tsm_redq_mean_q": (_int, [_p, _i32, _i64, _p, _p]),
+    "tsm_bdqn_check": (_int, [_i32, _i32]),
+    "tsm_bdqn_combine": (_int, [_p, _p, _i64, _i32, _i32, _p, _p]),
+    "tsm_bdqn_head": (_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _f64, _int, _p, _p, _p, _p, _p, _p]),
+    "tsm_bdqn_egreedy": (_int, [_p, _i64, _i32, _i32, _p, _u64, _u64, _p, _p, _p]),
 }
 
 _NO_STATUS = {"tsm_critic_rows_w1_image_kj", "tsm_critic_rows_w1_image_elems", "tsm_p2p_ipc_handle_bytes", "tsm_p2p_failed", "tsm_critic_rows_forward_supported", "tsm_critic_rows_param_count", "tsm_critic_rows_grad_grid", "tsm_critic_rows_dw1_chunks", "tsm_ppo_critic_rows_supported", "tsm_ppo_critic_rows_param_count", "tsm_ppo_critic_rows_grid",

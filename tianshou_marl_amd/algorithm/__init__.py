@@ -8,6 +8,7 @@ from .dsac import Alpha, AutoAlpha, DiscreteSAC, DiscreteSACPolicy, DiscreteSACT
 from .cac import (DDPG, SAC, TD3, ContinuousDeterministicPolicy, DDPGTrainingStats, GaussianNoise, SACPolicy,
                   SACTrainingStats, TD3TrainingStats)
 from .redq import REDQ, REDQPolicy, REDQTrainingStats
+from .bdqn import BDQN, BDQNPolicy
 from .pg import A2C, Reinforce
 from .ppo import PPO, policy_within_training_step
 from .ppo_generic import GenericPPO
@@ -16,5 +17,5 @@ __all__ = ["PPO", "A2C", "Reinforce", "GenericPPO", "DQN", "DiscreteQLearningPol
            "QRDQNPolicy", "IQN", "IQNPolicy", "FQF", "FQFPolicy", "FQFTrainingStats", "RainbowDQN", "RainbowPolicy",
            "DiscreteSAC", "DiscreteSACPolicy", "DiscreteSACTrainingStats", "Alpha", "FixedAlpha", "AutoAlpha",
            "DDPG", "TD3", "SAC", "ContinuousDeterministicPolicy", "SACPolicy", "DDPGTrainingStats", "TD3TrainingStats",
-           "SACTrainingStats", "GaussianNoise", "REDQ", "REDQPolicy", "REDQTrainingStats",
+           "SACTrainingStats", "GaussianNoise", "REDQ", "REDQPolicy", "REDQTrainingStats", "BDQN", "BDQNPolicy",
            "policy_within_training_step"]

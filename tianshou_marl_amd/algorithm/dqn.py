@@ -62,14 +62,9 @@ class DiscreteQLearningPolicy(nn.Module):
         if not isinstance(model, self._model_cls):
             raise TypeError(f"DiscreteQLearningPolicy needs a {self._model_cls.__name__} Q-network: the update runs in HIP, "
                             f"there is no autograd fallback (got {type(model).__name__})")
-        n = getattr(action_space, "n", None)
-        if n is None or int(n) * int(atoms) != model.dims[-1]:
-            raise ValueError(f"DiscreteQLearningPolicy: the model has {model.dims[-1]} outputs, the action space "
-                             f"{'no size' if n is None else f'{int(n)} actions'}" + (f" of {atoms} atoms each" if atoms != 1 else ""))
-        ops.dqn_check(int(n))
+        self.n_act = self._n_act_of(model, action_space, int(atoms))
         self.model = model
         self.action_space, self.observation_space = action_space, observation_space
-        self.n_act = int(n)
         self.seed = int(seed)
         self._sample_ctr = 0
         dev = model.flat.device
@@ -79,6 +74,16 @@ class DiscreteQLearningPolicy(nn.Module):
         self._within = False
         self.eps_training, self.eps_inference = float(eps_training), float(eps_inference)
         self._push_eps()
+
+    @staticmethod
+    def _n_act_of(model, action_space: Any, atoms: int) -> int:
+        """The number of actions the acting kernel chooses among, checked against the model's outputs and the kernels' bounds."""
+        n = getattr(action_space, "n", None)
+        if n is None or int(n) * atoms != model.dims[-1]:
+            raise ValueError(f"DiscreteQLearningPolicy: the model has {model.dims[-1]} outputs, the action space "
+                             f"{'no size' if n is None else f'{int(n)} actions'}" + (f" of {atoms} atoms each" if atoms != 1 else ""))
+        ops.dqn_check(int(n))
+        return int(n)
 
     @property
     def device(self) -> torch.device:
@@ -172,6 +177,19 @@ class DeviceOffPolicyRows:
     successor rows, the sampled batch of a prioritized buffer, the priority write-back and `update`.  A learner supplies
     `device`, `gamma`, `n_step`, `lr_scheduler`, `is_within_training_step`, `_preprocess_batch` and `_update_with_batch`."""
 
+    def _agent_column(self, buffer, agent: int | None) -> tuple[int, int]:
+        """-> (k, col): the agent's reward column and the lane its rows are read from (None: the buffer's only column)."""
+        n_col = buffer.rew_store.shape[2]
+        name = type(self).__name__
+        if agent is None:
+            if n_col != 1:
+                raise ValueError(f"{name}: the buffer holds {n_col} reward columns; say which agent's (agent=k)")
+            agent = 0
+        if not 0 <= int(agent) < n_col:
+            raise ValueError(f"{name}: agent column {agent} outside the buffer's {n_col}")
+        k = int(agent)
+        return k, (0 if getattr(buffer, "aec", False) else k)  # AEC rows: one observation / flag per row; joint rows: the lane
+
     # ---- compute_nstep_return (algorithm_base.py:720-815) ---------------------------------------------------------
     def _nstep_rows(self, batch: Batch, buffer, indices, agent: int | None):
         """The n-step walk for `indices` (one launch): the batch leaves with idx_n, mc, gpow, vmask and -- when it came empty,
@@ -182,17 +200,7 @@ class DeviceOffPolicyRows:
         idx = to_tensor(indices, dev, torch.int64).reshape(-1)
         if len(batch.get_keys()) != 0 and len(batch) != idx.numel():
             raise ValueError(f"Batch size {len(batch)} and indices size {idx.numel()} mismatch.")
-        aec = bool(getattr(buffer, "aec", False))
-        n_col = buffer.rew_store.shape[2]
-        name = type(self).__name__
-        if agent is None:
-            if n_col != 1:
-                raise ValueError(f"{name}: the buffer holds {n_col} reward columns; say which agent's (agent=k)")
-            agent = 0
-        if not 0 <= int(agent) < n_col:
-            raise ValueError(f"{name}: agent column {agent} outside the buffer's {n_col}")
-        k = int(agent)
-        col = 0 if aec else k  # AEC rows: one observation / flag per row; joint rows: the agent's lane
+        k, col = self._agent_column(buffer, agent)
         idx_n, mc, gpow, vmask = ops.nstep_return(buffer.index, buffer.term_store, buffer.rew_store, idx, self.n_step,
                                                   self.gamma, rew_col=k, term_col=col)
         batch.idx_n, batch.mc, batch.gpow, batch.vmask = idx_n, mc, gpow, vmask

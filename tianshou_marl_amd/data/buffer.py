@@ -7,7 +7,7 @@ API mirror of `VectorReplayBuffer(total_size, buffer_num)` / `ReplayBufferManage
 `subbuffer_edges`, `get_buffer_indices`, attribute access to stored fields (`buf.rew`, `buf.done` ...).
 
 Storage is time-major SoA in HBM:
-    obs[S, B, N, D] f32, obs_next (optional), act[S, B, N] i32 (with act_dim = k: act[S, B, N, k] f32), rew[S, B, N] f32,
+    obs[S, B, N, D] f32, obs_next (optional), act[S, B, N] i32 (with act_dim = k: act[S, B, N, k] f32; with act_branches = K: act[S, B, N, K] i32), rew[S, B, N] f32,
     terminated/truncated[S, B, N] u8, done[S, B] u8, policy extras logp[S, B, N], v_s[S, B, N]
 with S = ceil(total_size / buffer_num) slots and B = buffer_num envs.  One buffer row is one JOINT
 step of one env (all N agents), i.e. the parallel-mode layout of EnhancedPettingZooEnv
@@ -32,13 +32,20 @@ class DeviceVectorReplayBuffer:
     unfused_adds_only = False
 
     def __init__(self, total_size: int, buffer_num: int, n_agent: int, obs_dim: int, device: str | torch.device = "cuda",
-                 ignore_obs_next: bool = False, store_policy_outputs: bool = True, act_dim: int | None = None) -> None:
-        """act_dim: None -- discrete actions, i32 [S, B, N]; k >= 1 -- `Box` actions of k components, f32 [S, B, N, k]."""
+                 ignore_obs_next: bool = False, store_policy_outputs: bool = True, act_dim: int | None = None,
+                 act_branches: int | None = None) -> None:
+        """act_dim: None -- discrete actions, i32 [S, B, N]; k >= 1 -- `Box` actions of k components, f32 [S, B, N, k].
+        act_branches: K >= 1 -- MultiDiscrete actions of K integer components (BDQN), i32 [S, B, N, K]."""
         if act_dim is not None and int(act_dim) < 1:
             raise ValueError(f"act_dim = {act_dim}: a Box action has at least one component (None: discrete actions)")
+        if act_branches is not None and act_dim is not None:
+            raise ValueError("act_branches (integer components) and act_dim (Box components) exclude one another")
+        if act_branches is not None and int(act_branches) < 1:
+            raise ValueError(f"act_branches = {act_branches}: a branching action has at least one component (None: one integer)")
         self.act_dim = None if act_dim is None else int(act_dim)
-        if self.act_dim is not None:
-            self.unfused_adds_only = True  # the persistent rollouts write i32 actions: a Collector adds the rows unfused
+        self.act_branches = None if act_branches is None else int(act_branches)
+        if self.act_dim is not None or self.act_branches is not None:
+            self.unfused_adds_only = True  # the persistent rollouts write scalar i32 actions: a Collector adds the rows unfused
         self.buffer_num = int(buffer_num)
         self.n_agent = int(n_agent)
         self.obs_dim = int(obs_dim)
@@ -51,7 +58,10 @@ class DeviceVectorReplayBuffer:
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)  # noqa: E731
         self.obs_store = z((S, B, N, D), torch.float32)
         self.obs_next_store = z((S, B, N, D), torch.float32) if self._save_obs_next else None
-        self.act_store = z((S, B, N), torch.int32) if self.act_dim is None else z((S, B, N, self.act_dim), torch.float32)
+        if self.act_branches is not None:
+            self.act_store = z((S, B, N, self.act_branches), torch.int32)
+        else:
+            self.act_store = z((S, B, N), torch.int32) if self.act_dim is None else z((S, B, N, self.act_dim), torch.float32)
         self.rew_store = z((S, B, N), torch.float32)
         self.term_store = z((S, B, N), torch.uint8)
         self.trunc_store = z((S, B, N), torch.uint8)
@@ -196,8 +206,11 @@ class DeviceVectorReplayBuffer:
         pol = batch.get("policy", None)
         logp = t(pol.logp, torch.float32) if isinstance(pol, Batch) and "logp" in pol else None
         v_s = t(pol.v_s, torch.float32) if isinstance(pol, Batch) and "v_s" in pol else None
-        act = (t(np.asarray(batch.act).reshape(R, N), torch.int32) if self.act_dim is None else
-               t(np.asarray(batch.act, np.float32).reshape(R, N, self.act_dim), torch.float32))
+        if self.act_branches is not None:
+            act = t(np.asarray(batch.act).reshape(R, N, self.act_branches), torch.int32)
+        else:
+            act = (t(np.asarray(batch.act).reshape(R, N), torch.int32) if self.act_dim is None else
+                   t(np.asarray(batch.act, np.float32).reshape(R, N, self.act_dim), torch.float32))
         out = self.add_device(
             t(obs, torch.float32).reshape(R, N, self.obs_dim), act,
             t(rew, torch.float32), t(term, torch.uint8), t(trunc, torch.uint8),
@@ -358,10 +371,14 @@ class DeviceAECReplayBuffer(DeviceVectorReplayBuffer):
     aec = True
 
     def __init__(self, total_size: int, buffer_num: int, agents, obs_dim: int, n_act: int | None = None,
-                 device: str | torch.device = "cuda", ignore_obs_next: bool = False, act_dim: int | None = None) -> None:
+                 device: str | torch.device = "cuda", ignore_obs_next: bool = False, act_dim: int | None = None,
+                 act_branches: int | None = None) -> None:
         if act_dim is not None:
             raise NotImplementedError("DeviceAECReplayBuffer holds discrete actions only: `Box` actions (act_dim) go into a "
                                       "joint-step VectorReplayBuffer / PrioritizedVectorReplayBuffer")
+        if act_branches is not None:
+            raise NotImplementedError("DeviceAECReplayBuffer holds one integer action per row: branching actions (act_branches) "
+                                      "go into a joint-step VectorReplayBuffer / PrioritizedVectorReplayBuffer")
         super().__init__(total_size, buffer_num, 1, obs_dim, device=device, ignore_obs_next=ignore_obs_next,
                          store_policy_outputs=False)
         self.agents = list(agents)

@@ -2022,6 +2022,74 @@ def redq_mean_q(q, out=None):
 
 
 # --------------------------------------------------------------------------------------------
+# BDQN (bdqn.py; BranchingNet, utils/net/common.py:557-678; csrc/bdqn.hip)
+# --------------------------------------------------------------------------------------------
+def bdqn_check(num_branches: int, action_per_branch: int) -> None:
+    """The bounds of the BDQN kernels (include/tsmarl.h): ValueError naming the limit."""
+    call("tsm_bdqn_check", int(num_branches), int(action_per_branch))
+
+
+def _bdqn_q(name: str, q):
+    _dev_only(name, q)
+    if q.dim() != 3:
+        raise ValueError(f"{name}: q must be [B, K, A]")
+    bdqn_check(q.shape[1], q.shape[2])
+    return _chk(q, torch.float32, "q"), q.shape[0], q.shape[1], q.shape[2]
+
+
+def bdqn_combine(adv, v):
+    """BranchingNet.forward after its MLPs (common.py:669-677): adv [K, B, A] (the ensemble's output block), v [B] or [B, 1]
+    -> q [B, K, A] = v + adv - mean_a adv."""
+    _dev_only("bdqn_combine", adv, v)
+    if adv.dim() != 3 or adv.shape[1] < 1:
+        raise ValueError("bdqn_combine: adv must be [K, B, A] with B >= 1")
+    K, B, A = adv.shape
+    bdqn_check(K, A)
+    if v.numel() != B:
+        raise ValueError(f"bdqn_combine: v must have {B} entries")
+    q = torch.empty(B, K, A, dtype=torch.float32, device=adv.device)
+    call("tsm_bdqn_combine", ptr(_chk(adv, torch.float32, "adv")), ptr(_chk(v, torch.float32, "v").reshape(-1)), B, K, A, ptr(q),
+         stream_ptr())
+    return q
+
+
+def bdqn_head(q, q_next_online, q_next_target, act, rew, end, gamma: float, weight=None, is_double: bool = True):
+    """BDQN._target_q after its forwards, _compute_return and the masked TD loss with its gradient (bdqn.py:155-195, 211-221)
+    in one launch.  q, q_next_online [B, K, A]; q_next_target [B, K, A] or None (no lagged network); act i32 [B, K]; rew f32
+    [B]; end u8 / bool [B]; weight f32 [B] or None.
+    -> dict(returns [B], prio [B] = sum_k td, d_adv [K, B, A], d_v [B], partial f64): `qmix_finalize(partial, B, out)` gives
+    {loss, the mean taken q}."""
+    q, B, K, A = _bdqn_q("bdqn_head", q)
+    _dev_only("bdqn_head", q_next_online, q_next_target, act, rew, end, weight)
+    if B < 1:
+        raise ValueError("bdqn_head: empty batch")
+    args = _head_args("bdqn_head", B, (("q_next_online", q_next_online, (B, K, A), torch.float32),
+                                       ("q_next_target", q_next_target, (B, K, A), torch.float32),
+                                       ("act", act, (B, K), torch.int32)),
+                      (("rew", rew, torch.float32), ("end", end, torch.uint8), ("weight", weight, torch.float32)))
+    dev = q.device
+    f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
+    out = dict(returns=f(B), prio=f(B), d_adv=f(K, B, A), d_v=f(B), partial=_head_partial(B, _abi.BDQN_ROWS_PER_BLOCK, dev))
+    call("tsm_bdqn_head", ptr(q), *map(ptr, args), B, K, A, float(gamma), int(bool(is_double)), ptr(out["returns"]),
+         ptr(out["prio"]), ptr(out["d_adv"]), ptr(out["d_v"]), ptr(out["partial"]), stream_ptr())
+    return out
+
+
+def bdqn_egreedy(q, eps_dev, seed: int, offset: int = 0, offset_dev=None, out=None):
+    """Per-branch epsilon-greedy actions (bdqn.py:76, 80-103) on the device: q [R, K, A] -> act i32 [R, K].  One coin per ROW;
+    eps read from the device scalar eps_dev; row r draws at Philox counter offset + r."""
+    q, R, K, A = _bdqn_q("bdqn_egreedy", q)
+    _dev_only("bdqn_egreedy", eps_dev, out, offset_dev)
+    if out is None:
+        out = torch.empty(R, K, dtype=torch.int32, device=q.device)
+    elif out.numel() < R * K or not out.is_contiguous():
+        raise ValueError(f"bdqn_egreedy: out must be a contiguous i32 tensor of at least {R * K} entries")
+    call("tsm_bdqn_egreedy", ptr(q), R, K, A, ptr(_chk(eps_dev, torch.float32, "eps_dev")), seed & (2**64 - 1),
+         offset & (2**64 - 1), ptr(offset_dev), ptr(_chk(out, torch.int32, "out")), stream_ptr())
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # Prioritized replay (data/utils/segtree.py, data/buffer/prio.py; csrc/segtree.hip)
 # --------------------------------------------------------------------------------------------
 def segtree_bound(size: int) -> int:

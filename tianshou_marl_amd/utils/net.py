@@ -893,6 +893,157 @@ class RainbowNet(nn.Module):
             v.copy_(torch.as_tensor(np.asarray(sd[prefix + k])).to(v.device, v.dtype).reshape(v.shape))
 
 
+class BranchingNet(nn.Module):
+    """The reference's `BranchingNet` (common.py:557-678, arXiv 1711.08946) on ONE flat f32 vector [common | value | branches].
+    `common` (obs -> h_1 .. h_n) and `value` (h_n -> value_hidden -> 1) are `FlatMLP`s over slices of it (csrc/dense.hip); the K
+    branches (h_n -> action_hidden -> A each) lie behind them in `EnsembleLinear`'s layout with E = K -- per layer weight
+    [K, in, out], then bias [K, 1, out] -- and run as ONE grouped launch per layer (csrc/ensemble.hip).  The reference's common
+    MLP ends in its activation (output_dim = 0): here its last layer stays linear and `tsm_dueling_features` applies the ReLU, so
+    that `tsm_dueling_features_backward` can join the two streams' gradients behind it, as in `RainbowNet`.  The per-branch
+    dueling combine is `tsm_bdqn_combine` (csrc/bdqn.hip).  Only no norm layer and ReLU are served.
+
+    `forward(obs)` -> (logits [B, K, A], state).  `backward((d_adv, d_v))` takes the gradients w.r.t. the branches' raw outputs
+    [K, B, A] and the value [B], with the combine's backward already folded in, as `ops.bdqn_head` returns them."""
+
+    def __init__(self, *, state_shape, num_branches: int = 0, action_per_branch: int = 2, common_hidden_sizes=None,
+                 value_hidden_sizes=None, action_hidden_sizes=None, norm_layer=None, norm_args=None, activation=nn.ReLU,
+                 act_args=None, device: str | torch.device = "cuda", seed: int | None = None,
+                 storage: torch.Tensor | None = None) -> None:
+        super().__init__()
+        for name, v in (("norm_layer", norm_layer), ("norm_args", norm_args), ("act_args", act_args)):
+            if v is not None:
+                raise NotImplementedError(f"BranchingNet: {name} = {v!r} is not served (no norm layer, plain ReLU)")
+        if activation is not nn.ReLU and activation != "relu":
+            raise NotImplementedError(f"BranchingNet: activation = {activation!r} is not served (ReLU only)")
+        common_hidden_sizes = [int(h) for h in (common_hidden_sizes or [])]
+        self.value_hidden_sizes = [int(h) for h in (value_hidden_sizes or [])]
+        self.action_hidden_sizes = [int(h) for h in (action_hidden_sizes or [])]
+        self.state_shape = state_shape
+        K, A = self.num_branches, self.action_per_branch = int(num_branches), int(action_per_branch)
+        ops.bdqn_check(K, A)
+        H = common_hidden_sizes[-1]   # an empty list fails here, as in the reference (common.py:633)
+        self.common_hidden_sizes = common_hidden_sizes
+        D = int(np.prod(state_shape))
+        self._chains = [[D, *common_hidden_sizes], [H, *self.value_hidden_sizes, 1], [H, *self.action_hidden_sizes, A]]
+        self.branch_desc = ops.mlp_desc(self._chains[2], "relu")
+        sizes = [ops.mlp_param_count(ops.mlp_desc(c, "relu")) for c in self._chains[:2]] + [ops.ens_mlp_param_count(self.branch_desc, K)]
+        self.v_off, self.b_off, P = sizes[0], sizes[0] + sizes[1], sum(sizes)
+        if storage is None:
+            storage = torch.zeros(P, dtype=torch.float32, device=device)
+        elif storage.numel() != P or storage.dtype != torch.float32 or not storage.is_contiguous():
+            raise ValueError(f"BranchingNet: storage must be a contiguous f32 vector of {P} elements")
+        self.flat = nn.Parameter(storage, requires_grad=False)
+        s = lambda k: None if seed is None else seed + k  # noqa: E731
+        self.common = FlatMLP(self._chains[0], "relu", device=storage.device, seed=s(0), storage=storage[:self.v_off])
+        self.value = FlatMLP(self._chains[1], "relu", device=storage.device, seed=s(1), storage=storage[self.v_off:self.b_off])
+        self._b_offsets, o = [], self.b_off
+        for i in range(len(self._chains[2]) - 1):
+            k, m = self._chains[2][i], self._chains[2][i + 1]
+            self._b_offsets.append((o, o + K * k * m))
+            o += K * (k * m + m)
+        self.dims = [D, K * A]   # what the policies ask of a Q-network: input width, outputs per row
+        self._saved = None
+        self.reset_branches(s(2))
+
+    # ---- views ------------------------------------------------------------------------------------------------------------
+    @property
+    def branch_flat(self) -> torch.Tensor:
+        return self.flat.data[self.b_off:]
+
+    def branch_weight(self, i: int, flat: torch.Tensor | None = None) -> torch.Tensor:
+        """Layer i of the branches: weight [K, in, out], a view of the flat vector (or of any vector of its layout)."""
+        o, ob = self._b_offsets[i]
+        return (self.flat.data if flat is None else flat)[o:ob].view(self.num_branches, self._chains[2][i], self._chains[2][i + 1])
+
+    def branch_bias(self, i: int, flat: torch.Tensor | None = None) -> torch.Tensor:
+        """Layer i of the branches: bias [K, 1, out]."""
+        _, ob = self._b_offsets[i]
+        K, m = self.num_branches, self._chains[2][i + 1]
+        return (self.flat.data if flat is None else flat)[ob:ob + K * m].view(K, 1, m)
+
+    @torch.no_grad()
+    def reset_branches(self, seed: int | None = None) -> None:
+        """torch nn.Linear default init of every branch layer: uniform +-1 / sqrt(in) for the weight and for the bias."""
+        gen = torch.Generator().manual_seed(seed) if seed is not None else None
+        for i in range(len(self._b_offsets)):
+            bound = 1.0 / math.sqrt(self._chains[2][i])
+            for v in (self.branch_weight(i), self.branch_bias(i)):
+                v.copy_(torch.rand(v.shape, generator=gen) * 2 * bound - bound)
+
+    def clone_over(self, storage: torch.Tensor) -> "BranchingNet":
+        """As `FlatMLP.clone_over`."""
+        return BranchingNet(state_shape=self.state_shape, num_branches=self.num_branches, action_per_branch=self.action_per_branch,
+                            common_hidden_sizes=self.common_hidden_sizes, value_hidden_sizes=self.value_hidden_sizes,
+                            action_hidden_sizes=self.action_hidden_sizes, device=storage.device, seed=0, storage=storage)
+
+    # ---- forward / backward -------------------------------------------------------------------------------------------------
+    def forward(self, obs, state=None, info=None, save: bool = True):
+        """obs [..., D] -> (logits [B, K, A], state): trunk -> features -> value, K branches -> combine."""
+        x = obs if isinstance(obs, torch.Tensor) else torch.as_tensor(np.asarray(obs, np.float32))
+        x = x.to(self.flat.device, torch.float32).contiguous().reshape(-1, self.dims[0])
+        z = FlatMLP.forward(self.common, x, save=save)
+        f = ops.dueling_features(z)
+        v = FlatMLP.forward(self.value, f, save=save)
+        adv, acts = ops.ens_mlp_forward(self.branch_desc, self.num_branches, self.branch_flat, f)
+        if save:
+            self._saved = (z, f, acts)
+        return ops.bdqn_combine(adv, v), state
+
+    def backward(self, d_out, n_split: int = 0, slabs: torch.Tensor | None = None) -> torch.Tensor:
+        """Gradient slabs [n_split, P] of the whole flat vector for the last `forward(save=True)` (`FlatMLP.backward`'s
+        contract), d_out = (d_adv, d_v): the branches' weight slabs and their branch-summed input gradient (members in order),
+        the value stream's slabs and input gradient, the feature join, the trunk's slabs."""
+        if self._saved is None:
+            raise RuntimeError("BranchingNet.backward called before forward")
+        d_adv, d_v = d_out
+        z, f, acts = self._saved
+        B, P, H, K = z.shape[0], self.flat.numel(), self._chains[0][-1], self.num_branches
+        if n_split <= 0:
+            n_split = ops.mlp_n_split(B)
+        if slabs is None:
+            slabs = torch.empty(n_split, P, dtype=torch.float32, device=self.flat.device)
+        elif tuple(slabs.shape) != (n_split, P) or not slabs.is_contiguous():
+            raise ValueError(f"BranchingNet.backward: slabs must be a contiguous [{n_split}, {P}]")
+        d_adv = d_adv.reshape(K, B, self.action_per_branch).contiguous()
+        d_v = d_v.reshape(B, 1).contiguous()
+        ops.ens_mlp_backward(self.branch_desc, K, self.branch_flat, f, acts, d_adv, n_split, slabs=slabs[:, self.b_off:], slab_stride=P)
+        d_fq = ops.ens_mlp_input_grad(self.branch_desc, K, self.branch_flat, f, acts, d_adv, 0, H)
+        self.value.backward(d_v, n_split, slabs=slabs[:, self.v_off:], slab_stride=P)
+        d_z = ops.dueling_features_backward(z, d_fq, self.value.input_grad(d_v, 0, H))
+        self.common.backward(d_z, n_split, slabs=slabs, slab_stride=P)
+        return slabs
+
+    # ---- reference checkpoint compatibility ---------------------------------------------------------------------------
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        """[(key, view)] of `flat` (None: the net's own vector; else any vector of its layout, e.g. an Adam moment) in the
+        reference module's `parameters()` order and shapes: `common.model.{2 i}`, `value.model.{2 i}`, then per branch
+        `branches.{k}.model.{2 i}` -- `nn.Linear`'s [out, in], the transpose of the grouped layout's [in, out] slice."""
+        flat = self.flat.data if flat is None else flat
+        out = []
+        for name, net, lo, hi in (("common", self.common, 0, self.v_off), ("value", self.value, self.v_off, self.b_off)):
+            for (kw, kb), (W, b) in zip(ref_layer_keys(net.n_layers, "seq"), net.layer_views(flat[lo:hi])):
+                out += [(f"{name}.model.{kw}", W), (f"{name}.model.{kb}", b)]
+        for k in range(self.num_branches):
+            for i, (kw, kb) in enumerate(ref_layer_keys(len(self._b_offsets), "seq")):
+                out += [(f"branches.{k}.model.{kw}", self.branch_weight(i, flat)[k].t()),
+                        (f"branches.{k}.model.{kb}", self.branch_bias(i, flat)[k, 0])]
+        return out
+
+    def param_shapes(self) -> list[tuple[int, ...]]:
+        """The reference's parameter shapes in `parameters()` order."""
+        return [tuple(v.shape) for _, v in self.reference_named_views()]
+
+    def to_reference_state_dict(self, prefix: str = "", sd: OrderedDict | None = None) -> OrderedDict:
+        sd = OrderedDict() if sd is None else sd
+        sd.update((prefix + k, v.detach().clone().contiguous().cpu()) for k, v in self.reference_named_views())
+        return sd
+
+    @torch.no_grad()
+    def load_reference_state_dict(self, sd, prefix: str = "") -> None:
+        for k, v in self.reference_named_views():
+            v.copy_(torch.as_tensor(np.asarray(sd[prefix + k])).to(v.device, v.dtype).reshape(v.shape))
+
+
 class MLPActorCritic(nn.Module):
     """Actor and critic MLPs of ARBITRARY widths under one flat parameter vector (`ActorCritic(actor, critic)`,
     common.py:461-474: one optimizer, one global gradient-norm clip).  Layout = actor parameters then critic parameters,
@@ -987,34 +1138,43 @@ class FlatAdam:
                 list(getattr(m, "extra_param_shapes", ()))
         return [tuple(self.param.shape)]
 
+    def _views(self, moment: torch.Tensor) -> list[torch.Tensor]:
+        """`moment` (a vector of the parameter's layout) as the reference's parameters, in `parameters()` order: consecutive
+        blocks of `_shapes()`, or what the module's `reference_named_views` says where its layout is not the reference's
+        concatenation (BranchingNet: a branch's [out, in] weight is a transposed slice of the grouped [K, in, out])."""
+        if isinstance(self._module, BranchingNet):
+            return [v for _, v in self._module.reference_named_views(moment)]
+        out, o = [], 0
+        for shp in self._shapes():
+            n = int(np.prod(shp))
+            out.append(moment[o:o + n].view(shp))
+            o += n
+        return out
+
     def state_dict(self) -> dict:
         """torch.optim.Adam.state_dict() layout (per-parameter `state`, one `param_groups` entry), parameters in the
         module's `parameters()` order -- what `optim_actor.state_dict()` gives in the reference (ctde.py:36-37)."""
-        state, o = {}, 0
-        shapes = self._shapes()
-        for i, shp in enumerate(shapes):
-            n = int(np.prod(shp))
-            if self.step_count > 0:
-                state[i] = {"step": torch.tensor(float(self.step_count)), "exp_avg": self.exp_avg[o:o + n].view(shp).clone(),
-                            "exp_avg_sq": self.exp_avg_sq[o:o + n].view(shp).clone()}
-            o += n
+        state = {}
+        views = list(zip(self._views(self.exp_avg), self._views(self.exp_avg_sq)))
+        if self.step_count > 0:
+            for i, (m, v) in enumerate(views):
+                state[i] = {"step": torch.tensor(float(self.step_count)), "exp_avg": m.contiguous().clone(),
+                            "exp_avg_sq": v.contiguous().clone()}
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
                  "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
-                 "fused": None, "decoupled_weight_decay": False, "params": list(range(len(shapes)))}
+                 "fused": None, "decoupled_weight_decay": False, "params": list(range(len(views)))}
         return {"state": state, "param_groups": [group]}
 
     def load_state_dict(self, sd: dict) -> None:
         self.exp_avg.zero_()
         self.exp_avg_sq.zero_()
-        o, step = 0, 0
-        for i, shp in enumerate(self._shapes()):
-            n = int(np.prod(shp))
+        step = 0
+        for i, (m, v) in enumerate(zip(self._views(self.exp_avg), self._views(self.exp_avg_sq))):
             e = sd["state"].get(i, sd["state"].get(str(i)))
             if e is not None:
-                self.exp_avg[o:o + n].copy_(torch.as_tensor(e["exp_avg"]).reshape(-1))
-                self.exp_avg_sq[o:o + n].copy_(torch.as_tensor(e["exp_avg_sq"]).reshape(-1))
+                m.copy_(torch.as_tensor(e["exp_avg"]).reshape(m.shape))
+                v.copy_(torch.as_tensor(e["exp_avg_sq"]).reshape(v.shape))
                 step = int(float(e["step"]))
-            o += n
         g = sd["param_groups"][0]
         self.step_count, self.lr = step, float(g["lr"])
         self.betas, self.eps, self.weight_decay = tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"])
