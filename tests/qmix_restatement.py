@@ -27,6 +27,24 @@ def layer_shapes(N: int, D: int, A: int, H: int, S: int, E: int, Hh: int):
     return out
 
 
+def mix(q, w1, b1, w2, b2, monotonic: bool):
+    """QMIXMixer.forward after the hypernetworks (ctde.py:485-499): q [B, N], w1 [B, N, E], b1 [B, 1, E], w2 [B, E, 1],
+    b2 [B, 1, 1] -> q_tot [B, 1]."""
+    B = q.shape[0]
+    if monotonic:
+        w1, w2 = torch.abs(w1), torch.abs(w2)
+    h = F.elu(torch.bmm(q.view(B, 1, -1), w1) + b1)
+    return (torch.bmm(h, w2) + b2).view(B, 1)
+
+
+def td_loss(q_tot, q_tot_next, rew_by_agent, term, gamma: float):
+    """The TD target and loss of QMIXPolicy.learn (ctde.py:668-678): q_tot / q_tot_next [B, 1], rew_by_agent [N] of [B],
+    term [B] bool -> the mse_loss scalar."""
+    rewards = torch.stack(list(rew_by_agent), dim=-1).mean(dim=-1, keepdim=True)
+    td_target = rewards + gamma * q_tot_next * (~term).to(q_tot.dtype).unsqueeze(-1)
+    return F.mse_loss(q_tot, td_target)
+
+
 class QmixRestatement:
     def __init__(self, flat, dims, monotonic: bool = True, dtype=torch.float64, device="cpu", lr: float = 1e-3,
                  gamma: float = 0.99) -> None:
@@ -57,17 +75,18 @@ class QmixRestatement:
         x = F.relu(F.linear(x, w[2], w[3]))
         return F.linear(x, w[4], w[5])
 
-    def _mixer(self, ps, q, s):
+    def _hyper(self, ps, s):
+        """The four hypernetworks on the states s [B, S] -> (w1raw [B, N, E], b1 [B, 1, E], w2raw [B, E, 1], b2 [B, 1, 1])."""
         m = ps[6 * self.N:]
-        B = q.shape[0]
+        B = s.shape[0]
         w1 = F.linear(F.relu(F.linear(s, m[0], m[1])), m[2], m[3]).view(B, self.N, -1)
         w2 = F.linear(F.relu(F.linear(s, m[4], m[5])), m[6], m[7]).view(B, -1, 1)
         b1 = F.linear(s, m[8], m[9]).view(B, 1, -1)
         b2 = F.linear(F.relu(F.linear(s, m[10], m[11])), m[12], m[13]).view(B, 1, 1)
-        if self.monotonic:
-            w1, w2 = torch.abs(w1), torch.abs(w2)
-        h = F.elu(torch.bmm(q.view(B, 1, self.N), w1) + b1)
-        return (torch.bmm(h, w2) + b2).view(B, 1)
+        return w1, b1, w2, b2
+
+    def _mixer(self, ps, q, s):
+        return mix(q, *self._hyper(ps, s), self.monotonic)
 
     def _t(self, x, dtype=None):
         return torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x).to(self.device, dtype or self.dtype)
@@ -83,13 +102,10 @@ class QmixRestatement:
             with torch.no_grad():
                 qn.append(self._actor(self.target, i, self._t(obs_next[i])).max(dim=-1, keepdim=True)[0])
         q_all, qn_all = torch.cat(qs, dim=-1), torch.cat(qn, dim=-1)
-        rewards = torch.stack([self._t(rew[i]) for i in range(self.N)], dim=-1).mean(dim=-1, keepdim=True)
         q_total = self._mixer(self.params, q_all, self._t(gs))
         with torch.no_grad():
             q_total_next = self._mixer(self.target, qn_all, self._t(gsn))
-        terminated = self._t(term, torch.bool)
-        td_target = rewards + self.gamma * q_total_next * (~terminated).to(self.dtype).unsqueeze(-1)
-        loss = F.mse_loss(q_total, td_target)
+        loss = td_loss(q_total, q_total_next, [self._t(rew[i]) for i in range(self.N)], self._t(term, torch.bool), self.gamma)
         self.opt.zero_grad()
         loss.backward()
         grads = self.flat_of([p.grad for p in self.params]) if want_grads else None

@@ -4,12 +4,17 @@ Forward / dgrad / wgrad are compared with a float64 torch autograd replica of th
 relative to the tensor's scale, the north star's bar); the CTDE step is compared with the reference's own outputs
 (tests/golden/ctde.npz: logits, both losses, every gradient, every post-Adam weight)."""
 import os
+import sys
 
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from ctde_cases import ctde_head_reference  # noqa: E402
 
 if torch.cuda.is_available():
     from tianshou_marl_amd import ops
@@ -164,17 +169,11 @@ def test_ctde_head_quirk_q7_and_local_fallback():
     rew, term = torch.randn(B, device=DEV), (torch.rand(B, device=DEV) < 0.2).to(torch.uint8)
     logits, act = torch.randn(B, A, device=DEV), torch.randint(0, A, (B,), device=DEV)
     dq, dl, s = ops.ctde_td_head(q, qn, rew, term, 0.9, logits, act)
-    qd, ld = q.double().cpu().requires_grad_(), logits.double().cpu().requires_grad_()
-    td = rew.double().cpu().unsqueeze(-1) + 0.9 * qn.double().cpu() * (1 - term.double().cpu().unsqueeze(-1))
-    critic_loss = torch.nn.functional.mse_loss(qd, td)
-    adv = (td - qd).detach()
-    logp = -torch.nn.functional.cross_entropy(ld, act.cpu(), reduction="none")
-    actor_loss = -(logp * adv).mean()  # (B,) * (B,1) -> (B,B)
-    critic_loss.backward()
-    actor_loss.backward()
-    np.testing.assert_allclose(s.cpu().numpy(), [actor_loss.item(), critic_loss.item()], rtol=1e-5)
-    _close(dq, qd.grad)
-    _close(dl, ld.grad)
+    r = ctde_head_reference(dict(q=q.cpu().numpy(), q_next=qn.cpu().numpy(), rew=rew.cpu().numpy(), term=term.cpu().numpy(),
+                                 logits=logits.cpu().numpy(), act=act.cpu().numpy(), gamma=0.9))   # (B,) * (B,1) -> (B,B), in float64
+    np.testing.assert_allclose(s.cpu().numpy(), [r["actor_loss"], r["critic_loss"]], rtol=1e-5)
+    _close(dq, torch.as_tensor(r["dq"]))
+    _close(dl, torch.as_tensor(r["dlogits"]))
     # no global_obs in the batch -> the critic sees the local observation (ctde.py:144-147)
     actor, critic = DecentralizedActor(6, A, 32, device=DEV, seed=1), CentralizedCritic(6, 1, 32, device=DEV, seed=2)
     pol = CTDEPolicy(actor=actor, critic=critic)
