@@ -305,16 +305,16 @@ def test_counter_advance_iqn_fractions(monkeypatch):
 
 def test_counter_advance_normals_of_the_continuous_learners(monkeypatch):
     """algorithm/cac.py: the learners' `_normal` draws n = B Ad normals at the one counter `_sample_ctr`, then adds n --
-    `ActorCriticOffPolicyAlgorithm._normal` itself runs here on a bare object.  `SACPolicy._sample` advances alike (it needs the
+    `ContinuousActionRows._normal` itself runs here on a bare object.  `SACPolicy._sample` advances alike (it needs the
     actor's forward, so its `+= n` is restated below, not run: a change there would not fail this test); `_emit` draws its n at
     counters `_sample_ctr` .. + n - 1 under the plain seed, through `sample_counter`."""
-    from tianshou_marl_amd.algorithm.cac import ActorCriticOffPolicyAlgorithm
+    from tianshou_marl_amd.algorithm.cac import ContinuousActionRows
 
     seed = BIT63
     calls = _recorder(monkeypatch, "cac_normal", SimpleNamespace(view=lambda *a: None))
     algo = SimpleNamespace(policy=SimpleNamespace(act_dim=3, seed=seed, _sample_ctr=2**32 - 3), noise_source=None, device=None)
     for B in (1, 2, 341, 5):
-        ActorCriticOffPolicyAlgorithm._normal(algo, B)
+        ContinuousActionRows._normal(algo, B)
     assert [a[0] for a, _ in calls] == [3, 6, 1023, 15] and algo.policy._sample_ctr == 2**32 - 3 + 1047
     us = [sr.cac_normal(a[0], a[1], kw["offset"])[1] for a, kw in calls]
     _disjoint(*us)

@@ -4,7 +4,8 @@ from .dqn import DQN, DiscreteQLearningPolicy
 from .iqn import IQN, IQNPolicy
 from .fqf import FQF, FQFPolicy, FQFTrainingStats
 from .rainbow import RainbowDQN, RainbowPolicy
-from .dsac import Alpha, AutoAlpha, DiscreteSAC, DiscreteSACPolicy, DiscreteSACTrainingStats, FixedAlpha
+from .actor_critic import Alpha, AutoAlpha, FixedAlpha
+from .dsac import DiscreteSAC, DiscreteSACPolicy, DiscreteSACTrainingStats
 from .cac import (DDPG, SAC, TD3, ContinuousDeterministicPolicy, DDPGTrainingStats, GaussianNoise, SACPolicy,
                   SACTrainingStats, TD3TrainingStats)
 from .redq import REDQ, REDQPolicy, REDQTrainingStats

@@ -1,12 +1,12 @@
 """DDPG, TD3 and SAC: the off-policy actor-critics for `Box` actions on the HIP path.
 
 Mirror of /root/reference/tianshou/algorithm/modelfree/ddpg.py (`ContinuousPolicyWithExplorationNoise` :45-111,
-`ContinuousDeterministicPolicy` :114-190, `ActorCriticOffPolicyAlgorithm` :196-339, `DDPG` :342-410), td3.py
-(`ActorDualCriticsOffPolicyAlgorithm` :32-102, `TD3` :105-226) and sac.py (`SACPolicy` :54-131, `SAC` :212-336).  The actors and
-critics are `FlatMLP`s (utils/net.py: `ContinuousActorDeterministic`, `ContinuousActorProbabilistic`, `ContinuousCritic`;
-csrc/dense.hip); the critics read rows [obs | act] built by `tsm_maddpg_joint_rows` with one agent; the n-step walk is
-`tsm_nstep_return`; what lies between a network product and an optimiser step is one launch each in csrc/cac.hip.  `Alpha`,
-`FixedAlpha` and `AutoAlpha` are dsac.py's, and the alpha step is `tsm_dsac_alpha_step`.  There is no autograd fallback.
+`ContinuousDeterministicPolicy` :114-190, `DDPG` :342-410), td3.py (`TD3` :105-226) and sac.py (`SACPolicy` :54-131, `SAC`
+:212-336) on actor_critic.py's learner core, twin-critic base and entropy coefficient; `ContinuousActionRows` adds what only a
+`Box` action asks for.  The actors and critics are `FlatMLP`s (utils/net.py: `ContinuousActorDeterministic`,
+`ContinuousActorProbabilistic`, `ContinuousCritic`; csrc/dense.hip); the critics read rows [obs | act] built by
+`tsm_maddpg_joint_rows` with one agent; the n-step walk is `tsm_nstep_return`; what lies between a network product and an
+optimiser step is one launch each in csrc/cac.hip.  There is no autograd fallback.
 
 Kept quirks: Q44 -- DDPG's and TD3's actor loss reads the critic AFTER its step of the same call; Q45 --
 TD3 steps the actor, moves the lagged nets and reports a fresh actor_loss only on calls 0, f, 2f, ...; otherwise `_last` is
@@ -18,7 +18,6 @@ Q50 -- SAC's alpha is stepped from the entropy of before the actor's step, and t
 from __future__ import annotations
 
 import warnings
-from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Any, Literal
 
@@ -32,9 +31,9 @@ from ..data.stats import TrainingStats
 from ..utils.learner import act_result, result_slot, sample_counter, slab_workspace
 from ..utils.net import (ContinuousActorDeterministic, ContinuousActorProbabilistic, ContinuousCritic, FlatMLP, lagged_copy)
 from ..utils.tensor import to_tensor
-from .dqn import DeviceOffPolicyRows, _obs_rows
-from .dsac import Alpha, AutoAlpha, _Schedulers
-from .optim import AdamOptimizerFactory, flat_adam_of
+from .actor_critic import ActorCriticOffPolicyAlgorithm, ActorDualCriticsOffPolicyAlgorithm, Alpha, EntropyCoefficient
+from .dqn import _obs_rows
+from .optim import AdamOptimizerFactory
 
 
 @dataclass(kw_only=True)
@@ -225,34 +224,16 @@ class SACPolicy(_ContinuousPolicy):
 
 
 # ---- the learners (ddpg.py:196-410, td3.py, sac.py:212-336) -------------------------------------------------------------
-class ActorCriticOffPolicyAlgorithm(DeviceOffPolicyRows, nn.Module):
-    """ddpg.py:196-339 on the device buffer: policy, critic, lagged critic, their Adams, the rows [obs | act], the critic step.
-    Every `*_optim` is an `AdamOptimizerFactory` (its hyper-parameters drive the HIP Adam over that network's flat vector)."""
+class ContinuousActionRows:
+    """What a `Box` action adds to actor_critic.py's learner core, in front of it in a learner's bases: the critic
+    [obs | act] -> 1 and its checks, the rows [obs | act], the normal draws, the deterministic and the SAC-style actor step, the
+    twin target, and the policy's Philox counter in the checkpoint."""
 
     _policy_cls: type = _ContinuousPolicy
+    noise_source = None   # (rows, act_dim) -> f32 [rows, act_dim] in HBM: stands in for the Philox draws (tests)
 
-    def __init__(self, *, policy, policy_optim: AdamOptimizerFactory, critic: ContinuousCritic,
-                 critic_optim: AdamOptimizerFactory, tau: float = 0.005, gamma: float = 0.99,
-                 n_step_return_horizon: int = 1) -> None:
-        super().__init__()
-        name = type(self).__name__
-        if not isinstance(policy, self._policy_cls):
-            raise TypeError(f"{name} needs a {self._policy_cls.__name__}, got {type(policy).__name__}")
-        assert 0.0 <= tau <= 1.0, f"tau should be in [0, 1] but got: {tau}"
-        assert 0.0 <= gamma <= 1.0, f"gamma should be in [0, 1] but got: {gamma}"
-        assert n_step_return_horizon > 0, f"n_step_return_horizon should be greater than 0 but got: {n_step_return_horizon}"
-        ops.cac_check(policy.act_dim, int(n_step_return_horizon))
-        self.policy = policy
-        self._check_critic("critic", critic)
-        self.critic = critic
-        self.critic_old = lagged_copy(critic)
-        self.policy_optim, s_a = flat_adam_of(policy_optim, policy.actor, f"{name}: policy_optim", True, ("factory",))
-        self.critic_optim, s_c = flat_adam_of(critic_optim, critic, f"{name}: critic_optim", True, ("factory",))
-        self._scheds = [s for s in (s_a, s_c) if s is not None]
-        self.tau, self.gamma = tau, gamma
-        self.n_step = self.n_step_return_horizon = int(n_step_return_horizon)
-        self.noise_source = None   # (rows, act_dim) -> f32 [rows, act_dim] in HBM: stands in for the Philox draws (tests)
-        self._ws: dict = {}
+    def _check_bounds(self, policy, n_step: int) -> None:
+        ops.cac_check(policy.act_dim, n_step)
 
     def _check_critic(self, name: str, net) -> None:
         actor = self.policy.actor
@@ -264,23 +245,6 @@ class ActorCriticOffPolicyAlgorithm(DeviceOffPolicyRows, nn.Module):
             raise ValueError(f"{type(self).__name__}: {name} maps {net.dims[0]} -> {net.dims[-1]} on {net.flat.device}; it must "
                              f"map {D} + {Ad} -> 1 on {dev}")
 
-    @property
-    def lr_scheduler(self):
-        return _Schedulers(self._scheds) if self._scheds else None
-
-    @property
-    def device(self) -> torch.device:
-        return self.policy.device
-
-    @property
-    def is_within_training_step(self) -> bool:
-        return self.policy.is_within_training_step
-
-    @is_within_training_step.setter
-    def is_within_training_step(self, v: bool) -> None:
-        self.policy.is_within_training_step = bool(v)
-
-    # ---- what the three learners share ------------------------------------------------------------------------------
     def _normal(self, B: int) -> torch.Tensor:
         """Standard normals f32 [B, act_dim]: `noise_source`'s, or `tsm_cac_normal` at the policy's Philox counter."""
         Ad = self.policy.act_dim
@@ -314,18 +278,6 @@ class ActorCriticOffPolicyAlgorithm(DeviceOffPolicyRows, nn.Module):
         w["x_next"][:, :nxt.shape[1]].copy_(nxt)
         return nxt, w, w["x_next"]
 
-    def _critic_step(self, w: dict, x, returns, weight, twin: bool) -> dict:
-        """_minimize_critic_squared_loss for the critic (and critic2): forward, head, backward, Adam step."""
-        q1 = FlatMLP.forward(self.critic, x, save=True)
-        q2 = FlatMLP.forward(self.critic2, x, save=True) if twin else None
-        ch = ops.cac_critic_head(q1, q2, returns, weight)
-        self.critic.backward(ch["dq1"], w["n_split"], slabs=w["slabs_c1"])
-        self.critic_optim.step(w["slabs_c1"])
-        if twin:
-            self.critic2.backward(ch["dq2"], w["n_split"], slabs=w["slabs_c2"])
-            self.critic2_optim.step(w["slabs_c2"])
-        return ch
-
     def _begin_update(self, batch: Batch):
         dev = self.device
         weight = self._pop_weight(batch)
@@ -350,47 +302,43 @@ class ActorCriticOffPolicyAlgorithm(DeviceOffPolicyRows, nn.Module):
         self.policy_optim.step(w["slabs_a"])
         return ah["partial"]
 
-    def _polyak(self) -> None:
-        for old, net in self._lagged():
-            ops.polyak(old.flat.data, net.flat.data, self.tau)
+    def _sac_actor_step(self, w: dict, obs, act, B: int, critics, alpha_dev) -> dict:
+        """The Gaussian-tanh actor's step (sac.py:315-322, redq.py:284-291): a sample of the actor in the action columns of
+        x_pi, `critics(x_pi)` -> (q1a, q2a, g1, g2) the critic values there and their gradients to the action (q2a, g2 None:
+        one value), `tsm_sac_actor_head`, the actor's backward and Adam step.  -> the head's dict."""
+        actor, D = self.policy.actor, obs.shape[1]
+        raw = FlatMLP.forward(actor, obs, save=True)
+        z = self._normal(B)
+        x_pi = ops.maddpg_joint_rows([obs], [act], out=w["x_pi"])
+        ops.sac_action(raw, z, actor.max_action, actor.unbounded, sigma_param=actor.sigma_param, out=x_pi, col0=D)
+        q1a, q2a, g1, g2 = critics(x_pi)
+        ah = ops.sac_actor_head(raw, z, q1a, q2a, g1, g2, alpha_dev, actor.max_action, actor.unbounded,
+                                sigma_param=actor.sigma_param)
+        P = actor.flat.numel()   # the layers' gradient slabs, and behind them sigma_param's: the head's rows summed
+        actor.backward(ah["d_raw"], w["n_split"], slabs=w["slabs_a"], slab_stride=P)
+        if ah["d_sigma"] is not None:
+            ops.cac_col_sum(ah["d_sigma"], w["slabs_a"][:, actor.n_mlp_params:])
+        self.policy_optim.step(w["slabs_a"])
+        return ah
 
-    # ---- checkpoints ---------------------------------------------------------------------------------------------
-    def _nets(self) -> list[tuple[str, FlatMLP]]:
-        """(reference prefix, net) in the reference's module order."""
-        raise NotImplementedError
+    def _twin_target(self, batch: Batch, x_next, logp=None, alpha_dev=None):
+        """The minimum of the two lagged critics on the rows x_next (minus alpha logp: SAC's) as the n-step target."""
+        q1 = FlatMLP.forward(self.critic_old, x_next, save=False)
+        q2 = FlatMLP.forward(self.critic2_old, x_next, save=False)
+        return ops.cac_target(q1, q2, batch.mc, batch.gpow, batch.vmask, logp_next=logp, alpha_dev=alpha_dev)
 
-    def _optims(self) -> dict:
-        return dict(policy_optim=self.policy_optim, critic_optim=self.critic_optim)
-
+    # ---- checkpoints: the policy's Philox counter beside the core's entries --------------------------------------------
     def state_dict(self, *args, **kwargs):  # type: ignore[override]
-        sd = OrderedDict((name.rstrip("."), net.flat.data.detach().clone().cpu()) for name, net in self._nets())
-        sd.update({k: o.state_dict() for k, o in self._optims().items()})
+        sd = super().state_dict()
         sd["sample_ctr"] = self.policy._sample_ctr
         return sd
 
-    @torch.no_grad()
     def load_state_dict(self, sd, *args, **kwargs):  # type: ignore[override]
-        for name, net in self._nets():
-            net.flat.data.copy_(sd[name.rstrip(".")])
-        for k, o in self._optims().items():
-            o.load_state_dict(sd[k])
+        super().load_state_dict(sd)
         self.policy._sample_ctr = int(sd.get("sample_ctr", 0))
 
-    def to_reference_state_dict(self) -> OrderedDict:
-        """The module state_dict of the reference's learner around `Net` + `ContinuousActor*` / `ContinuousCritic`:
-        `policy.actor.*`, `critic.*`, `critic_old.module.*` (lagged_network.py wraps the copies), ..."""
-        sd = OrderedDict()
-        for prefix, net in self._nets():
-            net.to_reference_state_dict(prefix, sd)
-        return sd
 
-    @torch.no_grad()
-    def load_reference_state_dict(self, sd) -> None:
-        for prefix, net in self._nets():
-            net.load_reference_state_dict(sd, prefix)
-
-
-class DDPG(ActorCriticOffPolicyAlgorithm):
+class DDPG(ContinuousActionRows, ActorCriticOffPolicyAlgorithm):
     """ddpg.py:342-410."""
 
     _policy_cls = ContinuousDeterministicPolicy
@@ -402,15 +350,11 @@ class DDPG(ActorCriticOffPolicyAlgorithm):
                          gamma=gamma, n_step_return_horizon=n_step_return_horizon)
         self.actor_old = lagged_copy(policy.actor)
 
-    def _slab_widths(self) -> dict:
-        return dict(slabs_a=self.policy.actor.flat.numel(), slabs_c1=self.critic.flat.numel())
-
     def _lagged(self):
-        return [(self.critic_old, self.critic), (self.actor_old, self.policy.actor)]
+        return super()._lagged() + [(self.actor_old, self.policy.actor)]
 
     def _nets(self):
-        return [("policy.actor.", self.policy.actor), ("critic.", self.critic), ("critic_old.module.", self.critic_old),
-                ("actor_old.module.", self.actor_old)]
+        return super()._nets() + [("actor_old.module.", self.actor_old)]
 
     def _preprocess_batch(self, batch: Batch, buffer, indices, agent: int | None = None) -> Batch:
         """The n-step walk, the lagged actor and the lagged critic on obs_next[idx_n], the target (ddpg.py:287-339, 397-399)."""
@@ -425,7 +369,7 @@ class DDPG(ActorCriticOffPolicyAlgorithm):
         """The critic's step, the actor's step against the stepped critic (quirk Q44), the Polyak moves; both losses land in
         one pinned slot, read after the one synchronisation."""
         obs, act, B, w, x, returns, weight = self._begin_update(batch)
-        ch = self._critic_step(w, x, returns, weight, twin=False)
+        ch = self._critic_step(w, x, lambda q1, q2: ops.cac_critic_head(q1, q2, returns, weight), twin=False)
         batch.weight = ch["prio"]  # prio-buffer
         ap = self._det_actor_step(w, obs, act, B)
         slot = result_slot(w, 2, 2)
@@ -438,46 +382,7 @@ class DDPG(ActorCriticOffPolicyAlgorithm):
         return DDPGTrainingStats(actor_loss=float(h[1, 0]), critic_loss=float(h[0, 0]))
 
 
-class ActorDualCriticsOffPolicyAlgorithm(ActorCriticOffPolicyAlgorithm):
-    """td3.py:32-102: a second critic (None: a copy of the first, quirk Q48) with its lagged copy and Adam; the target is the
-    minimum of the two lagged critics."""
-
-    def __init__(self, *, policy, policy_optim: AdamOptimizerFactory, critic: ContinuousCritic,
-                 critic_optim: AdamOptimizerFactory, critic2: ContinuousCritic | None = None,
-                 critic2_optim: AdamOptimizerFactory | None = None, tau: float = 0.005, gamma: float = 0.99,
-                 n_step_return_horizon: int = 1) -> None:
-        super().__init__(policy=policy, policy_optim=policy_optim, critic=critic, critic_optim=critic_optim, tau=tau,
-                         gamma=gamma, n_step_return_horizon=n_step_return_horizon)
-        if critic2 is not None:
-            self._check_critic("critic2", critic2)
-        self.critic2 = critic2 if critic2 is not None else lagged_copy(critic)   # critic2 or deepcopy(critic) (td3.py:90)
-        self.critic2_old = lagged_copy(self.critic2)
-        self.critic2_optim, s = flat_adam_of(critic2_optim or critic_optim, self.critic2, f"{type(self).__name__}: critic2_optim",
-                                             True, ("factory",))
-        if s is not None:
-            self._scheds.append(s)
-
-    def _slab_widths(self) -> dict:
-        return dict(slabs_a=self.policy.actor.flat.numel(), slabs_c1=self.critic.flat.numel(),
-                    slabs_c2=self.critic2.flat.numel())
-
-    def _optims(self) -> dict:
-        return dict(super()._optims(), critic2_optim=self.critic2_optim)
-
-    def _lagged(self):
-        return [(self.critic_old, self.critic), (self.critic2_old, self.critic2)]
-
-    def _nets(self):
-        return [("policy.actor.", self.policy.actor), ("critic.", self.critic), ("critic_old.module.", self.critic_old),
-                ("critic2.", self.critic2), ("critic2_old.module.", self.critic2_old)]
-
-    def _twin_target(self, batch: Batch, x_next, logp=None, alpha_dev=None):
-        q1 = FlatMLP.forward(self.critic_old, x_next, save=False)
-        q2 = FlatMLP.forward(self.critic2_old, x_next, save=False)
-        return ops.cac_target(q1, q2, batch.mc, batch.gpow, batch.vmask, logp_next=logp, alpha_dev=alpha_dev)
-
-
-class TD3(ActorDualCriticsOffPolicyAlgorithm):
+class TD3(ContinuousActionRows, ActorDualCriticsOffPolicyAlgorithm):
     """td3.py:105-226."""
 
     _policy_cls = ContinuousDeterministicPolicy
@@ -514,7 +419,7 @@ class TD3(ActorDualCriticsOffPolicyAlgorithm):
         """Both critics' steps; on calls 0, f, 2f, ... the actor's step against the stepped critic and the Polyak moves
         (quirk Q45)."""
         obs, act, B, w, x, returns, weight = self._begin_update(batch)
-        ch = self._critic_step(w, x, returns, weight, twin=True)
+        ch = self._critic_step(w, x, lambda q1, q2: ops.cac_critic_head(q1, q2, returns, weight), twin=True)
         batch.weight = ch["prio"]  # prio-buffer
         slot = result_slot(w, 2, 2)
         h = slot["h"]
@@ -540,7 +445,7 @@ class TD3(ActorDualCriticsOffPolicyAlgorithm):
         self._cnt, self._last = int(sd["_cnt"]), sd["_last"]
 
 
-class SAC(ActorDualCriticsOffPolicyAlgorithm):
+class SAC(EntropyCoefficient, ContinuousActionRows, ActorDualCriticsOffPolicyAlgorithm):
     """sac.py:212-336."""
 
     _policy_cls = SACPolicy
@@ -552,8 +457,7 @@ class SAC(ActorDualCriticsOffPolicyAlgorithm):
         super().__init__(policy=policy, policy_optim=policy_optim, critic=critic, critic_optim=critic_optim, critic2=critic2,
                          critic2_optim=critic2_optim, tau=tau, gamma=gamma, n_step_return_horizon=n_step_return_horizon)
         self.deterministic_eval = deterministic_eval
-        self.alpha = Alpha.from_float_or_instance(alpha)
-        self.alpha.device_scalar(self.device)
+        self._init_alpha(alpha)
 
     def _preprocess_batch(self, batch: Batch, buffer, indices, agent: int | None = None) -> Batch:
         """The n-step walk, a sample of the ONLINE actor on obs_next[idx_n] (quirk Q47), the soft target (sac.py:298-302)."""
@@ -569,58 +473,25 @@ class SAC(ActorDualCriticsOffPolicyAlgorithm):
         """Both critics' steps, the actor's step against the stepped critics, the alpha step from the entropy of before the
         actor moved (quirk Q50), the Polyak moves; every statistic lands in one pinned slot."""
         obs, act, B, w, x, returns, weight = self._begin_update(batch)
-        actor, alpha, D, Ad = self.policy.actor, self.alpha, obs.shape[1], self.policy.act_dim
-        alpha_dev = alpha.device_scalar(self.device)
-        ch = self._critic_step(w, x, returns, weight, twin=True)
+        D, Ad = obs.shape[1], self.policy.act_dim
+        alpha_dev = self.alpha.device_scalar(self.device)
+        ch = self._critic_step(w, x, lambda q1, q2: ops.cac_critic_head(q1, q2, returns, weight), twin=True)
         batch.weight = ch["prio"]  # prio-buffer
-        # actor (sac.py:315-322)
-        raw = FlatMLP.forward(actor, obs, save=True)
-        z = self._normal(B)
-        x_pi = ops.maddpg_joint_rows([obs], [act], out=w["x_pi"])
-        ops.sac_action(raw, z, actor.max_action, actor.unbounded, sigma_param=actor.sigma_param, out=x_pi, col0=D)
-        q1a = FlatMLP.forward(self.critic, x_pi, save=True)
-        g1 = self.critic.input_grad(w["ones"], D, Ad)
-        q2a = FlatMLP.forward(self.critic2, x_pi, save=True)
-        g2 = self.critic2.input_grad(w["ones"], D, Ad)
-        ah = ops.sac_actor_head(raw, z, q1a, q2a, g1, g2, alpha_dev, actor.max_action, actor.unbounded,
-                                sigma_param=actor.sigma_param)
-        P = actor.flat.numel()   # the layers' gradient slabs, and behind them sigma_param's: the head's rows summed
-        actor.backward(ah["d_raw"], w["n_split"], slabs=w["slabs_a"], slab_stride=P)
-        if ah["d_sigma"] is not None:
-            ops.cac_col_sum(ah["d_sigma"], w["slabs_a"][:, actor.n_mlp_params:])
-        self.policy_optim.step(w["slabs_a"])
+
+        def critics(x_pi):   # each critic's value at the sampled action, then its gradient to the action columns
+            q1a = FlatMLP.forward(self.critic, x_pi, save=True)
+            g1 = self.critic.input_grad(w["ones"], D, Ad)
+            q2a = FlatMLP.forward(self.critic2, x_pi, save=True)
+            return q1a, q2a, g1, self.critic2.input_grad(w["ones"], D, Ad)
+
+        ah = self._sac_actor_step(w, obs, act, B, critics, alpha_dev)   # sac.py:315-322
         slot = result_slot(w, 3, 2)
         h = slot["h"]   # {critic1_loss, critic2_loss}, {actor_loss, mean entropy}, {alpha_loss, alpha}
         ops.qmix_finalize(ch["partial"], B, h[0])
         ops.qmix_finalize(ah["partial"], B, h[1])
-        auto = isinstance(alpha, AutoAlpha)
-        if auto:   # alpha.update(entropy) (:325-326), from the partials of before the actor's step
-            alpha.step_device(ah["partial"], B, h[2])
+        self._alpha_step(ah["partial"], B, h[2])   # alpha.update(entropy) (:325-326), from before the actor's step
         self._polyak()
         slot["event"].record()
         slot["event"].synchronize()
         return SACTrainingStats(actor_loss=float(h[1, 0]), critic1_loss=float(h[0, 0]), critic2_loss=float(h[0, 1]),
-                                alpha=float(h[2, 1]) if auto else alpha.value, alpha_loss=float(h[2, 0]) if auto else None)
-
-    def state_dict(self, *args, **kwargs):  # type: ignore[override]
-        sd = super().state_dict()
-        if isinstance(self.alpha, AutoAlpha):
-            sd["alpha"] = dict(log_alpha=self.alpha._log_alpha.detach().clone().cpu(), **self.alpha.adam_state())
-        return sd
-
-    def load_state_dict(self, sd, *args, **kwargs):  # type: ignore[override]
-        super().load_state_dict(sd)
-        if isinstance(self.alpha, AutoAlpha):
-            self.alpha.set_log_alpha(sd["alpha"]["log_alpha"])
-            self.alpha.load_adam_state(sd["alpha"])
-
-    def to_reference_state_dict(self) -> OrderedDict:
-        sd = super().to_reference_state_dict()
-        if isinstance(self.alpha, AutoAlpha):
-            sd["alpha._log_alpha"] = self.alpha._log_alpha.detach().clone().cpu()
-        return sd
-
-    def load_reference_state_dict(self, sd) -> None:
-        super().load_reference_state_dict(sd)
-        if isinstance(self.alpha, AutoAlpha):
-            self.alpha.set_log_alpha(sd["alpha._log_alpha"])
+                                **self._alpha_stats(h[2]))

@@ -27,9 +27,9 @@ from .. import ops
 from ..data.batch import Batch
 from ..utils.net import FractionProposalNet, FullQuantileNet
 from ..utils.tensor import to_tensor
+from .actor_critic import _Schedulers
 from .distq import QRDQN, QRDQNPolicy
 from .dqn import DiscreteQLearningPolicy, SimpleLossTrainingStats, _obs_rows
-from .dsac import _Schedulers
 from .iqn import IQN
 from .optim import flat_adam_of
 

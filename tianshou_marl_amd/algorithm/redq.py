@@ -1,8 +1,9 @@
 """REDQ (arXiv 2101.05982): the randomized-ensemble off-policy actor-critic for `Box` actions on the HIP path.
 
-Mirror of /root/reference/tianshou/algorithm/modelfree/redq.py (`REDQPolicy` :37-131, `REDQ` :134-304) on cac.py's plumbing:
-`SACPolicy._sample` for the Gaussian-tanh action, `ActorCriticOffPolicyAlgorithm` for the rows [obs | act], the n-step walk,
-workspaces, checkpoints and schedulers, dsac.py's `Alpha` / `AutoAlpha`.  The critic is an `EnsembleCritic` (utils/net.py):
+Mirror of /root/reference/tianshou/algorithm/modelfree/redq.py (`REDQPolicy` :37-131, `REDQ` :134-304) on cac.py's and
+actor_critic.py's plumbing: `SACPolicy._sample` for the Gaussian-tanh action, `ContinuousActionRows` for the rows [obs | act], the
+n-step walk, workspaces and the SAC-style actor step, `ActorCriticOffPolicyAlgorithm` for the Adams, checkpoints and schedulers,
+`EntropyCoefficient` for alpha.  The critic is an `EnsembleCritic` (utils/net.py):
 ONE flat vector, one grouped launch per layer and role for all E members (csrc/ensemble.hip); the subset target, the ensemble's
 squared loss and the ensemble mean are one launch each in csrc/redq.hip; the actor's head is `tsm_sac_actor_head` fed the
 ensemble's mean Q and its input gradient with d_out = 1 / E.  There is no autograd fallback.
@@ -26,8 +27,8 @@ from .. import ops
 from ..data.batch import Batch
 from ..utils.learner import result_slot
 from ..utils.net import ContinuousActorProbabilistic, EnsembleCritic, FlatMLP
-from .cac import ActorCriticOffPolicyAlgorithm, DDPGTrainingStats, SACPolicy, _ContinuousPolicy
-from .dsac import Alpha, AutoAlpha
+from .actor_critic import ActorCriticOffPolicyAlgorithm, Alpha, EntropyCoefficient
+from .cac import ContinuousActionRows, DDPGTrainingStats, SACPolicy, _ContinuousPolicy
 from .optim import AdamOptimizerFactory
 
 
@@ -49,7 +50,7 @@ class REDQPolicy(SACPolicy):
         self.deterministic_eval = deterministic_eval
 
 
-class REDQ(ActorCriticOffPolicyAlgorithm):
+class REDQ(EntropyCoefficient, ContinuousActionRows, ActorCriticOffPolicyAlgorithm):
     """redq.py:134-304.  `subset_source` (None: numpy's global RNG, quirk Q51) stands in for the subset draw as `noise_source`
     stands in for the normal draws: (ensemble_size, subset_size) -> the member indices of this target computation."""
 
@@ -73,8 +74,7 @@ class REDQ(ActorCriticOffPolicyAlgorithm):
         self.actor_delay = actor_delay
         self.deterministic_eval = deterministic_eval
         self._last_actor_loss = 0.0  # only for logging purposes
-        self.alpha = Alpha.from_float_or_instance(alpha)
-        self.alpha.device_scalar(self.device)
+        self._init_alpha(alpha)
         self.subset_source = None   # (ensemble_size, subset_size) -> member indices: stands in for np.random.choice (tests)
 
     def _check_critic(self, name: str, net) -> None:
@@ -86,21 +86,12 @@ class REDQ(ActorCriticOffPolicyAlgorithm):
         if net.dims[0] != D + Ad or net.flat.device != dev:
             raise ValueError(f"REDQ: {name} maps {net.dims[0]} -> 1 on {net.flat.device}; it must map {D} + {Ad} -> 1 on {dev}")
 
-    def _slab_widths(self) -> dict:
-        return dict(slabs_a=self.policy.actor.flat.numel(), slabs_c1=self.critic.flat.numel())
-
     def _work(self, B: int, **slabs: int) -> dict:
         w = super()._work(B, **slabs)
         if "inv_e" not in w:   # d_out of the actor loss's ensemble mean: 1 / E for every member and row
             E = self.ensemble_size
             w["inv_e"] = torch.full((E, B, 1), 1.0 / E, dtype=torch.float32, device=self.device)
         return w
-
-    def _lagged(self):
-        return [(self.critic_old, self.critic)]
-
-    def _nets(self):
-        return [("policy.actor.", self.policy.actor), ("critic.", self.critic), ("critic_old.module.", self.critic_old)]
 
     def _subset(self) -> np.ndarray:
         if self.subset_source is not None:
@@ -125,7 +116,7 @@ class REDQ(ActorCriticOffPolicyAlgorithm):
         """The ensemble's step; when critic_gradient_step % actor_delay == 0 after the increment (quirk Q53) the actor's step
         against the stepped ensemble's mean and the alpha step; the Polyak move on every call (quirk Q54)."""
         obs, act, B, w, x, returns, weight = self._begin_update(batch)
-        actor, alpha, D, Ad, E = self.policy.actor, self.alpha, obs.shape[1], self.policy.act_dim, self.ensemble_size
+        D, Ad, E = obs.shape[1], self.policy.act_dim, self.ensemble_size
         q = self.critic.forward(x, save=True)
         ch = ops.redq_critic_head(q, returns, weight)
         self.critic.backward(ch["dq"], w["n_split"], slabs=w["slabs_c1"])
@@ -136,56 +127,27 @@ class REDQ(ActorCriticOffPolicyAlgorithm):
         h = slot["h"]   # {critic_loss, 0}, {actor_loss, mean entropy}, {alpha_loss, alpha}
         ops.qmix_finalize(ch["partial"], E * B, h[0])
         stepped = self.critic_gradient_step % self.actor_delay == 0
-        auto = isinstance(alpha, AutoAlpha)
-        if stepped:   # redq.py:284-295
-            alpha_dev = alpha.device_scalar(self.device)
-            raw = FlatMLP.forward(actor, obs, save=True)
-            z = self._normal(B)
-            x_pi = ops.maddpg_joint_rows([obs], [act], out=w["x_pi"])
-            ops.sac_action(raw, z, actor.max_action, actor.unbounded, sigma_param=actor.sigma_param, out=x_pi, col0=D)
-            q_mean = ops.redq_mean_q(self.critic.forward(x_pi, save=True))
-            g_mean = self.critic.input_grad(w["inv_e"], D, Ad)
-            ah = ops.sac_actor_head(raw, z, q_mean, None, g_mean, None, alpha_dev, actor.max_action, actor.unbounded,
-                                    sigma_param=actor.sigma_param)
-            P = actor.flat.numel()   # the layers' gradient slabs, and behind them sigma_param's: the head's rows summed
-            actor.backward(ah["d_raw"], w["n_split"], slabs=w["slabs_a"], slab_stride=P)
-            if ah["d_sigma"] is not None:
-                ops.cac_col_sum(ah["d_sigma"], w["slabs_a"][:, actor.n_mlp_params:])
-            self.policy_optim.step(w["slabs_a"])
+        if stepped:   # redq.py:284-295: the ensemble's mean Q and its gradient to the action, d_out = 1 / E for every member
+            ah = self._sac_actor_step(w, obs, act, B, lambda x_pi: (
+                ops.redq_mean_q(self.critic.forward(x_pi, save=True)), None, self.critic.input_grad(w["inv_e"], D, Ad), None),
+                self.alpha.device_scalar(self.device))
             ops.qmix_finalize(ah["partial"], B, h[1])
-            if auto:   # alpha.update(entropy) (:292-293), from the partials of before the actor's step
-                alpha.step_device(ah["partial"], B, h[2])
+            self._alpha_step(ah["partial"], B, h[2])   # alpha.update(entropy) (:292-293), from before the actor's step
         self._polyak()
         slot["event"].record()
         slot["event"].synchronize()
         if stepped:
             self._last_actor_loss = float(h[1, 0])
-        return REDQTrainingStats(actor_loss=self._last_actor_loss, critic_loss=float(h[0, 0]),
-                                 alpha=float(h[2, 1]) if auto and stepped else alpha.value,
-                                 alpha_loss=float(h[2, 0]) if auto and stepped else None)
+        return REDQTrainingStats(actor_loss=self._last_actor_loss, critic_loss=float(h[0, 0]), **self._alpha_stats(h[2], stepped))
 
     # ---- checkpoints ---------------------------------------------------------------------------------------------
     def state_dict(self, *args, **kwargs):  # type: ignore[override]
         sd = super().state_dict()
         sd.update(critic_gradient_step=self.critic_gradient_step, _last_actor_loss=self._last_actor_loss)
-        if isinstance(self.alpha, AutoAlpha):
-            sd["alpha"] = dict(log_alpha=self.alpha._log_alpha.detach().clone().cpu(), **self.alpha.adam_state())
+        if "alpha" in sd:   # the entropy coefficient's entry stays the last one
+            sd.move_to_end("alpha")
         return sd
 
     def load_state_dict(self, sd, *args, **kwargs):  # type: ignore[override]
         super().load_state_dict(sd)
         self.critic_gradient_step, self._last_actor_loss = int(sd["critic_gradient_step"]), float(sd["_last_actor_loss"])
-        if isinstance(self.alpha, AutoAlpha):
-            self.alpha.set_log_alpha(sd["alpha"]["log_alpha"])
-            self.alpha.load_adam_state(sd["alpha"])
-
-    def to_reference_state_dict(self):
-        sd = super().to_reference_state_dict()
-        if isinstance(self.alpha, AutoAlpha):
-            sd["alpha._log_alpha"] = self.alpha._log_alpha.detach().clone().cpu()
-        return sd
-
-    def load_reference_state_dict(self, sd) -> None:
-        super().load_reference_state_dict(sd)
-        if isinstance(self.alpha, AutoAlpha):
-            self.alpha.set_log_alpha(sd["alpha._log_alpha"])
