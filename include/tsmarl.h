@@ -43,8 +43,11 @@ enum {
     TSM_ERR_MALFORMED_BUFFER = 3, /* buffer_base.py:380-386 */
     TSM_ERR_UNSUPPORTED = 4
 };
+/* In front of a prototype: this int is a result, not a TSM_* status.  Expands to nothing; the Python binding reads it (with the
+ * return types other than int) to know which calls carry a value back instead of raising on non-zero. */
+#define TSM_VALUE
 
-int tsm_abi_version(void);
+TSM_VALUE int tsm_abi_version(void);
 const char *tsm_last_error(void);
 /* name_out: >= 64 bytes.  Fails with TSM_ERR_HIP when no gfx950 device is visible. */
 int tsm_device_info(int *n_cu, int *wave_size, int64_t *hbm_bytes, char *name_out);
@@ -67,7 +70,7 @@ int tsm_mem_d2h(void *dst_host, const void *src, int64_t bytes, void *stream);
 int tsm_mem_set(void *dst, int value, int64_t bytes, void *stream);
 int tsm_stream_sync(void *stream);
 /* Ends a hipGraph capture that failed half-way on `stream` (drops the partial graph); returns 1 if one was ended, else 0. */
-int tsm_stream_abort_capture(void *stream);
+TSM_VALUE int tsm_stream_abort_capture(void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * GAE  [SURVEY 8a: a11, a12]
@@ -407,7 +410,7 @@ int tsm_policy_forward(const float *params, const float *param_image, int32_t ob
  * chip fewer slabs with two tiles each are faster): when one workspace serves minibatches of several sizes, size
  * grad_slabs_out / loss_partial_out by the LARGEST value over those sizes, not by the value at the largest size.
  * tsm_ppo_update_fused writes n_blocks * n_param floats and n_blocks * 4 doubles. */
-int tsm_ppo_update_grid(int64_t M, int32_t max_blocks);
+TSM_VALUE int tsm_ppo_update_grid(int64_t M, int32_t max_blocks);
 int tsm_ppo_update_fused(const float *params, const float *param_image, int32_t obs_dim, int32_t hidden,
                          int32_t n_act,
                          const float *obs, const int32_t *act, const float *logp_old, const float *adv,
@@ -537,7 +540,7 @@ typedef struct {
     double adv_size, good_size, obst_size;                       /* 0.075, 0.05, 0.2 */
     double adv_accel, good_accel, adv_speed, good_speed;        /* 3.0, 4.0, 1.0, 1.3 */
 } tsm_mpe_tag_cfg;
-int tsm_mpe_tag_obs_dim(const tsm_mpe_tag_cfg *cfg_host);
+TSM_VALUE int tsm_mpe_tag_obs_dim(const tsm_mpe_tag_cfg *cfg_host);
 int tsm_mpe_tag_reset(const tsm_mpe_tag_cfg *cfg_host, uint64_t seed, uint64_t *episode_ctr,
                       const int64_t *env_ids, int64_t n_ids, float *agent_pos, float *agent_vel,
                       float *landmark_pos, int32_t *steps, float *obs_out, void *stream);
@@ -609,12 +612,12 @@ int tsm_rollout_tag(const tsm_rollout_tag_desc *desc_host, void *stream);
  * sample -- the launch then yields d(-mean logp)/d params and sum logp (CTDEPolicy.learn's actor term up to the scalar
  * mean(advantage), quirk Q7).
  * ------------------------------------------------------------------------------------------- */
-int tsm_ppo_actor_rows_supported(int32_t obs_dim, int32_t hidden, int32_t n_act);
+TSM_VALUE int tsm_ppo_actor_rows_supported(int32_t obs_dim, int32_t hidden, int32_t n_act);
 /* Raises the dynamic-LDS limit of every instantiation of the actor / critic rows kernels (idempotent, no stream work).  The
  * launch entry points call it themselves; a host that CAPTURES them into a hipGraph calls it once before its first capture. */
 int tsm_ppo_rows_init(void);
 int64_t tsm_ppo_actor_rows_param_count(int32_t obs_dim, int32_t hidden, int32_t n_act);
-int tsm_ppo_actor_rows_grid(int64_t M);
+TSM_VALUE int tsm_ppo_actor_rows_grid(int64_t M);
 int tsm_ppo_actor_rows_update(const float *actor_params, int32_t obs_dim, int32_t hidden, int32_t n_act,
                               const float *obs, const int32_t *act, const float *logp_old, const float *adv,
                               const int64_t *perm, int64_t first_row, int64_t M, const float *adv_stats,
@@ -628,9 +631,9 @@ int tsm_ppo_actor_rows_update(const float *actor_params, int32_t obs_dim, int32_
  * Row i of the minibatch is joint row rows[i] (NULL: first_row + i) of obs_rows [n][in_dim]; returns / v_s_old are
  * per-sample arrays.  grad_slabs_out [n_blocks][tsm_ppo_critic_rows_param_count]; loss_partial_out f64 [n_blocks][4] =
  * {0, sum of the value-loss terms, 0, 0}; the mean is over Mr * n_agent samples. */
-int tsm_ppo_critic_rows_supported(int32_t in_dim, int32_t hidden, int32_t n_agent);
+TSM_VALUE int tsm_ppo_critic_rows_supported(int32_t in_dim, int32_t hidden, int32_t n_agent);
 int64_t tsm_ppo_critic_rows_param_count(int32_t in_dim, int32_t hidden);
-int tsm_ppo_critic_rows_grid(int64_t Mr);
+TSM_VALUE int tsm_ppo_critic_rows_grid(int64_t Mr);
 int tsm_ppo_critic_rows_update(const float *critic_params, int32_t in_dim, int32_t hidden, int32_t n_agent,
                                const float *obs_rows, const float *returns, const float *v_s_old, const int64_t *rows,
                                int64_t first_row, int64_t Mr, const tsm_ppo_cfg *cfg, int32_t n_blocks,
@@ -645,7 +648,7 @@ int tsm_ppo_critic_rows_update(const float *critic_params, int32_t in_dim, int32
  * captured graph carries for the rows that need it, tsm_value_next_select).  The first layer sums k in a fixed permuted
  * order (csrc/critic_rows.hip): values agree with tsm_mlp_forward to f32 rounding, not bit for bit.
  * tsm_critic_rows_init: one-time function attributes of the instantiation serving in_dim -- call outside stream capture. */
-int tsm_critic_rows_forward_supported(int32_t in_dim, int32_t hidden);
+TSM_VALUE int tsm_critic_rows_forward_supported(int32_t in_dim, int32_t hidden);
 int tsm_critic_rows_init(int32_t in_dim, int32_t hidden);
 int tsm_critic_rows_forward(const float *critic_params, int32_t in_dim, int32_t hidden, int32_t n_out,
                             const float *obs_rows, const int64_t *rows, int64_t first_row, int64_t Mr,
@@ -683,10 +686,10 @@ int tsm_critic_rows_forward(const float *critic_params, int32_t in_dim, int32_t 
  * (3.8 us of a 10 us prologue at in_dim = 384).  tsm_critic_rows_w1_image builds it from w0; tsm_adam_step_segs keeps it in
  * step with the parameters (tsm_slab_seg.frag_image).  It must hold the SAME values as critic_params' w0; NULL = gather. */
 int64_t tsm_critic_rows_param_count(int32_t in_dim, int32_t hidden, int32_t n_out);
-int tsm_critic_rows_w1_image_kj(int32_t in_dim);
+TSM_VALUE int tsm_critic_rows_w1_image_kj(int32_t in_dim);
 int64_t tsm_critic_rows_w1_image_elems(int32_t in_dim);
 int tsm_critic_rows_w1_image(const float *w0, int32_t in_dim, float *image_out, void *stream);
-int tsm_critic_rows_grad_grid(int64_t Mr, int32_t td);
+TSM_VALUE int tsm_critic_rows_grad_grid(int64_t Mr, int32_t td);
 int tsm_critic_rows_grad_ppo(const float *critic_params, const float *w1_image, int32_t in_dim, int32_t hidden, int32_t n_agent,
                              const float *obs_rows, const float *returns, const float *v_s_old, const int64_t *rows,
                              int64_t first_row, int64_t Mr, const tsm_ppo_cfg *cfg, int32_t n_blocks, float *dh1_out,
@@ -703,7 +706,7 @@ int tsm_critic_rows_grad_td(const float *critic_params, const float *w1_image, i
  * segment).  One workgroup; fixed summation order.  scalars_out may be pinned host memory. */
 int tsm_ctde_finalize(const double *critic_partial, int32_t nb_c, const double *actor_partial, int32_t nb_a, int64_t B,
                       float *scalars_out, float *mean_adv_out, void *stream);
-int tsm_critic_rows_dw1_chunks(int64_t Mr, int32_t in_dim);
+TSM_VALUE int tsm_critic_rows_dw1_chunks(int64_t Mr, int32_t in_dim);
 /* side (nullable, at most 2): gradient-slab sets of OTHER parameter segments, already complete when this launch starts (the
  * actor step's slabs, the small-gradient slabs of launch (A)), summed to ONE row each by extra workgroups of this launch while
  * its main workgroups wait on their loads: out[i] = sum over slabs of slabs[s * stride + i] in tsm_adam_step's own order, so
@@ -754,7 +757,7 @@ int tsm_p2p_adam_step(void *handle, float *param, const float *grad_slabs, int32
                       double beta2, double eps, double weight_decay, float *param_image, const int32_t *image_map, void *stream);
 int tsm_p2p_set_timeout(void *handle, double seconds);
 int tsm_p2p_handshake(void *handle, int32_t *ok_out, void *stream);
-int tsm_p2p_failed(void *handle);
+TSM_VALUE int tsm_p2p_failed(void *handle);
 /* The error word copied asynchronously into PINNED host memory behind the work queued on `stream`: valid once the host has waited
  * for that point of the stream.  The host binding queues it in front of the event of every update's loss statistics and raises
  * on every rank when it reads them (no extra synchronisation; algorithm/ppo.py, ppo_generic.py). */
@@ -984,6 +987,7 @@ int tsm_adam_step_coef64(float *param, const float *grad_slabs, int32_t n_slab, 
  *           words of Philox4x32-10 keyed by seed at counter offset + *offset_dev + r (offset_dev nullable), so a batch
  *           drawn in pieces with the offset advanced equals the batch drawn at once.  act_out i32 [R].
  * ------------------------------------------------------------------------------------------- */
+#define TSM_DQN_ROWS_PER_BLOCK 256  /* one row per thread of the TD head (tsm_dqn_partial_elems counts by it) */
 int tsm_nstep_return(const void *state, int64_t buffer_num, int64_t sub_size, const uint8_t *done_store,
                      const uint8_t *term_store, int64_t term_row_stride, int32_t term_col, const float *rew_store,
                      int64_t rew_row_stride, int32_t rew_col, const int64_t *indices, int64_t I, int32_t n_step,
@@ -1353,7 +1357,7 @@ int tsm_fqf_head(const float *out, const float *out_tau, const float *q_next, co
 #define TSM_NOISY_MAX_LAYERS 24
 typedef struct tsm_noisy_layer {
     int64_t off, eff_off, slot_off;
-    int32_t in, out, noisy, _pad;
+    int32_t n_in, n_out, noisy, _pad;
 } tsm_noisy_layer;
 typedef struct tsm_noisy_net {
     int32_t n_layers, _pad;

@@ -2,6 +2,7 @@
 symbol declared in include/tsmarl.h; argument validation that needs no device works."""
 import ctypes as C
 import os
+import re
 
 import pytest
 
@@ -38,6 +39,104 @@ def test_abi_version_and_sizes(lib):
     assert lib.tsm_vrb_state_bytes(8, 3) == (6 * 8 + 24 + 1) * 8
     assert lib.tsm_ppo_loss_partial_elems(0) == 0
     assert lib.tsm_ppo_loss_partial_elems(257) == 8
+
+
+def c_layout_mismatches(structs, header_path, workdir):
+    """The struct layouts the C compiler gives `header_path` against the ctypes classes `structs` {name: class}: a list of
+    (what, ctypes figure, compiler's figure), empty when they agree.  `structs` supplies only the struct and field names that
+    the generated program asks about; sizeof and every offsetof / member size are the compiler's."""
+    import shutil
+    import subprocess
+
+    lines = ["#include <stddef.h>", "#include <stdio.h>", f'#include "{header_path}"', "int main(void) {"]
+    for name, cls in structs.items():
+        lines.append(f'    printf("{name} %zu\\n", sizeof({name}));')
+        lines += [f'    printf("{name}.{f} %zu %zu\\n", offsetof({name}, {f}), sizeof((({name} *)0)->{f}));'
+                  for f, _ in cls._fields_]
+    lines += ["    return 0;", "}"]
+    cc = shutil.which("cc")
+    src = os.path.join(workdir, "layout.c" if cc else "layout.cpp")   # no cc: hipcc compiles it as plain host C++
+    exe = os.path.join(workdir, "layout")
+    with open(src, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    subprocess.run([cc or _build.HIPCC, src, "-o", exe], check=True, capture_output=True, text=True)
+    seen = {}
+    for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines():
+        what, *figures = line.split()
+        seen[what] = tuple(int(x) for x in figures)
+    want = {}
+    for name, cls in structs.items():
+        want[name] = (C.sizeof(cls),)
+        want.update({f"{name}.{f}": (getattr(cls, f).offset, getattr(cls, f).size) for f, _ in cls._fields_})
+    return [(what, want.get(what), seen.get(what)) for what in sorted(set(want) | set(seen)) if want.get(what) != seen.get(what)]
+
+
+def test_struct_layouts_match_the_c_compiler(tmp_path):
+    """Every ctypes struct that _abi derives from tsmarl.h has the size, and every field the offset and size, that the host
+    C compiler gives the same header: a dropped, reordered or mistyped field moves what follows it or the total."""
+    structs = {k: v for k, v in vars(_abi).items() if isinstance(v, type) and issubclass(v, C.Structure)}
+    sizes = {"tsm_field": 24, "tsm_slab_reduce": 40, "tsm_noisy_layer": 40, "tsm_mlp_desc": 44, "tsm_ppo_cfg": 48,
+             "tsm_slab_seg": 64, "tsm_gather_field": 72, "tsm_mpe_cfg": 88, "tsm_mpe_tag_cfg": 112, "tsm_qmix_agents": 320,
+             "tsm_maddpg_agents": 320, "tsm_rollout_desc": 368, "tsm_rollout_tag_desc": 416, "tsm_noisy_net": 992}
+    assert {k: C.sizeof(v) for k, v in structs.items()} == sizes   # ABI version 4: a change here bumps TSM_ABI_VERSION
+    assert len(_abi.tsm_rollout_desc._fields_) == len(_abi.tsm_rollout_tag_desc._fields_) == 40
+    assert c_layout_mismatches(structs, _abi.HEADER_PATH, str(tmp_path)) == []
+
+
+def test_binding_follows_the_mapping_rules():
+    """One or more literal cases per rule of _abi's docstring, read off the header by eye."""
+    sig, p, i32, i64, f64 = _abi.SIGNATURES, C.c_void_p, C.c_int32, C.c_int64, C.c_double
+    # scalars
+    assert sig["tsm_ctde_td_head"][1][5] is C.c_float and sig["tsm_ctde_td_head"][0] is C.c_int
+    assert sig["tsm_c51_head"][1][:15] == [p] * 10 + [i64, i32, i32, f64, f64] and len(sig["tsm_c51_head"][1]) == 20
+    assert sig["tsm_categorical_sample"][1] == [p, i64, i32, C.c_uint64, C.c_uint64, p, C.c_int, p, p, p]
+    assert sig["tsm_abi_version"] == (C.c_int, [])
+    # char * as return and as argument
+    assert sig["tsm_last_error"] == (C.c_char_p, [])
+    assert sig["tsm_kernel_option_set"][1] == [C.c_char_p, i32]
+    # a pointer to a struct of the header; every other pointer, `const float *const *` included
+    assert sig["tsm_mlp_param_count"] == (i64, [C.POINTER(_abi.tsm_mlp_desc)])
+    assert sig["tsm_adam_step_segs"][1][:3] == [p, C.POINTER(_abi.tsm_slab_seg), i32]
+    assert sig["tsm_global_state"][1][0] is p and sig["tsm_kernel_option_get"][1] == [C.c_char_p, p]
+    # members: any pointer is c_void_p, arrays by literal, macro and macro + 1, several declarators per line, nesting by value
+    fields = {name: dict(cls._fields_) for name, cls in vars(_abi).items() if isinstance(cls, type) and issubclass(cls, C.Structure)}
+    assert fields["tsm_qmix_agents"]["q"] is p * 8 and fields["tsm_rollout_tag_desc"]["params"] is p * 2
+    assert fields["tsm_mlp_desc"]["dims"] is i32 * 9
+    assert fields["tsm_rollout_tag_desc"]["offset"] is C.c_uint64 * 2 and fields["tsm_rollout_tag_desc"]["env"] is _abi.tsm_mpe_tag_cfg
+    assert fields["tsm_noisy_net"]["layer"] is _abi.tsm_noisy_layer * 24 and fields["tsm_rollout_desc"]["done_ctr"] is p
+    assert [f for f, _ in _abi.tsm_slab_seg._fields_] == ["slabs", "offset", "n", "stride", "n_slab", "frag_k1", "scale_dev",
+                                                          "frag_image", "frag_kj", "_pad"]
+    # constants come from their #defines and the enum
+    assert (_abi.MAX_GATHER_FIELDS, _abi.DQN_ROWS_PER_BLOCK, _abi.NOISY_MAX_LAYERS, _abi.QMIX_MAX_AGENTS) == (12, 256, 24, 8)
+    assert (_abi.TSM_OK, _abi.TSM_ERR_INVALID, _abi.TSM_ERR_HIP, _abi.TSM_ERR_MALFORMED_BUFFER, _abi.TSM_ERR_UNSUPPORTED) == (0, 1, 2, 3, 4)
+    # value, not status: by return type, or an int that TSM_VALUE marks (13 marked + 24 by type today)
+    assert {"tsm_abi_version", "tsm_vrb_state_bytes", "tsm_last_error", "tsm_ppo_update_grid"} <= _abi._NO_STATUS
+    assert not {"tsm_vrb_init", "tsm_dqn_check", "tsm_distq_check"} & _abi._NO_STATUS and len(_abi._NO_STATUS) == 37
+
+
+def test_header_reader_refuses_what_it_does_not_support(tmp_path):
+    ok = _abi.read_header("#define TSM_N 3\ntypedef struct { const float *a, *b[TSM_N + 1]; int32_t n; } tsm_s;\n"
+                          "TSM_VALUE int tsm_f(const tsm_s *s, void **out);\nint64_t tsm_g(void);")
+    assert ok.signatures == {"tsm_f": (C.c_int, [C.POINTER(ok.structs["tsm_s"]), C.c_void_p]), "tsm_g": (C.c_int64, [])}
+    assert ok.structs["tsm_s"]._fields_ == [("a", C.c_void_p), ("b", C.c_void_p * 4), ("n", C.c_int32)]
+    assert ok.no_status == {"tsm_f", "tsm_g"} and ok.defines == {"TSM_N": 3}
+    for bad in ("int tsm_f(void (*callback)(int), int n);",                      # a function-pointer parameter
+                "typedef struct { int32_t a[TSM_UNKNOWN]; } tsm_s;",             # an array length it cannot resolve
+                "#define TSM_N 2\ntypedef struct { int32_t a[2 * TSM_N]; } tsm_s;",
+                "typedef struct { unsigned n; } tsm_s;",                         # a type outside the scalar list
+                "int tsm_f(long n);",
+                "#define TSM_N (1 << 4)"):
+        with pytest.raises(ValueError, match="tsmarl.h reader"):
+            _abi.read_header(bad)
+    # no header: ImportError naming the path (a copy of the module in a tree without include/)
+    import importlib.util
+    import shutil
+
+    os.makedirs(tmp_path / "pkg")
+    shutil.copy(_abi.__file__, tmp_path / "pkg" / "_abi.py")
+    spec = importlib.util.spec_from_file_location("_abi_without_header", tmp_path / "pkg" / "_abi.py")
+    with pytest.raises(ImportError, match=re.escape(str(tmp_path / "include" / "tsmarl.h"))):
+        spec.loader.exec_module(importlib.util.module_from_spec(spec))
 
 
 def test_argument_validation_maps_to_python_errors(lib):
@@ -146,7 +245,6 @@ _REACHED_THROUGH_CLASSES = {
     # exports for ctypes callers and the runtime's own error path
     **{f"tsm_mem_{s}": "test_abi_symbols.py" for s in ("alloc", "free", "h2d", "d2h", "set")},
     "tsm_stream_sync": "test_abi_symbols.py", "tsm_stream_abort_capture": "test_abi_symbols.py",
-    "tsm_last_error": "test_abi_symbols.py",
 }
 
 

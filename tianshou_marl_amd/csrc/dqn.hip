@@ -24,7 +24,7 @@
 #include "q_head_dev.h"
 
 namespace {
-constexpr int kDThreads = 256;
+constexpr int kDThreads = TSM_DQN_ROWS_PER_BLOCK;
 
 __global__ __launch_bounds__(kDThreads) void dqn_td_head_kernel(
     const float *__restrict__ q, const float *__restrict__ qn_on, const float *__restrict__ qn_tg,

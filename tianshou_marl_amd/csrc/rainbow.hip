@@ -21,7 +21,7 @@ constexpr int kRMaxDim = 65536;
 constexpr int64_t kRMaxRows = (int64_t)1 << 31;
 constexpr uint64_t kNoiseKey = 0x52424E4F4953455Full;   // folded into the seed: a Philox key no other draw uses
 
-__device__ __forceinline__ int64_t layer_w(const tsm_noisy_layer &L) { return (int64_t)L.in * L.out; }
+__device__ __forceinline__ int64_t layer_w(const tsm_noisy_layer &L) { return (int64_t)L.n_in * L.n_out; }
 
 // ---- tsm_noisy_sample ------------------------------------------------------------------------------------------------
 // One thread per Philox block = four consecutive slots.  The slots of a layer are contiguous in the flat vector (eps_p [in]
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kRThreads) void noisy_sample_kernel(tsm_noisy_net n
         for (int l = 0; l < net.n_layers; ++l) {
             const tsm_noisy_layer L = net.layer[l];
             const int64_t k = s - L.slot_off;
-            if (L.noisy && k >= 0 && k < (int64_t)L.in + L.out) addr = L.off + 2 * layer_w(L) + 2 * (int64_t)L.out + k;
+            if (L.noisy && k >= 0 && k < (int64_t)L.n_in + L.n_out) addr = L.off + 2 * layer_w(L) + 2 * (int64_t)L.n_out + k;
         }
         if (addr >= 0) flat[addr] = noisy_f(z[j]);
     }
@@ -70,24 +70,24 @@ __global__ __launch_bounds__(kRThreads) void noisy_compose_kernel(tsm_noisy_net 
                                                                   int training, float *__restrict__ eff) {
     const tsm_noisy_layer L = net.layer[blockIdx.y];
     const int64_t nw = layer_w(L), j = (int64_t)blockIdx.x * kRThreads + threadIdx.x;
-    if (j >= nw + L.out) return;
+    if (j >= nw + L.n_out) return;
     const float *p = flat + L.off;
     float val;
     if (!L.noisy) {
         val = p[j];
     } else {
-        const float *eps_p = p + 2 * nw + 2 * (int64_t)L.out, *eps_q = eps_p + L.in;
+        const float *eps_p = p + 2 * nw + 2 * (int64_t)L.n_out, *eps_q = eps_p + L.n_in;
         if (j < nw) {
             val = p[j];
             if (training) {
-                const int o = (int)(j / L.in), i = (int)(j - (int64_t)o * L.in);
+                const int o = (int)(j / L.n_in), i = (int)(j - (int64_t)o * L.n_in);
                 const float e = eps_q[o] * eps_p[i];   // the outer product first (discrete.py:369)
                 val = val + p[nw + j] * e;
             }
         } else {
             const int o = (int)(j - nw);
             val = p[2 * nw + o];
-            if (training) val = val + p[2 * nw + L.out + o] * eps_q[o];
+            if (training) val = val + p[2 * nw + L.n_out + o] * eps_q[o];
         }
     }
     eff[L.eff_off + j] = val;
@@ -101,24 +101,24 @@ __global__ __launch_bounds__(kRThreads) void noisy_grad_kernel(tsm_noisy_net net
                                                                float *__restrict__ slabs) {
     const tsm_noisy_layer L = net.layer[blockIdx.y];
     const int64_t nw = layer_w(L), j = (int64_t)blockIdx.x * kRThreads + threadIdx.x;
-    if (j >= nw + L.out) return;
+    if (j >= nw + L.n_out) return;
     const float g = eff_slabs[(int64_t)blockIdx.z * net.P_eff + L.eff_off + j];
     float *d = slabs + (int64_t)blockIdx.z * net.P + L.off;
     if (!L.noisy) {
         d[j] = g;
         return;
     }
-    const float *eps_p = flat + L.off + 2 * nw + 2 * (int64_t)L.out, *eps_q = eps_p + L.in;
+    const float *eps_p = flat + L.off + 2 * nw + 2 * (int64_t)L.n_out, *eps_q = eps_p + L.n_in;
     if (j < nw) {
-        const int o = (int)(j / L.in), i = (int)(j - (int64_t)o * L.in);
+        const int o = (int)(j / L.n_in), i = (int)(j - (int64_t)o * L.n_in);
         d[j] = g;
         d[nw + j] = training ? g * (eps_q[o] * eps_p[i]) : 0.f;
     } else {
         const int o = (int)(j - nw);
         d[2 * nw + o] = g;
-        d[2 * nw + L.out + o] = training ? g * eps_q[o] : 0.f;
+        d[2 * nw + L.n_out + o] = training ? g * eps_q[o] : 0.f;
     }
-    if (j < (int64_t)L.in + L.out) d[2 * nw + 2 * (int64_t)L.out + j] = 0.f;
+    if (j < (int64_t)L.n_in + L.n_out) d[2 * nw + 2 * (int64_t)L.n_out + j] = 0.f;
 }
 
 // ---- dueling streams ---------------------------------------------------------------------------------------------------
@@ -173,16 +173,16 @@ int net_check(const char *who, const tsm_noisy_net *net) {
     int64_t off = 0, eff = 0, slot = 0;
     for (int l = 0; l < net->n_layers; ++l) {
         const tsm_noisy_layer &L = net->layer[l];
-        TSM_REQUIRE(L.in >= 1 && L.in <= kRMaxDim && L.out >= 1 && L.out <= kRMaxDim,
-                    "%s: layer %d is %d -> %d, widths must lie in [1, %d]", who, l, L.in, L.out, kRMaxDim);
+        TSM_REQUIRE(L.n_in >= 1 && L.n_in <= kRMaxDim && L.n_out >= 1 && L.n_out <= kRMaxDim,
+                    "%s: layer %d is %d -> %d, widths must lie in [1, %d]", who, l, L.n_in, L.n_out, kRMaxDim);
         TSM_REQUIRE(L.noisy == 0 || L.noisy == 1, "%s: layer %d: noisy = %d is neither 0 nor 1", who, l, L.noisy);
         TSM_REQUIRE(L.off == off && L.eff_off == eff && L.slot_off == slot,
                     "%s: layer %d starts at (%lld, %lld, slot %lld), the layers before it end at (%lld, %lld, slot %lld)", who, l,
                     (long long)L.off, (long long)L.eff_off, (long long)L.slot_off, (long long)off, (long long)eff, (long long)slot);
-        const int64_t nw = (int64_t)L.in * L.out;
-        off += L.noisy ? 2 * nw + 3 * (int64_t)L.out + L.in : nw + L.out;
-        eff += nw + L.out;
-        slot += L.noisy ? (int64_t)L.in + L.out : 0;
+        const int64_t nw = (int64_t)L.n_in * L.n_out;
+        off += L.noisy ? 2 * nw + 3 * (int64_t)L.n_out + L.n_in : nw + L.n_out;
+        eff += nw + L.n_out;
+        slot += L.noisy ? (int64_t)L.n_in + L.n_out : 0;
     }
     TSM_REQUIRE(net->P == off && net->P_eff == eff && net->n_slots == slot,
                 "%s: the table says P = %lld, P_eff = %lld, n_slots = %lld, its layers add up to %lld, %lld, %lld", who,
@@ -194,7 +194,7 @@ int net_check(const char *who, const tsm_noisy_net *net) {
 int64_t largest_layer(const tsm_noisy_net *net) {
     int64_t m = 0;
     for (int l = 0; l < net->n_layers; ++l) {
-        const int64_t n = (int64_t)net->layer[l].in * net->layer[l].out + net->layer[l].out;
+        const int64_t n = (int64_t)net->layer[l].n_in * net->layer[l].n_out + net->layer[l].n_out;
         m = n > m ? n : m;
     }
     return m;
