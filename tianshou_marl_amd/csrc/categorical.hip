@@ -6,6 +6,8 @@
 //  entropy = -sum(softmax * logits_n);  sample ~ softmax;  mode = argmax.
 // Sampling: inverse-CDF with one Philox4x32-10 uniform per row, counter = (offset + row), key = seed.
 // One thread per row; A is small (5 for simple_spread), rows are A*4 bytes apart.
+#include <float.h>
+
 #include "common.h"
 #include "philox.h"
 
@@ -53,7 +55,10 @@ __global__ void logp_ent_kernel(const float *__restrict__ logits, const int32_t 
     if (logp_out) logp_out[i] = lg[act[i]] - lse;
     if (ent_out) {
         float h = 0.f;
-        for (int j = 0; j < A; ++j) { const float l = lg[j] - lse; h -= expf(l) * l; }
+        // As torch: probs = softmax, which sums to 1 whatever rounding lse took, times the normalised logits clamped to finfo.min
+        // (an entry at -inf adds 0 * -FLT_MAX = 0, not NaN).  expf(lg[j] - lse) in the softmax's place sums to exp(-d) for an lse
+        // that is off by d -- half an ulp of lse, 5e-4 at |logits| ~ 1e4 -- and turns it into an error of d (1 - H) in place of d.
+        for (int j = 0; j < A; ++j) { const float l = fmaxf(lg[j] - lse, -FLT_MAX); h -= expf(lg[j] - m) / s * l; }
         ent_out[i] = h;
     }
 }

@@ -3,7 +3,8 @@
 // Replaces ReplayBufferManager.add / ReplayBuffer._update_state_pre_add / sample_indices(0) /
 // unfinished_index / _prev_index / _next_index / reset
 // (/root/reference/tianshou/data/buffer/manager.py:70-229,306-358; buffer_base.py:292-410,495-531;
-//  vecbuf.py:33-37).  Integer results are bit-exact with the reference (tests/test_gpu_vrb.py).
+//  vecbuf.py:33-37).  Integer results are bit-exact with the reference
+// (tests/test_gpu_kernels.py::test_vrb_trace_bit_exact; past one scan chunk and by copy branch: tests/test_gpu_data_shapes.py).
 //
 // State (one device allocation, caller-owned):
 //   i64 insertion_idx[B] size[B] ep_len[B] ep_start_idx[B] last_index[B] lengths[B]
