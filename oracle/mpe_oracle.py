@@ -19,8 +19,10 @@ AGENT_SIZE, ACCEL = 0.15, 5.0
 class SimpleSpreadWorld:
     """One world (the object a PettingZoo ParallelEnv wraps)."""
 
-    def __init__(self, n_agent: int = 3, max_cycles: int = 25, local_ratio: float = 0.5, seed: int = 0) -> None:
+    def __init__(self, n_agent: int = 3, max_cycles: int = 25, local_ratio: float = 0.5, seed: int = 0,
+                 max_speed: float | None = None) -> None:
         self.N, self.max_cycles, self.local_ratio = n_agent, max_cycles, local_ratio
+        self.max_speed = max_speed  # MPE core: agents of simple_spread have none; csrc/mpe.hip takes one on its config struct
         self.rng = np.random.default_rng(seed)
         self.agents = [f"agent_{i}" for i in range(n_agent)]
         self.reset()
@@ -64,6 +66,11 @@ class SimpleSpreadWorld:
                 f[i] += force
                 f[j] -= force
         self.avel = self.avel * (1 - DAMPING) + f * DT
+        if self.max_speed is not None and self.max_speed > 0:
+            for i in range(N):
+                sp = np.sqrt(self.avel[i, 0] ** 2 + self.avel[i, 1] ** 2)
+                if sp > self.max_speed:
+                    self.avel[i] = self.avel[i] / sp * self.max_speed
         self.apos = self.apos + self.avel * DT
         glob = 0.0
         for l in range(N):

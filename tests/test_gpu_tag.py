@@ -431,7 +431,7 @@ def test_tag_single_steps_match_oracle_tightly(n_env, n_adv, n_good, n_obst):
     env.agent_pos.mul_(0.3)
     worlds = [mpe_tag_oracle.SimpleTagWorld(n_adv, n_good, n_obst, max_cycles=50) for _ in range(n_env)]
     rng = np.random.default_rng(2)
-    caught = 0
+    caught = decisions = left_out = 0
     for step in range(10):
         apos, avel = env.agent_pos.cpu().numpy().astype(np.float64), env.agent_vel.cpu().numpy().astype(np.float64)
         lpos = env.landmark_pos[:, :n_obst].cpu().numpy().astype(np.float64)
@@ -442,8 +442,13 @@ def test_tag_single_steps_match_oracle_tightly(n_env, n_adv, n_good, n_obst):
             w.set_state(apos[e], avel[e], lpos[e])
             o, r = w.step(act[e])[:2]
             np.testing.assert_allclose(obs_next[e], o, rtol=2e-5, atol=2e-5)
-            near_threshold = np.abs(np.asarray(r) - rew[e]) > 5.0  # a contact decided the other way within f32 rounding
-            if not near_threshold.any():
-                np.testing.assert_allclose(rew[e], r, rtol=2e-5, atol=2e-4)
+            # a catch is decided on the new positions: only a pair the ORACLE puts within 1e-5 of the catch radius may go either
+            # way in f32 (sqrt(dx^2 + dy^2) errs by under 1e-7 there); it takes its good agent's reward and the adversaries' along
+            d = np.linalg.norm(w.apos[:n_adv, None] - w.apos[None, n_adv:], axis=-1)
+            close = np.abs(d - 0.125) <= 1e-5
+            keep = ~np.concatenate([np.full(n_adv, close.any()), close.any(0)])
+            decisions, left_out = decisions + close.size, left_out + int(close.sum())
+            np.testing.assert_allclose(rew[e][keep], np.asarray(r)[keep], rtol=2e-5, atol=2e-4)
             caught += int(rew[e, 0] >= 10.0)
     assert caught > 0  # adversaries did catch the prey in some worlds: the reward path was exercised
+    assert left_out <= 0.01 * decisions, (left_out, decisions)
