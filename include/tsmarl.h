@@ -1465,6 +1465,56 @@ int tsm_bdqn_head(const float *q, const float *q_next_online, const float *q_nex
 int tsm_bdqn_egreedy(const float *q, int64_t R, int32_t K, int32_t A, const float *eps_dev, uint64_t seed, uint64_t offset,
                      const uint64_t *offset_dev, int32_t *act_out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ICM  (tianshou/algorithm/modelbased/icm.py, IntrinsicCuriosityModule in tianshou/utils/net/discrete.py:378-429;
+ * csrc/icm.hip)
+ * Three MLPs (csrc/dense.hip) around one row-wise head.  The feature net runs ONCE over 2R interleaved rows, obs of row r at
+ * 2r and obs_next at 2r + 1: phi f32 [2R][feature_dim], so phi1[r] = phi[2r], phi2[r] = phi[2r + 1], and phi viewed as
+ * [R][2 feature_dim] is [phi1 | phi2], the inverse model's input, without a copy.  act i64 [R].  feature_dim in [1, 512], n_act
+ * in [1, 64] as for tsm_dqn_check, R (2 feature_dim + n_act) below 2^31: anything else, or a null pointer where none is
+ * allowed, is TSM_ERR_INVALID naming the limit before any launch.  Float64 arithmetic from the float32 inputs, rounded once
+ * where a value leaves; a row sum is every lane's columns l, l + 64, .. in index order, then the xor butterfly; no atomics:
+ * two runs give the same bits (the rule of the tsm_dsac_* heads).
+ * tsm_icm_check: the two bounds alone.  Needs no device.
+ * tsm_icm_rows replaces  torch.cat([phi1, F.one_hot(act, num_classes=action_dim)], dim=1) (discrete.py:424-426).  One launch.
+ *   out: x_fwd f32 [R][feature_dim + n_act] = [phi[2r] | one_hot(act[r])], the forward model's input.  An action outside
+ *   [0, n_act) gives an all-zero one-hot (the reference's F.one_hot raises).
+ * tsm_icm_head replaces  `0.5 * F.mse_loss(phi2_hat, phi2, reduction="none").sum(1)` (discrete.py:427), `batch.rew +=
+ *           mse_loss * reward_scale` (icm.py:83) and the loss of _icm_update with its backward down to the three networks'
+ *           outputs (icm.py:95-101).  One launch, one wave per row.
+ *   phi2_hat f32 [R][feature_dim]: the forward model on x_fwd; phi2: row r at phi2 + r * phi2_row_stride (phi + feature_dim
+ *   with stride 2 feature_dim); act_hat f32 [R][n_act]: the inverse model on phi as [R][2 feature_dim].
+ *   rew_io f32 (nullable: no store), ids i64 [R] (nullable): row r's reward lives at rew_io[ids ? ids[r] : r]; the ids are the
+ *   caller's to keep inside rew_io and distinct (one writer per element).
+ *   With d = phi2_hat - phi2, w = forward_loss_weight, s = lr_scale:
+ *   out: mse f32 [R] = 0.5 sum_k d[k]^2;  rew_io[..] += (float)mse * (float)reward_scale, a float32 product and a float32 add;
+ *        d_phi2_hat f32 [R][feature_dim] = s w d / R;  d_phi2_fwd f32 [R][feature_dim] = its negative (nothing is detached:
+ *        the forward loss reaches phi2 too);
+ *        d_act_hat f32 [R][n_act] = s (1 - w) (softmax(act_hat) - one_hot(act)) / R;
+ *        partial f64 [2 * ceil(R / TSM_ICM_ROWS_PER_BLOCK)] = per workgroup {sum mse, sum ce}, ce = logsumexp(act_hat) -
+ *        act_hat[act], both before their rounding to float32, in the layout of tsm_qmix_mix_td's partials:
+ *        tsm_qmix_finalize(partial, n_blocks, R, out) gives out[2] = {icm_forward_loss, icm_inverse_loss};
+ *        icm_loss = ((1 - w) icm_inverse_loss + w icm_forward_loss) s follows from the two in float64 on the host.
+ *   An action outside [0, n_act) reads nothing, as in tsm_dsac_critic_head: the row's mse and ce (and what its reward takes) are
+ *   NaN, its three gradient rows zero.  s = 0 gives exact zeros in all three gradients, w = 0 in the two forward ones, w = 1 in
+ *   d_act_hat.
+ * tsm_icm_join_grad: the feature net's d_out f32 [2R][feature_dim] in one launch.
+ *   g_fwd f32 [R][feature_dim]: the forward model's input gradient, columns [0, feature_dim) (tsm_mlp_input_grad);
+ *   g_inv f32 [R][2 feature_dim]: the inverse model's input gradient; d_phi2_fwd from tsm_icm_head.
+ *   d_out[2r] = g_fwd[r] + g_inv[r][0 .. feature_dim);  d_out[2r + 1] = g_inv[r][feature_dim ..) + d_phi2_fwd[r]: float32 sums
+ *   in that written order.  d_out may be g_inv itself (the two share their layout; every element has one reader and writer).
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_ICM_ROWS_PER_BLOCK 16
+int tsm_icm_check(int32_t feature_dim, int32_t n_act);
+int tsm_icm_rows(const float *phi, const int64_t *act, int64_t R, int32_t feature_dim, int32_t n_act, float *x_fwd,
+                 void *stream);
+int tsm_icm_head(const float *phi2_hat, const float *phi2, int64_t phi2_row_stride, const float *act_hat, const int64_t *act,
+                 float *rew_io, const int64_t *ids, int64_t R, int32_t feature_dim, int32_t n_act, double reward_scale,
+                 double forward_loss_weight, double lr_scale, float *mse, float *d_phi2_hat, float *d_phi2_fwd,
+                 float *d_act_hat, double *partial, void *stream);
+int tsm_icm_join_grad(const float *g_fwd, const float *g_inv, const float *d_phi2_fwd, int64_t R, int32_t feature_dim,
+                      float *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

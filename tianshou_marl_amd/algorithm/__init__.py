@@ -13,10 +13,11 @@ from .bdqn import BDQN, BDQNPolicy
 from .pg import A2C, Reinforce
 from .ppo import PPO, policy_within_training_step
 from .ppo_generic import GenericPPO
+from .icm import ICMOffPolicyWrapper, ICMOnPolicyWrapper, ICMTrainingStats
 
 __all__ = ["PPO", "A2C", "Reinforce", "GenericPPO", "DQN", "DiscreteQLearningPolicy", "C51", "C51Policy", "QRDQN",
            "QRDQNPolicy", "IQN", "IQNPolicy", "FQF", "FQFPolicy", "FQFTrainingStats", "RainbowDQN", "RainbowPolicy",
            "DiscreteSAC", "DiscreteSACPolicy", "DiscreteSACTrainingStats", "Alpha", "FixedAlpha", "AutoAlpha",
            "DDPG", "TD3", "SAC", "ContinuousDeterministicPolicy", "SACPolicy", "DDPGTrainingStats", "TD3TrainingStats",
            "SACTrainingStats", "GaussianNoise", "REDQ", "REDQPolicy", "REDQTrainingStats", "BDQN", "BDQNPolicy",
-           "policy_within_training_step"]
+           "policy_within_training_step", "ICMOnPolicyWrapper", "ICMOffPolicyWrapper", "ICMTrainingStats"]

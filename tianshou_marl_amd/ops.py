@@ -1733,6 +1733,94 @@ def dsac_alpha_step(entropy_partial, B: int, log_alpha, exp_avg, exp_avg_sq, ste
 
 
 # --------------------------------------------------------------------------------------------
+# ICM (modelbased/icm.py; IntrinsicCuriosityModule, utils/net/discrete.py:378-429; csrc/icm.hip)
+# --------------------------------------------------------------------------------------------
+def icm_check(feature_dim: int, n_act: int) -> None:
+    """The bounds of the ICM kernels (include/tsmarl.h): ValueError naming the limit."""
+    call("tsm_icm_check", int(feature_dim), int(n_act))
+
+
+def _icm_phi(name: str, phi, act):
+    """phi f32 [2R, F] (obs of row r at 2r, obs_next at 2r + 1), act i64 [R] -> (R, F, phi, act), contiguous."""
+    phi = _chk(phi, torch.float32, "phi")
+    if phi.dim() != 2 or phi.shape[0] < 2 or phi.shape[0] % 2:
+        raise ValueError(f"{name}: phi must be [2 R, feature_dim], the rows of obs and obs_next interleaved")
+    R, F = phi.shape[0] // 2, phi.shape[1]
+    if act.numel() != R:
+        raise ValueError(f"{name}: act must have {R} entries")
+    return R, F, phi, _chk(act, torch.int64, "act").reshape(-1)
+
+
+def icm_rows(phi, act, n_act: int, out=None):
+    """The forward model's input (discrete.py:424-426) in one launch: phi [2R, F], act i64 [R]
+    -> x_fwd f32 [R, F + n_act] = [phi[2r] | one_hot(act[r])]; an action outside [0, n_act) gives an all-zero one-hot."""
+    _dev_only("icm_rows", phi, act, out)
+    R, F, phi, act = _icm_phi("icm_rows", phi, act)
+    icm_check(F, n_act)
+    if out is None:
+        out = torch.empty(R, F + int(n_act), dtype=torch.float32, device=phi.device)
+    elif tuple(out.shape) != (R, F + int(n_act)):
+        raise ValueError(f"icm_rows: out must be [{R}, {F + int(n_act)}]")
+    call("tsm_icm_rows", ptr(phi), ptr(act), R, F, int(n_act), ptr(_chk(out, torch.float32, "out")), stream_ptr())
+    return out
+
+
+def icm_head(phi2_hat, phi, act_hat, act, reward_scale: float, forward_loss_weight: float, lr_scale: float, rew_io=None, ids=None):
+    """The ICM's row-wise head in one launch (include/tsmarl.h: tsm_icm_head).  phi2_hat [R, F]: the forward model's output; phi
+    [2R, F]: the feature net's (phi2 = its odd rows, read in place); act_hat [R, A]: the inverse model's output; act i64 [R].
+    rew_io f32 (any shape, contiguous) with ids i64 [R] or None: `rew_io.view(-1)[ids[r] or r] += mse[r] * reward_scale` in
+    float32, in place; the ids must be distinct and inside rew_io.
+    -> dict(mse [R], d_phi2_hat, d_phi2_fwd [R, F], d_act_hat [R, A], partial f64): `qmix_finalize(partial, R, out)` gives
+    {icm_forward_loss, icm_inverse_loss}."""
+    _dev_only("icm_head", phi2_hat, phi, act_hat, act, rew_io, ids)
+    R, F, phi, act = _icm_phi("icm_head", phi, act)
+    act_hat = _chk(act_hat, torch.float32, "act_hat")
+    if act_hat.dim() != 2 or act_hat.shape[0] != R:
+        raise ValueError(f"icm_head: act_hat must be [{R}, n_act]")
+    A = act_hat.shape[1]
+    icm_check(F, A)
+    phi2_hat = _chk(phi2_hat, torch.float32, "phi2_hat")
+    if tuple(phi2_hat.shape) != (R, F):
+        raise ValueError(f"icm_head: phi2_hat must be [{R}, {F}]")
+    if ids is not None:
+        if rew_io is None or ids.numel() != R:
+            raise ValueError(f"icm_head: ids needs rew_io and must have {R} entries")
+        ids = _chk(ids, torch.int64, "ids").reshape(-1)
+    if rew_io is not None:
+        rew_io = _chk(rew_io, torch.float32, "rew_io")
+        if ids is None and rew_io.numel() < R:
+            raise ValueError(f"icm_head: rew_io must have at least {R} entries")
+    dev = phi.device
+    out = dict(mse=torch.empty(R, dtype=torch.float32, device=dev), d_phi2_hat=torch.empty(R, F, dtype=torch.float32, device=dev),
+               d_phi2_fwd=torch.empty(R, F, dtype=torch.float32, device=dev), d_act_hat=torch.empty(R, A, dtype=torch.float32, device=dev),
+               partial=_head_partial(R, _abi.ICM_ROWS_PER_BLOCK, dev))
+    call("tsm_icm_head", ptr(phi2_hat), phi.data_ptr() + 4 * F, 2 * F, ptr(act_hat), ptr(act), ptr(rew_io), ptr(ids), R, F, A,
+         float(reward_scale), float(forward_loss_weight), float(lr_scale), ptr(out["mse"]), ptr(out["d_phi2_hat"]),
+         ptr(out["d_phi2_fwd"]), ptr(out["d_act_hat"]), ptr(out["partial"]), stream_ptr())
+    return out
+
+
+def icm_join_grad(g_fwd, g_inv, d_phi2_fwd, out=None):
+    """The feature net's d_out [2R, F] in one launch: row 2r = g_fwd[r] + g_inv[r, :F], row 2r + 1 = g_inv[r, F:] + d_phi2_fwd[r]
+    (float32 sums in that order).  g_fwd [R, F]: the forward model's input gradient over its first F columns; g_inv [R, 2F]: the
+    inverse model's; out None: g_inv's own memory (the two share their layout)."""
+    _dev_only("icm_join_grad", g_fwd, g_inv, d_phi2_fwd, out)
+    g_fwd, g_inv, d_phi2_fwd = (_chk(x, torch.float32, n) for x, n in ((g_fwd, "g_fwd"), (g_inv, "g_inv"), (d_phi2_fwd, "d_phi2_fwd")))
+    if g_fwd.dim() != 2 or g_fwd.shape[0] < 1:
+        raise ValueError("icm_join_grad: g_fwd must be [R, feature_dim]")
+    R, F = g_fwd.shape
+    icm_check(F, 1)
+    if tuple(g_inv.shape) != (R, 2 * F) or tuple(d_phi2_fwd.shape) != (R, F):
+        raise ValueError(f"icm_join_grad: g_inv must be [{R}, {2 * F}] and d_phi2_fwd [{R}, {F}]")
+    if out is None:
+        out = g_inv.view(2 * R, F)
+    elif out.numel() != 2 * R * F:
+        raise ValueError(f"icm_join_grad: out must be [{2 * R}, {F}]")
+    call("tsm_icm_join_grad", ptr(g_fwd), ptr(g_inv), ptr(d_phi2_fwd), R, F, ptr(_chk(out, torch.float32, "out")), stream_ptr())
+    return out.view(2 * R, F)
+
+
+# --------------------------------------------------------------------------------------------
 # Continuous-action actor-critics: DDPG, TD3, SAC (ddpg.py, td3.py, sac.py, utils/net/continuous.py; csrc/cac.hip)
 # --------------------------------------------------------------------------------------------
 def cac_check(act_dim: int, n_step: int = 1) -> None:

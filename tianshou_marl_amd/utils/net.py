@@ -1212,6 +1212,113 @@ def lagged_twins(nets, flat: torch.Tensor, offsets) -> tuple[torch.Tensor, list]
     return target_flat, twins
 
 
+# ---- the intrinsic curiosity module (utils/net/discrete.py:378-429) -------------------------------------------------------------
+class IntrinsicCuriosityModule(nn.Module):
+    """discrete.py:378-429: a feature net, a forward model [phi1 | one_hot(act)] -> phi2_hat and an inverse model
+    [phi1 | phi2] -> act_hat, as three `FlatMLP`s on ONE flat vector [feature_net | forward_model | inverse_model] (the
+    reference's `parameters()` order).  `feature_net`: a `FlatMLP` whose last width is `feature_dim`; its parameters move into
+    the joint vector.  `hidden_sizes`: of the two models (ReLU, as the reference's `MLP`).
+
+    The feature net runs once over 2R interleaved rows (obs of row r at 2r, obs_next at 2r + 1), so its output viewed as
+    [R, 2 feature_dim] is the inverse model's input without a copy.  `forward` keeps what `head` and `backward` need: the pair
+    replaces autograd for this module (csrc/icm.hip, csrc/dense.hip)."""
+
+    def __init__(self, *, feature_net: FlatMLP, feature_dim: int, action_dim: int, hidden_sizes=()) -> None:
+        super().__init__()
+        if not isinstance(feature_net, FlatMLP) or type(feature_net).forward is not FlatMLP.forward:
+            raise TypeError(f"IntrinsicCuriosityModule needs a FlatMLP feature net: the update runs in HIP, there is no autograd "
+                            f"fallback (got {type(feature_net).__name__})")
+        F, A = int(feature_dim), int(action_dim)
+        if feature_net.dims[-1] != F:
+            raise ValueError(f"IntrinsicCuriosityModule: the feature net has {feature_net.dims[-1]} outputs, feature_dim is {F}")
+        ops.icm_check(F, A)
+        dev = feature_net.flat.device
+        self.feature_dim, self.action_dim = F, A
+        self.feature_net = feature_net
+        self.forward_model = FlatMLP([F + A, *hidden_sizes, F], "relu", device=dev)
+        self.inverse_model = FlatMLP([2 * F, *hidden_sizes, A], "relu", device=dev)
+        flat, self._offs = join_nets(self.nets, dev)
+        self.flat = nn.Parameter(flat, requires_grad=False)
+        self.head = None   # what the last `forward(save=True)` left for `backward`: ops.icm_head's outputs
+
+    @property
+    def nets(self) -> list[FlatMLP]:
+        return [self.feature_net, self.forward_model, self.inverse_model]
+
+    def param_shapes(self) -> list[tuple[int, ...]]:
+        """The reference's parameters in `parameters()` order (what `FlatAdam.state_dict` lists)."""
+        return [s for m in self.nets for i in range(m.n_layers) for s in ((m.dims[i + 1], m.dims[i]), (m.dims[i + 1],))]
+
+    def forward(self, s1, act, s2, save: bool = True, **kwargs):
+        """s1, s2 [R, D], act [R] -> (mse_loss f32 [R], act_hat f32 [R, action_dim]) in HBM (discrete.py:411-429).  kwargs: the
+        loss weights and the reward shaping of `forward_rows`."""
+        dev = self.flat.device
+        s1 = torch.as_tensor(s1).to(dev, torch.float32)
+        s2 = torch.as_tensor(s2).to(dev, torch.float32)
+        D = self.feature_net.dims[0]
+        x = torch.empty(s1.numel() // D, 2, D, dtype=torch.float32, device=dev)
+        x[:, 0].copy_(s1.reshape(-1, D))
+        x[:, 1].copy_(s2.reshape(-1, D))
+        return self.forward_rows(x.view(-1, D), act, save=save, **kwargs)
+
+    def forward_rows(self, x: torch.Tensor, act, save: bool = True, rew_io=None, ids=None, reward_scale: float = 0.0,
+                     forward_loss_weight: float | None = None, lr_scale: float | None = None):
+        """`forward` on rows that are interleaved already: x [2R, D].  With `save`, the head's gradients for the given
+        `forward_loss_weight` / `lr_scale` are kept for `backward`, so both must be given (`backward` returns the gradient of
+        the loss they define); `rew_io` / `ids` / `reward_scale`: the in-place reward shaping of `ops.icm_head`."""
+        if save and (forward_loss_weight is None or lr_scale is None):
+            raise ValueError("IntrinsicCuriosityModule.forward(save=True) needs forward_loss_weight= and lr_scale=: the head forms "
+                             "the gradients that backward() returns; pass save=False for the outputs alone")
+        forward_loss_weight, lr_scale = float(forward_loss_weight or 0.0), float(lr_scale or 0.0)
+        dev = self.flat.device
+        act = torch.as_tensor(act).to(dev, torch.int64).reshape(-1)
+        F, A = self.feature_dim, self.action_dim
+        R = act.numel()
+        if x.shape[0] != 2 * R:
+            raise ValueError(f"IntrinsicCuriosityModule: {x.shape[0]} rows of obs / obs_next for {R} actions")
+        phi = self.feature_net.forward(x, save=save)                       # [2R, F]
+        phi2_hat = self.forward_model.forward(ops.icm_rows(phi, act, A), save=save)
+        act_hat = self.inverse_model.forward(phi.view(R, 2 * F), save=save)
+        head = ops.icm_head(phi2_hat, phi, act_hat, act, reward_scale, forward_loss_weight, lr_scale, rew_io=rew_io, ids=ids)
+        self.head = head if save else None
+        return head["mse"], act_hat
+
+    def backward(self, n_split: int = 0, slabs: torch.Tensor | None = None) -> torch.Tensor:
+        """Gradient slabs [n_split, n_param] of the whole vector for the last `forward(save=True)`: the two models' backwards,
+        their input gradients, `ops.icm_join_grad`, one feature-net backward on the 2R rows."""
+        if self.head is None:
+            raise RuntimeError("IntrinsicCuriosityModule.backward called before forward")
+        h, F = self.head, self.feature_dim
+        R, P = h["mse"].numel(), self.flat.numel()
+        if n_split <= 0:
+            n_split = ops.mlp_n_split(R)
+        if slabs is None:
+            slabs = torch.empty(n_split, P, dtype=torch.float32, device=self.flat.device)
+        o = self._offs
+        self.forward_model.backward(h["d_phi2_hat"], n_split, slabs=slabs[:, o[1]:], slab_stride=P)
+        self.inverse_model.backward(h["d_act_hat"], n_split, slabs=slabs[:, o[2]:], slab_stride=P)
+        g_fwd = self.forward_model.input_grad(h["d_phi2_hat"], 0, F)
+        g_inv = self.inverse_model.input_grad(h["d_act_hat"], 0, 2 * F)
+        d_phi = ops.icm_join_grad(g_fwd, g_inv, h["d_phi2_fwd"])
+        self.feature_net.backward(d_phi, n_split, slabs=slabs, slab_stride=P)
+        return slabs
+
+    # ---- checkpoints under the reference's key names: three `MLP`s (`ref_layer_keys`: "seq" under `<name>.model.`) -------------
+    def _ref_nets(self):
+        return [(f"{name}.model.", m, ref_layer_keys(m.n_layers, "seq"))
+                for name, m in zip(("feature_net", "forward_model", "inverse_model"), self.nets)]
+
+    def to_reference_state_dict(self) -> OrderedDict:
+        sd = OrderedDict()
+        for prefix, m, keys in self._ref_nets():
+            m.export_layers(keys, prefix, sd)
+        return sd
+
+    def load_reference_state_dict(self, sd) -> None:
+        for prefix, m, keys in self._ref_nets():
+            m.import_layers(sd, keys, prefix)
+
+
 class RunningMeanStd:
     """tianshou.utils.statistics.RunningMeanStd (statistics.py:68-114), scalar statistics, host f64.
     The batch moments come from a device reduction; only three scalars live on the host."""
