@@ -1515,6 +1515,49 @@ int tsm_icm_head(const float *phi2_hat, const float *phi2, int64_t phi2_row_stri
 int tsm_icm_join_grad(const float *g_fwd, const float *g_inv, const float *d_phi2_fwd, int64_t R, int32_t feature_dim,
                       float *d_out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * GAIL  (tianshou/algorithm/imitation/gail.py; csrc/gail.hip)
+ * PPO whose reward is -logsigmoid(-D([obs | act])) of a discriminator D (an MLP of csrc/dense.hip ending in one logit), trained
+ * by a few steps per update against an expert buffer.  A "pair" is one (buffer row, agent) sample; its id p is the flat index
+ * into obs_store viewed as [S B N][obs_dim], act_store viewed as i32 [S B N] and rew_store viewed as [S B N]: the kernels read
+ * the stores in place.  The action enters one-hot (the reference concatenates batch.act as it is, which serves Box actions
+ * only).  n_act in [1, 64] as for tsm_dqn_check, obs_dim >= 1, R (obs_dim + n_act) below 2^31 (R >= 1): anything else, or a null
+ * pointer where none is allowed, is TSM_ERR_INVALID naming the limit before any launch.  Float64 arithmetic from the float32
+ * inputs, rounded once where a value leaves; a workgroup's sum is every wave's xor butterfly over its 64 rows, then the waves
+ * in order (tsm_icm_head's rule); no atomics: two runs give the same bits.
+ * softplus(x) = max(x, 0) + log1p(exp(-|x|));  sigmoid(x) = 1 / (1 + exp(-x)) for x >= 0, exp(x) / (1 + exp(x)) below.
+ * tsm_gail_check: the bounds alone.  Needs no device.
+ * tsm_gail_draw replaces  expert_buffer.sample(bsz) (gail.py:227; uniform with replacement).  Element i takes Philox word 0 at
+ *   counter `counter + *counter_dev + i` (counter_dev nullable: 0) under the key seed ^ kGailKey (0x4741494C45585054, which no
+ *   other site uses); j = (w0 * (n_valid n_agent)) >> 32, the tsm_qmix_egreedy integer rule;
+ *   ids_out i64 [R]: [i] = (valid ? valid[j / n_agent] : j / n_agent) * n_agent + j % n_agent.  valid i64 [n_valid] (nullable: the
+ *   rows 0 .. n_valid - 1): the expert buffer's store rows that hold data.  n_valid n_agent in [1, 2^32).
+ * tsm_gail_rows replaces  torch.cat([obs, act], dim=1) (gail.py:208-212) on one-hot actions.  One launch.
+ *   out: x_out f32 [R][obs_dim + n_act] = [obs[p] | one_hot(act[p])], p = ids ? ids[r] : r (ids i64 [R] nullable).  An action
+ *   outside [0, n_act) gives an all-zero one-hot, as in tsm_icm_rows.  The learner calls it for the policy rows and for the
+ *   expert rows, each call writing its half of ONE matrix, so the discriminator runs once per step.
+ * tsm_gail_reward replaces  batch.rew = -F.logsigmoid(-disc(batch)) (gail.py:204-205).
+ *   rew_io[ids ? ids[r] : r] = (float)softplus(logits[r]): an overwrite.  The ids are the caller's to keep inside rew_io and
+ *   distinct.
+ * tsm_gail_head replaces  gail.py:226-235 and the backward of loss_disc down to the logits.  One launch.
+ *   logits f32 [Rp + Re]: the policy rows, then the expert rows; Rp, Re >= 1 may differ (merge_last makes the last policy chunk
+ *   longer).  d_logits f32 [Rp + Re] = sigmoid(l) / Rp for a policy row, (sigmoid(l) - 1) / Re for an expert row, formed as
+ *   -sigmoid(-l) / Re: no cancellation at large l.
+ *   partial f64 [4 * ceil((Rp + Re) / TSM_GAIL_ROWS_PER_BLOCK)] = per workgroup {sum softplus(l_pi), sum softplus(-l_exp),
+ *   count(l_pi < 0), count(l_exp > 0)}.
+ * tsm_gail_finalize: out f32 [3] (device or mapped host memory) = {loss_pi / Rp + loss_exp / Re, acc_pi, acc_exp} of one step,
+ *   the block sums added in index order.
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_GAIL_ROWS_PER_BLOCK 256
+int tsm_gail_check(int32_t obs_dim, int32_t n_act);
+int tsm_gail_draw(const int64_t *valid, int64_t n_valid, int32_t n_agent, int64_t R, uint64_t seed, uint64_t counter,
+                  const uint64_t *counter_dev, int64_t *ids_out, void *stream);
+int tsm_gail_rows(const float *obs, const int32_t *act, const int64_t *ids, int64_t R, int32_t obs_dim, int32_t n_act,
+                  float *x_out, void *stream);
+int tsm_gail_reward(const float *logits, const int64_t *ids, int64_t R, float *rew_io, void *stream);
+int tsm_gail_head(const float *logits, int64_t Rp, int64_t Re, float *d_logits, double *partial, void *stream);
+int tsm_gail_finalize(const double *partial, int64_t n_blocks, int64_t Rp, int64_t Re, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

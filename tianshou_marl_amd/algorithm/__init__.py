@@ -14,10 +14,12 @@ from .pg import A2C, Reinforce
 from .ppo import PPO, policy_within_training_step
 from .ppo_generic import GenericPPO
 from .icm import ICMOffPolicyWrapper, ICMOnPolicyWrapper, ICMTrainingStats
+from .gail import GAIL, GailTrainingStats
 
 __all__ = ["PPO", "A2C", "Reinforce", "GenericPPO", "DQN", "DiscreteQLearningPolicy", "C51", "C51Policy", "QRDQN",
            "QRDQNPolicy", "IQN", "IQNPolicy", "FQF", "FQFPolicy", "FQFTrainingStats", "RainbowDQN", "RainbowPolicy",
            "DiscreteSAC", "DiscreteSACPolicy", "DiscreteSACTrainingStats", "Alpha", "FixedAlpha", "AutoAlpha",
            "DDPG", "TD3", "SAC", "ContinuousDeterministicPolicy", "SACPolicy", "DDPGTrainingStats", "TD3TrainingStats",
            "SACTrainingStats", "GaussianNoise", "REDQ", "REDQPolicy", "REDQTrainingStats", "BDQN", "BDQNPolicy",
-           "policy_within_training_step", "ICMOnPolicyWrapper", "ICMOffPolicyWrapper", "ICMTrainingStats"]
+           "policy_within_training_step", "ICMOnPolicyWrapper", "ICMOffPolicyWrapper", "ICMTrainingStats",
+           "GAIL", "GailTrainingStats"]

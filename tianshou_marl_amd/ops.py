@@ -1821,6 +1821,118 @@ def icm_join_grad(g_fwd, g_inv, d_phi2_fwd, out=None):
 
 
 # --------------------------------------------------------------------------------------------
+# GAIL (imitation/gail.py; csrc/gail.hip)
+# --------------------------------------------------------------------------------------------
+def gail_check(obs_dim: int, n_act: int) -> None:
+    """The bounds of the GAIL kernels (include/tsmarl.h): ValueError naming the limit."""
+    call("tsm_gail_check", int(obs_dim), int(n_act))
+
+
+def _gail_ids(name: str, ids, R: int | None = None):
+    if ids is None:
+        return None
+    if R is not None and ids.numel() != R:
+        raise ValueError(f"{name}: ids must have {R} entries")
+    return _chk(ids, torch.int64, "ids").reshape(-1)
+
+
+def gail_draw(valid, n_valid: int, n_agent: int, R: int, seed: int, counter: int = 0, counter_dev=None, out=None, device="cuda"):
+    """`expert_buffer.sample(R)` (gail.py:227) as pair ids, uniform with replacement, in one launch: draw i is Philox word 0 at
+    counter + *counter_dev + i under the key seed ^ kGailKey, j = (w0 n_valid n_agent) >> 32,
+    -> i64 [R]: (valid[j // n_agent] or j // n_agent) * n_agent + j % n_agent.  valid: i64 [n_valid] store rows, or None."""
+    _dev_only("gail_draw", valid, counter_dev, out)
+    if valid is not None:
+        valid = _chk(valid, torch.int64, "valid").reshape(-1)
+        if valid.numel() != int(n_valid):
+            raise ValueError(f"gail_draw: valid must have {int(n_valid)} entries")
+        device = valid.device
+    if out is None:
+        out = torch.empty(max(int(R), 0), dtype=torch.int64, device=device)
+    elif out.numel() != int(R):
+        raise ValueError(f"gail_draw: out must have {int(R)} entries")
+    call("tsm_gail_draw", ptr(valid), int(n_valid), int(n_agent), int(R), seed & (2**64 - 1), counter & (2**64 - 1),
+         ptr(counter_dev), ptr(_chk(out, torch.int64, "out")), stream_ptr())
+    return out
+
+
+def gail_rows(obs, act, n_act: int, ids=None, R: int | None = None, out=None):
+    """The discriminator's input (gail.py:208-212, one-hot actions) in one launch.  obs f32 [.., D] and act i32 [..]: the
+    buffer's stores, read in place as [P, D] and [P]; ids i64 [R] or None (the first R pairs, R = P by default)
+    -> out f32 [R, D + n_act] = [obs[p] | one_hot(act[p])]; `out` may be R rows of a taller matrix.  The ids must lie in [0, P)."""
+    _dev_only("gail_rows", obs, act, ids, out)
+    obs, act = _chk(obs, torch.float32, "obs"), _chk(act, torch.int32, "act")
+    D = obs.shape[-1] if obs.dim() >= 1 else 0
+    P = act.numel()
+    if obs.dim() < 2 or obs.numel() != P * D:
+        raise ValueError("gail_rows: obs must be [.., obs_dim] and act hold one action per row of it")
+    gail_check(D, n_act)
+    ids = _gail_ids("gail_rows", ids, R)
+    R = int(R if R is not None else (ids.numel() if ids is not None else P))
+    if ids is None and R > P:
+        raise ValueError(f"gail_rows: R = {R} rows asked of {P} pairs")
+    if out is None:
+        out = torch.empty(R, D + int(n_act), dtype=torch.float32, device=obs.device)
+    elif tuple(out.shape) != (R, D + int(n_act)):
+        raise ValueError(f"gail_rows: out must be [{R}, {D + int(n_act)}]")
+    call("tsm_gail_rows", ptr(obs), ptr(act), ptr(ids), R, D, int(n_act), ptr(_chk(out, torch.float32, "out")), stream_ptr())
+    return out
+
+
+def gail_reward(logits, rew_io, ids=None):
+    """`batch.rew = -F.logsigmoid(-disc(batch))` (gail.py:204-205) in place: rew_io.view(-1)[ids[r] or r] = softplus(logits[r]),
+    an overwrite.  The ids must be distinct and inside rew_io."""
+    _dev_only("gail_reward", logits, rew_io, ids)
+    logits = _chk(logits, torch.float32, "logits").reshape(-1)
+    R = logits.numel()
+    ids = _gail_ids("gail_reward", ids, R)
+    rew_io = _chk(rew_io, torch.float32, "rew_io")
+    if ids is None and rew_io.numel() < R:
+        raise ValueError(f"gail_reward: rew_io must have at least {R} entries")
+    call("tsm_gail_reward", ptr(logits), ptr(ids), R, ptr(rew_io), stream_ptr())
+    return rew_io
+
+
+def gail_head(logits, Rp: int, d_logits=None, partial=None):
+    """The discriminator loss's row-wise head in one launch (include/tsmarl.h: tsm_gail_head).  logits f32 [Rp + Re]: the policy
+    rows, then the expert rows -> dict(d_logits f32 [Rp + Re], partial f64 [4 * blocks]) for `gail_finalize`."""
+    _dev_only("gail_head", logits, d_logits, partial)
+    logits = _chk(logits, torch.float32, "logits").reshape(-1)
+    n = logits.numel()
+    Rp, Re = int(Rp), n - int(Rp)
+    nb = max(-(-n // _abi.GAIL_ROWS_PER_BLOCK), 1)
+    if d_logits is None:
+        d_logits = torch.empty(n, dtype=torch.float32, device=logits.device)
+    elif d_logits.numel() != n:
+        raise ValueError(f"gail_head: d_logits must have {n} entries")
+    if partial is None:
+        partial = torch.empty(4 * nb, dtype=torch.float64, device=logits.device)
+    elif partial.numel() != 4 * nb:
+        raise ValueError(f"gail_head: partial must have {4 * nb} entries")
+    call("tsm_gail_head", ptr(logits), Rp, Re, ptr(_chk(d_logits, torch.float32, "d_logits")),
+         ptr(_chk(partial, torch.float64, "partial")), stream_ptr())
+    return dict(d_logits=d_logits, partial=partial)
+
+
+def gail_finalize(partial, Rp: int, Re: int, out=None):
+    """{loss_disc, acc_pi, acc_exp} of one discriminator step from `gail_head`'s partials (one launch).  out: device f32 [3] or
+    pinned host f32 [3] (None: a new device tensor)."""
+    _dev_only("gail_finalize", partial)
+    partial = _chk(partial, torch.float64, "partial").reshape(-1)
+    if out is None:
+        out = torch.empty(3, dtype=torch.float32, device=partial.device)
+    if out.numel() != 3 or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("gail_finalize: out must be 3 contiguous f32")
+    if out.is_cuda:
+        out_p = ptr(out)
+    elif out.is_pinned():
+        out_p = out.data_ptr()
+    else:
+        raise RuntimeError("gail_finalize: out must be a device tensor or pinned host memory (f32)")
+    call("tsm_gail_finalize", ptr(partial), partial.numel() // 4, int(Rp), int(Re), out_p, stream_ptr())
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # Continuous-action actor-critics: DDPG, TD3, SAC (ddpg.py, td3.py, sac.py, utils/net/continuous.py; csrc/cac.hip)
 # --------------------------------------------------------------------------------------------
 def cac_check(act_dim: int, n_step: int = 1) -> None:
