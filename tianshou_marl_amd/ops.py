@@ -2561,17 +2561,34 @@ def mlp_param_count(desc) -> int:
     return call("tsm_mlp_param_count", C.byref(desc))
 
 
+def _mlp_args(name: str, desc, params, x, acts=None, d_out=None):
+    """The host checks the dense entries share, before any launch: device f32 tensors, x [B, dims[0]], a parameter vector that
+    holds the net (the net reads its head: an actor keeps its sigma_param behind the layers) and, where given, `acts` of
+    tsm_mlp_act_elems floats and `d_out` [B, dims[-1]].  -> (params, x, B, n_act, the net's parameter count)."""
+    _dev_only(name, params, x, acts, d_out)
+    x = _chk(x, torch.float32, "x")
+    if x.dim() != 2 or x.shape[1] != desc.dims[0]:
+        raise ValueError(f"{name}: input width != dims[0]: x must be [B, {desc.dims[0]}], got {tuple(x.shape)}")
+    B = x.shape[0]
+    n_param = mlp_param_count(desc)
+    if n_param < 0:
+        _abi.check(_abi.TSM_ERR_INVALID)
+    if params.numel() < n_param:
+        raise ValueError(f"{name}: params must hold the net's {n_param} floats, got {params.numel()}")
+    n_act = call("tsm_mlp_act_elems", C.byref(desc), B)
+    if acts is not None and (acts.dtype != torch.float32 or not acts.is_contiguous() or acts.numel() != n_act):
+        raise ValueError(f"{name}: acts must be a contiguous f32 buffer of {n_act} floats, the activations of {B} rows")
+    if d_out is not None and (d_out.dtype != torch.float32 or d_out.numel() != B * desc.dims[desc.n_layers]):
+        raise ValueError(f"{name}: d_out must be f32 [{B}, {desc.dims[desc.n_layers]}]")
+    return _chk(params, torch.float32, "params"), x, B, n_act, n_param
+
+
 def mlp_forward(desc, params, x, acts=None):
     """-> (out [B, dims[-1]] view of the last activation block, acts buffer)."""
-    x = _chk(x, torch.float32, "x")
-    B = x.shape[0]
-    if x.shape[1] != desc.dims[0]:
-        raise ValueError(f"mlp_forward: input width {x.shape[1]} != dims[0] {desc.dims[0]}")
-    n = call("tsm_mlp_act_elems", C.byref(desc), B)
+    params, x, B, n, _ = _mlp_args("mlp_forward", desc, params, x, acts)
     if acts is None:
         acts = torch.empty(n, dtype=torch.float32, device=x.device)
-    call("tsm_mlp_forward", C.byref(desc), ptr(_chk(params, torch.float32, "params")), ptr(x), B, ptr(acts),
-         stream_ptr())
+    call("tsm_mlp_forward", C.byref(desc), ptr(params), ptr(x), B, ptr(acts), stream_ptr())
     O = desc.dims[desc.n_layers]
     return acts[n - B * O:].view(B, O), acts
 
@@ -2579,15 +2596,14 @@ def mlp_forward(desc, params, x, acts=None):
 def mlp_forward_cond(desc, params, x, run_if, acts=None):
     """`mlp_forward` whose launches are no-ops when the device flag `run_if` (i32[1]) is zero -- a pass a captured graph
     holds but only some inputs need (value_next_select).  The returned tensors hold garbage when it did not run."""
-    x = _chk(x, torch.float32, "x")
-    B = x.shape[0]
-    if x.shape[1] != desc.dims[0]:
-        raise ValueError(f"mlp_forward_cond: input width {x.shape[1]} != dims[0] {desc.dims[0]}")
-    n = call("tsm_mlp_act_elems", C.byref(desc), B)
+    params, x, B, n, _ = _mlp_args("mlp_forward_cond", desc, params, x, acts)
+    _dev_only("mlp_forward_cond", run_if)
+    if run_if.numel() < 1:
+        raise ValueError("mlp_forward_cond: run_if must hold one i32 flag")
     if acts is None:
         acts = torch.empty(n, dtype=torch.float32, device=x.device)
-    call("tsm_mlp_forward_cond", C.byref(desc), ptr(_chk(params, torch.float32, "params")), ptr(x), B, ptr(acts),
-         ptr(_chk(run_if, torch.int32, "run_if")), stream_ptr())
+    call("tsm_mlp_forward_cond", C.byref(desc), ptr(params), ptr(x), B, ptr(acts), ptr(_chk(run_if, torch.int32, "run_if")),
+         stream_ptr())
     O = desc.dims[desc.n_layers]
     return acts[n - B * O:].view(B, O), acts
 
@@ -2682,16 +2698,40 @@ def mlp_n_split(B: int) -> int:
     return max(1, min(64, -(-B // 256)))
 
 
+def _mlp_slabs(name: str, slabs, n_split: int, n_param: int, slab_stride: int, dev):
+    """Gradient slabs the launches may write: slab s covers the floats [s * stride, s * stride + n_param) behind the first
+    element of `slabs` (stride = slab_stride, or n_param when it is 0).  None: a fresh [n_split, stride]."""
+    if not 1 <= n_split <= 65535:
+        raise ValueError(f"{name}: n_split {n_split} outside [1, 65535]")
+    if slab_stride < 0 or 0 < slab_stride < n_param:
+        raise ValueError(f"{name}: slab_stride {slab_stride} smaller than the parameter count {n_param}")
+    stride = slab_stride or n_param
+    if slabs is None:
+        return torch.empty(n_split, stride, dtype=torch.float32, device=dev)
+    _dev_only(name, slabs)
+    if slabs.dtype != torch.float32 or slabs.dim() < 1 or slabs.numel() == 0 or slabs.stride(-1) != 1:
+        raise ValueError(f"{name}: slabs must be a non-empty f32 tensor, contiguous along the parameters")
+    if slabs.dim() == 2 and n_split > slabs.shape[0]:
+        raise ValueError(f"{name}: n_split {n_split} exceeds the {slabs.shape[0]} rows of slabs")
+    reach = 1 + sum((n - 1) * st for n, st in zip(slabs.shape, slabs.stride()))
+    if (n_split - 1) * stride + n_param > reach:
+        raise ValueError(f"{name}: slabs reach {reach} floats; {n_split} slabs of {n_param} floats at pitch {stride} need "
+                         f"{(n_split - 1) * stride + n_param}")
+    return slabs
+
+
 def mlp_backward(desc, params, x, acts, d_out, n_split: int = 0, slabs=None, slab_stride: int = 0):
     """Gradient slabs [n_split, n_param] of sum(out * d_out) w.r.t. the flat parameter vector.
     `slabs` may point INTO the slabs of a larger joint parameter vector (slab_stride = its parameter count)."""
-    x, d_out = _chk(x, torch.float32, "x"), _chk(d_out, torch.float32, "d_out")
-    B = x.shape[0]
+    params, x, B, _, n_param = _mlp_args("mlp_backward", desc, params, x, acts, d_out)
+    if B < 1:
+        raise ValueError("mlp_backward: batch must be >= 1")
+    d_out = _chk(d_out, torch.float32, "d_out")
     if n_split <= 0:
         n_split = mlp_n_split(B)
-    n_param = params.numel()
-    if slabs is None:
-        slabs = torch.empty(n_split, n_param, dtype=torch.float32, device=x.device)
+    if slabs is None and slab_stride == 0:
+        slab_stride = params.numel()   # fresh slabs are as wide as the caller's vector, which may hold more than the net
+    slabs = _mlp_slabs("mlp_backward", slabs, int(n_split), n_param, int(slab_stride), x.device)
     d_acts = torch.empty_like(acts)
     call("tsm_mlp_backward", C.byref(desc), ptr(params), ptr(x), B, ptr(acts), ptr(d_out), ptr(d_acts), n_split,
          slabs.data_ptr(), slab_stride, stream_ptr())
@@ -2701,20 +2741,23 @@ def mlp_backward(desc, params, x, acts, d_out, n_split: int = 0, slabs=None, sla
 def mlp_input_grad(desc, params, x, acts, d_out, col0: int, n_col: int, out=None, d_acts=None):
     """Gradient of sum(out * d_out) w.r.t. the input columns [col0, col0 + n_col) -> [B, n_col]; no weight gradients are
     computed (include/tsmarl.h: tsm_mlp_input_grad).  `acts`: the activations of mlp_forward on x."""
-    x, d_out = _chk(x, torch.float32, "x"), _chk(d_out, torch.float32, "d_out")
-    B = x.shape[0]
     if not (0 <= col0 and n_col >= 1 and col0 + n_col <= desc.dims[0]):
         raise ValueError(f"mlp_input_grad: columns [{col0}, {col0 + n_col}) leave the input width {desc.dims[0]}")
-    if d_out.numel() != B * desc.dims[desc.n_layers]:
-        raise ValueError("mlp_input_grad: d_out must be [B, dims[-1]]")
+    params, x, B, n_act, _ = _mlp_args("mlp_input_grad", desc, params, x, acts, d_out)
+    if B < 1:
+        raise ValueError("mlp_input_grad: batch must be >= 1")
+    d_out = _chk(d_out, torch.float32, "d_out")
+    _dev_only("mlp_input_grad", out, d_acts)
     if out is None:
         out = torch.empty(B, n_col, dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, n_col):
-        raise ValueError(f"mlp_input_grad: out must be [{B}, {n_col}]")
+    elif tuple(out.shape) != (B, n_col) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"mlp_input_grad: out must be a contiguous f32 [{B}, {n_col}]")
     if d_acts is None:
         d_acts = torch.empty_like(acts)
-    call("tsm_mlp_input_grad", C.byref(desc), ptr(_chk(params, torch.float32, "params")), ptr(x), B, ptr(acts), ptr(d_out),
-         ptr(d_acts), col0, n_col, ptr(_chk(out, torch.float32, "out")), n_col, stream_ptr())
+    elif d_acts.dtype != torch.float32 or not d_acts.is_contiguous() or d_acts.numel() != n_act:
+        raise ValueError(f"mlp_input_grad: d_acts must be a contiguous f32 workspace of {n_act} floats, the size of acts")
+    call("tsm_mlp_input_grad", C.byref(desc), ptr(params), ptr(x), B, ptr(acts), ptr(d_out), ptr(d_acts), col0, n_col, ptr(out),
+         n_col, stream_ptr())
     return out
 
 
