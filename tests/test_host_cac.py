@@ -223,8 +223,10 @@ def test_probabilistic_actor_keeps_the_reference_default_and_a_sigma_param_slot(
     net.sigma_param.copy_(torch.tensor([0.5, -1.0, 0.25]))
     twin = lagged_copy(net)
     assert torch.equal(twin.flat.data, net.flat.data) and twin.flat.data_ptr() != net.flat.data_ptr()
-    assert twin.extra_param_shapes == [(3, 1)] and ContinuousActorProbabilistic(6, 3, (16,), conditioned_sigma=True,
-                                                                               device="cpu").extra_param_shapes == []
+    # what lies behind the layers on the flat vector, as `FlatAdam.state_dict` lists it: sigma_param, or nothing
+    layers = [(16, 6), (16,), (16, 16), (16,), (3, 16), (3,)]
+    assert twin.param_shapes() == layers + [(3, 1)]
+    assert ContinuousActorProbabilistic(6, 3, (16,), conditioned_sigma=True, device="cpu").param_shapes() == [(16, 6), (16,), (6, 16), (6,)]
     from tianshou_marl_amd.utils.net import FlatAdam
     shapes = FlatAdam(net)._shapes()
     assert shapes[-1] == (3, 1) and sum(int(np.prod(x)) for x in shapes) == net.flat.numel()

@@ -17,7 +17,7 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..utils.net import FlatMLP, lagged_copy
+from ..utils.net import FlatMLP, export_views, import_views, lagged_copy
 from .dqn import DeviceOffPolicyRows
 from .optim import AdamOptimizerFactory, flat_adam_of
 
@@ -293,24 +293,22 @@ class ActorCriticOffPolicyAlgorithm(DeviceOffPolicyRows, nn.Module):
         for k, o in self._optims().items():
             o.load_state_dict(sd[k])
 
-    def _net_to_reference(self, net, prefix: str, sd: OrderedDict) -> None:
-        net.to_reference_state_dict(prefix, sd)
-
-    def _net_from_reference(self, net, sd, prefix: str) -> None:
-        net.load_reference_state_dict(sd, prefix)
+    @staticmethod
+    def _ref_views(net) -> list:
+        """[(key, view)] of a net under the reference's names: the net's own statement, unless a learner knows better."""
+        return net.reference_named_views()
 
     def to_reference_state_dict(self) -> OrderedDict:
         """The module state_dict of the reference's learner: `policy.actor.*`, `critic.*`, `critic_old.module.*`
         (lagged_network.py wraps the copies in an EvalModeModuleWrapper), ..."""
         sd = OrderedDict()
         for prefix, net in self._nets():
-            self._net_to_reference(net, prefix, sd)
+            export_views(self._ref_views(net), prefix, sd)
         return sd
 
-    @torch.no_grad()
     def load_reference_state_dict(self, sd) -> None:
         for prefix, net in self._nets():
-            self._net_from_reference(net, sd, prefix)
+            import_views(self._ref_views(net), sd, prefix)
 
 
 class ActorDualCriticsOffPolicyAlgorithm(ActorCriticOffPolicyAlgorithm):

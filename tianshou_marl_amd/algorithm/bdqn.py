@@ -19,7 +19,6 @@ branch mean: a one-row learner batch here follows the same formulas as every oth
 """
 from __future__ import annotations
 
-from collections import OrderedDict
 from typing import Any
 
 import numpy as np
@@ -142,15 +141,3 @@ class BDQN(DQN):
                              to_tensor(batch.rew, self.device, torch.float32), to_tensor(batch.end, self.device, torch.uint8),
                              self.gamma, weight=weight, is_double=self.is_double)
         return (head["d_adv"], head["d_v"]), head["partial"], head["returns"], head["prio"]
-
-    # ---- checkpoints ---------------------------------------------------------------------------------------------
-    def to_reference_state_dict(self) -> OrderedDict:
-        """`policy.model.*`, then `model_old.module.*` with a lagged network, under `BranchingNet`'s keys."""
-        sd = OrderedDict()
-        for prefix, net in self._ref_nets():
-            net.to_reference_state_dict(prefix, sd)
-        return sd
-
-    def load_reference_state_dict(self, sd) -> None:
-        for prefix, net in self._ref_nets():
-            net.load_reference_state_dict(sd, prefix)

@@ -30,7 +30,7 @@ from .. import ops
 from ..data.batch import Batch
 from ..data.stats import TrainingStats
 from ..utils.learner import act_result, result_slot, sample_counter, slab_workspace
-from ..utils.net import FlatMLP, lagged_copy, ref_layer_keys
+from ..utils.net import FlatMLP, export_views, import_views, lagged_copy, ref_layer_keys
 from ..utils.tensor import to_tensor
 from .optim import flat_adam_of
 
@@ -405,15 +405,22 @@ class DQN(DeviceOffPolicyRows, nn.Module):
         """(prefix, net) of a reference checkpoint: `policy.model.`, then `model_old.module.` with a target network."""
         return [("policy.model.", self.policy.model)] + ([("model_old.module.", self.model_old)] if self.use_target_network else [])
 
+    @staticmethod
+    def _ref_views(net) -> list:
+        """[(key, view)] of a Q-network: a `FlatMLP` is a `Net(hidden_sizes=[...])` used whole (`ref_layer_keys`: "body");
+        any other net states its own names."""
+        if isinstance(net, FlatMLP):
+            return net.named_layers(ref_layer_keys(net.n_layers, "body"))
+        return net.reference_named_views()
+
     def to_reference_state_dict(self) -> OrderedDict:
-        """The module state_dict of the reference's DQN around a `Net`: `policy.model.*`, then `model_old.module.*` when
-        a target network is used (lagged_network.py wraps it in an EvalModeModuleWrapper); the Q-network is a
-        `Net(hidden_sizes=[...])` used whole (`ref_layer_keys`: "body")."""
+        """The module state_dict of the reference's learner around its Q-network: `policy.model.*`, then
+        `model_old.module.*` when a target network is used (lagged_network.py wraps it in an EvalModeModuleWrapper)."""
         sd = OrderedDict()
         for prefix, net in self._ref_nets():
-            net.export_layers(ref_layer_keys(net.n_layers, "body"), prefix, sd)
+            export_views(self._ref_views(net), prefix, sd)
         return sd
 
     def load_reference_state_dict(self, sd) -> None:
         for prefix, net in self._ref_nets():
-            net.import_layers(sd, ref_layer_keys(net.n_layers, "body"), prefix)
+            import_views(self._ref_views(net), sd, prefix)

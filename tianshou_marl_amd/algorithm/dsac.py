@@ -138,11 +138,9 @@ class DiscreteSAC(EntropyCoefficient, ActorDualCriticsOffPolicyAlgorithm):
                              f"{actor.dims[0]} -> {n_act} on {dev}")
 
     # every net is a `DiscreteActor` / `DiscreteCritic` around a `Net(hidden_sizes=[...])` (`ref_layer_keys`: "head")
-    def _net_to_reference(self, net, prefix: str, sd) -> None:
-        net.export_layers(ref_layer_keys(net.n_layers, "head"), prefix, sd)
-
-    def _net_from_reference(self, net, sd, prefix: str) -> None:
-        net.import_layers(sd, ref_layer_keys(net.n_layers, "head"), prefix)
+    @staticmethod
+    def _ref_views(net) -> list:
+        return net.named_layers(ref_layer_keys(net.n_layers, "head"))
 
     # ---- ActorCriticOffPolicyAlgorithm._preprocess_batch (ddpg.py:287-339) with discrete_sac.py:147-155 -----------------
     def _preprocess_batch(self, batch: Batch, buffer, indices, agent: int | None = None) -> Batch:

@@ -30,7 +30,6 @@ from ..utils.tensor import to_tensor
 from .actor_critic import _Schedulers
 from .distq import QRDQN, QRDQNPolicy
 from .dqn import DiscreteQLearningPolicy, SimpleLossTrainingStats, _obs_rows
-from .iqn import IQN
 from .optim import flat_adam_of
 
 
@@ -194,7 +193,3 @@ class FQF(QRDQN):
         """`policy.model.`, `policy.fraction_model.`, then `model_old.module.` with a target network."""
         nets = super()._ref_nets()
         return nets[:1] + [("policy.fraction_model.", self.policy.fraction_model)] + nets[1:]
-
-    # `tau_hat`, then every net of `_ref_nets` under the reference's names: IQN's two methods, which read nothing else
-    to_reference_state_dict = IQN.to_reference_state_dict
-    load_reference_state_dict = IQN.load_reference_state_dict

@@ -16,7 +16,6 @@ Q32 -- `tau_hat` for `num_quantiles` leads the state dict and the loss never rea
 """
 from __future__ import annotations
 
-from collections import OrderedDict
 from typing import Any
 
 import torch
@@ -148,16 +147,3 @@ class IQN(QRDQN):
     def load_state_dict(self, sd, *args, **kwargs):  # type: ignore[override]
         super().load_state_dict(sd, *args, **kwargs)
         self.policy._tau_ctr = int(sd.get("tau_ctr", 0))
-
-    def to_reference_state_dict(self) -> OrderedDict:
-        """`tau_hat`, then `policy.model.*` and `model_old.module.*` under ImplicitQuantileNetwork's names."""
-        sd = OrderedDict((k, v.detach().clone().cpu()) for k, v in self._constants().items())
-        for prefix, net in self._ref_nets():
-            for k, v in net.reference_named_views():
-                sd[prefix + k] = v.detach().clone().cpu()
-        return sd
-
-    @torch.no_grad()
-    def load_reference_state_dict(self, sd) -> None:
-        for prefix, net in self._ref_nets():
-            net.load_reference_state_dict(sd, prefix=prefix)

@@ -34,7 +34,15 @@ from ...utils.net import FlatAdam, FlatMLP
 from ...utils.tensor import to_tensor
 
 
-class DecentralizedActor(FlatMLP):
+class _CTDENet(FlatMLP):
+    """A `FlatMLP` under the CTDE constructors' arguments.  Its lagged twin is the bare `FlatMLP` of its shape: the learners read
+    their targets through `FlatMLP.forward`."""
+
+    def clone_over(self, storage: torch.Tensor) -> FlatMLP:
+        return FlatMLP(self.dims, self.act, device=storage.device, seed=0, storage=storage)
+
+
+class DecentralizedActor(_CTDENet):
     """ctde.py:346-379: local observation -> action logits; `forward(obs, state) -> (logits, state)`."""
 
     def __init__(self, obs_dim: int, action_dim: int, hidden_dim: int = 128, device: str | torch.device = "cuda",
@@ -45,7 +53,7 @@ class DecentralizedActor(FlatMLP):
         return super().forward(obs, save=save), state
 
 
-class CentralizedCritic(FlatMLP):
+class CentralizedCritic(_CTDENet):
     """ctde.py:382-414: global state -> one value per agent."""
 
     def __init__(self, global_obs_dim: int, n_agents: int, hidden_dim: int = 128, device: str | torch.device = "cuda",

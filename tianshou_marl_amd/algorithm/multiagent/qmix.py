@@ -26,7 +26,7 @@ from torch import nn
 from ... import ops
 from ...data.batch import Batch
 from ...utils.learner import act_result, result_slot, sample_counter, slab_workspace
-from ...utils.net import FlatMLP, join_nets, lagged_twins, ref_layer_keys
+from ...utils.net import FlatMLP, FlatNet, join_nets, lagged_twins, ref_layer_keys
 from ...utils.tensor import to_tensor
 from ..optim import flat_adam_of
 from .ctde import LazyScalars
@@ -34,8 +34,10 @@ from .ctde import LazyScalars
 _HYPER = ("hyper_w1", "hyper_w2", "hyper_b1", "hyper_b2")
 
 
-class QMIXMixer(nn.Module):
+class QMIXMixer(FlatNet):
     """ctde.py:417-499.  The four hypernetworks are `FlatMLP`s on consecutive views of `flat` (registration order)."""
+
+    split_optimizer_state = False
 
     def __init__(self, n_agents: int, state_dim: int, mixing_embed_dim: int = 32, hypernet_embed_dim: int = 64,
                  enforce_monotonic: bool = True, device: str | torch.device = "cuda", seed: int | None = None,
@@ -48,39 +50,21 @@ class QMIXMixer(nn.Module):
         S, E, Hh, N = self.state_dim, self.embed_dim, self.hypernet_embed_dim, self.n_agents
         self._dims = {"hyper_w1": [S, Hh, N * E], "hyper_w2": [S, Hh, E], "hyper_b1": [S, E], "hyper_b2": [S, E, 1]}
         counts = [ops.mlp_param_count(ops.mlp_desc(self._dims[k])) for k in _HYPER]
-        n = sum(counts)
-        if storage is None:
-            storage = torch.zeros(n, dtype=torch.float32, device=device)
-        elif storage.numel() != n:
-            raise ValueError(f"QMIXMixer: storage must hold {n} floats")
-        self.flat = nn.Parameter(storage, requires_grad=False)
-        o = 0
-        for k, c in zip(_HYPER, counts):
-            setattr(self, k, FlatMLP(self._dims[k], "relu", device=storage.device,
-                                     seed=None if seed is None else seed + len(self._slices()),
-                                     storage=storage[o:o + c]))
-            o += c
-
-    def _slices(self) -> list:
-        return [k for k in _HYPER if k in self._modules]
+        self._offs = np.concatenate([[0], np.cumsum(counts)]).tolist()
+        storage = self._claim(self._offs[-1], storage, device)
+        for i, k in enumerate(_HYPER):   # hypernetwork i draws its init from seed + i
+            setattr(self, k, FlatMLP(self._dims[k], "relu", device=storage.device, seed=None if seed is None else seed + i,
+                                     storage=storage[self._offs[i]:self._offs[i + 1]]))
 
     @property
     def nets(self) -> list[FlatMLP]:
         return [getattr(self, k) for k in _HYPER]
 
-    def clone_over(self, storage: torch.Tensor) -> "QMIXMixer":
-        """As `FlatMLP.clone_over`."""
-        return QMIXMixer(self.n_agents, self.state_dim, self.embed_dim, self.hypernet_embed_dim, self.enforce_monotonic,
-                         device=storage.device, seed=0, storage=storage)
-
     def rebind(self, storage: torch.Tensor) -> None:
         """Move the parameters into `storage` (a slice of a joint vector) and view them there, hypernetwork by hypernetwork."""
         self.flat = nn.Parameter(storage, requires_grad=False)
-        o = 0
-        for net in self.nets:
-            c = net.flat.numel()
-            net.rebind(storage[o:o + c])
-            o += c
+        for net, o, e in zip(self.nets, self._offs, self._offs[1:]):
+            net.rebind(storage[o:e])
 
     def hyper_forward(self, state: torch.Tensor, save: bool = False) -> tuple:
         """(w1raw [B, N*E], b1 [B, E], w2raw [B, E], b2 [B, 1]): the hypernetworks on the global state."""
@@ -107,18 +91,16 @@ class QMIXMixer(nn.Module):
     def _layer_keys(name: str) -> list[tuple[str, str]]:
         return [("weight", "bias")] if name == "hyper_b1" else ref_layer_keys(2, "seq")
 
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        flat = self._vector(flat)
+        return [kv for name, net, o, e in zip(_HYPER, self.nets, self._offs, self._offs[1:])
+                for kv in net.named_layers(self._layer_keys(name), f"{name}.", flat[o:e])]
+
     def state_dict(self, *args, destination: OrderedDict | None = None, prefix: str = "", **kwargs):  # type: ignore[override]
-        sd = OrderedDict() if destination is None else destination
-        for name, net in zip(_HYPER, self.nets):
-            net.export_layers(self._layer_keys(name), f"{prefix}{name}.", sd)
-        return sd
+        return self.to_reference_state_dict(prefix, destination)
 
     def load_state_dict(self, sd, *args, **kwargs):  # type: ignore[override]
-        self._load(sd, "")
-
-    def _load(self, sd, prefix: str) -> None:
-        for name, net in zip(_HYPER, self.nets):
-            net.import_layers(sd, self._layer_keys(name), f"{prefix}{name}.")
+        self.load_reference_state_dict(sd)
 
 
 class QMIXPolicy(nn.Module):
@@ -264,4 +246,4 @@ class QMIXPolicy(nn.Module):
 
     def load_state_dict(self, sd, *args, **kwargs):  # type: ignore[override]
         for name, m in (("mixer", self.mixer), ("target_mixer", self.target_mixer)):
-            m._load(sd, name + ".")
+            m.load_reference_state_dict(sd, name + ".")

@@ -16,7 +16,6 @@ net without a noisy layer is legal and equals C51.
 """
 from __future__ import annotations
 
-from collections import OrderedDict
 from typing import Any
 
 import torch
@@ -107,16 +106,3 @@ class RainbowDQN(C51):
         """`policy.model.`, then `model_old.`: Rainbow holds the lagged module itself, not its eval-mode wrapper
         (rainbow.py:72-74), so no `.module` stands in its keys."""
         return [("policy.model.", self.policy.model)] + ([("model_old.", self.model_old)] if self.use_target_network else [])
-
-    def to_reference_state_dict(self) -> OrderedDict:
-        """`policy.support`, then both nets under the names of `Net` with NoisyLinear layers, noise slots included."""
-        sd = OrderedDict((k, v.detach().clone().cpu()) for k, v in self._constants().items())
-        for prefix, net in self._ref_nets():
-            for k, v in net.reference_named_views():
-                sd[prefix + k] = v.detach().clone().cpu()
-        return sd
-
-    @torch.no_grad()
-    def load_reference_state_dict(self, sd) -> None:
-        for prefix, net in self._ref_nets():
-            net.load_reference_state_dict(sd, prefix=prefix)

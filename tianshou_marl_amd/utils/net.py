@@ -10,6 +10,8 @@ exchanged with the reference (`to_reference_state_dict`).
 """
 from __future__ import annotations
 
+import functools
+import inspect
 import math
 from collections import OrderedDict
 
@@ -134,33 +136,153 @@ class DiscreteActorCritic(nn.Module):
         self.sync_image()
 
 
-class FlatMLP(nn.Module):
+def _generator(seed: int | None) -> torch.Generator | None:
+    """A private generator at `seed` (None: the global one draws)."""
+    return torch.Generator().manual_seed(seed) if seed is not None else None
+
+
+def _uniform(shape, bound: float, gen: torch.Generator | None) -> torch.Tensor:
+    """torch nn.Linear's draw, uniform in +-bound.  `_GroupedLayers.reset` spells its draw otherwise and the two give different
+    bits for one seed: a call site stays on the one it has."""
+    return torch.empty(shape).uniform_(-bound, bound, generator=gen)
+
+
+class FlatNet(nn.Module):
+    """A network whose parameters are ONE flat f32 vector `flat` with views over it.  A subclass states its layout once, as
+    `reference_named_views(flat)`; the storage claim, twins, the optimizer's split and the checkpoints under the reference's
+    names follow from that here, as do the two checks every backward starts with."""
+
+    # False: `FlatAdam.state_dict` lists the vector as ONE parameter, not split by `reference_named_views`.  The optimizer
+    # checkpoints of these nets have always had that form, and stay readable
+    split_optimizer_state = True
+    _saved = None   # what the last `forward(save=True)` kept for `backward`
+
+    def __init_subclass__(cls, **kwargs) -> None:
+        """Every constructor records its arguments, device, seed and storage apart, on the instance -- the outermost call
+        alone, so a subclass's arguments and not those it hands up: what `clone_over` rebuilds the net from."""
+        super().__init_subclass__(**kwargs)
+        init = cls.__dict__.get("__init__")
+        if init is None:
+            return
+        sig = inspect.signature(init)
+
+        @functools.wraps(init)
+        def recording(self, *args, **kw) -> None:
+            if "_ctor_args" not in self.__dict__:
+                given = list(sig.bind(self, *args, **kw).arguments.items())[1:]
+                self.__dict__["_ctor_args"] = {k: v for k, v in given if k not in ("device", "seed", "storage")}
+            init(self, *args, **kw)
+
+        cls.__init__ = recording
+
+    # ---- storage and twins ------------------------------------------------------------------------------------------------
+    def _claim(self, n: int, storage: torch.Tensor | None, device) -> torch.Tensor:
+        """Set `flat` to `n` zeros on `device`, or to `storage`: a contiguous f32 vector of n elements, possibly a slice of a
+        larger joint vector (actor and critic under one optimizer).  -> the vector."""
+        if storage is None:
+            storage = torch.zeros(n, dtype=torch.float32, device=device)
+        elif storage.numel() != n or storage.dtype != torch.float32 or not storage.is_contiguous():
+            raise ValueError(f"{type(self).__name__}: storage must be a contiguous f32 vector of {n} elements")
+        self.flat = nn.Parameter(storage, requires_grad=False)
+        return storage
+
+    @torch.no_grad()
+    def rebind(self, storage: torch.Tensor) -> None:
+        """Move the parameters into `storage` (a slice of a joint vector) and view them there.  A net with sub-nets over
+        slices of its vector moves those itself (`QMIXMixer`)."""
+        storage.copy_(self.flat.data)
+        self.flat = nn.Parameter(storage, requires_grad=False)
+
+    def clone_over(self, storage: torch.Tensor):
+        """A net of the same class and shape viewing `storage`, which holds the init of a private generator until the caller
+        copies over it (`lagged_copy`)."""
+        return type(self)(**self._ctor_args, device=storage.device, seed=0, storage=storage)
+
+    # ---- ONE statement of the parameters ----------------------------------------------------------------------------------
+    def _vector(self, flat: torch.Tensor | None) -> torch.Tensor:
+        return self.flat.data if flat is None else flat
+
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        """[(key, view)] of `flat` (None: the net's own vector; else any vector of its layout: a gradient, an Adam moment)
+        under the reference module's parameter names and shapes, in its `state_dict()` order."""
+        raise NotImplementedError
+
+    def param_views(self, flat: torch.Tensor | None = None) -> list[torch.Tensor]:
+        """The parameters in the ORDER OF THE VECTOR: what `FlatAdam` splits its moments by."""
+        if not self.split_optimizer_state:
+            return [self._vector(flat)]
+        return [v for _, v in self.reference_named_views(flat)]
+
+    def param_shapes(self) -> list[tuple[int, ...]]:
+        """The shapes `FlatAdam.state_dict` lists for this net."""
+        return [tuple(v.shape) for v in self.param_views()]
+
+    def to_reference_state_dict(self, prefix: str = "", sd: OrderedDict | None = None) -> OrderedDict:
+        """Host copies of the parameters under prefix + the reference's keys, added to `sd` (None: a new OrderedDict)."""
+        return export_views(self.reference_named_views(), prefix, sd)
+
+    def load_reference_state_dict(self, sd, prefix: str = "") -> None:
+        import_views(self.reference_named_views(), sd, prefix)
+
+    # ---- what a backward starts with ----------------------------------------------------------------------------------------
+    def _saved_forward(self, what: str = "backward"):
+        if self._saved is None:
+            raise RuntimeError(f"{type(self).__name__}.{what} called before forward")
+        return self._saved
+
+    def _slabs(self, rows: int, n_split: int, slabs: torch.Tensor | None) -> tuple[int, torch.Tensor]:
+        """(n_split, slabs [n_split, n_param]) of a backward of the whole vector over `rows` rows: `n_split` <= 0 is
+        `ops.mlp_n_split`'s choice, `slabs` None a fresh array."""
+        P = self.flat.numel()
+        if n_split <= 0:
+            n_split = ops.mlp_n_split(rows)
+        if slabs is None:
+            slabs = torch.empty(n_split, P, dtype=torch.float32, device=self.flat.device)
+        elif tuple(slabs.shape) != (n_split, P) or not slabs.is_contiguous():
+            raise ValueError(f"{type(self).__name__}.backward: slabs must be a contiguous [{n_split}, {P}]")
+        return n_split, slabs
+
+
+def export_views(views, prefix: str = "", sd: OrderedDict | None = None) -> OrderedDict:
+    """Host copies of `views` = [(key, view)] under prefix + key, added to `sd` (None: a new OrderedDict).  A view need not
+    be contiguous (`BranchingNet`'s transposed branch weights); its copy is."""
+    sd = OrderedDict() if sd is None else sd
+    sd.update((prefix + k, v.detach().clone().contiguous().cpu()) for k, v in views)
+    return sd
+
+
+@torch.no_grad()
+def import_views(views, sd, prefix: str = "") -> None:
+    """Fill `views` = [(key, view)] from the entries of `sd` (numpy or tensors) under prefix + key."""
+    for k, v in views:
+        t = sd[prefix + k]
+        v.copy_(torch.as_tensor(t if isinstance(t, torch.Tensor) else np.asarray(t)).to(v.device, v.dtype).reshape(v.shape))
+
+
+class FlatMLP(FlatNet):
     """Fully-connected net dims[0] -> ... -> dims[-1] (hidden activation relu | tanh, linear output) whose
     parameters are ONE flat HBM vector in torch `parameters()` order; forward/backward run in csrc/dense.hip.
 
     `forward(x)` keeps the activations of the last call so that `backward(d_out)` can produce the gradient slabs
-    (the pair replaces autograd for this module).  Layer views (`weight(i)`, `bias(i)`) alias the flat vector."""
+    (the pair replaces autograd for this module).  Layer views (`weight(i)`, `bias(i)`) alias the flat vector.
+    `n_extra`: elements a subclass keeps behind the layers on the vector."""
+
+    ref_scheme = "fc"   # of `ref_layer_keys`: the key names of `to_reference_state_dict`; any other through `export_layers`
 
     def __init__(self, dims, act: str = "relu", device: str | torch.device = "cuda", seed: int | None = None,
-                 storage: torch.Tensor | None = None) -> None:
+                 storage: torch.Tensor | None = None, n_extra: int = 0) -> None:
         super().__init__()
         self.dims = [int(d) for d in dims]
         self.act = act
         self.desc = ops.mlp_desc(self.dims, act)
-        n = ops.mlp_param_count(self.desc)
-        if storage is None:
-            storage = torch.zeros(n, dtype=torch.float32, device=device)
-        elif storage.numel() != n or storage.dtype != torch.float32 or not storage.is_contiguous():
-            raise ValueError(f"FlatMLP: storage must be a contiguous f32 vector of {n} elements")
-        # `storage` may be a slice of a larger joint parameter vector (actor + critic under one optimizer)
-        self.flat = nn.Parameter(storage, requires_grad=False)
+        self.n_mlp_params = ops.mlp_param_count(self.desc)
+        self._claim(self.n_mlp_params + n_extra, storage, device)
         self._offsets = []
         o = 0
         for i in range(len(self.dims) - 1):
             k, n = self.dims[i], self.dims[i + 1]
             self._offsets.append((o, o + n * k))
             o += n * k + n
-        self._saved = None
         self.reset_parameters(seed)
 
     @property
@@ -178,22 +300,11 @@ class FlatMLP(nn.Module):
     @torch.no_grad()
     def reset_parameters(self, seed: int | None = None) -> None:
         """torch nn.Linear default init (kaiming-uniform weights, uniform bias)."""
-        gen = torch.Generator().manual_seed(seed) if seed is not None else None
-        for i in range(self.n_layers):
+        gen = _generator(seed)
+        for i, (W, b) in enumerate(self.layer_views(self.flat.data)):
             bound = 1.0 / math.sqrt(self.dims[i])
-            self.weight(i).copy_(torch.empty(self.weight(i).shape).uniform_(-bound, bound, generator=gen))
-            self.bias(i).copy_(torch.empty(self.bias(i).shape).uniform_(-bound, bound, generator=gen))
-
-    def clone_over(self, storage: torch.Tensor) -> "FlatMLP":
-        """A net of the same shape viewing `storage`, which holds the init of a private generator until the caller copies
-        over it (`lagged_copy`)."""
-        return FlatMLP(self.dims, self.act, device=storage.device, seed=0, storage=storage)
-
-    @torch.no_grad()
-    def rebind(self, storage: torch.Tensor) -> None:
-        """Move the parameters into `storage` (a slice of a joint vector) and view them there."""
-        storage.copy_(self.flat.data)
-        self.flat = nn.Parameter(storage, requires_grad=False)
+            W.copy_(_uniform(W.shape, bound, gen))
+            b.copy_(_uniform(b.shape, bound, gen))
 
     @torch.no_grad()
     def load_layers(self, layers) -> None:
@@ -224,64 +335,40 @@ class FlatMLP(nn.Module):
                  slab_stride: int = 0) -> torch.Tensor:
         """Gradient slabs [n_split, n_param] for the inputs of the last `forward(save=True)`; `slabs` / `slab_stride`
         direct them into the slabs of a joint parameter vector."""
-        if self._saved is None:
-            raise RuntimeError("FlatMLP.backward called before forward")
-        x2, acts = self._saved
+        x2, acts = self._saved_forward()
         return ops.mlp_backward(self.desc, self.flat.data, x2, acts, d_out.reshape(x2.shape[0], self.dims[-1]).contiguous(),
                                 n_split, slabs=slabs, slab_stride=slab_stride)
 
     def input_grad(self, d_out: torch.Tensor, col0: int, n_col: int, out: torch.Tensor | None = None) -> torch.Tensor:
         """Gradient [B, n_col] w.r.t. the input columns [col0, col0 + n_col) of the last `forward(save=True)`; no weight
         gradient is computed (the critic's side of a deterministic policy gradient)."""
-        if self._saved is None:
-            raise RuntimeError("FlatMLP.input_grad called before forward")
-        x2, acts = self._saved
+        x2, acts = self._saved_forward("input_grad")
         return ops.mlp_input_grad(self.desc, self.flat.data, x2, acts, d_out.reshape(x2.shape[0], self.dims[-1]), col0, n_col,
                                   out=out)
 
     # ---- checkpoints under the reference's key names (`ref_layer_keys`) -----------------------------------------------
-    def named_layers(self, keys, prefix: str = "") -> list[tuple[str, torch.Tensor]]:
-        """[(prefix + key, view)]: every layer's weight, then its bias, under `keys` = [(weight key, bias key)]."""
-        return [(prefix + k, v) for i, kk in enumerate(keys) for k, v in zip(kk, (self.weight(i), self.bias(i)))]
+    def named_layers(self, keys, prefix: str = "", flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        """[(prefix + key, view)]: every layer's weight, then its bias, under `keys` = [(weight key, bias key)]; views of
+        `flat` (None: the net's own vector)."""
+        return [(prefix + k, v) for kk, Wb in zip(keys, self.layer_views(self._vector(flat))) for k, v in zip(kk, Wb)]
 
     def export_layers(self, keys, prefix: str = "", sd: OrderedDict | None = None) -> OrderedDict:
         """The layers as host copies under prefix + `keys`, added to `sd` (None: a new OrderedDict)."""
-        sd = OrderedDict() if sd is None else sd
-        sd.update((k, v.detach().clone().cpu()) for k, v in self.named_layers(keys, prefix))
-        return sd
+        return export_views(self.named_layers(keys), prefix, sd)
 
     def import_layers(self, sd, keys, prefix: str = "") -> None:
         """`load_layers` from the entries of `sd` under prefix + `keys`."""
         self.load_layers([(sd[prefix + kw], sd[prefix + kb]) for kw, kb in keys])
 
-    def to_reference_state_dict(self) -> OrderedDict:
-        return self.export_layers(ref_layer_keys(self.n_layers, "fc"))
-
-    def load_reference_state_dict(self, sd) -> None:
-        self.import_layers(sd, ref_layer_keys(self.n_layers, "fc"))
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        return self.named_layers(ref_layer_keys(self.n_layers, self.ref_scheme), flat=flat)
 
 
 # ---- the continuous-action nets (utils/net/continuous.py) ---------------------------------------------------------------
 class _ContinuousNet(FlatMLP):
-    """A `FlatMLP` under the reference's `Net(hidden_sizes=[...])` + `last` key names (`ref_layer_keys`: "head")."""
+    """A `FlatMLP` under the reference's `Net(hidden_sizes=[...])` + `last` key names."""
 
-    def _twin_kwargs(self) -> dict:
-        return {}
-
-    def clone_over(self, storage: torch.Tensor):
-        twin = FlatMLP.__new__(type(self))
-        FlatMLP.__init__(twin, self.dims, self.act, device=storage.device, seed=0, storage=storage)
-        twin.__dict__.update(self._twin_kwargs())
-        return twin
-
-    def _ref_keys(self):
-        return ref_layer_keys(self.n_layers, "head")
-
-    def to_reference_state_dict(self, prefix: str = "", sd: OrderedDict | None = None) -> OrderedDict:
-        return self.export_layers(self._ref_keys(), prefix, sd)
-
-    def load_reference_state_dict(self, sd, prefix: str = "") -> None:
-        self.import_layers(sd, self._ref_keys(), prefix)
+    ref_scheme = "head"
 
 
 class ContinuousActorDeterministic(_ContinuousNet):
@@ -289,26 +376,22 @@ class ContinuousActorDeterministic(_ContinuousNet):
     (`ops.cac_det_action`), which `forward` does NOT apply: the learners need the raw output for the backward."""
 
     def __init__(self, obs_dim: int, act_dim: int, hidden_sizes=(64, 64), max_action: float = 1.0, act: str = "relu",
-                 device: str | torch.device = "cuda", seed: int | None = None) -> None:
+                 device: str | torch.device = "cuda", seed: int | None = None, storage: torch.Tensor | None = None) -> None:
         ops.cac_check(int(act_dim))
-        super().__init__([int(obs_dim), *[int(h) for h in hidden_sizes], int(act_dim)], act, device=device, seed=seed)
+        super().__init__([int(obs_dim), *[int(h) for h in hidden_sizes], int(act_dim)], act, device=device, seed=seed,
+                         storage=storage)
         self.max_action = float(max_action)
         self.act_dim = int(act_dim)
-
-    def _twin_kwargs(self) -> dict:
-        return dict(max_action=self.max_action, act_dim=self.act_dim)
 
 
 class ContinuousCritic(_ContinuousNet):
     """continuous.py:102-175: rows [obs | act] -> hidden ... -> 1."""
 
     def __init__(self, obs_dim: int, act_dim: int, hidden_sizes=(64, 64), act: str = "relu",
-                 device: str | torch.device = "cuda", seed: int | None = None) -> None:
-        super().__init__([int(obs_dim) + int(act_dim), *[int(h) for h in hidden_sizes], 1], act, device=device, seed=seed)
+                 device: str | torch.device = "cuda", seed: int | None = None, storage: torch.Tensor | None = None) -> None:
+        super().__init__([int(obs_dim) + int(act_dim), *[int(h) for h in hidden_sizes], 1], act, device=device, seed=seed,
+                         storage=storage)
         self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
-
-    def _twin_kwargs(self) -> dict:
-        return dict(obs_dim=self.obs_dim, act_dim=self.act_dim)
 
 
 class ContinuousActorProbabilistic(_ContinuousNet):
@@ -324,61 +407,74 @@ class ContinuousActorProbabilistic(_ContinuousNet):
         ops.cac_check(int(act_dim))
         Ad, cond = int(act_dim), bool(conditioned_sigma)
         dims = [int(obs_dim), *[int(h) for h in hidden_sizes], 2 * Ad if cond else Ad]
-        n = ops.mlp_param_count(ops.mlp_desc(dims, act))
-        if storage is None:
-            storage = torch.zeros(n + (0 if cond else Ad), dtype=torch.float32, device=device)
-        super().__init__(dims, act, device=device, seed=seed, storage=storage[:n])
-        if not cond:   # the layers view the head of the vector, sigma_param its tail
-            self.flat = nn.Parameter(storage, requires_grad=False)
-            storage[n:].zero_()
+        # the layers view the head of the vector, sigma_param its tail
+        super().__init__(dims, act, device=device, seed=seed, storage=storage, n_extra=0 if cond else Ad)
+        self.flat.data[self.n_mlp_params:].zero_()
         if unbounded and not np.isclose(max_action, 1.0):
             max_action = 1.0   # continuous.py:208-210: discarded when unbounded
         self.max_action, self.unbounded, self.act_dim, self.conditioned_sigma = float(max_action), bool(unbounded), Ad, cond
-        self.n_mlp_params = n
 
     @property
     def sigma_param(self) -> torch.Tensor | None:
         """f32 [act_dim]: a view of the flat parameter's tail (None with conditioned sigma)."""
         return None if self.conditioned_sigma else self.flat.data[self.n_mlp_params:]
 
-    @property
-    def extra_param_shapes(self) -> list[tuple[int, ...]]:
-        """The parameters behind the layers on the flat vector, as `FlatAdam.state_dict` lists them."""
-        return [] if self.conditioned_sigma else [(self.act_dim, 1)]
+    def param_views(self, flat: torch.Tensor | None = None) -> list[torch.Tensor]:
+        """The layers, whole, then `sigma_param` where the vector has it: the vector's order, which is not the checkpoint's."""
+        flat = self._vector(flat)
+        tail = [] if self.conditioned_sigma else [flat[self.n_mlp_params:].view(self.act_dim, 1)]
+        return [v for Wb in self.layer_views(flat) for v in Wb] + tail
 
-    def clone_over(self, storage: torch.Tensor):
-        return ContinuousActorProbabilistic(self.dims[0], self.act_dim, self.dims[1:-1], self.max_action, self.unbounded,
-                                            self.conditioned_sigma, self.act, device=storage.device, seed=0, storage=storage)
-
-    def _heads(self):
-        """[(reference key, view)] of what is not the trunk, in the reference's state_dict order (a module's own parameters
-        come before its submodules': `sigma_param` leads)."""
-        L, Ad = self.n_layers - 1, self.act_dim
-        W, b = self.weight(L), self.bias(L)
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        """The reference's state_dict order: a module's own parameters come before its submodules', so `sigma_param` leads;
+        then the trunk, then the last layer as `mu` (with conditioned sigma: its halves as `mu` and `sigma`)."""
+        Ad = self.act_dim
+        trunk = super().reference_named_views(flat)[:-2]
+        W, b = self.layer_views(self._vector(flat))[-1]
         if self.conditioned_sigma:
-            return [], [("mu.model.0.weight", W[:Ad]), ("mu.model.0.bias", b[:Ad]), ("sigma.model.0.weight", W[Ad:]),
-                        ("sigma.model.0.bias", b[Ad:])]
-        return [("sigma_param", self.sigma_param.view(Ad, 1))], [("mu.model.0.weight", W), ("mu.model.0.bias", b)]
+            return trunk + [("mu.model.0.weight", W[:Ad]), ("mu.model.0.bias", b[:Ad]), ("sigma.model.0.weight", W[Ad:]),
+                            ("sigma.model.0.bias", b[Ad:])]
+        return [("sigma_param", self.param_views(flat)[-1])] + trunk + [("mu.model.0.weight", W), ("mu.model.0.bias", b)]
 
-    def to_reference_state_dict(self, prefix: str = "", sd: OrderedDict | None = None) -> OrderedDict:
-        sd = OrderedDict() if sd is None else sd
-        first, last = self._heads()
-        sd.update((prefix + k, v.detach().clone().cpu()) for k, v in first)
-        self.export_layers(self._ref_keys()[:-1], prefix, sd)
-        sd.update((prefix + k, v.detach().clone().cpu()) for k, v in last)
-        return sd
+
+class _GroupedLayers:
+    """`EnsembleLinear`'s layout (common.py:522-554) of `E` members of the chain `dims` on `net`'s flat vector from `offset`
+    on: per layer weight [E, in, out], then bias [E, 1, out] -- what csrc/ensemble.hip runs as one grouped launch per layer."""
+
+    def __init__(self, net: FlatNet, dims, E: int, offset: int = 0) -> None:
+        self.net, self.dims, self.E = net, list(dims), int(E)
+        self.offsets, o = [], offset
+        for k, m in zip(self.dims, self.dims[1:]):
+            self.offsets.append((o, o + E * k * m))
+            o += E * (k * m + m)
+        self.n_param = o - offset
+
+    @property
+    def n_layers(self) -> int:
+        return len(self.dims) - 1
+
+    def weight(self, i: int, flat: torch.Tensor | None = None) -> torch.Tensor:
+        """Layer i's weight [E, in, out], a view of the net's vector (or of any vector of its layout, e.g. a gradient)."""
+        o, ob = self.offsets[i]
+        return self.net._vector(flat)[o:ob].view(self.E, self.dims[i], self.dims[i + 1])
+
+    def bias(self, i: int, flat: torch.Tensor | None = None) -> torch.Tensor:
+        """Layer i's bias [E, 1, out]."""
+        _, ob = self.offsets[i]
+        return self.net._vector(flat)[ob:ob + self.E * self.dims[i + 1]].view(self.E, 1, self.dims[i + 1])
 
     @torch.no_grad()
-    def load_reference_state_dict(self, sd, prefix: str = "") -> None:
-        for i, (kw, kb) in enumerate(self._ref_keys()[:-1]):
-            self.weight(i).copy_(torch.as_tensor(np.asarray(sd[prefix + kw])).to(self.flat.device, torch.float32))
-            self.bias(i).copy_(torch.as_tensor(np.asarray(sd[prefix + kb])).to(self.flat.device, torch.float32))
-        first, last = self._heads()
-        for k, v in first + last:
-            v.copy_(torch.as_tensor(np.asarray(sd[prefix + k])).to(self.flat.device, torch.float32).reshape(v.shape))
+    def reset(self, seed: int | None, bound) -> None:
+        """Uniform +-bound(in) for the weight and for the bias, layer by layer.  The draw is EnsembleLinear's `rand * 2 k - k`
+        (common.py:541-548), whose bits are not `_uniform`'s; `bound` is the caller's, to the last bit of its own spelling."""
+        gen = _generator(seed)
+        for i in range(self.n_layers):
+            k = bound(self.dims[i])
+            for v in (self.weight(i), self.bias(i)):
+                v.copy_(torch.rand(v.shape, generator=gen) * 2 * k - k)
 
 
-class EnsembleCritic(nn.Module):
+class EnsembleCritic(FlatNet):
     """An ensemble of `ensemble_size` critics [obs | act] -> hidden ... -> 1 of one shape, the reference's
     `ContinuousCritic(preprocess_net=Net(..., linear_layer=EnsembleLinear), linear_layer=EnsembleLinear, flatten_input=False)`
     (utils/net/common.py:522-554, continuous.py:102-175; examples/mujoco/mujoco_redq.py), as ONE flat HBM vector in the
@@ -393,19 +489,9 @@ class EnsembleCritic(nn.Module):
         self.dims = [self.obs_dim + self.act_dim, *[int(h) for h in hidden_sizes], 1]
         self.act = act
         self.desc = ops.mlp_desc(self.dims, act)
-        n = ops.ens_mlp_param_count(self.desc, self.ensemble_size)
-        if storage is None:
-            storage = torch.zeros(n, dtype=torch.float32, device=device)
-        elif storage.numel() != n or storage.dtype != torch.float32 or not storage.is_contiguous():
-            raise ValueError(f"EnsembleCritic: storage must be a contiguous f32 vector of {n} elements")
-        self.flat = nn.Parameter(storage, requires_grad=False)
-        self._offsets = []
-        o, E = 0, self.ensemble_size
-        for i in range(self.n_layers):
-            k, m = self.dims[i], self.dims[i + 1]
-            self._offsets.append((o, o + E * k * m))
-            o += E * (k * m + m)
-        self._saved = None
+        self._layers = _GroupedLayers(self, self.dims, self.ensemble_size)
+        assert self._layers.n_param == ops.ens_mlp_param_count(self.desc, self.ensemble_size)
+        self._claim(self._layers.n_param, storage, device)
         self.reset_parameters(seed)
 
     @property
@@ -414,32 +500,15 @@ class EnsembleCritic(nn.Module):
 
     def weight(self, i: int, flat: torch.Tensor | None = None) -> torch.Tensor:
         """Layer i's weight [E, in, out], a view of the flat vector (or of any vector of its layout, e.g. a gradient)."""
-        o, ob = self._offsets[i]
-        return (self.flat.data if flat is None else flat)[o:ob].view(self.ensemble_size, self.dims[i], self.dims[i + 1])
+        return self._layers.weight(i, flat)
 
     def bias(self, i: int, flat: torch.Tensor | None = None) -> torch.Tensor:
         """Layer i's bias_weights [E, 1, out]."""
-        _, ob = self._offsets[i]
-        E, m = self.ensemble_size, self.dims[i + 1]
-        return (self.flat.data if flat is None else flat)[ob:ob + E * m].view(E, 1, m)
+        return self._layers.bias(i, flat)
 
-    def param_shapes(self) -> list[tuple[int, ...]]:
-        """The reference's parameter shapes in `parameters()` order (what `FlatAdam.state_dict` splits its moments by)."""
-        return [tuple(t.shape) for i in range(self.n_layers) for t in (self.weight(i), self.bias(i))]
-
-    @torch.no_grad()
     def reset_parameters(self, seed: int | None = None) -> None:
         """EnsembleLinear's init (common.py:541-548): uniform +-sqrt(1 / in) for the weight and for the bias."""
-        gen = torch.Generator().manual_seed(seed) if seed is not None else None
-        for i in range(self.n_layers):
-            k = math.sqrt(1.0 / self.dims[i])
-            for v in (self.weight(i), self.bias(i)):
-                v.copy_(torch.rand(v.shape, generator=gen) * 2 * k - k)
-
-    def clone_over(self, storage: torch.Tensor) -> "EnsembleCritic":
-        """A net of the same shape viewing `storage` (`lagged_copy`)."""
-        return EnsembleCritic(self.obs_dim, self.act_dim, self.ensemble_size, self.dims[1:-1], self.act, device=storage.device,
-                              seed=0, storage=storage)
+        self._layers.reset(seed, lambda k: math.sqrt(1.0 / k))
 
     def forward(self, x: torch.Tensor, save: bool = True) -> torch.Tensor:
         """x [B, obs_dim + act_dim], shared by all members -> Q [E, B, 1]."""
@@ -454,40 +523,24 @@ class EnsembleCritic(nn.Module):
     def backward(self, d_out: torch.Tensor, n_split: int = 0, slabs: torch.Tensor | None = None,
                  slab_stride: int = 0) -> torch.Tensor:
         """Gradient slabs [n_split, n_param] of sum(out * d_out), d_out [E, B(, 1)], for the last `forward(save=True)`."""
-        if self._saved is None:
-            raise RuntimeError("EnsembleCritic.backward called before forward")
-        x, acts = self._saved
+        x, acts = self._saved_forward()
         return ops.ens_mlp_backward(self.desc, self.ensemble_size, self.flat.data, x, acts, d_out.contiguous(), n_split,
                                     slabs=slabs, slab_stride=slab_stride)
 
     def input_grad(self, d_out: torch.Tensor, col0: int, n_col: int, out: torch.Tensor | None = None) -> torch.Tensor:
         """Gradient [B, n_col] of sum(out * d_out) w.r.t. the input columns [col0, col0 + n_col) of the last
         `forward(save=True)`, summed over the members in order; no weight gradient is computed."""
-        if self._saved is None:
-            raise RuntimeError("EnsembleCritic.input_grad called before forward")
-        x, acts = self._saved
+        x, acts = self._saved_forward("input_grad")
         return ops.ens_mlp_input_grad(self.desc, self.ensemble_size, self.flat.data, x, acts, d_out.contiguous(), col0, n_col,
                                       out=out)
 
-    # ---- checkpoints under the reference's key names ------------------------------------------------------------------
-    def _ref_keys(self) -> list[tuple[str, str]]:
-        return [(w, b[:-len("bias")] + "bias_weights") for w, b in ref_layer_keys(self.n_layers, "head")]
-
-    def to_reference_state_dict(self, prefix: str = "", sd: OrderedDict | None = None) -> OrderedDict:
-        sd = OrderedDict() if sd is None else sd
-        for i, (kw, kb) in enumerate(self._ref_keys()):
-            sd[prefix + kw] = self.weight(i).detach().clone().cpu()
-            sd[prefix + kb] = self.bias(i).detach().clone().cpu()
-        return sd
-
-    @torch.no_grad()
-    def load_reference_state_dict(self, sd, prefix: str = "") -> None:
-        for i, (kw, kb) in enumerate(self._ref_keys()):
-            for v, key in ((self.weight(i), kw), (self.bias(i), kb)):
-                v.copy_(torch.as_tensor(sd[prefix + key]).to(v.device, v.dtype).reshape(v.shape))
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        """`Net` + `last` key names, an EnsembleLinear's bias being its `bias_weights`."""
+        return [kv for i, (kw, kb) in enumerate(ref_layer_keys(self.n_layers, "head"))
+                for kv in ((kw, self.weight(i, flat)), (kb + "_weights", self.bias(i, flat)))]
 
 
-class ImplicitQuantileNet(nn.Module):
+class ImplicitQuantileNet(FlatNet):
     """ImplicitQuantileNetwork (discrete.py:164-217) on ONE flat f32 parameter vector in the reference module's
     `parameters()` order: the preprocess layers, the `last` layers, then the cosine embedding's weight [H, C] and bias [H].
     `preprocess` (obs -> ... -> H) and `last` (H -> hidden_sizes -> A) are `FlatMLP`s over slices of the vector (csrc/dense.hip);
@@ -495,6 +548,8 @@ class ImplicitQuantileNet(nn.Module):
     activation, as the reference's `Net` does (every hidden layer is followed by one); the ReLU is then applied inside the
     embedding kernels.  A network row is (b, s): `forward` returns out [R * S, A], the reference's [R, A, S] logits being
     `out.view(R, S, A).transpose(1, 2)`."""
+
+    split_optimizer_state = False
 
     def __init__(self, preprocess_dims, n_act: int, hidden_sizes=(), num_cosines: int = 64, act: str = "relu",
                  feature_act: bool = True, device: str | torch.device = "cuda", seed: int | None = None,
@@ -511,40 +566,33 @@ class ImplicitQuantileNet(nn.Module):
         n_pre = ops.mlp_param_count(ops.mlp_desc(self.pre_dims, act))
         n_last = ops.mlp_param_count(ops.mlp_desc(self.last_dims, act))
         self.w_off, self.b_off = n_pre + n_last, n_pre + n_last + H * self.num_cosines
-        n = self.b_off + H
-        if storage is None:
-            storage = torch.zeros(n, dtype=torch.float32, device=device)
-        elif storage.numel() != n or storage.dtype != torch.float32 or not storage.is_contiguous():
-            raise ValueError(f"ImplicitQuantileNet: storage must be a contiguous f32 vector of {n} elements")
-        self.flat = nn.Parameter(storage, requires_grad=False)
+        storage = self._claim(self.b_off + H, storage, device)
         self.n_pre, self.n_last = n_pre, n_last
         self.preprocess = FlatMLP(self.pre_dims, act, device=storage.device, seed=seed, storage=storage[:n_pre])
         self.last = FlatMLP(self.last_dims, act, device=storage.device, seed=None if seed is None else seed + 1,
                             storage=storage[n_pre:n_pre + n_last])
         self.dims = [self.pre_dims[0], self.n_act]   # what the policies ask of a Q-network: input width, outputs per sample
-        self._saved = None
         self.reset_embedding(None if seed is None else seed + 2)
+
+    def _embedding(self, flat: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+        flat = self._vector(flat)
+        return flat[self.w_off:self.b_off].view(self.embedding_dim, self.num_cosines), flat[self.b_off:]
 
     @property
     def We(self) -> torch.Tensor:
-        return self.flat.data[self.w_off:self.b_off].view(self.embedding_dim, self.num_cosines)
+        return self._embedding()[0]
 
     @property
     def be(self) -> torch.Tensor:
-        return self.flat.data[self.b_off:]
+        return self._embedding()[1]
 
     @torch.no_grad()
     def reset_embedding(self, seed: int | None = None) -> None:
         """torch nn.Linear default init of the embedding layer."""
-        gen = torch.Generator().manual_seed(seed) if seed is not None else None
+        gen = _generator(seed)
         bound = 1.0 / math.sqrt(self.num_cosines)
-        self.We.copy_(torch.empty(self.We.shape).uniform_(-bound, bound, generator=gen))
-        self.be.copy_(torch.empty(self.be.shape).uniform_(-bound, bound, generator=gen))
-
-    def clone_over(self, storage: torch.Tensor) -> "ImplicitQuantileNet":
-        """As `FlatMLP.clone_over`."""
-        return type(self)(self.pre_dims, self.n_act, self.hidden_sizes, self.num_cosines, self.act, self.feature_act,
-                          device=storage.device, seed=0, storage=storage)
+        self.We.copy_(_uniform(self.We.shape, bound, gen))
+        self.be.copy_(_uniform(self.be.shape, bound, gen))
 
     def forward(self, x: torch.Tensor, sample_size: int, taus: torch.Tensor | None = None, save: bool = True, seed: int = 0,
                 offset: int = 0, offset_dev: torch.Tensor | None = None):
@@ -569,17 +617,10 @@ class ImplicitQuantileNet(nn.Module):
         """Gradient slabs [n_split, n_param] of the whole flat vector for the last `forward(save=True)`, in one pass:
         `last`'s weight slabs, its input gradient (a second walk of its dgrad chain: `FlatMLP.input_grad`), the embedding's
         backward, the preprocess net's slabs."""
-        if self._saved is None:
-            raise RuntimeError("ImplicitQuantileNet.backward called before forward")
-        f, phi, taus = self._saved
+        f, phi, taus = self._saved_forward()
         R, S = taus.shape
         P = self.flat.numel()
-        if n_split <= 0:
-            n_split = ops.mlp_n_split(R)
-        if slabs is None:
-            slabs = torch.empty(n_split, P, dtype=torch.float32, device=self.flat.device)
-        elif tuple(slabs.shape) != (n_split, P) or not slabs.is_contiguous():
-            raise ValueError(f"ImplicitQuantileNet.backward: slabs must be a contiguous [{n_split}, {P}]")
+        n_split, slabs = self._slabs(R, n_split, slabs)
         d_out = d_out.reshape(R * S, self.n_act).contiguous()
         self.last.backward(d_out, n_split, slabs=slabs[:, self.n_pre:], slab_stride=P)
         d_e = self.last.input_grad(d_out, 0, self.embedding_dim)
@@ -589,26 +630,22 @@ class ImplicitQuantileNet(nn.Module):
         return slabs
 
     # ---- reference checkpoint compatibility ---------------------------------------------------------------------------
-    def reference_named_views(self) -> list[tuple[str, torch.Tensor]]:
-        """[(key, view)] in `parameters()` order under the reference's names: `preprocess.model.model.{2 i}` (Net: Linear,
-        activation, ...), `last.model.{2 i}` (MLP), `embed_model.net.0` (tests/golden/iqn.npz, sd_*)."""
-        return (self.preprocess.named_layers(ref_layer_keys(self.preprocess.n_layers, "body"), "preprocess.")
-                + self.last.named_layers(ref_layer_keys(self.last.n_layers, "seq"), "last.model.")
-                + [("embed_model.net.0.weight", self.We), ("embed_model.net.0.bias", self.be)])
-
-    def to_reference_state_dict(self) -> OrderedDict:
-        return OrderedDict((k, v.detach().clone().cpu()) for k, v in self.reference_named_views())
-
-    @torch.no_grad()
-    def load_reference_state_dict(self, sd, prefix: str = "") -> None:
-        for k, v in self.reference_named_views():
-            v.copy_(torch.as_tensor(np.asarray(sd[prefix + k])).to(v.device, v.dtype).reshape(v.shape))
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        """`preprocess.model.model.{2 i}` (Net: Linear, activation, ...), `last.model.{2 i}` (MLP), `embed_model.net.0`
+        (tests/golden/iqn.npz, sd_*)."""
+        flat = self._vector(flat)
+        We, be = self._embedding(flat)
+        return (self.preprocess.named_layers(ref_layer_keys(self.preprocess.n_layers, "body"), "preprocess.", flat[:self.n_pre])
+                + self.last.named_layers(ref_layer_keys(self.last.n_layers, "seq"), "last.model.", flat[self.n_pre:self.w_off])
+                + [("embed_model.net.0.weight", We), ("embed_model.net.0.bias", be)])
 
 
-class FractionProposalNet(nn.Module):
+class FractionProposalNet(FlatNet):
     """FractionProposalNetwork (discrete.py:220-253) on ONE flat f32 vector [N * H + N]: the linear layer's weight [N, H], then
     its bias [N]; softmax, cumulative sum and entropy are csrc/fqf.hip.  `feature_act` as `ImplicitQuantileNet`'s: `forward`
     takes the preprocess net's last LINEAR output and the kernels apply its ReLU."""
+
+    split_optimizer_state = False
 
     def __init__(self, num_fractions: int, embedding_dim: int, feature_act: bool = True, device: str | torch.device = "cuda",
                  seed: int | None = None, storage: torch.Tensor | None = None) -> None:
@@ -616,35 +653,27 @@ class FractionProposalNet(nn.Module):
         N, H = self.num_fractions, self.embedding_dim = int(num_fractions), int(embedding_dim)
         ops.fqf_check(N, H)
         self.feature_act = bool(feature_act)
-        n = N * H + N
-        if storage is None:
-            storage = torch.zeros(n, dtype=torch.float32, device=device)
-        elif storage.numel() != n or storage.dtype != torch.float32 or not storage.is_contiguous():
-            raise ValueError(f"FractionProposalNet: storage must be a contiguous f32 vector of {n} elements")
-        self.flat = nn.Parameter(storage, requires_grad=False)
-        self._saved = None
+        self._claim(N * H + N, storage, device)
         self.reset_parameters(seed)
+
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        flat, N, H = self._vector(flat), self.num_fractions, self.embedding_dim
+        return [("net.weight", flat[:N * H].view(N, H)), ("net.bias", flat[N * H:])]
 
     @property
     def Wf(self) -> torch.Tensor:
-        return self.flat.data[:self.num_fractions * self.embedding_dim].view(self.num_fractions, self.embedding_dim)
+        return self.reference_named_views()[0][1]
 
     @property
     def bf(self) -> torch.Tensor:
-        return self.flat.data[self.num_fractions * self.embedding_dim:]
+        return self.reference_named_views()[1][1]
 
     @torch.no_grad()
     def reset_parameters(self, seed: int | None = None) -> None:
         """discrete.py:235-236: xavier_uniform_(gain=0.01) weight, zero bias."""
-        gen = torch.Generator().manual_seed(seed) if seed is not None else None
         bound = 0.01 * math.sqrt(6.0 / (self.embedding_dim + self.num_fractions))
-        self.Wf.copy_(torch.empty(self.Wf.shape).uniform_(-bound, bound, generator=gen))
+        self.Wf.copy_(_uniform(self.Wf.shape, bound, _generator(seed)))
         self.bf.zero_()
-
-    def clone_over(self, storage: torch.Tensor) -> "FractionProposalNet":
-        """As `FlatMLP.clone_over`."""
-        return FractionProposalNet(self.num_fractions, self.embedding_dim, self.feature_act, device=storage.device, seed=0,
-                                   storage=storage)
 
     def forward(self, f: torch.Tensor, save: bool = True):
         """f [R, H] -> (taus [R, N + 1], tau_hats [R, N], logp [R, N], entropies [R])."""
@@ -655,21 +684,7 @@ class FractionProposalNet(nn.Module):
 
     def backward(self, d_logits: torch.Tensor, n_split: int = 0, slabs: torch.Tensor | None = None) -> torch.Tensor:
         """Gradient slabs [n_split, N * H + N] for the features of the last `forward(save=True)`."""
-        if self._saved is None:
-            raise RuntimeError("FractionProposalNet.backward called before forward")
-        return ops.fqf_propose_backward(d_logits, self._saved, n_split, slabs=slabs, relu_f=self.feature_act)
-
-    # ---- reference checkpoint compatibility ---------------------------------------------------------------------------
-    def reference_named_views(self) -> list[tuple[str, torch.Tensor]]:
-        return [("net.weight", self.Wf), ("net.bias", self.bf)]
-
-    def to_reference_state_dict(self) -> OrderedDict:
-        return OrderedDict((k, v.detach().clone().cpu()) for k, v in self.reference_named_views())
-
-    @torch.no_grad()
-    def load_reference_state_dict(self, sd, prefix: str = "") -> None:
-        for k, v in self.reference_named_views():
-            v.copy_(torch.as_tensor(np.asarray(sd[prefix + k])).to(v.device, v.dtype).reshape(v.shape))
+        return ops.fqf_propose_backward(d_logits, self._saved_forward(), n_split, slabs=slabs, relu_f=self.feature_act)
 
 
 class FullQuantileNet(ImplicitQuantileNet):
@@ -702,7 +717,7 @@ class FullQuantileNet(ImplicitQuantileNet):
         return out, fractions, out_tau
 
 
-class RainbowNet(nn.Module):
+class RainbowNet(FlatNet):
     """The reference's `Net(num_atoms=N, dueling_param=(Q, V), linear_layer=NoisyLinear)` (common.py:246-369 around
     discrete.py:318-375, as test/discrete/test_rainbow.py:97-107 builds it) on ONE flat f32 vector in the module's
     `parameters()` order: the layers of `model`, then of `Q`, then of `V`; a noisy layer is mu_W, sigma_W, mu_bias, sigma_bias,
@@ -713,6 +728,8 @@ class RainbowNet(nn.Module):
 
     `noisy_std` None: plain linear layers.  `dueling` False: one chain obs -> hidden -> A * N.  Noise acts only in torch
     training mode (`self.training`); in eval mode the net is its `mu`."""
+
+    split_optimizer_state = False
 
     def __init__(self, obs_dim: int, hidden_sizes, n_act: int, num_atoms: int = 51, q_hidden=(), v_hidden=(),
                  dueling: bool = True, noisy_std: float | None = 0.5, device: str | torch.device = "cuda",
@@ -738,12 +755,7 @@ class RainbowNet(nn.Module):
         self._layers = [(c[i], c[i + 1], noisy) for c in chains for i in range(len(c) - 1)]
         self.table = ops.noisy_net_table(self._layers)
         ops.rainbow_check(self.table)
-        P = int(self.table.P)
-        if storage is None:
-            storage = torch.zeros(P, dtype=torch.float32, device=device)
-        elif storage.numel() != P or storage.dtype != torch.float32 or not storage.is_contiguous():
-            raise ValueError(f"RainbowNet: storage must be a contiguous f32 vector of {P} elements")
-        self.flat = nn.Parameter(storage, requires_grad=False)
+        storage = self._claim(int(self.table.P), storage, device)
         # the effective parameters: not trained, not saved -- rewritten by every forward
         self.eff = torch.zeros(int(self.table.P_eff), dtype=torch.float32, device=storage.device)
         self._parts, o = [], 0
@@ -754,7 +766,6 @@ class RainbowNet(nn.Module):
         self.trunk = self._parts[0][1]
         self.Q, self.V = (self._parts[1][1], self._parts[2][1]) if self.dueling else (None, None)
         self.dims = [self.obs_dim, A * N]   # what the policies ask of a Q-network: input width, outputs per sample
-        self._saved = None
         self._eff_slabs: dict = {}
         self.reset_parameters(seed)
 
@@ -807,22 +818,17 @@ class RainbowNet(nn.Module):
     def reset_parameters(self, seed: int | None = None) -> None:
         """NoisyLinear.reset (discrete.py:351-356: mu uniform in +-1 / sqrt(in), sigma = noisy_std / sqrt(in)) and a first
         draw of the noise as `.f` forms it; plain layers get torch's nn.Linear default."""
-        gen = torch.Generator().manual_seed(seed) if seed is not None else None
+        gen = _generator(seed)
         for (i, o, z), v in zip(self._layers, self.layer_views()):
             bound = 1.0 / math.sqrt(i)
             for k in ("mu_W", "mu_bias") if z else ("weight", "bias"):
-                v[k].copy_(torch.empty(v[k].shape).uniform_(-bound, bound, generator=gen))
+                v[k].copy_(_uniform(v[k].shape, bound, gen))
             if z:
                 v["sigma_W"].fill_(self.noisy_std / math.sqrt(i))
                 v["sigma_bias"].fill_(self.noisy_std / math.sqrt(i))
                 for k in ("eps_p", "eps_q"):
                     x = torch.randn(v[k].shape, generator=gen)
                     v[k].copy_(x.sign() * x.abs().sqrt())
-
-    def clone_over(self, storage: torch.Tensor) -> "RainbowNet":
-        """As `FlatMLP.clone_over`."""
-        return RainbowNet(self.obs_dim, self.hidden_sizes, self.n_act, self.num_atoms, self.q_hidden, self.v_hidden, self.dueling,
-                          self.noisy_std, device=storage.device, seed=0, storage=storage)
 
     # ---- forward / backward -------------------------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor, save: bool = True) -> torch.Tensor:
@@ -849,18 +855,11 @@ class RainbowNet(nn.Module):
         """Gradient slabs [n_split, P] of the whole flat vector for the last `forward(save=True)` (`FlatMLP.backward`'s
         contract): the combine's backward, the streams' weight slabs and input gradients, the feature join, the trunk's slabs
         -- all over the effective layout --, then `tsm_noisy_grad` onto the flat layout.  No forward may come between."""
-        if self._saved is None:
-            raise RuntimeError("RainbowNet.backward called before forward")
-        if self._saved is False:
+        if self._saved_forward() is False:
             raise RuntimeError("RainbowNet.backward must follow its forward(save=True): a later forward recomposed the weights")
         z, training = self._saved
-        R, P, Pe = z.shape[0], int(self.table.P), int(self.table.P_eff)
-        if n_split <= 0:
-            n_split = ops.mlp_n_split(R)
-        if slabs is None:
-            slabs = torch.empty(n_split, P, dtype=torch.float32, device=self.flat.device)
-        elif tuple(slabs.shape) != (n_split, P) or not slabs.is_contiguous():
-            raise ValueError(f"RainbowNet.backward: slabs must be a contiguous [{n_split}, {P}]")
+        R, Pe = z.shape[0], int(self.table.P_eff)
+        n_split, slabs = self._slabs(R, n_split, slabs)
         eff_slabs = self._eff_slabs.get(n_split)
         if eff_slabs is None:
             eff_slabs = self._eff_slabs[n_split] = torch.empty(n_split, Pe, dtype=torch.float32, device=self.flat.device)
@@ -877,23 +876,14 @@ class RainbowNet(nn.Module):
         return ops.noisy_grad(self.table, self.flat.data, eff_slabs, training, slabs=slabs)
 
     # ---- reference checkpoint compatibility ---------------------------------------------------------------------------
-    def reference_named_views(self) -> list[tuple[str, torch.Tensor]]:
-        """[(key, view)] in `parameters()` order under the reference's names: `model.model.{2 i}`, `Q.model.{2 i}`,
-        `V.model.{2 i}` (every MLP is Linear, activation, Linear, ...), each with `.mu_W` ... `.eps_q` or `.weight`, `.bias`
-        (tests/golden/rainbow.npz, sd_*)."""
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        """`model.model.{2 i}`, `Q.model.{2 i}`, `V.model.{2 i}` (every MLP is Linear, activation, Linear, ...), each with
+        `.mu_W` ... `.eps_q` or `.weight`, `.bias` (tests/golden/rainbow.npz, sd_*)."""
         stems = [f"{name}.model.{2 * i}" for name, c in zip(("model", "Q", "V"), self._chains) for i in range(len(c) - 1)]
-        return [(f"{s}.{k}", t) for s, v in zip(stems, self.layer_views()) for k, t in v.items()]
-
-    def to_reference_state_dict(self) -> OrderedDict:
-        return OrderedDict((k, v.detach().clone().cpu()) for k, v in self.reference_named_views())
-
-    @torch.no_grad()
-    def load_reference_state_dict(self, sd, prefix: str = "") -> None:
-        for k, v in self.reference_named_views():
-            v.copy_(torch.as_tensor(np.asarray(sd[prefix + k])).to(v.device, v.dtype).reshape(v.shape))
+        return [(f"{s}.{k}", t) for s, v in zip(stems, self.layer_views(flat)) for k, t in v.items()]
 
 
-class BranchingNet(nn.Module):
+class BranchingNet(FlatNet):
     """The reference's `BranchingNet` (common.py:557-678, arXiv 1711.08946) on ONE flat f32 vector [common | value | branches].
     `common` (obs -> h_1 .. h_n) and `value` (h_n -> value_hidden -> 1) are `FlatMLP`s over slices of it (csrc/dense.hip); the K
     branches (h_n -> action_hidden -> A each) lie behind them in `EnsembleLinear`'s layout with E = K -- per layer weight
@@ -927,22 +917,15 @@ class BranchingNet(nn.Module):
         self._chains = [[D, *common_hidden_sizes], [H, *self.value_hidden_sizes, 1], [H, *self.action_hidden_sizes, A]]
         self.branch_desc = ops.mlp_desc(self._chains[2], "relu")
         sizes = [ops.mlp_param_count(ops.mlp_desc(c, "relu")) for c in self._chains[:2]] + [ops.ens_mlp_param_count(self.branch_desc, K)]
-        self.v_off, self.b_off, P = sizes[0], sizes[0] + sizes[1], sum(sizes)
-        if storage is None:
-            storage = torch.zeros(P, dtype=torch.float32, device=device)
-        elif storage.numel() != P or storage.dtype != torch.float32 or not storage.is_contiguous():
-            raise ValueError(f"BranchingNet: storage must be a contiguous f32 vector of {P} elements")
-        self.flat = nn.Parameter(storage, requires_grad=False)
+        self.v_off, self.b_off = sizes[0], sizes[0] + sizes[1]
+        self._branches = _GroupedLayers(self, self._chains[2], K, offset=self.b_off)
+        self._b_offsets = self._branches.offsets
+        assert self._branches.n_param == sizes[2]
+        storage = self._claim(sum(sizes), storage, device)
         s = lambda k: None if seed is None else seed + k  # noqa: E731
         self.common = FlatMLP(self._chains[0], "relu", device=storage.device, seed=s(0), storage=storage[:self.v_off])
         self.value = FlatMLP(self._chains[1], "relu", device=storage.device, seed=s(1), storage=storage[self.v_off:self.b_off])
-        self._b_offsets, o = [], self.b_off
-        for i in range(len(self._chains[2]) - 1):
-            k, m = self._chains[2][i], self._chains[2][i + 1]
-            self._b_offsets.append((o, o + K * k * m))
-            o += K * (k * m + m)
         self.dims = [D, K * A]   # what the policies ask of a Q-network: input width, outputs per row
-        self._saved = None
         self.reset_branches(s(2))
 
     # ---- views ------------------------------------------------------------------------------------------------------------
@@ -952,29 +935,15 @@ class BranchingNet(nn.Module):
 
     def branch_weight(self, i: int, flat: torch.Tensor | None = None) -> torch.Tensor:
         """Layer i of the branches: weight [K, in, out], a view of the flat vector (or of any vector of its layout)."""
-        o, ob = self._b_offsets[i]
-        return (self.flat.data if flat is None else flat)[o:ob].view(self.num_branches, self._chains[2][i], self._chains[2][i + 1])
+        return self._branches.weight(i, flat)
 
     def branch_bias(self, i: int, flat: torch.Tensor | None = None) -> torch.Tensor:
         """Layer i of the branches: bias [K, 1, out]."""
-        _, ob = self._b_offsets[i]
-        K, m = self.num_branches, self._chains[2][i + 1]
-        return (self.flat.data if flat is None else flat)[ob:ob + K * m].view(K, 1, m)
+        return self._branches.bias(i, flat)
 
-    @torch.no_grad()
     def reset_branches(self, seed: int | None = None) -> None:
         """torch nn.Linear default init of every branch layer: uniform +-1 / sqrt(in) for the weight and for the bias."""
-        gen = torch.Generator().manual_seed(seed) if seed is not None else None
-        for i in range(len(self._b_offsets)):
-            bound = 1.0 / math.sqrt(self._chains[2][i])
-            for v in (self.branch_weight(i), self.branch_bias(i)):
-                v.copy_(torch.rand(v.shape, generator=gen) * 2 * bound - bound)
-
-    def clone_over(self, storage: torch.Tensor) -> "BranchingNet":
-        """As `FlatMLP.clone_over`."""
-        return BranchingNet(state_shape=self.state_shape, num_branches=self.num_branches, action_per_branch=self.action_per_branch,
-                            common_hidden_sizes=self.common_hidden_sizes, value_hidden_sizes=self.value_hidden_sizes,
-                            action_hidden_sizes=self.action_hidden_sizes, device=storage.device, seed=0, storage=storage)
+        self._branches.reset(seed, lambda k: 1.0 / math.sqrt(k))
 
     # ---- forward / backward -------------------------------------------------------------------------------------------------
     def forward(self, obs, state=None, info=None, save: bool = True):
@@ -993,18 +962,11 @@ class BranchingNet(nn.Module):
         """Gradient slabs [n_split, P] of the whole flat vector for the last `forward(save=True)` (`FlatMLP.backward`'s
         contract), d_out = (d_adv, d_v): the branches' weight slabs and their branch-summed input gradient (members in order),
         the value stream's slabs and input gradient, the feature join, the trunk's slabs."""
-        if self._saved is None:
-            raise RuntimeError("BranchingNet.backward called before forward")
+        z, f, acts = self._saved_forward()
         d_adv, d_v = d_out
-        z, f, acts = self._saved
         B, P, H, K = z.shape[0], self.flat.numel(), self._chains[0][-1], self.num_branches
-        if n_split <= 0:
-            n_split = ops.mlp_n_split(B)
-        if slabs is None:
-            slabs = torch.empty(n_split, P, dtype=torch.float32, device=self.flat.device)
-        elif tuple(slabs.shape) != (n_split, P) or not slabs.is_contiguous():
-            raise ValueError(f"BranchingNet.backward: slabs must be a contiguous [{n_split}, {P}]")
-        d_adv = d_adv.reshape(K, B, self.action_per_branch).contiguous()
+        n_split, slabs = self._slabs(B, n_split, slabs)
+        d_adv =d_adv.reshape(K, B, self.action_per_branch).contiguous()
         d_v = d_v.reshape(B, 1).contiguous()
         ops.ens_mlp_backward(self.branch_desc, K, self.branch_flat, f, acts, d_adv, n_split, slabs=slabs[:, self.b_off:], slab_stride=P)
         d_fq = ops.ens_mlp_input_grad(self.branch_desc, K, self.branch_flat, f, acts, d_adv, 0, H)
@@ -1018,38 +980,25 @@ class BranchingNet(nn.Module):
         """[(key, view)] of `flat` (None: the net's own vector; else any vector of its layout, e.g. an Adam moment) in the
         reference module's `parameters()` order and shapes: `common.model.{2 i}`, `value.model.{2 i}`, then per branch
         `branches.{k}.model.{2 i}` -- `nn.Linear`'s [out, in], the transpose of the grouped layout's [in, out] slice."""
-        flat = self.flat.data if flat is None else flat
+        flat = self._vector(flat)
         out = []
         for name, net, lo, hi in (("common", self.common, 0, self.v_off), ("value", self.value, self.v_off, self.b_off)):
-            for (kw, kb), (W, b) in zip(ref_layer_keys(net.n_layers, "seq"), net.layer_views(flat[lo:hi])):
-                out += [(f"{name}.model.{kw}", W), (f"{name}.model.{kb}", b)]
+            out += net.named_layers(ref_layer_keys(net.n_layers, "seq"), f"{name}.model.", flat[lo:hi])
         for k in range(self.num_branches):
-            for i, (kw, kb) in enumerate(ref_layer_keys(len(self._b_offsets), "seq")):
+            for i, (kw, kb) in enumerate(ref_layer_keys(self._branches.n_layers, "seq")):
                 out += [(f"branches.{k}.model.{kw}", self.branch_weight(i, flat)[k].t()),
                         (f"branches.{k}.model.{kb}", self.branch_bias(i, flat)[k, 0])]
         return out
 
-    def param_shapes(self) -> list[tuple[int, ...]]:
-        """The reference's parameter shapes in `parameters()` order."""
-        return [tuple(v.shape) for _, v in self.reference_named_views()]
 
-    def to_reference_state_dict(self, prefix: str = "", sd: OrderedDict | None = None) -> OrderedDict:
-        sd = OrderedDict() if sd is None else sd
-        sd.update((prefix + k, v.detach().clone().contiguous().cpu()) for k, v in self.reference_named_views())
-        return sd
-
-    @torch.no_grad()
-    def load_reference_state_dict(self, sd, prefix: str = "") -> None:
-        for k, v in self.reference_named_views():
-            v.copy_(torch.as_tensor(np.asarray(sd[prefix + k])).to(v.device, v.dtype).reshape(v.shape))
-
-
-class MLPActorCritic(nn.Module):
+class MLPActorCritic(FlatNet):
     """Actor and critic MLPs of ARBITRARY widths under one flat parameter vector (`ActorCritic(actor, critic)`,
     common.py:461-474: one optimizer, one global gradient-norm clip).  Layout = actor parameters then critic parameters,
     each in torch `parameters()` order; `actor` / `critic` are `FlatMLP` views into it (csrc/dense.hip).  Use with
     `tianshou_marl_amd.algorithm.ppo_generic.GenericPPO` when the 64-wide fused kernels do not apply (hidden sizes
     other than 64, more layers, tanh, or a centralized critic: `critic_obs_dim = n_agent * obs_dim`)."""
+
+    split_optimizer_state = False
 
     def __init__(self, obs_dim: int, n_act: int, hidden_sizes=(128, 128), act: str = "relu",
                  critic_obs_dim: int | None = None, device: str | torch.device = "cuda", seed: int | None = None,
@@ -1061,7 +1010,7 @@ class MLPActorCritic(nn.Module):
         dims_c = [self.critic_obs_dim, *hidden_sizes, 1]
         na = ops.mlp_param_count(ops.mlp_desc(dims_a, act))
         nc = ops.mlp_param_count(ops.mlp_desc(dims_c, act))
-        self.flat = nn.Parameter(torch.zeros(na + nc, dtype=torch.float32, device=device), requires_grad=False)
+        self._claim(na + nc, None, device)
         self.n_actor, self.n_critic = na, nc
         self.actor = FlatMLP(dims_a, act, device=device, storage=self.flat.data[:na])
         self.critic = FlatMLP(dims_c, act, device=device, storage=self.flat.data[na:])
@@ -1071,12 +1020,14 @@ class MLPActorCritic(nn.Module):
     def sync_image(self) -> None:
         return None
 
-    def reference_named_views(self) -> list[tuple[str, torch.Tensor]]:
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
         """As DiscreteActorCritic.reference_named_views, for Net(hidden_sizes=[...]) of any depth: hidden layer i is
         `preprocess.model.model.{2 i}` (Linear, activation, Linear, ...), the output layer `last.model.0`."""
+        flat, na = self._vector(flat), self.n_actor
         keys = getattr(self, "_ref_keys", None) or {}
-        return [kv for name, net, prefix in (("actor", self.actor, "policy.actor."), ("critic", self.critic, "critic."))
-                for kv in net.named_layers(keys.get(name) or ref_layer_keys(net.n_layers, "head"), prefix)]
+        return [kv for name, net, prefix, part in (("actor", self.actor, "policy.actor.", flat[:na]),
+                                                   ("critic", self.critic, "critic.", flat[na:]))
+                for kv in net.named_layers(keys.get(name) or ref_layer_keys(net.n_layers, "head"), prefix, part)]
 
     @torch.no_grad()
     def reset_parameters(self, init: str = "orthogonal", seed: int | None = None) -> None:
@@ -1094,6 +1045,10 @@ class MLPActorCritic(nn.Module):
                 net.bias(i).zero_()
 
 
+def _one_parameter(flat: torch.Tensor) -> list[torch.Tensor]:
+    return [flat]
+
+
 class FlatAdam:
     """torch.optim.Adam semantics (algorithm_base.py:485-498 wraps it) on one flat parameter vector, executed by
     `tsm_adam_step` (slab reduction + optional grad-norm clip + Adam in one launch).  Stands where
@@ -1103,7 +1058,9 @@ class FlatAdam:
                  max_grad_norm: float | None = None, coef64: bool = False) -> None:
         self.coef64 = bool(coef64)  # `step` runs tsm_adam_step_coef64: torch's own f32 coefficients 1 - beta
         self.param = module.flat.data if hasattr(module, "flat") else module
-        self._module = module
+        # a vector of the parameter's layout (a moment) -> the parameters it holds, in the vector's order: the net's own
+        # statement; a bare vector, or a module that states none, is one parameter
+        self._views = getattr(module, "param_views", _one_parameter)
         self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm = lr, betas, eps, weight_decay, max_grad_norm
         self.exp_avg = torch.zeros_like(self.param)
         self.exp_avg_sq = torch.zeros_like(self.param)
@@ -1130,26 +1087,7 @@ class FlatAdam:
                            max_grad_norm=self.max_grad_norm, work=self._work, step_dev=step_dev)
 
     def _shapes(self) -> list[tuple[int, ...]]:
-        m = self._module
-        if hasattr(m, "param_shapes"):   # a net whose flat vector is not a FlatMLP's (EnsembleCritic)
-            return list(m.param_shapes())
-        if isinstance(m, FlatMLP):   # the layers, then what the net keeps behind them on the flat vector
-            return [s for i in range(m.n_layers) for s in ((m.dims[i + 1], m.dims[i]), (m.dims[i + 1],))] + \
-                list(getattr(m, "extra_param_shapes", ()))
-        return [tuple(self.param.shape)]
-
-    def _views(self, moment: torch.Tensor) -> list[torch.Tensor]:
-        """`moment` (a vector of the parameter's layout) as the reference's parameters, in `parameters()` order: consecutive
-        blocks of `_shapes()`, or what the module's `reference_named_views` says where its layout is not the reference's
-        concatenation (BranchingNet: a branch's [out, in] weight is a transposed slice of the grouped [K, in, out])."""
-        if isinstance(self._module, BranchingNet):
-            return [v for _, v in self._module.reference_named_views(moment)]
-        out, o = [], 0
-        for shp in self._shapes():
-            n = int(np.prod(shp))
-            out.append(moment[o:o + n].view(shp))
-            o += n
-        return out
+        return [tuple(v.shape) for v in self._views(self.exp_avg)]
 
     def state_dict(self) -> dict:
         """torch.optim.Adam.state_dict() layout (per-parameter `state`, one `param_groups` entry), parameters in the
@@ -1213,7 +1151,7 @@ def lagged_twins(nets, flat: torch.Tensor, offsets) -> tuple[torch.Tensor, list]
 
 
 # ---- the intrinsic curiosity module (utils/net/discrete.py:378-429) -------------------------------------------------------------
-class IntrinsicCuriosityModule(nn.Module):
+class IntrinsicCuriosityModule(FlatNet):
     """discrete.py:378-429: a feature net, a forward model [phi1 | one_hot(act)] -> phi2_hat and an inverse model
     [phi1 | phi2] -> act_hat, as three `FlatMLP`s on ONE flat vector [feature_net | forward_model | inverse_model] (the
     reference's `parameters()` order).  `feature_net`: a `FlatMLP` whose last width is `feature_dim`; its parameters move into
@@ -1238,16 +1176,16 @@ class IntrinsicCuriosityModule(nn.Module):
         self.forward_model = FlatMLP([F + A, *hidden_sizes, F], "relu", device=dev)
         self.inverse_model = FlatMLP([2 * F, *hidden_sizes, A], "relu", device=dev)
         flat, self._offs = join_nets(self.nets, dev)
-        self.flat = nn.Parameter(flat, requires_grad=False)
-        self.head = None   # what the last `forward(save=True)` left for `backward`: ops.icm_head's outputs
+        self._claim(flat.numel(), flat, dev)
 
     @property
     def nets(self) -> list[FlatMLP]:
         return [self.feature_net, self.forward_model, self.inverse_model]
 
-    def param_shapes(self) -> list[tuple[int, ...]]:
-        """The reference's parameters in `parameters()` order (what `FlatAdam.state_dict` lists)."""
-        return [s for m in self.nets for i in range(m.n_layers) for s in ((m.dims[i + 1], m.dims[i]), (m.dims[i + 1],))]
+    @property
+    def head(self):
+        """What the last `forward(save=True)` left for `backward`: ops.icm_head's outputs (None: nothing)."""
+        return self._saved
 
     def forward(self, s1, act, s2, save: bool = True, **kwargs):
         """s1, s2 [R, D], act [R] -> (mse_loss f32 [R], act_hat f32 [R, action_dim]) in HBM (discrete.py:411-429).  kwargs: the
@@ -1280,20 +1218,15 @@ class IntrinsicCuriosityModule(nn.Module):
         phi2_hat = self.forward_model.forward(ops.icm_rows(phi, act, A), save=save)
         act_hat = self.inverse_model.forward(phi.view(R, 2 * F), save=save)
         head = ops.icm_head(phi2_hat, phi, act_hat, act, reward_scale, forward_loss_weight, lr_scale, rew_io=rew_io, ids=ids)
-        self.head = head if save else None
+        self._saved = head if save else None
         return head["mse"], act_hat
 
     def backward(self, n_split: int = 0, slabs: torch.Tensor | None = None) -> torch.Tensor:
         """Gradient slabs [n_split, n_param] of the whole vector for the last `forward(save=True)`: the two models' backwards,
         their input gradients, `ops.icm_join_grad`, one feature-net backward on the 2R rows."""
-        if self.head is None:
-            raise RuntimeError("IntrinsicCuriosityModule.backward called before forward")
-        h, F = self.head, self.feature_dim
+        h, F = self._saved_forward(), self.feature_dim
         R, P = h["mse"].numel(), self.flat.numel()
-        if n_split <= 0:
-            n_split = ops.mlp_n_split(R)
-        if slabs is None:
-            slabs = torch.empty(n_split, P, dtype=torch.float32, device=self.flat.device)
+        n_split, slabs = self._slabs(R, n_split, slabs)
         o = self._offs
         self.forward_model.backward(h["d_phi2_hat"], n_split, slabs=slabs[:, o[1]:], slab_stride=P)
         self.inverse_model.backward(h["d_act_hat"], n_split, slabs=slabs[:, o[2]:], slab_stride=P)
@@ -1303,20 +1236,11 @@ class IntrinsicCuriosityModule(nn.Module):
         self.feature_net.backward(d_phi, n_split, slabs=slabs, slab_stride=P)
         return slabs
 
-    # ---- checkpoints under the reference's key names: three `MLP`s (`ref_layer_keys`: "seq" under `<name>.model.`) -------------
-    def _ref_nets(self):
-        return [(f"{name}.model.", m, ref_layer_keys(m.n_layers, "seq"))
-                for name, m in zip(("feature_net", "forward_model", "inverse_model"), self.nets)]
-
-    def to_reference_state_dict(self) -> OrderedDict:
-        sd = OrderedDict()
-        for prefix, m, keys in self._ref_nets():
-            m.export_layers(keys, prefix, sd)
-        return sd
-
-    def load_reference_state_dict(self, sd) -> None:
-        for prefix, m, keys in self._ref_nets():
-            m.import_layers(sd, keys, prefix)
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        """Three `MLP`s: `ref_layer_keys`' "seq" under `<name>.model.`."""
+        flat, o = self._vector(flat), self._offs
+        return [kv for k, (name, m) in enumerate(zip(("feature_net", "forward_model", "inverse_model"), self.nets))
+                for kv in m.named_layers(ref_layer_keys(m.n_layers, "seq"), f"{name}.model.", flat[o[k]:o[k + 1]])]
 
 
 class RunningMeanStd:
