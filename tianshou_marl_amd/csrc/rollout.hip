@@ -21,6 +21,7 @@
 #include "mpe_dev.h"
 #include "philox.h"
 #include "rollout_dev.h"
+#include "rollout_fwd.h"
 #include "wave_mlp.h"
 
 int tsm_mpe_check_cfg(const tsm_mpe_cfg *h, MpeCfg *c);  // mpe.hip
@@ -188,9 +189,18 @@ __global__ __launch_bounds__(NT2) void rollout_kernel(RolloutArgs a) {
     const bool u_lane = a.mode == 1 && ur >= 0 && ur < rows_here;
     if (u_lane) s_u[ur] = tsm_philox_uniform(a.pol_seed, off0 + (uint64_t)e0 * N + (uint64_t)ur);
     __syncthreads();
+    // (eight-wave form) the launch's constants of this wave's chains, read once: weight fragments and biases (rollout_fwd.h)
+    constexpr bool REGS = NT2 == 2 * NT;
+    constexpr int KB1 = REGS && DS ? dims_const(DS ? DS : 1, 5).Kp1 / 4 : 0;   // (the generic form keeps W1 in LDS)
+    FwdRegs<H, KB1> fr;
+    if constexpr (REGS) fwd_regs_load(fr, lds, ly, d);
     // two observation tiles, swapped every step: obs_next of step t IS obs of step t + 1 (rows of re-initialised
     // envs are rebuilt in F), so the observation function runs once per step, not twice
     Lay<H> lyf = ly;
+    auto forward = [&]() {   // of the tile at lyf.X
+        if constexpr (REGS) tile_forward_regs<H, KB1>(lds, lyf, d, fr);
+        else tile_forward<H>(lds, lyf, d);
+    };
     int xcur = ly.X, xnxt = tl.XN0;
     // A. observation rows from the LDS-resident state: one (row, element) per thread
     for (int i = threadIdx.x; i < rows_here * D; i += NT2) {
@@ -208,8 +218,7 @@ __global__ __launch_bounds__(NT2) void rollout_kernel(RolloutArgs a) {
         STAMP(1);
         // B. actor + critic forward of the 16-row tile
         lyf.X = xcur;
-        if constexpr (NT2 == 2 * NT) tile_forward_split<H>(lds, lyf, d);
-        else tile_forward<H>(lds, lyf, d);
+        forward();
         STAMP(2);
         bool tr = false;
         if (env_lane && !last) {   // the buffer index algebra of this step (beside the head; D .. F read generation t & 1)
@@ -403,8 +412,7 @@ __global__ __launch_bounds__(NT2) void rollout_kernel(RolloutArgs a) {
         if (any_done) {
             if (a.b.vnext_store) {
                 lyf.X = xnxt;
-                if constexpr (NT2 == 2 * NT) tile_forward_split<H>(lds, lyf, d);
-                else tile_forward<H>(lds, lyf, d);
+                forward();
                 if (lane_live && s_done[g + el]) a.b.vnext_store[s_row[g + el] * N + ai] = lds[ly.OUT + r * ly.ldo + 16];
             }
             if (a.auto_reset) {
