@@ -1558,6 +1558,47 @@ int tsm_gail_reward(const float *logits, const int64_t *ids, int64_t R, float *r
 int tsm_gail_head(const float *logits, int64_t Rp, int64_t Re, float *d_logits, double *partial, void *stream);
 int tsm_gail_finalize(const double *partial, int64_t n_blocks, int64_t Rp, int64_t Re, float *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Learned global states  (tianshou/algorithm/multiagent/ctde.py:230-343, GlobalStateConstructor modes "attention" and
+ * "graph"; csrc/gstate.hip)
+ * What lies between the modes' matrix products with weights, which stay on csrc/dense.hip.  A row is one joint step, its N
+ * agents in env.agents order.  1 <= N <= TSM_GSTATE_MAX_AGENTS; D % TSM_GSTATE_HEADS == 0 and TSM_GSTATE_HEADS <= D <=
+ * TSM_GSTATE_MAX_DIM (a head is dh = D / 4 <= 64 wide); H >= 1; B >= 1: anything else, or a null pointer where none is allowed,
+ * is TSM_ERR_INVALID naming the limit before any launch.  Float32 arithmetic; every sum is taken by one lane in index order, no
+ * atomics: two runs give the same bits.
+ * tsm_gstate_check: the bounds on (N, D) alone.  Needs no device.
+ * tsm_attn_pool_forward replaces  the core of nn.MultiheadAttention(embed_dim = D, num_heads = 4, batch_first = True) between
+ *   its in- and out-projection, and the mean over agents behind it (ctde.py:270-274, 308-311), without mask or dropout.
+ *   qkv f32 [B][N][3 D], 16-byte aligned (it is staged with 16-B loads; rows are multiples of 16 B as D % 4 == 0): the
+ *   in-projection of agent n's observation, [Q | K | V].  Per row and head h (columns h dh .. h dh + dh
+ *   of each part):  S = (Q_h / sqrt(dh)) K_h^T  [N][N];  P = softmax over the keys, the row maximum subtracted;  O = P V_h.
+ *   out: ctx f32 [B][D] = (1 / N) sum_n concat_h(O)[n] (the mean is taken BEFORE the out-projection, which is linear:
+ *   mean_n(W O_n + b) = W mean_n O_n + b), formed as sum_j ((sum_i P[h][i][j]) V[j][d]) / N;  P f32 [B][4][N][N] for the backward.
+ *   TSM_GSTATE_ROWS_PER_BLOCK rows per workgroup, one wave each.
+ * tsm_attn_pool_backward: d_ctx f32 [B][D], qkv and P as above -> d_qkv f32 [B][N][3 D], every element written:
+ *   d P[h][i][j] = (1 / N) sum_t d_ctx[h dh + t] V[j][h dh + t] (the same for every query i);  d S = P (d P - sum_j P d P);
+ *   d Q[i] = sum_j d S[i][j] K[j] / sqrt(dh);  d K[j] = sum_i d S[i][j] Q[i] / sqrt(dh);  d V[j][d] = (d_ctx[d] / N) sum_i P[h][i][j].
+ * tsm_agent_pool_forward replaces  the neighbour aggregation and the mean over agents of mode "graph" (ctde.py:320-335) around
+ *   gnn_layer2, which is linear:  mean_n(W2 (A^ x)_n + b2) = W2 (sum_m c_m x_m) + b2,  c_m = (1 / N) sum_n A^[n][m], A^ the
+ *   row-normalised adjacency (no adjacency: c_m = 1 / N).  h f32 [B][N][H], c f32 [N] (device) ->
+ *   out f32 [B][H] = sum_n c[n] f(h[b][n][:]), n in order;  relu != 0: f = max(., 0), the F.relu of ctde.py:320 behind
+ *   gnn_layer1, whose dense.hip net ends linear;  relu == 0: f the identity.
+ * tsm_agent_pool_backward: d f32 [B][H] -> d_h f32 [B][N][H] = c[n] d[b][:], times 1[h_relu[b][n][:] > 0] where h_relu (the
+ *   forward's h, nullable) is given.
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_GSTATE_MAX_AGENTS 8
+#define TSM_GSTATE_HEADS 4
+#define TSM_GSTATE_MAX_DIM 256
+#define TSM_GSTATE_ROWS_PER_BLOCK 4
+int tsm_gstate_check(int32_t n_agents, int32_t obs_dim);
+int tsm_attn_pool_forward(const float *qkv, int64_t B, int32_t n_agents, int32_t D, float *ctx, float *P, void *stream);
+int tsm_attn_pool_backward(const float *d_ctx, const float *qkv, const float *P, int64_t B, int32_t n_agents, int32_t D,
+                           float *d_qkv, void *stream);
+int tsm_agent_pool_forward(const float *h, const float *c, int64_t B, int32_t n_agents, int32_t H, int32_t relu, float *out,
+                           void *stream);
+int tsm_agent_pool_backward(const float *d, const float *c, const float *h_relu, int64_t B, int32_t n_agents, int32_t H,
+                            float *d_h, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,8 +2,9 @@
 
 Mirror of /root/reference/tianshou/algorithm/multiagent/ctde.py for the components of SURVEY section 8a row a16:
   `CTDEPolicy`               :22-227   forward = decentralized actor on local obs; learn = centralized critic TD
-  `GlobalStateConstructor`   :230-343  "concatenate" / "mean" (+ "custom"); attention / graph aggregation are
-                                       learned modules outside the hot path (out of scope)
+  `GlobalStateConstructor`   :230-343  "concatenate" / "mean" (+ "custom"), and the learned "attention" / "graph" aggregations:
+                                       `AttentionStateNet` / `GraphStateNet` (utils/net.py), dense.hip products around the
+                                       kernels of csrc/gstate.hip, trained by `CTDEPolicy(state_constructor=...)`
   `DecentralizedActor`       :346-379  obs -> H -> H -> action logits, ReLU
   `CentralizedCritic`        :382-414  global_obs -> H -> H -> n_agents values, ReLU
   `QMIXMixer`, `QMIXPolicy` :417-725  value decomposition with a monotonic mixer: built in qmix.py (csrc/qmix.hip) and
@@ -30,7 +31,7 @@ from ... import ops
 from ...data.batch import Batch
 from ...data.stats import LazyDict, ResultRing, pinned_slot, recycle
 from ...utils.learner import act_result, sample_counter
-from ...utils.net import FlatAdam, FlatMLP
+from ...utils.net import AttentionStateNet, FlatAdam, FlatMLP, GraphStateNet
 from ...utils.tensor import to_tensor
 
 
@@ -62,24 +63,81 @@ class CentralizedCritic(_CTDENet):
 
 
 class GlobalStateConstructor(nn.Module):
+    """ctde.py:230-343.  "concatenate", "mean" and "custom" hold no parameters.  "attention" and "graph" are learned: `self.net`
+    is an `AttentionStateNet` / `GraphStateNet` (utils/net.py; csrc/gstate.hip between csrc/dense.hip products), trained through
+    `CTDEPolicy(state_constructor=...)`; `state_dict()` speaks the reference module's keys."""
+
+    LEARNED = ("attention", "graph")
+
     def __init__(self, mode: Literal["concatenate", "mean", "attention", "graph", "custom"] = "concatenate",
                  obs_dim: int | None = None, n_agents: int | None = None, hidden_dim: int = 64,
-                 adjacency_matrix: torch.Tensor | None = None, custom_fn: Callable | None = None) -> None:
+                 adjacency_matrix: torch.Tensor | None = None, custom_fn: Callable | None = None,
+                 device: str | torch.device = "cuda", seed: int | None = None) -> None:
         super().__init__()
-        if mode in ("attention", "graph"):
-            raise NotImplementedError(
-                f"GlobalStateConstructor(mode={mode!r}) is a learned aggregation outside the north-star hot path "
-                "(SURVEY.md section 2); use 'concatenate', 'mean' or 'custom'")
-        self.mode, self.obs_dim, self.n_agents = mode, obs_dim, n_agents
+        self.mode, self.obs_dim, self.n_agents, self.hidden_dim = mode, obs_dim, n_agents, hidden_dim
         self.adjacency_matrix, self.custom_fn = adjacency_matrix, custom_fn
+        self.net = None
+        if mode in self.LEARNED:
+            self._check_learned(mode, obs_dim, n_agents)
+            if mode == "attention":
+                self.net = AttentionStateNet(obs_dim, n_agents, hidden_dim, device=device, seed=seed)
+            else:
+                self.net = GraphStateNet(obs_dim, n_agents, hidden_dim, adjacency_matrix, device=device, seed=seed)
+
+    @staticmethod
+    def _check_learned(mode: str, obs_dim, n_agents) -> None:
+        """A shape the kernels do not serve stays NotImplementedError, naming the limit (include/tsmarl.h: TSM_GSTATE_*)."""
+        lim = ops._abi
+        if not obs_dim or not n_agents:
+            raise NotImplementedError(f"GlobalStateConstructor(mode={mode!r}) needs obs_dim and n_agents: the HIP path builds its "
+                                      "network at construction (the reference builds none without them and concatenates)")
+        if not 1 <= int(n_agents) <= lim.GSTATE_MAX_AGENTS:
+            raise NotImplementedError(f"GlobalStateConstructor(mode={mode!r}): n_agents = {n_agents}; the HIP kernels serve 1 to "
+                                      f"{lim.GSTATE_MAX_AGENTS} agents")
+        if mode == "attention" and (int(obs_dim) % lim.GSTATE_HEADS or not lim.GSTATE_HEADS <= int(obs_dim) <= lim.GSTATE_MAX_DIM):
+            raise NotImplementedError(
+                f"GlobalStateConstructor(mode='attention'): obs_dim = {obs_dim}; the HIP kernels serve multiples of the "
+                f"{lim.GSTATE_HEADS} heads from {lim.GSTATE_HEADS} to {lim.GSTATE_MAX_DIM} (torch itself asserts embed_dim % "
+                "num_heads == 0)")
 
     def build(self, observations: dict[str, torch.Tensor]) -> torch.Tensor:
         """observations: agent_id -> [B, D] (dict order = env.agents order; never a set, quirk Q5)."""
         if self.mode == "custom" and self.custom_fn:
             return self.custom_fn(observations)
         obs = [torch.as_tensor(np.asarray(o) if not isinstance(o, torch.Tensor) else o) for o in observations.values()]
+        if self.net is not None:
+            dev = self.net.flat.device
+            if len(obs) != self.n_agents:
+                raise ValueError(f"GlobalStateConstructor.build: {len(obs)} agents, built for {self.n_agents}")
+            return self.net.forward(torch.stack([o.to(dev, torch.float32) for o in obs], dim=1), save=True)
         obs = [o.to("cuda", torch.float32).contiguous() if not o.is_cuda else o.to(torch.float32).contiguous() for o in obs]
         return ops.global_state(obs, "mean" if self.mode == "mean" else "concatenate")  # unknown modes concatenate (:340-343)
+
+    def _learned(self, what: str):
+        if self.net is None:
+            raise RuntimeError(f"GlobalStateConstructor.{what}: mode {self.mode!r} holds no network (attention | graph do)")
+        return self.net
+
+    def build_joint(self, obs: torch.Tensor, save: bool = False) -> torch.Tensor:
+        """Device layout shortcut of a learned mode: obs [R, N, D] (one joint step per row) -> [R, hidden_dim].  `save`: keep
+        what `backward` needs."""
+        return self._learned("build_joint").forward(obs, save=save)
+
+    def backward(self, d_state: torch.Tensor, n_split: int = 0, slabs: torch.Tensor | None = None) -> torch.Tensor:
+        """Gradient slabs [n_split, n_param] of the network for the last saved `build` / `build_joint`."""
+        return self._learned("backward").backward(d_state, n_split, slabs)
+
+    def state_dict(self, *args, destination=None, prefix: str = "", **kwargs):  # type: ignore[override]
+        """The reference module's keys: `attention.in_proj_weight`, ..., `output_proj.bias` | `gnn_layer{1,2}.weight|bias`;
+        nothing for the modes without parameters."""
+        from collections import OrderedDict
+
+        sd = OrderedDict() if destination is None else destination
+        return sd if self.net is None else self.net.to_reference_state_dict(prefix, sd)
+
+    def load_state_dict(self, sd, *args, **kwargs):  # type: ignore[override]
+        if self.net is not None:
+            self.net.load_reference_state_dict(sd)
 
     @staticmethod
     def from_joint_rows(obs: torch.Tensor, mode: str = "concatenate") -> torch.Tensor:
@@ -123,6 +181,21 @@ class CTDEPolicy(nn.Module):
         self.graph = bool(kwargs.pop("graph", True))  # the fused learn as one hipGraph replay per call
         self._ws: dict = {}
         self._cfg_pg = ops.make_ppo_cfg(adv_norm=False, ent_coef=0.0, vf_coef=0.0, loss_kind=1)
+        # a learned global state (GlobalStateConstructor "attention" | "graph") in front of the critic, trained by the critic's
+        # loss: `learn` then aggregates the concatenated joint observation itself (_learn_constructed)
+        self.state_constructor = kwargs.pop("state_constructor", None)
+        self.optim_state = kwargs.pop("optim_state", None)
+        if self.state_constructor is not None:
+            net = getattr(self.state_constructor, "net", None)
+            if net is None:
+                raise TypeError("CTDEPolicy: state_constructor must be a GlobalStateConstructor of a learned mode (attention | "
+                                "graph); the modes without parameters are applied to the batch by the caller")
+            if critic.dims[0] != net.hidden_dim:
+                raise ValueError(f"CTDEPolicy: the critic reads {critic.dims[0]} inputs, the state constructor gives "
+                                 f"hidden_dim = {net.hidden_dim}")
+            self.optim_state = self.optim_state or FlatAdam(net)
+        elif self.optim_state is not None:
+            raise ValueError("CTDEPolicy: optim_state without state_constructor")
 
     @property
     def device(self) -> torch.device:
@@ -249,8 +322,47 @@ class CTDEPolicy(nn.Module):
         slot["pending"] = out
         return out
 
+    def _learn_constructed(self, batch: Batch) -> dict[str, float]:
+        """`learn` with a learned global state: what the reference computes when `batch.global_obs = constructor.build(obs)` is
+        left attached to autograd and the constructor's parameters are in `optim_critic`.  `batch.global_obs` / `global_obs_next`
+        are the CONCATENATED joint observation [B, N D] (`agent_batches_from_buffer(..., global_state=True)`, mode
+        "concatenate"); the aggregation runs here.  The target side keeps nothing (detach, ctde.py:172); every gradient is
+        taken at the pre-step weights, as the single `critic_loss.backward()` gives.  Eager: no fused store path, no graph."""
+        gsc = self.state_constructor
+        N, D = gsc.net.n_agents, gsc.net.obs_dim
+        if not self.enable_global_info or "global_obs" not in batch or "global_obs_next" not in batch:
+            raise ValueError("CTDEPolicy.learn: a state constructor needs batch.global_obs and batch.global_obs_next, the "
+                             "concatenated joint observation (and enable_global_info)")
+        obs = self._t(batch.obs, torch.float32)
+        act = self._t(batch.act, torch.int64).reshape(-1)
+        rew = self._t(batch.rew, torch.float32).reshape(-1)
+        terminated = self._t(batch.terminated, torch.uint8).reshape(-1)
+        B = obs.shape[0]
+        joint, joint_next = self._t(batch.global_obs, torch.float32), self._t(batch.global_obs_next, torch.float32)
+        for name, g in (("global_obs", joint), ("global_obs_next", joint_next)):
+            if g.numel() != B * N * D:
+                raise ValueError(f"CTDEPolicy.learn: batch.{name} must be the concatenated joint observation [{B}, {N * D}], got "
+                                 f"{list(g.shape)}")
+        critic_in = gsc.build_joint(joint.reshape(B, N, D), save=True)
+        critic_in_next = gsc.build_joint(joint_next.reshape(B, N, D), save=False)
+        q = self.critic(critic_in, save=True).reshape(B, -1)
+        q_next = self.critic(critic_in_next, save=False).reshape(B, -1)
+        logits = FlatMLP.forward(self.actor, obs, save=True)
+        dq, dlogits, scalars = ops.ctde_td_head(q, q_next, rew, terminated, self.discount_factor, logits, act)
+        d_in = self.critic.input_grad(dq, 0, self.critic.dims[0])   # before the critic moves
+        self.optim_critic.zero_grad()
+        self.optim_critic.step(self.critic.backward(dq))
+        self.optim_state.zero_grad()
+        self.optim_state.step(gsc.backward(d_in))
+        self.optim_actor.zero_grad()
+        self.optim_actor.step(self.actor.backward(dlogits))
+        s = scalars.cpu().numpy()
+        return {"actor_loss": float(s[0]), "critic_loss": float(s[1])}
+
     def learn(self, batch: Batch, **kwargs: Any) -> dict[str, float]:
         """One centralized-critic TD step + one policy-gradient step (ctde.py:121-199)."""
+        if self.state_constructor is not None:
+            return self._learn_constructed(batch)
         fast = self._store_path(batch)
         if fast is not None:
             out = self._learn_store(*fast)

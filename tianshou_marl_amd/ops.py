@@ -1001,6 +1001,110 @@ def ctde_td_head(q, q_next, rew, terminated, gamma: float, logits, act):
 
 
 # --------------------------------------------------------------------------------------------
+# learned global states (ctde.py:230-343, modes "attention" and "graph"; csrc/gstate.hip)
+# --------------------------------------------------------------------------------------------
+def gstate_check(n_agents: int, obs_dim: int) -> None:
+    """The bounds of the attention kernels (include/tsmarl.h): ValueError naming the limit."""
+    N, D, heads = int(n_agents), int(obs_dim), _abi.GSTATE_HEADS
+    if not 1 <= N <= _abi.GSTATE_MAX_AGENTS:
+        raise ValueError(f"gstate: n_agents = {N}; the HIP kernels serve 1 to {_abi.GSTATE_MAX_AGENTS} agents")
+    if D % heads or not heads <= D <= _abi.GSTATE_MAX_DIM:
+        raise ValueError(f"gstate: obs_dim = {D}; the HIP kernels serve multiples of {heads} (the {heads} heads) from {heads} to "
+                         f"{_abi.GSTATE_MAX_DIM}")
+
+
+def _gstate_arg(name: str, nm: str, t, shape=None):
+    """An f32 tensor, contiguous as it stands (no silent copy: the backward reads what the forward wrote), of `shape`.  Shapes
+    and limits are checked before the device is: a host tensor reaches `_dev_only` with everything else in order."""
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{name}: {nm} must be a contiguous float32 tensor, got {t.dtype}, strides {tuple(t.stride())}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: {nm} must be {list(shape)}, got {list(t.shape)}")
+    if nm == "qkv" and t.data_ptr() % 16:
+        raise ValueError(f"{name}: qkv must be 16-byte aligned (the kernels stage it with 16-byte loads)")
+    return t
+
+
+def _pool_check(name: str, N: int, H: int, B: int) -> None:
+    if not 1 <= N <= _abi.GSTATE_MAX_AGENTS:
+        raise ValueError(f"{name}: n_agents = {N}; the HIP kernels serve 1 to {_abi.GSTATE_MAX_AGENTS} agents")
+    if H < 1 or B < 1:
+        raise ValueError(f"{name}: B = {B} rows of H = {H}; both at least 1")
+
+
+def attn_pool_forward(qkv, n_agents: int):
+    """The attention core and the mean over agents (tsm_attn_pool_forward): qkv f32 [B, N, 3 D] or [B * N, 3 D], the
+    in-projection's output -> (ctx [B, D], P [B, 4, N, N])."""
+    N = int(n_agents)
+    _gstate_arg("attn_pool_forward", "qkv", qkv)
+    if qkv.dim() not in (2, 3) or qkv.shape[-1] % 3 or qkv.numel() == 0:
+        raise ValueError(f"attn_pool_forward: qkv must be a non-empty [B, N, 3 D] or [B N, 3 D], got {list(qkv.shape)}")
+    D = qkv.shape[-1] // 3
+    gstate_check(N, D)
+    rows = qkv.numel() // (3 * D)
+    if rows % N or (qkv.dim() == 3 and qkv.shape[1] != N):
+        raise ValueError(f"attn_pool_forward: qkv {list(qkv.shape)} does not hold rows of n_agents = {N}")
+    B = rows // N
+    _dev_only("attn_pool_forward", qkv)
+    ctx = torch.empty(B, D, dtype=torch.float32, device=qkv.device)
+    P = torch.empty(B, _abi.GSTATE_HEADS, N, N, dtype=torch.float32, device=qkv.device)
+    call("tsm_attn_pool_forward", ptr(qkv), B, N, D, ptr(ctx), ptr(P), stream_ptr())
+    return ctx, P
+
+
+def attn_pool_backward(d_ctx, qkv, P):
+    """d_ctx [B, D], and the forward's qkv and P [B, 4, N, N] -> d_qkv [B, N, 3 D] (tsm_attn_pool_backward)."""
+    _gstate_arg("attn_pool_backward", "P", P)
+    if P.dim() != 4 or P.shape[1] != _abi.GSTATE_HEADS or P.shape[2] != P.shape[3] or P.numel() == 0:
+        raise ValueError(f"attn_pool_backward: P must be a non-empty [B, {_abi.GSTATE_HEADS}, N, N], got {list(P.shape)}")
+    B, N = P.shape[0], P.shape[2]
+    _gstate_arg("attn_pool_backward", "d_ctx", d_ctx)
+    if d_ctx.dim() != 2 or d_ctx.shape[0] != B:
+        raise ValueError(f"attn_pool_backward: d_ctx must be [{B}, D], got {list(d_ctx.shape)}")
+    D = d_ctx.shape[1]
+    gstate_check(N, D)
+    _gstate_arg("attn_pool_backward", "qkv", qkv)
+    if qkv.numel() != B * N * 3 * D or qkv.shape[-1] != 3 * D:
+        raise ValueError(f"attn_pool_backward: qkv must be [{B}, {N}, {3 * D}], got {list(qkv.shape)}")
+    _dev_only("attn_pool_backward", d_ctx, qkv, P)
+    d_qkv = torch.empty(B, N, 3 * D, dtype=torch.float32, device=qkv.device)
+    call("tsm_attn_pool_backward", ptr(d_ctx), ptr(qkv), ptr(P), B, N, D, ptr(d_qkv), stream_ptr())
+    return d_qkv
+
+
+def agent_pool_forward(h, c, relu: bool = False):
+    """h f32 [B, N, H], c f32 [N] -> [B, H] = sum_n c[n] f(h[:, n]) (tsm_agent_pool_forward); relu: f = max(., 0)."""
+    _gstate_arg("agent_pool_forward", "h", h)
+    if h.dim() != 3:
+        raise ValueError(f"agent_pool_forward: h must be [B, N, H], got {list(h.shape)}")
+    B, N, H = h.shape
+    _pool_check("agent_pool_forward", N, H, B)
+    _gstate_arg("agent_pool_forward", "c", c, (N,))
+    _dev_only("agent_pool_forward", h, c)
+    out = torch.empty(B, H, dtype=torch.float32, device=h.device)
+    call("tsm_agent_pool_forward", ptr(h), ptr(c), B, N, H, int(bool(relu)), ptr(out), stream_ptr())
+    return out
+
+
+def agent_pool_backward(d, c, n_agents: int, h_relu=None):
+    """d f32 [B, H], c f32 [N] -> d_h [B, N, H] = c[n] d (tsm_agent_pool_backward); h_relu [B, N, H], the input of a forward
+    with relu: zero where it was not positive."""
+    N = int(n_agents)
+    _gstate_arg("agent_pool_backward", "d", d)
+    if d.dim() != 2:
+        raise ValueError(f"agent_pool_backward: d must be [B, H], got {list(d.shape)}")
+    B, H = d.shape
+    _pool_check("agent_pool_backward", N, H, B)
+    _gstate_arg("agent_pool_backward", "c", c, (N,))
+    if h_relu is not None:
+        _gstate_arg("agent_pool_backward", "h_relu", h_relu, (B, N, H))
+    _dev_only("agent_pool_backward", d, c, h_relu)
+    d_h = torch.empty(B, N, H, dtype=torch.float32, device=d.device)
+    call("tsm_agent_pool_backward", ptr(d), ptr(c), ptr(h_relu), B, N, H, ptr(d_h), stream_ptr())
+    return d_h
+
+
+# --------------------------------------------------------------------------------------------
 # QMIX (ctde.py:417-725; csrc/qmix.hip)
 # --------------------------------------------------------------------------------------------
 QMIX_EMBED_DIMS = (32, 64)

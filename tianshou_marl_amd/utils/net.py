@@ -717,6 +717,157 @@ class FullQuantileNet(ImplicitQuantileNet):
         return out, fractions, out_tau
 
 
+# ---- the learned global states of CTDE (algorithm/multiagent/ctde.py:268-280, 302-335) ------------------------------------------
+class _StateNet(FlatNet):
+    """What the two learned `GlobalStateConstructor` modes share: joint rows obs [R, N, D] -> state [R, hidden_dim], two
+    `FlatMLP`s `head` and `tail` over consecutive slices of the vector around a kernel of csrc/gstate.hip that folds the agents."""
+
+    def _build(self, head_dims, head_act: str, tail_dims, storage, device, seeds) -> None:
+        n_head = ops.mlp_param_count(ops.mlp_desc(head_dims, head_act))
+        n_tail = ops.mlp_param_count(ops.mlp_desc(tail_dims, "none"))
+        storage = self._claim(n_head + n_tail, storage, device)
+        self.n_head = n_head
+        self.head = FlatMLP(head_dims, head_act, device=storage.device, seed=seeds[0], storage=storage[:n_head])
+        self.tail = FlatMLP(tail_dims, "none", device=storage.device, seed=seeds[1], storage=storage[n_head:])
+        self.dims = [self.n_agents * self.obs_dim, self.hidden_dim]   # a critic's input is dims[-1] wide
+
+    def rebind(self, storage: torch.Tensor) -> None:
+        self.flat = nn.Parameter(storage, requires_grad=False)
+        self.head.rebind(storage[:self.n_head])
+        self.tail.rebind(storage[self.n_head:])
+
+    def _rows(self, obs: torch.Tensor) -> tuple[torch.Tensor, int]:
+        N, D = self.n_agents, self.obs_dim
+        obs = obs.to(self.flat.device, torch.float32).contiguous()
+        if obs.dim() < 2 or obs.numel() == 0 or obs.numel() % (N * D) or (obs.dim() == 3 and tuple(obs.shape[1:]) != (N, D)):
+            raise ValueError(f"{type(self).__name__}: obs must be [R, {N}, {D}] (or [R, {N * D}], agents in order), got "
+                             f"{list(obs.shape)}")
+        return obs.reshape(-1, D), obs.numel() // (N * D)
+
+    def _fold(self, y: torch.Tensor, R: int):
+        """The head's output y [R N, .] -> (the tail's input [R, .], what `_unfold` needs)."""
+        raise NotImplementedError
+
+    def _unfold(self, d_x: torch.Tensor, y: torch.Tensor, kept) -> torch.Tensor:
+        """The gradient of the tail's input -> the gradient of the head's output [R N, .]."""
+        raise NotImplementedError
+
+    def forward(self, obs: torch.Tensor, save: bool = True) -> torch.Tensor:
+        """obs [R, N, D], agents in env.agents order -> [R, hidden_dim]."""
+        x, R = self._rows(obs)
+        y = FlatMLP.forward(self.head, x, save=save)
+        z, kept = self._fold(y, R)
+        out = FlatMLP.forward(self.tail, z, save=save)
+        if save:
+            self._saved = (y, kept, R)
+        return out
+
+    def backward(self, d_state: torch.Tensor, n_split: int = 0, slabs: torch.Tensor | None = None) -> torch.Tensor:
+        """Gradient slabs [n_split, n_param] of sum(state * d_state) for the last `forward(save=True)`: the tail's slabs and
+        its input gradient, the fold's backward, the head's slabs."""
+        y, kept, R = self._saved_forward()
+        P = self.flat.numel()
+        n_split, slabs = self._slabs(R, n_split, slabs)
+        d_state = d_state.to(self.flat.device, torch.float32).reshape(R, self.hidden_dim).contiguous()
+        self.tail.backward(d_state, n_split, slabs=slabs[:, self.n_head:], slab_stride=P)
+        d_x = self.tail.input_grad(d_state, 0, self.tail.dims[0])
+        self.head.backward(self._unfold(d_x, y, kept), n_split, slabs=slabs, slab_stride=P)
+        return slabs
+
+
+class AttentionStateNet(_StateNet):
+    """`GlobalStateConstructor(mode="attention")` (ctde.py:268-275, 302-312): nn.MultiheadAttention(embed_dim=obs_dim,
+    num_heads=4, batch_first=True) over the agents, the mean over agents, Linear(obs_dim, hidden_dim) -- on ONE flat f32 vector
+    in the module's `parameters()` order.  The in-projection is the `FlatMLP` [D, 3 D] `head`; the out-projection and
+    `output_proj` are the two linear layers of the `FlatMLP` [D, D, hidden_dim] `tail`, which runs on the POOLED rows (the mean
+    commutes with a linear layer); between them tsm_attn_pool_forward / _backward.  No mask, no dropout."""
+
+    def __init__(self, obs_dim: int, n_agents: int, hidden_dim: int = 64, device: str | torch.device = "cuda",
+                 seed: int | None = None, storage: torch.Tensor | None = None) -> None:
+        super().__init__()
+        self.obs_dim, self.n_agents, self.hidden_dim = int(obs_dim), int(n_agents), int(hidden_dim)
+        ops.gstate_check(self.n_agents, self.obs_dim)
+        D = self.obs_dim
+        self._build([D, 3 * D], "none", [D, D, self.hidden_dim], storage, device, (0, 0))
+        self.reset_parameters(seed)
+
+    @torch.no_grad()
+    def reset_parameters(self, seed: int | None = None) -> None:
+        """torch's own: xavier-uniform in_proj_weight, zero in_proj_bias and out_proj.bias (nn.MultiheadAttention
+        ._reset_parameters), nn.Linear's default for out_proj.weight and for output_proj."""
+        gen, D = _generator(seed), self.obs_dim
+        views = dict(self.reference_named_views())
+        views["attention.in_proj_weight"].copy_(_uniform((3 * D, D), math.sqrt(6.0 / (4 * D)), gen))
+        views["attention.in_proj_bias"].zero_()
+        views["attention.out_proj.weight"].copy_(_uniform((D, D), 1.0 / math.sqrt(D), gen))
+        views["attention.out_proj.bias"].zero_()
+        for k in ("output_proj.weight", "output_proj.bias"):
+            views[k].copy_(_uniform(views[k].shape, 1.0 / math.sqrt(D), gen))
+
+    def _fold(self, qkv: torch.Tensor, R: int):
+        return ops.attn_pool_forward(qkv.view(R, self.n_agents, 3 * self.obs_dim), self.n_agents)
+
+    def _unfold(self, d_ctx: torch.Tensor, qkv: torch.Tensor, P: torch.Tensor) -> torch.Tensor:
+        return ops.attn_pool_backward(d_ctx, qkv.view(P.shape[0], self.n_agents, 3 * self.obs_dim), P).view(qkv.shape)
+
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        flat = self._vector(flat)
+        return (self.head.named_layers([("attention.in_proj_weight", "attention.in_proj_bias")], flat=flat[:self.n_head])
+                + self.tail.named_layers([("attention.out_proj.weight", "attention.out_proj.bias"),
+                                          ("output_proj.weight", "output_proj.bias")], flat=flat[self.n_head:]))
+
+
+def agent_pool_coefficients(n_agents: int, adjacency_matrix=None) -> np.ndarray:
+    """float64 [N]: c_m = (1 / N) sum_n A^[n][m] with A^ the row-normalised adjacency (ctde.py:323-326); None: the plain mean
+    (:329), c_m = 1 / N.  ValueError unless the adjacency is [N, N], finite, non-negative, with every row sum > 0 (the reference
+    divides by the row sum and would return inf / nan)."""
+    N = int(n_agents)
+    if adjacency_matrix is None:
+        return np.full(N, 1.0 / N, np.float64)
+    A = adjacency_matrix.detach().cpu().numpy() if isinstance(adjacency_matrix, torch.Tensor) else np.asarray(adjacency_matrix)
+    A = A.astype(np.float64)
+    if A.shape != (N, N):
+        raise ValueError(f"adjacency_matrix must be [{N}, {N}], got {list(A.shape)}")
+    if not np.isfinite(A).all() or (A < 0).any():
+        raise ValueError("adjacency_matrix must be finite and non-negative")
+    rows = A.sum(axis=1)
+    if not (rows > 0).all():
+        raise ValueError(f"adjacency_matrix: every row sum must be > 0; rows {np.nonzero(~(rows > 0))[0].tolist()} have none")
+    return (A / rows[:, None]).sum(axis=0) / N
+
+
+class GraphStateNet(_StateNet):
+    """`GlobalStateConstructor(mode="graph")` (ctde.py:277-280, 314-335): relu(gnn_layer1(obs)) per agent, neighbour aggregation
+    by the row-normalised adjacency (or the plain mean), gnn_layer2, the mean over agents -- on ONE flat f32 vector in the
+    module's `parameters()` order.  gnn_layer1 is the `FlatMLP` [D, H] `head` (its ReLU is applied by the pool kernels: a
+    `FlatMLP` ends linear), gnn_layer2 the `FlatMLP` [H, H] `tail` on the pooled rows: aggregation and mean are ONE weighted sum
+    over the agents with the coefficients `c` (`agent_pool_coefficients`), which commutes with the linear layer."""
+
+    def __init__(self, obs_dim: int, n_agents: int, hidden_dim: int = 64, adjacency_matrix=None,
+                 device: str | torch.device = "cuda", seed: int | None = None, storage: torch.Tensor | None = None) -> None:
+        super().__init__()
+        self.obs_dim, self.n_agents, self.hidden_dim = int(obs_dim), int(n_agents), int(hidden_dim)
+        if self.obs_dim < 1 or self.hidden_dim < 1 or not 1 <= self.n_agents <= ops._abi.GSTATE_MAX_AGENTS:
+            raise ValueError(f"GraphStateNet: obs_dim = {self.obs_dim}, hidden_dim = {self.hidden_dim} (both at least 1), n_agents = "
+                             f"{self.n_agents}; the HIP kernels serve 1 to {ops._abi.GSTATE_MAX_AGENTS} agents")
+        self.c64 = agent_pool_coefficients(self.n_agents, adjacency_matrix)
+        H = self.hidden_dim
+        self._build([self.obs_dim, H], "relu", [H, H], storage, device, (seed, None if seed is None else seed + 1))
+        self.c = torch.as_tensor(self.c64.astype(np.float32)).to(self.flat.device)
+
+    def _fold(self, h: torch.Tensor, R: int):
+        return ops.agent_pool_forward(h.view(R, self.n_agents, self.hidden_dim), self.c, relu=True), None
+
+    def _unfold(self, d_pool: torch.Tensor, h: torch.Tensor, kept) -> torch.Tensor:
+        h3 = h.view(-1, self.n_agents, self.hidden_dim)
+        return ops.agent_pool_backward(d_pool, self.c, self.n_agents, h_relu=h3).view(h.shape)
+
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        flat = self._vector(flat)
+        return (self.head.named_layers([("gnn_layer1.weight", "gnn_layer1.bias")], flat=flat[:self.n_head])
+                + self.tail.named_layers([("gnn_layer2.weight", "gnn_layer2.bias")], flat=flat[self.n_head:]))
+
+
 class RainbowNet(FlatNet):
     """The reference's `Net(num_atoms=N, dueling_param=(Q, V), linear_layer=NoisyLinear)` (common.py:246-369 around
     discrete.py:318-375, as test/discrete/test_rainbow.py:97-107 builds it) on ONE flat f32 vector in the module's
