@@ -340,7 +340,7 @@ class DQN(DeviceOffPolicyRows, nn.Module):
         x = to_tensor(obs, dev, torch.float32).reshape(-1, model.dims[0])
         B = x.shape[0]
         act = to_tensor(batch.act, dev, torch.int64).reshape(-1)
-        w = slab_workspace(self._ws, B, dev, slabs=model.flat.numel())
+        w = slab_workspace(self._ws, B, dev, **self._slab_widths())
         q = self._online_forward(batch, x)
         d_out, partial, returns, prio = self._head(batch, q, act, None if weight is None else
                                                    to_tensor(weight, dev, torch.float32).reshape(-1))
@@ -357,6 +357,10 @@ class DQN(DeviceOffPolicyRows, nn.Module):
 
     # What a learner with a second loss changes (FQF): its other gradient and step, the slot's size and what lands in it.
     _n_results = 2
+
+    def _slab_widths(self) -> dict:
+        """The gradient slab arrays of a batch's workspace, by name."""
+        return dict(slabs=self.policy.model.flat.numel())
 
     def _before_step(self, batch: Batch, w: dict) -> None:
         """Between the model's backward and its Adam step: nothing here."""

@@ -158,12 +158,12 @@ class FQF(QRDQN):
         batch.d_logits, batch.partial_frac = head["d_logits"], head["partial_frac"]
         return head["d_out"], head["partial"], head["returns"], head["prio"]
 
+    def _slab_widths(self) -> dict:
+        return dict(super()._slab_widths(), frac_slabs=self.policy.fraction_model.flat.numel())
+
     def _before_step(self, batch: Batch, w: dict) -> None:
         """Both gradients exist before either step; the fraction model steps first, as fqf.py:248-249."""
-        fm = self.policy.fraction_model
-        if "frac_slabs" not in w:
-            w["frac_slabs"] = torch.empty(w["n_split"], fm.flat.numel(), dtype=torch.float32, device=self.device)
-        fm.backward(batch.pop("d_logits"), w["n_split"], slabs=w["frac_slabs"])
+        self.policy.fraction_model.backward(batch.pop("d_logits"), w["n_split"], slabs=w["frac_slabs"])
         self.fraction_optim.step(w["frac_slabs"])
 
     def _finalize(self, batch: Batch, partial, B: int, h) -> None:

@@ -23,7 +23,7 @@ from torch import nn
 from .. import ops
 from ..data.batch import Batch
 from ..data.stats import TrainingStats
-from ..utils.learner import result_slot
+from ..utils.learner import result_slot, slab_workspace
 from ..utils.net import IntrinsicCuriosityModule
 from ..utils.tensor import to_tensor
 from .dqn import DeviceOffPolicyRows
@@ -99,11 +99,7 @@ class _ICMMixin:
         model = self.model
         head = model.head
         R = head["mse"].numel()
-        w = self._icm_ws.get(R)
-        if w is None:
-            n_split = ops.mlp_n_split(R)
-            w = self._icm_ws[R] = dict(n_split=n_split, slabs=torch.empty(n_split, model.flat.numel(), dtype=torch.float32,
-                                                                          device=model.flat.device))
+        w = slab_workspace(self._icm_ws, R, model.flat.device, slabs=model.flat.numel())
         model.backward(w["n_split"], slabs=w["slabs"])
         self.optim.step(w["slabs"])
         slot = result_slot(w, 2)

@@ -6,6 +6,7 @@ kernels through `_abi.call` on torch's current stream.  Nothing here computes on
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import torch
@@ -18,6 +19,70 @@ def _chk(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
     if t.dtype != dtype:
         raise ValueError(f"{name}: expected dtype {dtype}, got {t.dtype}")
     return t.contiguous()
+
+
+def _dev_only(name: str, *tensors) -> None:
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{name} needs device (HIP) tensors; there is no CPU path")
+
+
+def _out(name: str, out, shape, dtype, device, what: str = "out", size: str = "shape"):
+    """The tensor a launch writes (`_chk` is for inputs: its copy of a strided `out` would take the result and the caller's
+    tensor stay as it was).  None: a fresh `shape` of `dtype`.  Else `out` ITSELF, which must be a contiguous device tensor of
+    `dtype` and, by `size`, "shape": of exactly `shape`; "numel": of any shape with as many entries; "min": with at least as many
+    (the floor of memory safety, for buffers the caller slices from something larger)."""
+    if out is None:
+        return torch.empty(tuple(shape), dtype=dtype, device=device)
+    n = math.prod(shape)
+    fits = tuple(out.shape) == tuple(shape) if size == "shape" else out.numel() == n if size == "numel" else out.numel() >= n
+    if out.dtype != dtype or not fits or not out.is_contiguous():
+        want = list(shape) if size == "shape" else f"{'at least ' if size == 'min' else ''}{n} entries"
+        raise ValueError(f"{name}: {what} must be {want}, contiguous {dtype}; got {list(out.shape)} {out.dtype}, strides "
+                         f"{tuple(out.stride())}")
+    _dev_only(name, out)
+    return out
+
+
+def _out_or_pinned(name: str, out, n: int, what: str = "out") -> int:
+    """The address of a result of at least n f32 that the host reads: a device tensor, or pinned host memory (mapped: the kernel
+    writes it directly, no D2H copy)."""
+    if not (out.is_cuda or out.is_pinned()):
+        raise RuntimeError(f"{name} needs device (HIP) tensors; there is no CPU path ({what} must be a device tensor or pinned "
+                           f"host memory)")
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < n:
+        raise ValueError(f"{name}: {what} must be at least {n} contiguous f32")
+    return out.data_ptr()
+
+
+def _philox(name: str, seed: int, offset: int, offset_dev) -> tuple:
+    """The three counter arguments of every sampling entry: the seed and the host's offset as u64 (Python ints of either sign
+    wrap modulo 2**64) and the address of the device's offset word (None: NULL), which must live in HBM."""
+    _dev_only(name, offset_dev)
+    return seed & (2**64 - 1), offset & (2**64 - 1), ptr(offset_dev)
+
+
+def _slab_dest(name: str, slabs, n_split: int, rows: int, pitch: int, extent: int, dev) -> tuple:
+    """Where a backward's weight gradients land: slab s may be written over the floats [s * pitch, s * pitch + extent) behind
+    the first element of `slabs`, which may be a view INTO the slabs of a larger joint vector.  n_split <= 0: `mlp_n_split(rows)`;
+    slabs None: a fresh [n_split, pitch].  -> (n_split, slabs, pitch), no write of which leaves the tensor."""
+    n_split, pitch = int(n_split) if n_split > 0 else mlp_n_split(rows), int(pitch)
+    if not 1 <= n_split <= 65535:
+        raise ValueError(f"{name}: n_split {n_split} outside [1, 65535]")
+    if pitch < extent:
+        raise ValueError(f"{name}: slab_stride {pitch} smaller than the parameter count {extent}, the floats of a slab")
+    if slabs is None:
+        return n_split, torch.empty(n_split, pitch, dtype=torch.float32, device=dev), pitch
+    if slabs.dtype != torch.float32 or slabs.dim() < 1 or slabs.numel() == 0 or slabs.stride(-1) != 1:
+        raise ValueError(f"{name}: slabs must be a non-empty f32 tensor, contiguous along the parameters")
+    if slabs.dim() == 2 and n_split > slabs.shape[0]:
+        raise ValueError(f"{name}: n_split {n_split} exceeds the {slabs.shape[0]} rows of slabs")
+    reach = 1 + sum((n - 1) * st for n, st in zip(slabs.shape, slabs.stride()))
+    if (n_split - 1) * pitch + extent > reach:
+        raise ValueError(f"{name}: slabs reach {reach} floats; {n_split} slabs of {extent} floats at pitch {pitch} need "
+                         f"{(n_split - 1) * pitch + extent}")
+    _dev_only(name, slabs)
+    return n_split, slabs, pitch
 
 
 # --------------------------------------------------------------------------------------------
@@ -46,10 +111,8 @@ def gae_lanes(v_s, v_s_next, rew, terminated, truncated, gamma=0.99, gae_lambda=
         raise ValueError("gae_lanes: flag tensors must be lane-shaped or env-shaped")
     if trunc.numel() != term.numel():
         raise ValueError("gae_lanes: terminated/truncated shape mismatch")
-    if out is None:
-        ret, adv = torch.empty_like(v_s), torch.empty_like(v_s)
-    else:
-        ret, adv = out
+    ret, adv = (_out("gae_lanes", o, v_s.shape, torch.float32, v_s.device, nm, "min")
+                for o, nm in zip(out or (None, None), ("out[0]", "out[1]")))
     if rms is not None:
         call("tsm_gae_lanes_rms", ptr(v_s), ptr(v_s_next), ptr(rew), ptr(term), ptr(trunc), flags_per_lane, T, L,
              lanes_per_env, ptr(env_start), ptr(env_len), float(gamma), float(gae_lambda),
@@ -93,8 +156,8 @@ def rms_update(returns, rms, rms_eps=1e-8, ids=None, work=None):
     n = returns.numel() if ids is None else ids.numel()
     if work is None:
         work = torch.empty(call("tsm_rms_update_work_elems", n), dtype=torch.float64, device=returns.device)
-    call("tsm_rms_update", ptr(returns), ptr(ids), n, ptr(_chk(rms, torch.float64, "rms")), float(rms_eps), ptr(work),
-         stream_ptr())
+    call("tsm_rms_update", ptr(returns), ptr(ids), n, ptr(_out("rms_update", rms, (3,), torch.float64, None, "rms", "min")),
+         float(rms_eps), ptr(work), stream_ptr())
     return rms
 
 
@@ -152,13 +215,9 @@ class VrbState:
         done = done.contiguous().view(torch.uint8) if done.dtype == torch.bool else _chk(done, torch.uint8, "done")
         ids = None if buffer_ids is None else _chk(buffer_ids, torch.int64, "buffer_ids")
         dev = self.device
-        if outs is not None:
-            ptr_out, ep_rew, ep_len, ep_idx = outs
-        else:
-            ptr_out = torch.empty(R, dtype=torch.int64, device=dev)
-            ep_rew = torch.empty(R, self.rew_dim, dtype=torch.float64, device=dev)
-            ep_len = torch.empty(R, dtype=torch.int64, device=dev)
-            ep_idx = torch.empty(R, dtype=torch.int64, device=dev)
+        ptr_out, ep_rew, ep_len, ep_idx = (
+            _out("VrbState.add", o, shape, dt, dev, f"outs[{k}]", "min") for k, (o, shape, dt) in enumerate(zip(
+                outs or (None,) * 4, ((R,), (R, self.rew_dim), (R,), (R,)), (torch.int64, torch.float64, torch.int64, torch.int64))))
         farr = (tsm_field * max(1, len(fields)))()
         keep = []
         for i, (src, dst) in enumerate(fields):
@@ -255,12 +314,11 @@ def categorical_sample(logits, seed: int, offset: int = 0, deterministic: bool =
     """Categorical(logits).sample() / .mode + log-prob; `out` = optional preallocated (act i32[B], logp f32[B])."""
     logits = _chk(logits, torch.float32, "logits")
     B, A = logits.shape
-    if out is not None:
-        act, logp = out
-    else:
-        act = torch.empty(B, dtype=torch.int32, device=logits.device)
-        logp = torch.empty(B, dtype=torch.float32, device=logits.device) if want_logp else None
-    call("tsm_categorical_sample", ptr(logits), B, A, seed & (2**64 - 1), offset & (2**64 - 1), ptr(offset_dev),
+    act, logp = out if out is not None else (None, None)
+    act = _out("categorical_sample", act, (B,), torch.int32, logits.device, "act", "min")
+    if logp is not None or (out is None and want_logp):
+        logp = _out("categorical_sample", logp, (B,), torch.float32, logits.device, "logp", "min")
+    call("tsm_categorical_sample", ptr(logits), B, A, *_philox("categorical_sample", seed, offset, offset_dev),
          int(deterministic), ptr(act), ptr(logp), stream_ptr())
     return act, logp
 
@@ -295,7 +353,7 @@ def ppo_adv_stats(adv, mb_start, perm=None, out=None, max_rows: int = 0, work=No
     adv = _chk(adv, torch.float32, "adv").reshape(-1)
     mb_start = _chk(mb_start, torch.int64, "mb_start")
     n_mb = mb_start.numel() - 1
-    stats = out if out is not None else torch.empty(n_mb, 2, dtype=torch.float32, device=adv.device)
+    stats = _out("ppo_adv_stats", out, (n_mb, 2), torch.float32, adv.device, size="min")
     if max_rows > 8192:
         if work is None:
             work = torch.empty(call("tsm_ppo_adv_stats_work_elems", n_mb, max_rows), dtype=torch.float64, device=adv.device)
@@ -349,11 +407,7 @@ def ppo_pack_minibatches(ws: dict, adv, mb_start, perm, obs, act, logp_old, retu
             raise ValueError(f"ppo_pack_minibatches: {name} holds {t.numel()} values for {n} rows of obs")
     if perm is not None and _chk(perm, torch.int64, "perm").numel() < sum(ws["sizes"]):
         raise ValueError(f"ppo_pack_minibatches: perm holds {perm.numel()} row ids, the minibatches {sum(ws['sizes'])}")
-    st = None
-    if stats:
-        st = out if out is not None else torch.empty(n_mb, 2, dtype=torch.float32, device=adv.device)
-        if st.numel() < 2 * n_mb:
-            raise ValueError(f"ppo_pack_minibatches: out holds {st.numel()} values, {n_mb} minibatches need {2 * n_mb}")
+    st = _out("ppo_pack_minibatches", out, (n_mb, 2), torch.float32, adv.device, size="min") if stats else None
     call("tsm_ppo_pack_minibatches", ptr(adv), ptr(perm), ptr(mb_start), n_mb, ws["max_rows"], ptr(st), ptr(obs), ws["obs_dim"],
          ptr(_chk(act, torch.int32, "act")), ptr(_chk(logp_old, torch.float32, "logp_old")), ptr(returns), ptr(v_old),
          ptr(ws["tile_start"]), ptr(ws["packed"]), stream_ptr())
@@ -368,18 +422,16 @@ def ppo_adv_stats_pack(stats, mb_start, out=None):
     n_mb = mb_start.numel() - 1
     if stats.shape[0] != n_mb:
         raise ValueError(f"ppo_adv_stats_pack: {stats.shape[0]} statistics rows for {n_mb} minibatches")
-    pack = out if out is not None else torch.empty(n_mb, 3, dtype=torch.float64, device=stats.device)
-    call("tsm_ppo_adv_stats_pack", ptr(stats), ptr(mb_start), n_mb, ptr(_chk(pack, torch.float64, "pack")), stream_ptr())
+    pack = _out("ppo_adv_stats_pack", out, (n_mb, 3), torch.float64, stats.device, size="min")
+    call("tsm_ppo_adv_stats_pack", ptr(stats), ptr(mb_start), n_mb, ptr(pack), stream_ptr())
     return pack
 
 
 def ppo_adv_stats_unpack(pack, stats):
     """Summed (n, sum x, sum x^2) -> (mean, unbiased std) of the union, written into `stats` [n_mb, 2] f32 in place."""
     pack = _chk(pack, torch.float64, "pack").reshape(-1, 3)
-    st = _chk(stats, torch.float32, "stats")
-    if st.numel() != 2 * pack.shape[0]:
-        raise ValueError("ppo_adv_stats_unpack: stats and pack disagree on the number of minibatches")
-    call("tsm_ppo_adv_stats_unpack", ptr(pack), pack.shape[0], ptr(st), stream_ptr())
+    _out("ppo_adv_stats_unpack", stats, (pack.shape[0], 2), torch.float32, None, "stats", "numel")
+    call("tsm_ppo_adv_stats_unpack", ptr(pack), pack.shape[0], ptr(stats), stream_ptr())
     return stats
 
 
@@ -465,10 +517,8 @@ def critic_w1_image(w0_flat, in_dim: int, out=None):
     n = call("tsm_critic_rows_w1_image_elems", in_dim)
     if n < 0:
         raise ValueError(f"critic_w1_image: in_dim = {in_dim} is not served by the rows kernels")
-    if out is None:
-        out = torch.empty(n, dtype=torch.float32, device=w0_flat.device)
-    call("tsm_critic_rows_w1_image", ptr(_chk(w0_flat, torch.float32, "w0")), in_dim, ptr(_chk(out, torch.float32, "out")),
-         stream_ptr())
+    out = _out("critic_w1_image", out, (n,), torch.float32, w0_flat.device, size="min")
+    call("tsm_critic_rows_w1_image", ptr(_chk(w0_flat, torch.float32, "w0")), in_dim, ptr(out), stream_ptr())
     return out
 
 
@@ -488,9 +538,7 @@ def adam_step_segs(param, segs, exp_avg, exp_avg_sq, step, lr=1e-3, betas=(0.9, 
 
 def reduce_slabs_segs(segs, n: int, out=None, scale: float = 1.0):
     """Flat gradient [n] = scale * per-segment slab sums (see adam_step_segs); one launch."""
-    dev = segs[0][0].device
-    if out is None:
-        out = torch.empty(n, dtype=torch.float32, device=dev)
+    out = _out("reduce_slabs_segs", out, (n,), torch.float32, segs[0][0].device, size="min")
     call("tsm_reduce_slabs_segs", _slab_segs(segs, n), len(segs), n, float(scale), ptr(out), stream_ptr())
     return out
 
@@ -499,8 +547,7 @@ def reduce_slabs(grad_slabs, out=None, scale: float = 1.0):
     """Flat gradient = scale * sum of per-workgroup slabs [n_slab, n] (deterministic slab order)."""
     grad_slabs = _chk(grad_slabs, torch.float32, "grad_slabs")
     n_slab, n = grad_slabs.shape
-    if out is None:
-        out = torch.empty(n, dtype=torch.float32, device=grad_slabs.device)
+    out = _out("reduce_slabs", out, (n,), torch.float32, grad_slabs.device, size="min")
     call("tsm_reduce_slabs", ptr(grad_slabs), n_slab, n, float(scale), ptr(out), stream_ptr())
     return out
 
@@ -526,21 +573,17 @@ def policy_forward(params, obs, n_act: int, hidden: int = 64, mode: str = "none"
     B, D = obs.shape
     dev = obs.device
     m = POLICY_MODES[mode]
-    if out is not None:  # preallocated outputs (graph capture): dict(logits, value, act, logp), entries may be None
-        logits, value, logp = out.get("logits"), out.get("value"), out.get("logp")
-        act = out.get("act") if m != 3 else _chk(act, torch.int32, "act")
-    else:
-        logits = torch.empty(B, n_act, dtype=torch.float32, device=dev) if want_logits else None
-        value = torch.empty(B, dtype=torch.float32, device=dev) if want_value else None
-        if m == 3:
-            act = _chk(act, torch.int32, "act")
-        elif m != 0:
-            act = torch.empty(B, dtype=torch.int32, device=dev)
-        logp = torch.empty(B, dtype=torch.float32, device=dev) if (want_logp and m != 0) else None
+    # preallocated outputs (graph capture): out = dict(logits, value, act, logp), entries may be None (not wanted)
+    want = dict(logits=want_logits, value=want_value, act=m in (1, 2), logp=want_logp and m != 0) if out is None else \
+        {k: out.get(k) is not None for k in ("logits", "value", "act", "logp")}
+    res = {k: _out("policy_forward", (out or {}).get(k), (B, n_act) if k == "logits" else (B,),
+                   torch.int32 if k == "act" else torch.float32, dev, k, "min") if want[k] else None for k in want}
+    if m == 3:
+        res["act"] = _chk(act, torch.int32, "act")
     call("tsm_policy_forward", ptr(_chk(params, torch.float32, "params")), ptr(image), D, hidden, n_act, ptr(obs), B, m,
-         seed & (2**64 - 1), offset & (2**64 - 1), ptr(offset_dev), ptr(logits), ptr(value), ptr(act), ptr(logp),
-         stream_ptr())
-    return dict(logits=logits, value=value, act=act, logp=logp)
+         *_philox("policy_forward", seed, offset, offset_dev), ptr(res["logits"]), ptr(res["value"]), ptr(res["act"]),
+         ptr(res["logp"]), stream_ptr())
+    return res
 
 
 def policy_image(obs_dim: int, hidden: int, n_act: int, device):
@@ -566,14 +609,9 @@ def scatter_image(params, image, image_map):
 def ppo_finalize_many(partial, stride_elems: int, n_blocks_dev, M_dev, cfg: tsm_ppo_cfg, scalars_out):
     """scalars_out[k] = {loss, clip, vf, ent} of gradient step k from its loss partials (one launch for all k).
     scalars_out may be a pinned host tensor (mapped memory: the kernel writes it directly, no D2H copy)."""
-    if scalars_out.is_cuda:
-        out_p = ptr(scalars_out)
-    elif scalars_out.is_pinned() and scalars_out.is_contiguous() and scalars_out.dtype == torch.float32:
-        out_p = scalars_out.data_ptr()
-    else:
-        raise RuntimeError("ppo_finalize_many: scalars_out must be a device tensor or pinned host memory (f32)")
     call("tsm_ppo_finalize_many", ptr(partial), stride_elems, ptr(_chk(n_blocks_dev, torch.int32, "n_blocks")),
-         ptr(_chk(M_dev, torch.int64, "M")), scalars_out.shape[0], C.byref(cfg), out_p, stream_ptr())
+         ptr(_chk(M_dev, torch.int64, "M")), scalars_out.shape[0], C.byref(cfg),
+         _out_or_pinned("ppo_finalize_many", scalars_out, 4 * scalars_out.shape[0], "scalars_out"), stream_ptr())
     return scalars_out
 
 
@@ -597,18 +635,11 @@ def ppo_update_fused(params, obs, act, logp_old, adv, returns, cfg: tsm_ppo_cfg,
         n_blocks = ppo_update_grid(M)
     P = params.numel()
     dev = obs.device
-    if slabs is None:
-        slabs = torch.empty(n_blocks, P, dtype=torch.float32, device=dev)
-    elif slabs.numel() < n_blocks * P:  # the kernel writes n_blocks slabs of P floats: never launch into a smaller buffer
-        raise ValueError(f"ppo_update_fused: slabs holds {slabs.numel()} floats, {n_blocks} slabs of {P} need {n_blocks * P}")
-    if partial is None:
-        partial = torch.empty(n_blocks * 4, dtype=torch.float64, device=dev)
-    elif partial.numel() < n_blocks * 4:
-        raise ValueError(f"ppo_update_fused: partial holds {partial.numel()} values, {n_blocks} workgroups need {n_blocks * 4}")
+    slabs, partial = _rows_slabs("ppo_update_fused", n_blocks, P, dev, slabs, partial)
     if perm is not None and perm.numel() < M:
         raise ValueError(f"ppo_update_fused: perm holds {perm.numel()} row ids, M = {M}")
-    if scalars is None and want_scalars:
-        scalars = torch.empty(4, dtype=torch.float32, device=dev)
+    if scalars is not None or want_scalars:
+        scalars = _out("ppo_update_fused", scalars, (4,), torch.float32, dev, "scalars", "min")
     args = (ptr(_chk(params, torch.float32, "params")), ptr(image), D, hidden, n_act, ptr(obs),
             ptr(_chk(act, torch.int32, "act")), ptr(_chk(logp_old, torch.float32, "logp_old")),
             ptr(_chk(adv, torch.float32, "adv")), ptr(_chk(returns, torch.float32, "returns")), ptr(v_s_old),
@@ -651,15 +682,9 @@ def _rows_ids(name: str, ids_name: str, ids, count_name: str, count, first_row: 
 def _rows_slabs(name: str, n_blocks: int, P: int, dev, slabs=None, partial=None):
     """(grad slabs f32 [n_blocks, P], loss partials f64 [n_blocks * 4]) of a gradient step: the caller's, if they are large
     enough, else new ones.  P = 0: the partials alone (the slabs live in the step's workspace)."""
-    if slabs is None and P:
-        slabs = torch.empty(n_blocks, P, dtype=torch.float32, device=dev)
-    elif P and slabs.numel() < n_blocks * P:
-        raise ValueError(f"{name}: slabs holds {slabs.numel()} floats, {n_blocks} slabs of {P} need {n_blocks * P}")
-    if partial is None:
-        partial = torch.empty(n_blocks * 4, dtype=torch.float64, device=dev)
-    elif partial.numel() < n_blocks * 4:
-        raise ValueError(f"{name}: partial is too small ({partial.numel()} doubles, {n_blocks} workgroups need {n_blocks * 4})")
-    return slabs, partial
+    if P:  # the kernel writes n_blocks slabs of P floats: never launch into a smaller buffer
+        slabs = _out(name, slabs, (n_blocks, P), torch.float32, dev, "slabs", "min")
+    return slabs, _out(name, partial, (n_blocks * 4,), torch.float64, dev, "partial", "min")
 
 
 def ppo_actor_rows_supported(obs_dim: int, hidden_sizes, n_act: int, act: str = "relu") -> bool:
@@ -777,10 +802,7 @@ def critic_rows_forward(critic_params, obs_rows, hidden: int = 128, rows=None, f
     if critic_params.numel() != _mlp3_param_count(K1, hidden, n_out):
         raise ValueError(f"critic_rows_forward: {critic_params.numel()} parameters do not match {K1} -> {hidden} -> {hidden} -> {n_out}")
     _critic_rows_init(K1, hidden)
-    if out is None:
-        out = torch.empty(Mr, dtype=torch.float32, device=obs_rows.device)
-    elif out.numel() < Mr:
-        raise ValueError("critic_rows_forward: out is too small")
+    out = _out("critic_rows_forward", out, (Mr,), torch.float32, obs_rows.device, size="min")
     call("tsm_critic_rows_forward", ptr(_chk(critic_params, torch.float32, "critic_params")), K1, hidden, n_out, ptr(obs_rows),
          ptr(rows), first_row, Mr,
          ptr(None if run_if is None else _chk(run_if, torch.int32, "run_if")), ptr(out), stream_ptr())
@@ -824,7 +846,7 @@ def _side_reductions(side):
         raise ValueError("at most two side reductions ride on the dW1 launch")
     arr = (_abi.tsm_slab_reduce * len(side))()
     for k, (sl, out) in enumerate(side):
-        sl, out = _chk(sl, torch.float32, "side slabs"), _chk(out, torch.float32, "side out")
+        sl, out = _chk(sl, torch.float32, "side slabs"), _out("side reduction", out, out.shape, torch.float32, None)
         if sl.dim() != 2 or out.numel() > sl.shape[1]:
             raise ValueError("side reduction: slabs [n_slab, >= n] and out [n] expected")
         arr[k] = _abi.tsm_slab_reduce(ptr(sl), out.numel(), int(sl.shape[1]), int(sl.shape[0]), 0, ptr(out))
@@ -906,15 +928,9 @@ def critic_rows_grad_td(critic_params, joint_store, T: int, E: int, rew, termina
 def ctde_finalize(critic_partial, nb_c: int, actor_partial, nb_a: int, B: int, scalars_out, mean_adv_out):
     """{actor_loss, critic_loss} and mean(advantage) of CTDEPolicy.learn from the kernels' partial sums (one launch).
     scalars_out: device f32[2] or pinned host f32[2]; mean_adv_out: device f32[1]."""
-    if scalars_out.is_cuda:
-        out_p = ptr(scalars_out)
-    elif scalars_out.is_pinned() and scalars_out.is_contiguous() and scalars_out.dtype == torch.float32:
-        out_p = scalars_out.data_ptr()
-    else:
-        raise RuntimeError("ctde_finalize: scalars_out must be a device tensor or pinned host memory (f32)")
     call("tsm_ctde_finalize", ptr(_chk(critic_partial, torch.float64, "critic_partial")), nb_c,
-         ptr(_chk(actor_partial, torch.float64, "actor_partial")), nb_a, B, out_p,
-         ptr(_chk(mean_adv_out, torch.float32, "mean_adv_out")), stream_ptr())
+         ptr(_chk(actor_partial, torch.float64, "actor_partial")), nb_a, B, _out_or_pinned("ctde_finalize", scalars_out, 2, "scalars_out"),
+         ptr(_out("ctde_finalize", mean_adv_out, (1,), torch.float32, None, "mean_adv_out", "min")), stream_ptr())
     return scalars_out
 
 
@@ -929,11 +945,7 @@ def ppo_value_loss(value, returns, cfg: tsm_ppo_cfg, M: int, v_s_old=None, perm=
         raise ValueError("ppo_value_loss needs a cfg with loss_kind = 2")
     dev = value.device
     dvalue = torch.empty(value.numel(), dtype=torch.float32, device=dev)
-    n_part = call("tsm_ppo_loss_partial_elems", M)
-    if partial is None:
-        partial = torch.empty(n_part, dtype=torch.float64, device=dev)
-    elif partial.numel() < n_part:
-        raise ValueError("ppo_value_loss: partial is too small")
+    partial = _out("ppo_value_loss", partial, (call("tsm_ppo_loss_partial_elems", M),), torch.float64, dev, "partial", "min")
     call("tsm_ppo_loss_fwd_bwd", None, ptr(value), None, None, None, ptr(_chk(returns, torch.float32, "returns")),
          ptr(v_s_old), ptr(perm), first_row, M, 1, None, C.byref(cfg), None, ptr(dvalue), ptr(partial), stream_ptr())
     return dvalue, partial
@@ -967,19 +979,16 @@ def random_permutations(n: int, n_perm: int, seed: int, counter: int = 0, counte
     *counter_dev once every workgroup has read it -- the draws of counter = 0 followed by tsm_u64_add, in one launch."""
     if n < 0 or n_perm < 0:
         raise ValueError("random_permutations: negative size")
-    if out is None:
-        out = torch.empty(n_perm, n, dtype=torch.int64, device=device)
-    if out.numel() != n_perm * n:
-        raise ValueError("random_permutations: out has the wrong size")
+    out = _out("random_permutations", out, (n_perm, n), torch.int64, device, size="numel")
+    seed, counter, ctr_p = _philox("random_permutations", seed, counter, counter_dev)
     if advance:
         if counter or counter_dev is None or done_ctr is None:
             raise ValueError("random_permutations: advance needs counter_dev and done_ctr, and no host counter")
-        call("tsm_random_permutations_advance", n, n_perm, seed & (2**64 - 1), ptr(counter_dev), int(advance),
-             ptr(_chk(done_ctr, torch.int32, "done_ctr")), scale, group_size, offset_mul, ptr(_chk(out, torch.int64, "out")),
-             stream_ptr())
+        call("tsm_random_permutations_advance", n, n_perm, seed, ctr_p, int(advance),
+             ptr(_out("random_permutations", done_ctr, (1,), torch.int32, None, "done_ctr", "min")), scale, group_size, offset_mul,
+             ptr(out), stream_ptr())
         return out
-    call("tsm_random_permutations", n, n_perm, seed & (2**64 - 1), counter & (2**64 - 1), ptr(counter_dev), scale,
-         group_size, offset_mul, ptr(_chk(out, torch.int64, "out")), stream_ptr())
+    call("tsm_random_permutations", n, n_perm, seed, counter, ctr_p, scale, group_size, offset_mul, ptr(out), stream_ptr())
     return out
 
 
@@ -1149,37 +1158,30 @@ def qmix_mix_td(q, q_next, act, rew, hyper, hyper_next, term, gamma: float, mono
     if term.numel() != B:
         raise ValueError(f"qmix_mix_td: term must have {B} entries")
     dev = q[0].device
-    if out is None:
-        dq = [torch.empty(B, A, dtype=torch.float32, device=dev) for _ in range(N)]
-        grads = tuple(torch.empty(B, w, dtype=torch.float32, device=dev) for w in (N * E, E, E, 1))
-        partial = torch.empty(qmix_partial_elems(B, E), dtype=torch.float64, device=dev)
-    else:
-        dq, grads, partial = out
+    dq, grads, partial = out if out is not None else ([None] * N, (None,) * 4, None)
+    dq = [_out("qmix_mix_td", x, (B, A), torch.float32, dev, "dq", "min") for x in dq]
+    grads = tuple(_out("qmix_mix_td", x, (B, w), torch.float32, dev, "grad", "min") for x, w in zip(grads, (N * E, E, E, 1)))
+    partial = _out("qmix_mix_td", partial, (qmix_partial_elems(B, E),), torch.float64, dev, "partial", "min")
+    if qtot_out is not None:
+        _out("qmix_mix_td", qtot_out, (B,), torch.float32, dev, "qtot_out", "min")
     ag = _abi.tsm_qmix_agents()
     for k in range(N):
         ag.q[k] = ptr(_chk(q[k], torch.float32, "q"))
         ag.q_next[k] = ptr(_chk(q_next[k], torch.float32, "q_next"))
         ag.act[k] = ptr(_chk(act[k], torch.int64, "act"))
         ag.rew[k] = ptr(_chk(rew[k], torch.float32, "rew"))
-        ag.dq[k] = ptr(_chk(dq[k], torch.float32, "dq"))
+        ag.dq[k] = ptr(dq[k])
     hp = [ptr(_chk(x, torch.float32, "hyper")) for x in (*hyper, *hyper_next)]
     call("tsm_qmix_mix_td", C.byref(ag), N, A, B, E, *hp, ptr(term), float(gamma), int(bool(monotonic)),
-         *(ptr(_chk(x, torch.float32, "grad")) for x in grads), ptr(_chk(partial, torch.float64, "partial")),
-         ptr(None if qtot_out is None else _chk(qtot_out, torch.float32, "qtot_out")), stream_ptr())
+         *map(ptr, grads), ptr(partial), ptr(qtot_out), stream_ptr())
     return dq, grads, partial
 
 
 def qmix_finalize(partial, B: int, out):
     """{loss, q_values} of QMIXPolicy.learn from tsm_qmix_mix_td's partials (one launch).  out: device f32[2] or pinned
     host f32[2]."""
-    if out.is_cuda:
-        out_p = ptr(out)
-    elif out.is_pinned() and out.is_contiguous() and out.dtype == torch.float32:
-        out_p = out.data_ptr()
-    else:
-        raise RuntimeError("qmix_finalize: out must be a device tensor or pinned host memory (f32)")
     partial = _chk(partial, torch.float64, "partial")
-    call("tsm_qmix_finalize", ptr(partial), partial.numel() // 2, B, out_p, stream_ptr())
+    call("tsm_qmix_finalize", ptr(partial), partial.numel() // 2, B, _out_or_pinned("qmix_finalize", out, 2), stream_ptr())
     return out
 
 
@@ -1192,23 +1194,16 @@ def qmix_egreedy(q, eps_dev, seed: int, offset: int = 0, offset_dev=None, out=No
     stride = N if row_stride is None else int(row_stride)
     if out is None:
         out = torch.empty(B, stride, dtype=torch.int32, device=q[0].device)
-    if out.numel() < (B - 1) * stride + N if B else False:
-        raise ValueError("qmix_egreedy: out is too small")
+    _out("qmix_egreedy", out, ((B - 1) * stride + N if B else 0,), torch.int32, None, size="min")  # the last row's window ends there
     arr = (C.c_void_p * N)(*[ptr(_chk(x, torch.float32, "q")) for x in q])
-    call("tsm_qmix_egreedy", arr, N, B, A, ptr(_chk(eps_dev, torch.float32, "eps_dev")), seed & (2**64 - 1),
-         offset & (2**64 - 1), ptr(offset_dev), ptr(_chk(out, torch.int32, "out")), stride, stream_ptr())
+    call("tsm_qmix_egreedy", arr, N, B, A, ptr(_chk(eps_dev, torch.float32, "eps_dev")),
+         *_philox("qmix_egreedy", seed, offset, offset_dev), ptr(out), stride, stream_ptr())
     return out
 
 
 # --------------------------------------------------------------------------------------------
 # n-step targets and DQN (algorithm_base.py:720-815; dqn.py; csrc/nstep.hip, csrc/dqn.hip)
 # --------------------------------------------------------------------------------------------
-def _dev_only(name: str, *tensors) -> None:
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f"{name} needs device (HIP) tensors; there is no CPU path")
-
-
 def _head_args(name: str, B: int, shaped: tuple, per_row: tuple, note: str = "") -> list:
     """The host checks every value-based head shares.  Each (nm, x, shape, dtype) of `shaped` must have that shape, each
     (nm, x, dtype) of `per_row` B entries; None is an argument left out.  dtype uint8 also takes bool, viewed as bytes.
@@ -1299,19 +1294,16 @@ def dqn_td_head(q, q_next_online, q_next_target, act, mc, gpow, vmask, mask_next
 def dqn_egreedy(q, eps_dev, seed: int, offset: int = 0, offset_dev=None, mask=None, out=None):
     """Masked epsilon-greedy actions (dqn.py:140-141, 153-171) on the device: q [R, A], mask u8 / bool [R, A] or None ->
     act i32 [R].  One coin per ROW; eps read from the device scalar eps_dev; row r draws at Philox counter offset + r."""
-    _dev_only("dqn_egreedy", q, eps_dev, mask, out, offset_dev)
+    _dev_only("dqn_egreedy", q, eps_dev, mask)
     q = _chk(q, torch.float32, "q")
     if q.dim() != 2:
         raise ValueError("dqn_egreedy: q must be [R, A]")
     R, A = q.shape
     dqn_check(A)
     mask, = _head_args("dqn_egreedy", R, (("mask", mask, (R, A), torch.uint8),), ())
-    if out is None:
-        out = torch.empty(R, dtype=torch.int32, device=q.device)
-    elif out.numel() < R or not out.is_contiguous():
-        raise ValueError(f"dqn_egreedy: out must be a contiguous i32 tensor of at least {R} entries")
-    call("tsm_dqn_egreedy", ptr(q), ptr(mask), R, A, ptr(_chk(eps_dev, torch.float32, "eps_dev")), seed & (2**64 - 1),
-         offset & (2**64 - 1), ptr(offset_dev), ptr(_chk(out, torch.int32, "out")), stream_ptr())
+    out = _out("dqn_egreedy", out, (R,), torch.int32, q.device, size="min")
+    call("tsm_dqn_egreedy", ptr(q), ptr(mask), R, A, ptr(_chk(eps_dev, torch.float32, "eps_dev")),
+         *_philox("dqn_egreedy", seed, offset, offset_dev), ptr(out), stream_ptr())
     return out
 
 
@@ -1402,13 +1394,8 @@ def iqn_taus(R: int, sample_size: int, seed: int, device, offset: int = 0, offse
     draws at counter offset + *offset_dev + r under a key of its own.  -> taus f32 [R, sample_size] in [0, 1)."""
     R, S = int(R), int(sample_size)
     iqn_check(4, 16, S)
-    if out is None:
-        out = torch.empty(R, S, dtype=torch.float32, device=device)
-    elif tuple(out.shape) != (R, S):
-        raise ValueError(f"iqn_taus: out must be [{R}, {S}]")
-    _dev_only("iqn_taus", out, offset_dev)
-    call("tsm_iqn_taus", R, S, seed & (2**64 - 1), offset & (2**64 - 1), ptr(offset_dev), ptr(_chk(out, torch.float32, "out")),
-         stream_ptr())
+    out = _out("iqn_taus", out, (R, S), torch.float32, device)
+    call("tsm_iqn_taus", R, S, *_philox("iqn_taus", seed, offset, offset_dev), ptr(out), stream_ptr())
     return out
 
 
@@ -1441,22 +1428,15 @@ def iqn_embed_backward(d_e, f, phi, taus, We, be, n_split: int = 0, slabs=None, 
                        b_off: int | None = None, relu_f: bool = False):
     """The backward of `iqn_embed_forward` in one launch: d_e [R * S, H] -> (d_f [R, H], slabs).  dWe / dbe fill n_split
     slabs at w_off / b_off of rows `slab_stride` apart (default: slabs of their own, [n_split, H * C + H])."""
-    _dev_only("iqn_embed_backward", d_e, f, phi, taus, We, be, slabs)
+    _dev_only("iqn_embed_backward", d_e, f, phi, taus, We, be)
     R, S, C, H = _iqn_embed_shapes("iqn_embed_backward", f, taus, We, be)
     if tuple(d_e.shape) != (R * S, H) or tuple(phi.shape) != (R * S, H):
         raise ValueError(f"iqn_embed_backward: d_e and phi must be [{R * S}, {H}]")
-    if n_split <= 0:
-        n_split = mlp_n_split(R)
     if b_off is None:
         b_off = w_off + H * C
-    if slabs is None:
-        slab_stride = slab_stride or H * C + H
-        slabs = torch.empty(n_split, slab_stride, dtype=torch.float32, device=f.device)
-    elif slab_stride <= 0:
-        slab_stride = slabs.stride(0)
-    if slabs.dim() != 2 or slabs.shape[0] < n_split or slabs.stride(1) != 1 or slabs.stride(0) != slab_stride \
-            or slabs.dtype != torch.float32 or max(w_off + H * C, b_off + H) > slabs.shape[1]:
-        raise ValueError("iqn_embed_backward: slabs must be f32 [n_split, >= the end of both blocks] with rows slab_stride apart")
+    end = max(w_off + H * C, b_off + H)   # a slab is written up to the end of the later block
+    n_split, slabs, slab_stride = _slab_dest("iqn_embed_backward", slabs, n_split, R,
+                                             slab_stride if slab_stride > 0 else end if slabs is None else slabs.stride(0), end, f.device)
     d_f = torch.empty(R, H, dtype=torch.float32, device=f.device)
     call("tsm_iqn_embed_backward", ptr(_chk(d_e, torch.float32, "d_e")), ptr(_chk(f, torch.float32, "f")),
          ptr(_chk(phi, torch.float32, "phi")), ptr(_chk(taus, torch.float32, "taus")), R, S, C, H, int(bool(relu_f)), ptr(d_f), int(n_split),
@@ -1547,25 +1527,18 @@ def fqf_propose_backward(d_logits, f, n_split: int = 0, slabs=None, slab_stride:
                          b_off: int | None = None, relu_f: bool = False):
     """The backward of `fqf_propose` from d_logits [R, N] in one launch -> slabs: dWf / dbf fill n_split slabs at w_off /
     b_off of rows `slab_stride` apart (default: slabs of their own, [n_split, N * H + N])."""
-    _dev_only("fqf_propose_backward", d_logits, f, slabs)
+    _dev_only("fqf_propose_backward", d_logits, f)
     if d_logits.dim() != 2:
         raise ValueError("fqf_propose_backward: d_logits must be [R, N]")
     N = d_logits.shape[1]
     R, H = _fqf_propose_shapes("fqf_propose_backward", f, N)
     d_logits, f = _head_args("fqf_propose_backward", R, (("d_logits", d_logits, (R, N), torch.float32),
                                                          ("f", f, (R, H), torch.float32)), ())
-    if n_split <= 0:
-        n_split = mlp_n_split(R)
     if b_off is None:
         b_off = w_off + N * H
-    if slabs is None:
-        slab_stride = slab_stride or N * H + N
-        slabs = torch.empty(n_split, slab_stride, dtype=torch.float32, device=f.device)
-    elif slab_stride <= 0:
-        slab_stride = slabs.stride(0)
-    if slabs.dim() != 2 or slabs.shape[0] < n_split or slabs.stride(1) != 1 or slabs.stride(0) != slab_stride \
-            or slabs.dtype != torch.float32 or max(w_off + N * H, b_off + N) > slabs.shape[1]:
-        raise ValueError("fqf_propose_backward: slabs must be f32 [n_split, >= the end of both blocks] with rows slab_stride apart")
+    end = max(w_off + N * H, b_off + N)   # a slab is written up to the end of the later block
+    n_split, slabs, slab_stride = _slab_dest("fqf_propose_backward", slabs, n_split, R,
+                                             slab_stride if slab_stride > 0 else end if slabs is None else slabs.stride(0), end, f.device)
     call("tsm_fqf_propose_backward", ptr(d_logits), ptr(f), R, N, H, int(bool(relu_f)), int(n_split), slabs.data_ptr(),
          int(slab_stride), int(w_off), int(b_off), stream_ptr())
     return slabs
@@ -1660,21 +1633,15 @@ def noisy_sample(table, flat, seed: int, offset: int = 0, offset_dev=None):
     """NoisyLinear.sample (discrete.py:358-365) for every noisy layer of the net, in place in `flat`: slot s gets
     sign(x) sqrt(|x|), x ~ N(0, 1) from Philox at counter offset + *offset_dev under a key of its own."""
     rainbow_check(table)
-    _dev_only("noisy_sample", flat, offset_dev)
-    if flat.dtype != torch.float32 or flat.dim() != 1 or flat.numel() != table.P or not flat.is_contiguous():
-        raise ValueError(f"noisy_sample: flat must be a contiguous f32 vector of {table.P} elements (it is written in place)")
-    call("tsm_noisy_sample", C.byref(table), ptr(flat), seed & (2**64 - 1), offset & (2**64 - 1), ptr(offset_dev), stream_ptr())
+    _out("noisy_sample", flat, (table.P,), torch.float32, None, "flat")   # (written in place)
+    call("tsm_noisy_sample", C.byref(table), ptr(flat), *_philox("noisy_sample", seed, offset, offset_dev), stream_ptr())
     return flat
 
 
 def noisy_compose(table, flat, training: bool, out=None):
     """The effective parameters of every layer (discrete.py:368-373) -> eff f32 [P_eff] in `FlatMLP` layout."""
     flat = _noisy_flat("noisy_compose", table, flat)
-    if out is None:
-        out = torch.empty(table.P_eff, dtype=torch.float32, device=flat.device)
-    elif out.dtype != torch.float32 or out.dim() != 1 or out.numel() != table.P_eff or not out.is_contiguous():
-        raise ValueError(f"noisy_compose: out must be a contiguous f32 vector of {table.P_eff} elements")
-    _dev_only("noisy_compose", out)
+    out = _out("noisy_compose", out, (table.P_eff,), torch.float32, flat.device)
     call("tsm_noisy_compose", C.byref(table), ptr(flat), int(bool(training)), ptr(out), stream_ptr())
     return out
 
@@ -1683,15 +1650,12 @@ def noisy_grad(table, flat, eff_slabs, training: bool, slabs=None):
     """Gradient slabs over the effective layout [n_split, P_eff] -> slabs over the flat layout [n_split, P], slab by slab:
     d mu = d, d sigma = d * noise (zeros when not training), the noise slots +0.0."""
     flat = _noisy_flat("noisy_grad", table, flat)
-    _dev_only("noisy_grad", eff_slabs, slabs)
+    _dev_only("noisy_grad", eff_slabs)
     eff_slabs = _chk(eff_slabs, torch.float32, "eff_slabs")
     if eff_slabs.dim() != 2 or eff_slabs.shape[1] != table.P_eff or eff_slabs.shape[0] < 1:
         raise ValueError(f"noisy_grad: eff_slabs must be [n_split, {table.P_eff}]")
     n_split = eff_slabs.shape[0]
-    if slabs is None:
-        slabs = torch.empty(n_split, table.P, dtype=torch.float32, device=flat.device)
-    elif tuple(slabs.shape) != (n_split, table.P) or slabs.dtype != torch.float32 or not slabs.is_contiguous():
-        raise ValueError(f"noisy_grad: slabs must be a contiguous f32 [{n_split}, {table.P}]")
+    slabs = _out("noisy_grad", slabs, (n_split, table.P), torch.float32, flat.device, "slabs")
     call("tsm_noisy_grad", C.byref(table), ptr(flat), ptr(eff_slabs), n_split, int(bool(training)), ptr(slabs), stream_ptr())
     return slabs
 
@@ -1818,21 +1782,16 @@ def dsac_alpha_step(entropy_partial, B: int, log_alpha, exp_avg, exp_avg_sq, ste
     B rows (the mean entropy is formed from them in float64); log_alpha, exp_avg, exp_avg_sq f32 [1] and step i64 [1] in
     HBM, updated in place; alpha_dev f32 [1] <- exp(log_alpha); out f32 [2] (device or pinned host memory) <- {alpha_loss,
     the new alpha}."""
-    _dev_only("dsac_alpha_step", entropy_partial, log_alpha, exp_avg, exp_avg_sq, step, alpha_dev)
-    if out.is_cuda:
-        out_p = ptr(_chk(out, torch.float32, "out"))
-    elif out.is_pinned() and out.is_contiguous() and out.dtype == torch.float32:
-        out_p = out.data_ptr()
-    else:
-        raise RuntimeError("dsac_alpha_step needs device (HIP) tensors; there is no CPU path (out is neither in HBM nor pinned f32)")
+    _dev_only("dsac_alpha_step", entropy_partial)
+    out_p = _out_or_pinned("dsac_alpha_step", out, 2)
     entropy_partial = _chk(entropy_partial, torch.float64, "entropy_partial")
-    if out.numel() < 2 or entropy_partial.numel() < 2 or entropy_partial.numel() % 2:
-        raise ValueError("dsac_alpha_step: out must have 2 entries and entropy_partial pairs of {loss, entropy} sums")
-    call("tsm_dsac_alpha_step", ptr(entropy_partial), entropy_partial.numel() // 2, int(B),
-         ptr(_chk(log_alpha, torch.float32, "log_alpha")), ptr(_chk(exp_avg, torch.float32, "exp_avg")),
-         ptr(_chk(exp_avg_sq, torch.float32, "exp_avg_sq")), ptr(_chk(step, torch.int64, "step")), float(target_entropy), float(lr),
-         float(betas[0]), float(betas[1]), float(eps), float(weight_decay), ptr(_chk(alpha_dev, torch.float32, "alpha_dev")), out_p,
-         stream_ptr())
+    if entropy_partial.numel() < 2 or entropy_partial.numel() % 2:
+        raise ValueError("dsac_alpha_step: entropy_partial must hold pairs of {loss, entropy} sums")
+    state = [_out("dsac_alpha_step", t, (1,), dt, None, nm, "min")   # (all four updated in place, alpha_dev written)
+             for nm, t, dt in (("log_alpha", log_alpha, torch.float32), ("exp_avg", exp_avg, torch.float32),
+                               ("exp_avg_sq", exp_avg_sq, torch.float32), ("step", step, torch.int64), ("alpha_dev", alpha_dev, torch.float32))]
+    call("tsm_dsac_alpha_step", ptr(entropy_partial), entropy_partial.numel() // 2, int(B), *map(ptr, state[:4]), float(target_entropy),
+         float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), ptr(state[4]), out_p, stream_ptr())
     return out
 
 
@@ -1858,14 +1817,11 @@ def _icm_phi(name: str, phi, act):
 def icm_rows(phi, act, n_act: int, out=None):
     """The forward model's input (discrete.py:424-426) in one launch: phi [2R, F], act i64 [R]
     -> x_fwd f32 [R, F + n_act] = [phi[2r] | one_hot(act[r])]; an action outside [0, n_act) gives an all-zero one-hot."""
-    _dev_only("icm_rows", phi, act, out)
+    _dev_only("icm_rows", phi, act)
     R, F, phi, act = _icm_phi("icm_rows", phi, act)
     icm_check(F, n_act)
-    if out is None:
-        out = torch.empty(R, F + int(n_act), dtype=torch.float32, device=phi.device)
-    elif tuple(out.shape) != (R, F + int(n_act)):
-        raise ValueError(f"icm_rows: out must be [{R}, {F + int(n_act)}]")
-    call("tsm_icm_rows", ptr(phi), ptr(act), R, F, int(n_act), ptr(_chk(out, torch.float32, "out")), stream_ptr())
+    out = _out("icm_rows", out, (R, F + int(n_act)), torch.float32, phi.device)
+    call("tsm_icm_rows", ptr(phi), ptr(act), R, F, int(n_act), ptr(out), stream_ptr())
     return out
 
 
@@ -1876,7 +1832,7 @@ def icm_head(phi2_hat, phi, act_hat, act, reward_scale: float, forward_loss_weig
     float32, in place; the ids must be distinct and inside rew_io.
     -> dict(mse [R], d_phi2_hat, d_phi2_fwd [R, F], d_act_hat [R, A], partial f64): `qmix_finalize(partial, R, out)` gives
     {icm_forward_loss, icm_inverse_loss}."""
-    _dev_only("icm_head", phi2_hat, phi, act_hat, act, rew_io, ids)
+    _dev_only("icm_head", phi2_hat, phi, act_hat, act, ids)
     R, F, phi, act = _icm_phi("icm_head", phi, act)
     act_hat = _chk(act_hat, torch.float32, "act_hat")
     if act_hat.dim() != 2 or act_hat.shape[0] != R:
@@ -1890,10 +1846,8 @@ def icm_head(phi2_hat, phi, act_hat, act, reward_scale: float, forward_loss_weig
         if rew_io is None or ids.numel() != R:
             raise ValueError(f"icm_head: ids needs rew_io and must have {R} entries")
         ids = _chk(ids, torch.int64, "ids").reshape(-1)
-    if rew_io is not None:
-        rew_io = _chk(rew_io, torch.float32, "rew_io")
-        if ids is None and rew_io.numel() < R:
-            raise ValueError(f"icm_head: rew_io must have at least {R} entries")
+    if rew_io is not None:   # (written in place)
+        _out("icm_head", rew_io, (R if ids is None else 0,), torch.float32, None, "rew_io", "min")
     dev = phi.device
     out = dict(mse=torch.empty(R, dtype=torch.float32, device=dev), d_phi2_hat=torch.empty(R, F, dtype=torch.float32, device=dev),
                d_phi2_fwd=torch.empty(R, F, dtype=torch.float32, device=dev), d_act_hat=torch.empty(R, A, dtype=torch.float32, device=dev),
@@ -1908,7 +1862,7 @@ def icm_join_grad(g_fwd, g_inv, d_phi2_fwd, out=None):
     """The feature net's d_out [2R, F] in one launch: row 2r = g_fwd[r] + g_inv[r, :F], row 2r + 1 = g_inv[r, F:] + d_phi2_fwd[r]
     (float32 sums in that order).  g_fwd [R, F]: the forward model's input gradient over its first F columns; g_inv [R, 2F]: the
     inverse model's; out None: g_inv's own memory (the two share their layout)."""
-    _dev_only("icm_join_grad", g_fwd, g_inv, d_phi2_fwd, out)
+    _dev_only("icm_join_grad", g_fwd, g_inv, d_phi2_fwd)
     g_fwd, g_inv, d_phi2_fwd = (_chk(x, torch.float32, n) for x, n in ((g_fwd, "g_fwd"), (g_inv, "g_inv"), (d_phi2_fwd, "d_phi2_fwd")))
     if g_fwd.dim() != 2 or g_fwd.shape[0] < 1:
         raise ValueError("icm_join_grad: g_fwd must be [R, feature_dim]")
@@ -1916,11 +1870,8 @@ def icm_join_grad(g_fwd, g_inv, d_phi2_fwd, out=None):
     icm_check(F, 1)
     if tuple(g_inv.shape) != (R, 2 * F) or tuple(d_phi2_fwd.shape) != (R, F):
         raise ValueError(f"icm_join_grad: g_inv must be [{R}, {2 * F}] and d_phi2_fwd [{R}, {F}]")
-    if out is None:
-        out = g_inv.view(2 * R, F)
-    elif out.numel() != 2 * R * F:
-        raise ValueError(f"icm_join_grad: out must be [{2 * R}, {F}]")
-    call("tsm_icm_join_grad", ptr(g_fwd), ptr(g_inv), ptr(d_phi2_fwd), R, F, ptr(_chk(out, torch.float32, "out")), stream_ptr())
+    out = g_inv if out is None else _out("icm_join_grad", out, (2 * R, F), torch.float32, None, size="numel")
+    call("tsm_icm_join_grad", ptr(g_fwd), ptr(g_inv), ptr(d_phi2_fwd), R, F, ptr(out), stream_ptr())
     return out.view(2 * R, F)
 
 
@@ -1944,18 +1895,15 @@ def gail_draw(valid, n_valid: int, n_agent: int, R: int, seed: int, counter: int
     """`expert_buffer.sample(R)` (gail.py:227) as pair ids, uniform with replacement, in one launch: draw i is Philox word 0 at
     counter + *counter_dev + i under the key seed ^ kGailKey, j = (w0 n_valid n_agent) >> 32,
     -> i64 [R]: (valid[j // n_agent] or j // n_agent) * n_agent + j % n_agent.  valid: i64 [n_valid] store rows, or None."""
-    _dev_only("gail_draw", valid, counter_dev, out)
+    _dev_only("gail_draw", valid)
     if valid is not None:
         valid = _chk(valid, torch.int64, "valid").reshape(-1)
         if valid.numel() != int(n_valid):
             raise ValueError(f"gail_draw: valid must have {int(n_valid)} entries")
         device = valid.device
-    if out is None:
-        out = torch.empty(max(int(R), 0), dtype=torch.int64, device=device)
-    elif out.numel() != int(R):
-        raise ValueError(f"gail_draw: out must have {int(R)} entries")
-    call("tsm_gail_draw", ptr(valid), int(n_valid), int(n_agent), int(R), seed & (2**64 - 1), counter & (2**64 - 1),
-         ptr(counter_dev), ptr(_chk(out, torch.int64, "out")), stream_ptr())
+    out = _out("gail_draw", out, (max(int(R), 0),), torch.int64, device, size="numel")
+    call("tsm_gail_draw", ptr(valid), int(n_valid), int(n_agent), int(R), *_philox("gail_draw", seed, counter, counter_dev), ptr(out),
+         stream_ptr())
     return out
 
 
@@ -1963,7 +1911,7 @@ def gail_rows(obs, act, n_act: int, ids=None, R: int | None = None, out=None):
     """The discriminator's input (gail.py:208-212, one-hot actions) in one launch.  obs f32 [.., D] and act i32 [..]: the
     buffer's stores, read in place as [P, D] and [P]; ids i64 [R] or None (the first R pairs, R = P by default)
     -> out f32 [R, D + n_act] = [obs[p] | one_hot(act[p])]; `out` may be R rows of a taller matrix.  The ids must lie in [0, P)."""
-    _dev_only("gail_rows", obs, act, ids, out)
+    _dev_only("gail_rows", obs, act, ids)
     obs, act = _chk(obs, torch.float32, "obs"), _chk(act, torch.int32, "act")
     D = obs.shape[-1] if obs.dim() >= 1 else 0
     P = act.numel()
@@ -1974,24 +1922,19 @@ def gail_rows(obs, act, n_act: int, ids=None, R: int | None = None, out=None):
     R = int(R if R is not None else (ids.numel() if ids is not None else P))
     if ids is None and R > P:
         raise ValueError(f"gail_rows: R = {R} rows asked of {P} pairs")
-    if out is None:
-        out = torch.empty(R, D + int(n_act), dtype=torch.float32, device=obs.device)
-    elif tuple(out.shape) != (R, D + int(n_act)):
-        raise ValueError(f"gail_rows: out must be [{R}, {D + int(n_act)}]")
-    call("tsm_gail_rows", ptr(obs), ptr(act), ptr(ids), R, D, int(n_act), ptr(_chk(out, torch.float32, "out")), stream_ptr())
+    out = _out("gail_rows", out, (R, D + int(n_act)), torch.float32, obs.device)
+    call("tsm_gail_rows", ptr(obs), ptr(act), ptr(ids), R, D, int(n_act), ptr(out), stream_ptr())
     return out
 
 
 def gail_reward(logits, rew_io, ids=None):
     """`batch.rew = -F.logsigmoid(-disc(batch))` (gail.py:204-205) in place: rew_io.view(-1)[ids[r] or r] = softplus(logits[r]),
     an overwrite.  The ids must be distinct and inside rew_io."""
-    _dev_only("gail_reward", logits, rew_io, ids)
+    _dev_only("gail_reward", logits, ids)
     logits = _chk(logits, torch.float32, "logits").reshape(-1)
     R = logits.numel()
     ids = _gail_ids("gail_reward", ids, R)
-    rew_io = _chk(rew_io, torch.float32, "rew_io")
-    if ids is None and rew_io.numel() < R:
-        raise ValueError(f"gail_reward: rew_io must have at least {R} entries")
+    _out("gail_reward", rew_io, (R if ids is None else 0,), torch.float32, None, "rew_io", "min")   # (written in place)
     call("tsm_gail_reward", ptr(logits), ptr(ids), R, ptr(rew_io), stream_ptr())
     return rew_io
 
@@ -1999,21 +1942,14 @@ def gail_reward(logits, rew_io, ids=None):
 def gail_head(logits, Rp: int, d_logits=None, partial=None):
     """The discriminator loss's row-wise head in one launch (include/tsmarl.h: tsm_gail_head).  logits f32 [Rp + Re]: the policy
     rows, then the expert rows -> dict(d_logits f32 [Rp + Re], partial f64 [4 * blocks]) for `gail_finalize`."""
-    _dev_only("gail_head", logits, d_logits, partial)
+    _dev_only("gail_head", logits)
     logits = _chk(logits, torch.float32, "logits").reshape(-1)
     n = logits.numel()
     Rp, Re = int(Rp), n - int(Rp)
     nb = max(-(-n // _abi.GAIL_ROWS_PER_BLOCK), 1)
-    if d_logits is None:
-        d_logits = torch.empty(n, dtype=torch.float32, device=logits.device)
-    elif d_logits.numel() != n:
-        raise ValueError(f"gail_head: d_logits must have {n} entries")
-    if partial is None:
-        partial = torch.empty(4 * nb, dtype=torch.float64, device=logits.device)
-    elif partial.numel() != 4 * nb:
-        raise ValueError(f"gail_head: partial must have {4 * nb} entries")
-    call("tsm_gail_head", ptr(logits), Rp, Re, ptr(_chk(d_logits, torch.float32, "d_logits")),
-         ptr(_chk(partial, torch.float64, "partial")), stream_ptr())
+    d_logits = _out("gail_head", d_logits, (n,), torch.float32, logits.device, "d_logits", "numel")
+    partial = _out("gail_head", partial, (4 * nb,), torch.float64, logits.device, "partial", "numel")
+    call("tsm_gail_head", ptr(logits), Rp, Re, ptr(d_logits), ptr(partial), stream_ptr())
     return dict(d_logits=d_logits, partial=partial)
 
 
@@ -2024,15 +1960,9 @@ def gail_finalize(partial, Rp: int, Re: int, out=None):
     partial = _chk(partial, torch.float64, "partial").reshape(-1)
     if out is None:
         out = torch.empty(3, dtype=torch.float32, device=partial.device)
-    if out.numel() != 3 or out.dtype != torch.float32 or not out.is_contiguous():
+    if out.numel() != 3:
         raise ValueError("gail_finalize: out must be 3 contiguous f32")
-    if out.is_cuda:
-        out_p = ptr(out)
-    elif out.is_pinned():
-        out_p = out.data_ptr()
-    else:
-        raise RuntimeError("gail_finalize: out must be a device tensor or pinned host memory (f32)")
-    call("tsm_gail_finalize", ptr(partial), partial.numel() // 4, int(Rp), int(Re), out_p, stream_ptr())
+    call("tsm_gail_finalize", ptr(partial), partial.numel() // 4, int(Rp), int(Re), _out_or_pinned("gail_finalize", out, 3), stream_ptr())
     return out
 
 
@@ -2046,13 +1976,8 @@ def cac_check(act_dim: int, n_step: int = 1) -> None:
 
 def cac_normal(n: int, seed: int, offset: int = 0, offset_dev=None, device="cuda", out=None):
     """n standard normals f32 from Philox (seed, offset + *offset_dev) under this draw's own key."""
-    if out is None:
-        out = torch.empty(int(n), dtype=torch.float32, device=device)
-    _dev_only("cac_normal", out, offset_dev)
-    out = _chk(out, torch.float32, "out")
-    if out.numel() != int(n) or not out.is_contiguous():
-        raise ValueError(f"cac_normal: out must be contiguous with {int(n)} entries")
-    call("tsm_cac_normal", ptr(out), int(n), seed & (2**64 - 1), offset & (2**64 - 1), ptr(offset_dev), stream_ptr())
+    out = _out("cac_normal", out, (int(n),), torch.float32, device, size="numel")
+    call("tsm_cac_normal", ptr(out), int(n), *_philox("cac_normal", seed, offset, offset_dev), stream_ptr())
     return out
 
 
@@ -2157,7 +2082,7 @@ def cac_col_sum(d, slabs):
 def cac_target(q1_next, q2_next, mc, gpow, vmask, logp_next=None, alpha_dev=None, out=None):
     """min of the lagged critics (q2_next None: the single critic), minus alpha * logp_next for SAC, then the n-step line
     (td3.py:94-102, sac.py:298-302, algorithm_base.py:1213-1215).  -> returns f32 [B]."""
-    _dev_only("cac_target", q1_next, q2_next, mc, gpow, vmask, logp_next, alpha_dev, out)
+    _dev_only("cac_target", q1_next, q2_next, mc, gpow, vmask, logp_next, alpha_dev)
     B = q1_next.numel()
     if B < 1:
         raise ValueError("cac_target: empty batch")
@@ -2166,10 +2091,7 @@ def cac_target(q1_next, q2_next, mc, gpow, vmask, logp_next=None, alpha_dev=None
     args = _head_args("cac_target", B, (), (("q1_next", q1_next, torch.float32), ("q2_next", q2_next, torch.float32),
                                             ("logp_next", logp_next, torch.float32), ("mc", mc, torch.float32),
                                             ("gpow", gpow, torch.float32), ("vmask", vmask, torch.uint8)))
-    if out is None:
-        out = torch.empty(B, dtype=torch.float32, device=q1_next.device)
-    elif out.numel() != B or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError(f"cac_target: out must be a contiguous f32 [{B}]")
+    out = _out("cac_target", out, (B,), torch.float32, q1_next.device, size="numel")
     call("tsm_cac_target", *map(ptr, args[:3]), ptr(None if alpha_dev is None else _chk(alpha_dev, torch.float32, "alpha_dev")),
          *map(ptr, args[3:]), B, ptr(out), stream_ptr())
     return out
@@ -2205,7 +2127,7 @@ def cac_det_actor_head(dq_da, one_minus_tanh2, q_pi, max_action: float = 1.0, ou
     """actor_loss = -mean Q(s, pi(s)) and its gradient w.r.t. the actor's raw output (ddpg.py:406, td3.py:216): dq_da [B, Ad]
     = d Q / d a (`mlp_input_grad` with d_out = 1), one_minus_tanh2 from `cac_det_action`, q_pi [B].
     -> dict(d_raw [B, Ad], partial f64): `qmix_finalize(partial, B, out)` gives {actor_loss, 0}."""
-    _dev_only("cac_det_actor_head", dq_da, one_minus_tanh2, q_pi, out)
+    _dev_only("cac_det_actor_head", dq_da, one_minus_tanh2, q_pi)
     if dq_da.dim() != 2 or dq_da.shape[0] < 1:
         raise ValueError("cac_det_actor_head: dq_da must be [B, Ad] with B >= 1")
     B, Ad = dq_da.shape
@@ -2213,10 +2135,7 @@ def cac_det_actor_head(dq_da, one_minus_tanh2, q_pi, max_action: float = 1.0, ou
     dq_da = _cac_grad("cac_det_actor_head", dq_da, B, Ad, "dq_da")
     omt2 = _cac_grad("cac_det_actor_head", one_minus_tanh2, B, Ad, "one_minus_tanh2")
     (q_pi,) = _head_args("cac_det_actor_head", B, (), (("q_pi", q_pi, torch.float32),))
-    if out is None:
-        out = torch.empty(B, Ad, dtype=torch.float32, device=dq_da.device)
-    elif tuple(out.shape) != (B, Ad) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError(f"cac_det_actor_head: out must be a contiguous f32 [{B}, {Ad}]")
+    out = _out("cac_det_actor_head", out, (B, Ad), torch.float32, dq_da.device)
     partial = _head_partial(B, _abi.CAC_ROWS_PER_BLOCK, dq_da.device)
     call("tsm_cac_det_actor_head", ptr(dq_da), Ad, ptr(omt2), ptr(q_pi), B, Ad, float(max_action), ptr(out), ptr(partial),
          stream_ptr())
@@ -2232,7 +2151,7 @@ def sac_actor_head(raw, z, q1a, q2a, dq1_da, dq2_da, alpha_dev, max_action: floa
     `qmix_finalize` gives {actor_loss, mean -logp}; the partials are what `AutoAlpha.step_device` takes."""
     raw, B, Ad, ld, sg, sg_ptr, ld_s = _sac_raw("sac_actor_head", raw, sigma_param)
     cac_check(Ad)
-    _dev_only("sac_actor_head", q1a, q2a, alpha_dev, out)
+    _dev_only("sac_actor_head", q1a, q2a, alpha_dev)
     if (q2a is None) != (dq2_da is None):
         raise ValueError("sac_actor_head: q2a and dq2_da come together")
     z = _cac_z("sac_actor_head", z, B, Ad)
@@ -2240,10 +2159,7 @@ def sac_actor_head(raw, z, q1a, q2a, dq1_da, dq2_da, alpha_dev, max_action: floa
     g2 = None if dq2_da is None else _cac_grad("sac_actor_head", dq2_da, B, Ad, "dq2_da")
     q1a, q2a = _head_args("sac_actor_head", B, (), (("q1a", q1a, torch.float32), ("q2a", q2a, torch.float32)))
     dev = raw.device
-    if out is None:
-        out = torch.empty_like(raw)
-    elif tuple(out.shape) != tuple(raw.shape) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError(f"sac_actor_head: out must be a contiguous f32 {list(raw.shape)}")
+    out = _out("sac_actor_head", out, raw.shape, torch.float32, dev)
     d_sigma = torch.empty(B, Ad, dtype=torch.float32, device=dev) if sigma_param is not None else None
     ds_ptr = out.data_ptr() + 4 * Ad if d_sigma is None else d_sigma.data_ptr()
     logp = torch.empty(B, dtype=torch.float32, device=dev)
@@ -2283,18 +2199,15 @@ def redq_target(q_next, subset_mask: int, mode: str, mc, gpow, vmask, logp_next=
     """The subset's min or mean of the lagged ensemble q_next [E, B], minus alpha * logp_next, then the n-step line
     (redq.py:254-269, algorithm_base.py:1213-1215).  -> returns f32 [B]."""
     q_next, E, B = _redq_q("redq_target", q_next)
-    _dev_only("redq_target", mc, gpow, vmask, logp_next, alpha_dev, out)
+    _dev_only("redq_target", mc, gpow, vmask, logp_next, alpha_dev)
     if mode not in ("min", "mean"):
         raise ValueError(f"Unsupported target_mode: {mode}")
     if (logp_next is None) != (alpha_dev is None):
         raise ValueError("redq_target: logp_next and alpha_dev come together")
     args = _head_args("redq_target", B, (), (("logp_next", logp_next, torch.float32), ("mc", mc, torch.float32),
                                              ("gpow", gpow, torch.float32), ("vmask", vmask, torch.uint8)))
-    if out is None:
-        out = torch.empty(B, dtype=torch.float32, device=q_next.device)
-    elif out.numel() != B or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError(f"redq_target: out must be a contiguous f32 [{B}]")
-    call("tsm_redq_target", ptr(q_next), E, int(subset_mask) & (2**64 - 1), 0 if mode == "min" else 1, ptr(args[0]),
+    out = _out("redq_target", out, (B,), torch.float32, q_next.device, size="numel")
+    call("tsm_redq_target", ptr(q_next), E, int(subset_mask) % 2**64, 0 if mode == "min" else 1, ptr(args[0]),
          ptr(None if alpha_dev is None else _chk(alpha_dev, torch.float32, "alpha_dev")), *map(ptr, args[1:]), B, ptr(out),
          stream_ptr())
     return out
@@ -2317,10 +2230,7 @@ def redq_critic_head(q, returns, weight=None):
 def redq_mean_q(q, out=None):
     """critic(obs, a).mean(dim=0) (redq.py:287): q [E, B] -> f32 [B], the members summed in order."""
     q, E, B = _redq_q("redq_mean_q", q)
-    if out is None:
-        out = torch.empty(B, dtype=torch.float32, device=q.device)
-    elif out.numel() != B or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError(f"redq_mean_q: out must be a contiguous f32 [{B}]")
+    out = _out("redq_mean_q", out, (B,), torch.float32, q.device, size="numel")
     call("tsm_redq_mean_q", ptr(q), E, B, ptr(out), stream_ptr())
     return out
 
@@ -2383,13 +2293,10 @@ def bdqn_egreedy(q, eps_dev, seed: int, offset: int = 0, offset_dev=None, out=No
     """Per-branch epsilon-greedy actions (bdqn.py:76, 80-103) on the device: q [R, K, A] -> act i32 [R, K].  One coin per ROW;
     eps read from the device scalar eps_dev; row r draws at Philox counter offset + r."""
     q, R, K, A = _bdqn_q("bdqn_egreedy", q)
-    _dev_only("bdqn_egreedy", eps_dev, out, offset_dev)
-    if out is None:
-        out = torch.empty(R, K, dtype=torch.int32, device=q.device)
-    elif out.numel() < R * K or not out.is_contiguous():
-        raise ValueError(f"bdqn_egreedy: out must be a contiguous i32 tensor of at least {R * K} entries")
-    call("tsm_bdqn_egreedy", ptr(q), R, K, A, ptr(_chk(eps_dev, torch.float32, "eps_dev")), seed & (2**64 - 1),
-         offset & (2**64 - 1), ptr(offset_dev), ptr(_chk(out, torch.int32, "out")), stream_ptr())
+    _dev_only("bdqn_egreedy", eps_dev)
+    out = _out("bdqn_egreedy", out, (R, K), torch.int32, q.device, size="min")
+    call("tsm_bdqn_egreedy", ptr(q), R, K, A, ptr(_chk(eps_dev, torch.float32, "eps_dev")),
+         *_philox("bdqn_egreedy", seed, offset, offset_dev), ptr(out), stream_ptr())
     return out
 
 
@@ -2443,22 +2350,20 @@ def segtree_check(t: "DeviceSegmentTree") -> None:
 def per_sample(t: "DeviceSegmentTree", n: int, seed: int, offset: int = 0, offset_dev=None) -> torch.Tensor:
     """prio.py:63-66 in one launch: n leaf indices i64 drawn in proportion to the leaves; draw i at Philox counter offset +
     *offset_dev + i."""
-    _dev_only("per_sample", offset_dev)
     out = torch.empty(int(n), dtype=torch.int64, device=t.tree.device)
-    call("tsm_per_sample", ptr(t.tree), t.size, int(n), seed & (2**64 - 1), offset & (2**64 - 1), ptr(offset_dev), ptr(out),
-         stream_ptr())
+    call("tsm_per_sample", ptr(t.tree), t.size, int(n), *_philox("per_sample", seed, offset, offset_dev), ptr(out), stream_ptr())
     return out
 
 
 def per_update_weight(t: "DeviceSegmentTree", index, td, alpha: float, prio) -> None:
     """prio.py:81-90: leaves index <- (|td| + eps) ** alpha in float32, and prio f64 [2] = {max_prio, min_prio} folded."""
     index = _tree_index(t, "per_update_weight", index)
-    _dev_only("per_update_weight", td, prio)
+    _dev_only("per_update_weight", td)
     td = _chk(td, torch.float32, "td").reshape(-1)
     if td.numel() != index.numel():
         raise ValueError(f"per_update_weight: {td.numel()} weights for {index.numel()} indices")
     call("tsm_per_update_weight", ptr(t.tree), ptr(t.mark), t.size, ptr(index), ptr(td), index.numel(), float(alpha),
-         ptr(_chk(prio, torch.float64, "prio")), ptr(t.err), stream_ptr())
+         ptr(_out("per_update_weight", prio, (2,), torch.float64, None, "prio", "min")), ptr(t.err), stream_ptr())
 
 
 def per_init_weight(t: "DeviceSegmentTree", index, alpha: float, prio) -> None:
@@ -2552,13 +2457,9 @@ def maddpg_joint_rows(obs, act, replace=None, out=None):
             raise ValueError(f"maddpg_joint_rows: agent {k}: expected obs [{B}, {D}], act [{B}, {Ad}]")
     W = N * (D + Ad)
     shape = (B, W) if replace is None else (N, B, W)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=obs[0].device)
-    elif tuple(out.shape) != shape:
-        raise ValueError(f"maddpg_joint_rows: out must be {shape}")
+    out = _out("maddpg_joint_rows", out, shape, torch.float32, obs[0].device)
     call("tsm_maddpg_joint_rows", _ptr_array(obs, "obs"), _ptr_array(act, "act"),
-         None if replace is None else _ptr_array(replace, "replace"), N, B, D, Ad, ptr(_chk(out, torch.float32, "out")),
-         stream_ptr())
+         None if replace is None else _ptr_array(replace, "replace"), N, B, D, Ad, ptr(out), stream_ptr())
     return out
 
 
@@ -2579,19 +2480,17 @@ def maddpg_td(q, q_next, rew, term, gamma: float, out=None):
         if not (q[k].numel() == q_next[k].numel() == rew[k].numel() == term[k].numel() == B):
             raise ValueError(f"maddpg_td: agent {k}: every array needs {B} entries")
     dev = q[0].device
-    if out is None:
-        dq = [torch.empty(B, dtype=torch.float32, device=dev) for _ in range(N)]
-        partial = torch.empty(maddpg_partial_elems(B, N), dtype=torch.float64, device=dev)
-    else:
-        dq, partial = out
+    dq, partial = out if out is not None else ([None] * N, None)
+    dq = [_out("maddpg_td", x, (B,), torch.float32, dev, "dq", "min") for x in dq]
+    partial = _out("maddpg_td", partial, (maddpg_partial_elems(B, N),), torch.float64, dev, "partial", "min")
     ag = _abi.tsm_maddpg_agents()
     for k in range(N):
         ag.q[k] = ptr(_chk(q[k], torch.float32, "q"))
         ag.q_next[k] = ptr(_chk(q_next[k], torch.float32, "q_next"))
         ag.rew[k] = ptr(_chk(rew[k], torch.float32, "rew"))
         ag.term[k] = ptr(term[k])
-        ag.dq[k] = ptr(_chk(dq[k], torch.float32, "dq"))
-    call("tsm_maddpg_td", C.byref(ag), N, B, float(gamma), ptr(_chk(partial, torch.float64, "partial")), stream_ptr())
+        ag.dq[k] = ptr(dq[k])
+    call("tsm_maddpg_td", C.byref(ag), N, B, float(gamma), ptr(partial), stream_ptr())
     return dq, partial
 
 
@@ -2600,16 +2499,11 @@ def maddpg_finalize(partial, q_pi, B: int, out):
     fixed summation order).  out: device f32 [2 N] or pinned host f32 [2 N]."""
     N = len(q_pi)
     maddpg_check(N)
-    if out.is_cuda:
-        out_p = ptr(out)
-    elif out.is_pinned() and out.is_contiguous() and out.dtype == torch.float32:
-        out_p = out.data_ptr()
-    else:
-        raise RuntimeError("maddpg_finalize: out must be a device tensor or pinned host memory (f32)")
-    if out.numel() < 2 * N or any(x.numel() != B for x in q_pi):
-        raise ValueError(f"maddpg_finalize: out needs {2 * N} entries and every q_pi {B}")
+    if any(x.numel() != B for x in q_pi):
+        raise ValueError(f"maddpg_finalize: every q_pi needs {B} entries")
     partial = _chk(partial, torch.float64, "partial")
-    call("tsm_maddpg_finalize", ptr(partial), partial.numel() // N, _ptr_array(q_pi, "q_pi"), N, B, out_p, stream_ptr())
+    call("tsm_maddpg_finalize", ptr(partial), partial.numel() // N, _ptr_array(q_pi, "q_pi"), N, B,
+         _out_or_pinned("maddpg_finalize", out, 2 * N), stream_ptr())
     return out
 
 
@@ -2623,23 +2517,18 @@ def maddpg_act(mu, sigma_dev, seed: int, offset: int = 0, offset_dev=None, low=N
         raise ValueError(f"maddpg_act: every actor output must be [{E}, {Ad}]")
     if (low is None) != (high is None) or (low is not None and (low.numel() != Ad or high.numel() != Ad)):
         raise ValueError(f"maddpg_act: low and high come together, {Ad} entries each")
-    if out is None:
-        out = torch.empty(E * N, Ad, dtype=torch.float32, device=mu[0].device)
-    elif out.numel() != E * N * Ad:
-        raise ValueError(f"maddpg_act: out needs {E * N * Ad} entries")
+    out = _out("maddpg_act", out, (E * N, Ad), torch.float32, mu[0].device, size="numel")
     call("tsm_maddpg_act", _ptr_array(mu, "mu"), N, E, Ad, ptr(_chk(sigma_dev, torch.float32, "sigma_dev")),
-         seed & (2**64 - 1), offset & (2**64 - 1), ptr(offset_dev),
-         ptr(None if low is None else _chk(low, torch.float32, "low")),
-         ptr(None if high is None else _chk(high, torch.float32, "high")), ptr(_chk(out, torch.float32, "out")), stream_ptr())
+         *_philox("maddpg_act", seed, offset, offset_dev), ptr(None if low is None else _chk(low, torch.float32, "low")),
+         ptr(None if high is None else _chk(high, torch.float32, "high")), ptr(out), stream_ptr())
     return out
 
 
 def polyak(target, param, tau: float):
     """target <- tau * param + (1 - tau) * target in place (update_target_networks, ctde.py:936-955), bit for bit the torch
     expression on f32 device tensors."""
-    target, param = _chk(target, torch.float32, "target"), _chk(param, torch.float32, "param")
-    if target.numel() != param.numel():
-        raise ValueError("polyak: target and param differ in size")
+    param = _chk(param, torch.float32, "param")
+    _out("polyak", target, (param.numel(),), torch.float32, None, "target", "numel")   # (written in place)
     call("tsm_polyak", ptr(target), ptr(param), target.numel(), float(tau), stream_ptr())
     return target
 
@@ -2757,7 +2646,7 @@ def gather_fields(fields: list, prepared: list | None = None) -> list:
 def any_nonzero_u8(x, out=None):
     """Device flag i32[1] = 1 if any byte of `x` (u8 / bool, contiguous) is non-zero."""
     x = _chk(x, torch.uint8, "x")
-    flag = out if out is not None else torch.empty(1, dtype=torch.int32, device=x.device)
+    flag = _out("any_nonzero_u8", out, (1,), torch.int32, x.device, size="min")
     call("tsm_any_nonzero_u8", ptr(x), x.numel(), ptr(flag), stream_ptr())
     return flag
 
@@ -2768,7 +2657,7 @@ def value_next_select(v_s, v_last, v_full, flag, T: int, U: int, out=None):
     v_s, v_last, v_full = (_chk(t, torch.float32, n) for t, n in ((v_s, "v_s"), (v_last, "v_last"), (v_full, "v_full")))
     if v_s.numel() != T * U or v_full.numel() != T * U or v_last.numel() != U:
         raise ValueError("value_next_select: shapes do not match T x U")
-    res = out if out is not None else torch.empty(T, U, dtype=torch.float32, device=v_s.device)
+    res = _out("value_next_select", out, (T, U), torch.float32, v_s.device, size="min")
     call("tsm_value_next_select", ptr(v_s), ptr(v_last), ptr(v_full), ptr(_chk(flag, torch.int32, "flag")), T, U, ptr(res),
          stream_ptr())
     return res
@@ -2781,7 +2670,7 @@ def value_next_index(v_s, done, T: int, U: int, lanes_per_env: int = 1, out=None
     done = done.contiguous().view(torch.uint8) if done.dtype == torch.bool else _chk(done, torch.uint8, "done")
     if v_s.numel() != T * U or done.numel() * lanes_per_env != T * U:
         raise ValueError("value_next_index: shapes do not match T x U")
-    res = out if out is not None else torch.empty(T, U, dtype=torch.float32, device=v_s.device)
+    res = _out("value_next_index", out, (T, U), torch.float32, v_s.device, size="min")
     call("tsm_value_next_index", ptr(v_s), ptr(done), T, U, lanes_per_env, ptr(res), stream_ptr())
     return res
 
@@ -2791,7 +2680,7 @@ def value_next_select_env_major(v_s, v_last, v_full, flag, E: int, T: int, U: in
     v_s, v_last, v_full = (_chk(t, torch.float32, n) for t, n in ((v_s, "v_s"), (v_last, "v_last"), (v_full, "v_full")))
     if v_s.numel() != E * T * U or v_full.numel() != E * T * U or v_last.numel() != E * U:
         raise ValueError("value_next_select_env_major: shapes do not match E x T x U")
-    res = out if out is not None else torch.empty(E * T, U, dtype=torch.float32, device=v_s.device)
+    res = _out("value_next_select_env_major", out, (E * T, U), torch.float32, v_s.device, size="min")
     call("tsm_value_next_select_env_major", ptr(v_s), ptr(v_last), ptr(v_full), ptr(_chk(flag, torch.int32, "flag")), E, T, U,
          ptr(res), stream_ptr())
     return res
@@ -2802,28 +2691,6 @@ def mlp_n_split(B: int) -> int:
     return max(1, min(64, -(-B // 256)))
 
 
-def _mlp_slabs(name: str, slabs, n_split: int, n_param: int, slab_stride: int, dev):
-    """Gradient slabs the launches may write: slab s covers the floats [s * stride, s * stride + n_param) behind the first
-    element of `slabs` (stride = slab_stride, or n_param when it is 0).  None: a fresh [n_split, stride]."""
-    if not 1 <= n_split <= 65535:
-        raise ValueError(f"{name}: n_split {n_split} outside [1, 65535]")
-    if slab_stride < 0 or 0 < slab_stride < n_param:
-        raise ValueError(f"{name}: slab_stride {slab_stride} smaller than the parameter count {n_param}")
-    stride = slab_stride or n_param
-    if slabs is None:
-        return torch.empty(n_split, stride, dtype=torch.float32, device=dev)
-    _dev_only(name, slabs)
-    if slabs.dtype != torch.float32 or slabs.dim() < 1 or slabs.numel() == 0 or slabs.stride(-1) != 1:
-        raise ValueError(f"{name}: slabs must be a non-empty f32 tensor, contiguous along the parameters")
-    if slabs.dim() == 2 and n_split > slabs.shape[0]:
-        raise ValueError(f"{name}: n_split {n_split} exceeds the {slabs.shape[0]} rows of slabs")
-    reach = 1 + sum((n - 1) * st for n, st in zip(slabs.shape, slabs.stride()))
-    if (n_split - 1) * stride + n_param > reach:
-        raise ValueError(f"{name}: slabs reach {reach} floats; {n_split} slabs of {n_param} floats at pitch {stride} need "
-                         f"{(n_split - 1) * stride + n_param}")
-    return slabs
-
-
 def mlp_backward(desc, params, x, acts, d_out, n_split: int = 0, slabs=None, slab_stride: int = 0):
     """Gradient slabs [n_split, n_param] of sum(out * d_out) w.r.t. the flat parameter vector.
     `slabs` may point INTO the slabs of a larger joint parameter vector (slab_stride = its parameter count)."""
@@ -2831,11 +2698,9 @@ def mlp_backward(desc, params, x, acts, d_out, n_split: int = 0, slabs=None, sla
     if B < 1:
         raise ValueError("mlp_backward: batch must be >= 1")
     d_out = _chk(d_out, torch.float32, "d_out")
-    if n_split <= 0:
-        n_split = mlp_n_split(B)
-    if slabs is None and slab_stride == 0:
-        slab_stride = params.numel()   # fresh slabs are as wide as the caller's vector, which may hold more than the net
-    slabs = _mlp_slabs("mlp_backward", slabs, int(n_split), n_param, int(slab_stride), x.device)
+    # (fresh slabs are as wide as the caller's vector, which may hold more than the net)
+    n_split, slabs, slab_stride = _slab_dest("mlp_backward", slabs, n_split, B,
+                                             slab_stride or (params.numel() if slabs is None else n_param), n_param, x.device)
     d_acts = torch.empty_like(acts)
     call("tsm_mlp_backward", C.byref(desc), ptr(params), ptr(x), B, ptr(acts), ptr(d_out), ptr(d_acts), n_split,
          slabs.data_ptr(), slab_stride, stream_ptr())
@@ -2851,15 +2716,8 @@ def mlp_input_grad(desc, params, x, acts, d_out, col0: int, n_col: int, out=None
     if B < 1:
         raise ValueError("mlp_input_grad: batch must be >= 1")
     d_out = _chk(d_out, torch.float32, "d_out")
-    _dev_only("mlp_input_grad", out, d_acts)
-    if out is None:
-        out = torch.empty(B, n_col, dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, n_col) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError(f"mlp_input_grad: out must be a contiguous f32 [{B}, {n_col}]")
-    if d_acts is None:
-        d_acts = torch.empty_like(acts)
-    elif d_acts.dtype != torch.float32 or not d_acts.is_contiguous() or d_acts.numel() != n_act:
-        raise ValueError(f"mlp_input_grad: d_acts must be a contiguous f32 workspace of {n_act} floats, the size of acts")
+    out = _out("mlp_input_grad", out, (B, n_col), torch.float32, x.device)
+    d_acts = _out("mlp_input_grad", d_acts, (n_act,), torch.float32, x.device, "d_acts", "numel")   # a workspace the size of acts
     call("tsm_mlp_input_grad", C.byref(desc), ptr(params), ptr(x), B, ptr(acts), ptr(d_out), ptr(d_acts), col0, n_col, ptr(out),
          n_col, stream_ptr())
     return out
@@ -2891,8 +2749,7 @@ def ens_mlp_forward(desc, E: int, params, x, acts=None):
     """x [B, dims[0]] through all E members -> (out [E, B, dims[-1]] view of the last activation block, acts buffer)."""
     params, x, B = _ens_args("ens_mlp_forward", desc, E, params, x)
     n = call("tsm_ens_mlp_act_elems", C.byref(desc), int(E), B)
-    if acts is None:
-        acts = torch.empty(n, dtype=torch.float32, device=x.device)
+    acts = _out("ens_mlp_forward", acts, (n,), torch.float32, x.device, "acts", "min")
     call("tsm_ens_mlp_forward", C.byref(desc), int(E), ptr(params), ptr(x), B, ptr(acts), stream_ptr())
     O = desc.dims[desc.n_layers]
     return acts[n - E * B * O:].view(E, B, O), acts
@@ -2904,10 +2761,8 @@ def ens_mlp_backward(desc, E: int, params, x, acts, d_out, n_split: int = 0, sla
     d_out = _chk(d_out, torch.float32, "d_out")
     if d_out.numel() != E * B * desc.dims[desc.n_layers]:
         raise ValueError(f"ens_mlp_backward: d_out must be [{E}, {B}, {desc.dims[desc.n_layers]}]")
-    if n_split <= 0:
-        n_split = mlp_n_split(B)
-    if slabs is None:
-        slabs = torch.empty(n_split, params.numel(), dtype=torch.float32, device=x.device)
+    n_split, slabs, slab_stride = _slab_dest("ens_mlp_backward", slabs, n_split, B, slab_stride or params.numel(), params.numel(),
+                                             x.device)
     d_acts = torch.empty_like(acts)
     call("tsm_ens_mlp_backward", C.byref(desc), int(E), ptr(params), ptr(x), B, ptr(acts), ptr(d_out), ptr(d_acts), n_split,
          slabs.data_ptr(), slab_stride, stream_ptr())
@@ -2923,13 +2778,10 @@ def ens_mlp_input_grad(desc, E: int, params, x, acts, d_out, col0: int, n_col: i
         raise ValueError(f"ens_mlp_input_grad: columns [{col0}, {col0 + n_col}) leave the input width {desc.dims[0]}")
     if d_out.numel() != E * B * desc.dims[desc.n_layers]:
         raise ValueError(f"ens_mlp_input_grad: d_out must be [{E}, {B}, {desc.dims[desc.n_layers]}]")
-    if out is None:
-        out = torch.empty(B, n_col, dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, n_col):
-        raise ValueError(f"ens_mlp_input_grad: out must be [{B}, {n_col}]")
+    out = _out("ens_mlp_input_grad", out, (B, n_col), torch.float32, x.device)
     d_acts = torch.empty_like(acts)
     call("tsm_ens_mlp_input_grad", C.byref(desc), int(E), ptr(params), ptr(x), B, ptr(acts), ptr(d_out), ptr(d_acts), col0, n_col,
-         ptr(_chk(out, torch.float32, "out")), n_col, stream_ptr())
+         ptr(out), n_col, stream_ptr())
     return out
 
 
