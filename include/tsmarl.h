@@ -1599,6 +1599,56 @@ int tsm_agent_pool_forward(const float *h, const float *c, int64_t B, int32_t n_
 int tsm_agent_pool_backward(const float *d, const float *c, const float *h_relu, int64_t B, int32_t n_agents, int32_t H,
                             float *d_h, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Recurrent Q-learning  (tianshou/utils/net/common.py:372-458 `Recurrent`; data/buffer/buffer_base.py:495-590 frame stacking;
+ * csrc/lstm.hip, csrc/dense.hip, csrc/vrb.hip)
+ * tsm_dense_linear / _dgrad / _wgrad: the three row GEMMs of ONE linear layer with its operands given apart (the engine of
+ *   tsm_mlp_*, f32 MFMA), for parameters that do not lie as W | b pairs and for strided rows:
+ *     linear  out[M][O] = x[M][K (row pitch ldx)] W[O][K]^T + bias[O]
+ *     dgrad   dx[M][K (row pitch ld_dx)] = dz[M][O] W[O][K]
+ *     wgrad   slab z of n_split, at slabs + z * slab_stride: [w_off + o * K + k] = sum over the slab's rows of dz[m][o] x[m][k],
+ *             [b_off + o] = sum of dz[m][o]; the rows are dealt to the slabs as by tsm_mlp_backward, the slabs sum to the gradient.
+ * The LSTM layer: torch's layout, gate order i, f, g, o; weight_hh [4H][H].  H a multiple of 16 in [16, TSM_LSTM_MAX_HIDDEN],
+ *   layer_num >= 1, L >= 1, B >= 1: anything else is TSM_ERR_INVALID from tsm_lstm_check (needs no device) before any launch.
+ *   A workgroup carries TSM_LSTM_ROWS_PER_BLOCK batch rows through all L steps: one launch per layer and direction.
+ * tsm_lstm_forward: proj f32 [B][L][4H] = X W_ih^T + b_ih (tsm_dense_linear); bias (nullable) [4H] is added to it (b_hh);
+ *   h0, c0 (nullable: zeros) and h_n, c_n (nullable) are [B] rows of H floats at row pitch ld_state (a layer's slice of a
+ *   [B][layers][H] state); h_n / c_n may be h0 / c0 themselves (the acting step, L = 1, advances the state in place).
+ *   Per step: gates = proj_t + bias + h_{t-1} W_hh^T;  i, f, o = sigmoid, g = tanh;  c_t = f c_{t-1} + i g;  h_t = o tanh(c_t).
+ *   out: h [B][L][H]; for the backward (each nullable) h_prev [B][L][H] = h_{t-1}, gates [B][L][4H] activated, c [B][L][H].
+ *   sigmoid and tanh are finite for every finite input.
+ * tsm_lstm_backward: d_h [B][L][H] = the gradient arriving at every h_t from above; d_hn, d_cn (nullable) at h_L, c_L;
+ *   gates, c as saved; c0 as given to the forward -> d_gates [B][L][4H] w.r.t. the pre-activations, every element written,
+ *   and (nullable) d_h0, d_c0.  d_h_{t-1} += d_gates_t W_hh on f32 MFMA.  The weight gradients are then
+ *   tsm_dense_wgrad(d_gates, X) -> weight_ih, bias_ih and tsm_dense_wgrad(d_gates, h_prev) -> weight_hh, bias_hh, and the
+ *   gradient for the layer below tsm_dense_dgrad(d_gates, W_ih).
+ * tsm_lstm_state_reset: h, c f32 [n_env * rows_per_env][row_elems]; the rows of env e are zeroed where done[e] != 0
+ *   (collector.py:977-979).  One launch, no host read: safe inside a captured graph.
+ * tsm_vrb_gather_stacked replaces  ReplayBuffer.get(index, key, stack_num) (buffer_base.py:533-590): stack_num - 1 rounds of
+ *   tsm_vrb_prev's rule from index[i], then out[i][l] = bytes [lane_off, lane_off + lane_bytes) of the store row of the
+ *   (stack_num - 1 - l)-th predecessor: oldest first, a frame repeating where the walk stops at an episode start or the oldest
+ *   row.  out [n][stack_num][lane_bytes].  Bit-identical to stack_num rounds of tsm_vrb_prev + tsm_vrb_gather.  One launch.
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_LSTM_MAX_HIDDEN 128
+#define TSM_LSTM_ROWS_PER_BLOCK 16
+int tsm_dense_linear(const float *x, int64_t ldx, const float *W, const float *bias, int64_t M, int32_t K, int32_t O, float *out,
+                     void *stream);
+int tsm_dense_dgrad(const float *dz, const float *W, int64_t M, int32_t O, int32_t K, float *dx, int64_t ld_dx, void *stream);
+int tsm_dense_wgrad(const float *dz, const float *x, int64_t ldx, int64_t M, int32_t O, int32_t K, int32_t n_split, float *slabs,
+                    int64_t slab_stride, int64_t w_off, int64_t b_off, void *stream);
+int tsm_lstm_check(int32_t hidden, int32_t layer_num, int32_t seq_len);
+int tsm_lstm_forward(const float *proj, const float *w_hh, const float *bias, const float *h0, const float *c0, int64_t ld_state,
+                     int64_t B, int32_t L, int32_t H, float *h, float *h_prev, float *gates, float *c, float *h_n, float *c_n,
+                     void *stream);
+int tsm_lstm_backward(const float *d_h, const float *d_hn, const float *d_cn, const float *w_hh, const float *gates,
+                      const float *c, const float *c0, int64_t ld_state, int64_t B, int32_t L, int32_t H, float *d_gates,
+                      float *d_h0, float *d_c0, void *stream);
+int tsm_lstm_state_reset(float *h, float *c, const uint8_t *done, int64_t n_env, int64_t rows_per_env, int64_t row_elems,
+                         void *stream);
+int tsm_vrb_gather_stacked(const void *state, int64_t buffer_num, int64_t sub_size, const uint8_t *done_store, const void *store,
+                           int64_t row_bytes, int64_t lane_off, int64_t lane_bytes, const int64_t *index, int64_t n,
+                           int32_t stack_num, void *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

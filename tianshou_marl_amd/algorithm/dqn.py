@@ -30,7 +30,7 @@ from .. import ops
 from ..data.batch import Batch
 from ..data.stats import TrainingStats
 from ..utils.learner import act_result, result_slot, sample_counter, slab_workspace
-from ..utils.net import FlatMLP, export_views, import_views, lagged_copy, ref_layer_keys
+from ..utils.net import FlatMLP, Recurrent, export_views, import_views, lagged_copy, ref_layer_keys
 from ..utils.tensor import to_tensor
 from .optim import flat_adam_of
 
@@ -59,7 +59,10 @@ class DiscreteQLearningPolicy(nn.Module):
                  eps_inference: float = 0.0, seed: int = 0, atoms: int = 1) -> None:
         """`atoms`: outputs per action -- 1 here; the distributional policies (algorithm/distq.py) pass their N."""
         super().__init__()
-        if not isinstance(model, self._model_cls):
+        # the reference's `Recurrent` (utils/net/common.py:372-458) stands where the plain Q-network does: DQN alone takes it
+        self.recurrent = type(self) is DiscreteQLearningPolicy and isinstance(model, Recurrent)   # (not the distributional policies)
+        self._act_state: tuple | None = None   # (hidden, cell) [rows, layers, H] of the collector's rows, in HBM
+        if not (isinstance(model, self._model_cls) or self.recurrent):
             raise TypeError(f"DiscreteQLearningPolicy needs a {self._model_cls.__name__} Q-network: the update runs in HIP, "
                             f"there is no autograd fallback (got {type(model).__name__})")
         self.n_act = self._n_act_of(model, action_space, int(atoms))
@@ -135,7 +138,12 @@ class DiscreteQLearningPolicy(nn.Module):
         """-> Batch(logits in HBM ([B, A]; a subclass: its distribution per action), act = the first argmax of the masked
         value per action (numpy i64), state)."""
         obs, mask = _obs_rows(batch.obs)
-        q, logits, extra = self._forward_values(to_tensor(obs, self.device, torch.float32), model)
+        if self.recurrent:   # obs [B, L, D] | [B, D]; state None (zeros) or Batch(hidden, cell) [B, layers, H], handed back
+            q, (hid, cell) = (self.model if model is None else model).forward(to_tensor(obs, self.device, torch.float32), state,
+                                                                              save=False)
+            logits, extra, state = q, {}, Batch(hidden=hid, cell=cell)
+        else:
+            q, logits, extra = self._forward_values(to_tensor(obs, self.device, torch.float32), model)
         m = None if mask is None else to_tensor(np.asarray(mask, bool) if not isinstance(mask, torch.Tensor) else mask,
                                                  self.device, torch.uint8).reshape(q.shape)
         act = ops.dqn_egreedy(q, self._zero_dev, 0, mask=m)
@@ -165,11 +173,32 @@ class DiscreteQLearningPolicy(nn.Module):
         rows = obs.reshape(-1, self.model.dims[0])
         R = rows.shape[0]
         ctr = sample_counter(self, R, row_offset, offset_dev)
-        q = self._act_values(rows, ctr, offset_dev)
+        if self.recurrent:   # the L = 1 step from the kept state, written back in place: a captured graph advances it on replay
+            if self._act_state is None or self._act_state[0].shape[0] != R:
+                self._act_state = self.model.zero_state(R)
+            q, _ = self.model.forward(rows, self._act_state, save=False, state_out=self._act_state)
+        else:
+            q = self._act_values(rows, ctr, offset_dev)
         m = None if mask is None else mask.reshape(R, self.n_act)
         act = ops.dqn_egreedy(q, self._eps_dev, self.seed, offset=ctr, offset_dev=offset_dev, mask=m,
                               out=None if out is None else out["act"].view(-1))
         return act_result(out, act, q=q)
+
+
+    def reset_state_device(self, done: torch.Tensor | None = None) -> None:
+        """collector.py:977-979 on the device: the kept state rows of the envs with done[e] != 0 restart from zero (None: all
+        of them).  One launch, no host read; nothing to do for a policy without a recurrent net or before its first acting step.
+        The state is ONE slot per policy, for the rows of one collector: two collectors that act with the same policy object
+        (a train and a test collector) would continue and reset one another's state -- give each a policy of its own over the
+        same net (`Recurrent(..., storage=net.flat.data)` shares the parameters)."""
+        if self._act_state is None:
+            return
+        hid, cell = self._act_state
+        if done is None:
+            hid.zero_()
+            cell.zero_()
+        else:
+            ops.lstm_state_reset(hid, cell, done.reshape(-1), rows_per_env=hid.shape[0] // done.numel())
 
 
 class DeviceOffPolicyRows:
@@ -204,8 +233,15 @@ class DeviceOffPolicyRows:
         idx_n, mc, gpow, vmask = ops.nstep_return(buffer.index, buffer.term_store, buffer.rew_store, idx, self.n_step,
                                                   self.gamma, rew_col=k, term_col=col)
         batch.idx_n, batch.mc, batch.gpow, batch.vmask = idx_n, mc, gpow, vmask
-        if "obs" not in batch:  # rows straight from the device stores (DQN.update)
+        stacked = getattr(buffer, "stack_num", 1) > 1
+        if stacked and not getattr(self, "takes_stacks", False):
+            raise ValueError(f"{type(self).__name__}: the buffer stacks {buffer.stack_num} frames, which only a learner around a "
+                             f"recurrent net reads (DQN on utils.net.Recurrent); build the buffer with stack_num=1")
+        if "obs" not in batch and stacked:  # the stack ending at idx, this agent's lane: [I, L, D] in one launch
+            batch.obs = buffer._gather_obs(buffer.obs_store, idx, lane=col)
+        elif "obs" not in batch:  # rows straight from the device stores (DQN.update)
             batch.obs = buffer._gather(buffer.obs_store, idx)[:, col].contiguous()
+        if "act" not in batch:
             act = buffer._gather(buffer.act_store, idx)[:, col].contiguous()
             batch.act = act if act.is_floating_point() else act.to(torch.int64)  # a Box store (act_dim): f32 [I, k]
         return idx, idx_n, col
@@ -214,11 +250,11 @@ class DeviceOffPolicyRows:
     def _successor_rows(buffer, rows, col: int):
         """obs_next[rows] (with ignore_obs_next: obs at next(rows), buffer_base.py:612-616) and the mask the buffer keeps for
         those rows (quirk Q19), gathered with tsm_vrb_gather.  -> (obs_next [I, D], mask or None)."""
-        if buffer._save_obs_next:
-            nxt = buffer._gather(buffer.obs_next_store, rows)
-        else:
-            nxt = buffer._gather(buffer.obs_store, buffer.index.next(rows))
+        store, at = (buffer.obs_next_store, rows) if buffer._save_obs_next else (buffer.obs_store, buffer.index.next(rows))
         mask_store = getattr(buffer, "mask_store", None)
+        if getattr(buffer, "stack_num", 1) > 1:   # the stack ending at `rows`: [I, L, D]
+            return buffer._gather_obs(store, at, lane=col), (None if mask_store is None else buffer._gather(mask_store, rows))
+        nxt = buffer._gather(store, at)
         return nxt[:, col].contiguous(), (None if mask_store is None else buffer._gather(mask_store, rows))
 
     @staticmethod
@@ -321,9 +357,9 @@ class DQN(DeviceOffPolicyRows, nn.Module):
         leaves with what the TD head needs; `returns` is set by `_update_with_batch`, where the head runs."""
         _, idx_n, col = self._nstep_rows(batch, buffer, indices, agent)
         nxt, mask_next = self._successor_rows(buffer, idx_n, col)
-        batch.q_next_online = FlatMLP.forward(self.policy.model, nxt, save=False)
+        batch.q_next_online = self._q_rows(self.policy.model, nxt)
         if self.use_target_network:
-            batch.q_next_target = FlatMLP.forward(self.model_old, nxt, save=False)
+            batch.q_next_target = self._q_rows(self.model_old, nxt)
         if mask_next is not None:
             batch.mask_next = mask_next
         return batch
@@ -337,7 +373,8 @@ class DQN(DeviceOffPolicyRows, nn.Module):
         weight = self._pop_weight(batch)
         obs, _ = _obs_rows(batch.obs)
         model = self.policy.model
-        x = to_tensor(obs, dev, torch.float32).reshape(-1, model.dims[0])
+        x = to_tensor(obs, dev, torch.float32)
+        x = x if self.takes_stacks else x.reshape(-1, model.dims[0])   # a recurrent net: [B, L, D] | [B, D]
         B = x.shape[0]
         act = to_tensor(batch.act, dev, torch.int64).reshape(-1)
         w = slab_workspace(self._ws, B, dev, **self._slab_widths())
@@ -374,7 +411,21 @@ class DQN(DeviceOffPolicyRows, nn.Module):
 
     def _online_forward(self, batch: Batch, x: torch.Tensor) -> torch.Tensor:
         """The online net on the sampled rows, activations kept for `model.backward`."""
+        if self.takes_stacks:
+            return self.policy.model.forward(x, None, save=True)[0]
         return FlatMLP.forward(self.policy.model, x, save=True)
+
+    @property
+    def takes_stacks(self) -> bool:
+        """The Q-network is recurrent: it reads the stacked rows of a `stack_num > 1` buffer, from zero state in every
+        forward of an update, as the reference's does with `state=None` (dqn.py:365-379)."""
+        return bool(getattr(self.policy, "recurrent", False))
+
+    def _q_rows(self, net, rows: torch.Tensor) -> torch.Tensor:
+        """`net` on successor rows, nothing kept."""
+        if self.takes_stacks:
+            return net.forward(rows, None, save=False)[0]
+        return FlatMLP.forward(net, rows, save=False)
 
     def _after_lagged_copy(self, batch: Batch) -> None:
         """What a learner computes between the lagged copy and its loss (C51's successor forwards); nothing here."""

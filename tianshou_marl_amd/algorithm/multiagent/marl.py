@@ -109,6 +109,11 @@ class MultiAgentPolicy(nn.Module):
     # ---- device rollout entry (Collector device path) --------------------------------------------
     def act_device(self, obs: torch.Tensor, out: dict | None = None, offset_dev: torch.Tensor | None = None) -> dict:
         """Joint-step rows obs[E, N, D] -> dict(act i32, logp, value) each flat [E*N] (agent a = column a)."""
+        if any(getattr(p, "recurrent", False) for p in self._agent_policies.values()):
+            # its members would carry (hidden, cell) across episode ends: the Collector resets the state of the policy it holds,
+            # and this wrapper does not pass `reset_state_device` on to its members yet
+            raise NotImplementedError("MultiAgentPolicy.act_device: a member policy around a recurrent net keeps state between steps, "
+                                      "which this wrapper does not reset for finished envs; collect with the policy itself")
         shared = self.shared_policy
         if shared is not None:
             return shared.act_device(obs, out=out, offset_dev=offset_dev)

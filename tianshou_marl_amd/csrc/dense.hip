@@ -328,3 +328,57 @@ TSM_EXPORT int tsm_mlp_input_grad(const tsm_mlp_desc *d, const float *params, co
     }
     return TSM_OK;
 }
+
+// ---- the three GEMMs of one linear layer on their own, for nets whose parameters do not lie as W | b pairs (the LSTM of
+// csrc/lstm.hip: weight_ih, weight_hh, bias_ih, bias_hh) or whose rows are strided (the last step of a [B][L][H] sequence).
+// The kernels are the instantiations above.
+TSM_EXPORT int tsm_dense_linear(const float *x, int64_t ldx, const float *W, const float *bias, int64_t M, int32_t K, int32_t O,
+                                float *out, void *stream) {
+    TSM_REQUIRE(M >= 1 && K >= 1 && O >= 1 && ldx >= K, "tsm_dense_linear: bad sizes M=%lld K=%d O=%d ldx=%lld", (long long)M, K, O,
+                (long long)ldx);
+    TSM_REQUIRE(x && W && bias && out, "tsm_dense_linear: null pointer");
+    TSM_REQUIRE(ceil_div(M, BM) <= 65535, "tsm_dense_linear: %lld rows too many for one launch (max %d)", (long long)M, 65535 * BM);
+    GemmArgs g{};
+    g.A = x; g.lda = ldx; g.B = W; g.ldb = K; g.M = M; g.N = O; g.K = K; g.k_per_split = K;
+    g.C = out; g.ldc = O; g.bias = bias; g.act = 0;
+    dim3 grid((unsigned)ceil_div(O, BN), (unsigned)ceil_div(M, BM), 1);
+    hipLaunchKernelGGL((gemm_kernel<false, false, EPI_FWD, 1>), grid, dim3(NT), 0, tsm_stream(stream), g);
+    TSM_LAUNCH_CHECK();
+    return TSM_OK;
+}
+
+TSM_EXPORT int tsm_dense_dgrad(const float *dz, const float *W, int64_t M, int32_t O, int32_t K, float *dx, int64_t ld_dx,
+                               void *stream) {
+    TSM_REQUIRE(M >= 1 && K >= 1 && O >= 1 && ld_dx >= K, "tsm_dense_dgrad: bad sizes M=%lld K=%d O=%d ld_dx=%lld", (long long)M, K,
+                O, (long long)ld_dx);
+    TSM_REQUIRE(dz && W && dx, "tsm_dense_dgrad: null pointer");
+    TSM_REQUIRE(ceil_div(M, BM) <= 65535, "tsm_dense_dgrad: %lld rows too many for one launch (max %d)", (long long)M, 65535 * BM);
+    GemmArgs g{};
+    g.A = dz; g.lda = O; g.B = W; g.ldb = K; g.M = M; g.N = K; g.K = O; g.k_per_split = O;
+    g.C = dx; g.ldc = ld_dx; g.act = 0;
+    dim3 grid((unsigned)ceil_div(K, BN), (unsigned)ceil_div(M, BM), 1);
+    hipLaunchKernelGGL((gemm_kernel<false, true, EPI_DGRAD, 1>), grid, dim3(NT), 0, tsm_stream(stream), g);
+    TSM_LAUNCH_CHECK();
+    return TSM_OK;
+}
+
+TSM_EXPORT int tsm_dense_wgrad(const float *dz, const float *x, int64_t ldx, int64_t M, int32_t O, int32_t K, int32_t n_split,
+                               float *slabs, int64_t slab_stride, int64_t w_off, int64_t b_off, void *stream) {
+    TSM_REQUIRE(M >= 1 && K >= 1 && O >= 1 && ldx >= K, "tsm_dense_wgrad: bad sizes M=%lld K=%d O=%d ldx=%lld", (long long)M, K, O,
+                (long long)ldx);
+    TSM_REQUIRE(n_split >= 1 && n_split <= 65535, "tsm_dense_wgrad: n_split out of range");
+    TSM_REQUIRE(dz && x && slabs, "tsm_dense_wgrad: null pointer");
+    TSM_REQUIRE(w_off >= 0 && b_off >= 0 && slab_stride >= 0, "tsm_dense_wgrad: negative offset");
+    TSM_REQUIRE(ceil_div(O, BM) <= 65535, "tsm_dense_wgrad: output width too large for one launch");
+    GemmArgs g{};
+    g.A = dz; g.lda = O; g.B = x; g.ldb = ldx; g.M = O; g.N = (int64_t)K + 1; g.K = M;
+    g.k_per_split = ceil_div(ceil_div(M, n_split), BK) * BK;   // whole k tiles per slab, as tsm_mlp_backward
+    g.C = slabs; g.slab_stride = slab_stride; g.w_off = w_off; g.b_off = b_off;
+    dim3 grid((unsigned)ceil_div(K + 1, BN), (unsigned)ceil_div(O, BM), (unsigned)n_split);
+    if ((int64_t)grid.x * grid.y * grid.z < 1024)
+        hipLaunchKernelGGL((gemm_kernel<true, true, EPI_WGRAD, 4>), grid, dim3(NT * 4), 0, tsm_stream(stream), g);
+    else
+        hipLaunchKernelGGL((gemm_kernel<true, true, EPI_WGRAD, 1>), grid, dim3(NT), 0, tsm_stream(stream), g);
+    TSM_LAUNCH_CHECK();
+    return TSM_OK;
+}

@@ -187,6 +187,34 @@ __global__ void vrb_gather_kernel(const char *__restrict__ store, int64_t B, int
     else out[r * row_bytes + o] = src[o];
 }
 
+// `L - 1` rounds of the prev rule of vrb_prevnext_kernel<false>, then the L rows oldest first: a stack never crosses an episode
+// start or the oldest row, whose frame repeats (buffer_base.py:495-590 `get` with stack_num, manager.py:306-331).  One thread
+// per output word; every thread of a row walks the same chain.  lane_off / lane_bytes: the window of a store row that is copied.
+__global__ void vrb_gather_stacked_kernel(const void *state, int64_t B, int64_t S, const uint8_t *__restrict__ done_store,
+                                          const char *__restrict__ store, int64_t row_bytes, int64_t lane_off,
+                                          int64_t lane_bytes, const int64_t *__restrict__ index, int64_t n, int L,
+                                          char *__restrict__ out, int word) {
+    VrbState s = vrb_view(const_cast<void *>(state), B, 1);
+    const int64_t wpr = lane_bytes / word;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * L * wpr) return;
+    const int64_t r = i / (L * wpr), rem = i - r * (L * wpr), l = rem / wpr, o = rem - l * wpr;
+    int64_t idx = pymod(index[r], B * S);
+    const int64_t e = idx / S, start = e * S;
+    int64_t cur_len = s.lengths[e];
+    if (cur_len < 1) cur_len = 1;
+    const int64_t last = s.last_index[e];
+    for (int k = L - 1; k > l; --k) {   // slot l of the stack lies L - 1 - l steps back
+        const int64_t sub = pymod(idx - start - 1, cur_len);
+        const int64_t end_flag = (done_store[sub * B + e] ? 1 : 0) | (sub + start == last ? 1 : 0);
+        idx = pymod(sub + end_flag, cur_len) + start;
+    }
+    const char *src = store + ((idx - start) * B + e) * row_bytes + lane_off;
+    char *dst = out + (r * L + l) * lane_bytes;
+    if (word == 4) reinterpret_cast<uint32_t *>(dst)[o] = reinterpret_cast<const uint32_t *>(src)[o];
+    else dst[o] = src[o];
+}
+
 }  // namespace
 
 TSM_EXPORT int64_t tsm_vrb_state_bytes(int64_t buffer_num, int64_t rew_dim) {
@@ -313,6 +341,26 @@ TSM_EXPORT int tsm_vrb_gather(const void *store, int64_t B, int64_t S, int64_t r
     hipLaunchKernelGGL(vrb_gather_kernel, dim3((unsigned)ceil_div(n * (row_bytes / word), 256)), dim3(256), 0,
                        tsm_stream(stream), reinterpret_cast<const char *>(store), B, S, row_bytes, index, n,
                        reinterpret_cast<char *>(out), word);
+    TSM_LAUNCH_CHECK();
+    return TSM_OK;
+}
+
+TSM_EXPORT int tsm_vrb_gather_stacked(const void *state, int64_t B, int64_t S, const uint8_t *done_store, const void *store,
+                                      int64_t row_bytes, int64_t lane_off, int64_t lane_bytes, const int64_t *index, int64_t n,
+                                      int32_t stack_num, void *out, void *stream) {
+    TSM_REQUIRE(n >= 0 && row_bytes > 0 && stack_num >= 1, "tsm_vrb_gather_stacked: bad sizes");
+    TSM_REQUIRE(lane_off >= 0 && lane_bytes >= 1 && lane_off + lane_bytes <= row_bytes,
+                "tsm_vrb_gather_stacked: lane window [%lld, %lld + %lld) leaves the %lld-byte row", (long long)lane_off,
+                (long long)lane_off, (long long)lane_bytes, (long long)row_bytes);
+    if (n == 0) return TSM_OK;
+    TSM_REQUIRE(state && done_store && store && index && out && B >= 1 && S >= 1, "tsm_vrb_gather_stacked: bad args");
+    const int word = (row_bytes % 4 == 0 && lane_off % 4 == 0 && lane_bytes % 4 == 0 &&
+                      ((uintptr_t)store | (uintptr_t)out) % 4 == 0) ? 4 : 1;
+    const int64_t total = n * stack_num * (lane_bytes / word);
+    TSM_REQUIRE(ceil_div(total, 256) <= 2147483647LL, "tsm_vrb_gather_stacked: too many words for one launch");
+    hipLaunchKernelGGL(vrb_gather_stacked_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, tsm_stream(stream), state, B,
+                       S, done_store, reinterpret_cast<const char *>(store), row_bytes, lane_off, lane_bytes, index, n,
+                       (int)stack_num, reinterpret_cast<char *>(out), word);
     TSM_LAUNCH_CHECK();
     return TSM_OK;
 }

@@ -32,10 +32,21 @@ class DeviceVectorReplayBuffer:
     unfused_adds_only = False
 
     def __init__(self, total_size: int, buffer_num: int, n_agent: int, obs_dim: int, device: str | torch.device = "cuda",
-                 ignore_obs_next: bool = False, store_policy_outputs: bool = True, act_dim: int | None = None,
+                 ignore_obs_next: bool = False, store_policy_outputs: bool = True, stack_num: int = 1,
+                 sample_avail: bool = False, save_only_last_obs: bool = False, act_dim: int | None = None,
                  act_branches: int | None = None) -> None:
-        """act_dim: None -- discrete actions, i32 [S, B, N]; k >= 1 -- `Box` actions of k components, f32 [S, B, N, k].
-        act_branches: K >= 1 -- MultiDiscrete actions of K integer components (BDQN), i32 [S, B, N, K]."""
+        """(`stack_num`, `sample_avail` and `save_only_last_obs` stand BEFORE `act_dim` / `act_branches`, which shifts those two for a
+        positional caller: tests/test_host_bdqn.py pins `act_branches` as the LAST parameter.  Pass everything behind
+        `store_policy_outputs` by keyword.)
+        act_dim: None -- discrete actions, i32 [S, B, N]; k >= 1 -- `Box` actions of k components, f32 [S, B, N, k].
+        act_branches: K >= 1 -- MultiDiscrete actions of K integer components (BDQN), i32 [S, B, N, K].
+        stack_num: L > 1 -- `obs` / `obs_next` of `__getitem__` / `get_device` are the L frames ending at the index, oldest
+        first, [I, L, N, D]; a stack never crosses an episode start (buffer_base.py:533-590).  sample_avail: `sample_indices`
+        keeps only indices with L - 1 distinct predecessors (buffer_base.py:523-531)."""
+        opts = self._stack_options(stack_num, sample_avail, save_only_last_obs, ignore_obs_next, act_branches)
+        # (a lazily bound subclass may have added entries of its own before the stores exist: alpha, beta)
+        self.options = {**opts, **{k: v for k, v in self.__dict__.get("options", {}).items() if k not in opts}}
+        self.stack_num, self._sample_avail = self.options["stack_num"], self.options["sample_avail"]
         if act_dim is not None and int(act_dim) < 1:
             raise ValueError(f"act_dim = {act_dim}: a Box action has at least one component (None: discrete actions)")
         if act_branches is not None and act_dim is not None:
@@ -84,6 +95,24 @@ class DeviceVectorReplayBuffer:
         self.rows_chained = "empty"
         self._host_rows: int | None = 0
         self._arange = torch.arange(self.maxsize, dtype=torch.int64, device=self.device)
+
+    @staticmethod
+    def _stack_options(stack_num, sample_avail, save_only_last_obs, ignore_obs_next, act_branches=None, aec: bool = False) -> dict:
+        """The reference's `options` (buffer_base.py:101-106) after the checks on frame stacking."""
+        stack_num = int(stack_num)
+        if stack_num < 1:
+            raise ValueError(f"stack_num should be greater than 0, got {stack_num}")
+        if stack_num > 1 and aec:
+            raise ValueError("stack_num > 1 needs joint-step rows: in an AEC buffer consecutive rows belong to different agents")
+        if stack_num > 1 and save_only_last_obs:
+            raise ValueError("save_only_last_obs (frames stacked by the env) and stack_num > 1 (frames stacked by the buffer) "
+                             "are not supported together")
+        if save_only_last_obs:
+            raise ValueError("save_only_last_obs is not supported: the device buffer stores whole observation rows")
+        if stack_num > 1 and act_branches is not None:
+            raise ValueError("stack_num > 1 is not supported with act_branches (branching learners take single frames)")
+        return dict(stack_num=stack_num, ignore_obs_next=bool(ignore_obs_next), save_only_last_obs=False,
+                    sample_avail=bool(sample_avail))
 
     def storage_key(self) -> tuple:
         """Identity of the HBM allocations behind this buffer: captured hipGraphs and cached kernel descriptors hold raw
@@ -223,6 +252,11 @@ class DeviceVectorReplayBuffer:
         if batch_size is not None and batch_size < 0:
             return np.array([], int)  # manager.py:197-199
         all_idx = self.index.sample_indices_all()
+        if self._sample_avail and self.stack_num > 1 and len(all_idx):   # buffer_base.py:523-528, per sub-buffer by prev's rule
+            back = all_idx
+            for _ in range(self.stack_num - 2):
+                back = self.index.prev(back)
+            all_idx = all_idx[self.index.prev(back) != back]
         if batch_size == 0:
             return all_idx.cpu().numpy()
         n = len(all_idx) if batch_size is None else batch_size
@@ -270,19 +304,46 @@ class DeviceVectorReplayBuffer:
     def _gather(self, store: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
         return self.index.gather(store, index)
 
+    def _gather_obs(self, store: torch.Tensor, index: torch.Tensor, stack_num: int | None = None, lane: int | None = None):
+        """`get(index, key)` of an observation store on the device: [I, N, D], or with stack_num > 1 [I, L, N, D] in one
+        launch (csrc/vrb.hip: tsm_vrb_gather_stacked); `lane`: one agent's column, [I, L, D]."""
+        L = self.stack_num if stack_num is None else int(stack_num)
+        if L == 1 and lane is None:
+            return self._gather(store, index)
+        out = self.index.gather_stacked(store, index, L, lane=lane)
+        return out[:, 0] if L == 1 else out
+
+    def get(self, index, key: str, default_value=None, stack_num: int | None = None):
+        """buffer_base.py:543-590 for the stored keys -> numpy: `stack_num` frames (None: the buffer's own) of ANY key, oldest
+        first, as the reference's `get` stacks whatever key it is asked for (`__getitem__` asks it for obs / obs_next only)."""
+        if key not in self._KEY_STORES or getattr(self, self._KEY_STORES[key]) is None:
+            if default_value is not None:
+                return default_value
+            raise KeyError(key)
+        idx = torch.as_tensor(np.atleast_1d(np.asarray(index))).to(self.device, torch.int64).reshape(-1)
+        store = getattr(self, self._KEY_STORES[key])
+        L = self.stack_num if stack_num is None else int(stack_num)
+        if L < 1:
+            raise ValueError(f"stack_num should be greater than 0, got {L}")
+        if key == "done":
+            store = store.unsqueeze(-1)
+        v = self.index.gather_stacked(store, idx, L) if L > 1 else self._gather(store, idx)
+        v = v.squeeze(-1) if key == "done" else v
+        return v.cpu().numpy()
+
     def get_device(self, index) -> dict[str, torch.Tensor]:
         """Rows by flat reference index as device tensors (ReplayBuffer.__getitem__, buffer_base.py:591-635)."""
         idx = (index if isinstance(index, torch.Tensor) else torch.as_tensor(np.asarray(index))).to(self.device, torch.int64).reshape(-1)
         out = {
-            "obs": self._gather(self.obs_store, idx), "act": self._gather(self.act_store, idx),
+            "obs": self._gather_obs(self.obs_store, idx), "act": self._gather(self.act_store, idx),
             "rew": self._gather(self.rew_store, idx), "terminated": self._gather(self.term_store, idx),
             "truncated": self._gather(self.trunc_store, idx),
             "done": self._gather(self.done_store.unsqueeze(-1), idx).squeeze(-1),
         }
         if self._save_obs_next:
-            out["obs_next"] = self._gather(self.obs_next_store, idx)
+            out["obs_next"] = self._gather_obs(self.obs_next_store, idx)
         else:  # ignore_obs_next: obs at next(index) (buffer_base.py:612-616)
-            out["obs_next"] = self._gather(self.obs_store, self.index.next(idx))
+            out["obs_next"] = self._gather_obs(self.obs_store, self.index.next(idx))
         if self.logp_store is not None:
             out["logp"] = self._gather(self.logp_store, idx)
             out["v_s"] = self._gather(self.vs_store, idx)
@@ -312,6 +373,10 @@ class DeviceVectorReplayBuffer:
     def __getattr__(self, key: str):
         # reference: buffer.rew / buffer.done / ... -> full-length arrays in flat index order
         if key in ("rew", "terminated", "truncated", "done", "obs", "act", "obs_next"):
+            if key in ("obs", "obs_next") and self.__dict__.get("stack_num", 1) > 1:   # the raw store, as the reference's buf.obs
+                if key == "obs_next" and not self._save_obs_next:
+                    raise AttributeError(key)
+                return self.get(np.arange(self.maxsize), key, stack_num=1)
             b = self.get_device(np.arange(self.maxsize))
             v = b[key].cpu().numpy()
             if key in ("terminated", "truncated", "done"):
@@ -372,7 +437,9 @@ class DeviceAECReplayBuffer(DeviceVectorReplayBuffer):
 
     def __init__(self, total_size: int, buffer_num: int, agents, obs_dim: int, n_act: int | None = None,
                  device: str | torch.device = "cuda", ignore_obs_next: bool = False, act_dim: int | None = None,
-                 act_branches: int | None = None) -> None:
+                 act_branches: int | None = None, stack_num: int = 1, sample_avail: bool = False,
+                 save_only_last_obs: bool = False) -> None:
+        self._stack_options(stack_num, sample_avail, save_only_last_obs, ignore_obs_next, aec=True)
         if act_dim is not None:
             raise NotImplementedError("DeviceAECReplayBuffer holds discrete actions only: `Box` actions (act_dim) go into a "
                                       "joint-step VectorReplayBuffer / PrioritizedVectorReplayBuffer")
@@ -484,6 +551,11 @@ class VectorReplayBuffer(DeviceVectorReplayBuffer):
     def __init__(self, total_size: int, buffer_num: int, n_agent: int | None = None, obs_dim: int | None = None,
                  device: str | torch.device = "cuda", **kwargs) -> None:
         self._lazy = dict(total_size=int(total_size), buffer_num=int(buffer_num), device=device, kwargs=kwargs)
+        # checked here, not at the first add: stack_num / sample_avail / save_only_last_obs as the reference's constructor takes them
+        self.options = self._stack_options(kwargs.get("stack_num", 1), kwargs.get("sample_avail", False),
+                                           kwargs.get("save_only_last_obs", False), kwargs.get("ignore_obs_next", False),
+                                           kwargs.get("act_branches"))
+        self.stack_num, self._sample_avail = self.options["stack_num"], self.options["sample_avail"]
         self.buffer_num = int(buffer_num)
         self.sub_size = -(-int(total_size) // self.buffer_num)
         self.maxsize = self.sub_size * self.buffer_num
@@ -548,8 +620,7 @@ class PrioritizedVectorReplayBuffer(VectorReplayBuffer):
         self._alpha, self._beta, self._weight_norm = float(alpha), float(beta), bool(weight_norm)
         self.weight = ops.DeviceSegmentTree(self.maxsize, device=device)
         self.prio = torch.ones(2, dtype=torch.float64, device=self.weight.device)
-        self.options = dict(stack_num=1, ignore_obs_next=bool(kwargs.get("ignore_obs_next", False)), save_only_last_obs=False,
-                            sample_avail=False, alpha=alpha, beta=beta)
+        self.options = dict(self.options, alpha=alpha, beta=beta)
         self.seed = int(seed)
         self._sample_ctr = 0
         self._has_rows = False  # host mirror of `len(self) > 0` (prio.py:64) that costs no device read

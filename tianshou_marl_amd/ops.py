@@ -271,6 +271,30 @@ class VrbState:
         return out
 
 
+    def gather_stacked(self, store: torch.Tensor, index: torch.Tensor, stack_num: int, lane: int | None = None) -> torch.Tensor:
+        """ReplayBuffer.get(index, key, stack_num) for one field (buffer_base.py:533-590) in one launch: the rows of a
+        [sub_size, buffer_num, ...] store at the `stack_num - 1` predecessors of `index` (prev's rule) and at `index`, oldest
+        first -> [I, stack_num, ...].  `lane`: only store[:, :, lane] of a [sub_size, buffer_num, N, ...] store -> [I, stack_num,
+        ...] without the agent axis.  Bit-identical to rounds of `prev` + `gather`."""
+        _dev_only("gather_stacked", store, index)
+        if int(stack_num) < 1:
+            raise ValueError(f"gather_stacked: stack_num {stack_num} must be >= 1")
+        if store.dim() < 2 or tuple(store.shape[:2]) != (self.sub_size, self.buffer_num) or not store.is_contiguous():
+            raise ValueError(f"gather_stacked: store must be a contiguous [{self.sub_size}, {self.buffer_num}, ...]")
+        index = _chk(index, torch.int64, "index").reshape(-1)
+        rb = store[0, 0].numel() * store.element_size()
+        row_shape, off, nb = tuple(store.shape[2:]), 0, rb
+        if lane is not None:
+            if store.dim() < 3 or not 0 <= int(lane) < store.shape[2]:
+                raise ValueError(f"gather_stacked: lane {lane} outside the store's agent axis {tuple(store.shape[2:3])}")
+            row_shape, nb = tuple(store.shape[3:]), rb // store.shape[2]
+            off = int(lane) * nb
+        out = torch.empty((index.numel(), int(stack_num), *row_shape), dtype=store.dtype, device=store.device)
+        call("tsm_vrb_gather_stacked", ptr(self.state), self.buffer_num, self.sub_size, ptr(self.done_store), ptr(store), rb, off,
+             nb, ptr(index), index.numel(), int(stack_num), ptr(out), stream_ptr())
+        return out
+
+
 # --------------------------------------------------------------------------------------------
 # agent dispatch (marl.py:148,170-180,233)
 # --------------------------------------------------------------------------------------------
@@ -1239,6 +1263,171 @@ def _head_partial(B: int, rows_per_block: int, dev) -> torch.Tensor:
 def dqn_check(n_act: int, n_step: int = 1) -> None:
     """The bounds of the DQN kernels (include/tsmarl.h): ValueError naming the limit."""
     call("tsm_dqn_check", int(n_act), int(n_step))
+
+
+def lstm_check(hidden: int, layer_num: int = 1, seq_len: int = 1) -> None:
+    """The bounds of the LSTM kernels (include/tsmarl.h): hidden a multiple of 16 in [16, 128], layer_num >= 1, seq_len >= 1;
+    ValueError naming the limit."""
+    call("tsm_lstm_check", int(hidden), int(layer_num), int(seq_len))
+
+
+def _f32(name: str, what: str, t, shape):
+    """`t` (None passes) as a contiguous device f32 tensor of `shape`."""
+    if t is None:
+        return None
+    _dev_only(name, t)
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name}: {what} must be a contiguous f32 {list(shape)}, got {list(t.shape)} {t.dtype}")
+    return t
+
+
+def _rows2(name: str, what: str, t, width: int) -> tuple:
+    """A [M, width] f32 device matrix whose rows are contiguous and `ld` floats apart -> (t, M, ld)."""
+    _dev_only(name, t)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != width or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < width):
+        raise ValueError(f"{name}: {what} must be f32 [M, {width}] with contiguous rows, got {list(t.shape)} {t.dtype} strides "
+                         f"{tuple(t.stride())}")
+    return t, t.shape[0], (t.stride(0) if t.shape[0] > 1 else width)
+
+
+def dense_linear(x, W, bias, out=None):
+    """out [M, O] = x [M, K] W [O, K]^T + bias [O] on the dense engine; the rows of x may be strided (a step of a sequence)."""
+    O, K = W.shape
+    x, M, ldx = _rows2("dense_linear", "x", x, K)
+    if M < 1:
+        raise ValueError("dense_linear: empty batch")
+    W, bias = _f32("dense_linear", "W", W, (O, K)), _f32("dense_linear", "bias", bias, (O,))
+    out = _out("dense_linear", out, (M, O), torch.float32, x.device)
+    call("tsm_dense_linear", x.data_ptr(), ldx, ptr(W), ptr(bias), M, K, O, ptr(out), stream_ptr())
+    return out
+
+
+def dense_dgrad(dz, W, out=None):
+    """dx [M, K] = dz [M, O] W [O, K]; `out` may be a strided [M, K] view (its rows contiguous)."""
+    O, K = W.shape
+    dz = _f32("dense_dgrad", "dz", dz, (dz.shape[0], O))
+    M = dz.shape[0]
+    if M < 1:
+        raise ValueError("dense_dgrad: empty batch")
+    W = _f32("dense_dgrad", "W", W, (O, K))
+    if out is None:
+        out = torch.empty(M, K, dtype=torch.float32, device=dz.device)
+    out, Mo, ld = _rows2("dense_dgrad", "out", out, K)
+    if Mo != M:
+        raise ValueError(f"dense_dgrad: out has {Mo} rows, dz {M}")
+    call("tsm_dense_dgrad", ptr(dz), ptr(W), M, O, K, out.data_ptr(), ld, stream_ptr())
+    return out
+
+
+def dense_wgrad(dz, x, slabs, n_split: int, w_off: int, b_off: int):
+    """Weight and bias gradient of one linear layer into the slabs of a flat parameter vector: slabs [n_split, P];
+    slabs[:, w_off : w_off + O K] sums to dz^T x, slabs[:, b_off : b_off + O] to the column sums of dz."""
+    dz = _f32("dense_wgrad", "dz", dz, tuple(dz.shape))
+    if dz.dim() != 2 or dz.shape[0] < 1:
+        raise ValueError("dense_wgrad: dz must be [M, O], M >= 1")
+    M, O = dz.shape
+    x, Mx, ldx = _rows2("dense_wgrad", "x", x, x.shape[-1])
+    K = x.shape[1]
+    if Mx != M:
+        raise ValueError(f"dense_wgrad: x has {Mx} rows, dz {M}")
+    _dev_only("dense_wgrad", slabs)
+    if slabs.dtype != torch.float32 or slabs.dim() != 2 or not slabs.is_contiguous() or slabs.shape[0] != int(n_split) or n_split < 1:
+        raise ValueError(f"dense_wgrad: slabs must be a contiguous f32 [{n_split}, P]")
+    P = slabs.shape[1]
+    if not (0 <= w_off and w_off + O * K <= P and 0 <= b_off and b_off + O <= P):
+        raise ValueError(f"dense_wgrad: the blocks at {w_off} (+{O * K}) and {b_off} (+{O}) leave the {P} floats of a slab")
+    call("tsm_dense_wgrad", ptr(dz), x.data_ptr(), ldx, M, O, K, int(n_split), ptr(slabs), P, int(w_off), int(b_off), stream_ptr())
+    return slabs
+
+
+def _lstm_state(name: str, what: str, t, B: int, H: int):
+    """A state operand: None, or f32 rows [B, H] that are contiguous and one common pitch apart (a layer of [B, layers, H])."""
+    if t is None:
+        return None, 0
+    t, M, ld = _rows2(name, what, t, H)
+    if M != B:
+        raise ValueError(f"{name}: {what} has {M} rows, the batch {B}")
+    return t, ld
+
+
+def _one_pitch(name: str, lds) -> int:
+    lds = {ld for ld in lds if ld}
+    if len(lds) > 1:
+        raise ValueError(f"{name}: the state operands must share one row pitch, got {sorted(lds)}")
+    return lds.pop() if lds else 0
+
+
+def lstm_forward(proj, w_hh, bias=None, h0=None, c0=None, h_n=None, c_n=None, save: bool = True):
+    """One LSTM layer through all L steps in one launch (include/tsmarl.h: tsm_lstm_forward).  proj [B, L, 4H] = the input
+    projection with b_ih; bias [4H] = b_hh; h0, c0 [B, H] or None (zeros); h_n, c_n [B, H] outputs, fresh when None, and
+    allowed to BE h0, c0 (the acting step).  State operands may be strided rows of a [B, layers, H] tensor.
+    -> dict(h [B, L, H], h_n, c_n, and with `save`: h_prev [B, L, H], gates [B, L, 4H], c [B, L, H])."""
+    _dev_only("lstm_forward", proj, w_hh, bias)
+    if proj.dim() != 3 or proj.shape[2] % 4:
+        raise ValueError(f"lstm_forward: proj must be [B, L, 4H], got {list(proj.shape)}")
+    B, L, H = proj.shape[0], proj.shape[1], proj.shape[2] // 4
+    lstm_check(H, 1, L)
+    if B < 1:
+        raise ValueError("lstm_forward: empty batch")
+    proj, w_hh = _f32("lstm_forward", "proj", proj, (B, L, 4 * H)), _f32("lstm_forward", "w_hh", w_hh, (4 * H, H))
+    bias = _f32("lstm_forward", "bias", bias, (4 * H,))
+    dev = proj.device
+    if h_n is None:
+        h_n = torch.empty(B, H, dtype=torch.float32, device=dev)
+    if c_n is None:
+        c_n = torch.empty(B, H, dtype=torch.float32, device=dev)
+    (h0, l0), (c0, l1) = _lstm_state("lstm_forward", "h0", h0, B, H), _lstm_state("lstm_forward", "c0", c0, B, H)
+    (h_n, l2), (c_n, l3) = _lstm_state("lstm_forward", "h_n", h_n, B, H), _lstm_state("lstm_forward", "c_n", c_n, B, H)
+    ld = _one_pitch("lstm_forward", (l0, l1, l2, l3))
+    out = dict(h=torch.empty(B, L, H, dtype=torch.float32, device=dev), h_n=h_n, c_n=c_n)
+    if save:
+        out.update(h_prev=torch.empty(B, L, H, dtype=torch.float32, device=dev),
+                   gates=torch.empty(B, L, 4 * H, dtype=torch.float32, device=dev),
+                   c=torch.empty(B, L, H, dtype=torch.float32, device=dev))
+    dp = lambda t: None if t is None else t.data_ptr()  # noqa: E731  (strided rows: `ptr` wants contiguous tensors)
+    call("tsm_lstm_forward", ptr(proj), ptr(w_hh), ptr(bias), dp(h0), dp(c0), ld, B, L, H, ptr(out["h"]), ptr(out.get("h_prev")),
+         ptr(out.get("gates")), ptr(out.get("c")), dp(h_n), dp(c_n), stream_ptr())
+    return out
+
+
+def lstm_backward(d_h, w_hh, gates, c, c0=None, d_hn=None, d_cn=None, want_state_grad: bool = False):
+    """The backward through time of `lstm_forward` in one launch: d_h [B, L, H] arriving at every step from above, d_hn, d_cn
+    [B, H] or None at the final state; gates, c as saved; c0 as given to the forward.
+    -> dict(d_gates [B, L, 4H], and with `want_state_grad`: d_h0, d_c0 [B, H])."""
+    _dev_only("lstm_backward", d_h, w_hh, gates, c)
+    if d_h.dim() != 3:
+        raise ValueError(f"lstm_backward: d_h must be [B, L, H], got {list(d_h.shape)}")
+    B, L, H = d_h.shape
+    lstm_check(H, 1, L)
+    if B < 1:
+        raise ValueError("lstm_backward: empty batch")
+    d_h, w_hh = _f32("lstm_backward", "d_h", d_h, (B, L, H)), _f32("lstm_backward", "w_hh", w_hh, (4 * H, H))
+    gates, c = _f32("lstm_backward", "gates", gates, (B, L, 4 * H)), _f32("lstm_backward", "c", c, (B, L, H))
+    dev = d_h.device
+    out = dict(d_gates=torch.empty(B, L, 4 * H, dtype=torch.float32, device=dev))
+    if want_state_grad:
+        out.update(d_h0=torch.empty(B, H, dtype=torch.float32, device=dev), d_c0=torch.empty(B, H, dtype=torch.float32, device=dev))
+    states = [_lstm_state("lstm_backward", n, t, B, H) for n, t in (("c0", c0), ("d_hn", d_hn), ("d_cn", d_cn),
+                                                                    ("d_h0", out.get("d_h0")), ("d_c0", out.get("d_c0")))]
+    ld = _one_pitch("lstm_backward", [l for _, l in states])
+    dp = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    c0, d_hn, d_cn, d_h0, d_c0 = (t for t, _ in states)
+    call("tsm_lstm_backward", ptr(d_h), dp(d_hn), dp(d_cn), ptr(w_hh), ptr(gates), ptr(c), dp(c0), ld, B, L, H, ptr(out["d_gates"]),
+         dp(d_h0), dp(d_c0), stream_ptr())
+    return out
+
+
+def lstm_state_reset(h, c, done, rows_per_env: int = 1) -> None:
+    """Zero the state rows of finished envs in place (collector.py:977-979): h, c f32 [E * rows_per_env, ...], done u8 / bool
+    [E].  One launch without a host read: safe inside a captured graph."""
+    _dev_only("lstm_state_reset", h, c, done)
+    done = done.contiguous().view(torch.uint8) if done.dtype == torch.bool else _chk(done, torch.uint8, "done")
+    E, R = done.numel(), int(rows_per_env)
+    if R < 1 or h.shape != c.shape or h.dtype != torch.float32 or c.dtype != torch.float32 or h.dim() < 2 or h.shape[0] != E * R \
+            or not (h.is_contiguous() and c.is_contiguous()):
+        raise ValueError(f"lstm_state_reset: h and c must be contiguous f32 [{E * R}, ...] for {E} envs of {R} rows")
+    if E:
+        call("tsm_lstm_state_reset", ptr(h), ptr(c), ptr(done), E, R, h[0].numel(), stream_ptr())
 
 
 def nstep_return(index: "VrbState", term_store, rew_store, indices, n_step: int, gamma: float, rew_col: int = 0,

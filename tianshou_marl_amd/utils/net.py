@@ -364,6 +364,122 @@ class FlatMLP(FlatNet):
         return self.named_layers(ref_layer_keys(self.n_layers, self.ref_scheme), flat=flat)
 
 
+# ---- the recurrent net (utils/net/common.py:372-458) -----------------------------------------------------------------------
+class Recurrent(FlatNet):
+    """The reference's `Recurrent`: fc1 -> nn.LSTM(hidden, hidden, layer_num, batch_first) -> fc2 on the last step, as ONE flat
+    vector in the reference's `state_dict()` order (nn.weight_ih_l0, nn.weight_hh_l0, nn.bias_ih_l0, nn.bias_hh_l0, ..., fc1.weight,
+    fc1.bias, fc2.weight, fc2.bias).  The recurrence runs in csrc/lstm.hip, one launch per layer for all steps; the input
+    projections, fc1, fc2 and every weight gradient on the dense engine (csrc/dense.hip).
+
+    `forward(obs [B, L, D] | [B, D], state=None)` -> (out [B, A], state), state = (hidden, cell) in HBM as [B, layers, H];
+    `state_out=(hidden, cell)` writes the new state there, and may be `state` itself: the acting step advances it in place.
+    `backward(d_out)` -> gradient slabs [n_split, n_param] of sum(out * d_out) for the last `forward(save=True)`."""
+
+    def __init__(self, *, layer_num: int, state_shape, action_shape, hidden_layer_size: int = 128,
+                 device: str | torch.device = "cuda", seed: int | None = None, storage: torch.Tensor | None = None) -> None:
+        super().__init__()
+        self.layer_num, self.hidden = int(layer_num), int(hidden_layer_size)
+        self.obs_dim, self.n_out = int(np.prod(state_shape)), int(np.prod(action_shape))
+        self.dims = [self.obs_dim, self.n_out]   # input and output width, as a FlatMLP states them
+        ops.lstm_check(self.hidden, self.layer_num)
+        if self.obs_dim < 1 or self.n_out < 1:
+            raise ValueError(f"Recurrent: state_shape {state_shape} and action_shape {action_shape} must be non-empty")
+        H = self.hidden
+        shapes = [(f"nn.{p}_l{k}", sh) for k in range(self.layer_num)
+                  for p, sh in (("weight_ih", (4 * H, H)), ("weight_hh", (4 * H, H)), ("bias_ih", (4 * H,)), ("bias_hh", (4 * H,)))]
+        shapes += [("fc1.weight", (H, self.obs_dim)), ("fc1.bias", (H,)), ("fc2.weight", (self.n_out, H)), ("fc2.bias", (self.n_out,))]
+        self._layout, o = [], 0
+        for key, sh in shapes:
+            self._layout.append((key, o, sh))
+            o += math.prod(sh)
+        self._off = {key: off for key, off, _ in self._layout}
+        self._claim(o, storage, device)
+        self.reset_parameters(seed)
+
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        v = self._vector(flat)
+        return [(key, v[o:o + math.prod(sh)].view(sh)) for key, o, sh in self._layout]
+
+    @torch.no_grad()
+    def reset_parameters(self, seed: int | None = None) -> None:
+        """torch's defaults: every nn.LSTM parameter uniform in +-1 / sqrt(hidden); nn.Linear uniform in +-1 / sqrt(fan_in)."""
+        gen = _generator(seed)
+        for key, v in self.reference_named_views():
+            fan = self.hidden if key.startswith("nn.") or key.startswith("fc2") else self.obs_dim
+            v.copy_(_uniform(v.shape, 1.0 / math.sqrt(fan), gen))
+
+    def zero_state(self, B: int) -> tuple[torch.Tensor, torch.Tensor]:
+        z = torch.zeros(2, B, self.layer_num, self.hidden, dtype=torch.float32, device=self.flat.device)
+        return z[0], z[1]
+
+    def _state(self, what: str, state, B: int):
+        if state is None:
+            return None
+        if not isinstance(state, (tuple, list)):
+            if not {"hidden", "cell"}.issubset(state.keys()):
+                raise ValueError(f"Expected to find keys 'hidden' and 'cell' but instead found {state.keys()}")
+            state = (state["hidden"], state["cell"])
+        shape = (B, self.layer_num, self.hidden)
+        out = []
+        for nm, t in zip(("hidden", "cell"), state):
+            t = torch.as_tensor(t)
+            if what == "state":   # an input: any source, brought to the device
+                t = t.to(self.flat.device, torch.float32).contiguous()
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"Recurrent: {what}.{nm} must be a contiguous device f32 {list(shape)}, got {list(t.shape)} {t.dtype}")
+            out.append(t)
+        return tuple(out)
+
+    def forward(self, obs, state=None, info=None, save: bool = True, state_out=None):
+        v, H, dev = self.flat.data, self.hidden, self.flat.device
+        obs = torch.as_tensor(obs).to(dev, torch.float32)
+        if obs.dim() == 2:
+            obs = obs.unsqueeze(1)
+        if obs.dim() != 3 or obs.shape[2] != self.obs_dim:
+            raise ValueError(f"Recurrent: obs must be [B, L, {self.obs_dim}] or [B, {self.obs_dim}], got {list(obs.shape)}")
+        obs = obs.contiguous()
+        B, L = obs.shape[:2]
+        ops.lstm_check(H, self.layer_num, L)
+        state = self._state("state", state, B)
+        hn, cn = self._state("state_out", state_out, B) if state_out is not None else self.zero_state(B)
+        views = dict(self.reference_named_views())
+        x = ops.dense_linear(obs.view(B * L, self.obs_dim), views["fc1.weight"], views["fc1.bias"])
+        xs, layers = [], []
+        for k in range(self.layer_num):
+            proj = ops.dense_linear(x, views[f"nn.weight_ih_l{k}"], views[f"nn.bias_ih_l{k}"]).view(B, L, 4 * H)
+            fw = ops.lstm_forward(proj, views[f"nn.weight_hh_l{k}"], views[f"nn.bias_hh_l{k}"],
+                                  None if state is None else state[0][:, k], None if state is None else state[1][:, k],
+                                  hn[:, k], cn[:, k], save=save)
+            xs.append(x)
+            layers.append(fw)
+            x = fw["h"].view(B * L, H)
+        out = ops.dense_linear(x.view(B, L, H)[:, L - 1], views["fc2.weight"], views["fc2.bias"])
+        if save:
+            self._saved = (obs, xs, layers, None if state is None else state[1])
+        return out, (hn, cn)
+
+    def backward(self, d_out: torch.Tensor, n_split: int = 0, slabs: torch.Tensor | None = None) -> torch.Tensor:
+        obs, xs, layers, c0 = self._saved_forward()
+        B, L = obs.shape[:2]
+        H, R, off = self.hidden, B * L, self._off
+        n_split, slabs = self._slabs(R, n_split, slabs)
+        views = dict(self.reference_named_views())
+        d_out = d_out.reshape(B, self.n_out).to(torch.float32).contiguous()
+        top = layers[-1]["h"]
+        ops.dense_wgrad(d_out, top[:, L - 1], slabs, n_split, off["fc2.weight"], off["fc2.bias"])
+        d_h = torch.zeros(B, L, H, dtype=torch.float32, device=obs.device)   # from above: only the last step of the top layer
+        ops.dense_dgrad(d_out, views["fc2.weight"], out=d_h[:, L - 1])
+        for k in range(self.layer_num - 1, -1, -1):
+            fw = layers[k]
+            dg = ops.lstm_backward(d_h, views[f"nn.weight_hh_l{k}"], fw["gates"], fw["c"],
+                                   None if c0 is None else c0[:, k])["d_gates"].view(R, 4 * H)
+            ops.dense_wgrad(dg, xs[k], slabs, n_split, off[f"nn.weight_ih_l{k}"], off[f"nn.bias_ih_l{k}"])
+            ops.dense_wgrad(dg, fw["h_prev"].view(R, H), slabs, n_split, off[f"nn.weight_hh_l{k}"], off[f"nn.bias_hh_l{k}"])
+            d_h = ops.dense_dgrad(dg, views[f"nn.weight_ih_l{k}"]).view(B, L, H)
+        ops.dense_wgrad(d_h.view(R, H), obs.view(R, self.obs_dim), slabs, n_split, off["fc1.weight"], off["fc1.bias"])
+        return slabs
+
+
 # ---- the continuous-action nets (utils/net/continuous.py) ---------------------------------------------------------------
 class _ContinuousNet(FlatMLP):
     """A `FlatMLP` under the reference's `Net(hidden_sizes=[...])` + `last` key names."""
