@@ -516,6 +516,20 @@ typedef struct {
 } tsm_rollout_desc;
 
 int tsm_rollout_spread(const tsm_rollout_desc *desc_host, void *stream);
+/* tsm_rollout_spread, and on the CUs its workgroups leave idle the draw of the permutations of the update that follows the
+ * collect: perm_out [n_perm][perm_n] as tsm_random_permutations(perm_n, n_perm, perm_seed, 0, perm_counter_dev, perm_scale,
+ * perm_group_size, perm_offset_mul, perm_out) writes it, bit for bit, without that launch.  *perm_counter_dev is read, never
+ * written: whoever advances it today still does.  The ride-along is taken only where the launch is the eight-wave tile form with
+ * fewer workgroups than the device has CUs (tsm_rollout_prep_extra > 0); *taken_out (host) says whether: 1 = perm_out is
+ * filled behind this launch, 0 = the launch was exactly tsm_rollout_spread's and the caller draws the permutations itself.
+ * perm_out NULL (or perm_n / n_perm 0): no request, tsm_rollout_spread.  n_cu: 0 = the device's CU count, else the count the
+ * rule is to assume (tests). */
+int tsm_rollout_spread_prep(const tsm_rollout_desc *desc_host, int64_t perm_n, int32_t n_perm, uint64_t perm_seed,
+                            const uint64_t *perm_counter_dev, int64_t perm_scale, int32_t perm_group_size,
+                            int64_t perm_offset_mul, int64_t *perm_out, int32_t n_cu, int32_t *taken_out, void *stream);
+/* The rule itself, on the host: *extra_out = the spare workgroups a launch of `tiles` rollout workgroups gets on n_cu CUs for
+ * n_perm permutations of perm_n entries -- min(idle CUs, one per 512 entries, 64); 0 = the request is declined. */
+int tsm_rollout_prep_extra(int64_t tiles, int32_t n_cu, int64_t perm_n, int32_t n_perm, int32_t *extra_out);
 /* The same collect loop for a 128-wide ACTOR (obs -> 128 -> 128 -> 5, e.g. BASELINE configs[2]: N = 8, actor
  * 48-128-128-5 next to a centralized critic that does not fit a CU's LDS): desc.params = the actor's parameters
  * (w0 b0 w1 b1 w2 b2), desc.hidden = 128, param_image unused; vs_store / vnext_store are NOT written -- the update

@@ -98,6 +98,12 @@ class PPO(nn.Module):
         self.eps_clip, self.dual_clip, self.value_clip = eps_clip, dual_clip, value_clip
         self.advantage_normalization, self.recompute_adv = advantage_normalization, recompute_advantage
         self.pack_rows = True  # the statistics launch also gathers the minibatches' rows for the gradient steps (`_minibatch_plan`)
+        # the collect's rollout launch draws the next captured update's permutations on the CUs it leaves idle
+        # (`rollout_prep_request`); False: they keep their own launch at the head of the update graph
+        self.rollout_prep = True
+        self._prep_offer = None   # the captured update whose permutations a collect may draw: (graph key, its workspace)
+        self._prep_gen = 0        # requests handed out so far
+        self._prep_filled = None  # what the last collect's launch reported as drawn: (generation, graph key, optimizer step count)
         self.vf_coef, self.ent_coef, self.max_grad_norm = vf_coef, ent_coef, max_grad_norm
         self.gae_lambda, self.gamma, self.max_batchsize = gae_lambda, gamma, max_batchsize
         self.return_scaling, self.ret_rms, self._eps = return_scaling, DeviceRunningMeanStd(net.flat.device), 1e-8
@@ -177,6 +183,25 @@ class PPO(nn.Module):
 
     def add_exploration_noise(self, act, batch):
         return act
+
+    def rollout_prep_request(self, buffer: DeviceVectorReplayBuffer) -> dict | None:
+        """What the Collector's persistent rollout launch may do for the update that follows it, under
+        `policy_within_training_step`: draw the permutations of the captured update (`_update_graph`) into that update's own
+        buffer, at the draw counter the update would use -- its device-resident optimizer step count, which nothing advances
+        between the collect and the update.  None: nothing to offer (no captured update yet for this buffer, the switch is off,
+        the device-side count is stale).  The launcher may still decline; `rollout_prep_done` hears what it did."""
+        self._prep_filled = None
+        if not (self.rollout_prep and self.is_within_training_step and self._prep_offer is not None):
+            return None
+        key, g = self._prep_offer
+        if self._ws.get(key) is not g or key[1] != buffer.storage_key() or g.get("step_host") != self.opt_step:
+            return None
+        self._prep_gen += 1
+        return dict(g["perm_request"], gen=self._prep_gen, key=key)
+
+    def rollout_prep_done(self, req: dict, taken: bool) -> None:
+        """The launch that got `req` has been issued; taken: it draws the permutations (else the update draws them itself)."""
+        self._prep_filled = (req["gen"], req["key"], self.opt_step) if taken else None
 
     # ---- update side --------------------------------------------------------------------------
     def _valid_rows(self, buffer: DeviceVectorReplayBuffer):
@@ -611,11 +636,13 @@ class PPO(nn.Module):
                                            out=dict(value=w["v_next"].view(-1), logits=None))
                 self._gae(w["v_s"], w["v_next"], rew, term, trunc, N, out=(w["ret"], w["adv"]))
 
+            skip_perm = [False]   # (capturing the "prepared" variant: the permutations are in w["perm"] already)
+
             def body():
                 # a generator: everything is launched in order; it yields the tensors that must be summed over the ranks at
                 # that point (data parallel only), so that one definition serves the single captured graph (collectives
                 # inside), and the segmented form (a graph per stretch between two collectives, collectives eager)
-                if self.shuffle == "device":
+                if self.shuffle == "device" and not skip_perm[0]:
                     # every permutation of this update (one per agent group and repeat, batch.py:1219) in ONE launch;
                     # the draw counter is the device-resident optimizer step count (it advances by >= one per permutation
                     # and update), so each replay of the graph draws fresh permutations without a counter kernel
@@ -663,13 +690,42 @@ class PPO(nn.Module):
                               segmented=self._grad_sync is not None and not self.graph_collectives)
             if self.shuffle == "numpy":
                 w["ref_ids"] = self._ref_ids(T, B, N, groups)
+            # The "prepared" variant of the captured update: the same launches without the permutation draw, for updates behind a
+            # collect whose rollout launch drew them (`rollout_prep_request`).  Which variant replays is decided on the host per
+            # call; nothing inside a graph changes.  Offered where the headline path runs: one GPU, advantages normalised over
+            # packed minibatches, no recompute_advantage.
+            if (self.shuffle == "device" and self._grad_sync is None and not self.recompute_adv
+                    and self.advantage_normalization and w["packed"] is not None):
+                w["perm_request"] = dict(out=w["perm"], n=n_g, n_perm=len(groups) * repeat, seed=self.seed ^ 0x5DEECE66D,
+                                         counter_dev=w["step_dev"], scale=N if per_agent else 1, group_size=repeat,
+                                         offset_mul=1 if per_agent else 0)
+
+                def capture_prepared():
+                    w2: dict = {}
+                    skip_perm[0] = True
+                    try:
+                        ops.capture_steps(w2, body, self._sum_over_ranks, capture=self._capture_graph)
+                    finally:
+                        skip_perm[0] = False
+                    w["graph_prep"] = w2["graph"]
+
+                w["capture_prepared"] = capture_prepared
             self._ws[key] = g = w
         # fresh permutations for this update (Batch.split draws one per repeat, batch.py:1219)
         # shuffle == "device": the permutations are drawn inside the graph (tsm_random_permutations)
         self._refill_host_perms(g)
-        self._refill_step_dev(g)
-        ops.replay_steps(g, self._sum_over_ranks)
+        filled, self._prep_filled = self._prep_filled, None
+        if (self.rollout_prep and "perm_request" in g and g.get("step_host") == self.opt_step
+                and filled == (self._prep_gen, key, self.opt_step)):
+            # the rollout launch of the collect just before drew this update's permutations, at this very step count
+            if g.get("graph_prep") is None:
+                g["capture_prepared"]()
+            g["graph_prep"].replay()
+        else:
+            self._refill_step_dev(g)
+            ops.replay_steps(g, self._sum_over_ranks)
         self._account_steps(g)
+        self._prep_offer = (key, g) if self.rollout_prep and "perm_request" in g else None
         # loss statistics (reference: 4 .item() per minibatch): one launch folds the loss partials of EVERY gradient step
         # and writes the result straight into a pinned (mapped) host slot -- no D2H copy on the stream; the host only
         # blocks when the stats are read

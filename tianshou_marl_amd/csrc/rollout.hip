@@ -16,9 +16,12 @@
 // Extra output v_next = V(obs_next) (needed by GAE, a2c.py:124): for rows whose episode continues it is the
 // critic value of the next step's forward; for finished episodes the terminal observation gets its own
 // forward pass before the env is re-initialised; the last step is bootstrapped after the loop.
+#include <algorithm>
+
 #include "common.h"
 #include "mlp_tile.h"
 #include "mpe_dev.h"
+#include "perm_dev.h"
 #include "philox.h"
 #include "rollout_dev.h"
 #include "rollout_fwd.h"
@@ -46,6 +49,9 @@ struct RolloutArgs {
     float *obs_cur_out;  // [n_env][N][D] next policy input after the rollout
     RolloutBufArgs b;   // buffer, per-step outputs, episode record, counter advance
     long long *stamps;  // diagnostic build only (tsm_debug_set_stamps): phase time stamps of workgroup 0
+    // rollout_kernel<.., PERM = true> only: workgroups [0, tiles) run the rollout, the others draw the update's permutations
+    int tiles;
+    PermReq perm;
 };
 
 
@@ -99,9 +105,19 @@ struct RtLay {
 // DS / NS: 0 = obs width / agent count from the launch arguments, else the values this instantiation is compiled for (BASELINE
 // configs[1]: 18 / 3): the per-step element loops divide by D, N and ld1 -- ~35-instruction integer divisions when those are run-time
 // values, a multiply and a shift when they are constants.
-template <int H, int NT2, int DS = 0, int NS = 0>
+// PERM: the launch carries spare workgroups, one per CU the tiles leave idle (blockIdx.x >= a.tiles).  They draw the permutations
+// of the update that follows this collect (perm_dev.h) and return: no rollout LDS, no barrier, no arrival at the counter advance --
+// which then counts a.tiles workgroups.  The request depends on nothing the rollout computes, and an entry's bits on nothing
+// but its key, counter and index: the draw of tsm_random_permutations without its launch.
+template <int H, int NT2, int DS = 0, int NS = 0, bool PERM = false>
 __global__ __launch_bounds__(NT2) void rollout_kernel(RolloutArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    if constexpr (PERM) {
+        if ((int)blockIdx.x >= a.tiles) {   // (uniform per workgroup)
+            perm_fill(a.perm, (int)blockIdx.x - a.tiles, (int)gridDim.x - a.tiles);
+            return;
+        }
+    }
     const Dims d = DS ? dims_const(DS, 5) : a.d;
     MpeCfg c_ = a.c;
     if (NS) { c_.N = NS; c_.obs_dim = DS; }
@@ -454,7 +470,9 @@ __global__ __launch_bounds__(NT2) void rollout_kernel(RolloutArgs a) {
         vl.store(vs, a.b.ep_rec, be);
     }
     if (ret_lane) epr.store(vs, N, e0 + rq);
-    rollout_advance_counter(a.b.done_ctr, a.b.offset_dev_rw, a.b.offset_inc, threadIdx.x == 0);   // (every workgroup read it, off0, before finishing)
+    // (every workgroup read it, off0, before finishing)
+    if constexpr (PERM) rollout_advance_counter(a.b.done_ctr, a.b.offset_dev_rw, a.b.offset_inc, threadIdx.x == 0, (unsigned)a.tiles);
+    else rollout_advance_counter(a.b.done_ctr, a.b.offset_dev_rw, a.b.offset_inc, threadIdx.x == 0);
 }
 
 // ---- wave-autonomous form ------------------------------------------------------------------------------------------------
@@ -781,10 +799,23 @@ TSM_EXPORT int tsm_u64_add(uint64_t *counter, uint64_t inc, void *stream) {
     return TSM_OK;
 }
 
-TSM_EXPORT int tsm_rollout_spread(const tsm_rollout_desc *desc_host, void *stream) {
+// The ride-along rule: how many spare workgroups a rollout launch of `tiles` eight-wave workgroups gets for a
+// permutation request of `entries` entries on a device of n_cu CUs; 0 = none, the permutations keep their own launch.  Every
+// workgroup of the launch requests the launch's LDS and therefore holds a CU: never more than the CUs the tiles leave idle, and
+// never more than give each of their 512 threads an entry.
+static int rollout_prep_extra(int64_t tiles, int n_cu, int64_t entries) {
+    if (entries <= 0 || tiles >= n_cu) return 0;
+    const int64_t idle = n_cu - tiles, useful = ceil_div(entries, (int64_t)(2 * NT));
+    return (int)std::min<int64_t>(std::min<int64_t>(idle, useful), 64);
+}
+
+// prep: the permutation request (NULL: none); taken (nullable): set to 1 when the launch serves it
+static int rollout_spread_launch(const tsm_rollout_desc *desc_host, const PermReq *prep, int n_cu, int32_t *taken, void *stream) {
     TSM_REQUIRE(desc_host, "tsm_rollout_spread: null descriptor");
     const tsm_rollout_desc &h = *desc_host;
     RolloutArgs a;
+    a.tiles = 0;
+    a.perm = PermReq{};
     if (int rc = make_dims(h.obs_dim, h.hidden, h.n_act, &a.d)) return rc;
     if (int rc = tsm_mpe_check_cfg(&h.env, &a.c)) return rc;
     TSM_REQUIRE(a.c.obs_dim == h.obs_dim, "tsm_rollout_spread: obs_dim %d != 6 * n_agent", h.obs_dim);
@@ -861,6 +892,22 @@ TSM_EXPORT int tsm_rollout_spread(const tsm_rollout_desc *desc_host, void *strea
     // collect, 4 / 8 waves): 1024 envs x 3 agents 242 / 234; 4096 x 3: 505 / 775; 4096 x 8 (91 KB of LDS): 7100 / 2250.
     const bool eight = n_wg <= 256 || shmem > 80 * 1024;
     const bool c18 = a.d.D == 18 && a.d.A == 5 && a.c.N == 3 && !tsm_opt(TSM_OPT_GENERIC);   // ("generic_kernels": the generic form)
+    const int extra = prep && eight ? rollout_prep_extra(n_wg, n_cu, prep->n * prep->n_perm) : 0;
+    if (extra > 0) {
+        static bool attr_prep = false;
+        if (!attr_prep) {
+            TSM_HIP(tsm_allow_max_lds(reinterpret_cast<const void *>(rollout_kernel<64, 2 * NT, 0, 0, true>)));
+            TSM_HIP(tsm_allow_max_lds(reinterpret_cast<const void *>(rollout_kernel<64, 2 * NT, 18, 3, true>)));
+            attr_prep = true;
+        }
+        a.tiles = (int)n_wg;
+        a.perm = *prep;
+        if (c18) hipLaunchKernelGGL((rollout_kernel<64, 2 * NT, 18, 3, true>), dim3(n_wg + extra), dim3(2 * NT), shmem, tsm_stream(stream), a);
+        else hipLaunchKernelGGL((rollout_kernel<64, 2 * NT, 0, 0, true>), dim3(n_wg + extra), dim3(2 * NT), shmem, tsm_stream(stream), a);
+        TSM_LAUNCH_CHECK();
+        if (taken) *taken = 1;
+        return TSM_OK;
+    }
     if (eight && c18) hipLaunchKernelGGL((rollout_kernel<64, 2 * NT, 18, 3>), dim3(n_wg), dim3(2 * NT), shmem, tsm_stream(stream), a);
     else if (eight) hipLaunchKernelGGL((rollout_kernel<64, 2 * NT>), dim3(n_wg), dim3(2 * NT), shmem, tsm_stream(stream), a);
     else hipLaunchKernelGGL((rollout_kernel<64, NT>), dim3(n_wg), dim3(NT), shmem, tsm_stream(stream), a);
@@ -868,3 +915,40 @@ TSM_EXPORT int tsm_rollout_spread(const tsm_rollout_desc *desc_host, void *strea
     return TSM_OK;
 }
 
+TSM_EXPORT int tsm_rollout_spread(const tsm_rollout_desc *desc_host, void *stream) {
+    return rollout_spread_launch(desc_host, nullptr, 0, nullptr, stream);
+}
+
+TSM_EXPORT int tsm_rollout_prep_extra(int64_t tiles, int32_t n_cu, int64_t perm_n, int32_t n_perm, int32_t *extra_out) {
+    TSM_REQUIRE(extra_out, "tsm_rollout_prep_extra: null output");
+    TSM_REQUIRE(tiles >= 0 && n_cu >= 0 && perm_n >= 0 && n_perm >= 0, "tsm_rollout_prep_extra: negative argument");
+    *extra_out = rollout_prep_extra(tiles, n_cu, perm_n * n_perm);
+    return TSM_OK;
+}
+
+TSM_EXPORT int tsm_rollout_spread_prep(const tsm_rollout_desc *desc_host, int64_t perm_n, int32_t n_perm, uint64_t perm_seed,
+                                       const uint64_t *perm_counter_dev, int64_t perm_scale, int32_t perm_group_size,
+                                       int64_t perm_offset_mul, int64_t *perm_out, int32_t n_cu, int32_t *taken_out, void *stream) {
+    TSM_REQUIRE(taken_out, "tsm_rollout_spread_prep: null taken_out");
+    *taken_out = 0;
+    if (!perm_out || perm_n == 0 || n_perm == 0) return rollout_spread_launch(desc_host, nullptr, 0, nullptr, stream);
+    // (the checks of tsm_random_permutations, whose launch this replaces)
+    TSM_REQUIRE(perm_n > 0 && perm_n < ((int64_t)1 << 30), "tsm_rollout_spread_prep: perm_n=%lld out of range [0, 2^30)", (long long)perm_n);
+    TSM_REQUIRE(n_perm > 0 && n_perm <= 65535, "tsm_rollout_spread_prep: n_perm out of range");
+    TSM_REQUIRE(perm_group_size >= 1, "tsm_rollout_spread_prep: perm_group_size must be >= 1");
+    TSM_REQUIRE(perm_counter_dev, "tsm_rollout_spread_prep: the permutation request needs its device counter");
+    TSM_REQUIRE(n_cu >= 0, "tsm_rollout_spread_prep: negative n_cu");
+    if (n_cu == 0) {   // 0: the device's own count
+        static int dev_cu = 0;
+        if (!dev_cu) {
+            int dev = 0;
+            TSM_HIP(hipGetDevice(&dev));
+            TSM_HIP(hipDeviceGetAttribute(&dev_cu, hipDeviceAttributeMultiprocessorCount, dev));
+        }
+        n_cu = dev_cu;
+    }
+    PermReq q;
+    q.out = perm_out; q.counter_dev = perm_counter_dev; q.n = perm_n; q.scale = perm_scale; q.offset_mul = perm_offset_mul;
+    q.seed = perm_seed; q.n_perm = n_perm; q.group_size = perm_group_size; q.hb = perm_half_bits(perm_n);
+    return rollout_spread_launch(desc_host, &q, n_cu, taken_out, stream);
+}

@@ -86,11 +86,16 @@ struct EpReturns {
 
 // The last workgroup to get here advances the sampling counter: every workgroup has read it before finishing.  Called at the very
 // end of the kernel; `first` = this is the workgroup's thread 0.
-__device__ __forceinline__ void rollout_advance_counter(uint32_t *done_ctr, uint64_t *offset_dev_rw, uint64_t offset_inc, bool first) {
+// n_wg: the workgroups that arrive here (a launch may carry others that never read the counter).
+__device__ __forceinline__ void rollout_advance_counter(uint32_t *done_ctr, uint64_t *offset_dev_rw, uint64_t offset_inc, bool first,
+                                                        unsigned n_wg) {
     if (done_ctr && first) {
-        if (atomicAdd(done_ctr, 1u) == gridDim.x - 1) {
+        if (atomicAdd(done_ctr, 1u) == n_wg - 1) {
             *offset_dev_rw += offset_inc;
             *done_ctr = 0u;
         }
     }
+}
+__device__ __forceinline__ void rollout_advance_counter(uint32_t *done_ctr, uint64_t *offset_dev_rw, uint64_t offset_inc, bool first) {
+    rollout_advance_counter(done_ctr, offset_dev_rw, offset_inc, first, gridDim.x);
 }
