@@ -220,6 +220,15 @@ class VectorReplayBufferIndex:
     def done(self) -> np.ndarray:
         return np.ctypeslib.as_array(self._l.orc_vrb_done(self._h), (self.maxsize,)).astype(bool)
 
+    def state(self) -> dict:
+        """The sub-buffers' `_insertion_idx / _size / _ep_len / _ep_start_idx / _ep_return` (buffer_base.py) with the manager's
+        `last_index / _lengths`."""
+        i64 = np.zeros((4, self.buffer_num), np.int64)
+        ret = np.zeros((self.buffer_num, self.rew_dim), np.float64)
+        self._l.orc_vrb_state(self._h, _p(i64, C.c_int64), _p(ret, C.c_double))
+        return dict(ins=i64[0], size=i64[1], ep_len=i64[2], ep_start=i64[3], last_index=self.last_index, lengths=self.lengths,
+                    ep_return=ret)
+
 
 def split_bounds(length: int, size: int, merge_last: bool = True):
     """`Batch.split` slice bounds, tianshou/data/batch.py:1209-1225."""

@@ -37,8 +37,9 @@ def _job(n_env, N, T, fused, seed=3, slots=None, **ppo_kw):
 @pytest.mark.parametrize("form", ["wave", "tile"])
 def test_fused_rollout_is_bit_identical_to_unfused(n_env, N, T, steps, form):
     """Both forms of the 64-wide persistent rollout (option "rollout_form": the wave-autonomous one -- a wave owns 16 // N whole envs
-    and runs actor, critic, heads, env step and buffer rows by itself; workgroups of 1, 2 or 4 such waves: (300, 3) / (600, 3) /
-    (1024, 3) -- and the eight- / four-wave tile form) against the unfused launch sequence."""
+    and runs actor, critic, heads, env step and buffer rows by itself; a workgroup has 1 such wave up to 256 waves in all, 2 up to 512, 4
+    above: (1400, 3) = 280 waves and (2100, 2) = 263 take two, every other size here one, and tests/test_gpu_rollout_ring.py runs
+    four at (2600, 3) -- and the eight- / four-wave tile form) against the unfused launch sequence."""
     slots = steps + 3 + 1  # both collects fit without wrap-around
     outs = []
     for fused in (False, True):
