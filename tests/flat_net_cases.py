@@ -1,6 +1,7 @@
 """The flat-parameter networks of utils/net.py and the QMIX mixer at one small shape each, and what tests/golden/flat_nets.npz
 pins of them (tests/golden/make_flat_net_fixtures.py writes it, tests/test_host_flat_nets.py reads it).  Two hidden layers of 8
-to 16, E = K = 3, 5 atoms, 4 cosines; the mixer's mixing width is 32, the smallest it builds."""
+to 16, E = K = 3, 5 atoms, 4 cosines; the mixer's mixing width is 32, the smallest it builds, and the fused actor-critic's hidden
+width 64, the only one it has."""
 from __future__ import annotations
 
 import json
@@ -40,8 +41,10 @@ CASES = OrderedDict([
     ("RainbowNet-plain", (lambda s: N.RainbowNet(**_RAINBOW, dueling=False, noisy_std=None, device="cpu", seed=s), True)),
     ("BranchingNet", (lambda s: N.BranchingNet(state_shape=(6,), num_branches=3, action_per_branch=4, common_hidden_sizes=[12, 8],
                                                value_hidden_sizes=[8], action_hidden_sizes=[8], device="cpu", seed=s), True)),
-    ("MLPActorCritic", (lambda s: N.MLPActorCritic(6, 4, (12, 8), device="cpu", seed=s), False)),
-    ("MLPActorCritic-uniform", (lambda s: N.MLPActorCritic(6, 4, (12, 8), device="cpu", seed=s, init="uniform"), False)),
+    ("MLPActorCritic", (lambda s: N.MLPActorCritic(6, 4, (12, 8), device="cpu", seed=s), True)),
+    ("MLPActorCritic-uniform", (lambda s: N.MLPActorCritic(6, 4, (12, 8), device="cpu", seed=s, init="uniform"), True)),
+    ("DiscreteActorCritic", (lambda s: N.DiscreteActorCritic(6, 4, 64, device="cpu", seed=s), True)),
+    ("DiscreteActorCritic-uniform", (lambda s: N.DiscreteActorCritic(6, 4, 64, device="cpu", seed=s, init="uniform"), True)),
     ("IntrinsicCuriosityModule", (_icm, False)),
     ("QMIXMixer", (lambda s: QMIXMixer(3, 10, 32, 16, device="cpu", seed=s), True)),
 ])

@@ -19,12 +19,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [os.path.dirname(os.path.dirname(HERE)), os.path.dirname(HERE)]
 
 from flat_net_cases import CASES, record  # noqa: E402
+from tianshou_marl_amd.utils.net import FlatNet  # noqa: E402
 
 
 def checkpoint_of(net) -> OrderedDict:
     """`to_reference_state_dict()`; for a net from before every class had one, the same entries from where it kept them:
-    `reference_named_views()` (MLPActorCritic) or the module's own `state_dict()` (QMIXMixer)."""
-    if hasattr(net, "to_reference_state_dict"):
+    `reference_named_views()` (MLPActorCritic; DiscreteActorCritic, whose own export was nested by trunk) or the module's own
+    `state_dict()` (QMIXMixer)."""
+    if isinstance(net, FlatNet):
         return net.to_reference_state_dict()
     if hasattr(net, "reference_named_views"):
         return OrderedDict(net.reference_named_views())

@@ -130,11 +130,13 @@ def test_clone_over_refuses_storage_that_is_not_the_vector(name):
 
 
 @pytest.mark.parametrize("name", TWINS)
-def test_lagged_copy_is_the_recorded_one_and_draws_nothing(name):
+def test_lagged_copy_is_the_recorded_one_and_draws_nothing(name, monkeypatch):
     net = _net(name)
     torch.manual_seed(123)
     before = torch.get_rng_state()
-    twin = lagged_copy(net)
+    with monkeypatch.context() as m:   # (`torch.manual_seed` seeds the device generators as well, which no host test sees)
+        m.setattr(torch, "manual_seed", lambda seed: pytest.fail("a twin seeded the global generators"))
+        twin = lagged_copy(net)
     assert torch.equal(torch.get_rng_state(), before)
     assert type(twin) is type(net) and twin.flat.data_ptr() != net.flat.data_ptr()
     assert np.array_equal(twin.flat.data.numpy(), ARRAYS[f"{name}/lagged"]) and torch.equal(twin.flat.data, net.flat.data)

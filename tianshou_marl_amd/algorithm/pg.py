@@ -31,28 +31,18 @@ from .ppo import PPO
 class A2C(PPO):
     """Synchronous advantage actor-critic (a2c.py:152-285) with the reference's constructor arguments."""
 
+    _fixed = ("eps_clip", "dual_clip", "value_clip", "advantage_normalization", "recompute_advantage")
+
     def __init__(self, *, policy=None, critic=None, optim=None, vf_coef: float = 0.5, ent_coef: float = 0.01,
                  max_grad_norm: float | None = None, gae_lambda: float = 0.95, max_batchsize: int = 256,
                  gamma: float = 0.99, return_scaling: bool = False, net: DiscreteActorCritic | None = None, **kw) -> None:
-        for banned in ("eps_clip", "dual_clip", "value_clip", "advantage_normalization", "recompute_advantage"):
+        for banned in self._fixed:
             if banned in kw:
                 raise TypeError(f"A2C has no `{banned}` (that is a PPO option)")
         super().__init__(policy=policy, critic=critic, optim=optim, net=net, vf_coef=vf_coef, ent_coef=ent_coef,
                          max_grad_norm=max_grad_norm, gae_lambda=gae_lambda, max_batchsize=max_batchsize, gamma=gamma, return_scaling=return_scaling,
                          advantage_normalization=False, recompute_advantage=False, value_clip=False, dual_clip=None, **kw)
         self._cfg = ops.make_ppo_cfg(adv_norm=False, vf_coef=vf_coef, ent_coef=ent_coef, loss_kind=1)
-        self._a2c_ctor = dict(vf_coef=vf_coef, ent_coef=ent_coef, max_grad_norm=max_grad_norm, gae_lambda=gae_lambda,
-                              max_batchsize=max_batchsize, gamma=gamma, return_scaling=return_scaling, **kw)
-
-    def __deepcopy__(self, memo):
-        net = DiscreteActorCritic(self.net.obs_dim, self.net.n_act, self.net.hidden, device=self.device)
-        net.flat.data.copy_(self.net.flat.data)
-        net.sync_image()
-        net._ref_keys = getattr(self.net, "_ref_keys", None)
-        new = type(self)(net=net, **self._a2c_ctor)
-        new.load_state_dict(self.state_dict())
-        new.train(self.training)
-        return new
 
 
 class LossSequenceTrainingStats(TrainingStats):
@@ -70,10 +60,12 @@ class Reinforce(PPO):
     """Vanilla policy gradient (reinforce.py:313-379).  `return_standardization` as in
     DiscountedReturnComputation (reinforce.py:240-311)."""
 
+    _fixed = ("eps_clip", "dual_clip", "value_clip", "advantage_normalization", "recompute_advantage",
+              "vf_coef", "ent_coef", "gae_lambda", "return_scaling", "max_grad_norm")
+
     def __init__(self, *, policy=None, gamma: float = 0.99, return_standardization: bool = False, optim=None,
                  net: DiscreteActorCritic | None = None, **kw) -> None:
-        for banned in ("eps_clip", "dual_clip", "value_clip", "advantage_normalization", "recompute_advantage",
-                       "vf_coef", "ent_coef", "gae_lambda", "return_scaling", "max_grad_norm"):
+        for banned in self._fixed:
             if banned in kw:
                 raise TypeError(f"Reinforce has no `{banned}`")
         kw.pop("use_graph", None)
@@ -84,7 +76,7 @@ class Reinforce(PPO):
                          use_graph=False, **kw)
         self.return_standardization = bool(return_standardization)
         self._cfg = ops.make_ppo_cfg(adv_norm=False, vf_coef=0.0, ent_coef=0.0, loss_kind=1)
-        self._r_ctor = dict(gamma=gamma, return_standardization=return_standardization, **kw)
+        self._ctor["return_standardization"] = return_standardization
 
     def _preprocess_batch(self, buffer: DeviceVectorReplayBuffer) -> dict:
         """reinforce.py:273-311: returns = discounted Monte-Carlo return, bootstrapped with ret_rms.mean where an
@@ -141,13 +133,3 @@ class Reinforce(PPO):
                   logp_old=zeros, n_env=1, n_agent=1)
         st = self._update_with_batch(pb, batch_size, repeat)
         return {"loss": st.loss.mean}
-
-    def __deepcopy__(self, memo):
-        net = DiscreteActorCritic(self.net.obs_dim, self.net.n_act, self.net.hidden, device=self.device)
-        net.flat.data.copy_(self.net.flat.data)
-        net.sync_image()
-        net._ref_keys = getattr(self.net, "_ref_keys", None)
-        new = type(self)(net=net, **self._r_ctor)
-        new.load_state_dict(self.state_dict())
-        new.train(self.training)
-        return new

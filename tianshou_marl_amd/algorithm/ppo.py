@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import os
 import time
+from collections import OrderedDict
 from typing import Literal
 
 import numpy as np
@@ -26,11 +27,18 @@ from ..data.batch import Batch, split_bounds
 from ..data.buffer import DeviceVectorReplayBuffer
 from ..data.stats import (A2CTrainingStats, LazyDict, MapTrainingStats, ResultRing, lazy_training_stats, pinned_slot,
                           training_stats_from_steps)
-from ..utils.net import DeviceRunningMeanStd, DiscreteActorCritic
+from ..utils.net import DeviceRunningMeanStd, DiscreteActorCritic, FlatAdam, lagged_copy
 from ..utils.tensor import to_tensor
 
 
+def _optim_attr(name: str) -> property:
+    """`algo.<attribute>` reads and sets `algo.optim.<name>`."""
+    return property(lambda self: getattr(self.optim, name), lambda self, value: setattr(self.optim, name, value))
+
+
 class PPO(nn.Module):
+    _fixed: tuple = ()  # constructor arguments of PPO that a subclass sets itself and does not take (A2C, Reinforce)
+
     def __new__(cls, *args, **kw):
         # reference-style construction `PPO(policy=..., critic=..., optim=...)`: nets the fused 64-wide kernels do not
         # cover (other widths / depths, tanh, a wider critic input) run on the general kernels of GenericPPO
@@ -74,13 +82,15 @@ class PPO(nn.Module):
             kw_o = optim.adam_kwargs()
             lr, betas, adam_eps, weight_decay = kw_o["lr"], kw_o["betas"], kw_o["adam_eps"], kw_o["weight_decay"]
             sched_factory = getattr(optim, "lr_scheduler_factory", None)
-        self._ctor = dict(lr=lr, betas=betas, adam_eps=adam_eps, weight_decay=weight_decay, eps_clip=eps_clip,
-                          dual_clip=dual_clip, value_clip=value_clip, advantage_normalization=advantage_normalization,
-                          recompute_advantage=recompute_advantage, vf_coef=vf_coef, ent_coef=ent_coef,
-                          max_grad_norm=max_grad_norm, gae_lambda=gae_lambda, max_batchsize=max_batchsize, gamma=gamma,
-                          return_scaling=return_scaling, deterministic_eval=deterministic_eval, dispatch=dispatch,
-                          shuffle=shuffle, seed=seed, use_graph=use_graph, async_stats=async_stats)
-        self._sched_factory = sched_factory
+        # what `__deepcopy__` builds the snapshot from: this constructor's arguments as resolved above, less those the
+        # subclass fixes itself (`_fixed`); a subclass adds its own
+        ctor = dict(lr=lr, betas=betas, adam_eps=adam_eps, weight_decay=weight_decay, eps_clip=eps_clip,
+                    dual_clip=dual_clip, value_clip=value_clip, advantage_normalization=advantage_normalization,
+                    recompute_advantage=recompute_advantage, vf_coef=vf_coef, ent_coef=ent_coef,
+                    max_grad_norm=max_grad_norm, gae_lambda=gae_lambda, max_batchsize=max_batchsize, gamma=gamma,
+                    return_scaling=return_scaling, deterministic_eval=deterministic_eval, dispatch=dispatch,
+                    shuffle=shuffle, seed=seed, use_graph=use_graph, async_stats=async_stats)
+        self._ctor = {k: v for k, v in ctor.items() if k not in self._fixed}
         self.net = net
         # Policy attributes the collector / MARL containers read (algorithm_base.py:159-373, marl.py:79-85)
         from ..env.spaces import Box, Discrete
@@ -90,11 +100,13 @@ class PPO(nn.Module):
         # the learning rate lives in HBM too (`_lr_dev`): LR schedulers move it between updates and the captured update
         # graph reads it in place (algorithm_base.py:626-627)
         self._lr_dev = torch.tensor([float(lr)], dtype=torch.float64, device=net.flat.device)
-        self._lr = float(lr)
+        # Adam's moments, step count, work buffer and hyper-parameters; the gradient steps below launch the optimizer
+        # kernels on them themselves.  Checkpoints list the moments per reference parameter, for either net
+        self.optim = FlatAdam(net, float(lr), betas, adam_eps, weight_decay, max_grad_norm,
+                              views=lambda flat: [v for _, v in net.reference_named_views(flat)])
         self.lr_schedulers: list = []
         if sched_factory is not None:  # Algorithm._create_optimizer (algorithm_base.py:506-519)
             self.lr_schedulers.append(sched_factory.create_scheduler(self))
-        self.betas, self.adam_eps, self.weight_decay = betas, adam_eps, weight_decay
         self.eps_clip, self.dual_clip, self.value_clip = eps_clip, dual_clip, value_clip
         self.advantage_normalization, self.recompute_adv = advantage_normalization, recompute_advantage
         self.pack_rows = True  # the statistics launch also gathers the minibatches' rows for the gradient steps (`_minibatch_plan`)
@@ -104,7 +116,7 @@ class PPO(nn.Module):
         self._prep_offer = None   # the captured update whose permutations a collect may draw: (graph key, its workspace)
         self._prep_gen = 0        # requests handed out so far
         self._prep_filled = None  # what the last collect's launch reported as drawn: (generation, graph key, optimizer step count)
-        self.vf_coef, self.ent_coef, self.max_grad_norm = vf_coef, ent_coef, max_grad_norm
+        self.vf_coef, self.ent_coef = vf_coef, ent_coef
         self.gae_lambda, self.gamma, self.max_batchsize = gae_lambda, gamma, max_batchsize
         self.return_scaling, self.ret_rms, self._eps = return_scaling, DeviceRunningMeanStd(net.flat.device), 1e-8
         self.deterministic_eval = deterministic_eval
@@ -114,13 +126,8 @@ class PPO(nn.Module):
         self.use_graph = use_graph
         self.async_stats = async_stats
         self.seed = int(seed)
-        dev = net.flat.device
-        self.exp_avg = torch.zeros_like(net.flat.data)
-        self.exp_avg_sq = torch.zeros_like(net.flat.data)
-        self.opt_step = 0
-        self._adam_work = torch.zeros(ops.call("tsm_adam_work_elems", net.flat.numel()), dtype=torch.float32, device=dev)
         self._sample_ctr = 0  # Philox counter base for action sampling
-        self._perm_ctr = torch.zeros(1, dtype=torch.int64, device=dev)  # draw counter of the device-side permutations
+        self._perm_ctr = torch.zeros(1, dtype=torch.int64, device=net.flat.device)  # draw counter of the device-side permutations
         self._cfg = ops.make_ppo_cfg(eps_clip, dual_clip, value_clip, advantage_normalization, vf_coef, ent_coef)
         self._ws: dict = {}
         self._grad_sync = None  # set by parallel.attach_data_parallel
@@ -139,12 +146,17 @@ class PPO(nn.Module):
 
     @property
     def lr(self) -> float:
-        return self._lr
+        return self.optim.lr
 
     @lr.setter
     def lr(self, value: float) -> None:
-        self._lr = float(value)
-        self._lr_dev.fill_(self._lr)
+        self.optim.lr = float(value)
+        self._lr_dev.fill_(self.optim.lr)
+
+    # the optimizer's state under the names it has always had on the algorithm (parallel.py, tools and tests read and set them)
+    exp_avg, exp_avg_sq, opt_step = _optim_attr("exp_avg"), _optim_attr("exp_avg_sq"), _optim_attr("step_count")
+    betas, adam_eps, weight_decay = _optim_attr("betas"), _optim_attr("eps"), _optim_attr("weight_decay")
+    max_grad_norm = _optim_attr("max_grad_norm")
 
     # ---- rollout side -------------------------------------------------------------------------
     def act_device(self, obs: torch.Tensor, out: dict | None = None, offset_dev: torch.Tensor | None = None,
@@ -457,7 +469,7 @@ class PPO(nn.Module):
             ops.reduce_slabs(grads, out=plan["flat_g"], scale=1.0 / gs.world)  # mean = sum of g_i / world
             yield plan["flat_g"]  # summed over the ranks by the driver, in place
             grads = plan["flat_g"].view(1, -1)
-        ops.adam_step(P, grads, self.exp_avg, self.exp_avg_sq, step, max_grad_norm=self.max_grad_norm, work=self._adam_work,
+        ops.adam_step(P, grads, self.exp_avg, self.exp_avg_sq, step, max_grad_norm=self.max_grad_norm, work=self.optim.work,
                       **hyper)
 
     def _update_steps(self, pb: dict, batch_size: int | None, repeat: int, agent: int | None = None,
@@ -521,7 +533,7 @@ class PPO(nn.Module):
         ops.ppo_update_fused(P, obs, act, z, z, z, self._cfg, A, H, adv_stats=st[0], v_s_old=z, image=self.net.image.clone(),
                              packed=pk["rows"](0))
         ops.adam_step(P, slabs, torch.zeros_like(P), torch.zeros_like(P), 1, max_grad_norm=self.max_grad_norm,
-                      work=self._adam_work)
+                      work=self.optim.work)
         ops.gae_lanes(z.view(32, 1), z.view(32, 1), z.view(32, 1), act.view(32, 1).to(torch.uint8),
                       act.view(32, 1).to(torch.uint8))
         torch.cuda.synchronize()
@@ -1011,12 +1023,9 @@ class PPO(nn.Module):
 
     def __deepcopy__(self, memo):
         """Snapshot for opponent pools (training_coordinator.py:481-494): parameters, optimizer state and counters are
-        copied; device workspaces (captured graphs, pinned rings) are rebuilt lazily by the copy."""
-        net = DiscreteActorCritic(self.net.obs_dim, self.net.n_act, self.net.hidden, device=self.device)
-        net.flat.data.copy_(self.net.flat.data)
-        net.sync_image()
-        net._ref_keys = getattr(self.net, "_ref_keys", None)
-        new = PPO(net=net, **self._ctor)
+        copied; device workspaces (captured graphs, pinned rings) are rebuilt lazily by the copy.  Of this class and every
+        subclass: the net's twin is over a vector of its own (`lagged_copy`: torch's global generator is not drawn from)."""
+        new = type(self)(net=lagged_copy(self.net), **self._ctor)
         new.load_state_dict(self.state_dict())
         new.train(self.training)
         return new
@@ -1030,27 +1039,14 @@ class PPO(nn.Module):
         directions (pinned by tests/golden/checkpoint.npz).  What the engine needs beyond that to resume bit-identically
         (return statistics, sampling / permutation counters, scheduler epochs) rides in `_optimizers[0]["tsm_engine"]`,
         a key torch's `Optimizer.load_state_dict` ignores."""
-        from collections import OrderedDict
-
-        views = self.net.reference_named_views()
-        sd = OrderedDict((k, v.detach().clone()) for k, v in views)
-        state, o = {}, 0
-        for i, (_, v) in enumerate(views):
-            n = v.numel()
-            if self.opt_step > 0:  # torch creates the per-parameter state at the first step
-                state[i] = {"step": torch.tensor(float(self.opt_step)),
-                            "exp_avg": self.exp_avg[o:o + n].view(v.shape).clone(),
-                            "exp_avg_sq": self.exp_avg_sq[o:o + n].view(v.shape).clone()}
-            o += n
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.adam_eps, "weight_decay": self.weight_decay,
-                 "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
-                 "fused": None, "decoupled_weight_decay": False, "params": list(range(len(views)))}
+        sd = OrderedDict((k, v.detach().clone()) for k, v in self.net.reference_named_views())
+        opt = self.optim.state_dict()   # `state` per reference parameter (`FlatAdam(views=)`) and `param_groups`
         if self.lr_schedulers:
-            group["initial_lr"] = self.lr_schedulers[0].base_lr  # torch's LambdaLR stores it in the group
-        engine = {"ret_rms": self.ret_rms.dev.detach().cpu().clone(), "sample_ctr": int(self._sample_ctr),
-                  "perm_ctr": int(self._perm_ctr.item()), "opt_step": int(self.opt_step),
-                  "lr_schedulers": [s.state_dict() for s in self.lr_schedulers]}
-        sd["_optimizers"] = [{"state": state, "param_groups": [group], "tsm_engine": engine}]
+            opt["param_groups"][0]["initial_lr"] = self.lr_schedulers[0].base_lr  # torch's LambdaLR stores it in the group
+        opt["tsm_engine"] = {"ret_rms": self.ret_rms.dev.detach().cpu().clone(), "sample_ctr": int(self._sample_ctr),
+                             "perm_ctr": int(self._perm_ctr.item()), "opt_step": int(self.opt_step),
+                             "lr_schedulers": [s.state_dict() for s in self.lr_schedulers]}
+        sd["_optimizers"] = [opt]
         return sd
 
     def load_state_dict(self, sd, *args, **kwargs):
@@ -1058,30 +1054,14 @@ class PPO(nn.Module):
         missing = [k for k, _ in views if k not in sd]
         if missing:
             raise KeyError(f"state_dict lacks {missing[:3]}{' ...' if len(missing) > 3 else ''}")
-        with torch.no_grad():
-            for k, v in views:
-                v.copy_(torch.as_tensor(sd[k]).to(v.device, v.dtype).reshape(v.shape))
-        self.net.sync_image()
+        self.net.load_reference_state_dict(sd)   # (and the fused net's image with it)
         self.param_version += 1
         opt = sd["_optimizers"][0]
-        st, o, step = opt["state"], 0, 0
-        self.exp_avg.zero_()
-        self.exp_avg_sq.zero_()
-        for i, (_, v) in enumerate(views):
-            n = v.numel()
-            e = st.get(i, st.get(str(i)))
-            if e is not None:
-                self.exp_avg[o:o + n].copy_(torch.as_tensor(e["exp_avg"]).reshape(-1))
-                self.exp_avg_sq[o:o + n].copy_(torch.as_tensor(e["exp_avg_sq"]).reshape(-1))
-                step = int(float(e["step"]))
-            o += n
-        self.opt_step = step
-        g = opt["param_groups"][0]
-        self.lr = float(g["lr"])
-        hyper = (tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]))
-        if hyper != (tuple(self.betas), self.adam_eps, self.weight_decay):
+        hyper = (tuple(self.betas), self.adam_eps, self.weight_decay)
+        self.optim.load_state_dict(opt)
+        self.lr = self.optim.lr  # (the device mirror follows)
+        if hyper != (self.betas, self.adam_eps, self.weight_decay):
             self._ws = {}  # captured graphs hold the old Adam constants as kernel arguments
-        self.betas, self.adam_eps, self.weight_decay = hyper
         eng = opt.get("tsm_engine")
         if eng is not None:
             self.ret_rms.dev.copy_(torch.as_tensor(eng["ret_rms"]))

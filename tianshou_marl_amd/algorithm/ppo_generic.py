@@ -17,7 +17,6 @@ the whole sequence -- permutations, critic passes, GAE, every gradient step -- i
 """
 from __future__ import annotations
 
-import copy
 import os
 from typing import Literal
 
@@ -252,7 +251,7 @@ class GenericPPO(PPO):
         ops.adam_step(net.flat.data, grads, self.exp_avg, self.exp_avg_sq, self.opt_step, lr=self.lr, lr_dev=self._lr_dev,
                       betas=self.betas,
                       eps=self.adam_eps, weight_decay=self.weight_decay, max_grad_norm=self.max_grad_norm,
-                      work=self._adam_work, step_dev=step_dev)
+                      work=self.optim.work, step_dev=step_dev)
         return scalars
 
     def _rows_grids(self, M: int, Mr: int, crit_rows: bool) -> tuple[int, int]:
@@ -345,13 +344,13 @@ class GenericPPO(PPO):
                      step_dev=step_dev)
         if self._grad_sync is None:
             ops.adam_step_segs(net.flat.data, segs, self.exp_avg, self.exp_avg_sq, self.opt_step,
-                               max_grad_norm=self.max_grad_norm, work=self._adam_work, **hyper)
+                               max_grad_norm=self.max_grad_norm, work=self.optim.work, **hyper)
             self._w1_img_ok = segs_c is not None and self._w1_img is not None
         else:
             ops.reduce_slabs_segs(segs, P_a + P_c, out=w["flat_g"], scale=1.0 / self._grad_sync.world)
             yield w["flat_g"]  # summed over the ranks by the driver, in place
             ops.adam_step(net.flat.data, w["flat_g"].view(1, -1), self.exp_avg, self.exp_avg_sq, self.opt_step,
-                          max_grad_norm=self.max_grad_norm, work=self._adam_work, **hyper)
+                          max_grad_norm=self.max_grad_norm, work=self.optim.work, **hyper)
         if partial_out is not None:
             return None
         scal = torch.empty(1, 4, dtype=torch.float32, device=dev)
@@ -638,15 +637,3 @@ class GenericPPO(PPO):
         st = yield from self._update_steps(pb, batch_size, repeat)
         return {"loss": st.loss.mean, "actor_loss": st.actor_loss.mean, "vf_loss": st.vf_loss.mean,
                 "ent_loss": st.ent_loss.mean}
-
-    # ---- snapshots (checkpoints: PPO.state_dict / load_state_dict on the reference key names) ------------------
-    def __deepcopy__(self, memo):
-        src = self.net
-        net = MLPActorCritic(src.obs_dim, src.n_act, tuple(src.actor.dims[1:-1]), act=src.actor.act,
-                             critic_obs_dim=src.critic_obs_dim, device=self.device)
-        net._ref_keys = getattr(src, "_ref_keys", None)
-        ctor = copy.copy(self._ctor)
-        new = GenericPPO(net=net, **ctor)
-        new.load_state_dict(self.state_dict())
-        new.train(self.training)
-        return new

@@ -626,6 +626,9 @@ def policy_image(obs_dim: int, hidden: int, n_act: int, device):
 def scatter_image(params, image, image_map):
     if image is None:
         return None
+    if not params.is_cuda:  # a host net (tests, checkpoint tools): the same placement, by indexing
+        image[image_map.long()] = params
+        return image
     call("tsm_scatter_image", ptr(params), params.numel(), ptr(image_map), ptr(image), stream_ptr())
     return image
 

@@ -35,107 +35,6 @@ def ref_layer_keys(n_layers: int, scheme: str) -> list[tuple[str, str]]:
     return [(s + ".weight", s + ".bias") for s in stems]
 
 
-def _layer_shapes(obs_dim: int, hidden: int, n_out: int):
-    return [("w0", (hidden, obs_dim)), ("b0", (hidden,)), ("w1", (hidden, hidden)), ("b1", (hidden,)),
-            ("w2", (n_out, hidden)), ("b2", (n_out,))]
-
-
-class DiscreteActorCritic(nn.Module):
-    """Separate actor and critic MLP trunks, obs[D] -> H -> H -> (A logits | 1 value), flat parameters."""
-
-    def __init__(self, obs_dim: int, n_act: int, hidden: int = 64, device: str | torch.device = "cuda",
-                 init: str = "orthogonal", seed: int | None = None) -> None:
-        super().__init__()
-        self.obs_dim, self.n_act, self.hidden = int(obs_dim), int(n_act), int(hidden)
-        n = ops.policy_param_count(self.obs_dim, self.hidden, self.n_act)
-        self.flat = nn.Parameter(torch.zeros(n, dtype=torch.float32, device=device), requires_grad=False)
-        self._slices: OrderedDict[str, tuple[int, tuple[int, ...]]] = OrderedDict()
-        o = 0
-        for net, n_out in (("actor", self.n_act), ("critic", 1)):
-            for name, shape in _layer_shapes(self.obs_dim, self.hidden, n_out):
-                self._slices[f"{net}.{name}"] = (o, shape)
-                o += int(np.prod(shape))
-        assert o == n
-        # padded LDS-layout copy of the parameters, refreshed by the Adam kernel (csrc/adam.hip) and by
-        # sync_image(); the fused kernels stage it with straight 16-B copies
-        self.image, self.image_map = ops.policy_image(self.obs_dim, self.hidden, self.n_act, device)
-        self.reset_parameters(init, seed)
-
-    def sync_image(self) -> None:
-        """Re-derive the padded image from `flat` (call after modifying `flat` outside the optimizer)."""
-        ops.scatter_image(self.flat.data, self.image, self.image_map)
-
-    def view(self, name: str) -> torch.Tensor:
-        o, shape = self._slices[name]
-        return self.flat.data[o:o + int(np.prod(shape))].view(shape)
-
-    def named_views(self):
-        return [(k, self.view(k)) for k in self._slices]
-
-    @torch.no_grad()
-    def reset_parameters(self, init: str = "orthogonal", seed: int | None = None) -> None:
-        """orthogonal weights + zero bias (the reference scripts' init, test/discrete/test_ppo_discrete.py:103-106)
-        or torch's nn.Linear default (kaiming-uniform)."""
-        gen = torch.Generator().manual_seed(seed) if seed is not None else None
-        for name, v in self.named_views():
-            if name.split(".")[1].startswith("w"):
-                w = torch.empty(v.shape)
-                if init == "orthogonal":
-                    if gen is not None:
-                        torch.manual_seed(int(torch.randint(0, 2**31 - 1, (1,), generator=gen)))
-                    nn.init.orthogonal_(w)
-                else:
-                    bound = 1.0 / math.sqrt(v.shape[1])
-                    w.uniform_(-bound, bound, generator=gen)
-                v.copy_(w)
-            elif init == "orthogonal":
-                v.zero_()
-            else:
-                fan_in = self.view(name.replace(".b", ".w")).shape[1]
-                b = torch.empty(v.shape).uniform_(-1.0 / math.sqrt(fan_in), 1.0 / math.sqrt(fan_in), generator=gen)
-                v.copy_(b)
-        self.sync_image()
-
-    # ---- reference checkpoint compatibility (SURVEY 8f-3) --------------------------------------
-    def reference_named_views(self) -> list[tuple[str, torch.Tensor]]:
-        """[(key, view)] in ActorCritic.parameters() order with the key names `Algorithm.state_dict()` gives the
-        reference's PPO over DiscreteActor/DiscreteCritic(Net(hidden_sizes=[H, H])): `policy.actor.<...>`, `critic.<...>`
-        (algorithm_base.py:521-541; verified by tests/golden/checkpoint.npz)."""
-        keys = getattr(self, "_ref_keys", None) or {"actor": ref_layer_keys(3, "head"), "critic": ref_layer_keys(3, "head")}
-        out = []
-        for name, v in self.named_views():
-            net, layer = name.split(".")
-            out.append((("policy.actor." if net == "actor" else "critic.") + keys[net][int(layer[1])][layer[0] == "b"], v))
-        return out
-
-    def _ref_named_views(self):
-        """(net, key of DiscreteActor/DiscreteCritic over Net, view) of every parameter."""
-        keys = ref_layer_keys(3, "head")
-        return [(name.split(".")[0], keys[int(name[-1])][name[-2] == "b"], v) for name, v in self.named_views()]
-
-    def to_reference_state_dict(self) -> dict[str, OrderedDict]:
-        """{'actor': ..., 'critic': ...} with the key names of DiscreteActor/DiscreteCritic over Net."""
-        out = {"actor": OrderedDict(), "critic": OrderedDict()}
-        for net, key, v in self._ref_named_views():
-            out[net][key] = v.detach().clone().cpu()
-        return out
-
-    @torch.no_grad()
-    def load_reference_state_dict(self, sd: dict) -> None:
-        for net, key, v in self._ref_named_views():
-            v.copy_(torch.as_tensor(sd[net][key]).to(v.device, v.dtype).reshape(v.shape))
-        self.sync_image()
-
-    @torch.no_grad()
-    def load_layers(self, actor, critic) -> None:
-        """actor / critic: [(W, b)] * 3 (numpy or tensors) in torch nn.Linear layout."""
-        for net, layers in (("actor", actor), ("critic", critic)):
-            for i, (W, b) in enumerate(layers):
-                self.view(f"{net}.w{i}").copy_(torch.as_tensor(np.asarray(W)).to(self.flat.device, torch.float32))
-                self.view(f"{net}.b{i}").copy_(torch.as_tensor(np.asarray(b)).to(self.flat.device, torch.float32))
-        self.sync_image()
-
-
 def _generator(seed: int | None) -> torch.Generator | None:
     """A private generator at `seed` (None: the global one draws)."""
     return torch.Generator().manual_seed(seed) if seed is not None else None
@@ -194,9 +93,14 @@ class FlatNet(nn.Module):
         self.flat = nn.Parameter(storage, requires_grad=False)
 
     def clone_over(self, storage: torch.Tensor):
-        """A net of the same class and shape viewing `storage`, which holds the init of a private generator until the caller
-        copies over it (`lagged_copy`)."""
+        """A net of the same class and shape viewing `storage`, which holds the init of a private generator (the actor-critic
+        nets: what it held) until the caller copies over it (`lagged_copy`)."""
         return type(self)(**self._ctor_args, device=storage.device, seed=0, storage=storage)
+
+    def sync_image(self) -> None:
+        """Re-derive what the net keeps beside `flat` in another layout (call after modifying `flat` outside the optimizer):
+        `DiscreteActorCritic`'s padded image.  Most nets keep nothing."""
+        return None
 
     # ---- ONE statement of the parameters ----------------------------------------------------------------------------------
     def _vector(self, flat: torch.Tensor | None) -> torch.Tensor:
@@ -1258,6 +1162,87 @@ class BranchingNet(FlatNet):
         return out
 
 
+def _trunk_keys(ref_keys: dict | None, trunk: str, n_layers: int) -> list[tuple[str, str]]:
+    """[(weight key, bias key)] of the "actor" / "critic" trunk: those of the modules the net was built from (`ref_keys`,
+    `net_from_reference_modules`), else a DiscreteActor / DiscreteCritic over Net(hidden_sizes=[...])'s."""
+    return (ref_keys or {}).get(trunk) or ref_layer_keys(n_layers, "head")
+
+
+class DiscreteActorCritic(FlatNet):
+    """Separate actor and critic MLP trunks, obs[D] -> H -> H -> (A logits | 1 value), flat parameters: actor then critic, each
+    w0 b0 w1 b1 w2 b2 (the fused 64-wide kernels, csrc/mlp_fused.hip).  `ref_keys`: see `_trunk_keys`."""
+
+    # a bare `FlatAdam` over this net has always listed ONE parameter, and tests/golden/flat_nets.npz pins that layout (PPO
+    # lists its moments per reference parameter all the same: `FlatAdam(views=)`)
+    split_optimizer_state = False
+
+    def __init__(self, obs_dim: int, n_act: int, hidden: int = 64, device: str | torch.device = "cuda",
+                 init: str = "orthogonal", seed: int | None = None, storage: torch.Tensor | None = None,
+                 ref_keys: dict | None = None) -> None:
+        super().__init__()
+        self.obs_dim, self.n_act, self.hidden, self._ref_keys = int(obs_dim), int(n_act), int(hidden), ref_keys
+        self._claim(ops.policy_param_count(self.obs_dim, self.hidden, self.n_act), storage, device)
+        # padded LDS-layout copy of the parameters, refreshed by the Adam kernel (csrc/adam.hip) and by
+        # sync_image(); the fused kernels stage it with straight 16-B copies
+        self.image, self.image_map = ops.policy_image(self.obs_dim, self.hidden, self.n_act, device)
+        # the orthogonal init seeds and draws from torch's GLOBAL generators; over given `storage` -- a twin, whose vector
+        # `lagged_copy` fills -- nothing is drawn and no generator, host or device, is touched
+        if storage is None:
+            self.reset_parameters(init, seed)
+        else:
+            self.sync_image()
+
+    def sync_image(self) -> None:
+        ops.scatter_image(self.flat.data, self.image, self.image_map)
+
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        """In ActorCritic.parameters() order with the key names `Algorithm.state_dict()` gives the reference's PPO over
+        DiscreteActor/DiscreteCritic(Net(hidden_sizes=[H, H])): `policy.actor.<...>`, `critic.<...>`
+        (algorithm_base.py:521-541; verified by tests/golden/checkpoint.npz)."""
+        flat, o, out = self._vector(flat), 0, []
+        D, H = self.obs_dim, self.hidden
+        for trunk, prefix, n_out in (("actor", "policy.actor.", self.n_act), ("critic", "critic.", 1)):
+            for (kw, kb), (n, k) in zip(_trunk_keys(self._ref_keys, trunk, 3), ((H, D), (H, H), (n_out, H))):
+                out += [(prefix + kw, flat[o:o + n * k].view(n, k)), (prefix + kb, flat[o + n * k:o + n * k + n])]
+                o += n * k + n
+        return out
+
+    def view(self, name: str) -> torch.Tensor:
+        """`actor.w0`, `actor.b0`, ... `critic.b2`: that layer's weight or bias."""
+        trunk, layer = name.split(".")
+        return self.reference_named_views()[6 * ("actor", "critic").index(trunk) + 2 * int(layer[1]) + "wb".index(layer[0])][1]
+
+    @torch.no_grad()
+    def reset_parameters(self, init: str = "orthogonal", seed: int | None = None) -> None:
+        """orthogonal weights + zero bias (the reference scripts' init, test/discrete/test_ppo_discrete.py:103-106)
+        or torch's nn.Linear default (kaiming-uniform).  Seeded, every orthogonal weight re-seeds the global generator from a
+        private one; `MLPActorCritic` seeds it once: two draws, and each class keeps its own."""
+        gen = _generator(seed)
+        views = [v for _, v in self.reference_named_views()]
+        for W, b in zip(views[::2], views[1::2]):
+            if init == "orthogonal":
+                if gen is not None:
+                    torch.manual_seed(int(torch.randint(0, 2**31 - 1, (1,), generator=gen)))
+                W.copy_(nn.init.orthogonal_(torch.empty(W.shape)))
+                b.zero_()
+            else:
+                bound = 1.0 / math.sqrt(W.shape[1])
+                W.copy_(_uniform(W.shape, bound, gen))
+                b.copy_(_uniform(b.shape, bound, gen))
+        self.sync_image()
+
+    def load_reference_state_dict(self, sd, prefix: str = "") -> None:
+        super().load_reference_state_dict(sd, prefix)
+        self.sync_image()
+
+    @torch.no_grad()
+    def load_layers(self, actor, critic) -> None:
+        """actor / critic: [(W, b)] * 3 (numpy or tensors) in torch nn.Linear layout."""
+        for (_, v), t in zip(self.reference_named_views(), [t for layer in (*actor, *critic) for t in layer]):
+            v.copy_(torch.as_tensor(np.asarray(t)).to(v.device, torch.float32))
+        self.sync_image()
+
+
 class MLPActorCritic(FlatNet):
     """Actor and critic MLPs of ARBITRARY widths under one flat parameter vector (`ActorCritic(actor, critic)`,
     common.py:461-474: one optimizer, one global gradient-norm clip).  Layout = actor parameters then critic parameters,
@@ -1266,35 +1251,35 @@ class MLPActorCritic(FlatNet):
     other than 64, more layers, tanh, or a centralized critic: `critic_obs_dim = n_agent * obs_dim`)."""
 
     split_optimizer_state = False
+    image = image_map = None  # no LDS image: the dense kernels stream the weights
 
     def __init__(self, obs_dim: int, n_act: int, hidden_sizes=(128, 128), act: str = "relu",
                  critic_obs_dim: int | None = None, device: str | torch.device = "cuda", seed: int | None = None,
-                 init: str = "orthogonal") -> None:
+                 init: str = "orthogonal", storage: torch.Tensor | None = None, ref_keys: dict | None = None) -> None:
         super().__init__()
-        self.obs_dim, self.n_act, self.hidden = int(obs_dim), int(n_act), int(hidden_sizes[0])
+        self.obs_dim, self.n_act, self.hidden, self._ref_keys = int(obs_dim), int(n_act), int(hidden_sizes[0]), ref_keys
         self.critic_obs_dim = int(critic_obs_dim or obs_dim)
         dims_a = [self.obs_dim, *hidden_sizes, self.n_act]
         dims_c = [self.critic_obs_dim, *hidden_sizes, 1]
         na = ops.mlp_param_count(ops.mlp_desc(dims_a, act))
         nc = ops.mlp_param_count(ops.mlp_desc(dims_c, act))
-        self._claim(na + nc, None, device)
+        flat = self._claim(na + nc, storage, device)
         self.n_actor, self.n_critic = na, nc
-        self.actor = FlatMLP(dims_a, act, device=device, storage=self.flat.data[:na])
-        self.critic = FlatMLP(dims_c, act, device=device, storage=self.flat.data[na:])
-        self.image = self.image_map = None  # no LDS image: the dense kernels stream the weights
-        self.reset_parameters(init, seed)
-
-    def sync_image(self) -> None:
-        return None
+        # the trunks' own constructors draw nn.Linear's init from the global generator, and the init proper seeds it; over
+        # given `storage` (a twin, as in `DiscreteActorCritic`) the trunks draw from a private one and the init is left out
+        trunk_seed = None if storage is None else 0
+        self.actor = FlatMLP(dims_a, act, device=device, seed=trunk_seed, storage=flat[:na])
+        self.critic = FlatMLP(dims_c, act, device=device, seed=trunk_seed, storage=flat[na:])
+        if storage is None:
+            self.reset_parameters(init, seed)
 
     def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
         """As DiscreteActorCritic.reference_named_views, for Net(hidden_sizes=[...]) of any depth: hidden layer i is
         `preprocess.model.model.{2 i}` (Linear, activation, Linear, ...), the output layer `last.model.0`."""
         flat, na = self._vector(flat), self.n_actor
-        keys = getattr(self, "_ref_keys", None) or {}
         return [kv for name, net, prefix, part in (("actor", self.actor, "policy.actor.", flat[:na]),
                                                    ("critic", self.critic, "critic.", flat[na:]))
-                for kv in net.named_layers(keys.get(name) or ref_layer_keys(net.n_layers, "head"), prefix, part)]
+                for kv in net.named_layers(_trunk_keys(self._ref_keys, name, net.n_layers), prefix, part)]
 
     @torch.no_grad()
     def reset_parameters(self, init: str = "orthogonal", seed: int | None = None) -> None:
@@ -1322,17 +1307,18 @@ class FlatAdam:
     `optim.Adam(module.parameters(), lr=...)` stands in the reference's CTDE constructors (ctde.py:36-37)."""
 
     def __init__(self, module, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 max_grad_norm: float | None = None, coef64: bool = False) -> None:
+                 max_grad_norm: float | None = None, coef64: bool = False, views=None) -> None:
         self.coef64 = bool(coef64)  # `step` runs tsm_adam_step_coef64: torch's own f32 coefficients 1 - beta
         self.param = module.flat.data if hasattr(module, "flat") else module
         # a vector of the parameter's layout (a moment) -> the parameters it holds, in the vector's order: the net's own
-        # statement; a bare vector, or a module that states none, is one parameter
-        self._views = getattr(module, "param_views", _one_parameter)
+        # statement; a bare vector, or a module that states none, is one parameter.  `views`: the owner's statement instead
+        # (PPO: per reference parameter, also where the net's own optimizer checkpoints list the vector whole)
+        self._views = views or getattr(module, "param_views", _one_parameter)
         self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm = lr, betas, eps, weight_decay, max_grad_norm
         self.exp_avg = torch.zeros_like(self.param)
         self.exp_avg_sq = torch.zeros_like(self.param)
         self.step_count = 0
-        self._work = torch.zeros(ops.call("tsm_adam_work_elems", self.param.numel()), dtype=torch.float32,
+        self.work = torch.zeros(ops.call("tsm_adam_work_elems", self.param.numel()), dtype=torch.float32,
                                  device=self.param.device)
 
     def zero_grad(self) -> None:  # gradients are produced fresh per step as slabs; nothing accumulates
@@ -1342,7 +1328,7 @@ class FlatAdam:
         self.step_count += 1
         ops.adam_step(self.param, grad_slabs, self.exp_avg, self.exp_avg_sq, self.step_count, lr=self.lr,
                       betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, max_grad_norm=self.max_grad_norm,
-                      work=self._work, coef64=self.coef64)
+                      work=self.work, coef64=self.coef64)
 
     def step_segs(self, segs: list, step_dev: torch.Tensor | None = None) -> None:
         """`step` for gradients that arrive as several slab arrays (ops.adam_step_segs: segments tiling the vector, each
@@ -1351,7 +1337,7 @@ class FlatAdam:
             self.step_count += 1
         ops.adam_step_segs(self.param, segs, self.exp_avg, self.exp_avg_sq, self.step_count if step_dev is None else 1,
                            lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
-                           max_grad_norm=self.max_grad_norm, work=self._work, step_dev=step_dev)
+                           max_grad_norm=self.max_grad_norm, work=self.work, step_dev=step_dev)
 
     def _shapes(self) -> list[tuple[int, ...]]:
         return [tuple(v.shape) for v in self._views(self.exp_avg)]
@@ -1395,6 +1381,7 @@ def lagged_copy(net, storage: torch.Tensor | None = None):
         storage = net.flat.data.clone()
     twin = net.clone_over(storage)
     storage.copy_(net.flat.data)
+    twin.sync_image()
     return twin
 
 
@@ -1414,6 +1401,8 @@ def lagged_twins(nets, flat: torch.Tensor, offsets) -> tuple[torch.Tensor, list]
     target_flat = flat.clone()
     twins = [n.clone_over(target_flat[o:e]) for n, o, e in zip(nets, offsets, offsets[1:])]
     target_flat.copy_(flat)
+    for t in twins:
+        t.sync_image()
     return target_flat, twins
 
 
@@ -1583,8 +1572,10 @@ def net_from_reference_modules(policy, critic, device="cuda"):
         critic_obs = lc[0][0].shape[1]
     else:
         lc, critic_obs = None, obs_dim
+    # (no critic: both trunks under the default names)
+    ref_keys = {"actor": reference_key_names(actor_mod), "critic": reference_key_names(critic)} if critic is not None else None
     if len(la) == 3 and hidden == [64, 64] and obs_dim <= 64 and n_act <= 16 and act == "relu" and critic_obs == obs_dim:
-        net = DiscreteActorCritic(obs_dim, n_act, 64, device=device)
+        net = DiscreteActorCritic(obs_dim, n_act, 64, device=device, ref_keys=ref_keys)
         if lc is None:
             lc = [(np.zeros_like(net.view(f"critic.w{i}").cpu().numpy()), np.zeros_like(net.view(f"critic.b{i}").cpu().numpy()))
                   for i in range(3)]
@@ -1592,13 +1583,9 @@ def net_from_reference_modules(policy, critic, device="cuda"):
     else:
         if lc is None:
             raise ValueError("Reinforce without a critic runs on the fused 64-64 layout only")
-        net = MLPActorCritic(obs_dim, n_act, tuple(hidden), act=act, critic_obs_dim=critic_obs, device=device)
+        net = MLPActorCritic(obs_dim, n_act, tuple(hidden), act=act, critic_obs_dim=critic_obs, device=device, ref_keys=ref_keys)
         net.actor.load_layers(la)
         net.critic.load_layers(lc)
-    net._ref_keys = {"actor": reference_key_names(actor_mod),
-                     "critic": reference_key_names(critic) if critic is not None else None}
-    if net._ref_keys["critic"] is None:
-        net._ref_keys = None
     try:
         policy._tsm_net = (critic, net)
     except Exception:  # noqa: BLE001  (objects without attribute assignment: no cache)
