@@ -1225,6 +1225,67 @@ int tsm_sac_actor_head(const float *mu_raw, int64_t ld_mu, const float *sigma_ra
                        float *d_mu_out, float *d_sigma_out, int64_t ld_d, float *logp_out, double *partial, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Offline continuous learners: CQL / Cal-QL and TD3+BC  (tianshou/algorithm/imitation/cql.py, td3_bc.py; csrc/cql.hip)
+ * What the two updates add to the entries above.  With B transitions, R = num_repeat_actions, D = obs_dim, Ad = act_dim, a
+ * flat index i in [0, B R) belongs to transition i / R.  All entries take a stream and read nothing from the host.
+ * tsm_cql_check: act_dim in [1, TSM_CAC_MAX_ACT_DIM], num_repeat >= 1: TSM_ERR_INVALID naming the limit.  Needs no device.
+ * tsm_cql_uniform replaces  torch.FloatTensor(B R, Ad).uniform_(-min_action, max_action) (cql.py:303-307).
+ *   out f32 [n]: element e = lo + u01(word e % 4) (hi - lo), each step rounded to float32, of Philox4x32-10 under the key
+ *   seed ^ a constant of its own at the ONE counter offset + *offset_dev (nullable) with e / 4 as third counter word -- the
+ *   shape of tsm_cac_normal.  The caller advances its counter by n.  lo == hi gives lo everywhere (quirk Q70: the reference's
+ *   defaults draw from uniform_(1, 1)).
+ * tsm_cql_rows replaces  the repeat/view of obs and obs_next (cql.py:309-313) and the torch.cat([obs, act]) of the critic on
+ *           the data rows and in _calc_random_values / _calc_pi_values (cql.py:218-241, 295-296).  One launch.
+ *   obs, obs_next [B][D]; act [B][Ad]; rand_act [B R][Ad].
+ *   x_out f32 [B + 3 B R][D + Ad]: rows [0, B) = [obs | act]; row B + i = [obs[i / R] | rand_act[i]]; rows B + B R + i and
+ *   B + 2 B R + i = [obs[i / R] | untouched]: their action columns are tsm_sac_action's to fill (rows_out = row B + B R, col0 = D)
+ *   from the actor on actor_rows_out.  The third group's action is sampled at obs_next but its row carries obs
+ *   (`_calc_pi_values(tmp_obs_next, tmp_obs)`).
+ *   actor_rows_out f32 [2 B R][D]: row i = obs[i / R], row B R + i = obs_next[i / R].
+ * tsm_cql_head replaces  F.mse_loss, the calibration torch.max, torch.cat + torch.logsumexp, the Lagrange scaling and the
+ *           backward of critic1_loss / critic2_loss down to the critics' outputs (cql.py:299-300, 331-384).  One launch for
+ *           both critics, one thread per flat index, TSM_CQL_ROWS_PER_BLOCK of them per workgroup.
+ *   q1, q2 f32 [B + 3 B R]: the critics on x_out; target [B]; logp_cur, logp_next [B R]: tsm_sac_action's logp of the second
+ *   and third group; calib [B] (nullable: not calibrated); log_half_pow = log(0.5 ** Ad), formed by the host in float64;
+ *   log_alpha f32 [1] in HBM (nullable: with_lagrange = False, cql_alpha = 1), read BEFORE tsm_cql_finalize steps it (Q72).
+ *   csrc/cql.hip states the loss and its closed-form gradient; dq1, dq2 f32 [B + 3 B R] <- d loss_k / d q_k, every entry
+ *   written; partial f64 [6 * ceil(B R / TSM_CQL_ROWS_PER_BLOCK)] = per workgroup and critic {sum (q - target)^2, sum q[b],
+ *   sum lse_i}.
+ * tsm_cql_finalize replaces  the scalars of cql.py:353-384 and cql_alpha_loss.backward() + cql_alpha_optim.step().  One launch
+ *           of one thread, the workgroups' partials in index order.
+ *   out f32 [6] (HBM or mapped pinned memory) = {critic1_loss, critic2_loss, cql_alpha, cql_alpha_loss = -(cql_1 + cql_2) / 2,
+ *   d cql_alpha_loss / d log_alpha (zero where the clamp is active), log_alpha after the step}; the last four NaN with
+ *   log_alpha null.  exp_avg, exp_avg_sq f32 [1] and step i64 [1] in HBM (null together: log_alpha is not stepped): one
+ *   torch Adam step on log_alpha with that gradient (amsgrad off, no weight decay, 1 - beta formed in float64).
+ * tsm_td3bc_actor_head replaces  TD3+BC's actor loss and its backward down to the actor's raw output (td3_bc.py:113-119).
+ *           TWO launches: one workgroup sums {|q_pi|, q_pi} over the batch in a fixed order into qsum_work f64 [2] (the
+ *           gradient of every row depends on mean |q_pi|), then the head reads that device scalar.
+ *   dq_da[b * ld + k] = d Q / d a (tsm_mlp_input_grad with d_out = 1); one_minus_tanh2 [B][Ad] (tsm_cac_det_action's);
+ *   q_pi [B]; act_pi[b * ld_a + k]: the policy's action (the action columns of the critic's rows); act_data [B][Ad].
+ *   lmbda = alpha / mean |q_pi| (a constant of the backward);  actor_loss = -lmbda mean(q_pi) + mean((a - a_data)^2);
+ *   d_raw_out f32 [B][Ad] = (-lmbda / B dq_da + 2 (a - a_data) / (B Ad)) max_action one_minus_tanh2;
+ *   partial f64 [2 * ceil(B / TSM_CAC_ROWS_PER_BLOCK)] = {sum_b (-lmbda q_pi[b] + sum_k (a - a_data)^2 / Ad), 0}:
+ *   tsm_qmix_finalize(partial, n_blocks, B, out) gives {actor_loss, 0}.
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_CQL_ROWS_PER_BLOCK 256
+int tsm_cql_check(int32_t act_dim, int32_t num_repeat);
+int tsm_cql_uniform(float *out, int64_t n, double lo, double hi, uint64_t seed, uint64_t offset, const uint64_t *offset_dev,
+                    void *stream);
+int tsm_cql_rows(const float *obs, const float *obs_next, const float *act, const float *rand_act, int64_t B,
+                 int32_t num_repeat, int32_t obs_dim, int32_t act_dim, float *x_out, float *actor_rows_out, void *stream);
+int tsm_cql_head(const float *q1, const float *q2, const float *target, const float *logp_cur, const float *logp_next,
+                 const float *calib, int64_t B, int32_t num_repeat, double log_half_pow, double temperature, double cql_weight,
+                 double alpha_min, double alpha_max, const float *log_alpha, float *dq1, float *dq2, double *partial,
+                 void *stream);
+int tsm_cql_finalize(const double *partial, int64_t n_blocks, int64_t B, int32_t num_repeat, double cql_weight,
+                     double lagrange_threshold, double alpha_min, double alpha_max, float *log_alpha, float *exp_avg,
+                     float *exp_avg_sq, int64_t *step, double lr, double beta1, double beta2, double eps, float *out,
+                     void *stream);
+int tsm_td3bc_actor_head(const float *dq_da, int64_t ld, const float *one_minus_tanh2, const float *q_pi, const float *act_pi,
+                         int64_t ld_a, const float *act_data, int64_t B, int32_t act_dim, double max_action, double alpha,
+                         double *qsum_work, float *d_raw_out, double *partial, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Implicit Quantile Network (tianshou/algorithm/modelfree/iqn.py; utils/net/discrete.py:127-217; csrc/iqn.hip)
  * A network row is (b, s) = b * sample_size + s: out f32 [R][sample_size][n_act] (the reference's [B, A, S] logits are its
  * transposed view), e / phi f32 [R * sample_size][embedding_dim], taus f32 [R][sample_size].  The MLPs before and after the

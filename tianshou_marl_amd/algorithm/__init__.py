@@ -9,6 +9,8 @@ from .dsac import DiscreteSAC, DiscreteSACPolicy, DiscreteSACTrainingStats
 from .cac import (DDPG, SAC, TD3, ContinuousDeterministicPolicy, DDPGTrainingStats, GaussianNoise, SACPolicy,
                   SACTrainingStats, TD3TrainingStats)
 from .redq import REDQ, REDQPolicy, REDQTrainingStats
+from .cql import CQL, CQLTrainingStats
+from .td3_bc import TD3BC
 from .bdqn import BDQN, BDQNPolicy
 from .pg import A2C, Reinforce
 from .ppo import PPO, policy_within_training_step
@@ -22,4 +24,4 @@ __all__ = ["PPO", "A2C", "Reinforce", "GenericPPO", "DQN", "DiscreteQLearningPol
            "DDPG", "TD3", "SAC", "ContinuousDeterministicPolicy", "SACPolicy", "DDPGTrainingStats", "TD3TrainingStats",
            "SACTrainingStats", "GaussianNoise", "REDQ", "REDQPolicy", "REDQTrainingStats", "BDQN", "BDQNPolicy",
            "policy_within_training_step", "ICMOnPolicyWrapper", "ICMOffPolicyWrapper", "ICMTrainingStats",
-           "GAIL", "GailTrainingStats"]
+           "GAIL", "GailTrainingStats", "CQL", "CQLTrainingStats", "TD3BC"]

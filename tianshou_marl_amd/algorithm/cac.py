@@ -297,10 +297,15 @@ class ContinuousActionRows:
         _, omt2 = ops.cac_det_action(raw, actor.max_action, out=x_pi, col0=D, want_backward=True)
         q_pi = FlatMLP.forward(self.critic, x_pi, save=True)
         dq_da = self.critic.input_grad(w["ones"], D, Ad)
-        ah = ops.cac_det_actor_head(dq_da, omt2, q_pi, actor.max_action)
+        ah = self._det_actor_head(dq_da, omt2, q_pi, x_pi[:, D:], act)
         actor.backward(ah["d_raw"], w["n_split"], slabs=w["slabs_a"])
         self.policy_optim.step(w["slabs_a"])
         return ah["partial"]
+
+    def _det_actor_head(self, dq_da, omt2, q_pi, act_pi, act) -> dict:
+        """The deterministic actor's loss head -> dict(d_raw, partial): -mean Q (ddpg.py:406, td3.py:216); a subclass with
+        another actor loss (TD3+BC) reads the policy's action `act_pi` and the batch's `act` as well."""
+        return ops.cac_det_actor_head(dq_da, omt2, q_pi, self.policy.actor.max_action)
 
     def _sac_actor_step(self, w: dict, obs, act, B: int, critics, alpha_dev) -> dict:
         """The Gaussian-tanh actor's step (sac.py:315-322, redq.py:284-291): a sample of the actor in the action columns of

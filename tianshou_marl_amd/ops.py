@@ -2364,6 +2364,115 @@ def sac_actor_head(raw, z, q1a, q2a, dq1_da, dq2_da, alpha_dev, max_action: floa
 
 
 # --------------------------------------------------------------------------------------------
+# Offline continuous learners: CQL / Cal-QL and TD3+BC (imitation/cql.py, td3_bc.py; csrc/cql.hip)
+# --------------------------------------------------------------------------------------------
+def cql_check(act_dim: int, num_repeat: int = 1) -> None:
+    """The bounds of the CQL kernels (include/tsmarl.h): ValueError naming the limit."""
+    call("tsm_cql_check", int(act_dim), int(num_repeat))
+
+
+def cql_uniform(n: int, lo: float, hi: float, seed: int, offset: int = 0, offset_dev=None, device="cuda", out=None):
+    """n uniforms f32 in [lo, hi) (`uniform_(lo, hi)`, cql.py:303-307) from Philox (seed, offset + *offset_dev) under this
+    draw's own key; lo == hi gives lo."""
+    out = _out("cql_uniform", out, (int(n),), torch.float32, device, size="numel")
+    call("tsm_cql_uniform", ptr(out), int(n), float(lo), float(hi), *_philox("cql_uniform", seed, offset, offset_dev), stream_ptr())
+    return out
+
+
+def cql_rows(obs, obs_next, act, rand_act, num_repeat: int, out=None, actor_rows=None):
+    """The critics' stacked row block and the actor's rows of one CQL update in one launch (include/tsmarl.h: tsm_cql_rows).
+    obs, obs_next [B, D], act [B, Ad], rand_act [B R, Ad] -> (x [B + 3 B R, D + Ad], actor_rows [2 B R, D]); the action columns
+    of x's last 2 B R rows are left as they are, for `sac_action(out=x[B + B R:], col0=D)`."""
+    _dev_only("cql_rows", obs, obs_next, act, rand_act)
+    obs, obs_next, act, rand_act = (_chk(t, torch.float32, nm) for t, nm in ((obs, "obs"), (obs_next, "obs_next"), (act, "act"),
+                                                                              (rand_act, "rand_act")))
+    if obs.dim() != 2 or act.dim() != 2 or obs.shape[0] < 1 or act.shape[0] != obs.shape[0]:
+        raise ValueError("cql_rows: obs must be [B, D] and act [B, Ad] with B >= 1")
+    (B, D), Ad, R = obs.shape, act.shape[1], int(num_repeat)
+    cql_check(Ad, R)
+    if tuple(obs_next.shape) != (B, D) or tuple(rand_act.shape) != (B * R, Ad):
+        raise ValueError(f"cql_rows: obs_next must be [{B}, {D}] and rand_act [{B * R}, {Ad}]")
+    out = _out("cql_rows", out, (B + 3 * B * R, D + Ad), torch.float32, obs.device)
+    actor_rows = _out("cql_rows", actor_rows, (2 * B * R, D), torch.float32, obs.device, "actor_rows")
+    call("tsm_cql_rows", ptr(obs), ptr(obs_next), ptr(act), ptr(rand_act), B, R, D, Ad, ptr(out), ptr(actor_rows), stream_ptr())
+    return out, actor_rows
+
+
+def cql_head(q1, q2, target, logp_cur, logp_next, num_repeat: int, act_dim: int, calib=None, temperature: float = 1.0,
+             cql_weight: float = 1.0, alpha_min: float = 0.0, alpha_max: float = 1e6, log_alpha=None):
+    """Both critics' CQL loss between the forward on `cql_rows`' block and the backward (include/tsmarl.h: tsm_cql_head), one
+    launch.  q1, q2 [B + 3 B R]; target [B]; logp_cur, logp_next [B R]; calib [B] or None; log_alpha f32 [1] in HBM or None
+    (no multiplier).  -> dict(dq1, dq2 [B + 3 B R], partial f64) for `cql_finalize`."""
+    _dev_only("cql_head", q1, q2, target, logp_cur, logp_next, calib, log_alpha)
+    B, R = target.numel(), int(num_repeat)
+    cql_check(act_dim, R)
+    if B < 1:
+        raise ValueError("cql_head: empty batch")
+    n = B + 3 * B * R
+    q1, q2 = _head_args("cql_head", n, (), (("q1", q1, torch.float32), ("q2", q2, torch.float32)))
+    (target, calib) = _head_args("cql_head", B, (), (("target", target, torch.float32), ("calib", calib, torch.float32)))
+    lpc, lpn = _head_args("cql_head", B * R, (), (("logp_cur", logp_cur, torch.float32), ("logp_next", logp_next, torch.float32)))
+    dev = q1.device
+    out = dict(dq1=torch.empty(n, dtype=torch.float32, device=dev), dq2=torch.empty(n, dtype=torch.float32, device=dev),
+               partial=torch.empty(6 * -(-B * R // _abi.CQL_ROWS_PER_BLOCK), dtype=torch.float64, device=dev))
+    # np.log(0.5 ** act.shape[-1]) (cql.py:236) in float64, as numpy forms it
+    call("tsm_cql_head", ptr(q1), ptr(q2), ptr(target), ptr(lpc), ptr(lpn), ptr(calib), B, R, math.log(0.5 ** int(act_dim)),
+         float(temperature), float(cql_weight), float(alpha_min), float(alpha_max),
+         ptr(None if log_alpha is None else _chk(log_alpha, torch.float32, "log_alpha")), ptr(out["dq1"]), ptr(out["dq2"]),
+         ptr(out["partial"]), stream_ptr())
+    return out
+
+
+def cql_finalize(partial, B: int, num_repeat: int, out, cql_weight: float = 1.0, lagrange_threshold: float = 10.0,
+                 alpha_min: float = 0.0, alpha_max: float = 1e6, log_alpha=None, exp_avg=None, exp_avg_sq=None, step=None,
+                 lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8):
+    """The scalars of one CQL critic loss from `cql_head`'s partials and the multiplier's Adam step, one launch
+    (include/tsmarl.h: tsm_cql_finalize).  out f32 [6] (HBM or pinned) <- {critic1_loss, critic2_loss, cql_alpha,
+    cql_alpha_loss, d cql_alpha_loss / d log_alpha, log_alpha after the step}.  log_alpha f32 [1] in HBM or None; exp_avg,
+    exp_avg_sq f32 [1], step i64 [1] in HBM, updated in place, or all None: no step."""
+    _dev_only("cql_finalize", partial, log_alpha, exp_avg, exp_avg_sq, step)
+    partial = _chk(partial, torch.float64, "partial").reshape(-1)
+    if partial.numel() < 6 or partial.numel() % 6:
+        raise ValueError("cql_finalize: partial must hold six sums per workgroup")
+    state = (exp_avg, exp_avg_sq, step)
+    if any(s is None for s in state) != all(s is None for s in state) or (exp_avg is not None and log_alpha is None):
+        raise ValueError("cql_finalize: exp_avg, exp_avg_sq and step come together, with log_alpha")
+    if log_alpha is not None:   # (stepped in place)
+        _out("cql_finalize", log_alpha, (1,), torch.float32, None, "log_alpha", "min")
+    if exp_avg is not None:
+        for nm, t, dt in (("exp_avg", exp_avg, torch.float32), ("exp_avg_sq", exp_avg_sq, torch.float32), ("step", step, torch.int64)):
+            _out("cql_finalize", t, (1,), dt, None, nm, "min")
+    call("tsm_cql_finalize", ptr(partial), partial.numel() // 6, int(B), int(num_repeat), float(cql_weight), float(lagrange_threshold),
+         float(alpha_min), float(alpha_max), ptr(log_alpha), ptr(exp_avg), ptr(exp_avg_sq), ptr(step), float(lr), float(betas[0]),
+         float(betas[1]), float(eps), _out_or_pinned("cql_finalize", out, 6), stream_ptr())
+    return out
+
+
+def td3bc_actor_head(dq_da, one_minus_tanh2, q_pi, act_pi, act_data, alpha: float, max_action: float = 1.0, out=None):
+    """TD3+BC's actor loss -lmbda mean Q(s, pi(s)) + mse(pi(s), a), lmbda = alpha / mean |Q|, and its gradient w.r.t. the
+    actor's raw output (td3_bc.py:113-119), two launches (include/tsmarl.h: tsm_td3bc_actor_head).  dq_da,
+    one_minus_tanh2, act_data [B, Ad]; q_pi [B]; act_pi [B, Ad]: the policy's action, which may be the action columns of the
+    critic's rows (a column slice).  -> dict(d_raw [B, Ad], partial f64): `qmix_finalize(partial, B, out)` gives {actor_loss, 0}."""
+    _dev_only("td3bc_actor_head", dq_da, one_minus_tanh2, q_pi, act_pi, act_data)
+    if dq_da.dim() != 2 or dq_da.shape[0] < 1:
+        raise ValueError("td3bc_actor_head: dq_da must be [B, Ad] with B >= 1")
+    B, Ad = dq_da.shape
+    cac_check(Ad)
+    dq_da = _cac_grad("td3bc_actor_head", dq_da, B, Ad, "dq_da")
+    omt2 = _cac_grad("td3bc_actor_head", one_minus_tanh2, B, Ad, "one_minus_tanh2")
+    act_data = _cac_grad("td3bc_actor_head", act_data, B, Ad, "act_data")
+    if tuple(act_pi.shape) != (B, Ad) or act_pi.dtype != torch.float32 or act_pi.stride(1) != 1 or (B > 1 and act_pi.stride(0) < Ad):
+        raise ValueError(f"td3bc_actor_head: act_pi must be f32 [{B}, {Ad}] with unit column stride")
+    (q_pi,) = _head_args("td3bc_actor_head", B, (), (("q_pi", q_pi, torch.float32),))
+    dev = dq_da.device
+    out = _out("td3bc_actor_head", out, (B, Ad), torch.float32, dev)
+    partial, qsum = _head_partial(B, _abi.CAC_ROWS_PER_BLOCK, dev), torch.empty(2, dtype=torch.float64, device=dev)
+    call("tsm_td3bc_actor_head", ptr(dq_da), Ad, ptr(omt2), ptr(q_pi), act_pi.data_ptr(), act_pi.stride(0) if B > 1 else Ad,
+         ptr(act_data), B, Ad, float(max_action), float(alpha), ptr(qsum), ptr(out), ptr(partial), stream_ptr())
+    return dict(d_raw=out, partial=partial, qsum=qsum)
+
+
+# --------------------------------------------------------------------------------------------
 # REDQ (redq.py; csrc/redq.hip)
 # --------------------------------------------------------------------------------------------
 def redq_subset_mask(indices, ensemble_size: int) -> int:
