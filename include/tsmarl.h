@@ -1286,6 +1286,69 @@ int tsm_td3bc_actor_head(const float *dq_da, int64_t ld, const float *one_minus_
                          double *qsum_work, float *d_raw_out, double *partial, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * BCQ: VAE action model, perturbation actor, target and acting  (tianshou/algorithm/imitation/bcq.py;
+ * utils/net/continuous.py:395-513; csrc/bcq.hip)
+ * With B transitions, K = num_sampled_action, S = forward_sampled_times, L = latent_dim, D = obs_dim, Ad = act_dim.  The encoder
+ * emits head f32 [B][2 L] = [mean | raw log_std]; the decoder reads rows [obs | z] of D + L floats and emits raw (pre-tanh)
+ * actions; the perturbation net and the critics read rows [obs | act] of D + Ad floats.  All entries take a stream and read
+ * nothing from the host; all are row-wise, float64 arithmetic from the float32 inputs rounded once; every documented output
+ * element is written and no other; rows need no alignment.  The normals are tsm_cac_normal's.
+ * tsm_bcq_check: act_dim in [1, TSM_CAC_MAX_ACT_DIM], latent_dim in [1, 2 TSM_CAC_MAX_ACT_DIM], num_sampled >= 1:
+ *   TSM_ERR_INVALID naming the limit.  Needs no device.
+ * tsm_bcq_latent replaces  the clamp, exp and reparameterised latent of VAE.forward and the torch.cat([state, z]) of decode
+ *           (continuous.py:487-495, 513).  std_out f32 [B][L] = exp(clamp(head[b][L + j], -4, 15));
+ *   x_dec_out f32 [B][D + L] = [obs[b] | head[b][j] + std eps[b][j]].
+ * tsm_bcq_decode_rows replaces  repeat_interleave (bcq.py:213), the clamp of decode's normals (continuous.py:508-510) and its
+ *           torch.cat, for two groups of observations in one launch.  src_a [n_a][D] with each row repeated rep_a times,
+ *   src_b [n_b][D] (n_b = 0: src_b nullable), z [n_a rep_a + n_b][L] unclamped normals.
+ *   rows_out f32 [n_a rep_a + n_b][D + L]: row i < n_a rep_a = [src_a[i / rep_a] | clamp(z[i], -0.5, 0.5)], row n_a rep_a + j =
+ *   [src_b[j] | clamp(z[n_a rep_a + j], -0.5, 0.5)]; a NaN normal stays a NaN.
+ * tsm_bcq_action_rows replaces  max_action * tanh(decoder(.)) (continuous.py:513) and the torch.cat([obs, act]) behind it.
+ *   raw [n][Ad], x_dec [n][D + L];  x_out f32 [n][D + Ad] = [x_dec[i][:D] | max_action tanh(raw[i])].
+ * tsm_bcq_target replaces  bcq.py:223-237.  q1, q2 f32 [B K]: the LAGGED critics on the K decoded (not perturbed) actions of
+ *           every obs_next; rew [B]; vmask u8 [B] = not done.
+ *   target_out f32 [B] = rew + vmask f32(gamma) max_k(lmbda min(q1, q2) + (1 - lmbda) max(q1, q2)); a NaN is kept.
+ * tsm_bcq_vae_head replaces  recon_loss, KL_loss (bcq.py:203-206) and the backward of vae_loss down to the decoder's raw
+ *           output.  raw_dec [B][Ad], act [B][Ad], head [B][2 L].  csrc/cac.hip's shape: TSM_CAC_ROWS_PER_BLOCK rows per
+ *           workgroup of four waves, each wave walking four rows one after another, a row's components across its lanes.
+ *   d_raw_out f32 [B][Ad] = 2 (recon - act) / (B Ad) max_action (1 - tanh^2(raw_dec)), recon = max_action tanh(raw_dec);
+ *   partial f64 [2 * ceil(B / TSM_CAC_ROWS_PER_BLOCK)] = {sum_b (sum_k (act - recon)^2 / Ad + kl_b / (2 L)), sum_b kl_b / L},
+ *   kl_b = sum_j (-clamp(ls) + (std^2 + mean^2 - 1) / 2):  tsm_qmix_finalize(partial, n_blocks, B, out) gives
+ *   {vae_loss = recon_loss + KL_loss / 2, KL_loss}.  (The sums are scaled per row, not the raw {sum (act - recon)^2, sum kl}, so that
+ *   the existing finalize's division by B is all that is left and no BCQ finalize is needed.)
+ * tsm_bcq_latent_grad: the decoder's input gradient -> the gradient of the encoder's output.  dz [B][L]: tsm_mlp_input_grad of
+ *           the decoder on columns [D, D + L) with d_out = d_raw_out;  head, eps as tsm_bcq_latent took them.
+ *   d_head_out f32 [B][2 L]: [b][j] = dz + mean / (2 B L);  [b][L + j] = m (dz eps std + (std^2 - 1) / (2 B L)) with m = 1 where
+ *   -4 <= ls <= 15 (torch.clamp's backward: bounds included), else 0.
+ * tsm_bcq_perturb replaces  Perturbation.forward behind its net (continuous.py:429-432).  raw_p [n][Ad]: the net on x_in
+ *           [n][D + Ad], whose action columns hold the base action a.  With u = a + phi max_action tanh(raw_p):
+ *   x_out f32 [n][D + Ad] (not x_in) = [x_in[i][:D] | clamp(u, -max_action, max_action)];
+ *   factor_out f32 [n][Ad] (nullable) = phi (1 - tanh^2(raw_p)) where -max_action <= u <= max_action, else 0: with
+ *   tsm_cac_det_actor_head(dq_da, factor, q_pi, max_action) the actor's loss -mean Q and its gradient at raw_p.
+ * tsm_bcq_select replaces  q1.argmax(0) and act[max_indice] per observation (bcq.py:103-115).  q f32 [n S]; the candidate
+ *           actions rows[(g S + s) * ld + col0 + k].  One wave per observation.
+ *   index_out i32 [n] = the FIRST s with the maximal q of group g (a NaN counts as the maximum, as torch.argmax);
+ *   act_out f32 [n][Ad] = that candidate's action, bit for bit.
+ * ------------------------------------------------------------------------------------------- */
+int tsm_bcq_check(int32_t act_dim, int32_t latent_dim, int32_t num_sampled);
+int tsm_bcq_latent(const float *head, const float *eps, const float *obs, int64_t B, int32_t obs_dim, int32_t latent_dim,
+                   float *x_dec_out, float *std_out, void *stream);
+int tsm_bcq_decode_rows(const float *src_a, int64_t n_a, int32_t rep_a, const float *src_b, int64_t n_b, const float *z,
+                        int32_t obs_dim, int32_t latent_dim, float *rows_out, void *stream);
+int tsm_bcq_action_rows(const float *raw, const float *x_dec, int64_t n, int32_t obs_dim, int32_t latent_dim, int32_t act_dim,
+                        double max_action, float *x_out, void *stream);
+int tsm_bcq_target(const float *q1, const float *q2, const float *rew, const uint8_t *vmask, int64_t B, int32_t num_sampled,
+                   double gamma, double lmbda, float *target_out, void *stream);
+int tsm_bcq_vae_head(const float *raw_dec, const float *act, const float *head, int64_t B, int32_t act_dim, int32_t latent_dim,
+                     double max_action, float *d_raw_out, double *partial, void *stream);
+int tsm_bcq_latent_grad(const float *dz, const float *head, const float *eps, int64_t B, int32_t latent_dim, float *d_head_out,
+                        void *stream);
+int tsm_bcq_perturb(const float *raw_p, const float *x_in, int64_t n, int32_t obs_dim, int32_t act_dim, double phi,
+                    double max_action, float *x_out, float *factor_out, void *stream);
+int tsm_bcq_select(const float *q, const float *rows, int64_t ld, int32_t col0, int64_t n, int32_t num_sampled, int32_t act_dim,
+                   float *act_out, int32_t *index_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Implicit Quantile Network (tianshou/algorithm/modelfree/iqn.py; utils/net/discrete.py:127-217; csrc/iqn.hip)
  * A network row is (b, s) = b * sample_size + s: out f32 [R][sample_size][n_act] (the reference's [B, A, S] logits are its
  * transposed view), e / phi f32 [R * sample_size][embedding_dim], taus f32 [R][sample_size].  The MLPs before and after the

@@ -11,6 +11,7 @@ from .cac import (DDPG, SAC, TD3, ContinuousDeterministicPolicy, DDPGTrainingSta
 from .redq import REDQ, REDQPolicy, REDQTrainingStats
 from .cql import CQL, CQLTrainingStats
 from .td3_bc import TD3BC
+from .bcq import BCQ, BCQPolicy, BCQTrainingStats
 from .bdqn import BDQN, BDQNPolicy
 from .pg import A2C, Reinforce
 from .ppo import PPO, policy_within_training_step
@@ -24,4 +25,5 @@ __all__ = ["PPO", "A2C", "Reinforce", "GenericPPO", "DQN", "DiscreteQLearningPol
            "DDPG", "TD3", "SAC", "ContinuousDeterministicPolicy", "SACPolicy", "DDPGTrainingStats", "TD3TrainingStats",
            "SACTrainingStats", "GaussianNoise", "REDQ", "REDQPolicy", "REDQTrainingStats", "BDQN", "BDQNPolicy",
            "policy_within_training_step", "ICMOnPolicyWrapper", "ICMOffPolicyWrapper", "ICMTrainingStats",
-           "GAIL", "GailTrainingStats", "CQL", "CQLTrainingStats", "TD3BC"]
+           "GAIL", "GailTrainingStats", "CQL", "CQLTrainingStats", "TD3BC", "BCQ", "BCQPolicy",
+           "BCQTrainingStats"]

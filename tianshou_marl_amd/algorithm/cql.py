@@ -40,6 +40,20 @@ class CQLTrainingStats(SACTrainingStats):
     cql_alpha_loss: float | None = None
 
 
+def offline_batch_rows(algo, batch: Batch, buffer, indices, agent: int | None):
+    """What an offline learner's `_preprocess_batch` gathers from the device stores (CQL, BCQ): obs, act, rew, done (terminated
+    | truncated: the batch's own flag, not the n-step walk's) and obs_next of the sampled rows, read at the agent's column.
+    -> (the indices i64 in HBM, the agent's reward column)."""
+    idx = to_tensor(indices, algo.device, torch.int64).reshape(-1)
+    k, col = algo._agent_column(buffer, agent)
+    batch.obs = buffer._gather(buffer.obs_store, idx)[:, col].contiguous()
+    batch.act = buffer._gather(buffer.act_store, idx)[:, col].contiguous()
+    batch.rew = buffer._gather(buffer.rew_store, idx)[:, k].contiguous()
+    batch.done = buffer._gather(buffer.done_store.unsqueeze(-1), idx).reshape(-1)
+    batch.obs_next, _ = algo._successor_rows(buffer, idx, col)
+    return idx, k
+
+
 class CQL(EntropyCoefficient, ContinuousActionRows, ActorDualCriticsOffPolicyAlgorithm):
     """cql.py:32-400."""
 
@@ -129,13 +143,7 @@ class CQL(EntropyCoefficient, ContinuousActionRows, ActorDualCriticsOffPolicyAlg
     def _preprocess_batch(self, batch: Batch, buffer, indices, agent: int | None = None) -> Batch:
         """The sampled rows from the device stores: obs, act, rew, done (terminated | truncated: the batch's own flag, not the
         n-step walk's), obs_next and, with `calibrated`, the calibration returns."""
-        idx = to_tensor(indices, self.device, torch.int64).reshape(-1)
-        k, col = self._agent_column(buffer, agent)
-        batch.obs = buffer._gather(buffer.obs_store, idx)[:, col].contiguous()
-        batch.act = buffer._gather(buffer.act_store, idx)[:, col].contiguous()
-        batch.rew = buffer._gather(buffer.rew_store, idx)[:, k].contiguous()
-        batch.done = buffer._gather(buffer.done_store.unsqueeze(-1), idx).reshape(-1)
-        batch.obs_next, _ = self._successor_rows(buffer, idx, col)
+        idx, k = offline_batch_rows(self, batch, buffer, indices, agent)
         if self.calibrated:
             if self._calib is None:
                 raise RuntimeError("CQL(calibrated=True): call process_buffer(buffer) before the first update")

@@ -2473,6 +2473,137 @@ def td3bc_actor_head(dq_da, one_minus_tanh2, q_pi, act_pi, act_data, alpha: floa
 
 
 # --------------------------------------------------------------------------------------------
+# BCQ (imitation/bcq.py, utils/net/continuous.py:395-513; csrc/bcq.hip)
+# --------------------------------------------------------------------------------------------
+def bcq_check(act_dim: int, latent_dim: int = 1, num_sampled: int = 1) -> None:
+    """The bounds of the BCQ kernels (include/tsmarl.h): ValueError naming the limit.  For constructors: every entry point
+    checks its own arguments, so the wrappers below do not call it."""
+    call("tsm_bcq_check", int(act_dim), int(latent_dim), int(num_sampled))
+
+
+def _bcq_rows(name: str, what: str, t, rows: int | None = None, width: int | None = None):
+    """`t` as a contiguous device f32 [rows, width] (None: any, at least one row and one column) -> (t, rows, width)."""
+    _dev_only(name, t)
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1 or (rows is not None and t.shape[0] != rows) or \
+            (width is not None and t.shape[1] != width):
+        want = ["n" if rows is None else rows, "width" if width is None else width]
+        raise ValueError(f"{name}: {what} must be {want}, got {list(t.shape)}")
+    return _chk(t, torch.float32, what), t.shape[0], t.shape[1]
+
+
+def bcq_latent(head, eps, obs, out=None):
+    """The VAE's reparameterised latent beside its observation (include/tsmarl.h: tsm_bcq_latent): head [B, 2 L] = [mean | raw
+    log_std], eps [B, L], obs [B, D] -> (x_dec [B, D + L] = [obs | mean + std eps], std [B, L])."""
+    eps, B, L = _bcq_rows("bcq_latent", "eps", eps)
+    head, _, _ = _bcq_rows("bcq_latent", "head", head, B, 2 * L)
+    obs, _, D = _bcq_rows("bcq_latent", "obs", obs, B)
+    out = _out("bcq_latent", out, (B, D + L), torch.float32, obs.device)
+    std = torch.empty(B, L, dtype=torch.float32, device=obs.device)
+    call("tsm_bcq_latent", ptr(head), ptr(eps), ptr(obs), B, D, L, ptr(out), ptr(std), stream_ptr())
+    return out, std
+
+
+def bcq_decode_rows(src_a, rep_a: int, src_b, z, out=None):
+    """The decoder's rows for `decode(obs)` with fresh clamped normals, two groups in one launch (include/tsmarl.h:
+    tsm_bcq_decode_rows): src_a [n_a, D] each repeated rep_a times, src_b [n_b, D] or None, z [n_a rep_a + n_b, L]
+    -> [n_a rep_a + n_b, D + L]."""
+    src_a, n_a, D = _bcq_rows("bcq_decode_rows", "src_a", src_a)
+    n_b = 0
+    if src_b is not None:
+        src_b, n_b, _ = _bcq_rows("bcq_decode_rows", "src_b", src_b, None, D)
+    n = n_a * max(int(rep_a), 0) + n_b
+    z, _, L = _bcq_rows("bcq_decode_rows", "z", z, n)
+    out = _out("bcq_decode_rows", out, (n, D + L), torch.float32, src_a.device)
+    call("tsm_bcq_decode_rows", ptr(src_a), n_a, int(rep_a), ptr(src_b), n_b, ptr(z), D, L, ptr(out), stream_ptr())
+    return out
+
+
+def bcq_action_rows(raw, x_dec, obs_dim: int, max_action: float = 1.0, out=None):
+    """`max_action * tanh(raw)` beside the observation of the decoder's rows (include/tsmarl.h: tsm_bcq_action_rows): raw
+    [n, Ad], x_dec [n, D + L] -> [n, D + Ad]."""
+    raw, n, Ad = _bcq_rows("bcq_action_rows", "raw", raw)
+    x_dec, _, Wd = _bcq_rows("bcq_action_rows", "x_dec", x_dec, n)
+    D = int(obs_dim)
+    if not 1 <= D < Wd:
+        raise ValueError(f"bcq_action_rows: obs_dim = {D} outside [1, {Wd}), the decoder rows' width")
+    out = _out("bcq_action_rows", out, (n, D + Ad), torch.float32, raw.device)
+    call("tsm_bcq_action_rows", ptr(raw), ptr(x_dec), n, D, Wd - D, Ad, float(max_action), ptr(out), stream_ptr())
+    return out
+
+
+def bcq_target(q1, q2, rew, vmask, num_sampled: int, gamma: float, lmbda: float, out=None):
+    """bcq.py:223-237 (include/tsmarl.h: tsm_bcq_target): q1, q2 [B K] of the lagged critics, rew [B], vmask [B] -> target [B]."""
+    _dev_only("bcq_target", q1, q2, rew, vmask)
+    B, K = rew.numel(), int(num_sampled)
+    if B < 1:
+        raise ValueError("bcq_target: empty batch")
+    q1, q2 = _head_args("bcq_target", B * K, (), (("q1", q1, torch.float32), ("q2", q2, torch.float32)))
+    rew, vmask = _head_args("bcq_target", B, (), (("rew", rew, torch.float32), ("vmask", vmask, torch.uint8)))
+    out = _out("bcq_target", out, (B,), torch.float32, q1.device, size="numel")
+    call("tsm_bcq_target", ptr(q1), ptr(q2), ptr(rew), ptr(vmask), B, K, float(gamma), float(lmbda), ptr(out), stream_ptr())
+    return out
+
+
+def bcq_vae_head(raw_dec, act, head, max_action: float = 1.0, out=None):
+    """vae_loss = mse(act, recon) + KL / 2 and its gradient at the decoder's raw output (include/tsmarl.h: tsm_bcq_vae_head):
+    raw_dec, act [B, Ad], head [B, 2 L] -> dict(d_raw [B, Ad], partial f64): `qmix_finalize(partial, B, out)` gives
+    {vae_loss, KL_loss}."""
+    raw_dec, B, Ad = _bcq_rows("bcq_vae_head", "raw_dec", raw_dec)
+    act, _, _ = _bcq_rows("bcq_vae_head", "act", act, B, Ad)
+    head, _, L2 = _bcq_rows("bcq_vae_head", "head", head, B)
+    if L2 % 2:
+        raise ValueError("bcq_vae_head: head is [mean | log_std], an even number of columns")
+    out = _out("bcq_vae_head", out, (B, Ad), torch.float32, raw_dec.device)
+    partial = _head_partial(B, _abi.CAC_ROWS_PER_BLOCK, raw_dec.device)
+    call("tsm_bcq_vae_head", ptr(raw_dec), ptr(act), ptr(head), B, Ad, L2 // 2, float(max_action), ptr(out), ptr(partial),
+         stream_ptr())
+    return dict(d_raw=out, partial=partial)
+
+
+def bcq_latent_grad(dz, head, eps, out=None):
+    """The decoder's input gradient dz [B, L] -> the gradient of the encoder's output [B, 2 L] (include/tsmarl.h:
+    tsm_bcq_latent_grad); head, eps as `bcq_latent` took them."""
+    eps, B, L = _bcq_rows("bcq_latent_grad", "eps", eps)
+    dz, _, _ = _bcq_rows("bcq_latent_grad", "dz", dz, B, L)
+    head, _, _ = _bcq_rows("bcq_latent_grad", "head", head, B, 2 * L)
+    out = _out("bcq_latent_grad", out, (B, 2 * L), torch.float32, dz.device)
+    call("tsm_bcq_latent_grad", ptr(dz), ptr(head), ptr(eps), B, L, ptr(out), stream_ptr())
+    return out
+
+
+def bcq_perturb(raw_p, x_in, phi: float, max_action: float = 1.0, out=None, want_factor: bool = True):
+    """Perturbation.forward behind its net (include/tsmarl.h: tsm_bcq_perturb): raw_p [n, Ad], x_in [n, D + Ad] the rows the
+    net read -> (x_out [n, D + Ad] with the perturbed, clamped action, factor [n, Ad] for `cac_det_actor_head` or None)."""
+    raw_p, n, Ad = _bcq_rows("bcq_perturb", "raw_p", raw_p)
+    x_in, _, W = _bcq_rows("bcq_perturb", "x_in", x_in, n)
+    if W <= Ad:
+        raise ValueError(f"bcq_perturb: rows of {W} floats hold no observation beside {Ad} action components")
+    out = _out("bcq_perturb", out, (n, W), torch.float32, raw_p.device)
+    if out.data_ptr() == x_in.data_ptr():
+        raise ValueError("bcq_perturb: out must not be x_in")
+    factor = torch.empty(n, Ad, dtype=torch.float32, device=raw_p.device) if want_factor else None
+    call("tsm_bcq_perturb", ptr(raw_p), ptr(x_in), n, W - Ad, Ad, float(phi), float(max_action), ptr(out), ptr(factor),
+         stream_ptr())
+    return out, factor
+
+
+def bcq_select(q, rows, num_sampled: int, col0: int, act_dim: int, out=None):
+    """The candidate of the first maximal q per group of `num_sampled` (include/tsmarl.h: tsm_bcq_select): q [n S], rows
+    [n S, W] whose columns [col0, col0 + act_dim) hold the candidates -> (act [n, act_dim], index i32 [n])."""
+    _dev_only("bcq_select", q)
+    rows, nS, W = _bcq_rows("bcq_select", "rows", rows)
+    S, Ad = int(num_sampled), int(act_dim)
+    if S < 1 or nS % S or not 0 <= col0 <= W - Ad:
+        raise ValueError(f"bcq_select: {nS} rows of {W} floats for groups of {S} and columns [{col0}, {col0 + Ad})")
+    (q,) = _head_args("bcq_select", nS, (), (("q", q, torch.float32),))
+    n = nS // S
+    out = _out("bcq_select", out, (n, Ad), torch.float32, rows.device)
+    index = torch.empty(n, dtype=torch.int32, device=rows.device)
+    call("tsm_bcq_select", ptr(q), ptr(rows), W, int(col0), n, S, Ad, ptr(out), ptr(index), stream_ptr())
+    return out, index
+
+
+# --------------------------------------------------------------------------------------------
 # REDQ (redq.py; csrc/redq.hip)
 # --------------------------------------------------------------------------------------------
 def redq_subset_mask(indices, ensemble_size: int) -> int:

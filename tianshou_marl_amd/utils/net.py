@@ -457,6 +457,121 @@ class ContinuousActorProbabilistic(_ContinuousNet):
         return [("sigma_param", self.param_views(flat)[-1])] + trunk + [("mu.model.0.weight", W), ("mu.model.0.bias", b)]
 
 
+class Perturbation(_ContinuousNet):
+    """continuous.py:395-432: BCQ's perturbation net, rows [obs | act] -> hidden ... -> act_dim raw outputs, with the two
+    constants of its epilogue `clamp(act + phi * max_action * tanh(raw), +-max_action)` (`ops.bcq_perturb`, which `forward`
+    does NOT apply: the learner needs the raw output for the backward).  The reference's `preprocess_net` is a
+    `Net(hidden_sizes=[...])`; a checkpoint carries the layers under `preprocess_net.model.model.{2 i}`."""
+
+    ref_scheme = "body"
+
+    def __init__(self, *, obs_dim: int, act_dim: int, hidden_sizes=(64, 64), max_action: float = 1.0, phi: float = 0.05,
+                 act: str = "relu", device: str | torch.device = "cuda", seed: int | None = None,
+                 storage: torch.Tensor | None = None) -> None:
+        ops.bcq_check(int(act_dim))
+        super().__init__([int(obs_dim) + int(act_dim), *[int(h) for h in hidden_sizes], int(act_dim)], act, device=device,
+                         seed=seed, storage=storage)
+        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
+        self.max_action, self.phi = float(max_action), float(phi)
+
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        return [("preprocess_net." + k, v) for k, v in super().reference_named_views(flat)]
+
+
+class VAE(FlatNet):
+    """continuous.py:435-513: BCQ's conditional VAE of the action on ONE flat f32 vector [encoder | decoder].  The reference's
+    encoder (an `MLP` that ends in its activation) and its two linear heads `mean` and `log_std` are ONE `FlatMLP`
+    [D + Ad, *encoder_hidden_sizes, 2 L]: rows [0, L) of its last layer are `mean`, rows [L, 2 L) `log_std`, so one forward, one
+    backward and one `input_grad` serve the three modules and the head's output is [mean | raw log_std].  The decoder is a
+    `FlatMLP` [D + L, *decoder_hidden_sizes, Ad].  So the vector's order is not the reference's `parameters()` order (there
+    mean.weight, mean.bias, log_std.weight, log_std.bias follow one another); `reference_named_views` gives its keys as views.
+    The latent, the loss and their gradients are csrc/bcq.hip's; `forward` takes the normals as an argument."""
+
+    def __init__(self, *, encoder_hidden_sizes=(750, 750), decoder_hidden_sizes=(750, 750), obs_dim: int, act_dim: int,
+                 latent_dim: int, max_action: float = 1.0, act: str = "relu", device: str | torch.device = "cuda",
+                 seed: int | None = None, storage: torch.Tensor | None = None) -> None:
+        super().__init__()
+        D, Ad, L = self.obs_dim, self.act_dim, self.latent_dim = int(obs_dim), int(act_dim), int(latent_dim)
+        ops.bcq_check(Ad, L)
+        if not len(encoder_hidden_sizes):
+            raise ValueError("VAE: the encoder needs a hidden layer (the reference's hidden_dim feeds the mean and log_std heads)")
+        self.max_action, self.act = float(max_action), act
+        enc_dims = [D + Ad, *[int(h) for h in encoder_hidden_sizes], 2 * L]
+        dec_dims = [D + L, *[int(h) for h in decoder_hidden_sizes], Ad]
+        self.n_enc = ops.mlp_param_count(ops.mlp_desc(enc_dims, act))
+        n_dec = ops.mlp_param_count(ops.mlp_desc(dec_dims, act))
+        storage = self._claim(self.n_enc + n_dec, storage, device)
+        self.encoder = FlatMLP(enc_dims, act, device=storage.device, seed=seed, storage=storage[:self.n_enc])
+        self.decoder = FlatMLP(dec_dims, act, device=storage.device, seed=None if seed is None else seed + 1,
+                               storage=storage[self.n_enc:])
+        self.dims = [D + Ad, Ad]
+
+    def rebind(self, storage: torch.Tensor) -> None:
+        storage.copy_(self.flat.data)
+        self.flat = nn.Parameter(storage, requires_grad=False)
+        self.encoder.rebind(storage[:self.n_enc])
+        self.decoder.rebind(storage[self.n_enc:])
+
+    def param_views(self, flat: torch.Tensor | None = None) -> list[torch.Tensor]:
+        """The layers in the vector's order: the encoder's, its last one whole ([mean | log_std]), then the decoder's."""
+        flat = self._vector(flat)
+        return [v for net, part in ((self.encoder, flat[:self.n_enc]), (self.decoder, flat[self.n_enc:]))
+                for Wb in net.layer_views(part) for v in Wb]
+
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        """`encoder.model.{2 i}`, `mean`, `log_std`, `decoder.model.{2 i}`: the reference module's `state_dict()` order."""
+        flat, L, enc = self._vector(flat), self.latent_dim, self.encoder
+        trunk = enc.named_layers(ref_layer_keys(enc.n_layers - 1, "seq"), "encoder.model.", flat[:self.n_enc])
+        W, b = enc.layer_views(flat[:self.n_enc])[-1]
+        heads = [("mean.weight", W[:L]), ("mean.bias", b[:L]), ("log_std.weight", W[L:]), ("log_std.bias", b[L:])]
+        return trunk + heads + self.decoder.named_layers(ref_layer_keys(self.decoder.n_layers, "seq"), "decoder.model.",
+                                                         flat[self.n_enc:])
+
+    def forward(self, obs: torch.Tensor, act: torch.Tensor, eps: torch.Tensor, save: bool = True):
+        """obs [B, D], act [B, Ad], eps [B, L] standard normals (`torch.randn_like(std)`, continuous.py:493)
+        -> (recon [B, Ad], mean [B, L], std [B, L]); with `save` the decoder's raw output, the head's and eps stay for
+        `backward`."""
+        dev = self.flat.device
+        obs = obs.to(dev, torch.float32).reshape(-1, self.obs_dim).contiguous()
+        act = act.to(dev, torch.float32).reshape(obs.shape[0], self.act_dim).contiguous()
+        eps = eps.to(dev, torch.float32).reshape(obs.shape[0], self.latent_dim).contiguous()
+        head, raw, std = self.forward_rows(ops.maddpg_joint_rows([obs], [act]), obs, eps, save=save)
+        return ops.cac_det_action(raw, self.max_action), head[:, :self.latent_dim], std
+
+    def forward_rows(self, x: torch.Tensor, obs: torch.Tensor, eps: torch.Tensor, save: bool = True):
+        """`forward` for a caller that has the rows x = [obs | act] already and needs no `recon` (the learner: `loss_head`
+        forms it again from the raw output) -> (head [B, 2 L], the decoder's raw output [B, Ad], std [B, L])."""
+        head = FlatMLP.forward(self.encoder, x, save=save)
+        x_dec, std = ops.bcq_latent(head, eps, obs)
+        raw = FlatMLP.forward(self.decoder, x_dec, save=save)
+        if save:
+            self._saved = (head, eps, raw)
+        return head, raw, std
+
+    def decode_rows(self, x: torch.Tensor) -> torch.Tensor:
+        """The decoder on rows [obs | z] that are already assembled (`ops.bcq_decode_rows`, `ops.bcq_latent`) -> its raw
+        output [n, Ad]; the action is `max_action * tanh(raw)` (`ops.bcq_action_rows`).  Nothing is kept."""
+        return FlatMLP.forward(self.decoder, x, save=False)
+
+    def loss_head(self, act: torch.Tensor) -> dict:
+        """`ops.bcq_vae_head` on the last `forward(save=True)`: dict(d_raw, partial)."""
+        head, _, raw = self._saved_forward("loss_head")
+        return ops.bcq_vae_head(raw, act, head, self.max_action)
+
+    def backward(self, d_raw: torch.Tensor, n_split: int = 0, slabs: torch.Tensor | None = None) -> torch.Tensor:
+        """Gradient slabs [n_split, n_param] of vae_loss for the last `forward(save=True)`, d_raw = `loss_head`'s: the
+        decoder's slabs and its gradient to the latent columns, `ops.bcq_latent_grad` (the KL term enters there), the
+        encoder's slabs."""
+        head, eps, raw = self._saved_forward()
+        P = self.flat.numel()
+        n_split, slabs = self._slabs(raw.shape[0], n_split, slabs)
+        d_raw = d_raw.reshape(raw.shape).contiguous()
+        self.decoder.backward(d_raw, n_split, slabs=slabs[:, self.n_enc:], slab_stride=P)
+        dz = self.decoder.input_grad(d_raw, self.obs_dim, self.latent_dim)
+        self.encoder.backward(ops.bcq_latent_grad(dz, head, eps), n_split, slabs=slabs, slab_stride=P)
+        return slabs
+
+
 class _GroupedLayers:
     """`EnsembleLinear`'s layout (common.py:522-554) of `E` members of the chain `dims` on `net`'s flat vector from `offset`
     on: per layer weight [E, in, out], then bias [E, 1, out] -- what csrc/ensemble.hip runs as one grouped launch per layer."""
