@@ -1787,6 +1787,70 @@ int tsm_vrb_gather_stacked(const void *state, int64_t buffer_num, int64_t sub_si
                            int64_t row_bytes, int64_t lane_off, int64_t lane_bytes, const int64_t *index, int64_t n,
                            int32_t stack_num, void *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * NPG and TRPO  (tianshou/algorithm/modelfree/npg.py, trpo.py; csrc/fisher.hip)
+ * The Fisher-vector product of a categorical actor MLP without autograd.  Where the reference evaluates it (npg.py:162-166:
+ * old_dist is the same forward as dist) the KL's gradient w.r.t. the logits is zero, so the Hessian of mean KL(old || new)
+ * w.r.t. the parameters is the Gauss-Newton form  F v = (1 / B) J^T M (J v),  M = diag(p) - p p^T per row, p = softmax(logits).
+ * tsm_mlp_tangent_forward replaces  the inner derivative of `(flat_kl_grad * v).sum()` (npg.py:195-200): J v, a forward-mode
+ *           pass.  v f32 in the layout of params (Vw_l, vb_l at the offsets of W_l, b_l); acts as tsm_mlp_forward left them;
+ *           t_acts (tsm_mlp_act_elems floats) receives T_1 .. T_L, the last block being J v [B][dims[L]]:
+ *             T_{l+1} = act'(H_{l+1}) * (T_l W_l^T + H_l Vw_l^T + vb_l),  T_0 = 0, H_0 = x, no derivative on the last layer,
+ *           act' from the saved output (relu: h > 0; tanh: 1 - h^2).  One launch per layer: both products are ONE f32-MFMA
+ *           accumulation over the concatenated k range [T_l | H_l] x [W_l | Vw_l], in that order.
+ * tsm_fisher_head replaces  M (J v) / B, the middle factor of the same second derivative, and p.dot(z) of npg.py:216 up to the
+ *           damping term.  logits, t f32 [B][n_act] (n_act in [1, 64]) -> u [B][n_act] = p (t - <p, t>) / B, the d_out of
+ *           tsm_mlp_backward; partial f64 [ceil(B / TSM_FISHER_ROWS_PER_BLOCK)]: per workgroup the sum over its rows of
+ *           (sum_k p_k t_k^2 - <p, t>^2) / B, which add up to v^T F v.  Probabilities and sums in float64 from the float32 logits.
+ * tsm_categorical_kl_surrogate replaces  kl_divergence(old_dist, new_dist).mean() (npg.py:164,177; trpo.py:177) and the actor
+ *           loss with its backward to the logits: kind 0  -mean(exp(logp_new - logp_old) adv) (trpo.py:136-138, 172-176),
+ *           kind 1  -mean(logp_new adv) (npg.py:153-155).  act i32 [B], logp_old, adv f32 [B].
+ *           partial f64 [2 * ceil(B / TSM_FISHER_ROWS_PER_BLOCK)] = per workgroup {sum KL(old || new), sum of the loss terms}; tsm_qmix_finalize gives the
+ *           two means.  d_logits (nullable) f32 [B][n_act] = d loss / d logits_new.  run_if (nullable device i32): a no-op at 0.
+ * The conjugate gradients of npg.py:202-224 on flat f32 vectors of n floats, without a host read: every workgroup of a
+ * launch owns TSM_CG_CHUNK consecutive elements, leaves the float64 sum of its chunk as one partial and re-sums the
+ * partials it reads in one fixed order, so all workgroups form the same scalars and two runs give the same bits.
+ * ceil(n / TSM_CG_CHUNK) partials per array.  done: device i32, set once new_rdotr < residual_tol; from then on x, r, p and
+ * every partial stay as they are (the `break` of npg.py:220-221).  rr_prev / rr_next: two partial arrays the caller swaps
+ * from one iteration to the next (rdotr and new_rdotr).
+ * tsm_cg_direction: init != 0: r = p = sum of the g_slabs (slab order), x = 0, rr_next and pp from them, done = 0.
+ *           init == 0: beta = new_rdotr / rdotr from rr_next / rr_prev; sets done, or p = r + beta p with partials pp of p.p.
+ * tsm_cg_update: alpha = rdotr / (pFp + damping p.p) with pFp from tsm_fisher_head's partials (n_head of them) -- p.dot(z)
+ *           in exact arithmetic; z = sum of the z_slabs (tsm_mlp_backward's, slab order) + damping p; x += alpha p;
+ *           r -= alpha z; partials rr_next of r.r.
+ * tsm_flat_axpy_dev: params = base + host_scale * scale_dev[0] * d (scale_dev nullable f64: 1) unless run_if (nullable) is 0:
+ *           the NPG step (npg.py:174) and the trials of TRPO's line search (trpo.py:168).
+ * TRPO's line search on the device (trpo.py:152-191).  ls f64 [TSM_TRPO_LS_ELEMS] = {step_size, loss, kl, reported step
+ *           size, backtracks, failed}; run i32: trials run while it is 1.
+ * tsm_trpo_step_size: ls[0] = sqrt(2 max_kl / (xFx + damping x.x)) with xFx from tsm_fisher_head's partials of a pass on x;
+ *           ls[1] = the actor loss from tsm_categorical_kl_surrogate's partials at the old parameters; run = 1.  One workgroup.
+ * tsm_trpo_accept: trial `trial` of max_backtracks: kl, new_loss from the trial's partials; accepted on kl < max_kl and
+ *           new_loss < loss (run = 0); else ls[0] *= backtrack_coeff, or on the last trial run = 0, failed, reported
+ *           step size 0 (the parameters stay at the last trial's, trpo.py:186).  out f32 [4] (HBM or mapped pinned memory)
+ *           = {actor_loss, kl, step_size, backtracks or -1 when the search failed}.  One thread.
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_FISHER_ROWS_PER_BLOCK 128
+#define TSM_CG_CHUNK 1024
+#define TSM_TRPO_LS_ELEMS 6
+int tsm_mlp_tangent_forward(const tsm_mlp_desc *desc, const float *params, const float *v, const float *x, int64_t B,
+                            const float *acts, float *t_acts, void *stream);
+int tsm_fisher_head(const float *logits, const float *t, int64_t B, int32_t n_act, float *u, double *partial, void *stream);
+int tsm_categorical_kl_surrogate(const float *logits_old, const float *logits_new, const int32_t *act, const float *logp_old,
+                                 const float *adv, int64_t B, int32_t n_act, int32_t kind, float *d_logits, double *partial,
+                                 const int32_t *run_if, void *stream);
+int tsm_cg_direction(int32_t init, const float *g_slabs, int32_t n_slab, int64_t slab_stride, int64_t n, float *x, float *r,
+                     float *p, const double *rr_prev, double *rr_next, double *pp, double residual_tol, int32_t *done,
+                     void *stream);
+int tsm_cg_update(const float *z_slabs, int32_t n_slab, int64_t slab_stride, int64_t n, float *x, float *r, const float *p,
+                  const double *head_partial, int32_t n_head, const double *pp, const double *rr_prev, double *rr_next,
+                  double damping, const int32_t *done, void *stream);
+int tsm_flat_axpy_dev(const float *base, const float *d, int64_t n, double host_scale, const double *scale_dev,
+                      const int32_t *run_if, float *params, void *stream);
+int tsm_trpo_step_size(const double *head_partial, int32_t n_head, const float *x, int64_t n, const double *loss_partial,
+                       int32_t n_loss, int64_t B, double damping, double max_kl, double *ls, int32_t *run, void *stream);
+int tsm_trpo_accept(const double *trial_partial, int32_t n_blocks, int64_t B, int32_t trial, int32_t max_backtracks,
+                    double max_kl, double backtrack_coeff, double *ls, int32_t *run, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

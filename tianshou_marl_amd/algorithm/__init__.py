@@ -16,6 +16,8 @@ from .bdqn import BDQN, BDQNPolicy
 from .pg import A2C, Reinforce
 from .ppo import PPO, policy_within_training_step
 from .ppo_generic import GenericPPO
+from .npg import NPG, NPGTrainingStats
+from .trpo import TRPO, TRPOTrainingStats
 from .icm import ICMOffPolicyWrapper, ICMOnPolicyWrapper, ICMTrainingStats
 from .gail import GAIL, GailTrainingStats
 
@@ -26,4 +28,4 @@ __all__ = ["PPO", "A2C", "Reinforce", "GenericPPO", "DQN", "DiscreteQLearningPol
            "SACTrainingStats", "GaussianNoise", "REDQ", "REDQPolicy", "REDQTrainingStats", "BDQN", "BDQNPolicy",
            "policy_within_training_step", "ICMOnPolicyWrapper", "ICMOffPolicyWrapper", "ICMTrainingStats",
            "GAIL", "GailTrainingStats", "CQL", "CQLTrainingStats", "TD3BC", "BCQ", "BCQPolicy",
-           "BCQTrainingStats"]
+           "BCQTrainingStats", "NPG", "NPGTrainingStats", "TRPO", "TRPOTrainingStats"]

@@ -102,8 +102,7 @@ class PPO(nn.Module):
         self._lr_dev = torch.tensor([float(lr)], dtype=torch.float64, device=net.flat.device)
         # Adam's moments, step count, work buffer and hyper-parameters; the gradient steps below launch the optimizer
         # kernels on them themselves.  Checkpoints list the moments per reference parameter, for either net
-        self.optim = FlatAdam(net, float(lr), betas, adam_eps, weight_decay, max_grad_norm,
-                              views=lambda flat: [v for _, v in net.reference_named_views(flat)])
+        self.optim = self._make_optim(net, float(lr), betas, adam_eps, weight_decay, max_grad_norm)
         self.lr_schedulers: list = []
         if sched_factory is not None:  # Algorithm._create_optimizer (algorithm_base.py:506-519)
             self.lr_schedulers.append(sched_factory.create_scheduler(self))
@@ -134,6 +133,11 @@ class PPO(nn.Module):
         # N>1: capture the per-step gradient all-reduce (RCCL) inside the update hipGraph (TSM_GRAPH_COLLECTIVES=0: eager)
         self.graph_collectives = os.environ.get("TSM_GRAPH_COLLECTIVES", "1") != "0"
         self.param_version = 0  # bumped whenever the parameters change (stored rollout outputs become stale)
+
+    def _make_optim(self, net, lr: float, betas, adam_eps: float, weight_decay: float, max_grad_norm) -> FlatAdam:
+        """The one optimizer over actor + critic (ActorCritic.parameters()); a subclass whose optimizer covers less builds its own."""
+        return FlatAdam(net, lr, betas, adam_eps, weight_decay, max_grad_norm,
+                        views=lambda flat: [v for _, v in net.reference_named_views(flat)])
 
     # the reference collector accepts an Algorithm and uses `.policy` (collector.py:358)
     @property

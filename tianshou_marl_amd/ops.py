@@ -3156,6 +3156,170 @@ def mlp_input_grad(desc, params, x, acts, d_out, col0: int, n_col: int, out=None
 
 
 # --------------------------------------------------------------------------------------------
+# NPG / TRPO: Fisher-vector products and conjugate gradients (npg.py:195-224, trpo.py:152-191; csrc/fisher.hip)
+# --------------------------------------------------------------------------------------------
+def mlp_tangent_forward(desc, params, v, x, acts, t_acts=None):
+    """J v of the net at x (include/tsmarl.h: tsm_mlp_tangent_forward): `v` a direction in the layout of `params`, `acts` what
+    mlp_forward left for x -> (J v [B, dims[-1]], a view of the last block of t_acts; the t_acts buffer)."""
+    params, x, B, n, n_param = _mlp_args("mlp_tangent_forward", desc, params, x, acts)
+    _dev_only("mlp_tangent_forward", v)
+    v = _chk(v, torch.float32, "v")
+    if v.numel() < n_param:
+        raise ValueError(f"mlp_tangent_forward: v must hold the net's {n_param} floats, got {v.numel()}")
+    if acts is None:
+        raise ValueError("mlp_tangent_forward: acts, the activations of mlp_forward on x, are required")
+    t_acts = _out("mlp_tangent_forward", t_acts, (n,), torch.float32, x.device, "t_acts", "numel")
+    call("tsm_mlp_tangent_forward", C.byref(desc), ptr(params), ptr(v), ptr(x), B, ptr(acts), ptr(t_acts), stream_ptr())
+    O = desc.dims[desc.n_layers]
+    return t_acts[n - B * O:].view(B, O), t_acts
+
+
+def _policy_rows(name: str, first, others: dict) -> tuple:
+    """[B, A] f32 device tensors of one shape (`first` decides it) -> (B, A, the contiguous tensors in order)."""
+    _dev_only(name, first, *others.values())
+    if first.dim() != 2 or first.shape[0] < 1:
+        raise ValueError(f"{name}: logits must be [B, n_act] with B >= 1, got {tuple(first.shape)}")
+    for nm, t in others.items():
+        if tuple(t.shape) != tuple(first.shape):
+            raise ValueError(f"{name}: {nm} must be {list(first.shape)}, got {list(t.shape)}")
+    return first.shape[0], first.shape[1], [_chk(t, torch.float32, nm) for nm, t in (("logits", first), *others.items())]
+
+
+def fisher_head_blocks(B: int) -> int:
+    """Workgroups, hence partial sums, of the row-wise heads of csrc/fisher.hip on B rows."""
+    return -(-int(B) // _abi.FISHER_ROWS_PER_BLOCK)
+
+
+def fisher_head(logits, t, u=None, partial=None):
+    """The middle factor of F v = J^T M (J v) / B for Categorical(logits): -> (u [B, A] = p (t - <p, t>) / B, the d_out of
+    mlp_backward; partial f64 [fisher_head_blocks(B)], which add up to v^T F v)."""
+    B, A, (logits, t) = _policy_rows("fisher_head", logits, {"t": t})
+    u = _out("fisher_head", u, (B, A), torch.float32, logits.device, "u")
+    partial = _out("fisher_head", partial, (fisher_head_blocks(B),), torch.float64, logits.device, "partial", "numel")
+    call("tsm_fisher_head", ptr(logits), ptr(t), B, A, ptr(u), ptr(partial), stream_ptr())
+    return u, partial
+
+
+def categorical_kl_surrogate(logits_old, logits_new, act, logp_old, adv, kind: str = "ratio", want_grad: bool = False,
+                             partial=None, run_if=None):
+    """Per-workgroup f64 pairs {sum KL(old || new), sum of the actor-loss terms} -- kind "ratio": -exp(logp_new - logp_old) adv
+    (TRPO), "logp": -logp_new adv (NPG); `qmix_finalize(partial, B, out)` gives the two means -- and, with want_grad, d (mean
+    loss) / d logits_new.  run_if (device i32[1]): a no-op when it is zero.  -> (partial, d_logits or None)."""
+    if kind not in ("ratio", "logp"):
+        raise ValueError(f"categorical_kl_surrogate: kind must be 'ratio' or 'logp', got {kind!r}")
+    B, A, (logits_old, logits_new) = _policy_rows("categorical_kl_surrogate", logits_old, {"logits_new": logits_new})
+    rows = _head_args("categorical_kl_surrogate", B, (), (("act", act, torch.int32), ("logp_old", logp_old, torch.float32),
+                                                          ("adv", adv, torch.float32), ))
+    _dev_only("categorical_kl_surrogate", *rows, run_if)
+    dev = logits_old.device
+    partial = _out("categorical_kl_surrogate", partial, (2 * fisher_head_blocks(B),), torch.float64, dev, "partial", "numel")
+    d_logits = torch.empty(B, A, dtype=torch.float32, device=dev) if want_grad else None
+    call("tsm_categorical_kl_surrogate", ptr(logits_old), ptr(logits_new), *map(ptr, rows), B, A, 0 if kind == "ratio" else 1,
+         ptr(d_logits), ptr(partial), ptr(None if run_if is None else _chk(run_if, torch.int32, "run_if")), stream_ptr())
+    return partial, d_logits
+
+
+def fisher_vector_product(net, v, n_split: int = 0, slabs=None, ws: dict | None = None):
+    """F v of the actor `net` (a FlatMLP with a categorical head) at the rows of its last `forward(save=True)`, as gradient
+    slabs [n_split, n_param] that sum to it: tangent forward, Fisher head, mlp_backward.  -> (slabs, partial: the head's f64
+    partials of v^T F v).  The damping term is the caller's (tsm_cg_update adds it).  ws: a dict that keeps the buffers."""
+    x, acts = net._saved_forward("fisher_vector_product")
+    B, O = x.shape[0], net.dims[-1]
+    ws = {} if ws is None else ws
+    jv, ws["t_acts"] = mlp_tangent_forward(net.desc, net.flat.data, v, x, acts, ws.get("t_acts"))
+    ws["u"], ws["partial"] = fisher_head(acts[acts.numel() - B * O:].view(B, O), jv, ws.get("u"), ws.get("partial"))
+    return mlp_backward(net.desc, net.flat.data, x, acts, ws["u"], n_split, slabs=slabs), ws["partial"]
+
+
+def cg_chunks(n: int) -> int:
+    """Partials per dot product of the CG kernels on a vector of n floats."""
+    return -(-int(n) // _abi.CG_CHUNK)
+
+
+def cg_state(n: int, device) -> dict:
+    """The device state of one conjugate-gradient solve on vectors of n floats: x, r, p; the partial arrays of r.r (two,
+    swapped from one iteration to the next) and p.p; the flag `done`."""
+    nb = cg_chunks(n)
+    if nb < 1:
+        raise ValueError(f"cg_state: n = {n} must be >= 1")
+    f = lambda: torch.empty(n, dtype=torch.float32, device=device)  # noqa: E731
+    d = lambda: torch.zeros(nb, dtype=torch.float64, device=device)  # noqa: E731
+    return dict(n=n, x=f(), r=f(), p=f(), rr=[d(), d()], pp=d(), done=torch.zeros(1, dtype=torch.int32, device=device), it=0)
+
+
+def _cg_slabs(name: str, slabs, n: int) -> tuple:
+    _dev_only(name, slabs)
+    if slabs.dtype != torch.float32 or slabs.dim() != 2 or slabs.shape[1] < n or slabs.stride(1) != 1 or slabs.shape[0] < 1:
+        raise ValueError(f"{name}: slabs must be f32 [n_slab >= 1, >= {n}], contiguous along the parameters")
+    return slabs.shape[0], slabs.stride(0)
+
+
+def cg_init(st: dict, g_slabs) -> None:
+    """x = 0, r = p = the sum of g_slabs (npg.py:209-213)."""
+    n_slab, stride = _cg_slabs("cg_init", g_slabs, st["n"])
+    st["it"] = 0
+    call("tsm_cg_direction", 1, g_slabs.data_ptr(), n_slab, stride, st["n"], ptr(st["x"]), ptr(st["r"]), ptr(st["p"]), None,
+         ptr(st["rr"][0]), ptr(st["pp"]), 0.0, ptr(st["done"]), stream_ptr())
+
+
+def cg_update(st: dict, z_slabs, head_partial, damping: float = 0.1) -> None:
+    """npg.py:215-219 with z = sum of z_slabs + damping p and p.z = sum(head_partial) + damping p.p: x, r and the partials of
+    the new r.r."""
+    n_slab, stride = _cg_slabs("cg_update", z_slabs, st["n"])
+    head_partial = _chk(head_partial, torch.float64, "head_partial")
+    prev, nxt = st["rr"][st["it"] & 1], st["rr"][(st["it"] + 1) & 1]
+    call("tsm_cg_update", z_slabs.data_ptr(), n_slab, stride, st["n"], ptr(st["x"]), ptr(st["r"]), ptr(st["p"]),
+         ptr(head_partial), head_partial.numel(), ptr(st["pp"]), ptr(prev), ptr(nxt), float(damping), ptr(st["done"]),
+         stream_ptr())
+
+
+def cg_direction(st: dict, residual_tol: float = 1e-10) -> None:
+    """npg.py:220-223: sets `done` once the new r.r < residual_tol, else p = r + beta p; the iteration count advances."""
+    prev, nxt = st["rr"][st["it"] & 1], st["rr"][(st["it"] + 1) & 1]
+    call("tsm_cg_direction", 0, None, 1, 0, st["n"], ptr(st["x"]), ptr(st["r"]), ptr(st["p"]), ptr(prev), ptr(nxt),
+         ptr(st["pp"]), float(residual_tol), ptr(st["done"]), stream_ptr())
+    st["it"] += 1
+
+
+def flat_axpy_dev(base, d, host_scale: float = 1.0, scale_dev=None, run_if=None, out=None):
+    """out = base + host_scale * scale_dev[0] * d on flat f32 vectors (scale_dev: device f64, None = 1), unless the device
+    flag run_if (i32) is zero."""
+    _dev_only("flat_axpy_dev", base, d, scale_dev, run_if)
+    base, d = _chk(base, torch.float32, "base"), _chk(d, torch.float32, "d")
+    if base.dim() != 1 or base.shape != d.shape:
+        raise ValueError(f"flat_axpy_dev: base and d must be flat vectors of one length, got {list(base.shape)} and {list(d.shape)}")
+    out = _out("flat_axpy_dev", out, base.shape, torch.float32, base.device)
+    call("tsm_flat_axpy_dev", ptr(base), ptr(d), base.numel(), float(host_scale),
+         ptr(None if scale_dev is None else _chk(scale_dev, torch.float64, "scale_dev")),
+         ptr(None if run_if is None else _chk(run_if, torch.int32, "run_if")), ptr(out), stream_ptr())
+    return out
+
+
+def trpo_step_size(head_partial, x, loss_partial, B: int, damping: float, max_kl: float, ls=None, run=None):
+    """trpo.py:153-160 on the device: ls[0] = sqrt(2 max_kl / (x F x + damping x.x)) with x F x = sum(head_partial), ls[1] = the
+    actor loss (loss_partial: categorical_kl_surrogate's at the old parameters), run = 1.  -> (ls f64 [TRPO_LS_ELEMS], run)."""
+    _dev_only("trpo_step_size", head_partial, x, loss_partial)
+    head_partial, loss_partial = _chk(head_partial, torch.float64, "head_partial"), _chk(loss_partial, torch.float64, "loss_partial")
+    x = _chk(x, torch.float32, "x")
+    ls = _out("trpo_step_size", ls, (_abi.TRPO_LS_ELEMS,), torch.float64, x.device, "ls")
+    run = _out("trpo_step_size", run, (1,), torch.int32, x.device, "run")
+    call("tsm_trpo_step_size", ptr(head_partial), head_partial.numel(), ptr(x), x.numel(), ptr(loss_partial),
+         loss_partial.numel() // 2, int(B), float(damping), float(max_kl), ptr(ls), ptr(run), stream_ptr())
+    return ls, run
+
+
+def trpo_accept(trial_partial, B: int, trial: int, max_backtracks: int, max_kl: float, backtrack_coeff: float, ls, run, out):
+    """One trial of trpo.py:167-191 decided on the device (include/tsmarl.h: tsm_trpo_accept); the last trial leaves
+    out f32[4] = {actor_loss, kl, step_size, backtracks or -1} (device or pinned host memory)."""
+    _dev_only("trpo_accept", trial_partial, ls, run)
+    trial_partial = _chk(trial_partial, torch.float64, "trial_partial")
+    call("tsm_trpo_accept", ptr(trial_partial), trial_partial.numel() // 2, int(B), int(trial), int(max_backtracks), float(max_kl),
+         float(backtrack_coeff), ptr(_chk(ls, torch.float64, "ls")), ptr(_chk(run, torch.int32, "run")),
+         _out_or_pinned("trpo_accept", out, 4), stream_ptr())
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # grouped ensemble MLP: E nets of one shape, one launch per layer and role (utils/net/common.py:522-554; csrc/ensemble.hip)
 # --------------------------------------------------------------------------------------------
 def ens_mlp_param_count(desc, E: int) -> int:
