@@ -1851,6 +1851,56 @@ int tsm_trpo_step_size(const double *head_partial, int32_t n_head, const float *
 int tsm_trpo_accept(const double *trial_partial, int32_t n_blocks, int64_t B, int32_t trial, int32_t max_backtracks,
                     double max_kl, double backtrack_coeff, double *ls, int32_t *run, float *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Gaussian policies for Box actions on the on-policy learners  (utils/net/continuous.py:238-247, reinforce.py:183-192,
+ * ppo.py:157-211, algorithm_base.py:255-288; csrc/gauss.hip)
+ * Independent(Normal(mu, sigma), 1) over the raw outputs of a ContinuousActorProbabilistic, the action NOT squashed.
+ * Rows are mu_raw[b * ld_mu + k], sigma_raw[b * ld_sigma + k] (tsm_sac_action's addressing; ld_sigma = 0: one
+ * state-independent row, `sigma_param`).  mu = max_action tanh(mu_raw) (unbounded != 0: mu_raw); log sigma =
+ * clamp(sigma_raw, -20, 2) with a conditioned sigma and sigma_raw UNCLAMPED for the state-independent row;
+ * logp = sum_k Normal(mu, sigma).log_prob(a_k);  entropy = sum_k (1/2 + log sqrt(2 pi) + log sigma_k).  float64 from the
+ * float32 inputs, rounded once on store.  One group of g lanes per row, g = the power of two >= act_dim in [8, 64], a
+ * workgroup per TSM_GAUSS_ROWS_PER_BLOCK rows; sums over k are the xor butterfly of the group, a workgroup's sums its groups
+ * in order: no atomics, two runs give the same bits.  act_dim in [1, TSM_CAC_MAX_ACT_DIM]; no entry reads the host.
+ * tsm_gauss_check: the bound on act_dim, TSM_ERR_INVALID naming it.  Needs no device.
+ * tsm_gauss_sample: act_out f32 [B][act_dim] = mu + sigma z, the raw sample a buffer stores, and logp_out f32 [B]
+ *   (nullable) of that stored number.  z is drawn inside the launch: element e = b * act_dim + k takes word e % 4 of the
+ *   Philox block (seed ^ a key of its own, offset + *offset_dev, third counter word e / 4), Box-Muller paired as
+ *   tsm_cac_normal.  deterministic != 0: the mode mu, nothing is drawn.  env_act_out (nullable) f32 [B][act_dim] =
+ *   map_action of the sample: bound_method 0 none, 1 clip to [-1, 1], 2 tanh; then low + (high - low) (x + 1) / 2 with
+ *   low, high f32 [act_dim] (nullable together: no scaling).
+ * tsm_gauss_logp_entropy: logp_out, entropy_out (nullable) f32 [B] of the actions act[perm[b]] (perm nullable: act[b]) under
+ *   the rows b of mu_raw / sigma_raw.  On a sample's act_out it gives the sample's logp_out bit for bit.
+ * tsm_gauss_ppo_head replaces  the policy terms of ppo.py:182-196, 210-211 (loss_kind 0) and a2c.py:260-270 (loss_kind 1)
+ *   and their backward.  mu_raw, sigma_raw: the M minibatch-contiguous rows; act [.][act_dim], logp_old, adv: full-batch
+ *   arrays read at perm[i] (perm nullable: first_row + i); adv_stats {mean, std} (nullable without adv_norm).  cfg: eps_clip,
+ *   dual_clip, ent_coef, adv_norm, loss_kind 0 | 1.  d_mu_out[i * ld_d + k] = d loss / d mu_raw; with a conditioned sigma
+ *   d_sigma_out[i * ld_d + k] = d loss / d sigma_raw (zero past the clamp), col_partial_out unused; with ld_sigma = 0
+ *   d_sigma_out is unused and col_partial_out f64 [n_blocks][act_dim] receives each workgroup's sum over its rows of
+ *   d loss / d sigma_param.  loss = -mean(obj) - ent_coef mean(entropy): the gradients carry 1 / M and the coefficients.
+ *   partial_out f64 [n_blocks][4] = {sum obj, 0, sum entropy, 0}, tsm_ppo_finalize_many's layout (the value term is
+ *   tsm_ppo_loss_fwd_bwd's with loss_kind 2).  n_blocks = ceil(M / TSM_GAUSS_ROWS_PER_BLOCK).
+ * tsm_gauss_sigma_fold: slabs_out[k] = sum over the n_blocks rows of col_partial in block order;
+ *   slabs_out[s * slab_stride + k] = 0 for the slabs 1 <= s < n_slab: the sigma_param columns of the actor's gradient slabs
+ *   (tsm_cac_col_sum's contract, without the [M][act_dim] array).
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_GAUSS_ROWS_PER_BLOCK 64
+int tsm_gauss_check(int32_t act_dim);
+int tsm_gauss_sample(const float *mu_raw, int64_t ld_mu, const float *sigma_raw, int64_t ld_sigma, int64_t B, int32_t act_dim,
+                     double max_action, int32_t unbounded, uint64_t seed, uint64_t offset, const uint64_t *offset_dev,
+                     int32_t deterministic, int32_t bound_method, const float *low, const float *high, float *act_out,
+                     float *logp_out, float *env_act_out, void *stream);
+int tsm_gauss_logp_entropy(const float *mu_raw, int64_t ld_mu, const float *sigma_raw, int64_t ld_sigma, const float *act,
+                           const int64_t *perm, int64_t B, int32_t act_dim, double max_action, int32_t unbounded,
+                           float *logp_out, float *entropy_out, void *stream);
+int tsm_gauss_ppo_head(const float *mu_raw, int64_t ld_mu, const float *sigma_raw, int64_t ld_sigma, const float *act,
+                       const float *logp_old, const float *adv, const int64_t *perm, int64_t first_row, int64_t M,
+                       int32_t act_dim, const float *adv_stats, const tsm_ppo_cfg *cfg_host, double max_action,
+                       int32_t unbounded, float *d_mu_out, float *d_sigma_out, int64_t ld_d, double *partial_out,
+                       double *col_partial_out, void *stream);
+int tsm_gauss_sigma_fold(const double *col_partial, int32_t n_blocks, int32_t act_dim, int32_t n_slab, float *slabs_out,
+                         int64_t slab_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,7 @@ class NPG(GenericPPO):
     _fixed = ("eps_clip", "dual_clip", "value_clip", "recompute_advantage", "vf_coef", "ent_coef", "max_grad_norm", "use_graph")
     _stats_cls, _stat_names = NPGTrainingStats, ("actor_loss", "vf_loss", "kl")
     _loss_kind = "logp"   # the actor loss of `ops.categorical_kl_surrogate`: -mean(logp adv)
+    _gaussian_ok = False  # the Fisher head and the KL surrogate are categorical: a GaussianActorCritic is refused by name
 
     def __init__(self, *, policy=None, critic=None, optim=None, optim_critic_iters: int = 5, trust_region_size: float = 0.5,
                  advantage_normalization: bool = True, gae_lambda: float = 0.95, max_batchsize: int = 256, gamma: float = 0.99,

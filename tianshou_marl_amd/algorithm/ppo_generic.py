@@ -28,16 +28,20 @@ from ..data.batch import Batch, split_bounds
 from ..data.buffer import DeviceVectorReplayBuffer
 from ..data.stats import ResultRing, lazy_training_stats, pinned_slot, training_stats_from_steps
 from ..utils.learner import act_result, sample_counter
-from ..utils.net import FlatMLP, MLPActorCritic
+from ..utils.net import FlatMLP, GaussianActorCritic, MLPActorCritic
 from ..utils.tensor import to_tensor
 from .ppo import PPO, ref_order_rows
 
 
 class GenericPPO(PPO):
+    _gaussian_ok = True   # a subclass whose update is categorical-only (NPG, TRPO) clears it
 
-    def __init__(self, *, net: MLPActorCritic | None = None, critic_input: Literal["local", "global"] | None = None,
+    def __init__(self, *, net: MLPActorCritic | GaussianActorCritic | None = None,
+                 critic_input: Literal["local", "global"] | None = None,
                  n_agent: int | None = None, graph: bool = True, fused_actor: bool = True,
-                 reuse_rollout_outputs: bool = True, shift_next_values: bool = True, **kwargs) -> None:
+                 reuse_rollout_outputs: bool = True, shift_next_values: bool = True, action_scaling: bool = False,
+                 action_bound_method: Literal["clip", "tanh"] | None = "clip", action_space=None, low=None, high=None,
+                 **kwargs) -> None:
         if net is None and kwargs.get("policy") is not None:  # reference-style construction (see PPO.__new__)
             from ..utils.net import net_from_reference_modules
 
@@ -48,8 +52,12 @@ class GenericPPO(PPO):
             kwargs["deterministic_eval"] = bool(getattr(kwargs["policy"], "deterministic_eval",
                                                         kwargs.get("deterministic_eval", False)))
             kwargs["dispatch"] = kwargs.get("dispatch") or "pooled"
-        if not isinstance(net, MLPActorCritic):
-            raise TypeError("GenericPPO needs an MLPActorCritic (use PPO for DiscreteActorCritic)")
+        gaussian = isinstance(net, GaussianActorCritic)
+        if gaussian and not self._gaussian_ok:
+            raise NotImplementedError(f"{type(self).__name__} on a GaussianActorCritic: its Fisher head and KL surrogate are "
+                                      "categorical (csrc/fisher.hip); Gaussian policies train with GenericPPO")
+        if not isinstance(net, MLPActorCritic) and not gaussian:
+            raise TypeError("GenericPPO needs an MLPActorCritic or a GaussianActorCritic (use PPO for DiscreteActorCritic)")
         if critic_input is None:  # a critic that is wider than the actor's observation sees the env's joint observation
             critic_input = "local" if net.critic_obs_dim == net.obs_dim else "global"
         if n_agent is None:
@@ -57,6 +65,9 @@ class GenericPPO(PPO):
         kwargs["use_graph"] = False  # the base class's graph path is the fused-kernel one
         super().__init__(net=net, **kwargs)
         self.graph = bool(graph)  # capture this class's own update sequence into one hipGraph
+        self.gaussian = gaussian
+        if gaussian:
+            self._init_gaussian(action_scaling, action_bound_method, action_space, low, high)
         self.critic_input, self.n_agent = critic_input, int(n_agent)
         want = net.obs_dim * (self.n_agent if critic_input == "global" else 1)
         if net.critic_obs_dim != want:
@@ -67,7 +78,7 @@ class GenericPPO(PPO):
         # value term alone (the actor's terms come from the one-launch actor step, csrc/ppo_rows.hip)
         self._cfg_value = {vg: ops.make_ppo_cfg(self.eps_clip, self.dual_clip, self.value_clip, False, self.vf_coef,
                                                 self.ent_coef, loss_kind=2, value_group=vg) for vg in (1, self.n_agent)}
-        self.fused_actor = bool(fused_actor) and ops.ppo_actor_rows_supported(net.obs_dim, net.actor.dims[1:-1], net.n_act,
+        self.fused_actor = bool(fused_actor) and not gaussian and ops.ppo_actor_rows_supported(net.obs_dim, net.actor.dims[1:-1], net.n_act,
                                                                               net.actor.act)
         # ... and the critic in its own single launch when it is in_dim -> 128 -> 128 -> 1 (row minibatches or a local
         # critic: the samples of a row are adjacent lanes)
@@ -98,6 +109,123 @@ class GenericPPO(PPO):
         self.shift_next_values = bool(shift_next_values)
         self._ctor.update(fused_actor=fused_actor, reuse_rollout_outputs=reuse_rollout_outputs,
                           shift_next_values=shift_next_values)
+
+    # ---- Gaussian policies for Box actions (GaussianActorCritic; csrc/gauss.hip) -------------------------------------
+    def _init_gaussian(self, action_scaling: bool, action_bound_method, action_space, low, high) -> None:
+        """The reference's `action_scaling` / `action_bound_method` (algorithm_base.py:166-224) and the bounds they map to:
+        `action_space` (a Box: its low / high) or `low`, `high` given directly, per component or one number for all."""
+        from ..env.spaces import Box
+
+        if action_bound_method not in ("clip", "tanh", None):
+            raise ValueError(f"Got invalid action_bound_method={action_bound_method!r}. Valid values are: ('clip', 'tanh').")
+        Ad, dev = self.net.act_dim, self.device
+        if action_space is not None:
+            low, high = (action_space.low if low is None else low), (action_space.high if high is None else high)
+        if action_scaling and (low is None or high is None):
+            raise ValueError("action_scaling needs the bounds it maps to: `action_space` (a Box) or `low` and `high`")
+        self.action_scaling, self.action_bound_method = bool(action_scaling), action_bound_method
+        bounds = [None if b is None else np.broadcast_to(np.asarray(b, np.float32), (Ad,)).copy() for b in (low, high)]
+        self.action_space = Box(-np.inf if bounds[0] is None else bounds[0], np.inf if bounds[1] is None else bounds[1], (Ad,))
+        self._low_dev, self._high_dev = ((torch.as_tensor(b).to(dev) for b in bounds) if action_scaling else (None, None))
+        self._ctor.update(action_scaling=action_scaling, action_bound_method=action_bound_method, low=bounds[0], high=bounds[1])
+
+    def _gauss_kw(self) -> dict:
+        """What every csrc/gauss.hip entry takes of the actor besides its raw output."""
+        actor = self.net.actor
+        return dict(max_action=actor.max_action, unbounded=actor.unbounded, sigma_param=actor.sigma_param)
+
+    def _act_device_gauss(self, obs: torch.Tensor, out: dict | None, offset_dev, row_offset: int) -> dict:
+        """`act_device` of a Gaussian policy: act f32 [rows, act_dim] is the raw sample (what the buffer stores and the update
+        reads), `env_act` its `map_action`, what the collector steps the env with."""
+        D = self.net.obs_dim
+        rows = obs.reshape(-1, D)
+        raw = FlatMLP.forward(self.net.actor, rows, save=False)
+        value = self._values(rows, obs.reshape(-1, self.n_agent * D) if self.critic_input == "global" else None)
+        greedy = bool(self.deterministic_eval and not self.is_within_training_step)
+        act, logp, env_act = ops.gauss_sample(
+            raw, self.seed, offset=sample_counter(self, rows.shape[0], row_offset, offset_dev), offset_dev=offset_dev,
+            deterministic=greedy, bound_method=self.action_bound_method, low=self._low_dev, high=self._high_dev,
+            want_env_act=True, out=(out["act"], out["logp"]) if out is not None else None, **self._gauss_kw())
+        if out is not None:
+            out["value"].copy_(value)
+            out["env_act"] = env_act
+            return out
+        return act_result(None, act, logp, value, logits=raw, env_act=env_act)
+
+    def map_action(self, act):
+        """algorithm_base.py:255-288 on the host, for callers that hold a stored action: bound, then scale."""
+        if not self.gaussian:
+            return act
+        act = np.asarray(act.detach().cpu() if isinstance(act, torch.Tensor) else act)
+        if self.action_bound_method == "clip":
+            act = np.clip(act, -1.0, 1.0)
+        elif self.action_bound_method == "tanh":
+            act = np.tanh(act)
+        if self.action_scaling:
+            low, high = self.action_space.low, self.action_space.high
+            act = low + (high - low) * (act + 1.0) / 2.0
+        return act
+
+    def forward(self, batch: Batch, state=None, **kwargs) -> Batch:
+        if not self.gaussian:
+            return super().forward(batch, state, **kwargs)
+        obs = batch.obs.obs if isinstance(batch.obs, Batch) and "obs" in batch.obs else batch.obs
+        obs_t = to_tensor(obs, self.device, torch.float32)
+        lead = obs_t.shape[:-1]
+        res = self._act_device_gauss(obs_t, None, None, 0)
+        return Batch(logits=res["logits"].reshape(*lead, -1), act=res["act"].reshape(*lead, -1),
+                     env_act=res["env_act"].reshape(*lead, -1), state=None,
+                     policy=Batch(logp=res["logp"].reshape(lead), v_s=res["value"].reshape(lead)))
+
+    def _logp_old_gauss(self, obs: torch.Tensor, act: torch.Tensor) -> torch.Tensor:
+        """logp of the stored actions under the current parameters (ppo.py:157-161), when the rollout's are stale."""
+        return ops.gauss_logp_entropy(FlatMLP.forward(self.net.actor, obs, save=False), act, **self._gauss_kw())[0]
+
+    def _grad_step_gauss(self, pb: dict, idx: torch.Tensor, adv_stats, step_dev, rows):
+        """`_grad_step_steps` for a Gaussian policy, in the same non-fused shape: both forwards, the policy head
+        (`ops.gauss_ppo_head`) with the value term beside it (`ops.ppo_value_loss`), both backwards into the joint slabs, the
+        fold of the head's sigma partials into `sigma_param`'s slab columns, clip + Adam.  -> the step's 4 scalars."""
+        net, actor = self.net, self.net.actor
+        if self._grad_sync is not None:
+            raise NotImplementedError("data-parallel replicas of a Gaussian policy: the flat-gradient all-reduce of "
+                                      "`_grad_step_steps` is not wired for GaussianActorCritic")
+        if rows is not None:
+            cx, vg = ops.gather_rows(pb["joint"], rows), pb["n_agent"]
+            x = cx.view(-1, net.obs_dim)
+        else:
+            x, vg = ops.gather_rows(pb["obs"], idx), 1
+            cx = x if pb["joint"] is None else ops.gather_rows(pb["joint"], torch.div(idx, pb["n_agent"], rounding_mode="floor"))
+        raw = FlatMLP.forward(actor, x, save=True)
+        value = FlatMLP.forward(net.critic, cx, save=True).reshape(-1)
+        M, n_total, dev = idx.numel(), net.flat.numel(), self.device
+        nb, nv = ops.gauss_blocks(M), ops.ppo_loss_partial_elems(M) // 4
+        n_split = ops.mlp_n_split(M)
+        w = self._ws.get(("gauss", M))
+        if w is None:   # (made by the eager first update of a shape: a captured one finds them)
+            w = self._ws[("gauss", M)] = dict(
+                partial=torch.zeros((nb + nv) * 4, dtype=torch.float64, device=dev),
+                col=torch.zeros(nb, net.act_dim, dtype=torch.float64, device=dev),
+                nb=torch.tensor([nb + nv], dtype=torch.int32, device=dev), M=torch.tensor([M], dtype=torch.int64, device=dev),
+                slabs=torch.empty(n_split, n_total, dtype=torch.float32, device=dev))
+        head = ops.gauss_ppo_head(raw, pb["act"], pb["logp_old"], pb["adv"], self._cfg, adv_stats=adv_stats, perm=idx,
+                                  partial=w["partial"][:nb * 4], col_partial=w["col"], **self._gauss_kw())
+        dvalue, _ = ops.ppo_value_loss(value, pb["ret"], self._cfg_value[vg], M, v_s_old=pb["v_s"] if self.value_clip else None,
+                                       perm=idx, partial=w["partial"][nb * 4:])
+        slabs = w["slabs"]
+        actor.backward(head["d_raw"], n_split, slabs=slabs, slab_stride=n_total)
+        net.critic.backward(dvalue.view(-1, 1), n_split, slabs=slabs[:, net.n_actor:], slab_stride=n_total)
+        if head["col_partial"] is not None:
+            ops.gauss_sigma_fold(head["col_partial"], nb, slabs[:, actor.n_mlp_params:net.n_actor])
+        if step_dev is None:
+            self.opt_step += 1
+        else:
+            ops.call("tsm_u64_add", ops.ptr(step_dev), 1, ops.stream_ptr())
+        ops.adam_step(net.flat.data, slabs, self.exp_avg, self.exp_avg_sq, self.opt_step, lr=self.lr, lr_dev=self._lr_dev,
+                      betas=self.betas, eps=self.adam_eps, weight_decay=self.weight_decay, max_grad_norm=self.max_grad_norm,
+                      work=self.optim.work, step_dev=step_dev)
+        scal = torch.empty(1, 4, dtype=torch.float32, device=dev)
+        ops.ppo_finalize_many(w["partial"], (nb + nv) * 4, w["nb"], w["M"], self._cfg, scal)
+        return scal[0]
 
     # ---- helpers --------------------------------------------------------------------------------------------------
     @property
@@ -148,6 +276,8 @@ class GenericPPO(PPO):
     # ---- rollout side -----------------------------------------------------------------------------------------------
     def act_device(self, obs: torch.Tensor, out: dict | None = None, offset_dev: torch.Tensor | None = None,
                    row_offset: int = 0) -> dict:
+        if self.gaussian:
+            return self._act_device_gauss(obs, out, offset_dev, row_offset)
         D = self.net.obs_dim
         rows = obs.reshape(-1, D)
         logits = FlatMLP.forward(self.net.actor, rows, save=False)
@@ -174,7 +304,10 @@ class GenericPPO(PPO):
         no_next = buffer.obs_next_store is None  # ignore_obs_next (PPO._next_values_by_index)
         obs = buffer.obs_store[:T].reshape(T * L, D)
         obs_next = None if no_next else buffer.obs_next_store[:T].reshape(T * L, D)
-        act = buffer.act_store[:T].reshape(T * L)
+        act = buffer.act_store[:T].reshape(T * L, -1) if self.gaussian else buffer.act_store[:T].reshape(T * L)
+        if self.gaussian and (buffer.act_dim or 0) != self.net.act_dim:
+            raise ValueError(f"a Gaussian policy of act_dim = {self.net.act_dim} needs a buffer with that act_dim, got "
+                             f"{buffer.act_dim}")
         glob = self.critic_input == "global"
         joint = buffer.obs_store[:T].reshape(T * B, N * D) if glob else None
         joint_next = buffer.obs_next_store[:T].reshape(T * B, N * D) if glob and not no_next else None
@@ -189,6 +322,8 @@ class GenericPPO(PPO):
             v_s = self._lanes(vu_s).view(T, L)
         if reuse and buffer.logp_outputs_version == self.param_version:
             logp_old = buffer.logp_store[:T].reshape(T * L)
+        elif self.gaussian:
+            logp_old = self._logp_old_gauss(obs, act)
         else:
             logp_old, _ = ops.categorical_logp_entropy(FlatMLP.forward(self.net.actor, obs, save=False), act)
         if no_next:
@@ -214,6 +349,8 @@ class GenericPPO(PPO):
         capture); None = the host counter.  partial_out (f64, row-kernel path only): the step's loss partials are left
         there for ONE `ppo_finalize_many` over all steps of the update and None is returned."""
         net = self.net
+        if self.gaussian:
+            return self._grad_step_gauss(pb, idx, adv_stats, step_dev, rows)
         if self.fused_actor:
             return (yield from self._grad_step_fused_actor(pb, idx, adv_stats, step_dev, rows, partial_out))
         if rows is not None:
@@ -529,7 +666,8 @@ class GenericPPO(PPO):
     def learn_graph_ok(self, repeat: int = 1) -> bool:
         """Can `learn` run from static buffers inside captured graphs?  (`graph` is this class's capture switch; recompute_advantage
         re-runs the critic between repeats from the host.)"""
-        return bool(self.graph and not (self.recompute_adv and repeat > 1))
+        # (a Gaussian policy's `learn` runs `learn_steps`' eager launches: the static buffers hold one i32 action per row)
+        return bool(self.graph and not self.gaussian and not (self.recompute_adv and repeat > 1))
 
     def _learn_static(self, n: int, batch_size: int | None, repeat: int, has_trunc: bool) -> dict:
         """`PPO._learn_static` for the wide nets: static HBM buffers + `w["body"]`, a generator that issues `learn_steps`' launches
@@ -614,7 +752,10 @@ class GenericPPO(PPO):
         else:
             joint = None
             v_s, v_next = self._critic_values(obs), self._critic_values(obs_next)
-        logp_old, _ = ops.categorical_logp_entropy(FlatMLP.forward(self.net.actor, obs, save=False), act)
+        if self.gaussian:
+            logp_old = self._logp_old_gauss(obs, act)
+        else:
+            logp_old, _ = ops.categorical_logp_entropy(FlatMLP.forward(self.net.actor, obs, save=False), act)
         ret, adv = ops.gae_lanes(v_s.view(n, 1), v_next.view(n, 1), rew, term, trunc, self.gamma, self.gae_lambda)
         return dict(T=n, rows=None, obs=obs, act=act, v_s=v_s.contiguous(), ret=ret.reshape(-1), adv=adv.reshape(-1),
                     logp_old=logp_old, n_env=1, n_agent=1, joint=joint)
@@ -632,7 +773,8 @@ class GenericPPO(PPO):
             joint, joint_next = t(batch.global_obs, torch.float32), t(batch.global_obs_next, torch.float32)
         term = t(batch.terminated, torch.uint8).reshape(n, 1)
         trunc = t(batch.truncated, torch.uint8).reshape(n, 1) if "truncated" in batch else torch.zeros_like(term)
-        pb = self._lane_pb(obs, t(batch.act, torch.int32).reshape(n), t(batch.rew, torch.float32).view(n, 1), term, trunc, obs_next,
+        act = t(batch.act, torch.float32).reshape(n, -1) if self.gaussian else t(batch.act, torch.int32).reshape(n)
+        pb = self._lane_pb(obs, act, t(batch.rew, torch.float32).view(n, 1), term, trunc, obs_next,
                            joint, joint_next)
         st = yield from self._update_steps(pb, batch_size, repeat)
         return {"loss": st.loss.mean, "actor_loss": st.actor_loss.mean, "vf_loss": st.vf_loss.mean,

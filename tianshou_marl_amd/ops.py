@@ -2364,6 +2364,140 @@ def sac_actor_head(raw, z, q1a, q2a, dq1_da, dq2_da, alpha_dev, max_action: floa
 
 
 # --------------------------------------------------------------------------------------------
+# Gaussian policies for Box actions on the on-policy learners (continuous.py:238-247, ppo.py:157-211; csrc/gauss.hip)
+# --------------------------------------------------------------------------------------------
+_GAUSS_BOUND = {None: 0, "clip": 1, "tanh": 2}
+
+
+def gauss_check(act_dim: int) -> None:
+    """The bound of the Gaussian-policy kernels (include/tsmarl.h): ValueError naming the limit."""
+    call("tsm_gauss_check", int(act_dim))
+
+
+def gauss_blocks(M: int) -> int:
+    """Workgroups, hence rows of loss and sigma partials, of `gauss_ppo_head` on M rows."""
+    return -(-int(M) // _abi.GAUSS_ROWS_PER_BLOCK)
+
+
+def _gauss_raw(name: str, raw, sigma_param):
+    """`_sac_raw` behind the bound on act_dim, which is checked first: it needs no device."""
+    if raw.dim() == 2:
+        gauss_check(raw.shape[1] // 2 if sigma_param is None else raw.shape[1])
+    return _sac_raw(name, raw, sigma_param)
+
+
+def _gauss_act(name: str, act, Ad: int, rows: int | None = None):
+    """Stored actions f32 [n, Ad] in HBM (rows: exactly that many)."""
+    _dev_only(name, act)
+    if act.dim() != 2 or act.shape[1] != Ad or (rows is not None and act.shape[0] != rows):
+        raise ValueError(f"{name}: act must be [{'n' if rows is None else rows}, {Ad}], got {list(act.shape)}")
+    return _chk(act, torch.float32, "act")
+
+
+def _gauss_perm(name: str, perm, B: int):
+    if perm is None:
+        return None
+    _dev_only(name, perm)
+    if perm.numel() != B:
+        raise ValueError(f"{name}: perm must have {B} entries")
+    return _chk(perm, torch.int64, "perm")
+
+
+def gauss_sample(raw, seed: int, offset: int = 0, offset_dev=None, deterministic: bool = False, max_action: float = 1.0,
+                 unbounded: bool = False, sigma_param=None, bound_method: str | None = None, low=None, high=None,
+                 want_env_act: bool = False, out=None):
+    """Independent(Normal(mu, sigma), 1).sample() (deterministic: the mode) with its log-prob, the normals drawn inside the
+    launch; raw and sigma_param as `_sac_raw` takes them.  -> (act f32 [B, Ad], the raw sample a buffer stores, logp f32 [B],
+    env_act): env_act = the reference's map_action of act (bound_method None | "clip" | "tanh", then the affine map to
+    [low, high] f32 [Ad] when both are given), None unless want_env_act.  out = optional preallocated (act, logp)."""
+    raw, B, Ad, ld, sg, sg_ptr, ld_s = _gauss_raw("gauss_sample", raw, sigma_param)
+    if bound_method not in _GAUSS_BOUND:
+        raise ValueError(f"gauss_sample: bound_method must be None, 'clip' or 'tanh', got {bound_method!r}")
+    if (low is None) != (high is None):
+        raise ValueError("gauss_sample: low and high come together")
+    _dev_only("gauss_sample", low, high)
+    if low is not None:
+        low, high = _chk(low, torch.float32, "low").reshape(-1), _chk(high, torch.float32, "high").reshape(-1)
+        if low.numel() != Ad or high.numel() != Ad:
+            raise ValueError(f"gauss_sample: low and high must have {Ad} entries")
+    act, logp = out if out is not None else (None, None)
+    act = _out("gauss_sample", act, (B, Ad), torch.float32, raw.device, "act", "numel")
+    logp = _out("gauss_sample", logp, (B,), torch.float32, raw.device, "logp", "numel")
+    env_act = torch.empty(B, Ad, dtype=torch.float32, device=raw.device) if want_env_act else None
+    call("tsm_gauss_sample", ptr(raw), ld, sg_ptr, ld_s, B, Ad, float(max_action), int(bool(unbounded)),
+         *_philox("gauss_sample", seed, offset, offset_dev), int(bool(deterministic)), _GAUSS_BOUND[bound_method], ptr(low),
+         ptr(high), ptr(act), ptr(logp), ptr(env_act), stream_ptr())
+    return act, logp, env_act
+
+
+def gauss_logp_entropy(raw, act, perm=None, max_action: float = 1.0, unbounded: bool = False, sigma_param=None):
+    """(logp, entropy) f32 [B] of the actions act[perm] (perm None: act, [B, Ad]) under the B rows of raw; on `gauss_sample`'s
+    act the sample's logp, bit for bit."""
+    raw, B, Ad, ld, sg, sg_ptr, ld_s = _gauss_raw("gauss_logp_entropy", raw, sigma_param)
+    act = _gauss_act("gauss_logp_entropy", act, Ad, None if perm is not None else B)
+    perm = _gauss_perm("gauss_logp_entropy", perm, B)
+    logp = torch.empty(B, dtype=torch.float32, device=raw.device)
+    ent = torch.empty(B, dtype=torch.float32, device=raw.device)
+    call("tsm_gauss_logp_entropy", ptr(raw), ld, sg_ptr, ld_s, ptr(act), ptr(perm), B, Ad, float(max_action),
+         int(bool(unbounded)), ptr(logp), ptr(ent), stream_ptr())
+    return logp, ent
+
+
+def gauss_ppo_head(raw, act, logp_old, adv, cfg: tsm_ppo_cfg, adv_stats=None, perm=None, first_row: int = 0,
+                   max_action: float = 1.0, unbounded: bool = False, sigma_param=None, out=None, partial=None,
+                   col_partial=None):
+    """The policy terms of one PPO (cfg.loss_kind 0) or policy-gradient (1) minibatch and their backward, in one launch: raw =
+    the actor's output on the M minibatch rows (as `_sac_raw`); act [n, Ad], logp_old, adv [n]: full-batch arrays read at perm
+    (None: first_row + i).  -> dict(d_raw: the shape of raw, d loss / d raw ([d mu_raw | d sigma_raw] with a conditioned sigma),
+    partial f64 [blocks, 4] = {sum obj, 0, sum entropy, 0} for `ppo_finalize_many`, col_partial f64 [blocks, Ad]: the workgroups'
+    d loss / d sigma_param for `gauss_sigma_fold` (None with a conditioned sigma), n_blocks)."""
+    raw, M, Ad, ld, sg, sg_ptr, ld_s = _gauss_raw("gauss_ppo_head", raw, sigma_param)
+    if cfg.loss_kind not in (0, 1):
+        raise ValueError("gauss_ppo_head needs a cfg with loss_kind 0 (PPO clip) or 1 (policy gradient)")
+    act = _gauss_act("gauss_ppo_head", act, Ad)
+    n = act.shape[0]
+    _dev_only("gauss_ppo_head", logp_old, adv, adv_stats)
+    perm = _gauss_perm("gauss_ppo_head", perm, M)
+    if perm is None and not 0 <= first_row <= n - M:
+        raise ValueError(f"gauss_ppo_head: rows [{first_row}, {first_row + M}) leave the batch of {n}")
+    adv = _chk(adv, torch.float32, "adv").reshape(-1)
+    logp_old = None if logp_old is None else _chk(logp_old, torch.float32, "logp_old").reshape(-1)
+    if adv.numel() != n or (logp_old is not None and logp_old.numel() != n):
+        raise ValueError(f"gauss_ppo_head: adv and logp_old must have the {n} entries of act")
+    if cfg.adv_norm and (adv_stats is None or adv_stats.numel() < 2):
+        raise ValueError("gauss_ppo_head: adv_norm needs adv_stats {mean, std}")
+    dev, nb = raw.device, gauss_blocks(M)
+    out = _out("gauss_ppo_head", out, raw.shape, torch.float32, dev)
+    partial = _out("gauss_ppo_head", partial, (nb, 4), torch.float64, dev, "partial", "min")
+    cond = sigma_param is None
+    if not cond:
+        col_partial = _out("gauss_ppo_head", col_partial, (nb, Ad), torch.float64, dev, "col_partial", "min")
+    call("tsm_gauss_ppo_head", ptr(raw), ld, sg_ptr, ld_s, ptr(act), ptr(logp_old), ptr(adv), ptr(perm), int(first_row), M, Ad,
+         ptr(None if adv_stats is None else _chk(adv_stats, torch.float32, "adv_stats")), C.byref(cfg), float(max_action),
+         int(bool(unbounded)), ptr(out), out.data_ptr() + 4 * Ad if cond else None, ld, ptr(partial),
+         None if cond else ptr(col_partial), stream_ptr())
+    return dict(d_raw=out, partial=partial, col_partial=None if cond else col_partial, n_blocks=nb)
+
+
+def gauss_sigma_fold(col_partial, n_blocks: int, slabs):
+    """`gauss_ppo_head`'s col_partial f64 [>= n_blocks, Ad] summed in block order into slabs [n_split, Ad], a (strided) view of
+    the sigma_param columns of the actor's gradient slabs: slab 0 <- the sums, the others zero (`cac_col_sum`'s contract)."""
+    if slabs.dim() != 2 or slabs.dtype != torch.float32 or slabs.shape[0] < 1:
+        raise ValueError("gauss_sigma_fold: slabs must be f32 [n_split, Ad]")
+    Ad = slabs.shape[1]
+    gauss_check(Ad)
+    _dev_only("gauss_sigma_fold", col_partial, slabs)
+    if slabs.stride(1) != 1:
+        raise ValueError("gauss_sigma_fold: slabs must have unit column stride")
+    col_partial = _chk(col_partial, torch.float64, "col_partial")
+    if n_blocks < 1 or col_partial.numel() < n_blocks * Ad:
+        raise ValueError(f"gauss_sigma_fold: col_partial must hold {n_blocks} rows of {Ad}")
+    call("tsm_gauss_sigma_fold", ptr(col_partial), int(n_blocks), Ad, slabs.shape[0], slabs.data_ptr(),
+         slabs.stride(0) if slabs.shape[0] > 1 else Ad, stream_ptr())
+    return slabs
+
+
+# --------------------------------------------------------------------------------------------
 # Offline continuous learners: CQL / Cal-QL and TD3+BC (imitation/cql.py, td3_bc.py; csrc/cql.hip)
 # --------------------------------------------------------------------------------------------
 def cql_check(act_dim: int, num_repeat: int = 1) -> None:

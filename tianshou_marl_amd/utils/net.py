@@ -1412,6 +1412,68 @@ class MLPActorCritic(FlatNet):
                 net.bias(i).zero_()
 
 
+class GaussianActorCritic(FlatNet):
+    """`MLPActorCritic` for `Box` actions: a `ContinuousActorProbabilistic` (either sigma mode, `unbounded`, `max_action`)
+    followed by a critic `FlatMLP` [critic_obs_dim, *hidden, 1] under one flat parameter vector, for
+    `GenericPPO` (Independent(Normal(mu, sigma), 1) policies, csrc/gauss.hip).  `n_actor` includes the actor's `sigma_param`
+    tail, so the one Adam and the one gradient-norm clip over the vector cover it (ActorCritic.parameters(), common.py:461-474).
+    Checkpoint keys are the reference's: `policy.actor.*` (sigma_param first, continuous.py:222) then `critic.*`."""
+
+    image = image_map = None  # no LDS image: the dense kernels stream the weights
+
+    def __init__(self, obs_dim: int, act_dim: int, hidden_sizes=(64, 64), act: str = "relu", max_action: float = 1.0,
+                 unbounded: bool = False, conditioned_sigma: bool = False, critic_obs_dim: int | None = None,
+                 device: str | torch.device = "cuda", seed: int | None = None, init: str = "orthogonal",
+                 storage: torch.Tensor | None = None) -> None:
+        super().__init__()
+        ops.gauss_check(int(act_dim))
+        self.obs_dim, self.act_dim, self.hidden = int(obs_dim), int(act_dim), int(hidden_sizes[0])
+        self.n_act = self.act_dim  # the width of an action row, where the categorical nets have the number of actions
+        self.critic_obs_dim = int(critic_obs_dim or obs_dim)
+        cond = bool(conditioned_sigma)
+        dims_a = [self.obs_dim, *hidden_sizes, (2 if cond else 1) * self.act_dim]
+        dims_c = [self.critic_obs_dim, *hidden_sizes, 1]
+        na = ops.mlp_param_count(ops.mlp_desc(dims_a, act)) + (0 if cond else self.act_dim)
+        nc = ops.mlp_param_count(ops.mlp_desc(dims_c, act))
+        flat = self._claim(na + nc, storage, device)
+        self.n_actor, self.n_critic = na, nc
+        trunk_seed = None if storage is None else 0   # (as MLPActorCritic: a twin draws from a private generator)
+        self.actor = ContinuousActorProbabilistic(self.obs_dim, self.act_dim, tuple(hidden_sizes), max_action=max_action,
+                                                  unbounded=unbounded, conditioned_sigma=cond, act=act, device=device,
+                                                  seed=trunk_seed, storage=flat[:na])
+        self.critic = FlatMLP(dims_c, act, device=device, seed=trunk_seed, storage=flat[na:])
+        self.critic.ref_scheme = "head"   # DiscreteCritic / ContinuousCritic over Net(hidden_sizes=[...]): `last.model.0`
+        if storage is None:
+            self.reset_parameters(init, seed)
+
+    def param_views(self, flat: torch.Tensor | None = None) -> list[torch.Tensor]:
+        flat = self._vector(flat)
+        return self.actor.param_views(flat[:self.n_actor]) + self.critic.param_views(flat[self.n_actor:])
+
+    def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+        flat, na = self._vector(flat), self.n_actor
+        return [(p + k, v) for p, net, part in (("policy.actor.", self.actor, flat[:na]), ("critic.", self.critic, flat[na:]))
+                for k, v in net.reference_named_views(part)]
+
+    @torch.no_grad()
+    def reset_parameters(self, init: str = "orthogonal", seed: int | None = None) -> None:
+        """orthogonal weights + zero bias (the reference scripts' init) or nn.Linear's default; `sigma_param` is zero either
+        way (continuous.py:222)."""
+        if seed is not None:
+            torch.manual_seed(seed)
+        for net in (self.actor, self.critic):
+            if init != "orthogonal":
+                net.reset_parameters(seed)
+                continue
+            for i in range(net.n_layers):
+                w = torch.empty(net.weight(i).shape)
+                nn.init.orthogonal_(w)
+                net.weight(i).copy_(w)
+                net.bias(i).zero_()
+        if self.actor.sigma_param is not None:
+            self.actor.sigma_param.zero_()
+
+
 def _one_parameter(flat: torch.Tensor) -> list[torch.Tensor]:
     return [flat]
 
@@ -1674,6 +1736,9 @@ def net_from_reference_modules(policy, critic, device="cuda"):
     if cached is not None and cached[0] is critic and str(cached[1].flat.device).startswith(str(device).split(":")[0]):
         return cached[1]
     actor_mod = getattr(policy, "actor", policy)
+    if hasattr(actor_mod, "sigma_param") or hasattr(actor_mod, "mu"):
+        raise NotImplementedError("reference-object construction (`policy=`, `critic=`) with a continuous actor: the Gaussian "
+                                  "policy is built from the engine's own net, `GenericPPO(net=GaussianActorCritic(...))`")
     la = linear_layers(actor_mod)
     act = activation_of(actor_mod)
     obs_dim, n_act = la[0][0].shape[1], la[-1][0].shape[0]
