@@ -1901,6 +1901,37 @@ int tsm_gauss_ppo_head(const float *mu_raw, int64_t ld_mu, const float *sigma_ra
 int tsm_gauss_sigma_fold(const double *col_partial, int32_t n_blocks, int32_t act_dim, int32_t n_slab, float *slabs_out,
                          int64_t slab_stride, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Fully-connected networks with LayerNorm in every hidden layer  (csrc/layernorm.hip)
+ * Replaces  MLP(norm_layer=nn.LayerNorm) (tianshou/utils/net/common.py:22-47, 90-169): hidden layer l is Linear ->
+ *           LayerNorm(dims[l + 1], eps) -> `act`; the last layer a plain Linear; and `loss.backward()` through the stack.
+ * The net is a tsm_mlp_desc and eps, given side by side (tsm_mlp_desc is as it was).  Hidden widths dims[1 .. L - 1] are at most
+ * TSM_LN_MAX_WIDTH: a forward workgroup holds whole rows; anything wider is TSM_ERR_INVALID naming the layer, before any launch.
+ * params: torch `parameters()` order: per hidden layer w [O][K], b [O], gamma [O], beta [O]; last layer w, b.
+ * tsm_mlp_ln_param_count / _save_elems: *n_param = the floats of the vector; *n_save = the floats of `saved` for B rows (per
+ *           hidden layer xhat [B][O], then rstd [B]).
+ * tsm_mlp_ln_forward: acts as tsm_mlp_forward (block l = the layer's activation output).  ONE launch per hidden layer: GEMM,
+ *           bias, row statistics (biased variance, two-pass in f32), affine and activation; the last layer is tsm_dense_linear.
+ *           saved (nullable: nothing is kept, no backward can follow).  A row's bits depend on neither B nor the other rows.
+ * tsm_mlp_ln_backward: slabs[n_split][n_param] of sum(out * d_out) as tsm_mlp_backward (slab row ranges, slab_stride, every
+ *           entry of every slab written, +0.0 in a slab without rows), gamma / beta gradients included.  Per hidden layer:
+ *           da = dz W (tsm_dense_dgrad), one row launch da -> dy and the slabs' gamma / beta entries, then tsm_dense_wgrad on dy.
+ *           d_acts: workspace of tsm_mlp_act_elems floats.
+ * tsm_mlp_ln_input_grad: as tsm_mlp_input_grad: the same chain without any parameter gradient, ended by the window of W_0.
+ * No atomics; two runs give the same bits.
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_LN_MAX_WIDTH 512
+int tsm_mlp_ln_param_count(const tsm_mlp_desc *desc, int64_t *n_param);
+int tsm_mlp_ln_save_elems(const tsm_mlp_desc *desc, int64_t B, int64_t *n_save);
+int tsm_mlp_ln_forward(const tsm_mlp_desc *desc, float eps, const float *params, const float *x, int64_t B, float *acts,
+                       float *saved, void *stream);
+int tsm_mlp_ln_backward(const tsm_mlp_desc *desc, const float *params, const float *x, int64_t B, const float *acts,
+                        const float *saved, const float *d_out, float *d_acts, int32_t n_split, float *slabs,
+                        int64_t slab_stride, void *stream);
+int tsm_mlp_ln_input_grad(const tsm_mlp_desc *desc, const float *params, const float *x, int64_t B, const float *acts,
+                          const float *saved, const float *d_out, float *d_acts, int32_t col0, int32_t n_col, float *dx,
+                          int64_t ldx, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,7 +30,7 @@ from .. import ops
 from ..data.batch import Batch
 from ..data.stats import TrainingStats
 from ..utils.learner import act_result, result_slot, sample_counter, slab_workspace
-from ..utils.net import FlatMLP, Recurrent, export_views, import_views, lagged_copy, ref_layer_keys
+from ..utils.net import FlatMLP, Recurrent, export_views, import_views, lagged_copy
 from ..utils.tensor import to_tensor
 from .optim import flat_adam_of
 
@@ -465,7 +465,7 @@ class DQN(DeviceOffPolicyRows, nn.Module):
         """[(key, view)] of a Q-network: a `FlatMLP` is a `Net(hidden_sizes=[...])` used whole (`ref_layer_keys`: "body");
         any other net states its own names."""
         if isinstance(net, FlatMLP):
-            return net.named_layers(ref_layer_keys(net.n_layers, "body"))
+            return net.named_reference_layers("body")
         return net.reference_named_views()
 
     def to_reference_state_dict(self) -> OrderedDict:

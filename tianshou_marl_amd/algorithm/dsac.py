@@ -25,7 +25,7 @@ from .. import ops
 from ..data.batch import Batch
 from ..data.stats import TrainingStats
 from ..utils.learner import act_result, result_slot, sample_counter, slab_workspace
-from ..utils.net import FlatMLP, ref_layer_keys
+from ..utils.net import FlatMLP
 from ..utils.tensor import to_tensor
 from .actor_critic import ActorDualCriticsOffPolicyAlgorithm, EntropyCoefficient
 from .actor_critic import Alpha, AutoAlpha, FixedAlpha  # noqa: F401  (public names of this module, as before)
@@ -140,7 +140,7 @@ class DiscreteSAC(EntropyCoefficient, ActorDualCriticsOffPolicyAlgorithm):
     # every net is a `DiscreteActor` / `DiscreteCritic` around a `Net(hidden_sizes=[...])` (`ref_layer_keys`: "head")
     @staticmethod
     def _ref_views(net) -> list:
-        return net.named_layers(ref_layer_keys(net.n_layers, "head"))
+        return net.named_reference_layers("head")
 
     # ---- ActorCriticOffPolicyAlgorithm._preprocess_batch (ddpg.py:287-339) with discrete_sac.py:147-155 -----------------
     def _preprocess_batch(self, batch: Batch, buffer, indices, agent: int | None = None) -> Batch:

@@ -31,7 +31,7 @@ from torch import nn
 from ... import ops
 from ...data.batch import Batch
 from ...utils.learner import act_result, result_slot, sample_counter, slab_workspace
-from ...utils.net import FlatMLP, join_nets, lagged_twins, ref_layer_keys
+from ...utils.net import FlatMLP, export_views, import_views, join_nets, lagged_twins
 from ...utils.tensor import to_tensor
 from ..optim import flat_adam_of
 from .ctde import LazyScalars
@@ -241,9 +241,9 @@ class MADDPGPolicy(nn.Module):
         """Every net under `actors.{i}.fc{k}.weight` style keys (critics, target_actors, target_critics alike)."""
         sd = OrderedDict()
         for prefix, m in self._named_nets():
-            m.export_layers(ref_layer_keys(m.n_layers, "fc"), prefix + ".", sd)
+            export_views(m.named_reference_layers("fc"), prefix + ".", sd)
         return sd
 
     def load_reference_state_dict(self, sd) -> None:
         for prefix, m in self._named_nets():
-            m.import_layers(sd, ref_layer_keys(m.n_layers, "fc"), prefix + ".")
+            import_views(m.named_reference_layers("fc"), sd, prefix + ".")

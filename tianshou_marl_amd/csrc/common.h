@@ -45,6 +45,11 @@ int tsm_opt(int id);
 
 static inline hipStream_t tsm_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+// dense.hip, for the chains of layernorm.hip: tsm_dense_dgrad on a window of W's columns, dx[m][0 .. n_col) = dz[m] . W[:, 0 .. n_col)
+// with W = the window's first column and ldw the pitch of W's rows
+int tsm_dense_dgrad_window(const float *dz, const float *W, int64_t ldw, int64_t M, int32_t O, int32_t n_col, float *dx,
+                           int64_t ld_dx, void *stream);
+
 constexpr int kWave = 64;  // gfx950 wavefront
 
 typedef float f4 __attribute__((ext_vector_type(4)));  // an MFMA accumulator tile / four floats in consecutive registers

@@ -353,10 +353,16 @@ TSM_EXPORT int tsm_dense_dgrad(const float *dz, const float *W, int64_t M, int32
                 O, (long long)ld_dx);
     TSM_REQUIRE(dz && W && dx, "tsm_dense_dgrad: null pointer");
     TSM_REQUIRE(ceil_div(M, BM) <= 65535, "tsm_dense_dgrad: %lld rows too many for one launch (max %d)", (long long)M, 65535 * BM);
+    return tsm_dense_dgrad_window(dz, W, K, M, O, K, dx, ld_dx, stream);
+}
+
+// (common.h) the same launch on n_col columns of a W whose rows have pitch ldw; the caller has checked the arguments
+int tsm_dense_dgrad_window(const float *dz, const float *W, int64_t ldw, int64_t M, int32_t O, int32_t n_col, float *dx,
+                           int64_t ld_dx, void *stream) {
     GemmArgs g{};
-    g.A = dz; g.lda = O; g.B = W; g.ldb = K; g.M = M; g.N = K; g.K = O; g.k_per_split = O;
+    g.A = dz; g.lda = O; g.B = W; g.ldb = ldw; g.M = M; g.N = n_col; g.K = O; g.k_per_split = O;
     g.C = dx; g.ldc = ld_dx; g.act = 0;
-    dim3 grid((unsigned)ceil_div(K, BN), (unsigned)ceil_div(M, BM), 1);
+    dim3 grid((unsigned)ceil_div(n_col, BN), (unsigned)ceil_div(M, BM), 1);
     hipLaunchKernelGGL((gemm_kernel<false, true, EPI_DGRAD, 1>), grid, dim3(NT), 0, tsm_stream(stream), g);
     TSM_LAUNCH_CHECK();
     return TSM_OK;

@@ -3120,16 +3120,17 @@ def mlp_param_count(desc) -> int:
     return call("tsm_mlp_param_count", C.byref(desc))
 
 
-def _mlp_args(name: str, desc, params, x, acts=None, d_out=None):
+def _mlp_args(name: str, desc, params, x, acts=None, d_out=None, count=None):
     """The host checks the dense entries share, before any launch: device f32 tensors, x [B, dims[0]], a parameter vector that
     holds the net (the net reads its head: an actor keeps its sigma_param behind the layers) and, where given, `acts` of
-    tsm_mlp_act_elems floats and `d_out` [B, dims[-1]].  -> (params, x, B, n_act, the net's parameter count)."""
+    tsm_mlp_act_elems floats and `d_out` [B, dims[-1]].  `count`: the net's parameter count where it is not `mlp_param_count`'s
+    (`mlp_ln_param_count`).  -> (params, x, B, n_act, the net's parameter count)."""
     _dev_only(name, params, x, acts, d_out)
     x = _chk(x, torch.float32, "x")
     if x.dim() != 2 or x.shape[1] != desc.dims[0]:
         raise ValueError(f"{name}: input width != dims[0]: x must be [B, {desc.dims[0]}], got {tuple(x.shape)}")
     B = x.shape[0]
-    n_param = mlp_param_count(desc)
+    n_param = (count or mlp_param_count)(desc)
     if n_param < 0:
         _abi.check(_abi.TSM_ERR_INVALID)
     if params.numel() < n_param:
@@ -3290,6 +3291,81 @@ def mlp_input_grad(desc, params, x, acts, d_out, col0: int, n_col: int, out=None
 
 
 # --------------------------------------------------------------------------------------------
+# fully-connected networks with LayerNorm in every hidden layer (csrc/layernorm.hip)
+# --------------------------------------------------------------------------------------------
+def _i64_query(entry: str, *args) -> int:
+    n = C.c_int64(0)
+    call(entry, *args, C.byref(n))
+    return n.value
+
+
+def mlp_ln_param_count(desc) -> int:
+    """Floats of a normalised net's vector: per hidden layer W, b, gamma, beta; the last layer W, b.  ValueError naming the
+    layer when a hidden width exceeds `_abi.LN_MAX_WIDTH`."""
+    return _i64_query("tsm_mlp_ln_param_count", C.byref(desc))
+
+
+def mlp_ln_save_elems(desc, B: int) -> int:
+    """Floats of the `saved` workspace of `mlp_ln_forward` for B rows (per hidden layer xhat [B, O] and rstd [B])."""
+    return _i64_query("tsm_mlp_ln_save_elems", C.byref(desc), B)
+
+
+def _mlp_ln_saved(name: str, desc, B: int, saved, dev):
+    n = mlp_ln_save_elems(desc, B)
+    return _out(name, saved, (n,), torch.float32, dev, "saved", "numel")
+
+
+def mlp_ln_forward(desc, eps: float, params, x, acts=None, saved=None, save: bool = True):
+    """`mlp_forward` of Linear -> LayerNorm(eps) -> act hidden layers, one launch per layer (include/tsmarl.h:
+    tsm_mlp_ln_forward) -> (out [B, dims[-1]], acts, saved); `save=False`: nothing is kept for a backward, saved is None."""
+    params, x, B, n, _ = _mlp_args("mlp_ln_forward", desc, params, x, acts, count=mlp_ln_param_count)
+    if not 0.0 < float(eps) < 1e30:
+        raise ValueError(f"mlp_ln_forward: eps must be positive and finite, got {eps}")
+    saved = _mlp_ln_saved("mlp_ln_forward", desc, B, saved, x.device) if save else None
+    if acts is None:
+        acts = torch.empty(n, dtype=torch.float32, device=x.device)
+    call("tsm_mlp_ln_forward", C.byref(desc), float(eps), ptr(params), ptr(x), B, ptr(acts), ptr(saved), stream_ptr())
+    O = desc.dims[desc.n_layers]
+    return acts[n - B * O:].view(B, O), acts, saved
+
+
+def mlp_ln_backward(desc, params, x, acts, saved, d_out, n_split: int = 0, slabs=None, slab_stride: int = 0):
+    """`mlp_backward` of a normalised net: gradient slabs [n_split, n_param] of sum(out * d_out), the gamma / beta gradients
+    at their offsets.  `acts`, `saved`: what `mlp_ln_forward` left for x."""
+    params, x, B, _, n_param = _mlp_args("mlp_ln_backward", desc, params, x, acts, d_out, count=mlp_ln_param_count)
+    if B < 1:
+        raise ValueError("mlp_ln_backward: batch must be >= 1")
+    if saved is None:
+        raise ValueError("mlp_ln_backward: saved, what mlp_ln_forward kept for x, is required")
+    saved = _mlp_ln_saved("mlp_ln_backward", desc, B, saved, x.device)
+    d_out = _chk(d_out, torch.float32, "d_out")
+    n_split, slabs, slab_stride = _slab_dest("mlp_ln_backward", slabs, n_split, B,
+                                             slab_stride or (params.numel() if slabs is None else n_param), n_param, x.device)
+    d_acts = torch.empty_like(acts)
+    call("tsm_mlp_ln_backward", C.byref(desc), ptr(params), ptr(x), B, ptr(acts), ptr(saved), ptr(d_out), ptr(d_acts), n_split,
+         slabs.data_ptr(), slab_stride, stream_ptr())
+    return slabs
+
+
+def mlp_ln_input_grad(desc, params, x, acts, saved, d_out, col0: int, n_col: int, out=None, d_acts=None):
+    """`mlp_input_grad` of a normalised net: gradient of sum(out * d_out) w.r.t. the input columns [col0, col0 + n_col)."""
+    if not (0 <= col0 and n_col >= 1 and col0 + n_col <= desc.dims[0]):
+        raise ValueError(f"mlp_ln_input_grad: columns [{col0}, {col0 + n_col}) leave the input width {desc.dims[0]}")
+    params, x, B, n_act, _ = _mlp_args("mlp_ln_input_grad", desc, params, x, acts, d_out, count=mlp_ln_param_count)
+    if B < 1:
+        raise ValueError("mlp_ln_input_grad: batch must be >= 1")
+    if saved is None:
+        raise ValueError("mlp_ln_input_grad: saved, what mlp_ln_forward kept for x, is required")
+    saved = _mlp_ln_saved("mlp_ln_input_grad", desc, B, saved, x.device)
+    d_out = _chk(d_out, torch.float32, "d_out")
+    out = _out("mlp_ln_input_grad", out, (B, n_col), torch.float32, x.device)
+    d_acts = _out("mlp_ln_input_grad", d_acts, (n_act,), torch.float32, x.device, "d_acts", "numel")
+    call("tsm_mlp_ln_input_grad", C.byref(desc), ptr(params), ptr(x), B, ptr(acts), ptr(saved), ptr(d_out), ptr(d_acts), col0,
+         n_col, ptr(out), n_col, stream_ptr())
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # NPG / TRPO: Fisher-vector products and conjugate gradients (npg.py:195-224, trpo.py:152-191; csrc/fisher.hip)
 # --------------------------------------------------------------------------------------------
 def mlp_tangent_forward(desc, params, v, x, acts, t_acts=None):
@@ -3357,12 +3433,13 @@ def fisher_vector_product(net, v, n_split: int = 0, slabs=None, ws: dict | None 
     """F v of the actor `net` (a FlatMLP with a categorical head) at the rows of its last `forward(save=True)`, as gradient
     slabs [n_split, n_param] that sum to it: tangent forward, Fisher head, mlp_backward.  -> (slabs, partial: the head's f64
     partials of v^T F v).  The damping term is the caller's (tsm_cg_update adds it).  ws: a dict that keeps the buffers."""
+    desc = net.desc   # (a normalised net refuses here, by name: the tangent forward is the plain chain's)
     x, acts = net._saved_forward("fisher_vector_product")
     B, O = x.shape[0], net.dims[-1]
     ws = {} if ws is None else ws
-    jv, ws["t_acts"] = mlp_tangent_forward(net.desc, net.flat.data, v, x, acts, ws.get("t_acts"))
+    jv, ws["t_acts"] = mlp_tangent_forward(desc, net.flat.data, v, x, acts, ws.get("t_acts"))
     ws["u"], ws["partial"] = fisher_head(acts[acts.numel() - B * O:].view(B, O), jv, ws.get("u"), ws.get("partial"))
-    return mlp_backward(net.desc, net.flat.data, x, acts, ws["u"], n_split, slabs=slabs), ws["partial"]
+    return mlp_backward(desc, net.flat.data, x, acts, ws["u"], n_split, slabs=slabs), ws["partial"]
 
 
 def cg_chunks(n: int) -> int:

@@ -23,15 +23,19 @@ from .. import ops
 from ..data.batch import Batch
 
 
-def ref_layer_keys(n_layers: int, scheme: str) -> list[tuple[str, str]]:
+def ref_layer_keys(n_layers: int, scheme: str, stride: int = 2, at: int = 0) -> list[tuple[str, str]]:
     """[(weight key, bias key)] per layer of a `FlatMLP` under the names the reference's modules give its parameters:
       "body"  a `Net(hidden_sizes=[...])` used whole: `model.model.{2 i}` (Linear, activation, Linear, ...)
       "head"  such a `Net` under a DiscreteActor / DiscreteCritic: `preprocess.model.model.{2 i}`, the output `last.model.0`
       "fc"    the CTDE nets (ctde.py:362-364, 398-400): `fc{i + 1}`
-      "seq"   a bare `nn.Sequential` of Linear and activation: `{2 i}`"""
-    stems = {"body": [f"model.model.{2 * i}" for i in range(n_layers)],
-             "head": [f"preprocess.model.model.{2 * i}" for i in range(n_layers - 1)] + ["last.model.0"],
-             "fc": [f"fc{i + 1}" for i in range(n_layers)], "seq": [str(2 * i) for i in range(n_layers)]}[scheme]
+      "seq"   a bare `nn.Sequential` of Linear and activation: `{2 i}`
+    `stride`: modules per hidden block of the Sequential (3 with a norm layer before the activation, common.py:40-45);
+    `at` = 1: the keys of the block's SECOND module, its LayerNorm (which "fc" names `norm{i + 1}`: the CTDE nets of the
+    reference have none)."""
+    stems = {"body": [f"model.model.{stride * i + at}" for i in range(n_layers)],
+             "head": [f"preprocess.model.model.{stride * i + at}" for i in range(n_layers - 1)] + ["last.model.0"],
+             "fc": [f"{'norm' if at else 'fc'}{i + 1}" for i in range(n_layers)],
+             "seq": [str(stride * i + at) for i in range(n_layers)]}[scheme]
     return [(s + ".weight", s + ".bias") for s in stems]
 
 
@@ -169,29 +173,65 @@ class FlatMLP(FlatNet):
 
     `forward(x)` keeps the activations of the last call so that `backward(d_out)` can produce the gradient slabs
     (the pair replaces autograd for this module).  Layer views (`weight(i)`, `bias(i)`) alias the flat vector.
-    `n_extra`: elements a subclass keeps behind the layers on the vector."""
+    `n_extra`: elements a subclass keeps behind the layers on the vector.
+
+    `norm="layer"`: the reference's `MLP(norm_layer=nn.LayerNorm)` (common.py:22-47): every hidden layer is Linear ->
+    LayerNorm(eps=norm_eps) -> activation, the last one a plain Linear; the vector holds W, b, gamma, beta per hidden layer
+    (gamma = 1, beta = 0 at first) and the passes run in csrc/layernorm.hip, one launch per normalised layer forward.  Hidden
+    widths are then at most `_abi.LN_MAX_WIDTH`.  `weight(i)` / `bias(i)` / `layer_views` still give (W, b), `norm_views` the
+    (gamma, beta) pairs.  Any other norm layer is refused by name."""
 
     ref_scheme = "fc"   # of `ref_layer_keys`: the key names of `to_reference_state_dict`; any other through `export_layers`
 
     def __init__(self, dims, act: str = "relu", device: str | torch.device = "cuda", seed: int | None = None,
-                 storage: torch.Tensor | None = None, n_extra: int = 0) -> None:
+                 storage: torch.Tensor | None = None, n_extra: int = 0, norm: str | None = None,
+                 norm_eps: float = 1e-5) -> None:
         super().__init__()
         self.dims = [int(d) for d in dims]
         self.act = act
-        self.desc = ops.mlp_desc(self.dims, act)
-        self.n_mlp_params = ops.mlp_param_count(self.desc)
+        if norm not in (None, "layer"):
+            raise ValueError(f"FlatMLP: norm={norm!r} is not supported: the HIP MLP kernels have LayerNorm with an elementwise "
+                             "affine (norm='layer') and no other norm layer (BatchNorm1d, elementwise_affine=False)")
+        self.norm, self.norm_eps = norm, float(norm_eps)
+        self._desc = ops.mlp_desc(self.dims, act)
+        self.n_mlp_params = (ops.mlp_ln_param_count if norm else ops.mlp_param_count)(self._desc)
         self._claim(self.n_mlp_params + n_extra, storage, device)
-        self._offsets = []
+        self._offsets, self._norm_offsets = [], []
         o = 0
         for i in range(len(self.dims) - 1):
             k, n = self.dims[i], self.dims[i + 1]
             self._offsets.append((o, o + n * k))
             o += n * k + n
+            if norm and i + 2 < len(self.dims):
+                self._norm_offsets.append(o)
+                o += 2 * n
         self.reset_parameters(seed)
+
+    @property
+    def desc(self):
+        """The `tsm_mlp_desc` of a plain Linear -> activation chain, for callers that launch `ops.mlp_*` on the vector
+        themselves.  A normalised net has no such form."""
+        if self.norm:
+            raise NotImplementedError(
+                f"{type(self).__name__}(norm={self.norm!r}) has no plain tsm_mlp_desc: the caller runs the un-normalised launch "
+                "sequence (ops.mlp_forward_cond / mlp_tangent_forward / fisher_vector_product) on the vector itself and would "
+                "compute a different net; use forward / backward / input_grad, or a net without norm")
+        return self._desc
 
     @property
     def n_layers(self) -> int:
         return len(self.dims) - 1
+
+    def norm_views(self, flat: torch.Tensor | None = None) -> list[tuple[torch.Tensor, torch.Tensor]]:
+        """[(gamma, beta)] per hidden layer of a normalised net ([] without norm): views of `flat` (None: the net's vector)."""
+        flat = self._vector(flat)
+        return [(flat[o:o + self.dims[i + 1]], flat[o + self.dims[i + 1]:o + 2 * self.dims[i + 1]])
+                for i, o in enumerate(self._norm_offsets)]
+
+    def mlp_views(self, flat: torch.Tensor | None = None) -> list[torch.Tensor]:
+        """Every tensor of the layers in the ORDER OF THE VECTOR: W, b (, gamma, beta) per layer."""
+        norms = self.norm_views(flat)
+        return [v for i, Wb in enumerate(self.layer_views(self._vector(flat))) for v in (*Wb, *(norms[i] if i < len(norms) else ()))]
 
     def weight(self, i: int) -> torch.Tensor:
         o, ob = self._offsets[i]
@@ -203,12 +243,15 @@ class FlatMLP(FlatNet):
 
     @torch.no_grad()
     def reset_parameters(self, seed: int | None = None) -> None:
-        """torch nn.Linear default init (kaiming-uniform weights, uniform bias)."""
+        """torch nn.Linear default init (kaiming-uniform weights, uniform bias); nn.LayerNorm's ones and zeros (no draw)."""
         gen = _generator(seed)
         for i, (W, b) in enumerate(self.layer_views(self.flat.data)):
             bound = 1.0 / math.sqrt(self.dims[i])
             W.copy_(_uniform(W.shape, bound, gen))
             b.copy_(_uniform(b.shape, bound, gen))
+        for gamma, beta in self.norm_views():
+            gamma.fill_(1.0)
+            beta.zero_()
 
     @torch.no_grad()
     def load_layers(self, layers) -> None:
@@ -230,42 +273,73 @@ class FlatMLP(FlatNet):
         if x.shape[-1] != self.dims[0]:
             raise ValueError(f"FlatMLP: input width {x.shape[-1]} != {self.dims[0]}")
         x2 = x.reshape(-1, self.dims[0])
-        out, acts = ops.mlp_forward(self.desc, self.flat.data, x2)
-        if save:
-            self._saved = (x2, acts)
+        if self.norm:
+            out, acts, kept = ops.mlp_ln_forward(self._desc, self.norm_eps, self.flat.data, x2, save=save)
+        else:
+            (out, acts), kept = ops.mlp_forward(self._desc, self.flat.data, x2), None
+        if save:   # (x, acts) of a plain net, as ever: the Fisher products read it
+            self._saved = (x2, acts, kept) if self.norm else (x2, acts)
         return out.view(*lead, self.dims[-1])
 
     def backward(self, d_out: torch.Tensor, n_split: int = 0, slabs: torch.Tensor | None = None,
                  slab_stride: int = 0) -> torch.Tensor:
         """Gradient slabs [n_split, n_param] for the inputs of the last `forward(save=True)`; `slabs` / `slab_stride`
         direct them into the slabs of a joint parameter vector."""
-        x2, acts = self._saved_forward()
-        return ops.mlp_backward(self.desc, self.flat.data, x2, acts, d_out.reshape(x2.shape[0], self.dims[-1]).contiguous(),
-                                n_split, slabs=slabs, slab_stride=slab_stride)
+        x2, acts, *kept = self._saved_forward()
+        d_out = d_out.reshape(x2.shape[0], self.dims[-1]).contiguous()
+        if self.norm:
+            return ops.mlp_ln_backward(self._desc, self.flat.data, x2, acts, kept[0], d_out, n_split, slabs=slabs,
+                                       slab_stride=slab_stride)
+        return ops.mlp_backward(self._desc, self.flat.data, x2, acts, d_out, n_split, slabs=slabs, slab_stride=slab_stride)
 
     def input_grad(self, d_out: torch.Tensor, col0: int, n_col: int, out: torch.Tensor | None = None) -> torch.Tensor:
         """Gradient [B, n_col] w.r.t. the input columns [col0, col0 + n_col) of the last `forward(save=True)`; no weight
         gradient is computed (the critic's side of a deterministic policy gradient)."""
-        x2, acts = self._saved_forward("input_grad")
-        return ops.mlp_input_grad(self.desc, self.flat.data, x2, acts, d_out.reshape(x2.shape[0], self.dims[-1]), col0, n_col,
-                                  out=out)
+        x2, acts, *kept = self._saved_forward("input_grad")
+        d_out = d_out.reshape(x2.shape[0], self.dims[-1])
+        if self.norm:
+            return ops.mlp_ln_input_grad(self._desc, self.flat.data, x2, acts, kept[0], d_out, col0, n_col, out=out)
+        return ops.mlp_input_grad(self._desc, self.flat.data, x2, acts, d_out, col0, n_col, out=out)
 
     # ---- checkpoints under the reference's key names (`ref_layer_keys`) -----------------------------------------------
-    def named_layers(self, keys, prefix: str = "", flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
+    def named_layers(self, keys, prefix: str = "", flat: torch.Tensor | None = None,
+                     norm_keys=None) -> list[tuple[str, torch.Tensor]]:
         """[(prefix + key, view)]: every layer's weight, then its bias, under `keys` = [(weight key, bias key)]; views of
-        `flat` (None: the net's own vector)."""
-        return [(prefix + k, v) for kk, Wb in zip(keys, self.layer_views(self._vector(flat))) for k, v in zip(kk, Wb)]
+        `flat` (None: the net's own vector).  `norm_keys` = [(weight key, bias key)] per hidden layer of a normalised net:
+        its gamma and beta follow the layer's bias, the order of the vector and of the reference's `state_dict()`.  A normalised
+        net refuses a call without them: its checkpoint would lack gamma and beta and still load."""
+        self._need_norm_keys("named_layers", norm_keys)
+        named = [[(prefix + k, v) for k, v in zip(kk, Wb)] for kk, Wb in zip(keys, self.layer_views(self._vector(flat)))]
+        for block, kk, gb in zip(named, norm_keys or (), self.norm_views(flat)):
+            block += [(prefix + k, v) for k, v in zip(kk, gb)]
+        return [kv for block in named for kv in block]
 
-    def export_layers(self, keys, prefix: str = "", sd: OrderedDict | None = None) -> OrderedDict:
-        """The layers as host copies under prefix + `keys`, added to `sd` (None: a new OrderedDict)."""
-        return export_views(self.named_layers(keys), prefix, sd)
+    def _need_norm_keys(self, who: str, norm_keys) -> None:
+        if len(norm_keys or ()) < len(self._norm_offsets):
+            raise ValueError(f"{type(self).__name__}.{who}: a net with norm={self.norm!r} needs norm_keys for its "
+                             f"{len(self._norm_offsets)} LayerNorms (`named_reference_layers` gives the reference's)")
 
-    def import_layers(self, sd, keys, prefix: str = "") -> None:
-        """`load_layers` from the entries of `sd` under prefix + `keys`."""
+    def named_reference_layers(self, scheme: str, prefix: str = "", flat: torch.Tensor | None = None):
+        """`named_layers` under `ref_layer_keys`' names of `scheme`; a normalised net's Linear layers sit three modules apart
+        (two with act="none") and its LayerNorms behind them, as in the reference's `MLP`."""
+        if not self.norm:
+            return self.named_layers(ref_layer_keys(self.n_layers, scheme), prefix, flat)
+        stride = 2 if self.act in ("none", None) else 3
+        return self.named_layers(ref_layer_keys(self.n_layers, scheme, stride), prefix, flat,
+                                 ref_layer_keys(self.n_layers, scheme, stride, at=1))
+
+    def export_layers(self, keys, prefix: str = "", sd: OrderedDict | None = None, norm_keys=None) -> OrderedDict:
+        """The layers as host copies under prefix + `keys` (and `norm_keys`), added to `sd` (None: a new OrderedDict)."""
+        return export_views(self.named_layers(keys, norm_keys=norm_keys), prefix, sd)
+
+    def import_layers(self, sd, keys, prefix: str = "", norm_keys=None) -> None:
+        """`load_layers` from the entries of `sd` under prefix + `keys`; gamma and beta from those under `norm_keys`."""
+        self._need_norm_keys("import_layers", norm_keys)
         self.load_layers([(sd[prefix + kw], sd[prefix + kb]) for kw, kb in keys])
+        import_views([(k, v) for kk, gb in zip(norm_keys or (), self.norm_views()) for k, v in zip(kk, gb)], sd, prefix)
 
     def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
-        return self.named_layers(ref_layer_keys(self.n_layers, self.ref_scheme), flat=flat)
+        return self.named_reference_layers(self.ref_scheme, flat=flat)
 
 
 # ---- the recurrent net (utils/net/common.py:372-458) -----------------------------------------------------------------------
@@ -396,10 +470,11 @@ class ContinuousActorDeterministic(_ContinuousNet):
     (`ops.cac_det_action`), which `forward` does NOT apply: the learners need the raw output for the backward."""
 
     def __init__(self, obs_dim: int, act_dim: int, hidden_sizes=(64, 64), max_action: float = 1.0, act: str = "relu",
-                 device: str | torch.device = "cuda", seed: int | None = None, storage: torch.Tensor | None = None) -> None:
+                 device: str | torch.device = "cuda", seed: int | None = None, storage: torch.Tensor | None = None,
+                 norm: str | None = None, norm_eps: float = 1e-5) -> None:
         ops.cac_check(int(act_dim))
         super().__init__([int(obs_dim), *[int(h) for h in hidden_sizes], int(act_dim)], act, device=device, seed=seed,
-                         storage=storage)
+                         storage=storage, norm=norm, norm_eps=norm_eps)
         self.max_action = float(max_action)
         self.act_dim = int(act_dim)
 
@@ -408,9 +483,10 @@ class ContinuousCritic(_ContinuousNet):
     """continuous.py:102-175: rows [obs | act] -> hidden ... -> 1."""
 
     def __init__(self, obs_dim: int, act_dim: int, hidden_sizes=(64, 64), act: str = "relu",
-                 device: str | torch.device = "cuda", seed: int | None = None, storage: torch.Tensor | None = None) -> None:
+                 device: str | torch.device = "cuda", seed: int | None = None, storage: torch.Tensor | None = None,
+                 norm: str | None = None, norm_eps: float = 1e-5) -> None:
         super().__init__([int(obs_dim) + int(act_dim), *[int(h) for h in hidden_sizes], 1], act, device=device, seed=seed,
-                         storage=storage)
+                         storage=storage, norm=norm, norm_eps=norm_eps)
         self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
 
 
@@ -423,12 +499,14 @@ class ContinuousActorProbabilistic(_ContinuousNet):
 
     def __init__(self, obs_dim: int, act_dim: int, hidden_sizes=(64, 64), max_action: float = 1.0, unbounded: bool = False,
                  conditioned_sigma: bool = False, act: str = "relu", device: str | torch.device = "cuda",
-                 seed: int | None = None, storage: torch.Tensor | None = None) -> None:
+                 seed: int | None = None, storage: torch.Tensor | None = None, norm: str | None = None,
+                 norm_eps: float = 1e-5) -> None:
         ops.cac_check(int(act_dim))
         Ad, cond = int(act_dim), bool(conditioned_sigma)
         dims = [int(obs_dim), *[int(h) for h in hidden_sizes], 2 * Ad if cond else Ad]
         # the layers view the head of the vector, sigma_param its tail
-        super().__init__(dims, act, device=device, seed=seed, storage=storage, n_extra=0 if cond else Ad)
+        super().__init__(dims, act, device=device, seed=seed, storage=storage, n_extra=0 if cond else Ad, norm=norm,
+                         norm_eps=norm_eps)
         self.flat.data[self.n_mlp_params:].zero_()
         if unbounded and not np.isclose(max_action, 1.0):
             max_action = 1.0   # continuous.py:208-210: discarded when unbounded
@@ -443,7 +521,7 @@ class ContinuousActorProbabilistic(_ContinuousNet):
         """The layers, whole, then `sigma_param` where the vector has it: the vector's order, which is not the checkpoint's."""
         flat = self._vector(flat)
         tail = [] if self.conditioned_sigma else [flat[self.n_mlp_params:].view(self.act_dim, 1)]
-        return [v for Wb in self.layer_views(flat) for v in Wb] + tail
+        return self.mlp_views(flat) + tail
 
     def reference_named_views(self, flat: torch.Tensor | None = None) -> list[tuple[str, torch.Tensor]]:
         """The reference's state_dict order: a module's own parameters come before its submodules', so `sigma_param` leads;
@@ -1673,7 +1751,7 @@ class IntrinsicCuriosityModule(FlatNet):
         """Three `MLP`s: `ref_layer_keys`' "seq" under `<name>.model.`."""
         flat, o = self._vector(flat), self._offs
         return [kv for k, (name, m) in enumerate(zip(("feature_net", "forward_model", "inverse_model"), self.nets))
-                for kv in m.named_layers(ref_layer_keys(m.n_layers, "seq"), f"{name}.model.", flat[o[k]:o[k + 1]])]
+                for kv in m.named_reference_layers("seq", f"{name}.model.", flat[o[k]:o[k + 1]])]
 
 
 class RunningMeanStd:
