@@ -467,6 +467,14 @@ int tsm_mpe_spread_step(const tsm_mpe_cfg *cfg_host, uint64_t seed, uint64_t *ep
                         int32_t *steps, float *obs_next_out, float *obs_cur_out, float *rew_out,
                         uint8_t *terminated_out, uint8_t *truncated_out, uint8_t *done_env_out,
                         int auto_reset, uint64_t *rng_tick, uint64_t rng_tick_inc, void *stream);
+/* The same step under Box actions (simple_spread_v3(continuous_actions=True)): act f32 [n_env][N][5], MPE's continuous form
+ * signed to agree with the discrete table: force = ((a[2] - a[1]) accel, (a[4] - a[3]) accel); a[0] is ignored and nothing is
+ * clamped (bounding is the policy's map_action).  A one-hot act gives tsm_mpe_spread_step's bits. */
+int tsm_mpe_spread_step_box(const tsm_mpe_cfg *cfg_host, uint64_t seed, uint64_t *episode_ctr,
+                            const float *act, float *agent_pos, float *agent_vel, float *landmark_pos,
+                            int32_t *steps, float *obs_next_out, float *obs_cur_out, float *rew_out,
+                            uint8_t *terminated_out, uint8_t *truncated_out, uint8_t *done_env_out,
+                            int auto_reset, uint64_t *rng_tick, uint64_t rng_tick_inc, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Persistent rollout  [a4 + a7 + a8 fused; SURVEY 8f-1]
@@ -562,6 +570,11 @@ int tsm_mpe_tag_step(const tsm_mpe_tag_cfg *cfg_host, uint64_t seed, uint64_t *e
                      float *agent_pos, float *agent_vel, float *landmark_pos, int32_t *steps, float *obs_next_out,
                      float *obs_cur_out, float *rew_out, uint8_t *terminated_out, uint8_t *truncated_out,
                      uint8_t *done_env_out, int auto_reset, uint64_t *rng_tick, uint64_t rng_tick_inc, void *stream);
+/* ... under Box actions, act f32 [n_env][NA][5] decoded as tsm_mpe_spread_step_box does, with the agent's own accel. */
+int tsm_mpe_tag_step_box(const tsm_mpe_tag_cfg *cfg_host, uint64_t seed, uint64_t *episode_ctr, const float *act,
+                         float *agent_pos, float *agent_vel, float *landmark_pos, int32_t *steps, float *obs_next_out,
+                         float *obs_cur_out, float *rew_out, uint8_t *terminated_out, uint8_t *truncated_out,
+                         uint8_t *done_env_out, int auto_reset, uint64_t *rng_tick, uint64_t rng_tick_inc, void *stream);
 int tsm_u64_add(uint64_t *counter, uint64_t inc, void *stream);
 
 /* Persistent rollout for simple_tag under GROUPED policies  [a4 + a6 + a7 + a8 fused for BASELINE configs[4]]

@@ -201,13 +201,14 @@ class SACPolicy(_ContinuousPolicy):
     def _deterministic(self) -> bool:
         return bool(self.deterministic_eval and not self.is_within_training_step)
 
-    def _sample(self, x: torch.Tensor, z: torch.Tensor | None = None):
-        """The actor on rows x -> (raw, act [B, Ad], logp [B]); z None: a draw, or the mode when deterministic."""
+    def _sample(self, x: torch.Tensor, z: torch.Tensor | None = None, offset_dev: torch.Tensor | None = None, row_offset: int = 0):
+        """The actor on rows x -> (raw, act [B, Ad], logp [B]); z None: a draw, or the mode when deterministic.  offset_dev: the
+        draw's Philox counter comes from that device word (a captured collect advances it), not from the policy's own."""
         raw = FlatMLP.forward(self.actor, x, save=False)
         if z is None and not self._deterministic:
             n = x.shape[0] * self.act_dim
-            z = ops.cac_normal(n, self.seed, offset=self._sample_ctr, device=x.device).view(x.shape[0], self.act_dim)
-            self._sample_ctr += n
+            z = ops.cac_normal(n, self.seed, offset=sample_counter(self, n, row_offset * self.act_dim, offset_dev),
+                               offset_dev=offset_dev, device=x.device).view(x.shape[0], self.act_dim)
         act, logp = ops.sac_action(raw, z, self.actor.max_action, self.actor.unbounded, sigma_param=self.actor.sigma_param)
         return raw, act, logp
 
@@ -219,7 +220,7 @@ class SACPolicy(_ContinuousPolicy):
 
     def act_device(self, obs: torch.Tensor, out: dict | None = None, offset_dev: torch.Tensor | None = None,
                    row_offset: int = 0) -> dict:
-        _, act, logp = self._sample(obs.reshape(-1, self.actor.dims[0]))
+        _, act, logp = self._sample(obs.reshape(-1, self.actor.dims[0]), offset_dev=offset_dev, row_offset=row_offset)
         return self._emit(act, 0.0, out, offset_dev, row_offset)
 
 

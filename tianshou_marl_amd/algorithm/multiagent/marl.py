@@ -117,6 +117,10 @@ class MultiAgentPolicy(nn.Module):
         shared = self.shared_policy
         if shared is not None:
             return shared.act_device(obs, out=out, offset_dev=offset_dev)
+        if any(hasattr(getattr(p, "action_space", None), "low") for p in self._agent_policies.values()):
+            # the column copies below move one i32 action per agent; a Box member would also need its env_act columns
+            raise NotImplementedError("MultiAgentPolicy.act_device: independent or grouped member policies with Box actions are "
+                                      "not built; one shared policy (parameter sharing) forwards in a single call")
         E, N = obs.shape[0], obs.shape[1]
         if out is None:
             dev = obs.device

@@ -145,7 +145,7 @@ class GenericPPO(PPO):
         act, logp, env_act = ops.gauss_sample(
             raw, self.seed, offset=sample_counter(self, rows.shape[0], row_offset, offset_dev), offset_dev=offset_dev,
             deterministic=greedy, bound_method=self.action_bound_method, low=self._low_dev, high=self._high_dev,
-            want_env_act=True, out=(out["act"], out["logp"]) if out is not None else None, **self._gauss_kw())
+            want_env_act=True, out=(out["act"], out["logp"], out.get("env_act")) if out is not None else None, **self._gauss_kw())
         if out is not None:
             out["value"].copy_(value)
             out["env_act"] = env_act

@@ -45,8 +45,12 @@ constexpr int kStepThreads = 128;  // >= kEnvPerBlock * kMpeMaxN agent lanes
 //   rew f32, terminated u8 (always 0 here), truncated u8;  done_env [n_env] u8
 // auto_reset != 0: finished envs are re-initialised in place (Collector's env.reset(env_id=done ids),
 // /root/reference/tianshou/data/collector.py:971).
+// Act = int32_t: one discrete action per agent, act [n_env][N].  Act = float: Box actions, act [n_env][N][5] (mpe_box_action_force);
+// the workgroup's n_here * N * 5 contiguous floats come in through LDS beside the state (s_act, behind s_cur) and each agent
+// lane reads its row there.  Everything behind the move is the same code for both.
+template <typename Act>
 __global__ __launch_bounds__(kStepThreads) void mpe_step_kernel(
-    MpeCfg c, uint64_t seed, uint64_t *episode_ctr, const int32_t *__restrict__ act, float *apos, float *avel,
+    MpeCfg c, uint64_t seed, uint64_t *episode_ctr, const Act *__restrict__ act, float *apos, float *avel,
     float *lpos, int32_t *steps, float *obs_next, float *obs_cur, float *rew, uint8_t *term, uint8_t *trunc,
     uint8_t *done_env, int auto_reset, uint64_t *tick, uint64_t tick_inc) {
     extern __shared__ float sm[];
@@ -67,13 +71,24 @@ __global__ __launch_bounds__(kStepThreads) void mpe_step_kernel(
         s_av[i] = avel[(int64_t)e0 * st + i];
         s_lp[i] = lpos[(int64_t)e0 * st + i];
     }
+    if constexpr (kMpeBox<Act>)
+        mpe_stage_box_actions(act + (int64_t)e0 * N * kMpeBoxDim, s_cur + kEnvPerBlock * row, n_here * N * kMpeBoxDim, threadIdx.x,
+                              kStepThreads);
     __syncthreads();
     const int lane_rows = n_here * N;
     const int el = threadIdx.x / N, i = threadIdx.x - el * N;  // agent lane -> (env, agent)
     const bool live = threadIdx.x < lane_rows;
     const int e = e0 + el;
     float npx = 0.f, npy = 0.f, nvx = 0.f, nvy = 0.f;
-    if (live) mpe_agent_move(c, s_ap + el * st, s_av + el * st, i, act[(int64_t)e * N + i], npx, npy, nvx, nvy);
+    if constexpr (kMpeBox<Act>) {
+        if (live) {
+            float fx, fy;
+            mpe_box_action_force(s_cur + kEnvPerBlock * row + threadIdx.x * kMpeBoxDim, c.accel, fx, fy);
+            mpe_agent_move_force(c, s_ap + el * st, s_av + el * st, i, fx, fy, npx, npy, nvx, nvy);
+        }
+    } else {
+        if (live) mpe_agent_move(c, s_ap + el * st, s_av + el * st, i, act[(int64_t)e * N + i], npx, npy, nvx, nvy);
+    }
     __syncthreads();
     if (live) {
         s_ap[el * st + 2 * i] = npx; s_ap[el * st + 2 * i + 1] = npy;
@@ -160,22 +175,44 @@ TSM_EXPORT int tsm_mpe_spread_reset(const tsm_mpe_cfg *cfg_host, uint64_t seed, 
     return TSM_OK;
 }
 
-TSM_EXPORT int tsm_mpe_spread_step(const tsm_mpe_cfg *cfg_host, uint64_t seed, uint64_t *episode_ctr,
-                                   const int32_t *act, float *agent_pos, float *agent_vel, float *landmark_pos,
-                                   int32_t *steps, float *obs_next_out, float *obs_cur_out, float *rew_out,
-                                   uint8_t *terminated_out, uint8_t *truncated_out, uint8_t *done_env_out,
-                                   int auto_reset, uint64_t *rng_tick, uint64_t rng_tick_inc, void *stream) {
+// Both step entries: the checks and the launch of the kernel for their action kind.  Box actions add their LDS staging block
+// ([16][N][5] floats, at most 2560 bytes) behind the two observation blocks.
+template <typename Act>
+static int mpe_step_launch(const char *name, const tsm_mpe_cfg *cfg_host, uint64_t seed, uint64_t *episode_ctr, const Act *act,
+                           float *agent_pos, float *agent_vel, float *landmark_pos, int32_t *steps, float *obs_next_out,
+                           float *obs_cur_out, float *rew_out, uint8_t *terminated_out, uint8_t *truncated_out,
+                           uint8_t *done_env_out, int auto_reset, uint64_t *rng_tick, uint64_t rng_tick_inc, void *stream) {
     MpeCfg c;
     if (int rc = tsm_mpe_check_cfg(cfg_host, &c)) return rc;
     TSM_REQUIRE(episode_ctr && act && agent_pos && agent_vel && landmark_pos && steps && obs_next_out && rew_out &&
                     terminated_out && truncated_out && done_env_out,
-                "tsm_mpe_spread_step: null pointer");
-    const size_t shmem = ((size_t)kEnvPerBlock * (3 * 2 * c.N + c.N + 1) + (size_t)2 * kEnvPerBlock * c.N * c.obs_dim) *
-                         sizeof(float);
-    hipLaunchKernelGGL(mpe_step_kernel, dim3((unsigned)ceil_div(c.n_env, kEnvPerBlock)), dim3(kStepThreads), shmem,
+                "%s: null pointer", name);
+    const size_t shmem = ((size_t)kEnvPerBlock * (3 * 2 * c.N + c.N + 1) + (size_t)2 * kEnvPerBlock * c.N * c.obs_dim +
+                          (kMpeBox<Act> ? (size_t)kEnvPerBlock * c.N * kMpeBoxDim : 0)) * sizeof(float);
+    hipLaunchKernelGGL(mpe_step_kernel<Act>, dim3((unsigned)ceil_div(c.n_env, kEnvPerBlock)), dim3(kStepThreads), shmem,
                        tsm_stream(stream), c, seed, episode_ctr, act, agent_pos, agent_vel, landmark_pos, steps,
                        obs_next_out, obs_cur_out, rew_out, terminated_out, truncated_out, done_env_out, auto_reset,
                        rng_tick, rng_tick_inc);
     TSM_LAUNCH_CHECK();
     return TSM_OK;
+}
+
+TSM_EXPORT int tsm_mpe_spread_step(const tsm_mpe_cfg *cfg_host, uint64_t seed, uint64_t *episode_ctr,
+                                   const int32_t *act, float *agent_pos, float *agent_vel, float *landmark_pos,
+                                   int32_t *steps, float *obs_next_out, float *obs_cur_out, float *rew_out,
+                                   uint8_t *terminated_out, uint8_t *truncated_out, uint8_t *done_env_out,
+                                   int auto_reset, uint64_t *rng_tick, uint64_t rng_tick_inc, void *stream) {
+    return mpe_step_launch("tsm_mpe_spread_step", cfg_host, seed, episode_ctr, act, agent_pos, agent_vel, landmark_pos, steps,
+                           obs_next_out, obs_cur_out, rew_out, terminated_out, truncated_out, done_env_out, auto_reset,
+                           rng_tick, rng_tick_inc, stream);
+}
+
+TSM_EXPORT int tsm_mpe_spread_step_box(const tsm_mpe_cfg *cfg_host, uint64_t seed, uint64_t *episode_ctr,
+                                       const float *act, float *agent_pos, float *agent_vel, float *landmark_pos,
+                                       int32_t *steps, float *obs_next_out, float *obs_cur_out, float *rew_out,
+                                       uint8_t *terminated_out, uint8_t *truncated_out, uint8_t *done_env_out,
+                                       int auto_reset, uint64_t *rng_tick, uint64_t rng_tick_inc, void *stream) {
+    return mpe_step_launch("tsm_mpe_spread_step_box", cfg_host, seed, episode_ctr, act, agent_pos, agent_vel, landmark_pos, steps,
+                           obs_next_out, obs_cur_out, rew_out, terminated_out, truncated_out, done_env_out, auto_reset,
+                           rng_tick, rng_tick_inc, stream);
 }

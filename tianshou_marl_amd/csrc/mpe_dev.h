@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "philox.h"
 
 constexpr int kMpeMaxN = 8;
@@ -132,6 +134,23 @@ __device__ __forceinline__ float mpe_action_force(const MpeCfg &c, int act, int 
     return axis == 0 ? (act == 1 ? -1.f : (act == 2 ? 1.f : 0.f)) * c.accel : (act == 3 ? -1.f : (act == 4 ? 1.f : 0.f)) * c.accel;
 }
 
+// The action force of a Box action a[5] (MPE's continuous form; simple_tag hands its per-agent accel): the difference of the two
+// components of an axis, signed to agree with the discrete table {noop, -x, +x, -y, +y}; a[0] is ignored and nothing is clamped
+// (bounding is the policy's map_action).  On a one-hot a both differences are exactly -1, 0 or 1 and the products are the
+// discrete table's: the same bits as mpe_action_force / tag_action_force.
+__device__ __forceinline__ void mpe_box_action_force(const float *a, float accel, float &fx, float &fy) {
+    fx = (a[2] - a[1]) * accel;
+    fy = (a[4] - a[3]) * accel;
+}
+constexpr int kMpeBoxDim = 5;
+template <typename Act> constexpr bool kMpeBox = std::is_same<Act, float>::value;  // the step kernels' action kind: f32 [5], else one i32
+
+// Box actions of a workgroup's envs: n contiguous floats ([n_here][N][5]) from HBM into LDS with the strided cooperative loop
+// the state comes in by (a lane reading its own row would stride 20 bytes: uncoalesced).  The caller's barrier follows.
+__device__ __forceinline__ void mpe_stage_box_actions(const float *__restrict__ g_act, float *s_act, int n, int tid, int n_thread) {
+    for (int k = tid; k < n; k += n_thread) s_act[k] = g_act[k];
+}
+
 // New position / velocity of agent i after one step (action force + soft contact forces, summed over the other
 // agents in increasing index; damping; optional speed clamp; explicit Euler).  rollout_rows.hip evaluates the pair forces
 // on other lanes (mpe_pair_force) and folds them in the same order: the same bits.
@@ -142,6 +161,22 @@ __device__ __forceinline__ void mpe_agent_move(const MpeCfg &c, const float *ap,
     const float vx = av[2 * i], vy = av[2 * i + 1];
     float fx = mpe_action_force(c, act, 0);
     float fy = mpe_action_force(c, act, 1);
+#pragma unroll
+    for (int j = 0; j < kMpeMaxN; ++j) {
+        if (j >= c.N) break;  // wave-uniform
+        float sx, sy;
+        if (j != i && mpe_pair_force(c, px, py, p.x[j], p.y[j], i, j, sx, sy)) { fx += sx; fy += sy; }
+    }
+    mpe_integrate(c, px, py, vx, vy, fx, fy, npx, npy, nvx, nvy);
+}
+// ... under a given action force (fx, fy) (Box actions: mpe_box_action_force): the same additions in the same order.  Stated
+// beside mpe_agent_move, not beneath it: routing the discrete move through this form (by value, by functor, or with the loads
+// hoisted) changed the register allocation of the discrete step kernel, whose instructions are to stay what they were.
+__device__ __forceinline__ void mpe_agent_move_force(const MpeCfg &c, const float *ap, const float *av, int i, float fx, float fy,
+                                                     float &npx, float &npy, float &nvx, float &nvy) {
+    const MpePos p = mpe_load_pos(c, ap);
+    const float px = ap[2 * i], py = ap[2 * i + 1];
+    const float vx = av[2 * i], vy = av[2 * i + 1];
 #pragma unroll
     for (int j = 0; j < kMpeMaxN; ++j) {
         if (j >= c.N) break;  // wave-uniform

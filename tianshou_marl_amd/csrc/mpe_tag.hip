@@ -46,8 +46,11 @@ constexpr int kTagThreads = kTagEnvPerBlock * kMaxAgents;  // one lane per (env,
 // 16 envs is staged in LDS, every agent lane sums the soft contact forces it receives from the other entities in
 // increasing entity index -- the order in which the serial pair loop (a < b) accumulates into f[i] -- so the result
 // is bit-identical to the pair formulation; observation rows leave through LDS as coalesced writes.
+// Act = int32_t: act [n_env][NA]; Act = float: Box actions act [n_env][NA][5], staged through LDS (s_act, behind s_next) as in
+// mpe_step_kernel, decoded with the agent's own accel.
+template <typename Act>
 __global__ __launch_bounds__(kTagThreads) void tag_step_kernel(
-    TagCfg c, uint64_t seed, uint64_t *episode_ctr, const int32_t *__restrict__ act, float *apos, float *avel,
+    TagCfg c, uint64_t seed, uint64_t *episode_ctr, const Act *__restrict__ act, float *apos, float *avel,
     float *lpos, int32_t *steps, float *obs_next, float *obs_cur, float *rew, uint8_t *term, uint8_t *trunc,
     uint8_t *done_env, int auto_reset, uint64_t *tick, uint64_t tick_inc) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -69,6 +72,9 @@ __global__ __launch_bounds__(kTagThreads) void tag_step_kernel(
         s_av[k] = avel[(int64_t)e0 * st + k];
     }
     for (int k = threadIdx.x; k < n_here * lst; k += kTagThreads) s_lp[k] = lpos[(int64_t)e0 * lst + k];
+    if constexpr (kMpeBox<Act>)
+        mpe_stage_box_actions(act + (int64_t)e0 * NA * kMpeBoxDim, s_next + kTagEnvPerBlock * row, n_here * NA * kMpeBoxDim,
+                              threadIdx.x, kTagThreads);
     __syncthreads();
     const int el = threadIdx.x / NA, i = threadIdx.x - el * NA;  // agent lane -> (env, agent)
     const bool live = threadIdx.x < n_here * NA;
@@ -76,7 +82,15 @@ __global__ __launch_bounds__(kTagThreads) void tag_step_kernel(
     const float *ap = s_ap + el * st, *av = s_av + el * st, *lp = s_lp + el * lst;
     const bool is_adv = i < c.n_adv;
     float npx = 0.f, npy = 0.f, nvx = 0.f, nvy = 0.f;
-    if (live) tag_agent_move(c, ap, av, lp, i, act[(int64_t)e * NA + i], npx, npy, nvx, nvy);
+    if constexpr (kMpeBox<Act>) {
+        if (live) {
+            float fx, fy;
+            mpe_box_action_force(s_next + kTagEnvPerBlock * row + threadIdx.x * kMpeBoxDim, is_adv ? c.adv_accel : c.good_accel, fx, fy);
+            tag_agent_move_force(c, ap, av, lp, i, fx, fy, npx, npy, nvx, nvy);
+        }
+    } else {
+        if (live) tag_agent_move(c, ap, av, lp, i, act[(int64_t)e * NA + i], npx, npy, nvx, nvy);
+    }
     __syncthreads();
     if (live) {
         s_ap[el * st + 2 * i] = npx; s_ap[el * st + 2 * i + 1] = npy;
@@ -171,23 +185,46 @@ TSM_EXPORT int tsm_mpe_tag_reset(const tsm_mpe_tag_cfg *cfg_host, uint64_t seed,
     return TSM_OK;
 }
 
-TSM_EXPORT int tsm_mpe_tag_step(const tsm_mpe_tag_cfg *cfg_host, uint64_t seed, uint64_t *episode_ctr,
-                                const int32_t *act, float *agent_pos, float *agent_vel, float *landmark_pos,
-                                int32_t *steps, float *obs_next_out, float *obs_cur_out, float *rew_out,
-                                uint8_t *terminated_out, uint8_t *truncated_out, uint8_t *done_env_out, int auto_reset,
-                                uint64_t *rng_tick, uint64_t rng_tick_inc, void *stream) {
+// Both step entries: the checks and the launch of the kernel for their action kind.  Box actions add their LDS staging block
+// ([16][NA][5] floats, at most 2560 bytes) behind the observation block.
+template <typename Act>
+static int tag_step_launch(const char *name, const tsm_mpe_tag_cfg *cfg_host, uint64_t seed, uint64_t *episode_ctr, const Act *act,
+                           float *agent_pos, float *agent_vel, float *landmark_pos, int32_t *steps, float *obs_next_out,
+                           float *obs_cur_out, float *rew_out, uint8_t *terminated_out, uint8_t *truncated_out,
+                           uint8_t *done_env_out, int auto_reset, uint64_t *rng_tick, uint64_t rng_tick_inc, void *stream) {
     TagCfg c;
     if (int rc = tsm_mpe_tag_check_cfg(cfg_host, &c)) return rc;
     TSM_REQUIRE(episode_ctr && act && agent_pos && agent_vel && landmark_pos && steps && obs_next_out && rew_out &&
                     terminated_out && truncated_out && done_env_out,
-                "tsm_mpe_tag_step: null pointer");
+                "%s: null pointer", name);
     const int NA = c.n_adv + c.n_good;
     const size_t shmem = sizeof(float) * (size_t)kTagEnvPerBlock * (4 * NA + (c.n_obst > 0 ? 2 * c.n_obst : 2) + NA + 1 +
-                                                                     NA * c.obs_dim) + sizeof(uint64_t) * (kTagEnvPerBlock + 1);
-    hipLaunchKernelGGL(tag_step_kernel, dim3((unsigned)ceil_div(c.n_env, kTagEnvPerBlock)), dim3(kTagThreads), shmem,
+                                                                     NA * c.obs_dim + (kMpeBox<Act> ? NA * kMpeBoxDim : 0)) +
+                         sizeof(uint64_t) * (kTagEnvPerBlock + 1);
+    hipLaunchKernelGGL(tag_step_kernel<Act>, dim3((unsigned)ceil_div(c.n_env, kTagEnvPerBlock)), dim3(kTagThreads), shmem,
                        tsm_stream(stream), c, seed,
                        episode_ctr, act, agent_pos, agent_vel, landmark_pos, steps, obs_next_out, obs_cur_out, rew_out,
                        terminated_out, truncated_out, done_env_out, auto_reset, rng_tick, rng_tick_inc);
     TSM_LAUNCH_CHECK();
     return TSM_OK;
+}
+
+TSM_EXPORT int tsm_mpe_tag_step(const tsm_mpe_tag_cfg *cfg_host, uint64_t seed, uint64_t *episode_ctr,
+                                const int32_t *act, float *agent_pos, float *agent_vel, float *landmark_pos,
+                                int32_t *steps, float *obs_next_out, float *obs_cur_out, float *rew_out,
+                                uint8_t *terminated_out, uint8_t *truncated_out, uint8_t *done_env_out, int auto_reset,
+                                uint64_t *rng_tick, uint64_t rng_tick_inc, void *stream) {
+    return tag_step_launch("tsm_mpe_tag_step", cfg_host, seed, episode_ctr, act, agent_pos, agent_vel, landmark_pos, steps,
+                           obs_next_out, obs_cur_out, rew_out, terminated_out, truncated_out, done_env_out, auto_reset, rng_tick,
+                           rng_tick_inc, stream);
+}
+
+TSM_EXPORT int tsm_mpe_tag_step_box(const tsm_mpe_tag_cfg *cfg_host, uint64_t seed, uint64_t *episode_ctr,
+                                    const float *act, float *agent_pos, float *agent_vel, float *landmark_pos,
+                                    int32_t *steps, float *obs_next_out, float *obs_cur_out, float *rew_out,
+                                    uint8_t *terminated_out, uint8_t *truncated_out, uint8_t *done_env_out, int auto_reset,
+                                    uint64_t *rng_tick, uint64_t rng_tick_inc, void *stream) {
+    return tag_step_launch("tsm_mpe_tag_step_box", cfg_host, seed, episode_ctr, act, agent_pos, agent_vel, landmark_pos, steps,
+                           obs_next_out, obs_cur_out, rew_out, terminated_out, truncated_out, done_env_out, auto_reset, rng_tick,
+                           rng_tick_inc, stream);
 }

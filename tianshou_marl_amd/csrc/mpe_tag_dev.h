@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mpe_dev.h"  // the Box action decode (mpe_box_action_force) and its LDS staging, shared with simple_spread
 #include "philox.h"
 
 constexpr int kTagMaxAgents = 8, kTagMaxObst = 4;
@@ -130,18 +131,23 @@ __device__ __forceinline__ void tag_integrate(const TagCfg &c, int i, float px, 
     npy = py + nvy * c.dt;
 }
 
-// One step of agent i (action a): soft contact forces from every other entity in increasing entity index -- the order in
-// which the serial pair loop (lo < hi) accumulates into f[i] -- then damping, speed clamp and integration.
-__device__ __forceinline__ void tag_agent_move(const TagCfg &c, const float *ap, const float *av, const float *lp, int i,
-                                               int a, float &npx, float &npy, float &nvx, float &nvy) {
+// One step of agent i under the action force (fx, fy): soft contact forces from every other entity in increasing entity index --
+// the order in which the serial pair loop (lo < hi) accumulates into f[i] -- then damping, speed clamp and integration.
+__device__ __forceinline__ void tag_agent_move_force(const TagCfg &c, const float *ap, const float *av, const float *lp, int i,
+                                                     float fx, float fy, float &npx, float &npy, float &nvx, float &nvy) {
     const int NE = c.n_adv + c.n_good + c.n_obst;
-    float fx, fy;
-    tag_action_force(c, i, a, fx, fy);
     for (int j = 0; j < NE; ++j) {  // wave-uniform trip count
         float sx, sy;
         if (j != i && tag_pair_force(c, ap, lp, i, j, sx, sy)) { fx += sx; fy += sy; }
     }
     tag_integrate(c, i, ap[2 * i], ap[2 * i + 1], av[2 * i], av[2 * i + 1], fx, fy, npx, npy, nvx, nvy);
+}
+// ... under the discrete action a
+__device__ __forceinline__ void tag_agent_move(const TagCfg &c, const float *ap, const float *av, const float *lp, int i,
+                                               int a, float &npx, float &npy, float &nvx, float &nvy) {
+    float fx, fy;
+    tag_action_force(c, i, a, fx, fy);
+    tag_agent_move_force(c, ap, av, lp, i, fx, fy, npx, npy, nvx, nvy);
 }
 
 // Own reward terms of agent i on the NEW positions (ap) -- a good agent: -10 per adversary touching it, minus the boundary

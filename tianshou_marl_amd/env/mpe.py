@@ -6,7 +6,8 @@ same vector-env contract (`len(env)`, `reset(env_id)`, `step(action, id)`, `acti
 `seed`, `close`), same per-agent data (obs per agent, reward list, terminated/truncated lists), but the
 joint state of every env lives in HBM and the AoS dict-of-agents is never materialised on the host.
 Two call styles:
-  * device path:  `reset_device()` / `step_device(act[n_env, N] i32)` -> HBM tensors (used by the Collector)
+  * device path:  `reset_device()` / `step_device(act[n_env, N] i32)` -> HBM tensors (used by the Collector);
+    with `continuous_actions=True`: `step_device(act[n_env, N, 5] f32)`, MPE's Box(0, 1, (5,)) form (csrc/mpe_dev.h)
   * reference style: `reset(env_id)` / `step(action, id)` -> numpy, obs as the parallel-mode dict layout.
 Dynamics follow the published MPE spec; parity with pettingzoo itself is UNPINNED (pettingzoo is neither
 in the reference tree nor installed) -- see csrc/mpe.hip and DESIGN.md.
@@ -22,13 +23,38 @@ from .._abi import call, ptr, stream_ptr, tsm_mpe_cfg
 from .spaces import Box, Discrete
 
 
+BOX_ACT_DIM = 5   # MPE's continuous action: [noop, -x, +x, -y, +y] components in [0, 1]
+
+
+def box_actions(act: torch.Tensor, n_env: int, n_agent: int) -> torch.Tensor:
+    """`step_device`'s argument check of a continuous_actions=True env: f32 [n_env, N, 5] or [n_env * N, 5], contiguous in HBM."""
+    if act.dtype != torch.float32:
+        raise ValueError(f"step_device: a continuous_actions=True env takes float32 Box actions [n_env, N, {BOX_ACT_DIM}], "
+                         f"got {act.dtype}")
+    if tuple(act.shape) not in ((n_env, n_agent, BOX_ACT_DIM), (n_env * n_agent, BOX_ACT_DIM)):
+        raise ValueError(f"step_device: continuous_actions=True actions must be [{n_env}, {n_agent}, {BOX_ACT_DIM}] or "
+                         f"[{n_env * n_agent}, {BOX_ACT_DIM}], got {list(act.shape)}")
+    if not act.is_contiguous() or not act.is_cuda:
+        raise ValueError("step_device: continuous_actions=True actions must be a contiguous device tensor")
+    return act
+
+
+def host_actions(env, action) -> torch.Tensor:
+    """The numpy `step()`'s actions on the device: i32 [n_env, N], or f32 [n_env, N, 5] for a continuous_actions=True env."""
+    if env.continuous_actions:
+        a = np.asarray(action, np.float32).reshape(env.env_num, env.n_agent, BOX_ACT_DIM)
+        return torch.as_tensor(a).to(env.device).contiguous()
+    return torch.as_tensor(np.asarray(action).reshape(env.env_num, env.n_agent)).to(env.device, torch.int32)
+
+
 class DeviceSimpleSpreadVectorEnv:
     """simple_spread_v3(N, local_ratio=0.5, max_cycles=25, continuous_actions=False) x n_env on one GPU."""
 
     is_async = False
 
     def __init__(self, n_env: int, n_agent: int = 3, max_cycles: int = 25, local_ratio: float = 0.5,
-                 device: str | torch.device = "cuda", seed: int = 0, auto_reset: bool = True) -> None:
+                 device: str | torch.device = "cuda", seed: int = 0, auto_reset: bool = True,
+                 continuous_actions: bool = False) -> None:
         self.env_num = int(n_env)
         self.n_agent = int(n_agent)
         self.obs_dim = 6 * self.n_agent
@@ -40,6 +66,10 @@ class DeviceSimpleSpreadVectorEnv:
         self.agent_idx = {a: i for i, a in enumerate(self.agents)}
         self.observation_space = Box(-np.inf, np.inf, (self.obs_dim,))
         self.action_space = [Discrete(self.n_act) for _ in range(self.env_num)]
+        self.continuous_actions = bool(continuous_actions)
+        if self.continuous_actions:  # force = ((a[2] - a[1]) accel, (a[4] - a[3]) accel); the kernel does not clamp
+            self.act_dim = BOX_ACT_DIM
+            self.action_space = [Box(0.0, 1.0, (BOX_ACT_DIM,)) for _ in range(self.env_num)]
         self._cfg = tsm_mpe_cfg(self.env_num, self.n_agent, self.max_cycles, 0, 0.1, 0.25, 100.0, 1e-3, 0.15, 0.05,
                                 5.0, -1.0, float(local_ratio))
         self._seed = int(seed)
@@ -86,13 +116,16 @@ class DeviceSimpleSpreadVectorEnv:
         return self.obs_cur
 
     def step_device(self, act: torch.Tensor, rng_tick_inc: int = 0):
-        """One joint step.  act i32 [n_env, N].  Returns (obs_next, rew, terminated, truncated, done_env) and
+        """One joint step.  act i32 [n_env, N] (continuous_actions: f32 [n_env, N, 5]).  Returns (obs_next, rew, terminated, truncated, done_env) and
         flips `self.obs_cur` to the next policy input (reset observation where an episode finished and
         auto_reset is on); the previous `obs_cur` tensor keeps its contents."""
-        if act.dtype != torch.int32:
+        entry = "tsm_mpe_spread_step"
+        if self.continuous_actions:
+            act, entry = box_actions(act, self.env_num, self.n_agent), "tsm_mpe_spread_step_box"
+        elif act.dtype != torch.int32:
             raise ValueError("step_device: act must be int32")
         self._pp ^= 1
-        call("tsm_mpe_spread_step", C.byref(self._cfg), self._seed, ptr(self.episode_ctr), ptr(act.contiguous()),
+        call(entry, C.byref(self._cfg), self._seed, ptr(self.episode_ctr), ptr(act.contiguous()),
              ptr(self.agent_pos), ptr(self.agent_vel), ptr(self.landmark_pos), ptr(self.steps), ptr(self.obs_next),
              ptr(self.obs_cur), ptr(self.rew), ptr(self.terminated), ptr(self.truncated), ptr(self.done_env),
              int(self.auto_reset), ptr(self.rng_tick), int(rng_tick_inc), stream_ptr())
@@ -116,7 +149,7 @@ class DeviceSimpleSpreadVectorEnv:
         ids = np.arange(self.env_num) if id is None else np.atleast_1d(np.asarray(id))
         if len(ids) != self.env_num:
             raise ValueError("DeviceSimpleSpreadVectorEnv steps all envs together (synchronous vector env)")
-        act = torch.as_tensor(np.asarray(action).reshape(self.env_num, self.n_agent)).to(self.device, torch.int32)
+        act = host_actions(self, action)
         keep = self.auto_reset
         self.auto_reset = False  # the reference Collector resets finished envs itself (collector.py:971)
         try:

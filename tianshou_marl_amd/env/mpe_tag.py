@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from .._abi import call, ptr, stream_ptr, tsm_mpe_tag_cfg
+from .mpe import BOX_ACT_DIM, box_actions, host_actions
 from .spaces import Box, Discrete
 
 
@@ -25,7 +26,8 @@ class DeviceSimpleTagVectorEnv:
     is_async = False
 
     def __init__(self, n_env: int, num_good: int = 1, num_adversaries: int = 3, num_obstacles: int = 2,
-                 max_cycles: int = 25, device: str | torch.device = "cuda", seed: int = 0, auto_reset: bool = True) -> None:
+                 max_cycles: int = 25, device: str | torch.device = "cuda", seed: int = 0, auto_reset: bool = True,
+                 continuous_actions: bool = False) -> None:
         self.env_num = int(n_env)
         self.n_adv, self.n_good, self.n_obst = int(num_adversaries), int(num_good), int(num_obstacles)
         self.n_agent = self.n_adv + self.n_good
@@ -43,6 +45,10 @@ class DeviceSimpleTagVectorEnv:
             raise ValueError("simple_tag: unsupported sizes (at most 8 agents and 4 obstacles)")
         self.observation_space = Box(-np.inf, np.inf, (self.obs_dim,))
         self.action_space = [Discrete(self.n_act) for _ in range(self.env_num)]
+        self.continuous_actions = bool(continuous_actions)
+        if self.continuous_actions:  # as env/mpe.py, with each team's own accel
+            self.act_dim = BOX_ACT_DIM
+            self.action_space = [Box(0.0, 1.0, (BOX_ACT_DIM,)) for _ in range(self.env_num)]
         self._seed = int(seed)
         E, N, D, dev = self.env_num, self.n_agent, self.obs_dim, self.device
         f = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)  # noqa: E731
@@ -82,11 +88,15 @@ class DeviceSimpleTagVectorEnv:
         return self.obs_cur
 
     def step_device(self, act: torch.Tensor, rng_tick_inc: int = 0):
-        """One joint step; act i32 [n_env, n_agent].  Returns (obs_next, rew, terminated, truncated, done_env)."""
-        if act.dtype != torch.int32:
+        """One joint step; act i32 [n_env, n_agent] (continuous_actions: f32 [n_env, n_agent, 5]).  Returns (obs_next, rew,
+        terminated, truncated, done_env)."""
+        entry = "tsm_mpe_tag_step"
+        if self.continuous_actions:
+            act, entry = box_actions(act, self.env_num, self.n_agent), "tsm_mpe_tag_step_box"
+        elif act.dtype != torch.int32:
             raise ValueError("step_device: act must be int32")
         self._pp ^= 1
-        call("tsm_mpe_tag_step", C.byref(self._tag_cfg), self._seed, ptr(self.episode_ctr), ptr(act.contiguous()),
+        call(entry, C.byref(self._tag_cfg), self._seed, ptr(self.episode_ctr), ptr(act.contiguous()),
              ptr(self.agent_pos), ptr(self.agent_vel), ptr(self.landmark_pos), ptr(self.steps), ptr(self.obs_next),
              ptr(self.obs_cur), ptr(self.rew), ptr(self.terminated), ptr(self.truncated), ptr(self.done_env),
              int(self.auto_reset), ptr(self.rng_tick), int(rng_tick_inc), stream_ptr())
@@ -109,7 +119,7 @@ class DeviceSimpleTagVectorEnv:
         ids = np.arange(self.env_num) if id is None else np.atleast_1d(np.asarray(id))
         if len(ids) != self.env_num:
             raise ValueError("DeviceSimpleTagVectorEnv steps all envs together (synchronous vector env)")
-        act = torch.as_tensor(np.asarray(action).reshape(self.env_num, self.n_agent)).to(self.device, torch.int32)
+        act = host_actions(self, action)
         keep, self.auto_reset = self.auto_reset, False  # the reference Collector resets finished envs itself
         try:
             obs_next, rew, term, trunc, _ = self.step_device(act)

@@ -2409,7 +2409,8 @@ def gauss_sample(raw, seed: int, offset: int = 0, offset_dev=None, deterministic
     """Independent(Normal(mu, sigma), 1).sample() (deterministic: the mode) with its log-prob, the normals drawn inside the
     launch; raw and sigma_param as `_sac_raw` takes them.  -> (act f32 [B, Ad], the raw sample a buffer stores, logp f32 [B],
     env_act): env_act = the reference's map_action of act (bound_method None | "clip" | "tanh", then the affine map to
-    [low, high] f32 [Ad] when both are given), None unless want_env_act.  out = optional preallocated (act, logp)."""
+    [low, high] f32 [Ad] when both are given), None unless want_env_act.  out = optional preallocated (act, logp) or (act, logp,
+    env_act): a captured collect steps the env from the third, whose address must not change between replays."""
     raw, B, Ad, ld, sg, sg_ptr, ld_s = _gauss_raw("gauss_sample", raw, sigma_param)
     if bound_method not in _GAUSS_BOUND:
         raise ValueError(f"gauss_sample: bound_method must be None, 'clip' or 'tanh', got {bound_method!r}")
@@ -2420,10 +2421,14 @@ def gauss_sample(raw, seed: int, offset: int = 0, offset_dev=None, deterministic
         low, high = _chk(low, torch.float32, "low").reshape(-1), _chk(high, torch.float32, "high").reshape(-1)
         if low.numel() != Ad or high.numel() != Ad:
             raise ValueError(f"gauss_sample: low and high must have {Ad} entries")
-    act, logp = out if out is not None else (None, None)
+    if out is not None and len(out) not in (2, 3):
+        raise ValueError("gauss_sample: out must be (act, logp) or (act, logp, env_act)")
+    act, logp, env_act = (*out, None)[:3] if out is not None else (None, None, None)
+    if env_act is not None and not want_env_act:
+        raise ValueError("gauss_sample: out carries an env_act buffer, which needs want_env_act=True")
     act = _out("gauss_sample", act, (B, Ad), torch.float32, raw.device, "act", "numel")
     logp = _out("gauss_sample", logp, (B,), torch.float32, raw.device, "logp", "numel")
-    env_act = torch.empty(B, Ad, dtype=torch.float32, device=raw.device) if want_env_act else None
+    env_act = _out("gauss_sample", env_act, (B, Ad), torch.float32, raw.device, "env_act", "numel") if want_env_act else None
     call("tsm_gauss_sample", ptr(raw), ld, sg_ptr, ld_s, B, Ad, float(max_action), int(bool(unbounded)),
          *_philox("gauss_sample", seed, offset, offset_dev), int(bool(deterministic)), _GAUSS_BOUND[bound_method], ptr(low),
          ptr(high), ptr(act), ptr(logp), ptr(env_act), stream_ptr())
