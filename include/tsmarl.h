@@ -1801,6 +1801,37 @@ int tsm_vrb_gather_stacked(const void *state, int64_t buffer_num, int64_t sub_si
                            int32_t stack_num, void *out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * GRU cells for the recurrent net  (`Recurrent(cell="gru")`: fc1 -> nn.GRU(hidden, hidden, layer_num, batch_first) -> fc2, the
+ * agent net of the recurrent value-based multi-agent learners; csrc/gru.hip, csrc/dense.hip)
+ * The GRU layer: torch's layout, gate order r, z, n; weight_hh [3H][H].  H a multiple of 16 in [16, TSM_GRU_MAX_HIDDEN],
+ *   layer_num >= 1, L >= 1, B >= 1: anything else is TSM_ERR_INVALID from tsm_gru_check (needs no device) before any launch.
+ *   A workgroup carries TSM_GRU_ROWS_PER_BLOCK batch rows through all L steps: one launch per layer and direction.
+ * tsm_gru_forward replaces  nn.GRU's recurrence.  proj f32 [B][L][3H] = X W_ih^T + b_ih (tsm_dense_linear); bias (nullable)
+ *   [3H] = b_hh; h0 (nullable: zeros) and h_n (nullable) are [B] rows of H floats at row pitch ld_state (a layer's slice of a
+ *   [B][layers][H] state); h_n may be h0 itself (the acting step, L = 1, advances the state in place).
+ *   Per step: r = sigmoid(x_r + b_hr + h_{t-1} W_hr^T), z = sigmoid(x_z + b_hz + h_{t-1} W_hz^T), q = h_{t-1} W_hn^T + b_hn,
+ *   n = tanh(x_n + r q), h_t = (1 - z) n + z h_{t-1}.
+ *   out: h [B][L][H]; for the backward (each nullable) h_prev [B][L][H] = h_{t-1}, gates [B][L][3H] = r, z, n activated,
+ *   q [B][L][H].  sigmoid and tanh are finite for every finite input.
+ * tsm_gru_backward replaces  `loss.backward()` through it.  d_h [B][L][H] = the gradient arriving at every h_t from above; d_hn
+ *   (nullable) at h_L; gates, q, h_prev as saved.  With dh = d_h[t] + carried: da_n = dh (1 - z)(1 - n^2),
+ *   da_z = dh (h_{t-1} - n) z (1 - z), da_r = da_n q r (1 - r); carried = dh z + d_gates_h W_hh on f32 MFMA.
+ *   out, every element written: d_gates_x [B][L][3H] = {da_r, da_z, da_n} and d_gates_h [B][L][3H] = {da_r, da_z, da_n r};
+ *   (nullable) d_h0 at row pitch ld_state.  The weight gradients are then tsm_dense_wgrad(d_gates_x, X) -> weight_ih, bias_ih
+ *   and tsm_dense_wgrad(d_gates_h, h_prev) -> weight_hh, bias_hh, the gradient for the layer below
+ *   tsm_dense_dgrad(d_gates_x, W_ih).  No atomics: two runs give the same bits.
+ * The hidden rows of finished envs are zeroed by tsm_lstm_state_reset with the one array given as both h and c.
+ * ------------------------------------------------------------------------------------------- */
+#define TSM_GRU_MAX_HIDDEN 128
+#define TSM_GRU_ROWS_PER_BLOCK 16
+int tsm_gru_check(int32_t hidden, int32_t layer_num, int32_t seq_len);
+int tsm_gru_forward(const float *proj, const float *w_hh, const float *bias, const float *h0, int64_t ld_state, int64_t B,
+                    int32_t L, int32_t H, float *h, float *h_prev, float *gates, float *q, float *h_n, void *stream);
+int tsm_gru_backward(const float *d_h, const float *d_hn, const float *w_hh, const float *gates, const float *q,
+                     const float *h_prev, int64_t ld_state, int64_t B, int32_t L, int32_t H, float *d_gates_x, float *d_gates_h,
+                     float *d_h0, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * NPG and TRPO  (tianshou/algorithm/modelfree/npg.py, trpo.py; csrc/fisher.hip)
  * The Fisher-vector product of a categorical actor MLP without autograd.  Where the reference evaluates it (npg.py:162-166:
  * old_dist is the same forward as dist) the KL's gradient w.r.t. the logits is zero, so the Hessian of mean KL(old || new)

@@ -61,7 +61,7 @@ class DiscreteQLearningPolicy(nn.Module):
         super().__init__()
         # the reference's `Recurrent` (utils/net/common.py:372-458) stands where the plain Q-network does: DQN alone takes it
         self.recurrent = type(self) is DiscreteQLearningPolicy and isinstance(model, Recurrent)   # (not the distributional policies)
-        self._act_state: tuple | None = None   # (hidden, cell) [rows, layers, H] of the collector's rows, in HBM
+        self._act_state: tuple | None = None   # (hidden, cell) [rows, layers, H] of the collector's rows, in HBM; a GRU: (hidden,)
         if not (isinstance(model, self._model_cls) or self.recurrent):
             raise TypeError(f"DiscreteQLearningPolicy needs a {self._model_cls.__name__} Q-network: the update runs in HIP, "
                             f"there is no autograd fallback (got {type(model).__name__})")
@@ -139,9 +139,9 @@ class DiscreteQLearningPolicy(nn.Module):
         value per action (numpy i64), state)."""
         obs, mask = _obs_rows(batch.obs)
         if self.recurrent:   # obs [B, L, D] | [B, D]; state None (zeros) or Batch(hidden, cell) [B, layers, H], handed back
-            q, (hid, cell) = (self.model if model is None else model).forward(to_tensor(obs, self.device, torch.float32), state,
-                                                                              save=False)
-            logits, extra, state = q, {}, Batch(hidden=hid, cell=cell)
+            net = self.model if model is None else model   # (a GRU net: Batch(hidden) alone)
+            q, new = net.forward(to_tensor(obs, self.device, torch.float32), state, save=False)
+            logits, extra, state = q, {}, Batch(**dict(zip(net.state_names, new)))
         else:
             q, logits, extra = self._forward_values(to_tensor(obs, self.device, torch.float32), model)
         m = None if mask is None else to_tensor(np.asarray(mask, bool) if not isinstance(mask, torch.Tensor) else mask,
@@ -193,7 +193,7 @@ class DiscreteQLearningPolicy(nn.Module):
         same net (`Recurrent(..., storage=net.flat.data)` shares the parameters)."""
         if self._act_state is None:
             return
-        hid, cell = self._act_state
+        hid, cell = self._act_state[0], self._act_state[-1]   # a GRU keeps `hidden` alone: the one array stands in both places
         if done is None:
             hid.zero_()
             cell.zero_()

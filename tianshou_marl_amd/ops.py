@@ -1433,6 +1433,70 @@ def lstm_state_reset(h, c, done, rows_per_env: int = 1) -> None:
         call("tsm_lstm_state_reset", ptr(h), ptr(c), ptr(done), E, R, h[0].numel(), stream_ptr())
 
 
+def gru_check(hidden: int, layer_num: int = 1, seq_len: int = 1) -> None:
+    """The bounds of the GRU kernels (include/tsmarl.h): hidden a multiple of 16 in [16, 128], layer_num >= 1, seq_len >= 1;
+    ValueError naming the limit."""
+    call("tsm_gru_check", int(hidden), int(layer_num), int(seq_len))
+
+
+def gru_forward(proj, w_hh, bias=None, h0=None, h_n=None, save: bool = True):
+    """One GRU layer through all L steps in one launch (include/tsmarl.h: tsm_gru_forward).  proj [B, L, 3H] = the input
+    projection with b_ih; bias [3H] = b_hh; h0 [B, H] or None (zeros); h_n [B, H] output, fresh when None, and allowed to BE
+    h0 (the acting step).  State operands may be strided rows of a [B, layers, H] tensor.
+    -> dict(h [B, L, H], h_n, and with `save`: h_prev [B, L, H], gates [B, L, 3H] (r, z, n), q [B, L, H])."""
+    _dev_only("gru_forward", proj, w_hh, bias)
+    if proj.dim() != 3 or proj.shape[2] % 3:
+        raise ValueError(f"gru_forward: proj must be [B, L, 3H], got {list(proj.shape)}")
+    B, L, H = proj.shape[0], proj.shape[1], proj.shape[2] // 3
+    gru_check(H, 1, L)
+    if B < 1:
+        raise ValueError("gru_forward: empty batch")
+    proj, w_hh = _f32("gru_forward", "proj", proj, (B, L, 3 * H)), _f32("gru_forward", "w_hh", w_hh, (3 * H, H))
+    bias = _f32("gru_forward", "bias", bias, (3 * H,))
+    dev = proj.device
+    if h_n is None:
+        h_n = torch.empty(B, H, dtype=torch.float32, device=dev)
+    (h0, l0), (h_n, l1) = _lstm_state("gru_forward", "h0", h0, B, H), _lstm_state("gru_forward", "h_n", h_n, B, H)
+    ld = _one_pitch("gru_forward", (l0, l1))
+    out = dict(h=torch.empty(B, L, H, dtype=torch.float32, device=dev), h_n=h_n)
+    if save:
+        out.update(h_prev=torch.empty(B, L, H, dtype=torch.float32, device=dev),
+                   gates=torch.empty(B, L, 3 * H, dtype=torch.float32, device=dev),
+                   q=torch.empty(B, L, H, dtype=torch.float32, device=dev))
+    dp = lambda t: None if t is None else t.data_ptr()  # noqa: E731  (strided rows: `ptr` wants contiguous tensors)
+    call("tsm_gru_forward", ptr(proj), ptr(w_hh), ptr(bias), dp(h0), ld, B, L, H, ptr(out["h"]), ptr(out.get("h_prev")),
+         ptr(out.get("gates")), ptr(out.get("q")), dp(h_n), stream_ptr())
+    return out
+
+
+def gru_backward(d_h, w_hh, gates, q, h_prev, d_hn=None, want_state_grad: bool = False):
+    """The backward through time of `gru_forward` in one launch: d_h [B, L, H] arriving at every step from above, d_hn [B, H]
+    or None at the final state; gates, q, h_prev as saved.
+    -> dict(d_gates_x [B, L, 3H] for weight_ih / bias_ih and the layer below, d_gates_h [B, L, 3H] for weight_hh / bias_hh,
+    and with `want_state_grad`: d_h0 [B, H])."""
+    _dev_only("gru_backward", d_h, w_hh, gates, q, h_prev)
+    if d_h.dim() != 3:
+        raise ValueError(f"gru_backward: d_h must be [B, L, H], got {list(d_h.shape)}")
+    B, L, H = d_h.shape
+    gru_check(H, 1, L)
+    if B < 1:
+        raise ValueError("gru_backward: empty batch")
+    d_h, w_hh = _f32("gru_backward", "d_h", d_h, (B, L, H)), _f32("gru_backward", "w_hh", w_hh, (3 * H, H))
+    gates, q = _f32("gru_backward", "gates", gates, (B, L, 3 * H)), _f32("gru_backward", "q", q, (B, L, H))
+    h_prev = _f32("gru_backward", "h_prev", h_prev, (B, L, H))
+    dev = d_h.device
+    out = dict(d_gates_x=torch.empty(B, L, 3 * H, dtype=torch.float32, device=dev),
+               d_gates_h=torch.empty(B, L, 3 * H, dtype=torch.float32, device=dev))
+    if want_state_grad:
+        out.update(d_h0=torch.empty(B, H, dtype=torch.float32, device=dev))
+    (d_hn, l0), (d_h0, l1) = _lstm_state("gru_backward", "d_hn", d_hn, B, H), _lstm_state("gru_backward", "d_h0", out.get("d_h0"), B, H)
+    ld = _one_pitch("gru_backward", (l0, l1))
+    dp = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    call("tsm_gru_backward", ptr(d_h), dp(d_hn), ptr(w_hh), ptr(gates), ptr(q), ptr(h_prev), ld, B, L, H, ptr(out["d_gates_x"]),
+         ptr(out["d_gates_h"]), dp(d_h0), stream_ptr())
+    return out
+
+
 def nstep_return(index: "VrbState", term_store, rew_store, indices, n_step: int, gamma: float, rew_col: int = 0,
                  term_col: int = 0):
     """The n-step walk of Algorithm.compute_nstep_return (algorithm_base.py:773-806, 1195-1211) for flat `indices` i64 [I]

@@ -7,6 +7,7 @@ forward + autograd backward -- the only yardstick there is: the reference has no
     timeout -k 10 120 python tools/bench_recurrent.py torch   [--rows 4096] [--steps 16]
     timeout -k 10 120 python tools/bench_recurrent.py update  [--rows 4096] [--steps 16]   # DQN.update on Recurrent
     timeout -k 10 120 python tools/bench_recurrent.py kernels [--rows 4096] [--steps 16]   # the two kernels of csrc/lstm.hip alone
+    ... --cell gru: the same four with `Recurrent(cell="gru")`, torch's `nn.GRU` and the two kernels of csrc/gru.hip
 
 Every GPU step runs under a time limit of its own, as above.  The inputs are fixed normal draws, far from zero-filled, so
 data-dependent power states see ordinary operands.  `update`: a full `DQN.update(buffer, B)` on `Recurrent` (double-Q, lagged
@@ -27,6 +28,7 @@ from tianshou_marl_amd import ops  # noqa: E402
 from tianshou_marl_amd.utils.net import Recurrent  # noqa: E402
 
 D, H, A, LAYERS, DEV = 18, 128, 5, 1, "cuda"
+CELL = "lstm"   # --cell
 
 
 def timed(fn, warmup: int, iters: int) -> float:
@@ -48,7 +50,7 @@ def inputs(B: int, L: int):
 
 
 def hip_cases(B: int, L: int) -> dict:
-    net = Recurrent(layer_num=LAYERS, state_shape=D, action_shape=A, hidden_layer_size=H, device=DEV, seed=0)
+    net = Recurrent(layer_num=LAYERS, state_shape=D, action_shape=A, hidden_layer_size=H, device=DEV, seed=0, cell=CELL)
     obs, d_out = inputs(B, L)
 
     def both():
@@ -59,10 +61,10 @@ def hip_cases(B: int, L: int) -> dict:
 
 
 def torch_cases(B: int, L: int) -> dict:
-    net = Recurrent(layer_num=LAYERS, state_shape=D, action_shape=A, hidden_layer_size=H, device=DEV, seed=0)
+    net = Recurrent(layer_num=LAYERS, state_shape=D, action_shape=A, hidden_layer_size=H, device=DEV, seed=0, cell=CELL)
     sd = net.to_reference_state_dict()
     fc1, fc2 = torch.nn.Linear(D, H).to(DEV), torch.nn.Linear(H, A).to(DEV)
-    lstm = torch.nn.LSTM(H, H, LAYERS, batch_first=True).to(DEV)
+    lstm = (torch.nn.GRU if CELL == "gru" else torch.nn.LSTM)(H, H, LAYERS, batch_first=True).to(DEV)
     lstm.load_state_dict({k[3:]: v for k, v in sd.items() if k.startswith("nn.")})
     fc1.load_state_dict({"weight": sd["fc1.weight"], "bias": sd["fc1.bias"]})
     fc2.load_state_dict({"weight": sd["fc2.weight"], "bias": sd["fc2.bias"]})
@@ -86,9 +88,14 @@ def torch_cases(B: int, L: int) -> dict:
 
 def kernel_cases(B: int, L: int) -> dict:
     g = torch.Generator(device=DEV).manual_seed(0)
-    proj = torch.randn(B, L, 4 * H, device=DEV, generator=g)
-    w_hh = torch.randn(4 * H, H, device=DEV, generator=g) / H ** 0.5
+    G = 3 if CELL == "gru" else 4
+    proj = torch.randn(B, L, G * H, device=DEV, generator=g)
+    w_hh = torch.randn(G * H, H, device=DEV, generator=g) / H ** 0.5
     d_h = torch.randn(B, L, H, device=DEV, generator=g)
+    if CELL == "gru":
+        fw = ops.gru_forward(proj, w_hh)
+        return {"tsm_gru_forward": lambda: ops.gru_forward(proj, w_hh),
+                "tsm_gru_backward": lambda: ops.gru_backward(d_h, w_hh, fw["gates"], fw["q"], fw["h_prev"])}
     fw = ops.lstm_forward(proj, w_hh)
     return {"tsm_lstm_forward": lambda: ops.lstm_forward(proj, w_hh),
             "tsm_lstm_backward": lambda: ops.lstm_backward(d_h, w_hh, fw["gates"], fw["c"])}
@@ -109,7 +116,7 @@ def update_cases(B: int, L: int) -> dict:
         buf.add_device(torch.randn(E, N, D, device=DEV, generator=g), torch.randint(0, A, (E, N), device=DEV, dtype=torch.int32, generator=g),
                        torch.randn(E, N, device=DEV, generator=g), (torch.rand(E, 1, device=DEV, generator=g) < 0.04).expand(E, N).to(torch.uint8).contiguous(),
                        torch.zeros(E, N, dtype=torch.uint8, device=DEV), torch.randn(E, N, D, device=DEV, generator=g))
-    net = Recurrent(layer_num=LAYERS, state_shape=D, action_shape=A, hidden_layer_size=H, device=DEV, seed=0)
+    net = Recurrent(layer_num=LAYERS, state_shape=D, action_shape=A, hidden_layer_size=H, device=DEV, seed=0, cell=CELL)
     algo = DQN(policy=DiscreteQLearningPolicy(model=net, action_space=Discrete()), optim=AdamOptimizerFactory(lr=1e-4),
                n_step_return_horizon=3, target_update_freq=100)
     algo.is_within_training_step = True
@@ -123,11 +130,14 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--cell", choices=["lstm", "gru"], default="lstm")
     args = ap.parse_args()
+    global CELL
+    CELL = args.cell
     cases = {"hip": hip_cases, "torch": torch_cases, "kernels": kernel_cases, "update": update_cases}[args.mode](args.rows, args.steps)
     for name, fn in cases.items():
         ms = timed(fn, args.warmup, args.iters)
-        print(f"{args.mode} hidden {H} layers {LAYERS} L {args.steps} B {args.rows}: {name}: {ms:.4f} ms by device events "
+        print(f"{args.mode} {CELL} hidden {H} layers {LAYERS} L {args.steps} B {args.rows}: {name}: {ms:.4f} ms by device events "
               f"({args.iters} calls after {args.warmup})", flush=True)
 
 
