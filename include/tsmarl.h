@@ -546,6 +546,25 @@ int tsm_rollout_prep_extra(int64_t tiles, int32_t n_cu, int64_t perm_n, int32_t 
  * tsm_vrb_add step by step.  Up to eight agents (obs_dim <= 48; TSM_ERR_INVALID above: hosts keep the three-launch loop). */
 int tsm_rollout_spread_actor(const tsm_rollout_desc *desc, void *stream);
 
+/* The same collect loop under Box actions: a Gaussian policy (tsm_gauss_sample's distribution over a 64-64 actor, with or without
+ * a 64-64 critic on the agent's own observation) on simple_spread's continuous form, n_steps vector steps in ONE launch
+ * (csrc/rollout_gauss.hip).  Replaces, per step, tsm_mlp_forward (actor; critic when run_critic) -> tsm_gauss_sample ->
+ * tsm_mpe_spread_step_box -> tsm_vrb_add, bit for bit: the stored action is the raw f32 sample, the env is stepped with its
+ * map_action (bound_method, then low / high).
+ * desc: tsm_rollout_spread's descriptor as it is, with  params = the net's flat vector in torch order: actor w0 b0 w1 b1 w2 b2 (w2:
+ *   act_dim rows, 2 act_dim with a conditioned sigma: [mu_raw | sigma_raw]), then sigma_param[act_dim] when sigma is
+ *   state-independent, then the critic w0 b0 w1 b1 w2 b2 (read only when run_critic);  hidden = 64;  n_act = act_dim = 5;
+ *   obs_dim = 6 n_agent <= 48;  mode 1 sample | 2 the mode mu (nothing is drawn);  param_image, act_store (NULL) and vnext_store
+ *   are not used.  The head's settings come beside it, as tsm_gauss_sample takes them.
+ * The Philox counter of step t is  offset + *offset_dev + t * n_env * n_agent * act_dim,  the element index
+ *   (env * n_agent + agent) * act_dim + k  under tsm_gauss_sample's key: offset_inc is n_steps * n_env * n_agent * act_dim.
+ * act_store f32 [sub_size][n_env][n_agent][act_dim].  bound_method 0 none | 1 clip | 2 tanh; low, high f32 [act_dim], nullable
+ * together (no scaling).  activation: 1 relu | 2 tanh, of both nets' hidden layers.  run_critic 0: the critic is compiled out and
+ * vs_store is not written (a centralized critic: the update computes V in batched passes). */
+int tsm_rollout_spread_gauss(const tsm_rollout_desc *desc_host, float *act_store, int32_t act_dim, int32_t conditioned_sigma,
+                             int32_t unbounded, double max_action, int32_t bound_method, const float *low, const float *high,
+                             int32_t activation, int32_t run_critic, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Batched simple_tag (predator-prey, two teams)  [(f)1, BASELINE configs[4]]
  * Same role and call shape as tsm_mpe_spread_*: the vector-env step the reference performs per env through

@@ -1,9 +1,12 @@
 #!/usr/bin/env python
-"""Collect time under Box actions: the per-step device loop (eager launches, captured graph) against the host loop.
+"""Collect time under Box actions: the persistent Gaussian rollout and the per-step device loop (eager launches, captured graph)
+against the host loop.
 
 Job: Collector.collect(n_step = 25 * E) on continuous simple_spread, N = 3, E = 1024, a 64-64 Gaussian GenericPPO sampling within
-a training step.  Three ways to run it:
-  device-eager     env.step_device fed from the policy's env_act in HBM, use_graph=False
+a training step.  Four ways to run it:
+  device-fused     the whole collect in one launch of the persistent Gaussian rollout (csrc/rollout_gauss.hip; the default)
+  device-eager     the per-step loop (fused_rollout=False, as the two modes below): env.step_device fed from the policy's env_act
+                   in HBM, use_graph=False
   device-captured  the same loop replayed as one captured graph (use_graph=True; engaged from the second collect)
   host-loop        what a Gaussian policy had before the Box step kernels: the Collector's host loop over the env's numpy
                    `step()` -- per vector step one D2H copy of the actions, one H2D copy into the env, D2H of its results and
@@ -53,8 +56,10 @@ def make(mode: str, E: int, N: int, T: int):
     algo = GenericPPO(net=net, dispatch="pooled", seed=11, action_scaling=True, action_bound_method="clip",
                       action_space=env.action_space[0])
     buf = VectorReplayBuffer(E * T, E, act_dim=env.act_dim, device="cuda")
-    col = Collector(algo, HostView(env) if mode == "host-loop" else env, buf, use_graph=mode == "device-captured")
+    col = Collector(algo, HostView(env) if mode == "host-loop" else env, buf, use_graph=mode == "device-captured",
+                    fused_rollout=mode == "device-fused")
     col.reset()
+    assert col._can_fuse() == (mode == "device-fused")
     return algo, buf, col
 
 
@@ -81,7 +86,7 @@ def main() -> None:
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_box_collect.py measures on the GPU; there is none here")
-    modes = ("device-eager", "device-captured", "host-loop")
+    modes = ("device-fused", "device-eager", "device-captured", "host-loop")
     n_step = a.steps * a.envs
     jobs = {m: make(m, a.envs, a.agents, a.steps) for m in modes}
     for m in modes:
