@@ -1995,6 +1995,42 @@ int tsm_mlp_ln_input_grad(const tsm_mlp_desc *desc, const float *params, const f
                           const float *saved, const float *d_out, float *d_acts, int32_t col0, int32_t n_col, float *dx,
                           int64_t ldx, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * One-launch Gaussian PPO gradient step for 64-64 nets  (ppo.py:182-212 for a Box action space; csrc/ppo_gauss.hip)
+ * Replaces, for one minibatch of M rows, the chain tsm_gather_rows -> tsm_mlp_forward (actor, critic) -> tsm_gauss_ppo_head ->
+ * tsm_ppo_loss_fwd_bwd (loss_kind 2) -> tsm_mlp_backward (actor, critic) -> tsm_gauss_sigma_fold -> tsm_u64_add: forward, both
+ * loss heads and the backward of BOTH nets of a GaussianActorCritic, activations on-chip.  Adam and tsm_ppo_finalize_many follow.
+ * params: the flat vector  actor w0 [64][D] b0 w1 [64][64] b1 w2 [W][64] b2 [W], sigma_param [act_dim] when conditioned_sigma
+ *   == 0, then critic w0 [64][D] b0 w1 b1 w2 [1][64] b2 [1];  W = act_dim, or 2 act_dim with a conditioned sigma (mu | sigma).
+ * Limits (tsm_ppo_update_gauss_check, no device needed; TSM_ERR_INVALID naming the limit, before any launch): hidden == 64 for
+ *   both hidden layers, 1 <= obs_dim <= 64, 1 <= W <= 16, act_kind 1 (relu) or 2 (tanh).  The critic sees the lane's own
+ *   observation.  max_action, unbounded: as tsm_gauss_sample.
+ * Rows: obs [n][obs_dim], act [n][act_dim], logp_old, adv, returns, v_s_old (nullable without value_clip) [n] are full-batch
+ *   arrays read at perm[i] (perm nullable: first_row + i), i < M; no other row is read.  adv_stats {mean, std} in device memory
+ *   (nullable without adv_norm).  cfg: eps_clip, dual_clip, ent_coef, adv_norm, loss_kind 0 | 1 for the policy terms
+ *   (tsm_gauss_ppo_head's arithmetic, f64 from the f32 raw outputs) and value_clip, vf_coef for the value term
+ *   (tsm_ppo_loss_fwd_bwd's with loss_kind 2, f32); value_group is not read.
+ * Launch: n_blocks x 2 workgroups, (b, 0) the actor and (b, 1) the critic of the 16-row tiles b, b + n_blocks, ...;
+ *   tsm_ppo_update_gauss_grid: *n_blocks_out for M rows (any 1 <= n_blocks <= ceil(M / 16) is accepted).
+ * grad_slabs_out [n_blocks][slab_stride], slab_stride >= the parameter count: workgroup (b, 0) writes every actor column of slab
+ *   b (sigma_param's included: its rows' sum of d loss / d sigma_param, f64, rounded once), workgroup (b, 1) every critic column.
+ *   No column is written as filler and none is written twice; columns at and past the parameter count are not touched.  Summed
+ *   over b the slabs are d loss / d params (tsm_adam_step's input).
+ * loss_partial_out f64 [2 n_blocks][4], tsm_ppo_finalize_many's layout: row b = {sum obj, 0, sum entropy, 0} of the actor
+ *   workgroup b, row n_blocks + b = {0, sum value loss, 0, 0} of the critic's; rows added tile after tile in row order.
+ * opt_step_dev (nullable, device i64[1]): advanced by one per call, as tsm_ppo_update_fused does.
+ * The raw outputs and V carry tsm_mlp_forward's bits (its k order per output element).  No atomics, no host read, no allocation:
+ * two runs give the same bits and the launch can be captured.
+ * ------------------------------------------------------------------------------------------- */
+int tsm_ppo_update_gauss_check(int32_t obs_dim, int32_t hidden, int32_t act_dim, int32_t conditioned_sigma, int32_t act_kind);
+int tsm_ppo_update_gauss_grid(int64_t M, int32_t *n_blocks_out);
+int tsm_ppo_update_gauss(const float *params, int32_t obs_dim, int32_t hidden, int32_t act_dim, int32_t conditioned_sigma,
+                         int32_t act_kind, double max_action, int32_t unbounded, const float *obs, const float *act,
+                         const float *logp_old, const float *adv, const float *returns, const float *v_s_old,
+                         const int64_t *perm, int64_t first_row, int64_t M, const float *adv_stats, const tsm_ppo_cfg *cfg_host,
+                         int32_t n_blocks, float *grad_slabs_out, int64_t slab_stride, double *loss_partial_out,
+                         int64_t *opt_step_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

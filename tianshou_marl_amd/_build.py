@@ -25,7 +25,7 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=h
 # the same and it spills in neither form (tools/resource_usage.py), so today the flag is a guard against a later compiler packing
 # the f32 chains of the CG kernels, not a work-around.  New sources go on this list; the older ones keep the flags their recorded
 # results were taken with.  (The host pass prints "not a recognized feature" for it: the feature is the device target's.)
-NO_PACKED_F32 = {"fisher.hip", "gauss.hip", "layernorm.hip", "gru.hip", "rollout_gauss.hip"}
+NO_PACKED_F32 = {"fisher.hip", "gauss.hip", "layernorm.hip", "gru.hip", "rollout_gauss.hip", "ppo_gauss.hip"}
 
 
 def _newest_header() -> float:

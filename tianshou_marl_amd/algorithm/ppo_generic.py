@@ -80,6 +80,9 @@ class GenericPPO(PPO):
                                                 self.ent_coef, loss_kind=2, value_group=vg) for vg in (1, self.n_agent)}
         self.fused_actor = bool(fused_actor) and not gaussian and ops.ppo_actor_rows_supported(net.obs_dim, net.actor.dims[1:-1], net.n_act,
                                                                               net.actor.act)
+        # a Gaussian policy over 64-64 nets with a per-lane critic: the whole gradient step up to Adam in one launch
+        # (csrc/ppo_gauss.hip); `fused_actor` / `fused_critic` stay the categorical row kernels' switches
+        self.fused_gauss = bool(fused_actor) and gaussian and critic_input == "local" and self._gauss_step_supported()
         # ... and the critic in its own single launch when it is in_dim -> 128 -> 128 -> 1 (row minibatches or a local
         # critic: the samples of a row are adjacent lanes)
         n_val = self.n_agent if critic_input == "global" else 1
@@ -181,14 +184,55 @@ class GenericPPO(PPO):
         """logp of the stored actions under the current parameters (ppo.py:157-161), when the rollout's are stale."""
         return ops.gauss_logp_entropy(FlatMLP.forward(self.net.actor, obs, save=False), act, **self._gauss_kw())[0]
 
+    def _gauss_step_supported(self) -> bool:
+        """Does the one-launch Gaussian step (csrc/ppo_gauss.hip) cover these nets?  obs -> 64 -> 64 -> (Ad | 2 Ad) <= 16 and
+        obs -> 64 -> 64 -> 1 on the same observation, relu or tanh, no LayerNorm."""
+        net, actor, critic = self.net, self.net.actor, self.net.critic
+        if actor.norm or critic.norm or critic.act != actor.act or critic.dims[1:] != [*actor.dims[1:-1], 1]:
+            return False
+        try:
+            ops.ppo_update_gauss_check(net.obs_dim, actor.dims[1:-1], net.act_dim, actor.conditioned_sigma, actor.act)
+        except ValueError:
+            return False
+        return net.critic_obs_dim == net.obs_dim
+
+    def _grad_step_gauss_fused(self, pb: dict, idx: torch.Tensor, adv_stats, step_dev):
+        """The Gaussian gradient step in three launches: `ops.ppo_update_gauss` (rows read through `idx`, both nets forward,
+        both heads, both backwards, the optimizer's step count), Adam over its slabs, the loss statistics."""
+        net, actor, dev = self.net, self.net.actor, self.device
+        M, n_total = idx.numel(), net.flat.numel()
+        w = self._ws.get(("gauss_fused", M))
+        if w is None:   # (made by the eager first update of a shape: a captured one finds them)
+            nb = ops.ppo_update_gauss_grid(M)
+            w = self._ws[("gauss_fused", M)] = dict(
+                n_blocks=nb, partial=torch.zeros(2 * nb * 4, dtype=torch.float64, device=dev),
+                nb=torch.tensor([2 * nb], dtype=torch.int32, device=dev), M=torch.tensor([M], dtype=torch.int64, device=dev),
+                slabs=torch.empty(nb, n_total, dtype=torch.float32, device=dev))
+        ops.ppo_update_gauss(net.flat.data, pb["obs"], pb["act"], pb["logp_old"], pb["adv"], pb["ret"], self._cfg,
+                             hidden_sizes=actor.dims[1:-1], act_fn=actor.act, conditioned_sigma=actor.conditioned_sigma,
+                             max_action=actor.max_action, unbounded=actor.unbounded, adv_stats=adv_stats,
+                             v_s_old=pb["v_s"] if self.value_clip else None, perm=idx, M=M, n_blocks=w["n_blocks"],
+                             slabs=w["slabs"], partial=w["partial"], opt_step_dev=step_dev)
+        if step_dev is None:
+            self.opt_step += 1
+        ops.adam_step(net.flat.data, w["slabs"], self.exp_avg, self.exp_avg_sq, self.opt_step, lr=self.lr, lr_dev=self._lr_dev,
+                      betas=self.betas, eps=self.adam_eps, weight_decay=self.weight_decay, max_grad_norm=self.max_grad_norm,
+                      work=self.optim.work, step_dev=step_dev)
+        scal = torch.empty(1, 4, dtype=torch.float32, device=dev)
+        ops.ppo_finalize_many(w["partial"], 2 * w["n_blocks"] * 4, w["nb"], w["M"], self._cfg, scal)
+        return scal[0]
+
     def _grad_step_gauss(self, pb: dict, idx: torch.Tensor, adv_stats, step_dev, rows):
-        """`_grad_step_steps` for a Gaussian policy, in the same non-fused shape: both forwards, the policy head
-        (`ops.gauss_ppo_head`) with the value term beside it (`ops.ppo_value_loss`), both backwards into the joint slabs, the
-        fold of the head's sigma partials into `sigma_param`'s slab columns, clip + Adam.  -> the step's 4 scalars."""
+        """`_grad_step_steps` for a Gaussian policy.  `fused_gauss`: `_grad_step_gauss_fused`.  Else the same non-fused shape:
+        both forwards, the policy head (`ops.gauss_ppo_head`) with the value term beside it (`ops.ppo_value_loss`), both
+        backwards into the joint slabs, the fold of the head's sigma partials into `sigma_param`'s slab columns, clip + Adam.
+        -> the step's 4 scalars."""
         net, actor = self.net, self.net.actor
         if self._grad_sync is not None:
             raise NotImplementedError("data-parallel replicas of a Gaussian policy: the flat-gradient all-reduce of "
                                       "`_grad_step_steps` is not wired for GaussianActorCritic")
+        if self.fused_gauss and rows is None and pb["joint"] is None:
+            return self._grad_step_gauss_fused(pb, idx, adv_stats, step_dev)
         if rows is not None:
             cx, vg = ops.gather_rows(pb["joint"], rows), pb["n_agent"]
             x = cx.view(-1, net.obs_dim)

@@ -2566,6 +2566,79 @@ def gauss_sigma_fold(col_partial, n_blocks: int, slabs):
     return slabs
 
 
+# ---- the one-launch Gaussian PPO gradient step for 64-64 nets (csrc/ppo_gauss.hip) ----
+_GAUSS_ACT_KIND = {"relu": 1, "tanh": 2}
+
+
+def ppo_update_gauss_check(obs_dim: int, hidden_sizes, act_dim: int, conditioned_sigma: bool, act: str = "relu") -> None:
+    """The limits of `ppo_update_gauss` (include/tsmarl.h): two equal hidden layers of 64, obs_dim <= 64, an actor output of at
+    most 16 columns, relu or tanh.  ValueError naming the limit; needs no device."""
+    hs = [int(h) for h in hidden_sizes]
+    if len(hs) != 2 or hs[0] != hs[1]:
+        raise ValueError(f"ppo_update_gauss: the nets must have two equal hidden layers of 64, got {hs}")
+    call("tsm_ppo_update_gauss_check", int(obs_dim), hs[0], int(act_dim), int(bool(conditioned_sigma)), _GAUSS_ACT_KIND.get(act, 0))
+
+
+def ppo_update_gauss_grid(M: int) -> int:
+    """Slabs (workgroup pairs) of `ppo_update_gauss` on M rows; it writes that many slabs and twice as many rows of loss partials."""
+    n = C.c_int32(0)
+    call("tsm_ppo_update_gauss_grid", int(M), C.byref(n))
+    return n.value
+
+
+def ppo_update_gauss(params, obs, act, logp_old, adv, returns, cfg: tsm_ppo_cfg, hidden_sizes=(64, 64), act_fn: str = "relu",
+                     conditioned_sigma: bool = False, max_action: float = 1.0, unbounded: bool = False, adv_stats=None,
+                     v_s_old=None, perm=None, first_row: int = 0, M=None, n_blocks=None, slabs=None, slab_stride=None,
+                     partial=None, opt_step_dev=None):
+    """One PPO gradient step of a Gaussian policy up to the gradients, in one launch: params = `GaussianActorCritic`'s flat vector
+    (actor, sigma_param unless conditioned_sigma, critic); obs [n, D], act [n, Ad], logp_old, adv, returns, v_s_old [n]:
+    full-batch arrays read at perm (None: first_row + i).  cfg: the policy's (loss_kind 0 | 1); its value_clip / vf_coef shape the
+    value term.  -> (slabs f32 [n_blocks, slab_stride], whose sum over the slabs is d loss / d params in the columns below
+    params.numel(), partial f64 [2 n_blocks * 4] for `ppo_finalize_many`)."""
+    name = "ppo_update_gauss"
+    _dev_only(name, params, obs, act, logp_old, adv, returns, adv_stats, v_s_old, perm, slabs, partial, opt_step_dev)
+    obs = _chk(obs, torch.float32, "obs")
+    if obs.dim() != 2 or act.dim() != 2 or act.shape[0] != obs.shape[0]:
+        raise ValueError(f"{name}: obs must be [n, D] and act [n, Ad], got {list(obs.shape)} and {list(act.shape)}")
+    n, D, Ad = obs.shape[0], obs.shape[1], act.shape[1]
+    ppo_update_gauss_check(D, hidden_sizes, Ad, conditioned_sigma, act_fn)
+    if cfg.loss_kind not in (0, 1):
+        raise ValueError(f"{name} needs a cfg with loss_kind 0 (PPO clip) or 1 (policy gradient)")
+    ow = Ad * (2 if conditioned_sigma else 1)
+    P = _mlp3_param_count(D, 64, ow) + (0 if conditioned_sigma else Ad) + _mlp3_param_count(D, 64, 1)
+    if params.numel() != P:
+        raise ValueError(f"{name}: params holds {params.numel()} floats, the nets of obs_dim {D} and act_dim {Ad} have {P}")
+    M, perm = _rows_ids(name, "perm", perm, "M", M, first_row, n)
+    if M < 1 or (perm is None and not 0 <= first_row <= n - M):
+        raise ValueError(f"{name}: rows [{first_row}, {first_row + M}) leave the batch of {n}")
+    rows = {"adv": adv, "returns": returns}
+    if cfg.loss_kind == 0:
+        rows["logp_old"] = logp_old
+    if cfg.value_clip:
+        rows["v_s_old"] = v_s_old
+    for what, t in rows.items():
+        if t is None or t.numel() != n:
+            raise ValueError(f"{name}: {what} must have the {n} entries of obs")
+        rows[what] = _chk(t, torch.float32, what).reshape(-1)
+    if cfg.adv_norm and (adv_stats is None or adv_stats.numel() < 2):
+        raise ValueError(f"{name}: adv_norm needs adv_stats {{mean, std}}")
+    tiles = -(-M // 16)
+    if n_blocks is None:
+        n_blocks = ppo_update_gauss_grid(M)
+    if not 1 <= n_blocks <= tiles:
+        raise ValueError(f"{name}: n_blocks {n_blocks} outside [1, {tiles}]")
+    n_blocks, slabs, pitch = _slab_dest(name, slabs, n_blocks, M, P if slab_stride is None else slab_stride, P, obs.device)
+    partial = _out(name, partial, (2 * n_blocks * 4,), torch.float64, obs.device, "partial", "min")
+    if opt_step_dev is not None:
+        _chk(opt_step_dev, torch.int64, "opt_step_dev")
+    call("tsm_ppo_update_gauss", ptr(_chk(params, torch.float32, "params")), D, 64, Ad, int(bool(conditioned_sigma)),
+         _GAUSS_ACT_KIND[act_fn], float(max_action), int(bool(unbounded)), ptr(obs), ptr(_chk(act, torch.float32, "act")),
+         ptr(rows.get("logp_old")), ptr(rows["adv"]), ptr(rows["returns"]), ptr(rows.get("v_s_old")), ptr(perm), int(first_row), M,
+         ptr(None if adv_stats is None else _chk(adv_stats, torch.float32, "adv_stats")), C.byref(cfg), n_blocks, ptr(slabs), pitch,
+         ptr(partial), ptr(opt_step_dev), stream_ptr())
+    return slabs, partial
+
+
 # --------------------------------------------------------------------------------------------
 # Offline continuous learners: CQL / Cal-QL and TD3+BC (imitation/cql.py, td3_bc.py; csrc/cql.hip)
 # --------------------------------------------------------------------------------------------
